@@ -8,7 +8,9 @@ B=256 per GPU, L=200, P=40, H=64, 2 layers, 2 heads, inner 256, V=3709, dropout 
         bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0.  `value` = masked positions (slots with masked_lm_ids != 0) consumed per second by the
-whole job, inputs resident in HBM.
+whole job, inputs resident in HBM; `ms_per_step` = the time of one step in a single timed region of exactly --steps steps.
+--dump-outputs DIR writes what the last timed step computed (bench.py:dump_outputs); inputs, weights and dropout streams are
+seeded, so two runs with the same arguments start from identical inputs.
 
 `roofline`: after the timed region a few more steps run under the library's launch timer (b4r_timing_begin / _end: a hipEvent on
 the launch stream behind every kernel of the step).  The kernel with the largest time per step IS the roofline kernel -- it is
@@ -241,6 +243,34 @@ def measure_step_breakdown(eng, lib, hp, prepared, nb, n_steps=10):
     return rows
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+STATE_FIELDS = ("loss_sum", "valid_count", "correct_masked", "correct_all", "slots_all", "grad_sqnorm", "grad_norm", "lr")
+
+
+def dump_outputs(out_dir, eng, st):
+    """--dump-outputs: what a caller of the train step has after its last step, one <out_dir>/<name>.npy per array -- the step's
+    loss and the device state's sums (float64 scalars: loss, state.<field>), every weight after the update and the AdamW moments
+    in the weights' Keras shapes (float32: weights.<variable name, '/' -> '.'>, adam_m.<...>, adam_v.<...>).  Above
+    DUMP_BUDGET_BYTES in all, every larger array is cut to a fixed, seeded sample of its elements (flattened, the same positions
+    on every run: <name>.sample)."""
+    arrays = {"loss": np.float64(st["loss_sum"] / max(st["valid_count"], 1.0))}
+    for k in STATE_FIELDS:
+        arrays["state." + k] = np.float64(st[k])
+    for prefix, buf in (("weights", None), ("adam_m", eng.adam_m), ("adam_v", eng.adam_v)):
+        for name, t in eng.export_named(buf).items():
+            arrays[prefix + "." + name.replace("/", ".")] = t.numpy().astype(np.float32, copy=False)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        keep = 0.9 * DUMP_BUDGET_BYTES / total
+        for name in [n for n, a in arrays.items() if a.size > 4096]:
+            a = arrays.pop(name).reshape(-1)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, int(a.size * keep), replace=False))
+            arrays[name + ".sample"] = a[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def eval_leg(device, V_items=3706, users=6040, seed=0):
     """Train + evaluate through the product surface on a synthetic Zipf log with successor structure (datasets.make_synthetic,
     order=0.6): dataloader factory -> prepare_training(device_masking) -> trainer -> evaluator (100 popularity negatives per
@@ -366,6 +396,9 @@ def main():
                                                               "ONE rank: the only way to rehearse it on a one-GPU box")
     ap.add_argument("--dry-launch", action="store_true", help="with --gpus N > 1 and no WORLD_SIZE in the environment: print the "
                                                               "torch.distributed.run command the launcher would start (JSON) and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed (the "
+                                                          "step's loss and metric sums, the updated weights and AdamW moments) "
+                                                          "as DIR/<name>.npy")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -445,35 +478,24 @@ def main():
     sys.stdout.flush()
     os.dup2(saved_stdout, 1)
     os.close(saved_stdout)
-    def timed_region(offset):
-        """EXACTLY args.steps steps between barriers + device synchronisation; the max over ranks"""
-        t0 = time.perf_counter()
-        for i in range(args.steps):
-            step(offset + i)
-        torch.cuda.synchronize()
-        if use_dist:
-            dist.barrier()
-        torch.cuda.synchronize()
-        el = time.perf_counter() - t0
-        if use_dist:
-            t = torch.tensor([el], dtype=torch.float64, device=device)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            el = float(t.item())
-        return el
-
-    # a region shorter than 200 ms (the driver's 20 steps are 12 ms) is repeated and the MEDIAN region reported: one region of that
-    # length moves by several per cent with the clock state it starts in.  Every rank takes the same decision (the first region's
-    # time is already the max over ranks).
-    regions = [timed_region(args.warmup)]
-    repeats = 1 if (regions[0] >= 0.2 or args.no_breakdown) else max(7, min(51, int(0.2 / max(regions[0], 1e-6)) | 1))   # (profiling runs: one region)
-    for k in range(1, repeats):
-        if use_dist:
-            dist.barrier()
-        regions.append(timed_region(args.warmup + k * args.steps))
-    regions.sort()
-    elapsed = regions[len(regions) // 2]
+    # the timed region: EXACTLY args.steps steps between barriers + device synchronisation; the max over ranks.  --steps sets the
+    # length of the region (a region of a fraction of a second measures the clock state it starts in as much as the step).
+    t0 = time.perf_counter()
+    for i in range(args.steps):
+        step(args.warmup + i)
+    torch.cuda.synchronize()
+    if use_dist:
+        dist.barrier()
+    torch.cuda.synchronize()
+    elapsed = time.perf_counter() - t0
+    if use_dist:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=device)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
     st = eng.read_state()
     loss = st["loss_sum"] / max(st["valid_count"], 1.0)
+    if args.dump_outputs and rank == 0:   # before any further step: what the last timed step left
+        dump_outputs(args.dump_outputs, eng, st)
     assert np.isfinite(loss), "training diverged"
 
     if rank == 0:
@@ -672,8 +694,7 @@ def main():
 
         result = {"metric": "masked positions/sec", "value": round(value, 1), "unit": "masked positions/s",
                   "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4),
-                  "repeats": len(regions), "ms_min": round(regions[0] / args.steps * 1e3, 4), "ms_max": round(regions[-1] / args.steps * 1e3, 4),
-                  "timing": f"median of {len(regions)} timed regions of {args.steps} steps each" if len(regions) > 1 else "one timed region",
+                  "timing": f"one timed region of {args.steps} steps",
                   "lib_sha256": library_hash(),
                   "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
                   "config": {"workload": f"{args.config}: full train step, B={B}/GPU L={L} P={P} H={H} layers={NL} heads={NH} "

@@ -27,15 +27,15 @@ def test_dry_launch_prints_the_torchrun_command_for_n_ranks():
 
 
 def test_a_rank_under_a_launcher_does_not_launch_again():
-    """with WORLD_SIZE in the environment the process IS a rank: it must go on to the GPU work (which fails here: no GPU) and not
-    start children of its own -- so no launch record is printed and the exit status is the rank's failure"""
-    env = dict(_env(), WORLD_SIZE="2", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29999")
+    """with WORLD_SIZE in the environment the process IS a rank: it must go on to the GPU work and not start children of its own --
+    so no launch record is printed and the exit status is the rank's failure.  The rank sees no device (HIP_VISIBLE_DEVICES=-1),
+    so its first GPU step fails on every machine: with a GPU in view it would wait in the rendezvous for a rank 1 that never comes."""
+    env = dict(_env(), WORLD_SIZE="2", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29999",
+               HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-launch"],
                          env=env, capture_output=True, text=True, timeout=240)
     assert '"launch"' not in out.stdout
-    import torch
-    if not torch.cuda.is_available():
-        assert out.returncode != 0 and "needs the GPU" in out.stderr
+    assert out.returncode != 0 and "needs the GPU" in out.stderr
 
 
 def test_attention_roofline_bytes_are_the_mean_over_the_layers_launches():
