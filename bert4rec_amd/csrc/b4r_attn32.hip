@@ -2062,7 +2062,7 @@ int32_t b4r_attn32_supported(int32_t hidden_size, int32_t num_heads, int32_t L) 
 // Sequences of at most two 32-token tiles leave five of the seven waves of a workgroup without a query / key tile: there round 2's
 // 16-token-tile kernels (one wave per 16 tokens) are faster -- Steam, L = 50: 0.408 against 0.440 ms per train step.  The 32-token-tile
 // kernels are PREFERRED from this length on (they still serve shorter sequences when a descriptor asks for what only they can do).
-static int g_attn32_min_len = getenv("B4R_ATTN32_MIN_L") ? atoi(getenv("B4R_ATTN32_MIN_L")) : 65;
+static int g_attn32_min_len = 65;
 extern "C" int32_t b4r_attn32_set_min_len(int32_t L) {
   const int old = g_attn32_min_len;
   if (L >= 0) g_attn32_min_len = L;
@@ -2075,10 +2075,9 @@ int32_t b4r_attn32_preferred(int32_t hidden_size, int32_t num_heads, int32_t L) 
 // ---- the attention core for any number of 32-wide heads (b4r_attn_fwd / b4r_attn_bwd in the bf16x3 mode) ----------------------
 int64_t b4r_attn_rx_keep_words(int B, int L, int heads);
 bool b4r_attn32_core_preferred(int L) {
-  static const bool on = !(getenv("B4R_ATTN32_CORE") && atoi(getenv("B4R_ATTN32_CORE")) == 0);
-  return on && L > 0 && L <= 224 && L >= g_attn32_min_len && b4r_get_gemm_mode() == B4R_GEMM_BF16X3;
+  return L > 0 && L <= 224 && L >= g_attn32_min_len && b4r_get_gemm_mode() == B4R_GEMM_BF16X3;
 }
-static int g_attn32_core_fwd = getenv("B4R_ATTN32_CORE_FWD") ? atoi(getenv("B4R_ATTN32_CORE_FWD")) : 0;
+static int g_attn32_core_fwd = 0;
 bool b4r_attn32_core_fwd_wanted() { return g_attn32_core_fwd != 0; }
 extern "C" int32_t b4r_attn32_set_core_fwd(int32_t on) {
   const int old = g_attn32_core_fwd;
@@ -2144,8 +2143,7 @@ int64_t b4r_attn32_keep_words(int32_t B, int32_t L, int32_t heads) {
 
 // ---- the attention core on the masked-LM slots' queries only (b4r_model.hip: the last layer under B4R_FLAG_HEAD_ROWS_ONLY) -------------
 bool b4r_attn32_slotq_supported(int L, int P) {
-  static const bool on = !(getenv("B4R_ATTN_SLOTQ") && atoi(getenv("B4R_ATTN_SLOTQ")) == 0);
-  return on && L > 64 && L <= 224 && P > 0 && P <= 64 && 2 * P <= L && b4r_get_gemm_mode() == B4R_GEMM_BF16X3;
+  return L > 64 && L <= 224 && P > 0 && P <= 64 && 2 * P <= L && b4r_get_gemm_mode() == B4R_GEMM_BF16X3;
 }
 int64_t b4r_attn32_slotq_keep_words(int B, int L, int heads, int P) {
   return (int64_t)B * heads * b4r_cdiv(L, 32) * b4r_cdiv(P, 32) * 32;
@@ -2251,8 +2249,7 @@ int b4r_attn32_bwd(const b4r_attn_block_bwd_desc* d, b4r_stream_t stream) {
   p.drop_e = b4r_make_drop(d->rng, d->emb_stream, d->emb_rate, d->rng != nullptr && embed);
   B4R_CHECK_ARG(!p.drop_p.rng || d->keep_bits, B4R_E_BADARG, "b4r_attn_block_bwd: attention dropout needs the forward's keep_bits");
   // the slots as the sweep's only queries (the kernel's CQ form): a row list of at most 64 slots on at least three token tiles
-  static const bool cq_on = !(getenv("B4R_ATTN32_CQ") && atoi(getenv("B4R_ATTN32_CQ")) == 0);
-  const bool cq = cq_on && p.slot_pos != nullptr && p.slots <= 64 && p.NT >= 3;
+  const bool cq = p.slot_pos != nullptr && p.slots <= 64 && p.NT >= 3;
   const size_t sh = cq ? (size_t)bwd32_lds_cq(p.NT) : (size_t)bwd32_lds(p.NT);
   const dim3 grid((unsigned)d->B), block((unsigned)(64 * p.NT));
   hipStream_t s = (hipStream_t)stream;
@@ -2313,11 +2310,8 @@ int b4r_attn32_fwd(const b4r_attn_block_desc* d, b4r_stream_t stream) {
   }
   const bool drop = p.drop_p.rng != nullptr && p.drop_p.thr != 0;
   // the slots as the only queries (the kernel's CQ form): a list of at most 64 rows on at least three token tiles, not the first layer
-  // (B4R_ATTN32_CQ=0 switches the backward's form off: it then reads every token's ctx / lse, so the forward must write them all)
-  static const bool cq_on = !(getenv("B4R_ATTN32_CQ_FWD") && atoi(getenv("B4R_ATTN32_CQ_FWD")) == 0) &&
-                            !(getenv("B4R_ATTN32_CQ") && atoi(getenv("B4R_ATTN32_CQ")) == 0);
   B4R_CHECK_ARG(d->out_slot_positions == nullptr || d->out_slots > 0, B4R_E_BADARG, "b4r_attn_block_fwd: out_slot_positions needs out_slots");
-  const bool cq = cq_on && d->out_slot_positions != nullptr && d->out_slots <= 64 && p.NT >= 3 && !embed && d->qkv == nullptr;
+  const bool cq = d->out_slot_positions != nullptr && d->out_slots <= 64 && p.NT >= 3 && !embed && d->qkv == nullptr;
   if (cq) { p.slot_pos = d->out_slot_positions; p.slots = d->out_slots; }
   const size_t sh = cq ? (size_t)fwd32_lds_cq(p.NT) : (size_t)fwd32_lds(p.NT);
   const dim3 grid((unsigned)d->B), block((unsigned)(64 * p.NT));

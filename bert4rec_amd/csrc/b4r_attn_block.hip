@@ -732,12 +732,7 @@ int32_t b4r_attn32_supported(int32_t hidden_size, int32_t num_heads, int32_t L);
 int32_t b4r_attn32_preferred(int32_t hidden_size, int32_t num_heads, int32_t L);   // supported AND long enough to pay (b4r_attn32.hip)
 int b4r_attn32_bwd(const b4r_attn_block_bwd_desc* d, b4r_stream_t stream);
 int64_t b4r_attn_rx_keep_words(int B, int L, int heads);
-static bool use_attn32() {
-  static const bool on = !(getenv("B4R_ATTN32") && atoi(getenv("B4R_ATTN32")) == 0);
-  return on;
-}
-
-bool b4r_attn32_active(int H, int heads, int L) { return use_attn32() && b4r_attn32_preferred(H, heads, L) != 0; }
+bool b4r_attn32_active(int H, int heads, int L) { return b4r_attn32_preferred(H, heads, L) != 0; }
 
 extern "C" int32_t b4r_attn_block_supported(int32_t hidden_size, int32_t num_heads, int32_t L) {
   return (hidden_size == HID && num_heads == 2 && L > 0 && L <= 256 && b4r_get_gemm_mode() == B4R_GEMM_BF16X3) ? 1 : 0;
@@ -766,7 +761,7 @@ extern "C" int b4r_attn_block_bwd(const b4r_attn_block_bwd_desc* d, b4r_stream_t
   B4R_CHECK_ARG(d != nullptr, B4R_E_BADARG, "b4r_attn_block_bwd: null descriptor");
   // the 32-token-tile kernel where it is preferred, and wherever the descriptor asks for what only it does (weight gradients inside
   // the launch, sparse dz1); the forward of the same step wrote the dropout decisions in both layouts (bits32 below)
-  if (use_attn32() && b4r_attn32_supported(d->H, d->heads, d->L) &&
+  if (b4r_attn32_supported(d->H, d->heads, d->L) &&
       (b4r_attn32_preferred(d->H, d->heads, d->L) || d->dWqkv != nullptr || d->dz1_slot_positions != nullptr || d->dqkv == nullptr))
     return b4r_attn32_bwd(d, stream);
   B4R_CHECK_ARG(d->dWqkv == nullptr && d->dqkv != nullptr, B4R_E_SHAPE, "b4r_attn_block_bwd: dWqkv inside the launch needs L <= 224 (this path writes dqkv)");
@@ -813,16 +808,14 @@ extern "C" int b4r_attn_block_bwd(const b4r_attn_block_bwd_desc* d, b4r_stream_t
 }
 
 int b4r_attn32_fwd(const b4r_attn_block_desc* d, b4r_stream_t stream);
-bool b4r_attn32_core_preferred(int L);
 extern "C" int b4r_attn_block_fwd(const b4r_attn_block_desc* d, b4r_stream_t stream) {
   B4R_CHECK_ARG(d != nullptr, B4R_E_BADARG, "b4r_attn_block_fwd: null descriptor");
-  static const bool fwd32 = !(getenv("B4R_ATTN32_FWD") && atoi(getenv("B4R_ATTN32_FWD")) == 0);
   // The 32-token-tile forward writes the attention-dropout decisions in the 32-key-tile layout ONLY.  Its readers are the
-  // 32-token-tile block backward and, where a step's backward is unfused (L > 208, B4R_ATTN_BWD_FUSED=0, ...), the attention core's
-  // backward -- which reads that layout only while b4r_attn32_core_preferred holds (B4R_ATTN32_CORE).  So the kernel is taken only
-  // where BOTH readers read what it writes; otherwise the 16-token-tile forward below runs, which writes both layouts.  (The minimum
-  // length of b4r_attn32_set_min_len enters both predicates: change it between steps, never between a forward and its backward.)
-  if (fwd32 && use_attn32() && b4r_attn32_preferred(d->H, d->heads, d->L) && b4r_attn32_core_preferred(d->L)) return b4r_attn32_fwd(d, stream);
+  // 32-token-tile block backward and, where a step's backward is unfused (L > 208), the attention core's backward, which reads that
+  // layout wherever b4r_attn32_core_preferred holds -- b4r_attn32_preferred implies it.  Where the 32-token-tile kernels are not
+  // preferred the 16-token-tile forward below runs, which writes both layouts.  (The minimum length of b4r_attn32_set_min_len enters
+  // both predicates: change it between steps, never between a forward and its backward.)
+  if (b4r_attn32_preferred(d->H, d->heads, d->L)) return b4r_attn32_fwd(d, stream);
   B4R_CHECK_ARG(b4r_attn_block_supported(d->H, d->heads, d->L), B4R_E_SHAPE,
                 "b4r_attn_block_fwd: needs hidden size 64, 2 heads, L <= 256 and the bf16x3 mode (H=%d heads=%d L=%d)", d->H, d->heads,
                 d->L);
@@ -846,7 +839,7 @@ extern "C" int b4r_attn_block_fwd(const b4r_attn_block_desc* d, b4r_stream_t str
   p.drop_p = b4r_make_drop(d->rng, d->probs_stream, d->probs_rate, d->rng != nullptr);
   p.drop_o = b4r_make_drop(d->rng, d->out_stream, d->out_rate, d->rng != nullptr);
   B4R_CHECK_ARG(!p.drop_p.rng || d->keep_bits, B4R_E_BADARG, "b4r_attn_block_fwd: attention dropout needs keep_bits");
-  if (p.bits && use_attn32() && b4r_attn32_supported(d->H, d->heads, d->L)) p.bits32 = p.bits + b4r_attn_rx_keep_words(d->B, d->L, d->heads);
+  if (p.bits && b4r_attn32_supported(d->H, d->heads, d->L)) p.bits32 = p.bits + b4r_attn_rx_keep_words(d->B, d->L, d->heads);
   if (embed) {
     p.ids = d->emb_ids; p.table = d->emb_table; p.pos = d->emb_pos; p.g0 = d->emb_gamma; p.be0 = d->emb_beta; p.V = d->emb_vocab;
     p.x_out = d->emb_x; p.mean0 = d->emb_mean; p.rstd0 = d->emb_rstd; p.eps0 = d->emb_eps;

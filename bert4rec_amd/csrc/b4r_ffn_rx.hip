@@ -126,8 +126,8 @@ __global__ __launch_bounds__(64 * FW) void ffn_fwd_kernel(FfnP p) {
 // -----------------------------------------------------------------------------------------------------------
 // backward, input gradient + the attention LayerNorm's backward.  LDS: [W1 image | W2 image | b1 | LayerNorm partials]
 // -----------------------------------------------------------------------------------------------------------
-// NW waves per workgroup: 16 (a 128-register cap, 10 registers spilled; the default) or 8 (B4R_FFN_DX_WAVES=8: two waves per SIMD, 256
-// registers, no spill, a wave walks two 16-token tiles at ML-1M -- 3-4 us slower per layer, see the launch site)
+// NW waves per workgroup: launched with 16 (a 128-register cap, 10 registers spilled).  8 (two waves per SIMD, 256 registers, no spill,
+// a wave walks two 16-token tiles at ML-1M) was measured 3-4 us slower per layer, see the launch site
 template <int NW>
 __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_bwd_dx_kernel(FfnP p) {
   FF_MARK(10);
@@ -534,12 +534,7 @@ extern "C" int b4r_ffn_block_fwd(const b4r_ffn_desc* d, b4r_stream_t stream) {
 int b4r_launch_slab_reduce_full(const float* slab, int S, int Mo, int No, float* out, int ldo, int accumulate,
                                 const float* cslab, float* colsum, const float* caslab, float* colsum_a, hipStream_t stream);
 
-// after_dx (optional): recorded between the two kernels -- dz1 is complete there, the weight gradients are not
-int b4r_ffn_block_bwd_marked(const b4r_ffn_desc* d, hipStream_t stream, hipEvent_t after_dx);
 extern "C" int b4r_ffn_block_bwd(const b4r_ffn_desc* d, b4r_stream_t stream) {
-  return b4r_ffn_block_bwd_marked(d, (hipStream_t)stream, nullptr);
-}
-int b4r_ffn_block_bwd_marked(const b4r_ffn_desc* d, hipStream_t stream, hipEvent_t after_dx) {
   B4R_CHECK_ARG(d != nullptr, B4R_E_BADARG, "b4r_ffn_block_bwd: null descriptor");
   B4R_CHECK_ARG(b4r_ffn_block_supported(d->H, d->I), B4R_E_SHAPE,
                 "b4r_ffn_block_bwd: needs hidden size 64, inner size 256 and the bf16x3 mode (H=%d I=%d)", d->H, d->I);
@@ -573,22 +568,10 @@ int b4r_ffn_block_bwd_marked(const b4r_ffn_desc* d, hipStream_t stream, hipEvent
   if (rowmode) { p.slotof = d->row_slot; p.dgr = d->slot_grad; p.dz2c = d->dz2_rows; }
   // measured (tools/bench_ffn.py, same box, dx + dw + reductions): 16 waves 81.2 / 81.4 us, 8 waves 84.0 / 85.7 us -- the spill-free
   // 256-register form loses more latency hiding (two waves per SIMD instead of four) than the 10 spilled registers cost
-  static const int dx_waves = getenv("B4R_FFN_DX_WAVES") ? atoi(getenv("B4R_FFN_DX_WAVES")) : 16;
-  int rc;
-  if (dx_waves == 16) {
-    rc = b4r_raise_lds((const void*)ffn_bwd_dx_kernel<16>, DX_LDS, "b4r_ffn_block_bwd");
-    if (rc) return rc;
-    hipLaunchKernelGGL(ffn_bwd_dx_kernel<16>, dim3(gdx), dim3(64 * 16), DX_LDS, s, p);
-  } else {
-    rc = b4r_raise_lds((const void*)ffn_bwd_dx_kernel<8>, DX_LDS, "b4r_ffn_block_bwd");
-    if (rc) return rc;
-    hipLaunchKernelGGL(ffn_bwd_dx_kernel<8>, dim3(gdx), dim3(64 * 8), DX_LDS, s, p);
-  }
+  int rc = b4r_raise_lds((const void*)ffn_bwd_dx_kernel<16>, DX_LDS, "b4r_ffn_block_bwd");
+  if (rc) return rc;
+  hipLaunchKernelGGL(ffn_bwd_dx_kernel<16>, dim3(gdx), dim3(64 * 16), DX_LDS, s, p);
   B4R_CHECK_LAUNCH("b4r_ffn_block_bwd (dx)");
-  if (after_dx != nullptr && hipEventRecord(after_dx, s) != hipSuccess) {
-    b4r_set_error("b4r_ffn_block_bwd: event record failed");
-    return B4R_E_HIP;
-  }
   hipLaunchKernelGGL(ffn_bwd_dw_kernel, dim3(gdw), dim3(64 * FW), 0, s, p);
   B4R_CHECK_LAUNCH("b4r_ffn_block_bwd (dw)");
   // ordered sums over the workgroups (queued when the caller collects its reductions into one launch)

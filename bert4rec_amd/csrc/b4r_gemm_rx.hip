@@ -102,14 +102,13 @@ __device__ __forceinline__ f32x8 drop8(const DropCtx& c, const f32x8 x, uint64_t
 // column splits of one row block, the output tiles of one row slice) are given consecutive LOGICAL ids, so the logical
 // id is chosen such that a run of consecutive logical ids sits on one XCD: logical = (id % 8) * ceil(n/8) + id / 8.
 // Ids whose logical id falls beyond n (n not a multiple of 8) return without work; the grid is rounded up to 8.
-// (ML-1M step, same box: 0.922 ms with the mapping, 0.931 ms without (B4R_XCD=0); single kernels move by < 1 us -- the
-// re-reads were mostly served by the shared MALL already.)
+// (ML-1M step, same box: 0.922 ms with the mapping, 0.931 ms without; single kernels move by < 1 us -- the re-reads were mostly
+// served by the shared MALL already.)
 __device__ __forceinline__ int xcd_logical_id(int id, int n) {
-  if (n < 0) return id;   // mapping switched off (B4R_XCD=0): n is passed negated
+  if (n < 0) return id;   // mapping switched off for this launch: n is passed negated
   const int per = (n + 7) >> 3;
   return (id & 7) * per + (id >> 3);
 }
-inline bool xcd_on() { static const bool on = !(getenv("B4R_XCD") && atoi(getenv("B4R_XCD")) == 0); return on; }
 inline unsigned xcd_grid(int64_t n) { return (unsigned)(((n + 7) >> 3) << 3); }
 
 constexpr int EPI_ADD_RES_LN_BWD_EMBED = 11;   // internal: B4R_EPI_ADD_RES_LN_BWD with ln_ids set
@@ -647,12 +646,9 @@ constexpr int WIDE_KC = 32;
 // ML-1M shapes (K <= 256) two are 1-3 % faster per product when the kernel runs back to back on its own (operands warm in the
 // 256 MB last-level cache) but 1.3 % SLOWER over the train step (0.859 vs 0.847 ms), where every product reads what the kernel
 // before it just wrote; at the ML-20M shapes (K up to 1024: 32 chunks) two win 1.9 % of the step (5.76 -> 5.66 ms).  So: two for
-// the 128 x 128 tiles with K >= B4R_WIDE_DEPTH2_K (256: 5.89 -> 5.79 ms on another box; 512: 5.84), one otherwise (no ML-1M
+// the 128 x 128 tiles with K >= WIDE_DEPTH2_K (256: 5.89 -> 5.79 ms on another box; 512: 5.84), one otherwise (no ML-1M
 // product has such a shape).
-inline int wide_depth2_k() {
-  static const int k = getenv("B4R_WIDE_DEPTH2_K") ? atoi(getenv("B4R_WIDE_DEPTH2_K")) : 256;
-  return k;
-}
+constexpr int WIDE_DEPTH2_K = 256;
 constexpr int wide_lds(int TM, int TN) { return (TM + TN) * 64 * 2 + STAGE_FLOATS * 4; }   // hi + lo images of TM + TN rows of 32 bf16
 
 __device__ __forceinline__ int wide_off(int row, int ch) {   // image 0 (hi); lo is 1024 bytes further
@@ -842,16 +838,14 @@ __global__ __launch_bounds__(256, 2) void rx_gemm_wide_kernel(RxP p) {   // two 
 //   K = 64:   QKV 19.2 -> 16.3, attention-out 12.5 -> 8.9, FFN-in 28.6 -> 26, dctx 10.2 -> 8.1 with tiles; the two products
 //             with B as [N,K] and many columns stay on rx_gemm_nk_kernel (GELU' product 30 vs 31.5; vocabulary
 //             projection 32 vs 38.5: its one-tile-per-workgroup sweep with the A strip in registers writes faster)
-// B4R_WIDE bits switch the three groups off for experiments: 1 = 128-tiles, 2 = 64-tiles, 4 = K = 64 shapes.
 template <bool B_NK>
 inline int wide_tile(const RxP& p) {
-  static const int mode = getenv("B4R_WIDE") ? atoi(getenv("B4R_WIDE")) : 7;
   if (p.K % WIDE_KC != 0 || p.slab_stride != 0) return 0;
   if (p.K < 128) {
-    if (!(mode & 4) || p.K != 64 || p.N > 256 || (B_NK && p.N > 128)) return 0;
+    if (p.K != 64 || p.N > 256 || (B_NK && p.N > 128)) return 0;
   }
-  if (p.N >= 128) return (mode & 1) ? 128 : 0;
-  if (p.N == 64) return (mode & 2) ? 64 : 0;
+  if (p.N >= 128) return 128;
+  if (p.N == 64) return 64;
   return 0;
 }
 
@@ -859,9 +853,8 @@ template <bool B_NK, int EPI, bool A_DROP, int T>
 void launch_wide(RxP p, hipStream_t s) {
   p.n_items = b4r_cdiv(p.M, T) * b4r_cdiv(p.N, T);
   const dim3 grid(xcd_grid(p.n_items));
-  if (!xcd_on()) p.n_items = -p.n_items;
   if constexpr (T == 128) {
-    if (p.K >= wide_depth2_k()) {
+    if (p.K >= WIDE_DEPTH2_K) {
       (void)b4r_raise_lds((const void*)rx_gemm_wide_kernel<B_NK, EPI, A_DROP, T, T, 2>, wide_lds(T, T), "gemm");
       hipLaunchKernelGGL((rx_gemm_wide_kernel<B_NK, EPI, A_DROP, T, T, 2>), grid, dim3(256), wide_lds(T, T), s, p);
       return;
@@ -1268,28 +1261,25 @@ __global__ __launch_bounds__(512, 2) void rx_gemm_tn128_kernel(RxTnP p) {
     }
 }
 
-// 128 x 128 tiles when both output dimensions allow it (B4R_TN_WIDE=0: the 64 x 64 kernel everywhere)
+// 128 x 128 tiles when both output dimensions allow it (else the 64 x 64 kernel)
 inline bool tn_wide_tiles(int Mo, int No) {
-  static const int on = getenv("B4R_TN_WIDE") ? atoi(getenv("B4R_TN_WIDE")) : 1;
-  return on && Mo >= 128 && No >= 128 && Mo % 128 == 0 && No % 128 == 0;
+  return Mo >= 128 && No >= 128 && Mo % 128 == 0 && No % 128 == 0;
 }
 
 constexpr int TN_KS = 64;   // measured on the ML-1M shapes: 32 -> 1.185, 64 -> 1.173, 128 -> 1.197 ms/step
 
-inline int tn_single_tile_cap() {
-  static const int c = getenv("B4R_TN_CAP1") ? atoi(getenv("B4R_TN_CAP1")) : 512;
-  return c;
-}
+constexpr int TN_CAP1 = 512;             // slice cap of a single-tile product
+constexpr int TN_TARGET = 512;           // workgroups aimed at by the 64 x 64 tiles
+constexpr int TN_TARGET_WIDE = 256;      // ... and by the 128 x 128 tiles.  Measured at ML-20M: 128 -> 10.83, 256 -> 9.55, 384 -> 9.54,
+                                         // 512 -> 9.56 ms per step (64 x 64 tiles: 9.85)
 int rx_tn_split(int R, int Mo, int No) {
-  static const int wg_target = getenv("B4R_TN_TARGET") ? atoi(getenv("B4R_TN_TARGET")) : 512;
-  static const int wg_target_wide = getenv("B4R_TN_TARGET_WIDE") ? atoi(getenv("B4R_TN_TARGET_WIDE")) : 256;   // measured at ML-20M: 128 -> 10.83, 256 -> 9.55, 384 -> 9.54, 512 -> 9.56 ms per step (64 x 64 tiles: 9.85)
   const bool wide = tn_wide_tiles(Mo, No);
   const int tw = wide ? 128 : 64;
   const int tiles = b4r_cdiv(Mo, tw) * b4r_cdiv(No, tw);
-  int S = b4r_cdiv(wide ? wg_target_wide : wg_target, tiles);
+  int S = b4r_cdiv(wide ? TN_TARGET_WIDE : TN_TARGET, tiles);
   const int max_s = b4r_cdiv(R, 2 * TN_KS);  // at least two chunks per workgroup
   if (S > max_s) S = max_s;
-  const int cap = tiles == 1 ? tn_single_tile_cap() : 256;   // one 64 x 64 output tile: the slices are the only parallelism
+  const int cap = tiles == 1 ? TN_CAP1 : 256;   // one 64 x 64 output tile: the slices are the only parallelism
   if (S > cap) S = cap;
   if (S < 1) S = 1;
   return S;
@@ -1351,9 +1341,9 @@ int b4r_gemm_rx_launch(const b4r_gemm_desc* d, hipStream_t stream) {
   const int total_steps = b4r_cdiv(d->N, 32);
   // one resident round: 256 CUs x 4 workgroups (96 VGPRs -> 4 waves/SIMD).  A grid a little above that leaves a half-empty
   // second round (measured on the MLM-head projection: 960 workgroups 31.7 us, 1360 36.2 us, 3120 40.6 us), so round the
-  // split count DOWN; B4R_RX_TARGET overrides the slot count for experiments
-  static const int wg_slots = getenv("B4R_RX_TARGET") ? atoi(getenv("B4R_RX_TARGET")) : 1024;
-  int splits = wg_slots / mblocks;
+  // split count DOWN
+  constexpr int RX_TARGET = 1024;
+  int splits = RX_TARGET / mblocks;
   if (splits > total_steps) splits = total_steps;
   if (splits < 1) splits = 1;
   p.steps_per_split = b4r_cdiv(total_steps, splits);
@@ -1362,7 +1352,7 @@ int b4r_gemm_rx_launch(const b4r_gemm_desc* d, hipStream_t stream) {
   dim3 grid(xcd_grid(p.n_items));
   // many column splits = a store-dominated product (the materialising vocabulary projection: 12 splits): there the
   // mapping concentrates each XCD's writes and costs time (34 -> 40 us measured), so it is kept to the few-split products
-  if (!xcd_on() || p.n_splits > 4) p.n_items = -p.n_items;
+  if (p.n_splits > 4) p.n_items = -p.n_items;
   int rc = d->b_is_nk ? dispatch_rx<true>(p, d->epilogue, a_drop, grid, stream)
                       : dispatch_rx<false>(p, d->epilogue, a_drop, grid, stream);
   if (rc != B4R_OK) return rc;

@@ -1,5 +1,5 @@
-// Masked-LM head of a TRAIN step without materialised logits, round 4's rebuild of b4r_head_rx.hip on 32 x 32 tiles (hidden size 64;
-// the 16-row-tile kernels keep 128 / 256 and serve as the A/B partner: B4R_HEAD32=0).  Same mathematics, same outputs:
+// Masked-LM head of a TRAIN step without materialised logits (split-precision arithmetic, hidden size 64, 128 or 256): round 4's
+// rebuild on 32 x 32 tiles of the 16-row-tile head of rounds 1-3 (removed since).  The mathematics:
 //
 //   logits x[m,v] = T[m,:].E[v,:] + b[v]      (T = transform output [M,H], E = tied item table [V,H];  bert4rec_model.py:76-81,143)
 //   loss_m = logsumexp_v x[m,v] - x[m,y_m] ;  g[m,v] = softmax(x[m,:])[v] - [v == y_m]      (trainer_utils.py:12-23)
@@ -24,6 +24,10 @@
 //     accumulator: no bias add, and in dE no subtraction in front of the exponential;
 //   * software pipeline: a step issues the logit products of tile i + 1, the value products of tile i - 1 and, between them one slice
 //     at a time, the vector work of tile i (and the row maximum / argmax bookkeeping of tile i + 1) as ONE hand-ordered stream.
+//
+// The forward sweep leaves per V slice and row the accumulators, max, sum, best logit and index; head_combine_kernel (or, deferred, the
+// dE sweep and the transform's LayerNorm backward: b4r_head_merge.h) merges the slices flash-decoding style into loss rows, lse and dT.
+// dE's partial tiles per M slice go to slabs that the backward's ordered reduction sums.
 #include "b4r_head32_pack.h"
 
 // H32_PROF (tools/build_variant.sh h32prof b4r_head32.hip -DH32_PROF): lane 0 of waves 0 and 5 of two workgroups stamps the shader clock
@@ -314,10 +318,11 @@ __global__ __launch_bounds__(64 * H32_WAVES, 2) void head32_fwd_kernel(H32P p) {
 #pragma unroll
   for (int t = 0; t < 16; ++t) rec[t] = -INFINITY;
   int btile = -1;
-  // `mx` only has to be COMMON to the two lanes of a row and close enough to the row maximum that 2^(x - mx) cannot overflow (the
-  // reasoning of b4r_head_rx.hip): it moves -- one exchange, one rescale -- only when some logit of the wave exceeds its row's reference
-  // by more than 2^SLACK: at the first tile of a slice (mx = -inf) and then almost never.  Everything that is still at the old reference
-  // is brought along exactly once: the pending products (fragments q of the tile in `slot`) are finished first, then acc and sum
+  // `mx` only has to be COMMON to the two lanes of a row and close enough to the row maximum that 2^(x - mx) cannot overflow; it need
+  // not be the maximum (the terms stay below 2^SLACK, their sum below 2^SLACK V, and the relative precision of a floating-point sum does
+  // not depend on the reference).  So it moves -- one exchange, one rescale -- only when some logit of the wave exceeds its row's
+  // reference by more than 2^SLACK: at the first tile of a slice (mx = -inf) and then almost never.  Everything that is still at the old
+  // reference is brought along exactly once: the pending products (fragments q of the tile in `slot`) are finished first, then acc and sum
   // rescaled.
   auto move_reference = [&](float pl8, const char* slot, f16x8 (&q)[2]) __attribute__((always_inline)) {
     constexpr float SLACK = 8.0f;
@@ -637,7 +642,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void head32w_fwd_kernel(H32P
 #pragma unroll
   for (int pp = 0; pp < NP; ++pp) acc[pp] = zero16();
   const int no_labels[16] = {};
-  // the reference of the running sums (b4r_head_rx.hip's reasoning): moved when a logit exceeds it by more than 2^SLACK; nothing is
+  // the reference of the running sums (the forward's reasoning): moved when a logit exceeds it by more than 2^SLACK; nothing is
   // pending between two steps here, so only acc and sum are brought along
   auto move_reference = [&](float pl8) __attribute__((always_inline)) {
     constexpr float SLACK = 8.0f;
@@ -804,10 +809,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void head32w_dE_kernel(H32P 
   }
 }
 
-int h32_target_wgs() {
-  static const int t = getenv("B4R_HEAD32_WGS") ? atoi(getenv("B4R_HEAD32_WGS")) : 256;
-  return t < 1 ? 1 : t;
-}
+constexpr int H32_TARGET_WGS = 256;
 // slices of the swept dimension for `own_rows` rows held in registers: about one workgroup per CU
 // rows of `own` per workgroup: 8 waves of 32 (hidden 64 / 128), 4 waves of 32 at hidden 256 (one wave per SIMD, 512 registers)
 // (dE at hidden 128 as well: its two code versions -- with and without a label among the wave's items -- spill under the 256-register cap
@@ -815,7 +817,7 @@ int h32_target_wgs() {
 int h32_rows_wg(int H, bool fwd) { return (H == 256 || (H == 128 && !fwd)) ? 128 : 256; }
 int h32_slices(int own_rows, int swept_rows, int max_slices, int H, bool fwd) {
   const int blocks = b4r_cdiv(own_rows, h32_rows_wg(H, fwd)), tiles = b4r_cdiv(swept_rows, 32);
-  int s = h32_target_wgs() / blocks;                           // never more workgroups than CUs: a workgroup that has to wait for a CU doubles the kernel
+  int s = H32_TARGET_WGS / blocks;                           // never more workgroups than CUs: a workgroup that has to wait for a CU doubles the kernel
   s = s < 1 ? 1 : (s > max_slices ? max_slices : s);
   s = s > tiles ? tiles : s;
   const int per = b4r_cdiv(tiles, s);
@@ -839,12 +841,8 @@ extern "C" int b4r_debug_h32_prof(long long* host_out) {   // the stamps of the 
 }
 #endif
 
-// ---- host side (called by b4r_head_rx.hip's entry points when the 32 x 32 kernels serve the shape) --------------------------
-bool b4r_head32_active(int H) {
-  static const bool off = getenv("B4R_HEAD32") && atoi(getenv("B4R_HEAD32")) == 0;
-  static const bool wide_off = getenv("B4R_HEAD32_WIDE") && atoi(getenv("B4R_HEAD32_WIDE")) == 0;
-  return !off && (H == 64 || (!wide_off && (H == 128 || H == 256)));
-}
+// ---- host side ----------------------------------------------------------------------------------------------------------------------
+bool b4r_head32_hidden_ok(int H) { return H == 64 || H == 128 || H == 256; }
 int b4r_head32_fwd_slices(int M, int V, int H) { return h32_slices(M, V, 16, H, true); }
 // (at most 16 slabs: the ordered reduction then sums a gradient element in one thread with every load in flight, b4r_gemm.hip)
 int b4r_head32_dE_slices(int M, int V, int H) { return h32_slices(V, M, 16, H, false); }
@@ -895,9 +893,28 @@ int h32_dispatch(int H, const H32PackP& pk, const H32P& p, int own_rows, int sli
     default: b4r_set_error("head32: hidden size %d not supported", H); return B4R_E_SHAPE;
   }
 }
+
+// the merge of the forward's V slices (b4r_head_merge.h) as a launch of its own: loss rows, lse, labels and dT
+template <int NKH>
+__global__ __launch_bounds__(256) void head_combine_kernel(const float* part, int slices, int M, int V, const float* T,
+                                                           const float* E, const float* bias, const int64_t* y, float* dT,
+                                                           float* row_out, float* lse_out, int32_t* ylab) {
+  constexpr int TPR = 8 * NKH;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx / TPR >= M) return;                                   // whole TPR-lane groups are in or out of range together
+  constexpr int H = 32 * NKH;
+  const HeadMergeP mp{part, slices, M, V, T, E, bias, y, row_out, lse_out, ylab};
+  const f32x4 d = head_merge_row<NKH>(mp, idx / TPR, idx % TPR);
+  *reinterpret_cast<f32x4*>(dT + (int64_t)(idx / TPR) * H + 4 * (idx % TPR)) = d;
+}
 }  // namespace
 
-int b4r_head32_fwd_launch(const float* T, const float* E, const float* bias, int M, int V, int H, float* scratch, hipStream_t stream) {
+// may the dE launch merge the forward's V slices itself (b4r_head32_dE_launch with fwd_part)?
+bool b4r_head32_combine_foldable(int M, int V, int H) { return H == 64 && b4r_head32_fwd_slices(M, V, H) <= CMAX; }
+
+// loss rows (as b4r_softmax_ce writes them), lse, labels and dT from T, E, bias, y; only_sweep: the V slices' partials only (in scratch)
+int b4r_head32_fwd_launch(const float* T, const float* E, const float* bias, const int64_t* y, int M, int V, int H, float* scratch,
+                          float* dT, float* row_out, float* lse, int32_t* ylab, int only_sweep, hipStream_t stream) {
   const int slices = b4r_head32_fwd_slices(M, V, H), tiles = b4r_cdiv(V, 32);
   char* recs = reinterpret_cast<char*>(scratch + up4l((int64_t)slices * M * (H + 8 + 2)));
   H32PackP pk{};
@@ -907,16 +924,22 @@ int b4r_head32_fwd_launch(const float* T, const float* E, const float* bias, int
   const int rc = h32_dispatch<true>(H, pk, p, M, slices, stream);
   if (rc) return rc;
   B4R_CHECK_LAUNCH("masked-LM head forward (fused)");
+  if (only_sweep) return B4R_OK;
+  const dim3 grid(b4r_cdiv((int64_t)M * (H / 4), 256));
+  if (H == 64) hipLaunchKernelGGL(head_combine_kernel<2>, grid, dim3(256), 0, stream, (const float*)scratch, slices, M, V, T, E, bias, y, dT, row_out, lse, ylab);
+  else if (H == 128) hipLaunchKernelGGL(head_combine_kernel<4>, grid, dim3(256), 0, stream, (const float*)scratch, slices, M, V, T, E, bias, y, dT, row_out, lse, ylab);
+  else hipLaunchKernelGGL(head_combine_kernel<8>, grid, dim3(256), 0, stream, (const float*)scratch, slices, M, V, T, E, bias, y, dT, row_out, lse, ylab);
+  B4R_CHECK_LAUNCH("masked-LM head combine");
   return B4R_OK;
 }
 
-// slabs of dE [slices][V][H] and of db [slices][V] into scratch (the caller reduces them); lse / ylab given, or (fwd_part != NULL)
-// formed from the forward's compact (max, sum) pairs and the labels y
-// the conversion of the transform rows for dE as a job another launch can carry (b4r_zero2's rider): *out is an H32PackP
+// the conversion of the transform rows for dE as a job another launch can carry (b4r_zero2's rider): *out is an H32PackP; a following
+// b4r_head32_dE_launch with records_ready = 1 then skips its own conversion launch
 int b4r_head32_dE_pack_job(const float* T, const float* lse, const int32_t* ylab, int M, int V, int H, float* scratch, const float* fwd_part,
-                           int fwd_slices, const int64_t* y, void* out, size_t out_bytes, int* blocks) {
+                           const int64_t* y, void* out, size_t out_bytes, int* blocks) {
+  *blocks = 0;
   if (out_bytes < sizeof(H32PackP)) return B4R_E_BADARG;
-  const int slices = b4r_head32_dE_slices(M, V, H);
+  const int slices = b4r_head32_dE_slices(M, V, H), fwd_slices = b4r_head32_fwd_slices(M, V, H);
   H32PackP pk{};
   pk.src = T; pk.R = M; pk.dst = reinterpret_cast<char*>(scratch + up4l((int64_t)slices * ((int64_t)V * H + V))); pk.mode = 1; pk.np = H / 32;
   pk.lse = lse; pk.ylab = ylab; pk.V = V;
@@ -926,9 +949,18 @@ int b4r_head32_dE_pack_job(const float* T, const float* lse, const int32_t* ylab
   return B4R_OK;
 }
 
+int b4r_launch_slab_reduce_full(const float* slab, int S, int Mo, int No, float* out, int ldo, int accumulate,
+                                const float* cslab, float* colsum, const float* caslab, float* colsum_a, hipStream_t stream);
+
+// dE [V,H] and db [V] (overwritten, through the ordered slab reduction) from T, E, bias and the forward's lse / labels.
+// fwd_part != NULL: the forward ran with only_sweep = 1 and left its per-slice partials there; lse / ylab are not read (y: the labels),
+// the dE sweep forms them from the forward's compact (max, sum) pairs, and the merge itself (dT, loss rows) is the business of the
+// LayerNorm backward behind this launch (b4r_ln_bwd_launch's merge argument)
 int b4r_head32_dE_launch(const float* T, const float* E, const float* bias, const float* lse, const int32_t* ylab, int M, int V, int H,
-                         float* scratch, hipStream_t stream, const float* fwd_part, int fwd_slices, const int64_t* y, int records_ready) {
-  const int slices = b4r_head32_dE_slices(M, V, H), tiles = b4r_cdiv(M, 32);
+                         float* scratch, float* dE, float* db, hipStream_t stream, const float* fwd_part, const int64_t* y, int records_ready) {
+  if (fwd_part != nullptr)
+    B4R_CHECK_ARG(b4r_head32_combine_foldable(M, V, H), B4R_E_BADARG, "fused masked-LM head: the merge cannot ride on dE for this shape");
+  const int slices = b4r_head32_dE_slices(M, V, H), fwd_slices = b4r_head32_fwd_slices(M, V, H), tiles = b4r_cdiv(M, 32);
   char* recs = reinterpret_cast<char*>(scratch + up4l((int64_t)slices * ((int64_t)V * H + V)));
   H32PackP pk{};
   pk.src = records_ready ? nullptr : T; pk.R = M; pk.dst = recs; pk.mode = 1; pk.np = H / 32; pk.lse = lse; pk.ylab = ylab; pk.V = V;
@@ -939,5 +971,32 @@ int b4r_head32_dE_launch(const float* T, const float* E, const float* bias, cons
   const int rc = h32_dispatch<false>(H, pk, p, V, slices, stream);
   if (rc) return rc;
   B4R_CHECK_LAUNCH("masked-LM head dE (fused)");
-  return B4R_OK;
+  return b4r_launch_slab_reduce_full(p.slab, slices, V, H, dE, H, 0, nullptr, nullptr, p.bslab, db, stream);
+}
+
+extern "C" int64_t b4r_mlm_head_fused_scratch_floats(int32_t M, int32_t V, int32_t H) {
+  if (M <= 0 || V <= 0 || !b4r_head32_hidden_ok(H)) return 0;
+  const int64_t a = b4r_head32_fwd_scratch_floats(M, V, H), b = b4r_head32_dE_scratch_floats(M, V, H);
+  return a > b ? a : b;
+}
+
+extern "C" int b4r_mlm_head_fused_fwd(const float* T, const float* E, const float* bias, const int64_t* y_true, int32_t M,
+                                      int32_t V, int32_t H, float* scratch, float* dT, float* row_scratch, float* lse,
+                                      int32_t* labels, int32_t only_sweep, b4r_stream_t stream) {
+  B4R_CHECK_ARG(T && E && bias && y_true && scratch, B4R_E_BADARG, "b4r_mlm_head_fused_fwd: null argument");
+  B4R_CHECK_ARG(only_sweep || (dT && row_scratch && lse && labels), B4R_E_BADARG, "b4r_mlm_head_fused_fwd: null output");
+  B4R_CHECK_ARG(M > 0 && V > 0 && b4r_head32_hidden_ok(H), B4R_E_SHAPE, "b4r_mlm_head_fused_fwd: bad shape (H = 64, 128 or 256)");
+  B4R_CHECK_ARG(b4r_aligned16(T) && b4r_aligned16(E) && b4r_aligned16(scratch) && (only_sweep || b4r_aligned16(dT)), B4R_E_ALIGN,
+                "b4r_mlm_head_fused_fwd: T, E, scratch and dT must be 16-byte aligned");
+  return b4r_head32_fwd_launch(T, E, bias, y_true, M, V, H, scratch, dT, row_scratch, lse, labels, only_sweep, (hipStream_t)stream);
+}
+
+extern "C" int b4r_mlm_head_fused_bwd(const float* T, const float* E, const float* bias, const float* lse, const int32_t* labels,
+                                     int32_t M, int32_t V, int32_t H, float* scratch, float* dE, float* dbias,
+                                     b4r_stream_t stream) {
+  B4R_CHECK_ARG(T && E && bias && lse && labels && scratch && dE && dbias, B4R_E_BADARG, "b4r_mlm_head_fused_bwd: null argument");
+  B4R_CHECK_ARG(M > 0 && V > 0 && b4r_head32_hidden_ok(H), B4R_E_SHAPE, "b4r_mlm_head_fused_bwd: bad shape (H = 64, 128 or 256)");
+  B4R_CHECK_ARG(b4r_aligned16(T) && b4r_aligned16(E) && b4r_aligned16(scratch), B4R_E_ALIGN,
+                "b4r_mlm_head_fused_bwd: T, E and scratch must be 16-byte aligned");
+  return b4r_head32_dE_launch(T, E, bias, lse, labels, M, V, H, scratch, dE, dbias, (hipStream_t)stream, nullptr, nullptr, 0);
 }

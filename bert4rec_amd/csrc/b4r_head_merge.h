@@ -1,6 +1,6 @@
-// Merge of the V slices of the logits-free masked-LM head's forward (b4r_head_rx.hip: head_fwd_kernel leaves, per slice and row,
+// Merge of the V slices of the logits-free masked-LM head's forward (b4r_head32.hip: the forward sweep leaves, per slice and row,
 // H accumulators of sum_v exp(x - max) E[v,:], the slice's max and sum in log2 units, its best logit and index): flash-decoding
-// style.  Shared by head_combine_kernel (the forward's second launch), head_dE_kernel (lse / labels of the rows it sweeps when the
+// style.  Shared by head_combine_kernel (the forward's second launch), head32_pack_kernel (lse / labels of the rows dE sweeps when the
 // merge is deferred) and the LayerNorm backward of the transform (ln_bwd_kernel<.., MERGE>: in a train step the merged dT is consumed
 // right there, so the merge needs no launch and dT no round trip).
 #pragma once
@@ -20,7 +20,7 @@ struct HeadMergeP {
 
 // max and sum of a row over the forward's V slices (at most CMAX: the host does not fold the merge into dE beyond that), requested
 // early and finished a chunk later -> log-sum-exp in natural units (+inf for a slot without a label: zero gradient rows in
-// head_dE_kernel) and the label (-1: none).  The same arithmetic as head_merge_row: slices past the end add +0.
+// the dE sweep) and the label (-1: none).  The same arithmetic as head_merge_row: slices past the end add +0.
 #ifndef B4R_CMAX
 #define B4R_CMAX 16   // (the 32 x 32-tile forward uses up to 16 slices: Steam 12; 8 until round 4)
 #endif
@@ -89,7 +89,7 @@ __device__ __forceinline__ f32x4 head_merge_row(const HeadMergeP& q, int m, int 
     row_out[4 * (int64_t)m + 1] = valid ? 1.f : 0.f;
     row_out[4 * (int64_t)m + 2] = (valid && (int64_t)bidx == y64) ? 1.f : 0.f;
     row_out[4 * (int64_t)m + 3] = ((int64_t)bidx == y64) ? 1.f : 0.f;
-    lse_out[m] = valid ? lse : INFINITY;                        // +inf => zero gradient rows in head_dE_kernel
+    lse_out[m] = valid ? lse : INFINITY;                        // +inf => zero gradient rows in the dE sweep
     ylab[m] = (valid && y_ok) ? (int32_t)y64 : -1;
   }
   return d;

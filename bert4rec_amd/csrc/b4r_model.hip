@@ -20,28 +20,24 @@ int b4r_ln_bwd_launch(const float* dy, const float* z, const float* mean, const 
                       int rows, int H, float* dz, float* dgamma, float* dbeta, float* scratch, const int64_t* ids,
                       const float* table, const float* pos_table, int L, int V, DropArgs drop, hipStream_t stream,
                       const float* gelu_pre = nullptr, const B4rHeadMerge* merge = nullptr);
-int b4r_head_rx_fwd_slices(int M, int V, int H);
 int b4r_scatter_add_rows_impl(const float* src, const int64_t* idx, int64_t idx_add_per, int per, int n, int H,
                               float* dst, int dst_ld, const int64_t* skip_if_zero, int64_t dst_rows, int hot_rows,
                               float* hot_scratch, hipStream_t stream);
 int64_t b4r_scatter_hot_scratch_floats(int hot_rows, int H);
 int b4r_batch_colsum(const float* x, int B, int L, int H, float* dpos, float* scratch, hipStream_t stream);
 int b4r_gemm_f32_splitk(const b4r_gemm_desc* d, int splits, float* scratch, int k_pad_ok, hipStream_t stream);
-// b4r_head_rx.hip: masked-LM head of a train step without materialised logits (hidden size 64, bf16x3 mode)
-bool b4r_head_rx_hidden_ok(int H);
-int64_t b4r_head_rx_fwd_scratch_floats(int M, int V, int H);
-int64_t b4r_head_rx_dE_scratch_floats(int M, int V, int H);
-int b4r_head_rx_fwd_launch(const float* T, const float* E, const float* bias, const int64_t* y, int M, int V, int H,
-                           float* scratch, float* dT, float* row_out, float* lse, int32_t* ylab, hipStream_t stream);
-int b4r_head_rx_dE_launch(const float* T, const float* E, const float* bias, const float* lse, const int32_t* ylab, int M, int V,
-                          int H, float* scratch, float* dE, float* db, hipStream_t stream, const float* fwd_part, const int64_t* y,
-                          int records_ready);
-int b4r_head_rx_dE_pack_job(const float* T, const float* lse, const int32_t* ylab, int M, int V, int H, float* scratch,
-                            const float* fwd_part, const int64_t* y, void* out, size_t out_bytes, int* blocks);
-bool b4r_head_rx_combine_foldable(int M, int V, int H);
-int b4r_head_rx_fwd_launch2(const float* T, const float* E, const float* bias, const int64_t* y, int M, int V, int H,
-                            float* scratch, float* dT, float* row_out, float* lse, int32_t* ylab, int only_sweep, hipStream_t stream);
-int b4r_ffn_block_bwd_marked(const b4r_ffn_desc* d, hipStream_t stream, hipEvent_t after_dx);
+// b4r_head32.hip: masked-LM head of a train step without materialised logits (hidden size 64 / 128 / 256, bf16x3 mode)
+bool b4r_head32_hidden_ok(int H);
+int b4r_head32_fwd_slices(int M, int V, int H);
+int64_t b4r_head32_fwd_scratch_floats(int M, int V, int H);
+int64_t b4r_head32_dE_scratch_floats(int M, int V, int H);
+bool b4r_head32_combine_foldable(int M, int V, int H);
+int b4r_head32_fwd_launch(const float* T, const float* E, const float* bias, const int64_t* y, int M, int V, int H, float* scratch,
+                          float* dT, float* row_out, float* lse, int32_t* ylab, int only_sweep, hipStream_t stream);
+int b4r_head32_dE_pack_job(const float* T, const float* lse, const int32_t* ylab, int M, int V, int H, float* scratch, const float* fwd_part,
+                           const int64_t* y, void* out, size_t out_bytes, int* blocks);
+int b4r_head32_dE_launch(const float* T, const float* E, const float* bias, const float* lse, const int32_t* ylab, int M, int V, int H,
+                         float* scratch, float* dE, float* db, hipStream_t stream, const float* fwd_part, const int64_t* y, int records_ready);
 // b4r_rowops.hip: the last layer's feed-forward half on the masked-LM head's rows (compact [B*P, .] operands)
 int b4r_slot_rows_gather(const float* a, const float* b, const float* s0, const float* s1, const int64_t* pos, int L, int P, int M, int H,
                          float* ac, float* bc, float* s0c, float* s1c, hipStream_t s);
@@ -68,10 +64,6 @@ int64_t b4r_embed_fixed_floats(int64_t V, int H, int hot_rows);
 int b4r_gemm_tn_pair(const b4r_gemm_tn_desc* d0, float* scratch0, const b4r_gemm_tn_desc* d1, float* scratch1, hipStream_t stream);
 bool b4r_attn32_active(int H, int heads, int L);   // b4r_attn_block.hip: the 32-token-tile backward (it can form dWqkv / dbqkv itself)
 int b4r_ce_finalize_launch(const float* row_scratch, int M, b4r_train_state* state, int overwrite, hipStream_t stream);
-int b4r_attn_bwd_streams(const float* qkv, const int64_t* input_mask, const float* ctx, const float* lse, const float* dctx,
-                         int32_t B, int32_t L, int32_t heads, float qscale, float* dqkv, const uint32_t* rng,
-                         uint32_t drop_stream, float drop_rate, const uint32_t* keep_bits, hipStream_t stream,
-                         hipStream_t stream_dkv);
 int b4r_zero2(float* a, int64_t na, float* b, int64_t nb, hipStream_t stream, float* tail = nullptr, b4r_train_state* state = nullptr,
               const float* fin_rows = nullptr, int fin_M = 0, const void* rider = nullptr, int rider_blocks = 0);
 int b4r_optimizer_fused(const b4r_adamw_config* hp, float* params, const float* grads, float* adam_m, float* adam_v, int64_t n,
@@ -319,12 +311,12 @@ WsLayout make_ws_layout(const b4r_model_config& c, int B, int L, int P) {
     add(b4r_gemm_tn_scratch_floats((int)M, (int)H, (int)H));
     add(b4r_ln_bwd_scratch_floats((int)M, (int)H));
     add((int64_t)mlm_dt_splits(M, H, V) * M * H);
-    if (b4r_head_rx_hidden_ok((int)H)) add(b4r_head_rx_dE_scratch_floats((int)M, (int)V, (int)H));
+    if (b4r_head32_hidden_ok((int)H)) add(b4r_head32_dE_scratch_floats((int)M, (int)V, (int)H));
   }
   add((int64_t)b4r_cdiv(B, 16) * L * H);  // position-table gradient partials
   // the fused head's forward partials live at the start of the scratch region; a train step's backward merges them itself (its dE
   // launch), so they stay reserved in front of the backward's own regions
-  if (M > 0 && b4r_head_rx_hidden_ok((int)H)) add(b4r_head_rx_fwd_scratch_floats((int)M, (int)V, (int)H));
+  if (M > 0 && b4r_head32_hidden_ok((int)H)) add(b4r_head32_fwd_scratch_floats((int)M, (int)V, (int)H));
   w.scratch = take(s); w.scratch_floats = s;
   w.total = off;
   return w;
@@ -358,17 +350,16 @@ int gemm(const float* A, int lda, const float* Bm, int ldb, float* C, int ldc, i
 }
 
 // dense + bias + dropout + residual (-> z) + LayerNorm (-> y, mean, rstd): one launch where b4r_gemm_ln_supported (hidden
-// size 64 in the bf16x3 mode), else the product with B4R_EPI_BIAS_DROP_RES followed by b4r_ln_fwd.  B4R_FUSE_LN=0: always two.
+// size 64 in the bf16x3 mode), else the product with B4R_EPI_BIAS_DROP_RES followed by b4r_ln_fwd.
 int dense_res_ln(const float* A, int lda, const float* W, float* z, float* y, float* mean, float* rstd, int M, int H, int K,
                  const float* bias, const float* R, const float* gamma, const float* beta, float eps, const uint32_t* rng,
                  uint32_t stream_id, float rate, hipStream_t s) {
-  static const bool fuse = !(getenv("B4R_FUSE_LN") && atoi(getenv("B4R_FUSE_LN")) == 0);
   b4r_gemm_desc d{};
   d.A = A; d.lda = lda; d.B = W; d.ldb = H; d.C = z; d.ldc = H; d.M = M; d.N = H; d.K = K;
   d.epilogue = B4R_EPI_BIAS_DROP_RES_LN; d.bias = bias; d.C2 = y; d.ldc2 = H; d.R = R; d.ldr = H; d.qscale = 1.f;
   d.rng = rng; d.drop_stream = stream_id; d.drop_rate = rate; d.c_pad_scratch = 1;
   d.ln_gamma = gamma; d.ln_beta = beta; d.ln_mean = mean; d.ln_rstd = rstd; d.ln_eps = eps;
-  if (fuse && b4r_gemm_ln_supported(&d)) return b4r_gemm_f32(&d, (b4r_stream_t)s);
+  if (b4r_gemm_ln_supported(&d)) return b4r_gemm_f32(&d, (b4r_stream_t)s);
   d.epilogue = B4R_EPI_BIAS_DROP_RES; d.C2 = nullptr; d.ldc2 = 0;
   RC(b4r_gemm_f32(&d, (b4r_stream_t)s));
   return b4r_ln_fwd(z, M, H, gamma, beta, eps, y, mean, rstd, (b4r_stream_t)s);
@@ -381,7 +372,6 @@ int dgrad_ln_bwd(const float* A, int lda, const float* W, int K, const float* R,
                  const float* mean, const float* rstd, const float* gamma, float* dgamma, float* dbeta, float* scratch,
                  hipStream_t s, const int64_t* ids = nullptr, const float* table = nullptr, const float* pos_table = nullptr,
                  int L = 1, int V = 1, const uint32_t* rng = nullptr, uint32_t drop_stream = 0, float drop_rate = 0.f) {
-  static const bool fuse = !(getenv("B4R_FUSE_LN") && atoi(getenv("B4R_FUSE_LN")) == 0);
   b4r_gemm_desc d{};
   d.A = A; d.lda = lda; d.B = W; d.ldb = K; d.C = dz; d.ldc = H; d.M = M; d.N = H; d.K = K; d.b_is_nk = 1;
   d.epilogue = B4R_EPI_ADD_RES_LN_BWD; d.R = R; d.ldr = H; d.qscale = 1.f; d.c_pad_scratch = 1;
@@ -389,49 +379,37 @@ int dgrad_ln_bwd(const float* A, int lda, const float* W, int K, const float* R,
   d.ln_z = z; d.ln_ldz = H; d.ln_dgamma = dgamma; d.ln_dbeta = dbeta;
   d.ln_ids = ids; d.ln_table = table; d.ln_pos = pos_table; d.ln_L = L; d.ln_V = V;
   d.rng = rng; d.drop_stream = drop_stream; d.drop_rate = drop_rate;
-  if (fuse && dbeta == dgamma + 64 && b4r_gemm_ln_supported(&d)) return b4r_gemm_f32(&d, (b4r_stream_t)s);
+  if (dbeta == dgamma + 64 && b4r_gemm_ln_supported(&d)) return b4r_gemm_f32(&d, (b4r_stream_t)s);
   d.epilogue = B4R_EPI_ADD_RES; d.C2 = nullptr; d.rng = nullptr; d.drop_rate = 0.f;
   RC(b4r_gemm_f32(&d, (b4r_stream_t)s));
   return b4r_ln_bwd_launch(dz, z, mean, rstd, gamma, M, H, dz, dgamma, dbeta, scratch, ids, table, pos_table, L, V,
                            b4r_make_drop(rng, drop_stream, drop_rate, 1), s, nullptr);
 }
 
-// the feed-forward half of a layer as one launch forward / two backward (b4r_ffn_rx.hip); B4R_FFN_FUSED=0: the separate
-// dense launches of round 1 (kept for A/B timing and for shapes / modes the fused block does not cover)
+// the feed-forward half of a layer as one launch forward / two backward (b4r_ffn_rx.hip); else the separate dense launches of
+// round 1 (for the shapes / modes the fused block does not cover)
 bool ffn_fused(const b4r_model_config* c) {
-  static const bool on = !(getenv("B4R_FFN_FUSED") && atoi(getenv("B4R_FFN_FUSED")) == 0);
-  return on && b4r_ffn_block_supported(c->hidden_size, c->inner_dim) != 0;
+  return b4r_ffn_block_supported(c->hidden_size, c->inner_dim) != 0;
 }
 
-// the attention half of a layer as one launch forward (b4r_attn_block.hip); B4R_ATTN_FUSED=0: the three launches of round 1
+// the attention half of a layer as one launch forward (b4r_attn_block.hip); else the three launches of round 1
 bool attn_fused(const b4r_model_config* c, int L) {
-  static const bool on = !(getenv("B4R_ATTN_FUSED") && atoi(getenv("B4R_ATTN_FUSED")) == 0);
-  return on && b4r_attn_block_supported(c->hidden_size, c->num_heads, L) != 0;
+  return b4r_attn_block_supported(c->hidden_size, c->num_heads, L) != 0;
 }
 
-// ... and one launch backward (b4r_attn_block_bwd; then the forward need not store qkv); B4R_ATTN_BWD_FUSED=0: round 1's kernels
+// ... and one launch backward (b4r_attn_block_bwd; then the forward need not store qkv); else round 1's kernels
 bool attn_bwd_fused(const b4r_model_config* c, int L) {
-  static const bool on = !(getenv("B4R_ATTN_BWD_FUSED") && atoi(getenv("B4R_ATTN_BWD_FUSED")) == 0);
-  return on && attn_fused(c, L) && b4r_attn_block_bwd_supported(c->hidden_size, c->num_heads, L) != 0;
-}
-
-// x1 = LayerNorm(z1) is not stored between the two fused halves of a layer: the feed-forward kernels form it on load (B4R_X1_ON_LOAD=0:
-// the attention block writes it as before)
-bool x1_on_load() {
-  static const bool on = !(getenv("B4R_X1_ON_LOAD") && atoi(getenv("B4R_X1_ON_LOAD")) == 0);
-  return on;
+  return attn_fused(c, L) && b4r_attn_block_bwd_supported(c->hidden_size, c->num_heads, L) != 0;
 }
 
 // B4R_FLAG_HEAD_ROWS_ONLY is honoured where the last layer's feed-forward half runs as the fused block and the row list fits
 bool head_rows_ok(const b4r_model_config* c, const b4r_batch* b) {
-  static const bool on = !(getenv("B4R_HEAD_ROWS") && atoi(getenv("B4R_HEAD_ROWS")) == 0);
-  return on && ffn_fused(c) && b->masked_lm_positions && b->masked_lm_ids && b->P > 0;
+  return ffn_fused(c) && b->masked_lm_positions && b->masked_lm_ids && b->P > 0;
 }
 // ... and, where that half runs as dense products (every hidden size but 64), with those products on compact [B*P, .] operands: the
 // rows are gathered first (b4r_slot_rows_*).  Worth it when the head reads a minority of the rows (P = L / 5 at the benchmark shapes).
 bool head_rows_dense_ok(const b4r_model_config* c, const b4r_batch* b) {
-  static const bool on = !(getenv("B4R_HEAD_ROWS_DENSE") && atoi(getenv("B4R_HEAD_ROWS_DENSE")) == 0);
-  return on && !ffn_fused(c) && c->num_layers > 0 && b->masked_lm_positions && b->masked_lm_ids && b->P > 0 && 2 * b->P <= b->L &&
+  return !ffn_fused(c) && c->num_layers > 0 && b->masked_lm_positions && b->masked_lm_ids && b->P > 0 && 2 * b->P <= b->L &&
          c->hidden_size % 32 == 0 && c->inner_dim >= 3 * c->hidden_size + 8;
 }
 // The compact operands of that mode live inside the last layer's own dense regions (an encoder-only forward has nothing else,
@@ -439,10 +417,9 @@ bool head_rows_dense_ok(const b4r_model_config* c, const b4r_batch* b) {
 // (2 M <= N, 3 H + 8 <= I): x1 rows, z1 rows, the second product's output, mean1, rstd1.
 // The one-launch feed-forward pair of b4r_ffn32w.hip inside a TRAIN step (it then also writes f and the pre-activation): measured per
 // dense layer at N = 51 200 -- hidden 128: forward 102 us against 121 (two tile products + LayerNorm), backward 103 against 124; hidden
-// 256: 323 against 320 and 403 against 313.  So: hidden 128 only.  B4R_FFN32W_TRAIN = 0 never, 2 both sizes.
+// 256: 323 against 320 and 403 against 313.  So: hidden 128 only.
 bool ffn32w_train_ok(const b4r_model_config* c) {
-  static const int lv = getenv("B4R_FFN32W_TRAIN") ? atoi(getenv("B4R_FFN32W_TRAIN")) : 1;
-  return lv > 0 && b4r_ffn32w_supported(c->hidden_size, c->inner_dim) && (c->hidden_size == 128 || lv > 1);
+  return c->hidden_size == 128 && b4r_ffn32w_supported(c->hidden_size, c->inner_dim);
 }
 // ... and the attention half of that layer with the slots as its only queries (hidden sizes on the tile products; P <= 64)
 bool slotq_layer(const b4r_model_config* c, const b4r_batch* b, uint32_t flags, int layer) {
@@ -457,72 +434,12 @@ CompactRows compact_rows(const WsLayout& w, int layer, int64_t M, int64_t H, int
   return c;
 }
 
-// pair kernels (input gradient inside the weight-gradient kernel, b4r_gemm_tn_desc.dgrad_*): B4R_PAIR bit 0 = the 64 x 64 layers
-// (attention output, masked-LM transform), bit 1 = the FFN output layer with its GELU' tail
-int pair_level() {
-  static const int lv = getenv("B4R_PAIR") ? atoi(getenv("B4R_PAIR")) : 3;
-  return lv;
-}
-
-// ---- a second stream for the branches of the backward pass that nothing downstream waits for -------------------------
-// (weight-gradient products, the dE sweep of the fused head, dK/dV next to dQ).  The idea: every kernel of this workload
-// leaves part of the chip idle at its start and tail, a concurrent independent kernel could fill those holes.  MEASURED
-// (ML-1M step, one MI355X, same box, ms per step): single stream 0.943 | head dE only 0.958 | + dK/dV 0.970 | + all weight
-// gradients 0.990 -- the event hand-offs between streams cost more than the overlap returns, and the concurrent kernels
-// mostly take each other's CUs.  So it is OFF by default; B4R_SIDE_STREAM=1|2|3 re-enables the three levels.
-struct SideStream {
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[64];
-  int next = 0, device = -1;
-};
-thread_local SideStream g_side;
-
-int side_level() {   // 0: off; 1: everything independent; 2: head dE + dK/dV; 3: head dE only; 4: dWo / dWqkv of the fused-block path
-  static const int lv = getenv("B4R_SIDE_STREAM") ? atoi(getenv("B4R_SIDE_STREAM")) : 0;
-  return lv;
-}
-
-hipStream_t side_stream() {
-  if (side_level() == 0) return nullptr;
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  if (g_side.stream == nullptr || g_side.device != dev) {
-    if (hipStreamCreateWithFlags(&g_side.stream, hipStreamNonBlocking) != hipSuccess) { g_side.stream = nullptr; return nullptr; }
-    for (int i = 0; i < 64; ++i)
-      if (hipEventCreateWithFlags(&g_side.ev[i], hipEventDisableTiming) != hipSuccess) { g_side.stream = nullptr; return nullptr; }
-    g_side.device = dev;
-  }
-  return g_side.stream;
-}
-
-// work enqueued on `to` after this call starts only when everything enqueued on `from` so far has finished
-int order_after(hipStream_t from, hipStream_t to) {
-  if (from == to) return B4R_OK;
-  hipEvent_t e = g_side.ev[(g_side.next++) & 63];
-  if (hipEventRecord(e, from) != hipSuccess || hipStreamWaitEvent(to, e, 0) != hipSuccess) {
-    b4r_set_error("b4r_backward: stream ordering failed");
-    return B4R_E_HIP;
-  }
-  return B4R_OK;
-}
-
 b4r_gemm_tn_desc tn_desc(const float* A, int lda, const float* Bm, int ldb, float* out, int ldo, int R, int Mo, int No, float* colsum,
                          const uint32_t* rng, uint32_t stream_id, float rate, int b_dropout) {
   b4r_gemm_tn_desc d{};
   d.A = A; d.lda = lda; d.B = Bm; d.ldb = ldb; d.out = out; d.ldo = ldo; d.R = R; d.Mo = Mo; d.No = No;
   d.colsum = colsum; d.rng = rng; d.drop_stream = stream_id; d.drop_rate = rate; d.b_dropout = b_dropout; d.accumulate = 0;
   return d;
-}
-
-hipEvent_t side_event() { return g_side.ev[(g_side.next++) & 63]; }
-int side_mark(hipStream_t on, hipEvent_t* e) {
-  *e = side_event();
-  if (hipEventRecord(*e, on) != hipSuccess) { b4r_set_error("b4r_backward: event record failed"); return B4R_E_HIP; }
-  return B4R_OK;
-}
-int side_wait(hipStream_t s, hipEvent_t e) {
-  if (e != nullptr && hipStreamWaitEvent(s, e, 0) != hipSuccess) { b4r_set_error("b4r_backward: stream wait failed"); return B4R_E_HIP; }
-  return B4R_OK;
 }
 
 int gemm_tn(const float* A, int lda, const float* Bm, int ldb, float* out, int ldo, int R, int Mo, int No, float* colsum,
@@ -654,7 +571,7 @@ extern "C" int b4r_workspace_region(const b4r_model_config* cfg, int32_t B, int3
 
 // ===============================================================================================================
 extern "C" int32_t b4r_fused_head_supported(const b4r_model_config* cfg) {
-  return (cfg != nullptr && b4r_head_rx_hidden_ok(cfg->hidden_size) && b4r_get_gemm_mode() == B4R_GEMM_BF16X3) ? 1 : 0;
+  return (cfg != nullptr && b4r_head32_hidden_ok(cfg->hidden_size) && b4r_get_gemm_mode() == B4R_GEMM_BF16X3) ? 1 : 0;
 }
 
 // The public entry points take the documented flags only: the internal bits (B4R_FLAG_*_INTERNAL) couple a forward and a backward
@@ -700,8 +617,7 @@ static int forward_impl(const b4r_model_config* cfg, const b4r_batch* batch, con
   const float qscale = 1.0f / sqrtf(32.0f);
 
   // the embedding stage: inside the first layer's attention block where that runs fused, else a launch of its own
-  static const bool emb_in_block = !(getenv("B4R_EMB_FUSED") && atoi(getenv("B4R_EMB_FUSED")) == 0);
-  const bool emb_fused = emb_in_block && attn_fused(cfg, L) && cfg->num_layers > 0;
+  const bool emb_fused = attn_fused(cfg, L) && cfg->num_layers > 0;
   if (!emb_fused)
     RC(b4r_embed_ln_fwd(batch->input_word_ids, B, L, params + pl.word_emb, V, params + pl.pos_emb, params + pl.emb_ln_g,
                         params + pl.emb_ln_b, H, cfg->ln_eps, ws + w.x0, ws + w.mean0, ws + w.rstd0, rng, od, stream));
@@ -721,7 +637,7 @@ static int forward_impl(const b4r_model_config* cfg, const b4r_batch* batch, con
       ad.qkv = attn_bwd_fused(cfg, L) ? nullptr : ws + w.qkv[i];   // only round 1's backward kernels read it
       ad.ctx = ws + w.ctx[i]; ad.lse = ws + w.lse[i]; ad.keep_bits = reinterpret_cast<uint32_t*>(ws + w.keep[i]);
       ad.z1 = ws + w.z1[i]; ad.mean1 = ws + w.mean1[i]; ad.rstd1 = ws + w.rstd1[i];
-      ad.x1 = (layer_fused && x1_on_load()) ? nullptr : ws + w.x1[i];   // the fused feed-forward half forms x1 from z1 itself
+      ad.x1 = layer_fused ? nullptr : ws + w.x1[i];   // the fused feed-forward half forms x1 from z1 itself
       if (head_rows && i == cfg->num_layers - 1) {   // nothing but the head's rows leaves the last layer: only those queries are swept
         ad.out_slot_positions = batch->masked_lm_positions; ad.out_slots = batch->P;
       }
@@ -760,7 +676,7 @@ static int forward_impl(const b4r_model_config* cfg, const b4r_batch* batch, con
     }
     }
     if (ffn_fused(cfg)) {
-      fd.N = N; fd.H = H; fd.I = I; fd.x1 = (layer_fused && x1_on_load()) ? nullptr : ws + w.x1[i];
+      fd.N = N; fd.H = H; fd.I = I; fd.x1 = layer_fused ? nullptr : ws + w.x1[i];
       fd.z1 = ws + w.z1[i]; fd.mean1 = ws + w.mean1[i]; fd.rstd1 = ws + w.rstd1[i];
       fd.ln1_gamma = params + pl.ln1_g[i]; fd.ln1_beta = params + pl.ln1_b[i];
       fd.W1 = params + pl.w1[i]; fd.b1 = params + pl.b1[i]; fd.W2 = params + pl.w2[i]; fd.b2 = params + pl.b2[i];
@@ -815,7 +731,6 @@ static int forward_impl(const b4r_model_config* cfg, const b4r_batch* batch, con
   if (P > 0 && !(flags & B4R_FLAG_ENCODER_ONLY)) {
     // tfm MaskedLM: gather -> dense(gelu) -> LayerNorm -> . E^T + bias
     {   // gather + dense(gelu) + LayerNorm: one launch where the LayerNorm tail applies (hidden size 64), else three
-      static const bool fuse = !(getenv("B4R_FUSE_LN") && atoi(getenv("B4R_FUSE_LN")) == 0);
       b4r_gemm_desc d{};
       d.A = x; d.lda = H; d.B = params + pl.wd; d.ldb = H; d.C = ws + w.u; d.ldc = H; d.M = M; d.N = H; d.K = H;
       d.a_gather_idx = batch->masked_lm_positions; d.a_gather_add_per = L; d.a_gather_per = P;
@@ -824,7 +739,7 @@ static int forward_impl(const b4r_model_config* cfg, const b4r_batch* batch, con
       d.qscale = 1.f; d.c_pad_scratch = 1;
       d.ln_gamma = params + pl.lnm_g; d.ln_beta = params + pl.lnm_b; d.ln_mean = ws + w.meanm; d.ln_rstd = ws + w.rstdm;
       d.ln_eps = cfg->ln_eps;
-      if (fuse && b4r_gemm_ln_supported(&d)) {
+      if (b4r_gemm_ln_supported(&d)) {
         RC(b4r_gemm_f32(&d, (b4r_stream_t)s));
       } else {
         RC(b4r_gather_rows(x, H, batch->masked_lm_positions, L, P, M, H, ws + w.gath, stream));
@@ -838,9 +753,9 @@ static int forward_impl(const b4r_model_config* cfg, const b4r_batch* batch, con
       // no [M,V] tensor: loss rows, log-sum-exp and d loss_sum / d T straight from T, E and the bias
       B4R_CHECK_ARG(b4r_fused_head_supported(cfg), B4R_E_BADARG, "b4r_forward: B4R_FLAG_FUSED_HEAD needs hidden size 64 / 128 / 256 and the bf16x3 mode");
       B4R_CHECK_ARG(batch->masked_lm_ids != nullptr, B4R_E_BADARG, "b4r_forward: B4R_FLAG_FUSED_HEAD needs masked_lm_ids");
-      RC(b4r_head_rx_fwd_launch2(ws + w.t, params + pl.word_emb, params + pl.out_bias, batch->masked_lm_ids, M, V, H, ws + w.scratch,
-                                 ws + w.dt, ws + w.rowsc, ws + w.head_lse, reinterpret_cast<int32_t*>(ws + w.head_ylab),
-                                 (flags & B4R_FLAG_DEFER_COMBINE_INTERNAL) ? 1 : 0, s));
+      RC(b4r_head32_fwd_launch(ws + w.t, params + pl.word_emb, params + pl.out_bias, batch->masked_lm_ids, M, V, H, ws + w.scratch,
+                               ws + w.dt, ws + w.rowsc, ws + w.head_lse, reinterpret_cast<int32_t*>(ws + w.head_ylab),
+                               (flags & B4R_FLAG_DEFER_COMBINE_INTERNAL) ? 1 : 0, s));
     } else {
       RC(gemm(ws + w.t, H, params + pl.word_emb, H, ws + w.logits, (int)w.Vp, M, V, H, 1, B4R_EPI_BIAS, params + pl.out_bias,
               nullptr, 0, nullptr, 0, 1.f, 0, nullptr, 0, 0.f, 0, s));
@@ -923,41 +838,33 @@ static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, co
                 "b4r_backward: B4R_FLAG_LOSS_SUMS needs B4R_FLAG_FUSED_HEAD, the state and masked_lm_ids");
   // row-list mode with the 32-token-tile attention backward: that kernel is told which rows of the last layer's dz1 exist and never
   // reads the others -- db need not be cleared (13 MB per step at ML-1M)
-  const bool sparse_dz1 = head_rows && ffn_fused(cfg) && attn_bwd_fused(cfg, L) && b4r_attn32_active(H, cfg->num_heads, L) &&
-                          side_level() != 4;
+  const bool sparse_dz1 = head_rows && ffn_fused(cfg) && attn_bwd_fused(cfg, L) && b4r_attn32_active(H, cfg->num_heads, L);
   // the scratch regions of the fused head are fixed here already: the records dE sweeps (the transform rows as fp16 images, -lse, labels)
   // are formed by extra workgroups of the clearing launch (b4r_zero2's rider) instead of a launch of their own
   const bool fused_head_early = (flags & B4R_FLAG_FUSED_HEAD) != 0 && b4r_fused_head_supported(cfg);
-  const float* fwd_part_early = (fused_head_early && defer_combine) ? take(b4r_head_rx_fwd_scratch_floats(M, V, H)) : nullptr;   // = ws + w.scratch
-  float* dE_scratch = fused_head_early ? take(b4r_head_rx_dE_scratch_floats(M, V, H)) : nullptr;
+  const float* fwd_part_early = (fused_head_early && defer_combine) ? take(b4r_head32_fwd_scratch_floats(M, V, H)) : nullptr;   // = ws + w.scratch
+  float* dE_scratch = fused_head_early ? take(b4r_head32_dE_scratch_floats(M, V, H)) : nullptr;
   alignas(8) char rider[128];
   int rider_blocks = 0;
   if (fused_head_early)
-    RC(b4r_head_rx_dE_pack_job(ws + w.t, ws + w.head_lse, reinterpret_cast<const int32_t*>(ws + w.head_ylab), M, V, H, dE_scratch,
-                               fwd_part_early, batch->masked_lm_ids, rider, sizeof(rider), &rider_blocks));
+    RC(b4r_head32_dE_pack_job(ws + w.t, ws + w.head_lse, reinterpret_cast<const int32_t*>(ws + w.head_ylab), M, V, H, dE_scratch,
+                              fwd_part_early, batch->masked_lm_ids, rider, sizeof(rider), &rider_blocks));
   RC(b4r_zero2(grads, pl.total, ws + (head_rows ? w.hot : w.dx), head_rows ? (sparse_dz1 ? w.db - w.hot : w.da - w.hot) : w.db - w.dx, s,
                ((flags & B4R_FLAG_GRAD_TAIL) && !defer_combine) ? grads + pl.total : nullptr, state,
                (loss_sums && !defer_combine) ? ws + w.rowsc : nullptr, (int)w.M, rider_blocks > 0 ? rider : nullptr, rider_blocks));
 
   // ---- masked-LM head (logits buffer holds d loss_sum / d logits, pad columns zero) --------------------------------
-  // s2: independent branches (see SideStream); it is ordered after the memsets here, joined before every reuse of a buffer
-  // a branch reads (top of each layer) and before the final reductions
-  hipStream_t s2 = side_stream();
-  if (s2 == nullptr) s2 = s;
-  hipStream_t s_tn = side_level() == 1 ? s2 : s;                          // weight-gradient products
-  hipStream_t s_kv = (side_level() == 1 || side_level() == 2) ? s2 : s;  // dK/dV
-  RC(order_after(s, s2));
   float* dlog = ws + w.logits;
   const bool fused_head = (flags & B4R_FLAG_FUSED_HEAD) != 0;
   const float* fwd_part = nullptr;
   B4R_CHECK_ARG(!fused_head || b4r_fused_head_supported(cfg), B4R_E_BADARG, "b4r_backward: B4R_FLAG_FUSED_HEAD needs hidden size 64 / 128 / 256 and the bf16x3 mode");
   if (fused_head) {
     // dT came with the forward -- or (defer_combine) the forward left its per-slice partials: dE forms the lse it needs from them, the
-    // transform's LayerNorm backward below merges them into dT as it reads it; dE / d output_bias recompute the logit tiles (b4r_head_rx.hip)
+    // transform's LayerNorm backward below merges them into dT as it reads it; dE / d output_bias recompute the logit tiles (b4r_head32.hip)
     fwd_part = fwd_part_early;
-    RC(b4r_head_rx_dE_launch(ws + w.t, params + pl.word_emb, params + pl.out_bias, ws + w.head_lse,
-                             reinterpret_cast<const int32_t*>(ws + w.head_ylab), M, V, H, dE_scratch,
-                             grads + pl.word_emb, grads + pl.out_bias, s2, fwd_part, batch->masked_lm_ids, rider_blocks > 0 ? 1 : 0));
+    RC(b4r_head32_dE_launch(ws + w.t, params + pl.word_emb, params + pl.out_bias, ws + w.head_lse,
+                            reinterpret_cast<const int32_t*>(ws + w.head_ylab), M, V, H, dE_scratch,
+                            grads + pl.word_emb, grads + pl.out_bias, s, fwd_part, batch->masked_lm_ids, rider_blocks > 0 ? 1 : 0));
   } else {
   // dT = dlogits . E   (K = V is long and the output small: split K so that the whole chip streams dlogits)
   {
@@ -974,7 +881,7 @@ static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, co
              take(b4r_gemm_tn_scratch_floats(M, V, H)), s));
   }
   // LayerNorm of the transform (with the deferred merge: dT, the loss rows, lse and labels are formed here, from the forward's partials)
-  const B4rHeadMerge merge{fwd_part, fwd_part ? b4r_head_rx_fwd_slices(M, V, H) : 0, M, V, ws + w.t, params + pl.word_emb,
+  const B4rHeadMerge merge{fwd_part, fwd_part ? b4r_head32_fwd_slices(M, V, H) : 0, M, V, ws + w.t, params + pl.word_emb,
                            params + pl.out_bias, batch->masked_lm_ids, ws + w.rowsc, ws + w.head_lse,
                            reinterpret_cast<int32_t*>(ws + w.head_ylab)};
   RC(b4r_ln_bwd_launch(ws + w.dt, ws + w.u, ws + w.meanm, ws + w.rstdm, params + pl.lnm_g, M, H, ws + w.dt, grads + pl.lnm_g,
@@ -986,12 +893,11 @@ static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, co
     d.A = ws + w.gath; d.lda = H; d.B = ws + w.dt; d.ldb = H; d.out = grads + pl.wd; d.ldo = H; d.R = M; d.Mo = H; d.No = H;
     d.colsum = grads + pl.bd;
     d.dgrad_w = params + pl.wd; d.dgrad_ldw = H; d.dgrad_out = ws + w.dg; d.dgrad_ldo = H;
-    if ((pair_level() & 1) && b4r_gemm_tn_dgrad_supported(&d)) {
+    if (b4r_gemm_tn_dgrad_supported(&d)) {
       RC(b4r_gemm_tn_f32(&d, take(b4r_gemm_tn_scratch_floats(M, H, H)), (b4r_stream_t)s));
     } else {
-      RC(order_after(s, s_tn));
       RC(gemm_tn(ws + w.gath, H, ws + w.dt, H, grads + pl.wd, H, M, H, H, grads + pl.bd, nullptr, nullptr, 0, 0.f, 0,
-                 take(b4r_gemm_tn_scratch_floats(M, H, H)), s_tn));
+                 take(b4r_gemm_tn_scratch_floats(M, H, H)), s));
       RC(gemm(ws + w.dt, H, params + pl.wd, H, ws + w.dg, H, M, H, H, 1, B4R_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, 1.f, 0,
               nullptr, 0, 0.f, 0, s));
     }
@@ -1003,12 +909,8 @@ static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, co
 
   // ---- encoder layers, last to first ---------------------------------------------------------------------------------
   const int64_t ln_scratch = std::max(b4r_ln_bwd_scratch_floats(N, H), b4r_gemm_ln_bwd_partial_floats(N));
-  const bool side4 = side_level() == 4 && s2 != s && ffn_fused(cfg) && attn_bwd_fused(cfg, L);
-  hipEvent_t ev_dx = nullptr, ev_wo = nullptr, ev_wqkv = nullptr;
   for (int i = cfg->num_layers - 1; i >= 0; --i) {
     const float* x_in = (i == 0) ? ws + w.x0 : ws + w.x2[i - 1];
-    RC(order_after(s_tn, s));   // the branches of the previous layer still read da / df / db / dqkv, which this layer rewrites
-    if (side4) RC(side_wait(s, ev_wo));   // dWo of the layer above reads db, which this layer's feed-forward backward rewrites
     float* wo_scratch_of_layer = nullptr;
     // output LayerNorm (for every layer but the last its backward rode on the QKV input-gradient product of layer i + 1)
     const bool rows_here = head_rows && i == cfg->num_layers - 1;
@@ -1020,7 +922,7 @@ static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, co
       // the [N, inner] pre-activation is recomputed from x1 inside the two kernels
       b4r_ffn_desc fd{};
       fd.N = N; fd.H = H; fd.I = I;
-      fd.x1 = (attn_fused(cfg, L) && x1_on_load()) ? nullptr : ws + w.x1[i];   // as the forward of this step left it
+      fd.x1 = attn_fused(cfg, L) ? nullptr : ws + w.x1[i];   // as the forward of this step left it
       fd.W1 = params + pl.w1[i]; fd.b1 = params + pl.b1[i]; fd.W2 = params + pl.w2[i]; fd.b2 = params + pl.b2[i];
       fd.rng = od > 0.f ? rng : nullptr; fd.drop_stream = B4R_STREAM_FFN_OUT(i); fd.drop_rate = od;
       fd.dz2 = ws + w.da; fd.z1 = ws + w.z1[i]; fd.mean1 = ws + w.mean1[i]; fd.rstd1 = ws + w.rstd1[i];
@@ -1035,12 +937,7 @@ static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, co
         fd.slot_grad = ws + w.dg; fd.z2 = ws + w.z2[i]; fd.mean2 = ws + w.mean2[i]; fd.rstd2 = ws + w.rstd2[i];
         fd.ln_gamma = params + pl.ln2_g[i]; fd.dln_gamma = grads + pl.ln2_g[i]; fd.dz2_rows = ws + w.dz2c;
       }
-      if (side4) {
-        ev_dx = side_event();
-        RC(b4r_ffn_block_bwd_marked(&fd, s, ev_dx));
-      } else {
-        RC(b4r_ffn_block_bwd(&fd, stream));
-      }
+      RC(b4r_ffn_block_bwd(&fd, stream));
     } else if (rows_here) {
       // the compact form of the chain below: every operand is [M, .], one row per masked-LM slot (slots without a label carry an exactly
       // zero gradient; two labelled slots never share a row).  dz1 (db) was cleared by the opening launch; the compact result is
@@ -1054,14 +951,12 @@ static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, co
         RC(b4r_slot_rows_drop(dz2c, batch->masked_lm_positions, L, P, M, H, b4r_make_drop(rng, B4R_STREAM_FFN_OUT(i), od, 1), dz2d, s));
       RC(gemm(dz2d, H, params + pl.w2[i], H, ws + w.df, I, M, I, H, 1, B4R_EPI_GELU_BWD, nullptr, nullptr, 0, ws + w.fpre[i], I, 1.f, 0,
               nullptr, 0, 0.f, 0, s));
-      RC(order_after(s, s_tn));
       RC(gemm_tn(ws + w.f[i], I, dz2d, H, grads + pl.w2[i], H, M, I, H, grads + pl.b2[i], nullptr, nullptr, 0, 0.f, 0,
-                 take(b4r_gemm_tn_scratch_floats(M, I, H)), s_tn));
+                 take(b4r_gemm_tn_scratch_floats(M, I, H)), s));
       RC(dgrad_ln_bwd(ws + w.df, I, params + pl.w1[i], I, dz2c, ws + w.dz2c, M, H, ws + cr.z1c, ws + cr.mean1c, ws + cr.rstd1c,
                       params + pl.ln1_g[i], grads + pl.ln1_g[i], grads + pl.ln1_b[i], take(ln_scratch), s));
-      RC(order_after(s, s_tn));
       RC(gemm_tn(ws + cr.x1c, H, ws + w.df, I, grads + pl.w1[i], I, M, H, I, grads + pl.b1[i], nullptr, nullptr, 0, 0.f, 0,
-                 take(b4r_gemm_tn_scratch_floats(M, H, I)), s_tn));
+                 take(b4r_gemm_tn_scratch_floats(M, H, I)), s));
       RC(b4r_scatter_add_rows_impl(ws + w.dz2c, batch->masked_lm_positions, L, P, M, H, ws + w.db, H, batch->masked_lm_ids, N, 0, nullptr, s));
     } else if (ffn32w_train_ok(cfg)) {
       // dF and dX1 (residual included) in one launch from the records the forward packed; LayerNorm1's backward in place; the two
@@ -1072,51 +967,41 @@ static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, co
       fd.rng = od > 0.f ? rng : nullptr; fd.drop_stream = B4R_STREAM_FFN_OUT(i); fd.drop_rate = od;
       fd.dz2 = ws + w.da;
       RC(b4r_ffn32w_bwd(&fd, ws + w.ffnrec[i], ws + w.fpre[i], ws + w.df, ws + w.db, true, s));
-      RC(order_after(s, s_tn));
       RC(gemm_tn(ws + w.f[i], I, ws + w.da, H, grads + pl.w2[i], H, N, I, H, grads + pl.b2[i], nullptr, rng, B4R_STREAM_FFN_OUT(i), od, 1,
-                 take(b4r_gemm_tn_scratch_floats(N, I, H)), s_tn));
+                 take(b4r_gemm_tn_scratch_floats(N, I, H)), s));
       RC(b4r_ln_bwd_launch(ws + w.db, ws + w.z1[i], ws + w.mean1[i], ws + w.rstd1[i], params + pl.ln1_g[i], N, H, ws + w.db,
                            grads + pl.ln1_g[i], grads + pl.ln1_b[i], take(ln_scratch), nullptr, nullptr, nullptr, 1, 1, nodrop, s));
       RC(gemm_tn(ws + w.x1[i], H, ws + w.df, I, grads + pl.w1[i], I, N, H, I, grads + pl.b1[i], nullptr, nullptr, 0, 0.f, 0,
-                 take(b4r_gemm_tn_scratch_floats(N, H, I)), s_tn));
+                 take(b4r_gemm_tn_scratch_floats(N, H, I)), s));
     } else {
     // FFN: dFpre = (dropmask(dz2) . W2^T) * gelu'(fpre) and dW2 = f^T . dropmask(dz2) (+ bias gradient): one pass over dz2
-    // where the pair kernel applies (B4R_PAIR bit 1), else two products
+    // where the pair kernel applies, else two products
     {
       b4r_gemm_tn_desc d{};
       d.A = ws + w.f[i]; d.lda = I; d.B = ws + w.da; d.ldb = H; d.out = grads + pl.w2[i]; d.ldo = H; d.R = N; d.Mo = I; d.No = H;
       d.colsum = grads + pl.b2[i]; d.rng = rng; d.drop_stream = B4R_STREAM_FFN_OUT(i); d.drop_rate = od; d.b_dropout = 1;
       d.dgrad_w = params + pl.w2[i]; d.dgrad_ldw = H; d.dgrad_out = ws + w.df; d.dgrad_ldo = I;
       d.dgrad_gelu_pre = ws + w.fpre[i]; d.dgrad_ldg = I;
-      if ((pair_level() & 2) && b4r_gemm_tn_dgrad_supported(&d)) {
+      if (b4r_gemm_tn_dgrad_supported(&d)) {
         RC(b4r_gemm_tn_f32(&d, take(b4r_gemm_tn_scratch_floats(N, I, H)), (b4r_stream_t)s));
       } else {
         RC(gemm(ws + w.da, H, params + pl.w2[i], H, ws + w.df, I, N, I, H, 1, B4R_EPI_GELU_BWD, nullptr, nullptr, 0, ws + w.fpre[i],
                 I, 1.f, 0, rng, B4R_STREAM_FFN_OUT(i), od, 1, s));
-        RC(order_after(s, s_tn));
         RC(gemm_tn(ws + w.f[i], I, ws + w.da, H, grads + pl.w2[i], H, N, I, H, grads + pl.b2[i], nullptr, rng,
-                   B4R_STREAM_FFN_OUT(i), od, 1, take(b4r_gemm_tn_scratch_floats(N, I, H)), s_tn));
+                   B4R_STREAM_FFN_OUT(i), od, 1, take(b4r_gemm_tn_scratch_floats(N, I, H)), s));
       }
     }
     // dz1 = attention LayerNorm backward of dX1 = dFpre . W1^T + dz2
     RC(dgrad_ln_bwd(ws + w.df, I, params + pl.w1[i], I, ws + w.da, ws + w.db, N, H, ws + w.z1[i], ws + w.mean1[i], ws + w.rstd1[i],
                     params + pl.ln1_g[i], grads + pl.ln1_g[i], grads + pl.ln1_b[i], take(ln_scratch), s));
-    RC(order_after(s, s_tn));
     RC(gemm_tn(ws + w.x1[i], H, ws + w.df, I, grads + pl.w1[i], I, N, H, I, grads + pl.b1[i], nullptr, nullptr, 0, 0.f, 0,
-               take(b4r_gemm_tn_scratch_floats(N, H, I)), s_tn));
+               take(b4r_gemm_tn_scratch_floats(N, H, I)), s));
     }
     const bool dw_folded = attn_bwd_fused(cfg, L) && b4r_attn32_active(H, cfg->num_heads, L);
     if (attn_bwd_fused(cfg, L)) {
       // dWo = ctx^T . dropmask(dz1) (+ bias gradient); then the attention block's backward in one launch: dqkv and, through the
       // LayerNorm in front of this layer, da (for layer 0: through the embedding stage's dropout and LayerNorm)
-      float* wo_scratch = wo_scratch_of_layer = take(b4r_gemm_tn_scratch_floats(N, H, H));
-      if (side4) {
-        RC(side_wait(s2, ev_dx));   // next to the feed-forward weight-gradient kernel, which leaves room on every CU
-        RC(gemm_tn(ws + w.ctx[i], H, ws + w.db, H, grads + pl.wo[i], H, N, H, H, grads + pl.bo[i], nullptr, rng, B4R_STREAM_ATTN_OUT(i),
-                   od, 1, wo_scratch, s2));
-        RC(side_mark(s2, &ev_wo));
-        RC(side_wait(s, ev_wqkv));   // dWqkv of the layer above reads dqkv, which this launch rewrites
-      }
+      wo_scratch_of_layer = take(b4r_gemm_tn_scratch_floats(N, H, H));   // dWo's slabs for the pair launch after the block
       b4r_attn_block_bwd_desc bd{};
       bd.B = B; bd.L = L; bd.H = H; bd.heads = cfg->num_heads;
       bd.x = x_in; bd.dz1 = ws + w.db; bd.ctx = ws + w.ctx[i]; bd.lse = ws + w.lse[i];
@@ -1138,7 +1023,7 @@ static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, co
       if (dw_folded) {   // dWqkv / dbqkv inside the launch: no [N, 3H] round trip, no weight-gradient launch for them
         bd.dqkv = nullptr; bd.dWqkv = grads + pl.wqkv[i]; bd.dbqkv = grads + pl.bqkv[i];
         bd.dw_scratch = take(b4r_attn_block_bwd_dw_scratch_floats(B));
-        if (!side4) { bd.dWo = grads + pl.wo[i]; bd.dbo = grads + pl.bo[i]; }   // ... nor for dWo / dbo
+        bd.dWo = grads + pl.wo[i]; bd.dbo = grads + pl.bo[i];   // ... nor for dWo / dbo
       }
       if (sparse_dz1 && i == cfg->num_layers - 1) {
         bd.dz1_slot_positions = batch->masked_lm_positions; bd.dz1_slot_ids = batch->masked_lm_ids; bd.dz1_slots = batch->P;
@@ -1153,9 +1038,8 @@ static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, co
       float* dctx_c = ws + w.dctx;
       if (od > 0.f)
         RC(b4r_slot_rows_drop(ws + w.dz2c, batch->masked_lm_positions, L, P, M, H, b4r_make_drop(rng, B4R_STREAM_ATTN_OUT(i), od, 1), dz1d, s));
-      RC(order_after(s, s_tn));
       RC(gemm_tn(ws + w.ctx[i], H, dz1d, H, grads + pl.wo[i], H, M, H, H, grads + pl.bo[i], nullptr, nullptr, 0, 0.f, 0,
-                 take(b4r_gemm_tn_scratch_floats(N, H, H)), s_tn));
+                 take(b4r_gemm_tn_scratch_floats(N, H, H)), s));
       RC(gemm(dz1d, H, params + pl.wo[i], H, dctx_c, H, M, H, H, 1, B4R_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, 1.f, 0, nullptr, 0,
               0.f, 0, s));
       RC(b4r_attn32_slotq_bwd_launch(ws + w.qkv[i], batch->input_mask, batch->masked_lm_positions, batch->masked_lm_ids, ws + w.ctx[i],
@@ -1170,25 +1054,20 @@ static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, co
       d.A = ws + w.ctx[i]; d.lda = H; d.B = ws + w.db; d.ldb = H; d.out = grads + pl.wo[i]; d.ldo = H; d.R = N; d.Mo = H; d.No = H;
       d.colsum = grads + pl.bo[i]; d.rng = rng; d.drop_stream = B4R_STREAM_ATTN_OUT(i); d.drop_rate = od; d.b_dropout = 1;
       d.dgrad_w = params + pl.wo[i]; d.dgrad_ldw = H; d.dgrad_out = ws + w.dctx; d.dgrad_ldo = H;
-      if ((pair_level() & 1) && b4r_gemm_tn_dgrad_supported(&d)) {
+      if (b4r_gemm_tn_dgrad_supported(&d)) {
         RC(b4r_gemm_tn_f32(&d, take(b4r_gemm_tn_scratch_floats(N, H, H)), (b4r_stream_t)s));
       } else {
         RC(gemm(ws + w.db, H, params + pl.wo[i], H, ws + w.dctx, H, N, H, H, 1, B4R_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, 1.f,
                 0, rng, B4R_STREAM_ATTN_OUT(i), od, 1, s));
-        RC(order_after(s, s_tn));
         RC(gemm_tn(ws + w.ctx[i], H, ws + w.db, H, grads + pl.wo[i], H, N, H, H, grads + pl.bo[i], nullptr, rng,
-                   B4R_STREAM_ATTN_OUT(i), od, 1, take(b4r_gemm_tn_scratch_floats(N, H, H)), s_tn));
+                   B4R_STREAM_ATTN_OUT(i), od, 1, take(b4r_gemm_tn_scratch_floats(N, H, H)), s));
       }
     }
-    // attention core: dQ on the main stream, dK/dV on the other (both need dctx; the QKV product below needs both)
-    RC(order_after(s, s_kv));
-    RC(b4r_attn_bwd_streams(ws + w.qkv[i], batch->input_mask, ws + w.ctx[i], ws + w.lse[i], ws + w.dctx, B, L, cfg->num_heads,
-                            qscale, ws + w.dqkv, rng, B4R_STREAM_ATTN_PROBS(i), adp,
-                            reinterpret_cast<const uint32_t*>(ws + w.keep[i]), s, s_kv));
-    RC(order_after(s_kv, s));
+    // attention core: dQ, dK, dV
+    RC(b4r_attn_bwd(ws + w.qkv[i], batch->input_mask, ws + w.ctx[i], ws + w.lse[i], ws + w.dctx, B, L, cfg->num_heads, qscale,
+                    ws + w.dqkv, rng, B4R_STREAM_ATTN_PROBS(i), adp, reinterpret_cast<const uint32_t*>(ws + w.keep[i]), stream));
     }
     // QKV projection: dX_in = dqkv . Wqkv^T + dz1, and for i > 0 straight on to layer i-1's output LayerNorm backward (-> da)
-    if (i > 0) RC(order_after(s_tn, s));   // this layer's side branches still read da, which the fused product rewrites
     if (i > 0)
       RC(dgrad_ln_bwd(ws + w.dqkv, 3 * H, params + pl.wqkv[i], 3 * H, ws + w.db, ws + w.da, N, H, ws + w.z2[i - 1],
                       ws + w.mean2[i - 1], ws + w.rstd2[i - 1], params + pl.ln2_g[i - 1], grads + pl.ln2_g[i - 1],
@@ -1199,7 +1078,7 @@ static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, co
                       params + pl.word_emb, params + pl.pos_emb, L, V, rng, B4R_STREAM_EMB, od));
     }
     if (dw_folded) continue;   // every weight gradient of the attention half came out of its backward launch
-    if (!side4 && attn_bwd_fused(cfg, L)) {   // dWo (inputs ready since the feed-forward backward) and dWqkv: one launch
+    if (attn_bwd_fused(cfg, L)) {   // dWo (inputs ready since the feed-forward backward) and dWqkv: one launch
       const b4r_gemm_tn_desc d_wo = tn_desc(ws + w.ctx[i], H, ws + w.db, H, grads + pl.wo[i], H, N, H, H, grads + pl.bo[i], rng,
                                             B4R_STREAM_ATTN_OUT(i), od, 1);
       const b4r_gemm_tn_desc d_wqkv = tn_desc(x_in, H, ws + w.dqkv, 3 * H, grads + pl.wqkv[i], 3 * H, N, H, 3 * H, grads + pl.bqkv[i],
@@ -1207,23 +1086,14 @@ static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, co
       RC(b4r_gemm_tn_pair(&d_wo, wo_scratch_of_layer, &d_wqkv, take(b4r_gemm_tn_scratch_floats(N, H, 3 * H)), s));
       continue;
     }
-    if (side4 && attn_bwd_fused(cfg, L)) {   // next to the feed-forward backward of the layer below
-      RC(order_after(s, s2));
-      RC(gemm_tn(x_in, H, ws + w.dqkv, 3 * H, grads + pl.wqkv[i], 3 * H, N, H, 3 * H, grads + pl.bqkv[i], nullptr, nullptr, 0, 0.f,
-                 0, take(b4r_gemm_tn_scratch_floats(N, H, 3 * H)), s2));
-      RC(side_mark(s2, &ev_wqkv));
-      continue;
-    }
-    RC(order_after(s, s_tn));
     RC(gemm_tn(x_in, H, ws + w.dqkv, 3 * H, grads + pl.wqkv[i], 3 * H, N, H, 3 * H, grads + pl.bqkv[i], nullptr, nullptr, 0, 0.f,
-               0, take(b4r_gemm_tn_scratch_floats(N, H, 3 * H)), s_tn));
+               0, take(b4r_gemm_tn_scratch_floats(N, H, 3 * H)), s));
   }
   // ---- embedding stage: its dropout -> LayerNorm backward ran with layer 0's QKV product (da = d(item row + position row));
   // what remains: word table scatter-add, position table batch sum
   // the item-table scatter sums in 64-bit fixed point beside the float gradient (bitwise reproducible; b4r_rowops.hip), so it
   // need not wait for the head's part of that gradient: ONE launch then sums every queued ordered reduction (weight / bias /
   // LayerNorm gradients, the position table) and adds the fixed-point sums to the item table
-  RC(order_after(s2, s));
   RC(b4r_embed_grads(ws + w.da, batch->input_word_ids, B, L, H, grads + pl.word_emb, V, 3, ws + w.hot /* zeroed at the top */,
                      grads + pl.pos_emb, take((int64_t)b4r_cdiv(B, 16) * L * H), s, defer_combine ? ws + w.rowsc : nullptr, (int)w.M, state,
                      (defer_combine && (flags & B4R_FLAG_GRAD_TAIL)) ? grads + pl.total : nullptr));
@@ -1273,7 +1143,7 @@ extern "C" int b4r_train_step(const b4r_model_config* cfg, const b4r_adamw_confi
                               float* grads, float* adam_m, float* adam_v, void* workspace, int64_t workspace_bytes,
                               b4r_train_state* state, b4r_stream_t stream) {
   const int fused = b4r_fused_head_supported(cfg) ? 1 : 0;   // the train step never needs the logits themselves
-  const int defer = (fused && batch && b4r_head_rx_combine_foldable(batch->B * batch->P, cfg->vocab_size, cfg->hidden_size))
+  const int defer = (fused && batch && b4r_head32_combine_foldable(batch->B * batch->P, cfg->vocab_size, cfg->hidden_size))
                         ? B4R_FLAG_DEFER_COMBINE_INTERNAL : 0;
   // no b4r_state_begin_step launch: the loss reduction overwrites the sums (B4R_LOSS_OVERWRITE)
   // nothing but the loss, the metrics and the gradients leave a train step: the last layer's feed-forward half runs on the rows the

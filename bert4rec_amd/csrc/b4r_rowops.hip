@@ -931,7 +931,7 @@ __global__ __launch_bounds__(256) void zero2_kernel(float* a, int64_t na4, float
     else *reinterpret_cast<f32x4*>(b + 4 * (i - na4)) = z;
   }
 }
-// rider / rider_blocks: an H32PackP job (b4r_head_rx_dE_pack_job) carried by rider_blocks extra workgroups of the launch
+// rider / rider_blocks: an H32PackP job (b4r_head32_dE_pack_job) carried by rider_blocks extra workgroups of the launch
 int b4r_zero2(float* a, int64_t na, float* b, int64_t nb, hipStream_t stream, float* tail, b4r_train_state* state,
               const float* fin_rows, int fin_M, const void* rider, int rider_blocks) {
   B4R_CHECK_ARG(na % 4 == 0 && nb % 4 == 0 && b4r_aligned16(a) && b4r_aligned16(b), B4R_E_ALIGN, "zero2: regions must be 16-byte granular");

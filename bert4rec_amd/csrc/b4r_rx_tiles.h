@@ -1,5 +1,5 @@
 // Shared pieces of the split-precision (bf16x3) kernels that sweep 16-row tiles held in LDS as bf16 hi / lo images
-// (b4r_attn_rx.hip: attention; b4r_head_rx.hip: the masked-LM head).  See b4r_attn_rx.hip for the layout notes.
+// (b4r_attn_rx.hip: attention).  See b4r_attn_rx.hip for the layout notes.
 #pragma once
 #include "b4r_common.h"
 

@@ -89,3 +89,15 @@ def test_null_arguments_return_error_codes():
     d.A = d.B = d.C = 16
     d.M, d.N, d.K, d.lda, d.ldb, d.ldc = 4, 4, 8, 4, 4, 4     # lda < K
     assert lib.b4r_gemm_f32(C.byref(d), None) == -2
+
+
+def test_native_library_reads_no_environment():
+    # a switch read from the environment is fixed for the life of a process, so the suite could only ever run its default: every
+    # path of the library must follow from shapes, modes, flags and ABI setters, which the tests vary
+    csrc = os.path.join(ROOT, "bert4rec_amd", "csrc")
+    readers = []
+    for name in sorted(os.listdir(csrc)):
+        if name.endswith((".hip", ".h", ".cpp", ".cc", ".c")):
+            text = open(os.path.join(csrc, name)).read()
+            readers += [f"{name}:{text.count(chr(10), 0, m.start()) + 1}" for m in re.finditer(r"\b(secure_)?getenv\s*\(", text)]
+    assert not readers, "environment reads in the native library: " + ", ".join(readers)

@@ -23,4 +23,4 @@ def timeit(f, reps=100):
     for _ in range(reps): f()
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) * 1e3 / reps
-print("stagger", os.environ.get("B4R_ATTN_STAGGER", "0"), "forward %.1f us  backward (dq + dkv) %.1f us  ctx checksum %.6f" % (timeit(fwd), timeit(bwd), float(ctx.double().abs().sum())))
+print("forward %.1f us  backward (dq + dkv) %.1f us  ctx checksum %.6f" % (timeit(fwd), timeit(bwd), float(ctx.double().abs().sum())))

@@ -25,8 +25,7 @@ def timeit(f, reps=100):
 fwd(0)
 ref = torch.logsumexp(T.double() @ E.double().t() + b.double(), 1)
 err = float((lse.double() - ref).abs().max())
-print("occ", os.environ.get("B4R_HEAD_OCC", "-"), "fwd_wgs", os.environ.get("B4R_HEAD_FWD_WGS", "-"),
-      "sweep %.1f us  forward %.1f us  backward %.1f us  lse err %.2e" % (timeit(lambda: fwd(1)), timeit(lambda: fwd(0)), timeit(bwd), err))
+print("sweep %.1f us  forward %.1f us  backward %.1f us  lse err %.2e" % (timeit(lambda: fwd(1)), timeit(lambda: fwd(0)), timeit(bwd), err))
 
 # per-launch times of one forward + one backward from the library's event timer
 import ctypes as C

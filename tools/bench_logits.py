@@ -18,7 +18,7 @@ def run(mode, reps=50):
     for _ in range(reps): lib.b4r_gemm_f32(C.byref(d), st)
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) * 1e3 / reps
-print("variant", os.environ.get("B4R_RX_VARIANT", "0"), "target", os.environ.get("B4R_RX_TARGET", "-"), "f32 %.1f us  bf16x3 %.1f us" % (run(0), run(1)))
+print("f32 %.1f us  bf16x3 %.1f us" % (run(0), run(1)))
 # plain fill of the same buffer for reference
 x = torch.empty_like(out)
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
