@@ -347,19 +347,29 @@ __global__ __launch_bounds__(256) void batch_colsum_kernel(const float* x, int B
 // added to the float gradient by the reduce launch that follows (B4rReduceJob::fix).
 // Destination rows [0, hot_rows) (PAD / MASK / UNK: [MASK] alone is ~20 % of all tokens) are summed in LDS first and leave the
 // workgroup once, into slot (workgroup % HOT_SLOTS) -- every workgroup on one row runs an order of magnitude below the atomic rate.
-// Range (round 4): units of 2^-36.  A value of magnitude < 2^18 converts without overflow and a 64-bit sum holds 2^27 in total: with
-// the 2^-44 units of round 3 a row's sum wrapped silently at 2^19 = 5.2e5 -- reachable by the [MASK] row of a diverging run, whose
-// d(loss_SUM) contributions number in the tens of thousands.  Values of magnitude >= 2^-12 are multiples of the unit (fp32 carries 24
-// bits): only smaller contributions are rounded at all, to 7e-12 absolute.  A contribution that is not finite or reaches 2^18 in
-// magnitude -- float atomics would have carried an Inf / NaN into the gradient -- sets a sticky POISON word next to the sums; the
-// closing reduction then stores NaN for every element of the table gradient, so the step's gradient norm, loss checks and the
+// Range: units of 2^-36, so a 64-bit sum holds 2^27 in total (with the 2^-44 units of round 3 a row's sum wrapped silently at 2^19 =
+// 5.2e5 -- reachable by the [MASK] row of a diverging run, whose d(loss_SUM) contributions number in the tens of thousands).  Each
+// element of a row receives at most one contribution per source row, so the launch bounds every contribution by
+// limit = min(2^18, 2^27 / n) (fix_contribution_limit, n = source rows): n values of magnitude < limit sum to less than 2^63 units,
+// and so does every partial sum of them -- LDS pre-sums, atomics, the slots of the closing reduction -- in whatever order they form.
+// Values of magnitude >= 2^-12 are multiples of the unit (fp32 carries 24 bits): only smaller contributions are rounded at all, to
+// 7e-12 absolute.  A contribution that is not finite or reaches the limit in magnitude -- float
+// atomics would have carried an Inf / NaN into the gradient, a larger total would wrap -- sets a sticky POISON word next to the sums;
+// the closing reduction then stores NaN for every element of the table gradient, so the step's gradient norm, loss checks and the
 // optimizer see the failure instead of finite garbage.
 constexpr float FIX_SCALE = 68719476736.f;             // 2^36
 constexpr float FIX_UNSCALE = 1.f / 68719476736.f;
-constexpr float FIX_LIMIT = 262144.f;                  // 2^18
+constexpr float FIX_LIMIT = 262144.f;                  // 2^18: what one contribution may reach at all (its conversion stays exact)
+// the per-contribution limit of a scatter over n source rows: the largest float <= min(2^18, 2^27 / n), so that n * limit <= 2^27
+static float fix_contribution_limit(int64_t n) {
+  if (n <= 512) return FIX_LIMIT;
+  float lim = (float)(134217728.0 / (double)n);
+  while ((double)lim * (double)n > 134217728.0) lim = nextafterf(lim, 0.f);
+  return lim;
+}
 __device__ __forceinline__ void scatter_fixed_rows_body(const float* src, const int64_t* idx, int n, int H, long long* fix,
                                                         int64_t dst_rows, int hot_rows, long long* hot, const int block,
-                                                        const int nblocks, int* poison) {
+                                                        const int nblocks, int* poison, const float limit) {
   extern __shared__ unsigned long long s_hot64[];
   for (int k = threadIdx.x; k < hot_rows * H; k += 256) s_hot64[k] = 0ull;
   if (hot_rows > 0) __syncthreads();
@@ -369,7 +379,7 @@ __device__ __forceinline__ void scatter_fixed_rows_body(const float* src, const 
     const int64_t r = idx[i];
     if (r < 0 || r >= dst_rows) continue;
     const float val = src[(int64_t)i * H + c];
-    if (!(fabsf(val) < FIX_LIMIT)) { atomicOr(poison, 1); continue; }   // (also true for NaN) rare: one atomic per offending element
+    if (!(fabsf(val) < limit)) { atomicOr(poison, 1); continue; }   // (also true for NaN) rare: one atomic per offending element
     const unsigned long long q = (unsigned long long)__float2ll_rn(val * FIX_SCALE);
     if (r < hot_rows) atomicAdd(&s_hot64[(int)r * H + c], q);
     else atomicAdd(reinterpret_cast<unsigned long long*>(fix) + r * H + c, q);
@@ -495,10 +505,10 @@ __device__ __forceinline__ void loss_rows_reduce(const float* rows, int M, float
 __global__ __launch_bounds__(256) void embed_grads_kernel(const float* x, const int64_t* ids, int n, int H, long long* fix,
                                                           int64_t table_rows, int hot_rows, long long* hot, int n_scatter, int B, int L,
                                                           int bchunk, int gx, float* partial, int n_colsum, const float* fin_rows,
-                                                          int fin_M, float* state_f, float* tail) {
+                                                          int fin_M, float* state_f, float* tail, float fix_limit) {
   if ((int)blockIdx.x < n_scatter) {
     scatter_fixed_rows_body(x, ids, n, H, fix, table_rows, hot_rows, hot, (int)blockIdx.x, n_scatter,
-                            reinterpret_cast<int*>(hot + (int64_t)HOT_SLOTS * hot_rows * H));
+                            reinterpret_cast<int*>(hot + (int64_t)HOT_SLOTS * hot_rows * H), fix_limit);
   } else if ((int)blockIdx.x < n_scatter + n_colsum) {
     const int k = (int)blockIdx.x - n_scatter;
     batch_colsum_body(x, B, L, H, bchunk, partial, k % gx, k / gx);
@@ -871,7 +881,7 @@ int b4r_embed_grads(const float* x, const int64_t* ids, int B, int L, int H, flo
   const int gx = b4r_cdiv((int64_t)L * (H / 4), 256);
   hipLaunchKernelGGL(embed_grads_kernel, dim3(n_scatter + gx * S + (fin_rows ? 1 : 0)), dim3(256), (size_t)hot_rows * H * sizeof(long long),
                      stream, x, ids, n, H, fix, V, hot_rows, hot, n_scatter, B, L, bchunk, gx, colsum_scratch, gx * S, fin_rows, fin_M,
-                     reinterpret_cast<float*>(state), tail);
+                     reinterpret_cast<float*>(state), tail, fix_contribution_limit(n));
   B4R_CHECK_LAUNCH("embedding gradients (scatter-add + position sums)");
   const int* poison = reinterpret_cast<const int*>(hot + (int64_t)HOT_SLOTS * hot_rows * H);
   if (!b4r_reduce_queue_attach_fixed(table_grad, fix, hot, hot_rows * H, HOT_SLOTS, poison)) {

@@ -146,9 +146,11 @@ int b4r_workspace_region(const b4r_model_config* cfg, int32_t B, int32_t L, int3
  * reduced sums from there.  No copy kernels around the collective. */
 #define B4R_FLAG_GRAD_TAIL 8
 /* Range of the item-table gradient: the embedding rows' contributions d loss_sum / d (token row) are scatter-added in 64-bit fixed
- * point (units of 2^-36, order-free => bitwise reproducible).  A contribution that is not finite or reaches 2^18 = 262 144 in magnitude
- * cannot be represented: the whole "word_embeddings/embeddings" gradient of that step is then NaN (and with it the step's gradient
- * norm), as an Inf / NaN would have made it with float atomics -- never a silently wrapped finite value. */
+ * point (units of 2^-36, order-free => bitwise reproducible); a sum holds 2^27 = 134 217 728.  With n = B * L token rows, one element
+ * of the table receives up to n contributions, so each must stay below min(2^18, 2^27 / n) in magnitude (2 621.44 at B = 256,
+ * L = 200).  A contribution that is not finite or reaches that bound cannot be summed safely: the whole "word_embeddings/embeddings"
+ * gradient of that step is then NaN (and with it the step's gradient norm), as an Inf / NaN would have made it with float atomics --
+ * never a silently wrapped finite value. */
 /* b4r_forward + b4r_backward of one TRAIN step (both or neither): the last encoder layer's feed-forward half is evaluated only on the
  * rows of the sequence output that the masked-LM head gathers (about P/L of them: 20 % at ML-1M) -- forward and backward.  Loss, metrics
  * and every gradient are unchanged (the other rows of that output reach neither the loss nor, through attention, any row that does);

@@ -67,3 +67,20 @@ def gemm_tn(A, B, R, Mo, No, want_colsum=False, want_colsum_a=False, rng=None, d
 
 def maxdiff(a, b):
     return float((a.detach().cpu().double() - b.detach().cpu().double()).abs().max())
+
+
+def set_row_slots(batch, row, positions, mask_token_id=1):
+    """Make the valid masked positions of one row of an oracle batch exactly `positions` (distinct; their tokens become [MASK] in
+    input_word_ids, every other token its label), the remaining slots padding slots (position 0, id 0) -- as the reference's
+    preprocessor writes a row with fewer masks than slots."""
+    pos = torch.as_tensor(positions, dtype=torch.int64)
+    seq = batch["labels"][row]
+    ids = seq.clone()
+    ids[pos] = mask_token_id
+    batch["input_word_ids"][row] = ids
+    for k in ("masked_lm_positions", "masked_lm_ids", "masked_lm_weights"):
+        batch[k][row] = 0
+    n = pos.numel()
+    batch["masked_lm_positions"][row, :n] = pos
+    batch["masked_lm_ids"][row, :n] = seq[pos]
+    batch["masked_lm_weights"][row, :n] = 1

@@ -17,6 +17,7 @@ import torch
 
 from oracle import bert4rec_oracle as orc
 from tests.test_gpu_model import LOGIT_TOL, build, compare_grads, maxdiff, outputs, run_loss_and_grads
+from tests.test_gpu_train_step import run_and_check_train_step
 
 pytestmark = pytest.mark.gpu
 
@@ -89,6 +90,28 @@ def test_full_ml1m_batch_train_mode_matches_oracle_mask_for_mask():
     assert st2["loss_sum"] == st["loss_sum"]
     for n in grads:   # every gradient, the item table included: its 51200 embedding rows are scatter-added in 64-bit fixed point
         assert torch.equal(grads[n], grads2[n]), n
+
+
+@pytest.mark.parametrize("cfg_o,shp,rate,drop", [(ML1M, ML1M_SHAPE, 0.2, 0.2), (STEAM, STEAM_SHAPE, 0.4, 0.1)], ids=["ml1m", "steam"])
+def test_full_batch_train_step_matches_oracle(cfg_o, shp, rate, drop):
+    """One b4r_train_step at the benchmark's shapes and dropout rates, checked as tests/test_gpu_train_step.py checks every shipped
+    configuration: gradient buffer, the gradient the fused AdamW consumed, the optimizer against the oracle's on the step's own
+    gradient, loss / norm / counts.  At these shapes the head's merge of its 6 (ML-1M) / 12 (Steam) vocabulary slices rides on the
+    transform's LayerNorm backward and the gradient norm comes from the closing reduce launch: the launch timer must show it (no
+    combine launch, no norm launch), or the test would be checking some other path."""
+    cfg_t = orc.OracleConfig(**{**cfg_o.__dict__, "output_dropout": drop, "attention_dropout": drop})
+    eng, _ = build(cfg_t)
+    assert eng.fused_head_supported()
+    batch = orc.synthetic_batch(shp["B"], shp["L"], shp["P"], cfg_t.vocab_size, rate=rate, seed=41, ragged=True)
+    hp_o = orc.AdamWConfig(num_warmup_steps=0, num_train_steps=100)
+    seed = 7
+    eng.set_seed(seed)
+    cb, keep = eng.prepare_batch(batch)
+    labels = []
+    run_and_check_train_step(eng, cfg_t, batch, cb, hp_o, 0, seed, rel=5e-3, labels=labels)
+    assert labels.count("multi_slab_reduce") == 1, labels
+    assert "global norm" not in labels and "masked-LM head combine" not in labels, labels
+    assert "masked-LM head forward (fused)" in labels and "masked-LM head dE (fused)" in labels, labels
 
 
 @pytest.mark.parametrize("cfg_o,B,L,P,shards", [(ML1M, 256, 200, 40, 4), (ML20M, 128, 200, 40, 4), (ML20M, 256, 200, 40, 2)],

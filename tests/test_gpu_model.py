@@ -431,9 +431,9 @@ def test_item_table_gradient_with_hundreds_of_contributions_per_row():
 
 def test_item_table_scatter_reports_out_of_range_contributions_instead_of_wrapping():
     """The item-table scatter adds in 64-bit fixed point (units of 2^-36: a 64-bit sum holds 2^27).  A contribution that is not finite or
-    reaches 2^18 in magnitude cannot be represented: float atomics would have carried it (or an Inf / NaN) into the gradient, round 3's
-    integer sums wrapped silently into finite garbage.  Now a sticky poison word makes the closing reduction store NaN for the whole
-    table gradient.  The backward is linear in d loss / d logits, so scaling that tensor between b4r_loss and b4r_backward scales
+    reaches min(2^18, 2^27 / (B * L)) in magnitude cannot be summed safely: float atomics would have carried it (or an Inf / NaN) into
+    the gradient, round 3's integer sums wrapped silently into finite garbage.  Now a sticky poison word makes the closing reduction
+    store NaN for the whole table gradient.  The backward is linear in d loss / d logits, so scaling that tensor between b4r_loss and b4r_backward scales
     every contribution: x 1 must reproduce the oracle, x 1e9 (contributions of ~1e7: finite in fp32, out of range here) must poison
     the table gradient and leave the gradients that do not pass through the scatter finite."""
     cfg_o, shp = CONFIGS["tiny"]
@@ -457,6 +457,53 @@ def test_item_table_scatter_reports_out_of_range_contributions_instead_of_wrappi
             assert maxdiff(table, want) < 2e-3 * float(want.abs().max())
         else:
             assert bool(torch.isnan(table).all()), "out-of-range contributions must poison the table gradient, not wrap"
+
+
+@pytest.mark.parametrize("item", [1, 7], ids=["mask_row", "item_row"])
+def test_item_table_scatter_poisons_a_row_total_out_of_range_instead_of_wrapping(item):
+    """The per-contribution bound alone does not keep the fixed-point sums in range: one table row receives up to B * L contributions,
+    and a 64-bit sum in units of 2^-36 holds 2^27.  Here every one of the n = B * L = 1024 tokens is the same item at a zeroed
+    position with every key visible and every position a slot labelled with that item, so every token's hidden state -- and its
+    contribution c to the item's row -- is the same (c = position-table gradient / B) and the row's total is n * c.  Scaling
+    d loss / d logits by s between b4r_loss and b4r_backward scales every contribution; for each s the table gradient must be
+    all NaN or s times the unscaled gradient, and below |s c| = 2^27 / n (= 2^17 here) it must be the latter.  s c = 1.5 * 2^17 is
+    below the old per-contribution limit 2^18, but the total is 1.5 * 2^27: it wrapped to a finite wrong gradient.  The [MASK] row
+    (hot rows: summed in LDS first) and an ordinary row."""
+    cfg_o = orc.OracleConfig(vocab_size=37, hidden_size=64, num_layers=1, num_attention_heads=2, max_sequence_length=16, inner_dim=64)
+    B, L = 64, 16
+    n = B * L
+    batch = {"input_word_ids": torch.full((B, L), item, dtype=torch.int64), "input_mask": torch.ones(B, L, dtype=torch.int64),
+             "masked_lm_positions": torch.arange(L).repeat(B, 1), "masked_lm_ids": torch.full((B, L), item, dtype=torch.int64)}
+
+    def table_gradient(scale):
+        eng, _ = build(cfg_o)
+        eng.view("position_embedding/embeddings").zero_()
+        cb, keep = eng.prepare_batch(batch)
+        eng.begin_step()
+        eng.forward(cb, training=False, pooler=False)
+        eng.loss(cb, want_grad=True)
+        eng.region("mlm_logits", cb.B, cb.L, cb.P).mul_(scale)
+        eng.backward(cb, training=False)
+        torch.cuda.synchronize()
+        g = eng.export_named(eng.grads)
+        assert bool(torch.isfinite(g["transformer/layer_0/intermediate/kernel"]).all())
+        return g["word_embeddings/embeddings"].double(), g["position_embedding/embeddings"].double()
+
+    base, gpos = table_gradient(1.0)
+    c = gpos[:L] / B
+    assert float((c - c[0]).abs().max()) <= 1e-3 * float(c[0].abs().max()), "the tokens' contributions are not all the same"
+    c_max = float(c.abs().max())
+    bound = 2.0 ** 27 / n
+    assert bound < 2.0 ** 18 and c_max > 0
+    for target in (0.5 * bound, 0.9 * bound, 1.5 * bound, 4.0 * 2.0 ** 18):
+        s = target / c_max
+        table, _ = table_gradient(s)
+        if bool(torch.isnan(table).all()):
+            assert target >= bound, f"|s c| = {target:.4g} < 2^27 / n: the total is in range, the table gradient must not be poisoned"
+            continue
+        assert bool(torch.isfinite(table).all()), f"|s c| = {target:.4g}: partly poisoned table gradient"
+        err = float((table - s * base).abs().max()) / float((s * base).abs().max())
+        assert err <= 1e-5, f"|s c| = {target:.4g} (|n s c| = {n * target:.4g}): the table gradient is finite but wrong (rel {err:.2e})"
 
 
 def test_launch_timer_lists_the_launches_of_a_train_step_in_order():

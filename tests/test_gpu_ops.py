@@ -806,7 +806,15 @@ def test_fused_mlm_head_at_the_ml20m_vocabulary_matches_fp64_autograd():
     """b4r_mlm_head_fused_fwd / _bwd at V = 26 732, H = 256 (BASELINE.json configs[3]) against fp64 logits -> softmax CE -> autograd:
     loss rows, lse, dT, dE, d bias (M = 256 rows is enough to run every vocabulary tile of the NKH = 8 sweeps)."""
     lib = _lib.load()
+    prev = lib.b4r_get_gemm_mode()
     _lib.check(lib.b4r_set_gemm_mode(_lib.GEMM_BF16X3))
+    try:
+        _fused_mlm_head_at_the_ml20m_vocabulary(lib)
+    finally:
+        lib.b4r_set_gemm_mode(prev)      # as the gemm_mode fixture does: the tests after this one run in the mode they expect
+
+
+def _fused_mlm_head_at_the_ml20m_vocabulary(lib):
     M, V, H = 256, 26732, 256
     Tm, E, bias = rnd(M, H, seed=80), rnd(V, H, seed=81, scale=0.03), rnd(V, seed=82, scale=0.01)
     y = torch.randint(1, V, (M,), generator=torch.Generator().manual_seed(83))
