@@ -149,6 +149,8 @@ PROTOTYPES = {
     "b4r_gemm_tn_dgrad_supported": (C.c_int, [C.POINTER(GemmTnDesc)]),
     "b4r_attn_fwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _U32, _F, _P, _P]),
     "b4r_attn_bwd": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _F, _P, _P, _U32, _F, _P, _P]),
+    "b4r_attn_fwd_hd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _U32, _F, _P, _P]),
+    "b4r_attn_bwd_hd": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _F, _P, _P, _U32, _F, _P, _P]),
     "b4r_attn_keep_words": (C.c_int64, [_I32, _I32, _I32]),
     "b4r_attn_block_supported": (_I32, [_I32, _I32, _I32]),
     "b4r_attn_block_fwd": (C.c_int, [C.POINTER(AttnBlockDesc), _P]),

@@ -159,13 +159,16 @@ namespace {
 inline int64_t up4(int64_t x) { return (x + 3) & ~(int64_t)3; }
 inline int64_t up32(int64_t x) { return (x + 31) & ~(int64_t)31; }
 
+// the width of one attention head, 32 or 64 (check_cfg)
+inline int head_dim(const b4r_model_config* c) { return c->hidden_size / c->num_heads; }
+
 int check_cfg(const b4r_model_config* c) {
   B4R_CHECK_ARG(c != nullptr, B4R_E_BADARG, "null model config");
   B4R_CHECK_ARG(c->vocab_size > 0 && c->num_layers > 0 && c->num_layers <= B4R_MAX_LAYERS && c->num_heads > 0 &&
                     c->inner_dim > 0 && c->max_seq_len > 0,
                 B4R_E_SHAPE, "bad model config");
-  B4R_CHECK_ARG(c->hidden_size == 32 * c->num_heads, B4R_E_SHAPE,
-                "hidden_size %d / num_heads %d: head_dim must be 32", c->hidden_size, c->num_heads);
+  B4R_CHECK_ARG(c->hidden_size == 32 * c->num_heads || c->hidden_size == 64 * c->num_heads, B4R_E_SHAPE,
+                "hidden_size %d / num_heads %d: head_dim must be 32 or 64", c->hidden_size, c->num_heads);
   const int H = c->hidden_size;
   B4R_CHECK_ARG(H == 32 || H == 64 || H == 128 || H == 256 || H == 512 || H == 1024, B4R_E_SHAPE,
                 "hidden_size %d not supported (32,64,128,256,512,1024)", H);
@@ -393,8 +396,9 @@ bool ffn_fused(const b4r_model_config* c) {
 }
 
 // the attention half of a layer as one launch forward (b4r_attn_block.hip); else the three launches of round 1
+// (heads of width 32 only: the blocks and the 32-token-tile kernels behind them stage [rows][32] head slices)
 bool attn_fused(const b4r_model_config* c, int L) {
-  return b4r_attn_block_supported(c->hidden_size, c->num_heads, L) != 0;
+  return head_dim(c) == 32 && b4r_attn_block_supported(c->hidden_size, c->num_heads, L) != 0;
 }
 
 // ... and one launch backward (b4r_attn_block_bwd; then the forward need not store qkv); else round 1's kernels
@@ -421,9 +425,11 @@ bool head_rows_dense_ok(const b4r_model_config* c, const b4r_batch* b) {
 bool ffn32w_train_ok(const b4r_model_config* c) {
   return c->hidden_size == 128 && b4r_ffn32w_supported(c->hidden_size, c->inner_dim);
 }
-// ... and the attention half of that layer with the slots as its only queries (hidden sizes on the tile products; P <= 64)
+// ... and the attention half of that layer with the slots as its only queries (hidden sizes on the tile products; P <= 64; heads of
+// width 32 -- at width 64 the last layer's attention runs dense and the rows are gathered after it)
 bool slotq_layer(const b4r_model_config* c, const b4r_batch* b, uint32_t flags, int layer) {
-  return (flags & B4R_FLAG_HEAD_ROWS_ONLY) && layer == c->num_layers - 1 && head_rows_dense_ok(c, b) && !attn_fused(c, b->L) &&
+  return (flags & B4R_FLAG_HEAD_ROWS_ONLY) && layer == c->num_layers - 1 && head_dim(c) == 32 && head_rows_dense_ok(c, b) &&
+         !attn_fused(c, b->L) &&
          b4r_attn32_slotq_supported(b->L, b->P) &&
          b4r_attn32_slotq_keep_words(b->B, b->L, c->num_heads, b->P) <= b4r_attn_keep_words(b->B, b->L, c->num_heads);
 }
@@ -614,7 +620,7 @@ static int forward_impl(const b4r_model_config* cfg, const b4r_batch* batch, con
   float* ws = static_cast<float*>(workspace);
   hipStream_t s = (hipStream_t)stream;
   const int H = cfg->hidden_size, I = cfg->inner_dim, V = cfg->vocab_size, N = B * L, M = B * P;
-  const float qscale = 1.0f / sqrtf(32.0f);
+  const float qscale = 1.0f / sqrtf((float)head_dim(cfg));
 
   // the embedding stage: inside the first layer's attention block where that runs fused, else a launch of its own
   const bool emb_fused = attn_fused(cfg, L) && cfg->num_layers > 0;
@@ -668,8 +674,8 @@ static int forward_impl(const b4r_model_config* cfg, const b4r_batch* batch, con
                             b4r_make_drop(rng, B4R_STREAM_ATTN_OUT(i), od, 1), ws + cr.z1c, ws + cr.mean1c, ws + cr.rstd1c, nullptr,
                             ws + cr.x1c, s));
     } else {
-    RC(b4r_attn_fwd(ws + w.qkv[i], batch->input_mask, B, L, cfg->num_heads, ws + w.ctx[i], ws + w.lse[i], rng,
-                    B4R_STREAM_ATTN_PROBS(i), adp, reinterpret_cast<uint32_t*>(ws + w.keep[i]), stream));
+    RC(b4r_attn_fwd_hd(ws + w.qkv[i], batch->input_mask, B, L, cfg->num_heads, head_dim(cfg), ws + w.ctx[i], ws + w.lse[i], rng,
+                       B4R_STREAM_ATTN_PROBS(i), adp, reinterpret_cast<uint32_t*>(ws + w.keep[i]), stream));
     RC(dense_res_ln(ws + w.ctx[i], H, params + pl.wo[i], ws + w.z1[i], ws + w.x1[i], ws + w.mean1[i], ws + w.rstd1[i], N, H, H,
                     params + pl.bo[i], x, params + pl.ln1_g[i], params + pl.ln1_b[i], cfg->ln_eps, rng, B4R_STREAM_ATTN_OUT(i),
                     od, s));
@@ -819,7 +825,7 @@ static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, co
   float* ws = static_cast<float*>(workspace);
   hipStream_t s = (hipStream_t)stream;
   const int H = cfg->hidden_size, I = cfg->inner_dim, V = cfg->vocab_size, N = B * L, M = B * P, Vp = (int)w.Vp;
-  const float qscale = 1.0f / sqrtf(32.0f);
+  const float qscale = 1.0f / sqrtf((float)head_dim(cfg));
   float* scratch_base = ws + w.scratch;
   int64_t scratch_used = 0;
   auto take = [&](int64_t n) { float* ptr = scratch_base + scratch_used; scratch_used += up4(n); return ptr; };
@@ -1064,8 +1070,9 @@ static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, co
       }
     }
     // attention core: dQ, dK, dV
-    RC(b4r_attn_bwd(ws + w.qkv[i], batch->input_mask, ws + w.ctx[i], ws + w.lse[i], ws + w.dctx, B, L, cfg->num_heads, qscale,
-                    ws + w.dqkv, rng, B4R_STREAM_ATTN_PROBS(i), adp, reinterpret_cast<const uint32_t*>(ws + w.keep[i]), stream));
+    RC(b4r_attn_bwd_hd(ws + w.qkv[i], batch->input_mask, ws + w.ctx[i], ws + w.lse[i], ws + w.dctx, B, L, cfg->num_heads,
+                       head_dim(cfg), qscale, ws + w.dqkv, rng, B4R_STREAM_ATTN_PROBS(i), adp,
+                       reinterpret_cast<const uint32_t*>(ws + w.keep[i]), stream));
     }
     // QKV projection: dX_in = dqkv . Wqkv^T + dz1, and for i > 0 straight on to layer i-1's output LayerNorm backward (-> da)
     if (i > 0)

@@ -34,7 +34,7 @@ enum { B4R_OK = 0, B4R_E_BADARG = -1, B4R_E_SHAPE = -2, B4R_E_ALIGN = -3, B4R_E_
 
 /* Encoder hyper-parameters: Bert4RecEncoder.__init__ kwargs, bert4rec_encoder.py:62-80, as set by
  * bert4rec/config/bert4rec_train_configs/ *.json.  head_dim = hidden_size / num_heads must be 32 (true for every
- * shipped config). */
+ * shipped config) or 64. */
 typedef struct b4r_model_config {
   int32_t vocab_size;
   int32_t hidden_size;
@@ -395,6 +395,16 @@ int b4r_attn_bwd(const float* qkv, const int64_t* input_mask, const float* ctx, 
  * dropout is active); the B4R_GEMM_F32 kernels regenerate the decisions from the hash and ignore the buffer.  Forward and
  * backward of one step must run in the same mode. */
 int64_t b4r_attn_keep_words(int32_t B, int32_t L, int32_t heads);
+/* The same core for a given head width: hidden size H = heads * head_dim, head h = columns head_dim*h .. +head_dim-1 of each
+ * third of qkv (q pre-scaled by 1/sqrt(head_dim)).  head_dim 32 is b4r_attn_fwd / b4r_attn_bwd; head_dim 64 runs the kernels of
+ * b4r_attn64.hip (both arithmetic modes, L <= 256; the backward is one launch and hashes the dropout decisions again, so
+ * keep_bits is not read or written); any other head_dim returns B4R_E_SHAPE. */
+int b4r_attn_fwd_hd(const float* qkv, const int64_t* input_mask, int32_t B, int32_t L, int32_t heads, int32_t head_dim, float* ctx,
+                    float* lse, const uint32_t* rng, uint32_t drop_stream, float drop_rate, uint32_t* keep_bits,
+                    b4r_stream_t stream);
+int b4r_attn_bwd_hd(const float* qkv, const int64_t* input_mask, const float* ctx, const float* lse, const float* dctx,
+                    int32_t B, int32_t L, int32_t heads, int32_t head_dim, float qscale, float* dqkv, const uint32_t* rng,
+                    uint32_t drop_stream, float drop_rate, const uint32_t* keep_bits, b4r_stream_t stream);
 
 /* ---- fused encoder-layer halves (hidden size 64, B4R_GEMM_BF16X3) ------------------------------------------------------
  * One Keras TransformerEncoderBlock call (bert4rec_encoder.py:136-147 constructs it, :220-222 calls it once per layer) is
