@@ -1,0 +1,492 @@
+// Full-catalogue top-K and rank of a held-out item, without an [R, V] score matrix.
+//
+// Serves  batched recommendation   (top K unseen items for many users: Recommender.recommend_batch, BERT4RecModel.recommend)
+//         full-ranking evaluation  (rank of the held-out item among every item the user has not interacted with, the protocol of
+//                                   the BERT4Rec replication studies instead of bert4rec_evaluator.py:60-120's 100 sampled negatives)
+//
+// Contract (include/b4r.h, b4r_rank_full): scores are the b4r_rank_candidates scores bit for bit (k-ascending fp32 fma chain +
+// bias, oracle/rank_oracle.c::rank_oracle_scores); the top K is the stable descending order over the allowed ids (ties: lower id
+// first); gt_rank = 1 + #{allowed j: s_j > s_gt} + #{allowed j < gt: s_j == s_gt}.
+//
+// Three launches per group of rows that fits the scratch:
+//   1. gt key     one thread per row: s_gt by the same chain, as the order-preserving integer image ("key") of the score.
+//   2. sweep      grid (group of FG = 16 rows) x (chunk of FCH = 1024 ids).  Each 256-thread workgroup stages its chunk's table
+//                 rows through LDS in k-blocks of FKB floats (16-byte loads), once for all 16 rows, and forms 16 x 1024 scores
+//                 with the fma chain on the VALU (the hidden rows are LDS broadcasts; 2 ids per thread per k-block halve those).
+//                 Scores stay in registers (4 ids x 16 rows per thread).  Excluded ids come from a per-row LDS bitmap built from
+//                 exclude[r].  Per row it counts, in integers, the allowed ids that beat gt, and selects the chunk's best
+//                 min(K, 1024) by a radix select on the unique 48-bit key (score key << 16 | 1023 - local id): the passes start
+//                 below the bits every allowed key of the row shares, and stop as soon as the digit found holds exactly what is
+//                 still missing.  The selected (score, id) pairs go to scratch in any order.
+//   3. merge      one workgroup per row: the same radix select on (score key << 32 | ~id) over all chunks' candidates, then the
+//                 order of the K survivors by counting, descending key; gt_rank = 1 + the sum of the chunks' counts.
+// No floating-point atomics; LDS integer atomics only place or count, and the outputs do not depend on their order.
+#include <algorithm>
+
+#include "b4r_common.h"
+
+namespace {
+
+constexpr int FT = 256;          // threads per workgroup
+constexpr int FG = 16;           // rows per sweep workgroup
+constexpr int FQ = 4;            // ids per thread per chunk
+constexpr int FIPT = 2;          // ids scored together per k-block (FQ / FIPT steps)
+constexpr int FCH = FT * FQ;     // ids per chunk
+constexpr int FKB = 16;          // k-block (floats of a table row staged at a time)
+constexpr int FK_MAX = 1024;     // largest K
+constexpr uint32_t NOT_ALLOWED = 0xFFFFFFFFu;   // raw-bits marker of an id that is not ranked (a NaN pattern: out of contract)
+
+static_assert(FT == FG * 16, "digit search: 16 threads per row");
+static_assert(FCH <= 65536, "the local id takes the low 16 bits of the sweep key");
+
+// order-preserving image of a score for an ascending unsigned compare; -0.0 counts as +0.0 (they compare equal)
+__device__ __forceinline__ uint32_t score_key_bits(uint32_t u) {
+  if (u == 0x80000000u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ uint32_t score_key(float s) { return score_key_bits(__builtin_bit_cast(uint32_t, s)); }
+
+__device__ __forceinline__ float row_score(const float* h, const float* e, const float* bias, int64_t j, int H) {
+  float acc = 0.f;
+  for (int k = 0; k < H; ++k) acc = __builtin_fmaf(h[k], e[k], acc);   // k-ordered fp32 fma chain (the contract)
+  return acc + bias[j];
+}
+
+// state of one row's radix select over W-bit unique keys: `hi` top bits are resolved (= prefix); `rem` ids are still to be taken
+// from those whose top bits equal the prefix; done: every key >= thr is taken (take = 0: none)
+struct Sel {
+  uint64_t prefix, thr;
+  int hi, rem, done, take;
+};
+
+// init: n allowed keys, `need` to take; kmin / kmax over the allowed score keys (the top 32 bits of every W-bit key)
+__device__ __forceinline__ void sel_init(Sel& s, int n, int need, uint32_t kmin, uint32_t kmax, int W) {
+  s.take = need > 0;
+  s.rem = need;
+  s.thr = 0;
+  if (need <= 0 || need >= n) {
+    s.done = 1; s.hi = 0; s.prefix = 0;   // none, or every allowed id (thr = 0)
+    return;
+  }
+  const uint32_t diff = kmin ^ kmax;
+  s.hi = diff ? __clz(diff) : 32;
+  s.prefix = (uint64_t)kmax >> (32 - s.hi);
+  s.done = 0;
+  (void)W;
+}
+
+__device__ __forceinline__ bool sel_match(const Sel& s, uint64_t key, int W) {
+  return s.hi == 0 || (key >> (W - s.hi)) == s.prefix;
+}
+
+__device__ __forceinline__ int sel_nb(const Sel& s, int W) { return min(8, W - s.hi); }
+
+// the 16 threads qq = 0..15 of a row: part[qq] = count of digits 255-16qq .. 240-16qq (descending)
+__device__ __forceinline__ void sel_part(const uint32_t* hist, uint32_t* part, int qq) {
+  uint32_t c = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) c += hist[255 - 16 * qq - i];
+  part[qq] = c;
+}
+
+// the thread whose 16 digits hold the rem-th key from the top writes the advanced state `s` (a copy taken before the barrier
+// that precedes this call) to `out`; the other threads of the row leave it alone
+__device__ __forceinline__ void sel_advance(Sel s, Sel& out, const uint32_t* hist, const uint32_t* part, int qq, int W) {
+  uint32_t above = 0;
+  for (int i = 0; i < qq; ++i) above += part[i];
+  const uint32_t rem = (uint32_t)s.rem;
+  if (!(above < rem && above + part[qq] >= rem)) return;
+  const int nb = sel_nb(s, W);
+  for (int i = 0; i < 16; ++i) {
+    const int d = 255 - 16 * qq - i;
+    const uint32_t c = hist[d];
+    if (above + c >= rem) {
+      const uint32_t left = rem - above;
+      s.prefix = (s.prefix << nb) | (uint64_t)d;
+      s.hi += nb;
+      s.rem = (int)left;
+      if (c == left || s.hi >= W) {
+        s.done = 1;
+        s.thr = s.hi >= W ? s.prefix : (s.prefix << (W - s.hi));
+      }
+      out = s;
+      return;
+    }
+    above += c;
+  }
+}
+
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+  for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+  return v;
+}
+
+// ---- 1. score key of the held-out item ----------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void full_gt_key_kernel(const float* __restrict__ hidden, int hidden_ld,
+                                                          const int64_t* __restrict__ hidden_row, const float* __restrict__ table,
+                                                          const float* __restrict__ bias, int H, int V, int lo,
+                                                          const int64_t* __restrict__ gt, int64_t r0, int n,
+                                                          uint32_t* __restrict__ gkey) {
+  const int lr = blockIdx.x * 64 + threadIdx.x;
+  if (lr >= n) return;
+  const int64_t r = r0 + lr;
+  const int64_t g = gt[r];
+  if (g < lo || g >= V) { gkey[lr] = 0u; return; }
+  const int64_t hr = hidden_row ? hidden_row[r] : r;
+  gkey[lr] = score_key(row_score(hidden + hr * hidden_ld, table + g * H, bias, g, H));
+}
+
+// ---- 2. sweep: (group of FG rows) x (chunk of FCH ids) -------------------------------------------------------------------------
+struct SweepArgs {
+  const float* hidden; const int64_t* hidden_row; const float* table; const float* bias;
+  const int64_t* exclude; const int64_t* gt;
+  const uint32_t* gkey;
+  float* c_score; int32_t* c_id; int32_t* c_cnt; int32_t* c_beat;   // [n][nch][cap], [n][nch]
+  int64_t r0;
+  int hidden_ld, H, V, lo, E, n, nch, cap;
+};
+
+__global__ __launch_bounds__(FT, 2) void full_sweep_kernel(SweepArgs a) {
+  __shared__ float tile[FIPT * FT * (FKB + 1)];
+  __shared__ __attribute__((aligned(16))) float hsh[FG * FKB];
+  __shared__ uint32_t bits[FG][FCH / 32];
+  __shared__ uint32_t hist[FG][256];
+  __shared__ uint32_t part[FG][16];
+  __shared__ Sel st[FG];
+  __shared__ uint32_t s_cnt[FG], s_beat[FG], s_kmin[FG], s_kmax[FG], s_out[FG];
+  __shared__ int64_t s_hoff[FG], s_gt[FG];
+  __shared__ int s_alldone;
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int lr0 = blockIdx.x * FG;
+  const int chunk = blockIdx.y;
+  const int64_t c0 = (int64_t)chunk * FCH;
+  const int H = a.H;
+
+  if (tid < FG) {
+    const int lr = lr0 + tid;
+    const bool rv = lr < a.n;
+    const int64_t r = a.r0 + lr;
+    s_hoff[tid] = rv ? (a.hidden_row ? a.hidden_row[r] : r) * a.hidden_ld : -1;
+    s_gt[tid] = (rv && a.gt) ? a.gt[r] : -1;
+    s_cnt[tid] = 0; s_beat[tid] = 0; s_out[tid] = 0;
+    s_kmin[tid] = 0xFFFFFFFFu; s_kmax[tid] = 0u;
+  }
+  for (int i = tid; i < FG * (FCH / 32); i += FT) (&bits[0][0])[i] = 0u;
+  __syncthreads();
+  if (a.E > 0) {
+    for (int f = tid; f < FG * a.E; f += FT) {
+      const int g = f / a.E, e = f - g * a.E;
+      if (s_hoff[g] < 0) continue;
+      const int64_t id = a.exclude[(a.r0 + lr0 + g) * (int64_t)a.E + e];
+      if (id >= c0 && id < c0 + FCH) {
+        const int l = (int)(id - c0);
+        atomicOr(&bits[g][l >> 5], 1u << (l & 31));
+      }
+    }
+  }
+
+  // ---- scores: raw fp32 bits in registers, NOT_ALLOWED where the id is not ranked -----------------------------------------------
+  uint32_t raw[FQ][FG];
+#pragma unroll
+  for (int ps = 0; ps < FQ / FIPT; ++ps) {
+    float acc[FIPT][FG];
+#pragma unroll
+    for (int ii = 0; ii < FIPT; ++ii)
+#pragma unroll
+      for (int g = 0; g < FG; ++g) acc[ii][g] = 0.f;
+    const int64_t cj0 = c0 + (int64_t)ps * FIPT * FT;   // first id of this step
+    for (int kb = 0; kb < H; kb += FKB) {
+      const int kn = min(FKB, H - kb);   // a multiple of 4 (H % 4 == 0)
+      const int k4 = kn >> 2;
+      __syncthreads();   // the previous block is consumed (and, the first time, the bitmap is complete)
+      for (int f = tid; f < FIPT * FT * k4; f += FT) {
+        const int i = f / k4, c4 = f - i * k4;
+        const int64_t j = cj0 + i;
+        const f32x4 v = j < a.V ? *reinterpret_cast<const f32x4*>(a.table + j * H + kb + 4 * c4) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        float* dst = tile + i * (FKB + 1) + 4 * c4;
+        dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3];
+      }
+      {
+        const int g = tid / FKB, k = tid - g * FKB;   // FG * FKB == FT
+        hsh[tid] = (k < kn && s_hoff[g] >= 0) ? a.hidden[s_hoff[g] + kb + k] : 0.f;
+      }
+      __syncthreads();
+      for (int k = 0; k < kn; k += 4) {
+        float e[FIPT][4];
+#pragma unroll
+        for (int ii = 0; ii < FIPT; ++ii)
+#pragma unroll
+          for (int u = 0; u < 4; ++u) e[ii][u] = tile[(ii * FT + tid) * (FKB + 1) + k + u];
+#pragma unroll
+        for (int g = 0; g < FG; ++g) {
+          const f32x4 h = *reinterpret_cast<const f32x4*>(hsh + g * FKB + k);
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int ii = 0; ii < FIPT; ++ii) acc[ii][g] = __builtin_fmaf(h[u], e[ii][u], acc[ii][g]);
+        }
+      }
+    }
+#pragma unroll
+    for (int ii = 0; ii < FIPT; ++ii) {
+      const int q = ps * FIPT + ii;
+      const int l = q * FT + tid;
+      const int64_t j = c0 + l;
+      const bool inb = j >= a.lo && j < a.V;
+      const float b = inb ? a.bias[j] : 0.f;
+#pragma unroll
+      for (int g = 0; g < FG; ++g) {
+        const bool ex = (bits[g][l >> 5] >> (l & 31)) & 1u;
+        const bool ok = inb && s_hoff[g] >= 0 && (!ex || j == s_gt[g]);
+        raw[q][g] = ok ? __builtin_bit_cast(uint32_t, acc[ii][g] + b) : NOT_ALLOWED;
+      }
+    }
+  }
+
+  // ---- per row: allowed count, ids that beat gt, key range ------------------------------------------------------------------
+#pragma unroll
+  for (int g = 0; g < FG; ++g) {
+    const bool gv = a.gt && s_gt[g] >= a.lo && s_gt[g] < a.V && s_hoff[g] >= 0;
+    const uint32_t gk = gv ? a.gkey[lr0 + g] : 0u;
+    const int64_t gid = s_gt[g];
+    uint32_t cnt = 0, beat = 0, kmin = 0xFFFFFFFFu, kmax = 0u;
+#pragma unroll
+    for (int q = 0; q < FQ; ++q) {
+      if (raw[q][g] == NOT_ALLOWED) continue;
+      const uint32_t k = score_key_bits(raw[q][g]);
+      const int64_t j = c0 + q * FT + tid;
+      cnt += 1;
+      beat += (gv && (k > gk || (k == gk && j < gid))) ? 1u : 0u;
+      kmin = min(kmin, k); kmax = max(kmax, k);
+    }
+    cnt = wave_sum_u32(cnt); beat = wave_sum_u32(beat);
+    kmin = wave_min_u32(kmin); kmax = wave_max_u32(kmax);
+    if (lane == 0) {
+      atomicAdd(&s_cnt[g], cnt); atomicAdd(&s_beat[g], beat);
+      atomicMin(&s_kmin[g], kmin); atomicMax(&s_kmax[g], kmax);
+    }
+  }
+  __syncthreads();
+  if (tid < FG && lr0 + tid < a.n) {
+    const int64_t o = (int64_t)(lr0 + tid) * a.nch + chunk;
+    a.c_beat[o] = (int32_t)s_beat[tid];
+    const int n = (int)s_cnt[tid];
+    sel_init(st[tid], n, min(a.cap, n), s_kmin[tid], s_kmax[tid], 48);
+  } else if (tid < FG) {
+    sel_init(st[tid], 0, 0, 0u, 0u, 48);
+  }
+  if (tid == 0) s_alldone = 0;
+
+  // ---- radix select over (score key << 16 | FCH-1 - local id) --------------------------------------------------------------
+  for (int pass = 0; pass < 6; ++pass) {
+    __syncthreads();
+    if (tid == 0) {
+      int all = 1;
+      for (int g = 0; g < FG; ++g) all &= st[g].done;
+      s_alldone = all;
+    }
+    for (int i = tid; i < FG * 256; i += FT) (&hist[0][0])[i] = 0u;
+    __syncthreads();
+    if (s_alldone) break;
+#pragma unroll
+    for (int g = 0; g < FG; ++g) {
+      const Sel s = st[g];
+      if (s.done) continue;
+      const int nb = sel_nb(s, 48), sh = 48 - s.hi - nb;
+#pragma unroll
+      for (int q = 0; q < FQ; ++q) {
+        if (raw[q][g] == NOT_ALLOWED) continue;
+        const uint64_t key = ((uint64_t)score_key_bits(raw[q][g]) << 16) | (uint64_t)(FCH - 1 - (q * FT + tid));
+        if (sel_match(s, key, 48)) atomicAdd(&hist[g][(key >> sh) & ((1u << nb) - 1u)], 1u);
+      }
+    }
+    __syncthreads();
+    const int g = tid >> 4, qq = tid & 15;
+    const Sel mine = st[g];
+    if (!mine.done) sel_part(hist[g], part[g], qq);
+    __syncthreads();
+    if (!mine.done) sel_advance(mine, st[g], hist[g], part[g], qq, 48);
+  }
+  __syncthreads();
+
+  // ---- emit the selected ids of each row (any order: the merge orders them) ------------------------------------------------
+#pragma unroll
+  for (int g = 0; g < FG; ++g) {
+    const Sel s = st[g];
+    if (!s.take || !s.done) continue;
+    const int64_t base = ((int64_t)(lr0 + g) * a.nch + chunk) * a.cap;
+#pragma unroll
+    for (int q = 0; q < FQ; ++q) {
+      if (raw[q][g] == NOT_ALLOWED) continue;
+      const int l = q * FT + tid;
+      const uint64_t key = ((uint64_t)score_key_bits(raw[q][g]) << 16) | (uint64_t)(FCH - 1 - l);
+      if (key < s.thr) continue;
+      const uint32_t slot = atomicAdd(&s_out[g], 1u);
+      if (slot < (uint32_t)a.cap) {
+        a.c_score[base + slot] = __builtin_bit_cast(float, raw[q][g]);
+        a.c_id[base + slot] = (int32_t)(c0 + l);
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < FG && lr0 + tid < a.n) a.c_cnt[(int64_t)(lr0 + tid) * a.nch + chunk] = (int32_t)min(s_out[tid], (uint32_t)a.cap);
+}
+
+// ---- 3. merge: one workgroup per row ------------------------------------------------------------------------------------------
+struct MergeArgs {
+  const float* c_score; const int32_t* c_id; const int32_t* c_cnt; const int32_t* c_beat;
+  const int64_t* gt;
+  int64_t* topk_ids; float* topk_scores; int32_t* gt_rank;
+  int64_t r0;
+  int nch, cap, K, lo, V;
+};
+
+__global__ __launch_bounds__(FT) void full_merge_kernel(MergeArgs a) {
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t part[16];
+  __shared__ Sel st;
+  __shared__ uint32_t s_n, s_kmin, s_kmax, s_out, s_beat;
+  __shared__ uint64_t sel_key[FK_MAX];
+  __shared__ float sel_score[FK_MAX];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int lr = blockIdx.x;
+  const int64_t r = a.r0 + lr;
+  const int32_t* cnt = a.c_cnt + (int64_t)lr * a.nch;
+  const int64_t base = (int64_t)lr * a.nch * a.cap;
+  const int64_t total_slots = (int64_t)a.nch * a.cap;
+
+  if (tid == 0) { s_n = 0; s_kmin = 0xFFFFFFFFu; s_kmax = 0u; s_out = 0; s_beat = 0; }
+  __syncthreads();
+  {
+    uint32_t n = 0, beat = 0, kmin = 0xFFFFFFFFu, kmax = 0u;
+    for (int c = tid; c < a.nch; c += FT) { n += (uint32_t)cnt[c]; beat += (uint32_t)a.c_beat[(int64_t)lr * a.nch + c]; }
+    for (int64_t e = tid; e < total_slots; e += FT) {
+      const int c = (int)(e / a.cap), i = (int)(e - (int64_t)c * a.cap);
+      if (i >= cnt[c]) continue;
+      const uint32_t k = score_key(a.c_score[base + e]);
+      kmin = min(kmin, k); kmax = max(kmax, k);
+    }
+    n = wave_sum_u32(n); beat = wave_sum_u32(beat);
+    kmin = wave_min_u32(kmin); kmax = wave_max_u32(kmax);
+    if (lane == 0) { atomicAdd(&s_n, n); atomicAdd(&s_beat, beat); atomicMin(&s_kmin, kmin); atomicMax(&s_kmax, kmax); }
+  }
+  __syncthreads();
+  const int n = (int)s_n;
+  const int need = min(a.K, n);
+  if (tid == 0) sel_init(st, n, need, s_kmin, s_kmax, 64);
+  for (int pass = 0; pass < 8; ++pass) {
+    __syncthreads();
+    if (st.done) break;
+    for (int i = tid; i < 256; i += FT) hist[i] = 0u;
+    __syncthreads();
+    const Sel s = st;
+    const int nb = sel_nb(s, 64), sh = 64 - s.hi - nb;
+    for (int64_t e = tid; e < total_slots; e += FT) {
+      const int c = (int)(e / a.cap), i = (int)(e - (int64_t)c * a.cap);
+      if (i >= cnt[c]) continue;
+      const uint64_t key = ((uint64_t)score_key(a.c_score[base + e]) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)a.c_id[base + e]);
+      if (sel_match(s, key, 64)) atomicAdd(&hist[(key >> sh) & ((1u << nb) - 1u)], 1u);
+    }
+    __syncthreads();
+    if (tid < 16) sel_part(hist, part, tid);
+    __syncthreads();
+    if (tid < 16) sel_advance(s, st, hist, part, tid, 64);
+  }
+  __syncthreads();
+  if (st.take && st.done) {
+    const uint64_t thr = st.thr;
+    for (int64_t e = tid; e < total_slots; e += FT) {
+      const int c = (int)(e / a.cap), i = (int)(e - (int64_t)c * a.cap);
+      if (i >= cnt[c]) continue;
+      const float sc = a.c_score[base + e];
+      const uint64_t key = ((uint64_t)score_key(sc) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)a.c_id[base + e]);
+      if (key < thr) continue;
+      const uint32_t slot = atomicAdd(&s_out, 1u);
+      if (slot < (uint32_t)FK_MAX) { sel_key[slot] = key; sel_score[slot] = sc; }
+    }
+  }
+  __syncthreads();
+  const int m = min((int)s_out, min(a.K, FK_MAX));
+  for (int i = tid; i < m; i += FT) {
+    const uint64_t ki = sel_key[i];
+    int pos = 0;
+    for (int j = 0; j < m; ++j) pos += sel_key[j] > ki ? 1 : 0;   // keys are unique: a permutation of 0 .. m-1
+    if (a.topk_ids) a.topk_ids[r * a.K + pos] = (int64_t)(0xFFFFFFFFu - (uint32_t)(ki & 0xFFFFFFFFu));
+    if (a.topk_scores) a.topk_scores[r * a.K + pos] = sel_score[i];
+  }
+  for (int p = m + tid; p < a.K; p += FT) {
+    if (a.topk_ids) a.topk_ids[r * a.K + p] = -1;
+    if (a.topk_scores) a.topk_scores[r * a.K + p] = -INFINITY;
+  }
+  if (tid == 0 && a.gt_rank) {
+    const int64_t g = a.gt ? a.gt[r] : -1;
+    a.gt_rank[r] = (a.gt && g >= a.lo && g < a.V) ? (int32_t)(1 + s_beat) : 0;
+  }
+}
+
+int64_t chunks_of(int32_t V) { return ((int64_t)V + FCH - 1) / FCH; }
+int64_t cap_of(int32_t K) { return std::min<int64_t>(K, FCH); }
+int64_t row_bytes(int32_t V, int32_t K) { return chunks_of(V) * (cap_of(K) * 8 + 8) + 4; }   // scores, ids | counts, beats | gt key
+
+}  // namespace
+
+extern "C" int64_t b4r_rank_full_scratch_bytes(int32_t R, int32_t V, int32_t K) {
+  if (R <= 0 || V <= 0 || K < 0 || K > FK_MAX) return 0;
+  return (int64_t)R * row_bytes(V, K) + 64;   // + room for the 16-byte alignment of the regions
+}
+
+extern "C" int b4r_rank_full(const float* hidden, int32_t hidden_ld, const int64_t* hidden_row, const float* table, const float* bias,
+                             int32_t H, int32_t V, int32_t first_item, int32_t R, const int64_t* exclude, int32_t E, const int64_t* gt,
+                             int32_t K, int64_t* topk_ids, float* topk_scores, int32_t* gt_rank, void* scratch, int64_t scratch_bytes,
+                             b4r_stream_t stream) {
+  B4R_CHECK_ARG(R >= 0 && K >= 0 && K <= FK_MAX && E >= 0 && first_item >= 0, B4R_E_SHAPE,
+                "b4r_rank_full: bad shape (R = %d, K = %d in [0, %d], E = %d, first_item = %d)", R, K, FK_MAX, E, first_item);
+  B4R_CHECK_ARG(H > 0 && H % 4 == 0 && H <= 4096 && hidden_ld >= H && V > 0, B4R_E_SHAPE,
+                "b4r_rank_full: bad shape (H = %d, hidden_ld = %d, V = %d)", H, hidden_ld, V);
+  if (R == 0) return B4R_OK;
+  B4R_CHECK_ARG(hidden && table && bias, B4R_E_BADARG, "b4r_rank_full: null argument");
+  B4R_CHECK_ARG(E == 0 || exclude, B4R_E_BADARG, "b4r_rank_full: exclude is NULL with E = %d", E);
+  B4R_CHECK_ARG(b4r_aligned16(table), B4R_E_ALIGN, "b4r_rank_full: the table must be 16-byte aligned");
+  const int64_t per_row = row_bytes(V, K);
+  const int64_t usable = scratch ? scratch_bytes - (int64_t)((16 - ((uintptr_t)scratch & 15)) & 15) : 0;
+  int64_t group = usable > 0 ? usable / per_row : 0;
+  group = std::min<int64_t>(group, R);
+  if (group < R) group = group / FG * FG;   // whole sweep groups
+  B4R_CHECK_ARG(group >= std::min<int64_t>(R, FG), B4R_E_NOMEM,
+                "b4r_rank_full: scratch of %lld bytes is too small: %lld bytes per row, %d rows at least (b4r_rank_full_scratch_bytes)",
+                (long long)scratch_bytes, (long long)per_row, std::min<int32_t>(R, FG));
+  group = std::min<int64_t>(group, 65535LL * FG);
+  hipStream_t s = (hipStream_t)stream;
+  const int nch = (int)chunks_of(V);
+  B4R_CHECK_ARG(nch <= 65535, B4R_E_SHAPE, "b4r_rank_full: V = %d is too large", V);
+  const int cap = (int)cap_of(K);
+  char* p = reinterpret_cast<char*>(((uintptr_t)scratch + 15) & ~(uintptr_t)15);
+  float* c_score = reinterpret_cast<float*>(p);
+  int32_t* c_id = reinterpret_cast<int32_t*>(c_score + group * nch * cap);
+  int32_t* c_cnt = c_id + group * nch * cap;
+  int32_t* c_beat = c_cnt + group * nch;
+  uint32_t* gkey = reinterpret_cast<uint32_t*>(c_beat + group * nch);
+  for (int64_t r0 = 0; r0 < R; r0 += group) {
+    const int n = (int)std::min<int64_t>(group, R - r0);
+    if (gt) {
+      hipLaunchKernelGGL(full_gt_key_kernel, dim3(b4r_cdiv(n, 64)), dim3(64), 0, s, hidden, hidden_ld, hidden_row, table, bias, H, V,
+                         first_item, gt, r0, n, gkey);
+    }
+    SweepArgs sa{hidden, hidden_row, table, bias, exclude, gt, gkey, c_score, c_id, c_cnt, c_beat, r0,
+                 hidden_ld, H, V, first_item, E, n, nch, cap};
+    hipLaunchKernelGGL(full_sweep_kernel, dim3(b4r_cdiv(n, FG), nch), dim3(FT), 0, s, sa);
+    MergeArgs ma{c_score, c_id, c_cnt, c_beat, gt, topk_ids, topk_scores, gt_rank, r0, nch, cap, K, first_item, V};
+    hipLaunchKernelGGL(full_merge_kernel, dim3(n), dim3(FT), 0, s, ma);
+  }
+  B4R_CHECK_LAUNCH("b4r_rank_full");
+  return B4R_OK;
+}

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import operator
 from typing import Dict, Iterable, List, Optional, Tuple
 
 import torch
@@ -121,6 +122,26 @@ def device_mask_batch(tokens: torch.Tensor, max_predictions: int, vocab_size: in
 # hipGraph captures only contain this library's launches on the capturing thread; "thread_local" keeps runtime calls made by
 # other threads of the process during the capture (the RCCL watchdog polls events) from invalidating it
 _CAPTURE_MODE = "thread_local"
+
+
+RANK_FULL_MAX_K = 1024
+SPECIAL_IDS = 3   # [PAD] 0, [MASK] 1, [UNK] 2: never ranked by the full-catalogue path of the model
+
+
+def check_rank_full_args(k, exclude: Optional[torch.Tensor] = None, n_rows: Optional[int] = None) -> int:
+    """Argument checks of Engine.rank_full that need no GPU: 0 <= k <= 1024, exclude None or [R, E]."""
+    try:
+        k = operator.index(k)
+    except TypeError:
+        raise ValueError(f"k must be an integer, got {k!r}") from None
+    if k < 0 or k > RANK_FULL_MAX_K:
+        raise ValueError(f"k must lie in [0, {RANK_FULL_MAX_K}], got {k}")
+    if exclude is not None:
+        if exclude.ndim != 2:
+            raise ValueError(f"exclude must be rank 2 [rows, ids], got shape {tuple(exclude.shape)}")
+        if n_rows is not None and exclude.shape[0] != n_rows:
+            raise ValueError(f"exclude has {exclude.shape[0]} rows for {n_rows} ranked rows")
+    return k
 
 
 class Engine:
@@ -543,6 +564,41 @@ class Engine:
                                                 0 if scratch is None else scratch.numel() * 4,
                                                 _stream(self.device)), "b4r_rank_candidates")
         return ranking, gt_rank, scores
+
+    def rank_full(self, hidden: torch.Tensor, rows: Optional[torch.Tensor], exclude: Optional[torch.Tensor], first_item: int,
+                  gt: Optional[torch.Tensor], k: int):
+        """b4r_rank_full on `hidden` [*,H] (ld = stride(0)): rows [R] (hidden row of each ranked row) or None (R = hidden rows);
+        exclude [R,E] int64 ids not to rank (-1 padded) or None; gt [R] int64 or None.  Returns (ids [R,k] int64, scores [R,k] fp32,
+        gt_rank [R] int32 or None): the best k allowed items of every row over the whole vocabulary, ties to the lower id, -1 / -inf
+        where fewer than k are allowed.  The scratch buffer is kept between calls."""
+        R = int(rows.numel()) if rows is not None else int(hidden.shape[0])
+        k = check_rank_full_args(k, exclude, R)
+        if hidden.dtype != torch.float32 or hidden.ndim != 2 or hidden.stride(1) != 1 or hidden.shape[1] != self.cfg.hidden_size:
+            raise ValueError(f"hidden must be float32 [rows, {self.cfg.hidden_size}] with unit column stride")
+        rows_d = None if rows is None else rows.to(device=self.device, dtype=torch.int64).contiguous()
+        ex_d = None if exclude is None or exclude.shape[1] == 0 else exclude.to(device=self.device, dtype=torch.int64).contiguous()
+        E = 0 if ex_d is None else int(ex_d.shape[1])
+        gt_d = None if gt is None else gt.to(device=self.device, dtype=torch.int64).contiguous()
+        if gt_d is not None and gt_d.numel() != R:
+            raise ValueError(f"{gt_d.numel()} ground-truth ids for {R} rows")
+        ids = torch.empty((R, k), dtype=torch.int64, device=self.device)
+        scores = torch.empty((R, k), dtype=torch.float32, device=self.device)
+        gt_rank = torch.empty((R,), dtype=torch.int32, device=self.device) if gt_d is not None else None
+        if R == 0:
+            return ids, scores, gt_rank
+        V = self.cfg.vocab_size
+        need = int(self.lib.b4r_rank_full_scratch_bytes(R, V, k))
+        least = int(self.lib.b4r_rank_full_scratch_bytes(min(R, 16), V, k))
+        want = min(need, max(least, 2 << 30))   # at most 2 GiB: more rows are then ranked in groups
+        sc = getattr(self, "_rank_full_scratch", None)
+        if sc is None or sc.numel() < want:
+            sc = self._rank_full_scratch = torch.empty(want, dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.b4r_rank_full(_ptr(hidden), hidden.stride(0), _ptr(rows_d),
+                                          _ptr(self.view("word_embeddings/embeddings")),
+                                          _ptr(self.view("cls/predictions/output_bias/bias")), self.cfg.hidden_size, V, int(first_item),
+                                          R, _ptr(ex_d), E, _ptr(gt_d), k, _ptr(ids), _ptr(scores), _ptr(gt_rank), _ptr(sc),
+                                          sc.numel(), _stream(self.device)), "b4r_rank_full")
+        return ids, scores, gt_rank
 
     def rank_metrics(self, gt_rank: torch.Tensor, families, cutoffs, gain_sums: torch.Tensor, users: torch.Tensor) -> None:
         """b4r_rank_metrics: add this batch's gain sums to the device accumulators (float64 [n], int64 [1])."""

@@ -9,13 +9,19 @@ and under torch.distributed the batches are dealt round-robin to the ranks with 
 ("shard users across ranks ... one 8-float all-reduce").  With the popularity sampler the 100
 negatives of every slot of a batch are drawn by one b4r_sample_candidates launch as well (`device_sampling`, default on
 when the model runs on a GPU): same distribution as the reference's per-slot np.random.choice, own random stream;
-`sample_candidates` keeps the reference's host procedure (pinned by the golden vectors)."""
+`sample_candidates` keeps the reference's host procedure (pinned by the golden vectors).
+
+full_ranking=True replaces the sampled protocol by full-catalogue ranking (the protocol of the BERT4Rec replication studies): no
+negatives are drawn, every test slot's ground truth is ranked against the whole vocabulary minus [PAD] / [MASK] / [UNK] and the ids
+in the row's `labels` (the ground truth itself always stays), by one b4r_rank_full launch per batch; the ranks feed the same metric
+sums.  The default keeps the sampled protocol exactly."""
 from typing import Union
 
 import numpy as np
 import torch
 
 from ..dataloaders import samplers
+from ..engine import SPECIAL_IDS
 from .base_evaluator import BaseEvaluator
 from .evaluation_metrics import HR, MAP, NDCG, Counter, EvaluationMetric, gain_table
 
@@ -27,8 +33,9 @@ def default_metrics():
 
 class BERT4RecEvaluator(BaseEvaluator):
     def __init__(self, metrics: list = None, sampler: Union[str, "samplers.BaseSampler"] = "pop_random", dataloader=None,
-                 device_sampling: bool = True, seed: int = 0):
+                 device_sampling: bool = True, seed: int = 0, full_ranking: bool = False):
         self.device_sampling = device_sampling
+        self.full_ranking = bool(full_ranking)
         self._dev = None   # (engine, float64 gain sums [n_metrics], int64 user count [1]) on the GPU
         self._seed = int(seed)
         self._draws = 0
@@ -50,7 +57,7 @@ class BERT4RecEvaluator(BaseEvaluator):
     def evaluate(self, model, test_data, group=None) -> list:
         """bert4rec_evaluator.py:46-58.  With an initialised torch.distributed process group (`group`, default WORLD) rank k
         evaluates batches k, k + world, ... and every rank ends with the metrics of ALL users."""
-        if self.dataloader is None and not self.sampler.is_fully_prepared():
+        if not self.full_ranking and self.dataloader is None and not self.sampler.is_fully_prepared():
             raise ValueError("The evaluator has to be either initialized with a dataloader or a fully prepared sampler "
                              "has to be given.")
         rank, world = _dist_rank_world(group)
@@ -203,6 +210,8 @@ class BERT4RecEvaluator(BaseEvaluator):
         """bert4rec_evaluator.py:60-120 for one batch.  Returns the ground-truth ranks: a device int32 tensor when the metric
         sums are accumulated on the GPU (flushed by evaluate() / get_metrics_results()), else a numpy array."""
         slots = None
+        if self.full_ranking and candidates is None:
+            return self._evaluate_batch_full(model, test_batch)
         if candidates is None:
             if self._device_sampler_ready(model):
                 candidates, ground_truth = self.sample_candidates_device(model, test_batch)
@@ -218,6 +227,31 @@ class BERT4RecEvaluator(BaseEvaluator):
                                                    want_ranking=False, **extra)
         engine = getattr(model, "engine", None)
         if engine is not None and gt_rank.is_cuda and len(self._metrics) <= 32:
+            _, sums, users = self._device_sums(engine)
+            table = gain_table(self._metrics)
+            engine.rank_metrics(gt_rank, [f for f, _ in table], [k for _, k in table], sums, users)
+            return gt_rank
+        ranks = gt_rank.cpu().numpy().astype(np.int64)
+        for metric in self._metrics:
+            metric.update(ranks)
+        return ranks
+
+    def _evaluate_batch_full(self, model, test_batch: dict):
+        """full_ranking: the rank of every test slot's ground truth among all items but the specials and the row's labels."""
+        engine = getattr(model, "engine", None)
+        if engine is None or engine.device.type != "cuda":
+            raise ValueError("full_ranking needs a model on the GPU (b4r_rank_full)")
+        dev = engine.device
+        w = torch.as_tensor(test_batch["masked_lm_weights"]).to(dev)
+        b_idx, p_idx = torch.nonzero(w != 0, as_tuple=True)   # batch order, then slot order
+        if b_idx.numel() == 0:
+            return []
+        slots = b_idx * w.shape[1] + p_idx
+        gt = torch.as_tensor(test_batch["masked_lm_ids"]).to(dev)[b_idx, p_idx].to(torch.int64)
+        exclude = torch.as_tensor(test_batch["labels"]).to(dev)[b_idx].to(torch.int64)   # the user's whole sequence
+        hidden, _, _ = model._ranked_slot_hidden(test_batch, slots)
+        _, _, gt_rank = engine.rank_full(hidden, None, exclude, SPECIAL_IDS, gt, 0)
+        if len(self._metrics) <= 32:
             _, sums, users = self._device_sums(engine)
             table = gain_table(self._metrics)
             engine.rank_metrics(gt_rank, [f for f, _ in table], [k for _, k in table], sums, users)

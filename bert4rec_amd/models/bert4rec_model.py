@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .. import engine as engine_mod
 from ..trainers import trainer_utils
 from ..trainers.optimizers import AdamWeightDecay
 from ..trainers import optimizers as _optimizers
@@ -313,6 +314,42 @@ class BERT4RecModel:
         for n in counts:
             out.append([ranking[r + j] for j in range(n)])
             r += n
+        return out
+
+    def recommend_tensor(self, encoder_input: Dict[str, torch.Tensor], k: int = 10, exclude_seen: bool = True,
+                         exclude: Optional[torch.Tensor] = None):
+        """Top k of the whole catalogue for every slot with masked_lm_weights == 1 (all slots when the key is absent), from one
+        b4r_rank_full call: no [R, V] scores.  The forward is rank_items_tensor's (encoder, then tfm MaskedLM's transform on those
+        slots only).  [PAD] / [MASK] / [UNK] are never recommended; exclude_seen drops the row's own input_word_ids; exclude
+        [B, E] int64 (-1 padded): more ids per batch row not to recommend.  Returns (ids [R,k] int64, scores [R,k] fp32,
+        slot_index [R] int64 = b*P+p), on the device; a row with fewer than k allowed items ends in -1 / -inf."""
+        k = engine_mod.check_rank_full_args(k, exclude)
+        hidden, slots, _ = self._ranked_slot_hidden(encoder_input)
+        dev = self.device
+        if hidden is None:
+            return (torch.empty((0, k), dtype=torch.int64, device=dev), torch.empty((0, k), dtype=torch.float32, device=dev), slots)
+        P = int(torch.as_tensor(encoder_input["masked_lm_positions"]).shape[1])
+        b_idx = torch.div(slots, P, rounding_mode="floor")
+        parts = []
+        if exclude_seen:
+            parts.append(torch.as_tensor(encoder_input["input_word_ids"]).to(device=dev, dtype=torch.int64)[b_idx])
+        if exclude is not None:
+            ex = torch.as_tensor(exclude).to(device=dev, dtype=torch.int64)
+            B = int(torch.as_tensor(encoder_input["input_word_ids"]).shape[0])
+            if ex.shape[0] != B:
+                raise ValueError(f"exclude has {ex.shape[0]} rows for a batch of {B}")
+            parts.append(ex[b_idx])
+        ex_rows = torch.cat(parts, dim=1) if parts else None
+        ids, scores, _ = self.engine.rank_full(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, k)
+        return ids, scores, slots
+
+    def recommend(self, encoder_input: dict, k: int = 10, exclude_seen: bool = True, exclude=None):
+        """recommend_tensor as Python lists: per batch row, one list per ranked slot of (ids, scores) lists of length k."""
+        ids, scores, slots = self.recommend_tensor(encoder_input, k, exclude_seen, exclude)
+        B, P = (int(x) for x in torch.as_tensor(encoder_input["masked_lm_positions"]).shape)
+        out = [[] for _ in range(B)]
+        for s, i_row, s_row in zip(slots.cpu().tolist(), ids.cpu().tolist(), scores.cpu().tolist()):
+            out[s // P].append((i_row, s_row))
         return out
 
     def _rank_items_ragged(self, encoder_input, items):

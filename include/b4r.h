@@ -254,6 +254,26 @@ int b4r_rank_candidates(const float* hidden, int32_t hidden_ld, const int64_t* h
                         const float* bias, int32_t H, int32_t V, const int64_t* cand, int32_t R, int32_t C, const int64_t* gt,
                         int64_t* ranking, int32_t* gt_rank, float* scores, void* scratch, int64_t scratch_bytes,
                         b4r_stream_t stream);
+/* ---- full-catalogue top K and held-out rank (batched recommendation, full-ranking evaluation) ---------------------------
+ * One sweep over the vocabulary for groups of rows, no [R, V] scores anywhere.  Row r (hidden row hidden_row[r], or r when NULL):
+ *   s(r, j)     = the b4r_rank_candidates score: fma-chain_k(hidden[.][k] * table[j][k]) + bias[j]  (k ascending, fp32, no MFMA),
+ *                 bit-equal to oracle/rank_oracle.c::rank_oracle_scores
+ *   allowed(r)  = { j in [first_item, V) : j not in exclude[r] } plus gt[r] when it lies in [first_item, V), even if listed.
+ *                 exclude [R, E] int64 (NULL when E = 0): ids outside [0, V) (-1 padding) are ignored, repeats are harmless.
+ *                 first_item = 3 keeps [PAD] / [MASK] / [UNK] out.
+ *   topk_ids[r] / topk_scores[r]  [R, K]: the first K of the stable descending order over allowed(r) (ties: lower id first) --
+ *                 b4r_rank_candidates(cand = NULL)'s ranking with the disallowed ids removed; fewer than K allowed: id -1 and
+ *                 score -inf fill the tail.  K in [0, 1024].
+ *   gt_rank[r]  = 1 + #{j in allowed: s_j > s_gt} + #{j in allowed, j < gt: s_j == s_gt}; 0 when gt is NULL or gt[r] is outside
+ *                 [first_item, V).  Any output may be NULL.
+ * scratch: b4r_rank_full_scratch_bytes(R, V, K) bytes for one pass over all rows (it grows with R * ceil(V / 1024) * min(K, 1024),
+ * not with R * V); a smaller scratch ranks the rows in groups of 16, and one too small for a group returns B4R_E_NOMEM.  Only
+ * enqueues (three launches per group, one stream, no host sync, graph-capturable); integer counting only, bitwise reproducible.
+ * Non-finite hidden values are outside the contract (they are never read out of bounds). */
+int64_t b4r_rank_full_scratch_bytes(int32_t R, int32_t V, int32_t K);
+int b4r_rank_full(const float* hidden, int32_t hidden_ld, const int64_t* hidden_row, const float* table, const float* bias, int32_t H,
+                  int32_t V, int32_t first_item, int32_t R, const int64_t* exclude, int32_t E, const int64_t* gt, int32_t K,
+                  int64_t* topk_ids, float* topk_scores, int32_t* gt_rank, void* scratch, int64_t scratch_bytes, b4r_stream_t stream);
 /* replaces the metric loop of bert4rec_evaluator.py:118-120 over evaluation_metrics.py:47-112 for a batch of ranks:
  * gain_sums[m] += sum over gt_rank[i] > 0 of gain_m(gt_rank[i]), users[0] += #{gt_rank[i] > 0}; double / int64 DEVICE
  * accumulators the caller reads once per evaluate().  family[m]: 0 count (gain 1), 1 hit@cutoff (rank <= k), 2 NDCG@cutoff
