@@ -70,13 +70,13 @@ int b4r_optimizer_fused(const b4r_adamw_config* hp, float* params, const float* 
                         int64_t n_decay, float* scratch, b4r_train_state* state, hipStream_t stream, int sums_from_tail = 0,
                         int np_given = 0);
 // internal flag of b4r_backward (b4r_train_step sets it): the closing reduce launch also leaves the partial sums of squares of the
-// gradients at the start of the workspace (dead by then) and their number in g_norm_np, so that the optimizer needs no norm launch
+// gradients at the start of the workspace (dead by then) and their number in backward_impl's norm_np, so that the optimizer needs no
+// norm launch
 #define B4R_FLAG_NORM_PARTIALS_INTERNAL (1 << 20)
 // internal flag of b4r_forward AND b4r_backward of one train step (b4r_train_step sets it on both; fused head + B4R_FLAG_LOSS_SUMS):
 // the forward runs the head's vocabulary sweep only, the backward's dE launch merges the slices (dT, loss rows, lse, labels) in its
 // prologue and the loss / metric sums are formed by one extra workgroup of the embedding-gradient launch -- one launch fewer
 #define B4R_FLAG_DEFER_COMBINE_INTERNAL (1 << 21)
-static thread_local int g_norm_np = 0;
 
 // ---- error message (thread local) ---------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -341,31 +341,23 @@ int check_batch(const b4r_batch* b, const b4r_model_config* c, bool need_mlm) {
     if (rc__ != B4R_OK) return rc__; \
   } while (0)
 
-int gemm(const float* A, int lda, const float* Bm, int ldb, float* C, int ldc, int M, int N, int K, int b_is_nk, int epi,
-         const float* bias, float* C2, int ldc2, const float* R, int ldr, float qscale, int qcols, const uint32_t* rng,
-         uint32_t stream_id, float rate, int a_dropout, hipStream_t s) {
-  b4r_gemm_desc d{};
-  d.A = A; d.lda = lda; d.B = Bm; d.ldb = ldb; d.C = C; d.ldc = ldc; d.M = M; d.N = N; d.K = K;
-  d.b_is_nk = b_is_nk; d.epilogue = epi; d.bias = bias; d.C2 = C2; d.ldc2 = ldc2; d.R = R; d.ldr = ldr;
-  d.qscale = qscale; d.qcols = qcols; d.rng = rng; d.drop_stream = stream_id; d.drop_rate = rate; d.a_dropout = a_dropout;
-  d.c_pad_scratch = 1;  // every C of the model path is a workspace region whose pad columns are scratch
-  return b4r_gemm_f32(&d, (b4r_stream_t)s);
-}
+int gemm_f32(const b4r_gemm_desc& d, hipStream_t s) { return b4r_gemm_f32(&d, s); }
+int gemm_tn_f32(const b4r_gemm_tn_desc& d, float* scratch, hipStream_t s) { return b4r_gemm_tn_f32(&d, scratch, s); }
+int64_t ln_scratch_floats(int N, int H) { return std::max(b4r_ln_bwd_scratch_floats(N, H), b4r_gemm_ln_bwd_partial_floats(N)); }
 
 // dense + bias + dropout + residual (-> z) + LayerNorm (-> y, mean, rstd): one launch where b4r_gemm_ln_supported (hidden
 // size 64 in the bf16x3 mode), else the product with B4R_EPI_BIAS_DROP_RES followed by b4r_ln_fwd.
 int dense_res_ln(const float* A, int lda, const float* W, float* z, float* y, float* mean, float* rstd, int M, int H, int K,
                  const float* bias, const float* R, const float* gamma, const float* beta, float eps, const uint32_t* rng,
                  uint32_t stream_id, float rate, hipStream_t s) {
-  b4r_gemm_desc d{};
-  d.A = A; d.lda = lda; d.B = W; d.ldb = H; d.C = z; d.ldc = H; d.M = M; d.N = H; d.K = K;
-  d.epilogue = B4R_EPI_BIAS_DROP_RES_LN; d.bias = bias; d.C2 = y; d.ldc2 = H; d.R = R; d.ldr = H; d.qscale = 1.f;
-  d.rng = rng; d.drop_stream = stream_id; d.drop_rate = rate; d.c_pad_scratch = 1;
-  d.ln_gamma = gamma; d.ln_beta = beta; d.ln_mean = mean; d.ln_rstd = rstd; d.ln_eps = eps;
-  if (b4r_gemm_ln_supported(&d)) return b4r_gemm_f32(&d, (b4r_stream_t)s);
+  b4r_gemm_desc d{.A = A, .lda = lda, .B = W, .ldb = H, .C = z, .ldc = H, .M = M, .N = H, .K = K, .epilogue = B4R_EPI_BIAS_DROP_RES_LN,
+                  .bias = bias, .C2 = y, .ldc2 = H, .R = R, .ldr = H, .qscale = 1.f, .rng = rng, .drop_stream = stream_id,
+                  .drop_rate = rate, .c_pad_scratch = 1, .ln_gamma = gamma, .ln_beta = beta, .ln_mean = mean, .ln_rstd = rstd,
+                  .ln_eps = eps};
+  if (b4r_gemm_ln_supported(&d)) return gemm_f32(d, s);
   d.epilogue = B4R_EPI_BIAS_DROP_RES; d.C2 = nullptr; d.ldc2 = 0;
-  RC(b4r_gemm_f32(&d, (b4r_stream_t)s));
-  return b4r_ln_fwd(z, M, H, gamma, beta, eps, y, mean, rstd, (b4r_stream_t)s);
+  RC(gemm_f32(d, s));
+  return b4r_ln_fwd(z, M, H, gamma, beta, eps, y, mean, rstd, s);
 }
 
 // input-gradient product + residual gradient + the LayerNorm backward in front of it:  dz = LN'(A.W^T + R)  (W as [N=H, K]).
@@ -375,64 +367,117 @@ int dgrad_ln_bwd(const float* A, int lda, const float* W, int K, const float* R,
                  const float* mean, const float* rstd, const float* gamma, float* dgamma, float* dbeta, float* scratch,
                  hipStream_t s, const int64_t* ids = nullptr, const float* table = nullptr, const float* pos_table = nullptr,
                  int L = 1, int V = 1, const uint32_t* rng = nullptr, uint32_t drop_stream = 0, float drop_rate = 0.f) {
-  b4r_gemm_desc d{};
-  d.A = A; d.lda = lda; d.B = W; d.ldb = K; d.C = dz; d.ldc = H; d.M = M; d.N = H; d.K = K; d.b_is_nk = 1;
-  d.epilogue = B4R_EPI_ADD_RES_LN_BWD; d.R = R; d.ldr = H; d.qscale = 1.f; d.c_pad_scratch = 1;
-  d.C2 = scratch; d.ln_gamma = gamma; d.ln_mean = const_cast<float*>(mean); d.ln_rstd = const_cast<float*>(rstd);
-  d.ln_z = z; d.ln_ldz = H; d.ln_dgamma = dgamma; d.ln_dbeta = dbeta;
-  d.ln_ids = ids; d.ln_table = table; d.ln_pos = pos_table; d.ln_L = L; d.ln_V = V;
-  d.rng = rng; d.drop_stream = drop_stream; d.drop_rate = drop_rate;
-  if (dbeta == dgamma + 64 && b4r_gemm_ln_supported(&d)) return b4r_gemm_f32(&d, (b4r_stream_t)s);
+  b4r_gemm_desc d{.A = A, .lda = lda, .B = W, .ldb = K, .C = dz, .ldc = H, .M = M, .N = H, .K = K, .b_is_nk = 1,
+                  .epilogue = B4R_EPI_ADD_RES_LN_BWD, .C2 = scratch, .R = R, .ldr = H, .qscale = 1.f, .rng = rng,
+                  .drop_stream = drop_stream, .drop_rate = drop_rate, .c_pad_scratch = 1, .ln_gamma = gamma,
+                  .ln_mean = const_cast<float*>(mean), .ln_rstd = const_cast<float*>(rstd), .ln_z = z, .ln_ldz = H, .ln_dgamma = dgamma,
+                  .ln_dbeta = dbeta, .ln_ids = ids, .ln_table = table, .ln_pos = pos_table, .ln_L = L, .ln_V = V};
+  if (dbeta == dgamma + 64 && b4r_gemm_ln_supported(&d)) return gemm_f32(d, s);
   d.epilogue = B4R_EPI_ADD_RES; d.C2 = nullptr; d.rng = nullptr; d.drop_rate = 0.f;
-  RC(b4r_gemm_f32(&d, (b4r_stream_t)s));
+  RC(gemm_f32(d, s));
   return b4r_ln_bwd_launch(dz, z, mean, rstd, gamma, M, H, dz, dgamma, dbeta, scratch, ids, table, pos_table, L, V,
                            b4r_make_drop(rng, drop_stream, drop_rate, 1), s, nullptr);
 }
 
-// the feed-forward half of a layer as one launch forward / two backward (b4r_ffn_rx.hip); else the separate dense launches of
-// round 1 (for the shapes / modes the fused block does not cover)
-bool ffn_fused(const b4r_model_config* c) {
-  return b4r_ffn_block_supported(c->hidden_size, c->inner_dim) != 0;
+// gather + dense(gelu) + LayerNorm of the masked-LM transform (`d`: B4R_EPI_BIAS_GELU_LN with gathered A rows): one launch where the
+// LayerNorm tail applies (hidden size 64), else the gathered rows into `gath`, the product and b4r_ln_fwd
+int transform_fwd(const b4r_gemm_desc& d, float* gath, hipStream_t s) {
+  if (b4r_gemm_ln_supported(&d)) return gemm_f32(d, s);
+  RC(b4r_gather_rows(d.A, d.lda, d.a_gather_idx, d.a_gather_add_per, d.a_gather_per, d.M, d.K, gath, s));
+  RC(gemm_f32({.A = gath, .lda = d.K, .B = d.B, .ldb = d.ldb, .C = d.C, .ldc = d.ldc, .M = d.M, .N = d.N, .K = d.K,
+               .epilogue = B4R_EPI_BIAS_GELU, .bias = d.bias, .C2 = d.C3, .ldc2 = d.ldc3, .qscale = 1.f, .c_pad_scratch = 1}, s));
+  return b4r_ln_fwd(d.C, d.M, d.N, d.ln_gamma, d.ln_beta, d.ln_eps, d.C2, d.ln_mean, d.ln_rstd, s);
 }
 
-// the attention half of a layer as one launch forward (b4r_attn_block.hip); else the three launches of round 1
-// (heads of width 32 only: the blocks and the 32-token-tile kernels behind them stage [rows][32] head slices)
-bool attn_fused(const b4r_model_config* c, int L) {
-  return head_dim(c) == 32 && b4r_attn_block_supported(c->hidden_size, c->num_heads, L) != 0;
+// dWo = ctx^T . dropmask(dz1) (+ dbo): the weight gradient of the attention output projection
+b4r_gemm_tn_desc wo_grad_desc(const float* ctx, const float* dz1, float* dWo, float* dbo, int N, int H, const uint32_t* rng,
+                              uint32_t drop_stream, float drop_rate) {
+  return {.A = ctx, .lda = H, .B = dz1, .ldb = H, .out = dWo, .ldo = H, .R = N, .Mo = H, .No = H, .colsum = dbo, .rng = rng,
+          .drop_stream = drop_stream, .drop_rate = drop_rate, .b_dropout = 1};
+}
+// ... and dWqkv = x^T . dqkv (+ dbqkv) in the same launch
+int attn_wgrad_pair(const b4r_gemm_tn_desc& d_wo, float* wo_scratch, const float* x, const float* dqkv, float* dWqkv, float* dbqkv,
+                    float* wqkv_scratch, hipStream_t s) {
+  const int N = d_wo.R, H = d_wo.Mo;
+  const b4r_gemm_tn_desc d_wqkv{.A = x, .lda = H, .B = dqkv, .ldb = 3 * H, .out = dWqkv, .ldo = 3 * H, .R = N, .Mo = H, .No = 3 * H,
+                                .colsum = dbqkv};
+  return b4r_gemm_tn_pair(&d_wo, wo_scratch, &d_wqkv, wqkv_scratch, s);
 }
 
-// ... and one launch backward (b4r_attn_block_bwd; then the forward need not store qkv); else round 1's kernels
-bool attn_bwd_fused(const b4r_model_config* c, int L) {
-  return attn_fused(c, L) && b4r_attn_block_bwd_supported(c->hidden_size, c->num_heads, L) != 0;
+// ---- the launch plan of one step ----------------------------------------------------------------------------------------------
+// Each half of an encoder layer runs in one of several forms.  plan_step picks them once for the forward and the backward of a
+// step and is the only caller of the shape predicates behind them, so what a forward stores is what the backward of the same plan
+// reads.  (The predicates read the gemm mode and the 32-token-tile length threshold: set those between steps only.)
+// AttnFwd::Block: one launch (QKV product, attention core, output projection, dropout, residual, LayerNorm; b4r_attn_block.hip).
+// SlotQuery: the last layer with the masked-LM slots as its only queries, outputs on compact [B*P, .] rows (b4r_attn32.hip).  Core:
+// the QKV product, the attention core and the output projection with its LayerNorm as launches of their own.  AttnBwd::BlockFolded:
+// the block's backward also forms dWqkv / dbqkv and dWo / dbo.  FfnForm::Block: one launch forward, two backward (b4r_ffn_rx.hip).
+// CompactRows: the last layer on the head's rows only, products on compact [B*P, .] operands (b4r_slot_rows_*).  Wide: the one-launch
+// pair of b4r_ffn32w.hip.  TileProducts: two products and the LayerNorm.
+enum class AttnFwd { Block, SlotQuery, Core };
+enum class AttnBwd { Block, BlockFolded, SlotQuery, Core };
+enum class FfnForm { Block, CompactRows, Wide, TileProducts };
+struct StepPlan {
+  bool emb_fused;         // the embedding stage runs inside the first layer's attention block
+  bool head_rows;         // B4R_FLAG_HEAD_ROWS_ONLY honoured by the last layer's fused feed-forward block ...
+  bool head_rows_dense;   // ... or by its compact products
+  bool fused_head;        // B4R_FLAG_FUSED_HEAD
+  bool defer_combine;     // B4R_FLAG_DEFER_COMBINE_INTERNAL with B4R_FLAG_LOSS_SUMS
+  bool qkv_stored;        // the attention block's forward stores qkv: a backward other than the block's reads it
+  bool x1_stored;         // ... and x1: the fused feed-forward half, which forms x1 from z1 on load, does not run
+  bool slot_only_last;    // the last layer's attention block sweeps the slots' queries only and its backward reads the slots' dz1 only
+  bool slotq_rows;        // the last layer's SlotQuery forward leaves the compact rows the compact feed-forward half reads
+  AttnFwd attn_fwd[B4R_MAX_LAYERS];
+  AttnBwd attn_bwd[B4R_MAX_LAYERS];
+  FfnForm ffn[B4R_MAX_LAYERS];
+  bool rows() const { return head_rows || head_rows_dense; }   // nothing but the head's rows leave the last layer
+};
+
+StepPlan plan_step(const b4r_model_config* c, const b4r_batch* b, uint32_t flags) {
+  const int H = c->hidden_size, I = c->inner_dim, L = b->L, P = b->P, heads = c->num_heads, last = c->num_layers - 1;
+  const bool hro = (flags & B4R_FLAG_HEAD_ROWS_ONLY) != 0, slots = b->masked_lm_positions && b->masked_lm_ids && P > 0;
+  // the halves as one launch each (attention: heads of width 32 only, the blocks stage [rows][32] head slices; its backward L <= 208)
+  const bool ffn_fused = b4r_ffn_block_supported(H, I) != 0;
+  const bool attn_fused = head_dim(c) == 32 && b4r_attn_block_supported(H, heads, L) != 0;
+  const bool attn_bwd_fused = attn_fused && b4r_attn_block_bwd_supported(H, heads, L) != 0;
+  const bool attn32 = b4r_attn32_active(H, heads, L);   // the 32-token-tile block backward: it can form the weight gradients itself
+  StepPlan p{};
+  p.emb_fused = attn_fused && c->num_layers > 0;
+  p.head_rows = hro && ffn_fused && slots;
+  // where the last feed-forward half runs as dense products (every hidden size but 64): on compact [B*P, .] operands.  Worth it when
+  // the head reads a minority of the rows (P = L / 5 at the benchmark shapes).  Those operands live inside the last layer's own dense
+  // regions (an encoder-only forward has nothing else, b4r_workspace_bytes_encoder): f / fpre / z2 / mean2 / rstd2 at the start of
+  // theirs, and in the unused upper half of fpre [N, I] (2 M <= N, 3 H + 8 <= I): x1 rows, z1 rows, the second product's output,
+  // mean1, rstd1 (compact_rows)
+  p.head_rows_dense = hro && !ffn_fused && c->num_layers > 0 && slots && 2 * P <= L && H % 32 == 0 && I >= 3 * H + 8;
+  p.fused_head = (flags & B4R_FLAG_FUSED_HEAD) != 0;
+  p.defer_combine = (flags & B4R_FLAG_DEFER_COMBINE_INTERNAL) && (flags & B4R_FLAG_LOSS_SUMS);
+  p.qkv_stored = !attn_bwd_fused;
+  p.x1_stored = !(attn_fused && ffn_fused);
+  // The block forward sweeps the slots' queries only where it is asked to (out_slot_positions) AND where its 32-token-tile kernel runs
+  // (attn32), with P <= 64, L > 64, not for layer 0 and with qkv not stored (b4r_attn32_fwd); its backward then reads the slots' dz1
+  // only (dz1_slot_positions).  Both are asked for under this one condition, so a slot-only forward never meets a dense backward.
+  p.slot_only_last = p.head_rows && attn_bwd_fused && attn32;
+  // the last layer's attention with the slots as its only queries: where that half runs as products, P <= 64, heads of width 32 (at
+  // width 64 the last layer's attention runs dense and the rows are gathered after it)
+  p.slotq_rows = p.head_rows_dense && head_dim(c) == 32 && !attn_fused && b4r_attn32_slotq_supported(L, P) &&
+                 b4r_attn32_slotq_keep_words(b->B, L, heads, P) <= b4r_attn_keep_words(b->B, L, heads);
+  // The one-launch feed-forward pair: no backward follows an encoder-only forward, so [N, inner] stays on the chip.  Inside a TRAIN
+  // step (the launch then also writes f and the pre-activation) measured per dense layer at N = 51 200 -- hidden 128: forward 102 us
+  // against 121 (two tile products + LayerNorm), backward 103 against 124; hidden 256: 323 against 320 and 403 against 313.  So:
+  // hidden 128 only.
+  const bool wide = b4r_ffn32w_supported(H, I) && ((flags & B4R_FLAG_ENCODER_ONLY) || H == 128);
+  for (int i = 0; i <= last; ++i) {
+    const bool slotq = p.slotq_rows && i == last;
+    p.attn_fwd[i] = attn_fused ? AttnFwd::Block : slotq ? AttnFwd::SlotQuery : AttnFwd::Core;
+    p.attn_bwd[i] = attn_bwd_fused ? (attn32 ? AttnBwd::BlockFolded : AttnBwd::Block) : slotq ? AttnBwd::SlotQuery : AttnBwd::Core;
+    p.ffn[i] = ffn_fused ? FfnForm::Block
+               : (p.head_rows_dense && i == last) ? FfnForm::CompactRows
+               : wide ? FfnForm::Wide : FfnForm::TileProducts;
+  }
+  return p;
 }
 
-// B4R_FLAG_HEAD_ROWS_ONLY is honoured where the last layer's feed-forward half runs as the fused block and the row list fits
-bool head_rows_ok(const b4r_model_config* c, const b4r_batch* b) {
-  return ffn_fused(c) && b->masked_lm_positions && b->masked_lm_ids && b->P > 0;
-}
-// ... and, where that half runs as dense products (every hidden size but 64), with those products on compact [B*P, .] operands: the
-// rows are gathered first (b4r_slot_rows_*).  Worth it when the head reads a minority of the rows (P = L / 5 at the benchmark shapes).
-bool head_rows_dense_ok(const b4r_model_config* c, const b4r_batch* b) {
-  return !ffn_fused(c) && c->num_layers > 0 && b->masked_lm_positions && b->masked_lm_ids && b->P > 0 && 2 * b->P <= b->L &&
-         c->hidden_size % 32 == 0 && c->inner_dim >= 3 * c->hidden_size + 8;
-}
-// The compact operands of that mode live inside the last layer's own dense regions (an encoder-only forward has nothing else,
-// b4r_workspace_bytes_encoder): f / fpre / z2 / mean2 / rstd2 at the start of theirs, and in the unused upper half of fpre [N, I]
-// (2 M <= N, 3 H + 8 <= I): x1 rows, z1 rows, the second product's output, mean1, rstd1.
-// The one-launch feed-forward pair of b4r_ffn32w.hip inside a TRAIN step (it then also writes f and the pre-activation): measured per
-// dense layer at N = 51 200 -- hidden 128: forward 102 us against 121 (two tile products + LayerNorm), backward 103 against 124; hidden
-// 256: 323 against 320 and 403 against 313.  So: hidden 128 only.
-bool ffn32w_train_ok(const b4r_model_config* c) {
-  return c->hidden_size == 128 && b4r_ffn32w_supported(c->hidden_size, c->inner_dim);
-}
-// ... and the attention half of that layer with the slots as its only queries (hidden sizes on the tile products; P <= 64; heads of
-// width 32 -- at width 64 the last layer's attention runs dense and the rows are gathered after it)
-bool slotq_layer(const b4r_model_config* c, const b4r_batch* b, uint32_t flags, int layer) {
-  return (flags & B4R_FLAG_HEAD_ROWS_ONLY) && layer == c->num_layers - 1 && head_dim(c) == 32 && head_rows_dense_ok(c, b) &&
-         !attn_fused(c, b->L) &&
-         b4r_attn32_slotq_supported(b->L, b->P) &&
-         b4r_attn32_slotq_keep_words(b->B, b->L, c->num_heads, b->P) <= b4r_attn_keep_words(b->B, b->L, c->num_heads);
-}
 struct CompactRows { int64_t x1c, z1c, yc, mean1c, rstd1c; };
 CompactRows compact_rows(const WsLayout& w, int layer, int64_t M, int64_t H, int64_t I) {
   CompactRows c;
@@ -440,22 +485,51 @@ CompactRows compact_rows(const WsLayout& w, int layer, int64_t M, int64_t H, int
   return c;
 }
 
-b4r_gemm_tn_desc tn_desc(const float* A, int lda, const float* Bm, int ldb, float* out, int ldo, int R, int Mo, int No, float* colsum,
-                         const uint32_t* rng, uint32_t stream_id, float rate, int b_dropout) {
-  b4r_gemm_tn_desc d{};
-  d.A = A; d.lda = lda; d.B = Bm; d.ldb = ldb; d.out = out; d.ldo = ldo; d.R = R; d.Mo = Mo; d.No = No;
-  d.colsum = colsum; d.rng = rng; d.drop_stream = stream_id; d.drop_rate = rate; d.b_dropout = b_dropout; d.accumulate = 0;
-  return d;
-}
+// What every form of a layer half reads: the step's shapes, buffers, plan, dropout and stream, and the backward's scratch allocator.
+struct Step {
+  const b4r_model_config& cfg; const b4r_batch& batch; const StepPlan& plan; const int32_t flags;
+  const ParamLayout pl; const WsLayout w;
+  const float* const params; float* const grads; float* const ws; b4r_train_state* const state;
+  const int B, L, P, H, I, V, N, M, last;
+  const uint32_t* const rng;   // the dropout stream (training only)
+  const float od, adp, qscale;
+  const hipStream_t s;
+  int64_t scratch_used = 0;
 
-int gemm_tn(const float* A, int lda, const float* Bm, int ldb, float* out, int ldo, int R, int Mo, int No, float* colsum,
-            float* colsum_a, const uint32_t* rng, uint32_t stream_id, float rate, int b_dropout, float* scratch,
-            hipStream_t s) {
-  b4r_gemm_tn_desc d{};
-  d.A = A; d.lda = lda; d.B = Bm; d.ldb = ldb; d.out = out; d.ldo = ldo; d.R = R; d.Mo = Mo; d.No = No;
-  d.colsum = colsum; d.colsum_a = colsum_a; d.rng = rng; d.drop_stream = stream_id; d.drop_rate = rate;
-  d.b_dropout = b_dropout; d.accumulate = 0;
-  return b4r_gemm_tn_f32(&d, scratch, (b4r_stream_t)s);
+  Step(const b4r_model_config* c, const b4r_batch* b, const StepPlan& p, const float* prm, float* g, void* workspace,
+       b4r_train_state* st, int32_t f, hipStream_t stream)
+      : cfg(*c), batch(*b), plan(p), flags(f), pl(make_param_layout(*c)), w(make_ws_layout(*c, b->B, b->L, b->P)), params(prm),
+        grads(g), ws(static_cast<float*>(workspace)), state(st), B(b->B), L(b->L), P(b->masked_lm_positions ? b->P : 0),
+        H(c->hidden_size), I(c->inner_dim), V(c->vocab_size), N(B * L), M(B * P), last(c->num_layers - 1),
+        rng((f & B4R_FLAG_TRAINING) ? reinterpret_cast<const uint32_t*>(st) : nullptr),
+        od((f & B4R_FLAG_TRAINING) ? c->output_dropout : 0.f), adp((f & B4R_FLAG_TRAINING) ? c->attention_dropout : 0.f),
+        qscale(1.0f / sqrtf((float)head_dim(c))), s(stream) {}
+  const float* prm(int64_t off) const { return params + off; }
+  float* grd(int64_t off) const { return grads + off; }
+  float* at(int64_t off) const { return ws + off; }
+  uint32_t* keep(int i) const { return reinterpret_cast<uint32_t*>(ws + w.keep[i]); }
+  // the next region of the backward's scratch; B4R_E_NOMEM, before anything is enqueued on it, where it would end past the scratch
+  int take(int64_t n, float** out) {
+    B4R_CHECK_ARG(scratch_used + up4(n) <= w.scratch_floats, B4R_E_NOMEM, "b4r_backward: internal scratch overflow");
+    *out = ws + w.scratch + scratch_used; scratch_used += up4(n);
+    return B4R_OK;
+  }
+};
+
+// the fields every form of the feed-forward half shares: shapes, weights and the output dropout
+b4r_ffn_desc ffn_desc(const Step& c, int i) {
+  b4r_ffn_desc fd{};
+  fd.N = c.N; fd.H = c.H; fd.I = c.I;
+  fd.W1 = c.prm(c.pl.w1[i]); fd.b1 = c.prm(c.pl.b1[i]); fd.W2 = c.prm(c.pl.w2[i]); fd.b2 = c.prm(c.pl.b2[i]);
+  fd.rng = c.od > 0.f ? c.rng : nullptr; fd.drop_stream = B4R_STREAM_FFN_OUT(i); fd.drop_rate = c.od;
+  return fd;
+}
+// ... and of its forward forms: the output LayerNorm and the outputs
+b4r_ffn_desc ffn_fwd_desc(const Step& c, int i) {
+  b4r_ffn_desc fd = ffn_desc(c, i);
+  fd.ln_gamma = c.prm(c.pl.ln2_g[i]); fd.ln_beta = c.prm(c.pl.ln2_b[i]); fd.ln_eps = c.cfg.ln_eps;
+  fd.z2 = c.at(c.w.z2[i]); fd.x2 = c.at(c.w.x2[i]); fd.mean2 = c.at(c.w.mean2[i]); fd.rstd2 = c.at(c.w.rstd2[i]);
+  return fd;
 }
 
 }  // namespace
@@ -485,23 +559,18 @@ extern "C" int b4r_encoder_layer_bwd(const b4r_ffn_desc* ffn, const b4r_attn_blo
   B4R_CHECK_ARG(attn && ffn && dWo && dbo && dWqkv && dbqkv && tn_scratch, B4R_E_BADARG, "b4r_encoder_layer_bwd: null argument");
   B4R_CHECK_ARG(ffn->dz1 != nullptr && attn->dz1 == ffn->dz1 && (int64_t)attn->B * attn->L == ffn->N && attn->H == ffn->H, B4R_E_BADARG,
                 "b4r_encoder_layer_bwd: the feed-forward half's dz1 [B*L,H] must be the attention half's input gradient");
-  const int N = ffn->N, H = ffn->H;
-  hipStream_t s = (hipStream_t)stream;
   RC(b4r_ffn_block_bwd(ffn, stream));
   RC(b4r_attn_block_bwd(attn, stream));
+  const b4r_gemm_tn_desc d_wo = wo_grad_desc(attn->ctx, attn->dz1, dWo, dbo, ffn->N, ffn->H, attn->out_rate > 0.f ? attn->rng : nullptr,
+                                             attn->out_stream, attn->out_rate);
   if (attn->dWqkv != nullptr) {   // the attention block formed dWqkv / dbqkv itself (its descriptor's dWqkv: same buffers expected)
     B4R_CHECK_ARG(attn->dWqkv == dWqkv && attn->dbqkv == dbqkv && (attn->dWo == nullptr || (attn->dWo == dWo && attn->dbo == dbo)),
                   B4R_E_BADARG, "b4r_encoder_layer_bwd: the attention descriptor's dWqkv / dbqkv / dWo / dbo must be the call's");
-    if (attn->dWo != nullptr) return B4R_OK;
-    const b4r_gemm_tn_desc d1 = tn_desc(attn->ctx, H, attn->dz1, H, dWo, H, N, H, H, dbo, attn->out_rate > 0.f ? attn->rng : nullptr,
-                                        attn->out_stream, attn->out_rate, 1);
-    return b4r_gemm_tn_f32(&d1, tn_scratch, stream);
+    return attn->dWo != nullptr ? B4R_OK : gemm_tn_f32(d_wo, tn_scratch, stream);
   }
-  // dWo = ctx^T . dropmask(dz1) and dWqkv = x^T . dqkv (+ their bias gradients): one launch
-  const b4r_gemm_tn_desc d_wo = tn_desc(attn->ctx, H, attn->dz1, H, dWo, H, N, H, H, dbo, attn->out_rate > 0.f ? attn->rng : nullptr,
-                                        attn->out_stream, attn->out_rate, 1);
-  const b4r_gemm_tn_desc d_wqkv = tn_desc(attn->x, H, attn->dqkv, 3 * H, dWqkv, 3 * H, N, H, 3 * H, dbqkv, nullptr, 0, 0.f, 0);
-  return b4r_gemm_tn_pair(&d_wo, tn_scratch, &d_wqkv, tn_scratch + b4r_gemm_tn_scratch_floats(N, H, H), s);
+  // dWo and dWqkv = x^T . dqkv (+ their bias gradients): one launch
+  return attn_wgrad_pair(d_wo, tn_scratch, attn->x, attn->dqkv, dWqkv, dbqkv, tn_scratch + b4r_gemm_tn_scratch_floats(ffn->N, ffn->H, ffn->H),
+                         stream);
 }
 
 // ===============================================================================================================
@@ -581,193 +650,215 @@ extern "C" int32_t b4r_fused_head_supported(const b4r_model_config* cfg) {
 }
 
 // The public entry points take the documented flags only: the internal bits (B4R_FLAG_*_INTERNAL) couple a forward and a backward
-// of ONE b4r_train_step call and are set there alone.
-static int forward_impl(const b4r_model_config* cfg, const b4r_batch* batch, const float* params, const float* pooler, void* workspace,
-                        int64_t workspace_bytes, b4r_train_state* state, int32_t flags, b4r_stream_t stream);
-static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, const float* params, float* grads, void* workspace,
-                         int64_t workspace_bytes, b4r_train_state* state, int32_t flags, b4r_stream_t stream);
+// of ONE b4r_train_step call and are set there alone.  Each plans its own call; a train step plans once for both.
+static int forward_impl(const b4r_model_config* cfg, const b4r_batch* batch, const StepPlan& plan, const float* params,
+                        const float* pooler, void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags,
+                        b4r_stream_t stream);
+static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, const StepPlan& plan, const float* params, float* grads,
+                         void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags, b4r_stream_t stream,
+                         int* norm_np);
 constexpr int32_t B4R_PUBLIC_FLAGS = 0xFFFF;
 extern "C" int b4r_forward(const b4r_model_config* cfg, const b4r_batch* batch, const float* params, const float* pooler,
                            void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags,
                            b4r_stream_t stream) {
-  return forward_impl(cfg, batch, params, pooler, workspace, workspace_bytes, state, flags & B4R_PUBLIC_FLAGS, stream);
+  RC(check_cfg(cfg));
+  RC(check_batch(batch, cfg, false));
+  flags &= B4R_PUBLIC_FLAGS;
+  return forward_impl(cfg, batch, plan_step(cfg, batch, flags), params, pooler, workspace, workspace_bytes, state, flags, stream);
 }
 extern "C" int b4r_backward(const b4r_model_config* cfg, const b4r_batch* batch, const float* params, float* grads,
                             void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags,
                             b4r_stream_t stream) {
-  return backward_impl(cfg, batch, params, grads, workspace, workspace_bytes, state, flags & B4R_PUBLIC_FLAGS, stream);
+  RC(check_cfg(cfg));
+  RC(check_batch(batch, cfg, true));
+  flags &= B4R_PUBLIC_FLAGS;   // (no backward follows an encoder-only forward: that flag picks forward forms only)
+  return backward_impl(cfg, batch, plan_step(cfg, batch, flags & ~B4R_FLAG_ENCODER_ONLY), params, grads, workspace, workspace_bytes,
+                       state, flags, stream, nullptr);
 }
 
-static int forward_impl(const b4r_model_config* cfg, const b4r_batch* batch, const float* params, const float* pooler, void* workspace,
-                        int64_t workspace_bytes, b4r_train_state* state, int32_t flags, b4r_stream_t stream) {
-  RC(check_cfg(cfg));
-  RC(check_batch(batch, cfg, false));
+// ===============================================================================================================
+// the forms of the forward (the plan picks them; forward_impl runs them layer by layer)
+namespace {
+
+// AttnFwd::Block: the descriptor of the one-launch attention half (for the first layer with the embedding stage inside)
+b4r_attn_block_desc attn_block_desc(const Step& c, int i, const float* x) {
+  const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
+  b4r_attn_block_desc ad{};
+  ad.B = c.B; ad.L = c.L; ad.H = c.H; ad.heads = c.cfg.num_heads; ad.x = x; ad.input_mask = c.batch.input_mask;
+  ad.Wqkv = c.prm(pl.wqkv[i]); ad.bqkv = c.prm(pl.bqkv[i]); ad.Wo = c.prm(pl.wo[i]); ad.bo = c.prm(pl.bo[i]);
+  ad.ln_gamma = c.prm(pl.ln1_g[i]); ad.ln_beta = c.prm(pl.ln1_b[i]); ad.ln_eps = c.cfg.ln_eps;
+  ad.rng = (c.od > 0.f || c.adp > 0.f) ? c.rng : nullptr;
+  ad.probs_stream = B4R_STREAM_ATTN_PROBS(i); ad.probs_rate = c.adp; ad.out_stream = B4R_STREAM_ATTN_OUT(i); ad.out_rate = c.od;
+  ad.qkv = c.plan.qkv_stored ? c.at(w.qkv[i]) : nullptr;
+  ad.ctx = c.at(w.ctx[i]); ad.lse = c.at(w.lse[i]); ad.keep_bits = c.keep(i);
+  ad.z1 = c.at(w.z1[i]); ad.mean1 = c.at(w.mean1[i]); ad.rstd1 = c.at(w.rstd1[i]);
+  ad.x1 = c.plan.x1_stored ? c.at(w.x1[i]) : nullptr;
+  if (c.plan.slot_only_last && i == c.last) {   // nothing but the head's rows leave the last layer: only those queries are swept
+    ad.out_slot_positions = c.batch.masked_lm_positions; ad.out_slots = c.batch.P;
+  }
+  if (i == 0 && c.plan.emb_fused) {
+    ad.emb_ids = c.batch.input_word_ids; ad.emb_table = c.prm(pl.word_emb); ad.emb_pos = c.prm(pl.pos_emb); ad.emb_vocab = c.V;
+    ad.emb_gamma = c.prm(pl.emb_ln_g); ad.emb_beta = c.prm(pl.emb_ln_b); ad.emb_eps = c.cfg.ln_eps;
+    ad.emb_stream = B4R_STREAM_EMB; ad.emb_rate = c.od; if (c.od > 0.f) ad.rng = c.rng;
+    ad.emb_x = c.at(c.w.x0); ad.emb_mean = c.at(c.w.mean0); ad.emb_rstd = c.at(c.w.rstd0);
+  }
+  return ad;
+}
+
+// the QKV product of the other two forms: qkv = x.Wqkv + bqkv, the queries times 1/sqrt(head width)
+int qkv_fwd(const Step& c, int i, const float* x) {
+  return gemm_f32({.A = x, .lda = c.H, .B = c.prm(c.pl.wqkv[i]), .ldb = 3 * c.H, .C = c.at(c.w.qkv[i]), .ldc = 3 * c.H, .M = c.N,
+                   .N = 3 * c.H, .K = c.H, .epilogue = B4R_EPI_BIAS_QSCALE, .bias = c.prm(c.pl.bqkv[i]), .qscale = c.qscale,
+                   .qcols = c.H, .c_pad_scratch = 1}, c.s);
+}
+
+// AttnFwd::SlotQuery: only the rows the head reads leave this layer: the attention core with the slots as its queries (keys: all
+// tokens), then the output projection, dropout, residual and LayerNorm on the compact [M, H] rows.  ctx / lse / decision words:
+// compact, at the start of the layer's dense regions; x1 / z1 / statistics: where the compact feed-forward half expects them
+int attn_fwd_slotq(const Step& c, int i, const float* x) {
+  const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
+  const int64_t* pos = c.batch.masked_lm_positions;
+  const CompactRows cr = compact_rows(w, i, c.M, c.H, c.I);
+  float* xc = c.at(w.x1[i]);   // the layer input's rows (the residual)
+  float* yc = c.at(w.x1[i] + up4((int64_t)c.M * c.H));
+  RC(qkv_fwd(c, i, x));
+  RC(b4r_attn32_slotq_fwd_launch(c.at(w.qkv[i]), c.batch.input_mask, pos, c.B, c.L, c.cfg.num_heads, c.P, c.at(w.ctx[i]),
+                                 c.at(w.lse[i]), b4r_make_drop(c.rng, B4R_STREAM_ATTN_PROBS(i), c.adp, 1), c.keep(i), c.s));
+  RC(b4r_slot_rows_gather(x, nullptr, nullptr, nullptr, pos, c.L, c.P, c.M, c.H, xc, nullptr, nullptr, nullptr, c.s));
+  RC(gemm_f32({.A = c.at(w.ctx[i]), .lda = c.H, .B = c.prm(pl.wo[i]), .ldb = c.H, .C = yc, .ldc = c.H, .M = c.M, .N = c.H, .K = c.H,
+               .epilogue = B4R_EPI_BIAS, .bias = c.prm(pl.bo[i]), .qscale = 1.f, .c_pad_scratch = 1}, c.s));
+  return b4r_slot_rows_tail(yc, xc, pos, c.L, c.P, c.M, c.H, c.prm(pl.ln1_g[i]), c.prm(pl.ln1_b[i]), c.cfg.ln_eps,
+                            b4r_make_drop(c.rng, B4R_STREAM_ATTN_OUT(i), c.od, 1), c.at(cr.z1c), c.at(cr.mean1c), c.at(cr.rstd1c),
+                            nullptr, c.at(cr.x1c), c.s);
+}
+
+// AttnFwd::Core
+int attn_fwd_core(const Step& c, int i, const float* x) {
+  const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
+  RC(qkv_fwd(c, i, x));
+  RC(b4r_attn_fwd_hd(c.at(w.qkv[i]), c.batch.input_mask, c.B, c.L, c.cfg.num_heads, head_dim(&c.cfg), c.at(w.ctx[i]), c.at(w.lse[i]),
+                     c.rng, B4R_STREAM_ATTN_PROBS(i), c.adp, c.keep(i), c.s));
+  return dense_res_ln(c.at(w.ctx[i]), c.H, c.prm(pl.wo[i]), c.at(w.z1[i]), c.at(w.x1[i]), c.at(w.mean1[i]), c.at(w.rstd1[i]), c.N, c.H,
+                      c.H, c.prm(pl.bo[i]), x, c.prm(pl.ln1_g[i]), c.prm(pl.ln1_b[i]), c.cfg.ln_eps, c.rng, B4R_STREAM_ATTN_OUT(i), c.od,
+                      c.s);
+}
+
+// FfnForm::Block (on the last layer of a head-rows step: only the rows the head reads, nothing else of this output is looked at)
+int ffn_fwd_block(const Step& c, int i) {
+  b4r_ffn_desc fd = ffn_fwd_desc(c, i);
+  fd.x1 = c.plan.x1_stored ? c.at(c.w.x1[i]) : nullptr;
+  fd.z1 = c.at(c.w.z1[i]); fd.mean1 = c.at(c.w.mean1[i]); fd.rstd1 = c.at(c.w.rstd1[i]);
+  fd.ln1_gamma = c.prm(c.pl.ln1_g[i]); fd.ln1_beta = c.prm(c.pl.ln1_b[i]);
+  if (c.plan.head_rows && i == c.last) {
+    fd.slot_positions = c.batch.masked_lm_positions; fd.slot_ids = c.batch.masked_lm_ids; fd.slots_per_seq = c.batch.P;
+    fd.seq_len = c.L; fd.max_rows = (int32_t)c.w.maxrows;
+  }
+  return b4r_ffn_block_fwd(&fd, c.s);
+}
+
+// FfnForm::CompactRows: gather x1 (and, for the backward, z1 and its statistics) -- unless the SlotQuery attention left them --, the two
+// products on [M, .] operands, then dropout + residual + LayerNorm per compact row with the result scattered to its row of x2.  The
+// compact f / fpre / z2 / mean2 / rstd2 lie at the start of the layer's dense regions (the backward of this form reads them there).
+int ffn_fwd_compact(const Step& c, int i) {
+  const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
+  const int64_t* pos = c.batch.masked_lm_positions;
+  const CompactRows cr = compact_rows(w, i, c.M, c.H, c.I);
+  if (!c.plan.slotq_rows)
+    RC(b4r_slot_rows_gather(c.at(w.x1[i]), c.at(w.z1[i]), c.at(w.mean1[i]), c.at(w.rstd1[i]), pos, c.L, c.P, c.M, c.H, c.at(cr.x1c),
+                            c.at(cr.z1c), c.at(cr.mean1c), c.at(cr.rstd1c), c.s));
+  RC(gemm_f32({.A = c.at(cr.x1c), .lda = c.H, .B = c.prm(pl.w1[i]), .ldb = c.I, .C = c.at(w.f[i]), .ldc = c.I, .M = c.M, .N = c.I,
+               .K = c.H, .epilogue = B4R_EPI_BIAS_GELU, .bias = c.prm(pl.b1[i]), .C2 = c.at(w.fpre[i]), .ldc2 = c.I, .qscale = 1.f,
+               .c_pad_scratch = 1}, c.s));
+  RC(gemm_f32({.A = c.at(w.f[i]), .lda = c.I, .B = c.prm(pl.w2[i]), .ldb = c.H, .C = c.at(cr.yc), .ldc = c.H, .M = c.M, .N = c.H,
+               .K = c.I, .epilogue = B4R_EPI_BIAS, .bias = c.prm(pl.b2[i]), .qscale = 1.f, .c_pad_scratch = 1}, c.s));
+  return b4r_slot_rows_tail(c.at(cr.yc), c.at(cr.x1c), pos, c.L, c.P, c.M, c.H, c.prm(pl.ln2_g[i]), c.prm(pl.ln2_b[i]), c.cfg.ln_eps,
+                            b4r_make_drop(c.rng, B4R_STREAM_FFN_OUT(i), c.od, 1), c.at(w.z2[i]), c.at(w.mean2[i]), c.at(w.rstd2[i]),
+                            c.at(w.x2[i]), nullptr, c.s);
+}
+
+// FfnForm::Wide.  After an encoder-only forward no backward follows: [N, inner] stays on the chip; otherwise the launch also writes f
+// and the pre-activation, where the backward of this step expects them
+int ffn_fwd_wide(const Step& c, int i) {
+  const bool keep = !(c.flags & B4R_FLAG_ENCODER_ONLY);
+  b4r_ffn_desc fd = ffn_fwd_desc(c, i);
+  fd.x1 = c.at(c.w.x1[i]);
+  return b4r_ffn32w_fwd(&fd, c.at(c.w.ffnrec[i]), keep ? c.at(c.w.f[i]) : nullptr, keep ? c.at(c.w.fpre[i]) : nullptr, c.s);
+}
+
+// FfnForm::TileProducts
+int ffn_fwd_tiles(const Step& c, int i) {
+  const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
+  RC(gemm_f32({.A = c.at(w.x1[i]), .lda = c.H, .B = c.prm(pl.w1[i]), .ldb = c.I, .C = c.at(w.f[i]), .ldc = c.I, .M = c.N, .N = c.I,
+               .K = c.H, .epilogue = B4R_EPI_BIAS_GELU, .bias = c.prm(pl.b1[i]), .C2 = c.at(w.fpre[i]), .ldc2 = c.I, .qscale = 1.f,
+               .c_pad_scratch = 1}, c.s));
+  return dense_res_ln(c.at(w.f[i]), c.I, c.prm(pl.w2[i]), c.at(w.z2[i]), c.at(w.x2[i]), c.at(w.mean2[i]), c.at(w.rstd2[i]), c.N, c.H,
+                      c.I, c.prm(pl.b2[i]), c.at(w.x1[i]), c.prm(pl.ln2_g[i]), c.prm(pl.ln2_b[i]), c.cfg.ln_eps, c.rng,
+                      B4R_STREAM_FFN_OUT(i), c.od, c.s);
+}
+
+// tfm MaskedLM: gather -> dense(gelu) -> LayerNorm -> . E^T + bias (the fused head: no [M,V] tensor, loss rows, log-sum-exp and
+// d loss_sum / d T straight from T, E and the bias)
+int head_fwd(const Step& c, const float* x) {
+  const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
+  RC(transform_fwd({.A = x, .lda = c.H, .B = c.prm(pl.wd), .ldb = c.H, .C = c.at(w.u), .ldc = c.H, .M = c.M, .N = c.H, .K = c.H,
+                    .epilogue = B4R_EPI_BIAS_GELU_LN, .bias = c.prm(pl.bd), .C2 = c.at(w.t), .ldc2 = c.H, .qscale = 1.f,
+                    .c_pad_scratch = 1, .ln_gamma = c.prm(pl.lnm_g), .ln_beta = c.prm(pl.lnm_b), .ln_mean = c.at(w.meanm),
+                    .ln_rstd = c.at(w.rstdm), .ln_eps = c.cfg.ln_eps, .C3 = c.at(w.upre), .ldc3 = c.H,
+                    .a_gather_idx = c.batch.masked_lm_positions, .a_gather_add_per = c.L, .a_gather_per = c.P,
+                    .a_copy = c.at(w.gath) /* the transform's weight-gradient operand */, .a_copy_ld = c.H}, c.at(w.gath), c.s));
+  if (c.plan.fused_head)
+    return b4r_head32_fwd_launch(c.at(w.t), c.prm(pl.word_emb), c.prm(pl.out_bias), c.batch.masked_lm_ids, c.M, c.V, c.H,
+                                 c.at(w.scratch), c.at(w.dt), c.at(w.rowsc), c.at(w.head_lse), reinterpret_cast<int32_t*>(c.at(w.head_ylab)),
+                                 c.plan.defer_combine ? 1 : 0, c.s);
+  return gemm_f32({.A = c.at(w.t), .lda = c.H, .B = c.prm(pl.word_emb), .ldb = c.H, .C = c.at(w.logits), .ldc = (int)w.Vp, .M = c.M,
+                   .N = c.V, .K = c.H, .b_is_nk = 1, .epilogue = B4R_EPI_BIAS, .bias = c.prm(pl.out_bias), .qscale = 1.f,
+                   .c_pad_scratch = 1}, c.s);
+}
+
+}  // namespace
+
+static int forward_impl(const b4r_model_config* cfg, const b4r_batch* batch, const StepPlan& plan, const float* params,
+                        const float* pooler, void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags,
+                        b4r_stream_t stream) {
   B4R_CHECK_ARG(params && workspace, B4R_E_BADARG, "b4r_forward: null params/workspace");
   B4R_CHECK_ARG(b4r_aligned16(params) && b4r_aligned16(workspace), B4R_E_ALIGN, "b4r_forward: buffers must be 16-byte aligned");
-  const int B = batch->B, L = batch->L, P = batch->masked_lm_positions ? batch->P : 0;
-  const ParamLayout pl = make_param_layout(*cfg);
-  const WsLayout w = make_ws_layout(*cfg, B, L, batch->P);
+  const Step c(cfg, batch, plan, params, nullptr, workspace, state, flags, stream);
   // an encoder-only forward without the pooler touches nothing behind the encoder's own regions (the masked-LM head's buffers -- the
   // [B*P, V] logits above all -- and the whole backward area): b4r_workspace_bytes_encoder is enough for it
-  const int64_t ws_need = ((flags & B4R_FLAG_ENCODER_ONLY) && !(flags & B4R_FLAG_POOLER)) ? w.gath : w.total;
+  const int64_t ws_need = ((flags & B4R_FLAG_ENCODER_ONLY) && !(flags & B4R_FLAG_POOLER)) ? c.w.gath : c.w.total;
   B4R_CHECK_ARG(workspace_bytes >= ws_need * (int64_t)sizeof(float), B4R_E_NOMEM, "b4r_forward: workspace too small (%lld < %lld)",
                 (long long)workspace_bytes, (long long)(ws_need * sizeof(float)));
-  const int training = (flags & B4R_FLAG_TRAINING) ? 1 : 0;
-  B4R_CHECK_ARG(!training || state || (cfg->output_dropout == 0.f && cfg->attention_dropout == 0.f), B4R_E_BADARG,
+  B4R_CHECK_ARG(!(flags & B4R_FLAG_TRAINING) || state || (cfg->output_dropout == 0.f && cfg->attention_dropout == 0.f), B4R_E_BADARG,
                 "b4r_forward: training with dropout needs a state (rng)");
-  const uint32_t* rng = training ? reinterpret_cast<const uint32_t*>(state) : nullptr;
-  const float od = training ? cfg->output_dropout : 0.f, adp = training ? cfg->attention_dropout : 0.f;
-  float* ws = static_cast<float*>(workspace);
-  hipStream_t s = (hipStream_t)stream;
-  const int H = cfg->hidden_size, I = cfg->inner_dim, V = cfg->vocab_size, N = B * L, M = B * P;
-  const float qscale = 1.0f / sqrtf((float)head_dim(cfg));
+  const bool head = c.P > 0 && !(flags & B4R_FLAG_ENCODER_ONLY);
+  B4R_CHECK_ARG(!head || !plan.fused_head || b4r_fused_head_supported(cfg), B4R_E_BADARG,
+                "b4r_forward: B4R_FLAG_FUSED_HEAD needs hidden size 64 / 128 / 256 and the bf16x3 mode");
+  B4R_CHECK_ARG(!head || !plan.fused_head || batch->masked_lm_ids != nullptr, B4R_E_BADARG,
+                "b4r_forward: B4R_FLAG_FUSED_HEAD needs masked_lm_ids");
 
   // the embedding stage: inside the first layer's attention block where that runs fused, else a launch of its own
-  const bool emb_fused = attn_fused(cfg, L) && cfg->num_layers > 0;
-  if (!emb_fused)
-    RC(b4r_embed_ln_fwd(batch->input_word_ids, B, L, params + pl.word_emb, V, params + pl.pos_emb, params + pl.emb_ln_g,
-                        params + pl.emb_ln_b, H, cfg->ln_eps, ws + w.x0, ws + w.mean0, ws + w.rstd0, rng, od, stream));
-  const bool head_rows = (flags & B4R_FLAG_HEAD_ROWS_ONLY) && head_rows_ok(cfg, batch);
-  const bool head_rows_dense = (flags & B4R_FLAG_HEAD_ROWS_ONLY) && head_rows_dense_ok(cfg, batch);
-  const float* x = ws + w.x0;
-  for (int i = 0; i < cfg->num_layers; ++i) {
-    const bool layer_fused = attn_fused(cfg, L) && ffn_fused(cfg);
-    b4r_attn_block_desc ad{};
-    b4r_ffn_desc fd{};
-    if (attn_fused(cfg, L)) {
-      ad.B = B; ad.L = L; ad.H = H; ad.heads = cfg->num_heads; ad.x = x; ad.input_mask = batch->input_mask;
-      ad.Wqkv = params + pl.wqkv[i]; ad.bqkv = params + pl.bqkv[i]; ad.Wo = params + pl.wo[i]; ad.bo = params + pl.bo[i];
-      ad.ln_gamma = params + pl.ln1_g[i]; ad.ln_beta = params + pl.ln1_b[i]; ad.ln_eps = cfg->ln_eps;
-      ad.rng = (od > 0.f || adp > 0.f) ? rng : nullptr;
-      ad.probs_stream = B4R_STREAM_ATTN_PROBS(i); ad.probs_rate = adp; ad.out_stream = B4R_STREAM_ATTN_OUT(i); ad.out_rate = od;
-      ad.qkv = attn_bwd_fused(cfg, L) ? nullptr : ws + w.qkv[i];   // only round 1's backward kernels read it
-      ad.ctx = ws + w.ctx[i]; ad.lse = ws + w.lse[i]; ad.keep_bits = reinterpret_cast<uint32_t*>(ws + w.keep[i]);
-      ad.z1 = ws + w.z1[i]; ad.mean1 = ws + w.mean1[i]; ad.rstd1 = ws + w.rstd1[i];
-      ad.x1 = layer_fused ? nullptr : ws + w.x1[i];   // the fused feed-forward half forms x1 from z1 itself
-      if (head_rows && i == cfg->num_layers - 1) {   // nothing but the head's rows leaves the last layer: only those queries are swept
-        ad.out_slot_positions = batch->masked_lm_positions; ad.out_slots = batch->P;
-      }
-      if (i == 0 && emb_fused) {
-        ad.emb_ids = batch->input_word_ids; ad.emb_table = params + pl.word_emb; ad.emb_pos = params + pl.pos_emb; ad.emb_vocab = V;
-        ad.emb_gamma = params + pl.emb_ln_g; ad.emb_beta = params + pl.emb_ln_b; ad.emb_eps = cfg->ln_eps;
-        ad.emb_stream = B4R_STREAM_EMB; ad.emb_rate = od; if (od > 0.f) ad.rng = rng;
-        ad.emb_x = ws + w.x0; ad.emb_mean = ws + w.mean0; ad.emb_rstd = ws + w.rstd0;
-      }
-      if (!layer_fused) RC(b4r_attn_block_fwd(&ad, stream));
-    } else {
-    RC(gemm(x, H, params + pl.wqkv[i], 3 * H, ws + w.qkv[i], 3 * H, N, 3 * H, H, 0, B4R_EPI_BIAS_QSCALE, params + pl.bqkv[i],
-            nullptr, 0, nullptr, 0, qscale, H, nullptr, 0, 0.f, 0, s));
-    if (slotq_layer(cfg, batch, flags, i)) {
-      // only the rows the head reads leave this layer: the attention core with the slots as its queries (keys: all tokens), then the
-      // output projection, dropout, residual and LayerNorm on the compact [M, H] rows.  ctx / lse / decision words: compact, at the
-      // start of the layer's dense regions; x1 / z1 / statistics: where the compact feed-forward half below expects them
-      const CompactRows cr = compact_rows(w, i, M, H, I);
-      float* xc = ws + w.x1[i];              // the layer input's rows (the residual)
-      float* yc = ws + w.x1[i] + up4((int64_t)M * H);
-      RC(b4r_attn32_slotq_fwd_launch(ws + w.qkv[i], batch->input_mask, batch->masked_lm_positions, B, L, cfg->num_heads, P, ws + w.ctx[i],
-                                     ws + w.lse[i], b4r_make_drop(rng, B4R_STREAM_ATTN_PROBS(i), adp, 1),
-                                     reinterpret_cast<uint32_t*>(ws + w.keep[i]), s));
-      RC(b4r_slot_rows_gather(x, nullptr, nullptr, nullptr, batch->masked_lm_positions, L, P, M, H, xc, nullptr, nullptr, nullptr, s));
-      RC(gemm(ws + w.ctx[i], H, params + pl.wo[i], H, yc, H, M, H, H, 0, B4R_EPI_BIAS, params + pl.bo[i], nullptr, 0, nullptr, 0, 1.f, 0,
-              nullptr, 0, 0.f, 0, s));
-      RC(b4r_slot_rows_tail(yc, xc, batch->masked_lm_positions, L, P, M, H, params + pl.ln1_g[i], params + pl.ln1_b[i], cfg->ln_eps,
-                            b4r_make_drop(rng, B4R_STREAM_ATTN_OUT(i), od, 1), ws + cr.z1c, ws + cr.mean1c, ws + cr.rstd1c, nullptr,
-                            ws + cr.x1c, s));
-    } else {
-    RC(b4r_attn_fwd_hd(ws + w.qkv[i], batch->input_mask, B, L, cfg->num_heads, head_dim(cfg), ws + w.ctx[i], ws + w.lse[i], rng,
-                       B4R_STREAM_ATTN_PROBS(i), adp, reinterpret_cast<uint32_t*>(ws + w.keep[i]), stream));
-    RC(dense_res_ln(ws + w.ctx[i], H, params + pl.wo[i], ws + w.z1[i], ws + w.x1[i], ws + w.mean1[i], ws + w.rstd1[i], N, H, H,
-                    params + pl.bo[i], x, params + pl.ln1_g[i], params + pl.ln1_b[i], cfg->ln_eps, rng, B4R_STREAM_ATTN_OUT(i),
-                    od, s));
+  if (!plan.emb_fused)
+    RC(b4r_embed_ln_fwd(batch->input_word_ids, c.B, c.L, c.prm(c.pl.word_emb), c.V, c.prm(c.pl.pos_emb), c.prm(c.pl.emb_ln_g),
+                        c.prm(c.pl.emb_ln_b), c.H, cfg->ln_eps, c.at(c.w.x0), c.at(c.w.mean0), c.at(c.w.rstd0), c.rng, c.od, c.s));
+  const float* x = c.at(c.w.x0);
+  for (int i = 0; i <= c.last; ++i) {
+    switch (plan.attn_fwd[i]) {
+      case AttnFwd::Block: { const b4r_attn_block_desc ad = attn_block_desc(c, i, x); RC(b4r_attn_block_fwd(&ad, c.s)); break; }
+      case AttnFwd::SlotQuery: RC(attn_fwd_slotq(c, i, x)); break;
+      case AttnFwd::Core: RC(attn_fwd_core(c, i, x)); break;
     }
+    switch (plan.ffn[i]) {
+      case FfnForm::Block: RC(ffn_fwd_block(c, i)); break;
+      case FfnForm::CompactRows: RC(ffn_fwd_compact(c, i)); break;
+      case FfnForm::Wide: RC(ffn_fwd_wide(c, i)); break;
+      case FfnForm::TileProducts: RC(ffn_fwd_tiles(c, i)); break;
     }
-    if (ffn_fused(cfg)) {
-      fd.N = N; fd.H = H; fd.I = I; fd.x1 = layer_fused ? nullptr : ws + w.x1[i];
-      fd.z1 = ws + w.z1[i]; fd.mean1 = ws + w.mean1[i]; fd.rstd1 = ws + w.rstd1[i];
-      fd.ln1_gamma = params + pl.ln1_g[i]; fd.ln1_beta = params + pl.ln1_b[i];
-      fd.W1 = params + pl.w1[i]; fd.b1 = params + pl.b1[i]; fd.W2 = params + pl.w2[i]; fd.b2 = params + pl.b2[i];
-      fd.ln_gamma = params + pl.ln2_g[i]; fd.ln_beta = params + pl.ln2_b[i]; fd.ln_eps = cfg->ln_eps;
-      fd.rng = od > 0.f ? rng : nullptr; fd.drop_stream = B4R_STREAM_FFN_OUT(i); fd.drop_rate = od;
-      fd.z2 = ws + w.z2[i]; fd.x2 = ws + w.x2[i]; fd.mean2 = ws + w.mean2[i]; fd.rstd2 = ws + w.rstd2[i];
-      if (head_rows && i == cfg->num_layers - 1) {   // only the rows the head reads: nothing else of this output is looked at
-        fd.slot_positions = batch->masked_lm_positions; fd.slot_ids = batch->masked_lm_ids; fd.slots_per_seq = batch->P; fd.seq_len = L;
-        fd.max_rows = (int32_t)w.maxrows;
-      }
-      if (layer_fused) RC(b4r_encoder_layer_fwd(&ad, &fd, stream));
-      else RC(b4r_ffn_block_fwd(&fd, stream));
-    } else if (head_rows_dense && i == cfg->num_layers - 1) {
-      // only the rows the head reads: gather x1 (and, for the backward, z1 and its statistics), the two products on [M, .] operands,
-      // then dropout + residual + LayerNorm per compact row with the result scattered to its row of x2.  The compact f / fpre / z2 /
-      // mean2 / rstd2 lie at the start of the layer's dense regions (the backward of this mode reads them there).
-      const CompactRows cr = compact_rows(w, i, M, H, I);
-      if (!slotq_layer(cfg, batch, flags, i))   // (else the attention half above left the compact rows itself)
-        RC(b4r_slot_rows_gather(ws + w.x1[i], ws + w.z1[i], ws + w.mean1[i], ws + w.rstd1[i], batch->masked_lm_positions, L, P, M, H,
-                                ws + cr.x1c, ws + cr.z1c, ws + cr.mean1c, ws + cr.rstd1c, s));
-      RC(gemm(ws + cr.x1c, H, params + pl.w1[i], I, ws + w.f[i], I, M, I, H, 0, B4R_EPI_BIAS_GELU, params + pl.b1[i], ws + w.fpre[i], I,
-              nullptr, 0, 1.f, 0, nullptr, 0, 0.f, 0, s));
-      RC(gemm(ws + w.f[i], I, params + pl.w2[i], H, ws + cr.yc, H, M, H, I, 0, B4R_EPI_BIAS, params + pl.b2[i], nullptr, 0, nullptr, 0,
-              1.f, 0, nullptr, 0, 0.f, 0, s));
-      RC(b4r_slot_rows_tail(ws + cr.yc, ws + cr.x1c, batch->masked_lm_positions, L, P, M, H, params + pl.ln2_g[i], params + pl.ln2_b[i],
-                            cfg->ln_eps, b4r_make_drop(rng, B4R_STREAM_FFN_OUT(i), od, 1), ws + w.z2[i], ws + w.mean2[i], ws + w.rstd2[i],
-                            ws + w.x2[i], nullptr, s));
-    } else if (((flags & B4R_FLAG_ENCODER_ONLY) && b4r_ffn32w_supported(H, I)) || ffn32w_train_ok(cfg)) {
-      // the one-launch form (b4r_ffn32w.hip).  No backward follows an encoder-only forward: [N, inner] stays on the chip; otherwise the
-      // launch also writes f and the pre-activation, where the backward of this step expects them
-      const bool keep = !(flags & B4R_FLAG_ENCODER_ONLY);
-      fd.N = N; fd.H = H; fd.I = I; fd.x1 = ws + w.x1[i];
-      fd.W1 = params + pl.w1[i]; fd.b1 = params + pl.b1[i]; fd.W2 = params + pl.w2[i]; fd.b2 = params + pl.b2[i];
-      fd.ln_gamma = params + pl.ln2_g[i]; fd.ln_beta = params + pl.ln2_b[i]; fd.ln_eps = cfg->ln_eps;
-      fd.rng = od > 0.f ? rng : nullptr; fd.drop_stream = B4R_STREAM_FFN_OUT(i); fd.drop_rate = od;
-      fd.z2 = ws + w.z2[i]; fd.x2 = ws + w.x2[i]; fd.mean2 = ws + w.mean2[i]; fd.rstd2 = ws + w.rstd2[i];
-      RC(b4r_ffn32w_fwd(&fd, ws + w.ffnrec[i], keep ? ws + w.f[i] : nullptr, keep ? ws + w.fpre[i] : nullptr, s));
-    } else {
-    RC(gemm(ws + w.x1[i], H, params + pl.w1[i], I, ws + w.f[i], I, N, I, H, 0, B4R_EPI_BIAS_GELU, params + pl.b1[i],
-            ws + w.fpre[i], I, nullptr, 0, 1.f, 0, nullptr, 0, 0.f, 0, s));
-    RC(dense_res_ln(ws + w.f[i], I, params + pl.w2[i], ws + w.z2[i], ws + w.x2[i], ws + w.mean2[i], ws + w.rstd2[i], N, H, I,
-                    params + pl.b2[i], ws + w.x1[i], params + pl.ln2_g[i], params + pl.ln2_b[i], cfg->ln_eps, rng,
-                    B4R_STREAM_FFN_OUT(i), od, s));
-    }
-    x = ws + w.x2[i];
+    x = c.at(c.w.x2[i]);
   }
-  if ((flags & B4R_FLAG_POOLER) && pooler) {
-    // tanh(x[:,0,:] . Wp + bp): rows b of A are L*H apart
-    RC(gemm(x, L * H, pooler, H, ws + w.pooled, H, B, H, H, 0, B4R_EPI_BIAS_TANH, pooler + (int64_t)H * H, nullptr, 0, nullptr,
-            0, 1.f, 0, nullptr, 0, 0.f, 0, s));
-  }
-  if (P > 0 && !(flags & B4R_FLAG_ENCODER_ONLY)) {
-    // tfm MaskedLM: gather -> dense(gelu) -> LayerNorm -> . E^T + bias
-    {   // gather + dense(gelu) + LayerNorm: one launch where the LayerNorm tail applies (hidden size 64), else three
-      b4r_gemm_desc d{};
-      d.A = x; d.lda = H; d.B = params + pl.wd; d.ldb = H; d.C = ws + w.u; d.ldc = H; d.M = M; d.N = H; d.K = H;
-      d.a_gather_idx = batch->masked_lm_positions; d.a_gather_add_per = L; d.a_gather_per = P;
-      d.a_copy = ws + w.gath; d.a_copy_ld = H;   // the gathered rows: A operand of the transform's weight gradient
-      d.epilogue = B4R_EPI_BIAS_GELU_LN; d.bias = params + pl.bd; d.C2 = ws + w.t; d.ldc2 = H; d.C3 = ws + w.upre; d.ldc3 = H;
-      d.qscale = 1.f; d.c_pad_scratch = 1;
-      d.ln_gamma = params + pl.lnm_g; d.ln_beta = params + pl.lnm_b; d.ln_mean = ws + w.meanm; d.ln_rstd = ws + w.rstdm;
-      d.ln_eps = cfg->ln_eps;
-      if (b4r_gemm_ln_supported(&d)) {
-        RC(b4r_gemm_f32(&d, (b4r_stream_t)s));
-      } else {
-        RC(b4r_gather_rows(x, H, batch->masked_lm_positions, L, P, M, H, ws + w.gath, stream));
-        RC(gemm(ws + w.gath, H, params + pl.wd, H, ws + w.u, H, M, H, H, 0, B4R_EPI_BIAS_GELU, params + pl.bd, ws + w.upre, H,
-                nullptr, 0, 1.f, 0, nullptr, 0, 0.f, 0, s));
-        RC(b4r_ln_fwd(ws + w.u, M, H, params + pl.lnm_g, params + pl.lnm_b, cfg->ln_eps, ws + w.t, ws + w.meanm, ws + w.rstdm,
-                      stream));
-      }
-    }
-    if (flags & B4R_FLAG_FUSED_HEAD) {
-      // no [M,V] tensor: loss rows, log-sum-exp and d loss_sum / d T straight from T, E and the bias
-      B4R_CHECK_ARG(b4r_fused_head_supported(cfg), B4R_E_BADARG, "b4r_forward: B4R_FLAG_FUSED_HEAD needs hidden size 64 / 128 / 256 and the bf16x3 mode");
-      B4R_CHECK_ARG(batch->masked_lm_ids != nullptr, B4R_E_BADARG, "b4r_forward: B4R_FLAG_FUSED_HEAD needs masked_lm_ids");
-      RC(b4r_head32_fwd_launch(ws + w.t, params + pl.word_emb, params + pl.out_bias, batch->masked_lm_ids, M, V, H, ws + w.scratch,
-                               ws + w.dt, ws + w.rowsc, ws + w.head_lse, reinterpret_cast<int32_t*>(ws + w.head_ylab),
-                               (flags & B4R_FLAG_DEFER_COMBINE_INTERNAL) ? 1 : 0, s));
-    } else {
-      RC(gemm(ws + w.t, H, params + pl.word_emb, H, ws + w.logits, (int)w.Vp, M, V, H, 1, B4R_EPI_BIAS, params + pl.out_bias,
-              nullptr, 0, nullptr, 0, 1.f, 0, nullptr, 0, 0.f, 0, s));
-    }
-  }
-  return B4R_OK;
+  if ((flags & B4R_FLAG_POOLER) && pooler)   // tanh(x[:,0,:] . Wp + bp): rows b of A are L*H apart
+    RC(gemm_f32({.A = x, .lda = c.L * c.H, .B = pooler, .ldb = c.H, .C = c.at(c.w.pooled), .ldc = c.H, .M = c.B, .N = c.H, .K = c.H,
+                 .epilogue = B4R_EPI_BIAS_TANH, .bias = pooler + (int64_t)c.H * c.H, .qscale = 1.f, .c_pad_scratch = 1}, c.s));
+  return head ? head_fwd(c, x) : B4R_OK;
 }
 
 extern "C" int b4r_mlm_transform_rows(const b4r_model_config* cfg, const float* params, const float* seq, int64_t n_seq_rows,
@@ -778,20 +869,14 @@ extern "C" int b4r_mlm_transform_rows(const b4r_model_config* cfg, const float* 
                 "b4r_mlm_transform_rows: buffers must be 16-byte aligned");
   const ParamLayout pl = make_param_layout(*cfg);
   const int H = cfg->hidden_size;
-  hipStream_t s = (hipStream_t)stream;
   float* gath = scratch; float* upre = gath + up4((int64_t)R * H); float* u = upre + up4((int64_t)R * H);
   float* mean = u + up4((int64_t)R * H); float* rstd = mean + up4(R);
-  b4r_gemm_desc d{};
-  d.A = seq; d.lda = H; d.B = params + pl.wd; d.ldb = H; d.C = u; d.ldc = H; d.M = R; d.N = H; d.K = H;
-  d.a_gather_idx = rows; d.a_gather_add_per = n_seq_rows; d.a_gather_per = R;   // one group: row m reads seq[rows[m]]
-  d.epilogue = B4R_EPI_BIAS_GELU_LN; d.bias = params + pl.bd; d.C2 = out; d.ldc2 = H; d.C3 = upre; d.ldc3 = H;
-  d.qscale = 1.f; d.c_pad_scratch = 0;
-  d.ln_gamma = params + pl.lnm_g; d.ln_beta = params + pl.lnm_b; d.ln_mean = mean; d.ln_rstd = rstd; d.ln_eps = cfg->ln_eps;
-  if (b4r_gemm_ln_supported(&d)) return b4r_gemm_f32(&d, stream);
-  RC(b4r_gather_rows(seq, H, rows, n_seq_rows, R, R, H, gath, stream));
-  RC(gemm(gath, H, params + pl.wd, H, u, H, R, H, H, 0, B4R_EPI_BIAS_GELU, params + pl.bd, upre, H, nullptr, 0, 1.f, 0, nullptr, 0,
-          0.f, 0, s));
-  return b4r_ln_fwd(u, R, H, params + pl.lnm_g, params + pl.lnm_b, cfg->ln_eps, out, mean, rstd, stream);
+  return transform_fwd({.A = seq, .lda = H, .B = params + pl.wd, .ldb = H, .C = u, .ldc = H, .M = R, .N = H, .K = H,
+                        .epilogue = B4R_EPI_BIAS_GELU_LN, .bias = params + pl.bd, .C2 = out, .ldc2 = H, .qscale = 1.f,
+                        .c_pad_scratch = 0, .ln_gamma = params + pl.lnm_g, .ln_beta = params + pl.lnm_b, .ln_mean = mean,
+                        .ln_rstd = rstd, .ln_eps = cfg->ln_eps, .C3 = upre, .ldc3 = H,
+                        .a_gather_idx = rows, .a_gather_add_per = n_seq_rows, .a_gather_per = R /* one group: row m reads seq[rows[m]] */},
+                       gath, stream);
 }
 
 extern "C" int b4r_loss(const b4r_model_config* cfg, const b4r_batch* batch, void* workspace, int64_t workspace_bytes,
@@ -808,317 +893,344 @@ extern "C" int b4r_loss(const b4r_model_config* cfg, const b4r_batch* batch, voi
                         want_grad & (1 | B4R_LOSS_OVERWRITE), stream);
 }
 
-static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, const float* params, float* grads, void* workspace,
-                         int64_t workspace_bytes, b4r_train_state* state, int32_t flags, b4r_stream_t stream) {
-  RC(check_cfg(cfg));
-  RC(check_batch(batch, cfg, true));
-  B4R_CHECK_ARG(params && grads && workspace && batch->masked_lm_ids, B4R_E_BADARG, "b4r_backward: null argument");
-  B4R_CHECK_ARG(b4r_aligned16(params) && b4r_aligned16(grads) && b4r_aligned16(workspace), B4R_E_ALIGN,
-                "b4r_backward: buffers must be 16-byte aligned");
-  const int B = batch->B, L = batch->L, P = batch->P;
-  const ParamLayout pl = make_param_layout(*cfg);
-  const WsLayout w = make_ws_layout(*cfg, B, L, P);
-  B4R_CHECK_ARG(workspace_bytes >= w.total * (int64_t)sizeof(float), B4R_E_NOMEM, "b4r_backward: workspace too small");
-  const int training = (flags & B4R_FLAG_TRAINING) ? 1 : 0;
-  const uint32_t* rng = training ? reinterpret_cast<const uint32_t*>(state) : nullptr;
-  const float od = training ? cfg->output_dropout : 0.f, adp = training ? cfg->attention_dropout : 0.f;
-  float* ws = static_cast<float*>(workspace);
-  hipStream_t s = (hipStream_t)stream;
-  const int H = cfg->hidden_size, I = cfg->inner_dim, V = cfg->vocab_size, N = B * L, M = B * P, Vp = (int)w.Vp;
-  const float qscale = 1.0f / sqrtf((float)head_dim(cfg));
-  float* scratch_base = ws + w.scratch;
-  int64_t scratch_used = 0;
-  auto take = [&](int64_t n) { float* ptr = scratch_base + scratch_used; scratch_used += up4(n); return ptr; };
-  const DropArgs nodrop = b4r_make_drop(nullptr, 0, 0.f, 0);
-  B4rReduceQueue queue;
-  b4r_reduce_queue_begin(&queue);   // every ordered reduction below is summed by ONE launch at the end
+// ===============================================================================================================
+// the forms of the backward
+namespace {
 
-  // the gradient buffer; dx and the scatter's hot-row slots (row-list mode: the hot-row slots and db, whose rows outside the list
-  // carry no gradient); with B4R_FLAG_GRAD_TAIL also the step's sums behind the gradients
-  B4R_CHECK_ARG(!(flags & B4R_FLAG_GRAD_TAIL) || state, B4R_E_BADARG, "b4r_backward: B4R_FLAG_GRAD_TAIL needs the state");
-  const bool head_rows_dense = (flags & B4R_FLAG_HEAD_ROWS_ONLY) && head_rows_dense_ok(cfg, batch);
-  const bool head_rows = ((flags & B4R_FLAG_HEAD_ROWS_ONLY) && head_rows_ok(cfg, batch)) || head_rows_dense;
-  const bool loss_sums = (flags & B4R_FLAG_LOSS_SUMS) != 0;
-  const bool defer_combine = (flags & B4R_FLAG_DEFER_COMBINE_INTERNAL) && loss_sums;
-  B4R_CHECK_ARG(!loss_sums || ((flags & B4R_FLAG_FUSED_HEAD) && state && batch->masked_lm_ids), B4R_E_BADARG,
-                "b4r_backward: B4R_FLAG_LOSS_SUMS needs B4R_FLAG_FUSED_HEAD, the state and masked_lm_ids");
-  // row-list mode with the 32-token-tile attention backward: that kernel is told which rows of the last layer's dz1 exist and never
-  // reads the others -- db need not be cleared (13 MB per step at ML-1M)
-  const bool sparse_dz1 = head_rows && ffn_fused(cfg) && attn_bwd_fused(cfg, L) && b4r_attn32_active(H, cfg->num_heads, L);
-  // the scratch regions of the fused head are fixed here already: the records dE sweeps (the transform rows as fp16 images, -lse, labels)
-  // are formed by extra workgroups of the clearing launch (b4r_zero2's rider) instead of a launch of their own
-  const bool fused_head_early = (flags & B4R_FLAG_FUSED_HEAD) != 0 && b4r_fused_head_supported(cfg);
-  const float* fwd_part_early = (fused_head_early && defer_combine) ? take(b4r_head32_fwd_scratch_floats(M, V, H)) : nullptr;   // = ws + w.scratch
-  float* dE_scratch = fused_head_early ? take(b4r_head32_dE_scratch_floats(M, V, H)) : nullptr;
+// the opening launch (it clears the gradient buffer, dx and the scatter's hot-row slots -- in the row-list mode the hot-row slots and
+// db, whose rows outside the list carry no gradient --, with B4R_FLAG_GRAD_TAIL also the step's sums behind the gradients) and the
+// masked-LM head down to d sequence_output
+int head_bwd(Step& c) {
+  const StepPlan& p = c.plan;
+  const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
+  const int H = c.H, M = c.M, V = c.V, Vp = (int)w.Vp;
+  const bool loss_sums = (c.flags & B4R_FLAG_LOSS_SUMS) != 0;
+  // the scratch regions of the fused head are fixed here already: the records dE sweeps (the transform rows as fp16 images, -lse,
+  // labels) are formed by extra workgroups of the clearing launch (b4r_zero2's rider) instead of a launch of their own.  With the
+  // deferred merge the forward's partials stay where it left them, at the start of the scratch.
+  float *fwd_part = nullptr, *dE_scratch = nullptr;
+  if (p.fused_head && p.defer_combine) RC(c.take(b4r_head32_fwd_scratch_floats(M, V, H), &fwd_part));
+  if (p.fused_head) RC(c.take(b4r_head32_dE_scratch_floats(M, V, H), &dE_scratch));
   alignas(8) char rider[128];
   int rider_blocks = 0;
-  if (fused_head_early)
-    RC(b4r_head32_dE_pack_job(ws + w.t, ws + w.head_lse, reinterpret_cast<const int32_t*>(ws + w.head_ylab), M, V, H, dE_scratch,
-                              fwd_part_early, batch->masked_lm_ids, rider, sizeof(rider), &rider_blocks));
-  RC(b4r_zero2(grads, pl.total, ws + (head_rows ? w.hot : w.dx), head_rows ? (sparse_dz1 ? w.db - w.hot : w.da - w.hot) : w.db - w.dx, s,
-               ((flags & B4R_FLAG_GRAD_TAIL) && !defer_combine) ? grads + pl.total : nullptr, state,
-               (loss_sums && !defer_combine) ? ws + w.rowsc : nullptr, (int)w.M, rider_blocks > 0 ? rider : nullptr, rider_blocks));
+  if (p.fused_head)
+    RC(b4r_head32_dE_pack_job(c.at(w.t), c.at(w.head_lse), reinterpret_cast<const int32_t*>(c.at(w.head_ylab)), M, V, H, dE_scratch,
+                              fwd_part, c.batch.masked_lm_ids, rider, sizeof(rider), &rider_blocks));
+  // row-list mode with the slots' dz1 only in the last layer's attention backward (it never reads the other rows): db is not cleared
+  RC(b4r_zero2(c.grads, pl.total, c.at(p.rows() ? w.hot : w.dx),
+               p.rows() ? (p.slot_only_last ? w.db - w.hot : w.da - w.hot) : w.db - w.dx, c.s,
+               ((c.flags & B4R_FLAG_GRAD_TAIL) && !p.defer_combine) ? c.grd(pl.total) : nullptr, c.state,
+               (loss_sums && !p.defer_combine) ? c.at(w.rowsc) : nullptr, M, rider_blocks > 0 ? rider : nullptr, rider_blocks));
 
-  // ---- masked-LM head (logits buffer holds d loss_sum / d logits, pad columns zero) --------------------------------
-  float* dlog = ws + w.logits;
-  const bool fused_head = (flags & B4R_FLAG_FUSED_HEAD) != 0;
-  const float* fwd_part = nullptr;
-  B4R_CHECK_ARG(!fused_head || b4r_fused_head_supported(cfg), B4R_E_BADARG, "b4r_backward: B4R_FLAG_FUSED_HEAD needs hidden size 64 / 128 / 256 and the bf16x3 mode");
-  if (fused_head) {
+  float* dlog = c.at(w.logits);   // (the materialising head: d loss_sum / d logits, pad columns zero)
+  float* sc;
+  if (p.fused_head) {
     // dT came with the forward -- or (defer_combine) the forward left its per-slice partials: dE forms the lse it needs from them, the
     // transform's LayerNorm backward below merges them into dT as it reads it; dE / d output_bias recompute the logit tiles (b4r_head32.hip)
-    fwd_part = fwd_part_early;
-    RC(b4r_head32_dE_launch(ws + w.t, params + pl.word_emb, params + pl.out_bias, ws + w.head_lse,
-                            reinterpret_cast<const int32_t*>(ws + w.head_ylab), M, V, H, dE_scratch,
-                            grads + pl.word_emb, grads + pl.out_bias, s, fwd_part, batch->masked_lm_ids, rider_blocks > 0 ? 1 : 0));
+    RC(b4r_head32_dE_launch(c.at(w.t), c.prm(pl.word_emb), c.prm(pl.out_bias), c.at(w.head_lse),
+                            reinterpret_cast<const int32_t*>(c.at(w.head_ylab)), M, V, H, dE_scratch, c.grd(pl.word_emb),
+                            c.grd(pl.out_bias), c.s, fwd_part, c.batch.masked_lm_ids, rider_blocks > 0 ? 1 : 0));
   } else {
-  // dT = dlogits . E   (K = V is long and the output small: split K so that the whole chip streams dlogits)
-  {
-    b4r_gemm_desc d{};
-    d.A = dlog; d.lda = Vp; d.B = params + pl.word_emb; d.ldb = H; d.C = ws + w.dt; d.ldc = H;
-    d.M = M; d.N = H; d.K = V; d.b_is_nk = 0; d.epilogue = B4R_EPI_NONE;
-    // the loss kernel zeroed columns [V, Vp) of dlogits, and the table is followed by the position table in the flat
-    // parameter buffer, so the reduction may run over whole chunks of 64 (rows V..Vp-1 of "E" meet zeros)
-    const int k_pad_ok = (pl.word_emb + (int64_t)Vp * H <= pl.total) ? 1 : 0;
-    RC(b4r_gemm_f32_splitk(&d, mlm_dt_splits(M, H, V), take((int64_t)mlm_dt_splits(M, H, V) * M * H), k_pad_ok, s));
-  }
-  // dE = dlogits^T . T ; d output_bias = column sums of dlogits
-  RC(gemm_tn(dlog, Vp, ws + w.t, H, grads + pl.word_emb, H, M, V, H, nullptr, grads + pl.out_bias, nullptr, 0, 0.f, 0,
-             take(b4r_gemm_tn_scratch_floats(M, V, H)), s));
+    // dT = dlogits . E   (K = V is long and the output small: split K so that the whole chip streams dlogits).  The loss kernel zeroed
+    // columns [V, Vp) of dlogits, and the table is followed by the position table in the flat parameter buffer, so the reduction may
+    // run over whole chunks of 64 (rows V..Vp-1 of "E" meet zeros)
+    const b4r_gemm_desc d{.A = dlog, .lda = Vp, .B = c.prm(pl.word_emb), .ldb = H, .C = c.at(w.dt), .ldc = H, .M = M, .N = H, .K = V,
+                          .b_is_nk = 0, .epilogue = B4R_EPI_NONE};
+    const int splits = mlm_dt_splits(M, H, V);
+    RC(c.take((int64_t)splits * M * H, &sc));
+    RC(b4r_gemm_f32_splitk(&d, splits, sc, (pl.word_emb + (int64_t)Vp * H <= pl.total) ? 1 : 0, c.s));
+    // dE = dlogits^T . T ; d output_bias = column sums of dlogits
+    RC(c.take(b4r_gemm_tn_scratch_floats(M, V, H), &sc));
+    RC(gemm_tn_f32({.A = dlog, .lda = Vp, .B = c.at(w.t), .ldb = H, .out = c.grd(pl.word_emb), .ldo = H, .R = M, .Mo = V, .No = H,
+                    .colsum_a = c.grd(pl.out_bias)}, sc, c.s));
   }
   // LayerNorm of the transform (with the deferred merge: dT, the loss rows, lse and labels are formed here, from the forward's partials)
-  const B4rHeadMerge merge{fwd_part, fwd_part ? b4r_head32_fwd_slices(M, V, H) : 0, M, V, ws + w.t, params + pl.word_emb,
-                           params + pl.out_bias, batch->masked_lm_ids, ws + w.rowsc, ws + w.head_lse,
-                           reinterpret_cast<int32_t*>(ws + w.head_ylab)};
-  RC(b4r_ln_bwd_launch(ws + w.dt, ws + w.u, ws + w.meanm, ws + w.rstdm, params + pl.lnm_g, M, H, ws + w.dt, grads + pl.lnm_g,
-                       grads + pl.lnm_b, take(b4r_ln_bwd_scratch_floats(M, H)), nullptr, nullptr, nullptr, 1, 1, nodrop, s,
-                       ws + w.upre, fwd_part ? &merge : nullptr));   // ... and straight through the GELU of the transform's dense layer
-  {   // dense layer of the transform: dWd = gath^T . du (+ bias gradient) and dgath = du . Wd^T, one pass over du where the pair
-      // kernel applies (hidden size 64)
-    b4r_gemm_tn_desc d{};
-    d.A = ws + w.gath; d.lda = H; d.B = ws + w.dt; d.ldb = H; d.out = grads + pl.wd; d.ldo = H; d.R = M; d.Mo = H; d.No = H;
-    d.colsum = grads + pl.bd;
-    d.dgrad_w = params + pl.wd; d.dgrad_ldw = H; d.dgrad_out = ws + w.dg; d.dgrad_ldo = H;
-    if (b4r_gemm_tn_dgrad_supported(&d)) {
-      RC(b4r_gemm_tn_f32(&d, take(b4r_gemm_tn_scratch_floats(M, H, H)), (b4r_stream_t)s));
-    } else {
-      RC(gemm_tn(ws + w.gath, H, ws + w.dt, H, grads + pl.wd, H, M, H, H, grads + pl.bd, nullptr, nullptr, 0, 0.f, 0,
-                 take(b4r_gemm_tn_scratch_floats(M, H, H)), s));
-      RC(gemm(ws + w.dt, H, params + pl.wd, H, ws + w.dg, H, M, H, H, 1, B4R_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, 1.f, 0,
-              nullptr, 0, 0.f, 0, s));
-    }
+  // ... and straight through the GELU of the transform's dense layer
+  const B4rHeadMerge merge{fwd_part, fwd_part ? b4r_head32_fwd_slices(M, V, H) : 0, M, V, c.at(w.t), c.prm(pl.word_emb),
+                           c.prm(pl.out_bias), c.batch.masked_lm_ids, c.at(w.rowsc), c.at(w.head_lse),
+                           reinterpret_cast<int32_t*>(c.at(w.head_ylab))};
+  RC(c.take(b4r_ln_bwd_scratch_floats(M, H), &sc));
+  RC(b4r_ln_bwd_launch(c.at(w.dt), c.at(w.u), c.at(w.meanm), c.at(w.rstdm), c.prm(pl.lnm_g), M, H, c.at(w.dt), c.grd(pl.lnm_g),
+                       c.grd(pl.lnm_b), sc, nullptr, nullptr, nullptr, 1, 1, b4r_make_drop(nullptr, 0, 0.f, 0), c.s, c.at(w.upre),
+                       fwd_part ? &merge : nullptr));
+  // dense layer of the transform: dWd = gath^T . du (+ bias gradient) and dgath = du . Wd^T, one pass over du where the pair kernel
+  // applies (hidden size 64), else the two products
+  b4r_gemm_tn_desc d{.A = c.at(w.gath), .lda = H, .B = c.at(w.dt), .ldb = H, .out = c.grd(pl.wd), .ldo = H, .R = M, .Mo = H, .No = H,
+                     .colsum = c.grd(pl.bd), .dgrad_w = c.prm(pl.wd), .dgrad_ldw = H, .dgrad_out = c.at(w.dg), .dgrad_ldo = H};
+  RC(c.take(b4r_gemm_tn_scratch_floats(M, H, H), &sc));
+  if (b4r_gemm_tn_dgrad_supported(&d)) {
+    RC(gemm_tn_f32(d, sc, c.s));
+  } else {
+    d.dgrad_w = nullptr; d.dgrad_ldw = 0; d.dgrad_out = nullptr; d.dgrad_ldo = 0;
+    RC(gemm_tn_f32(d, sc, c.s));
+    RC(gemm_f32({.A = c.at(w.dt), .lda = H, .B = c.prm(pl.wd), .ldb = H, .C = c.at(w.dg), .ldc = H, .M = M, .N = H, .K = H,
+                 .b_is_nk = 1, .epilogue = B4R_EPI_NONE, .qscale = 1.f, .c_pad_scratch = 1}, c.s));
   }
   // scatter into d sequence_output (slots with y_true == 0 carry exactly zero gradient and are skipped); in the row-list mode the last
   // layer's feed-forward backward reads the slot gradients directly
-  if (!head_rows)
-    RC(b4r_scatter_add_rows_impl(ws + w.dg, batch->masked_lm_positions, L, P, M, H, ws + w.dx, H, batch->masked_lm_ids, N, 0, nullptr, s));
+  if (p.rows()) return B4R_OK;
+  return b4r_scatter_add_rows_impl(c.at(w.dg), c.batch.masked_lm_positions, c.L, c.P, M, H, c.at(w.dx), H, c.batch.masked_lm_ids, c.N,
+                                   0, nullptr, c.s);
+}
 
+// a weight gradient `d` with the input gradient of the same layer from one pass over its B operand where b4r_gemm_tn_dgrad_supported,
+// else the input-gradient product `dx` (the same dropout on its A operand) followed by the weight gradient alone
+int wgrad_with_dgrad(Step& c, b4r_gemm_tn_desc d, const b4r_gemm_desc& dx) {
+  float* sc; RC(c.take(b4r_gemm_tn_scratch_floats(d.R, d.Mo, d.No), &sc));
+  if (b4r_gemm_tn_dgrad_supported(&d)) return gemm_tn_f32(d, sc, c.s);
+  RC(gemm_f32(dx, c.s));
+  d.dgrad_w = nullptr; d.dgrad_ldw = 0; d.dgrad_out = nullptr; d.dgrad_ldo = 0; d.dgrad_gelu_pre = nullptr; d.dgrad_ldg = 0;
+  return gemm_tn_f32(d, sc, c.s);
+}
+
+// FfnForm::Block: dz1 (-> db), dW1 / db1 / dW2 / db2 and the attention LayerNorm's gamma / beta gradients from dz2 (da); the
+// [N, inner] pre-activation is recomputed from x1 inside the two kernels.  On the last layer of the row-list mode the output
+// LayerNorm's backward runs inside, on the rows with a gradient; dz1 elsewhere stays zero.
+int ffn_bwd_block(Step& c, int i) {
+  const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
+  b4r_ffn_desc fd = ffn_desc(c, i);
+  fd.x1 = c.plan.x1_stored ? c.at(w.x1[i]) : nullptr;   // as the forward of this step left it
+  fd.dz2 = c.at(w.da); fd.z1 = c.at(w.z1[i]); fd.mean1 = c.at(w.mean1[i]); fd.rstd1 = c.at(w.rstd1[i]);
+  fd.ln1_gamma = c.prm(pl.ln1_g[i]); fd.ln1_beta = c.prm(pl.ln1_b[i]); fd.dz1 = c.at(w.db);
+  fd.dW1 = c.grd(pl.w1[i]); fd.db1 = c.grd(pl.b1[i]); fd.dW2 = c.grd(pl.w2[i]); fd.db2 = c.grd(pl.b2[i]);
+  fd.dln1_gamma = c.grd(pl.ln1_g[i]);
+  RC(c.take(b4r_ffn_block_bwd_scratch_floats(c.N), &fd.scratch));
+  if (c.plan.head_rows && i == c.last) {
+    fd.dz2 = nullptr;
+    fd.slot_positions = c.batch.masked_lm_positions; fd.slot_ids = c.batch.masked_lm_ids; fd.slots_per_seq = c.batch.P; fd.seq_len = c.L;
+    fd.max_rows = (int32_t)w.maxrows;
+    fd.slot_grad = c.at(w.dg); fd.z2 = c.at(w.z2[i]); fd.mean2 = c.at(w.mean2[i]); fd.rstd2 = c.at(w.rstd2[i]);
+    fd.ln_gamma = c.prm(pl.ln2_g[i]); fd.dln_gamma = c.grd(pl.ln2_g[i]); fd.dz2_rows = c.at(w.dz2c);
+  }
+  return b4r_ffn_block_bwd(&fd, c.s);
+}
+
+// FfnForm::CompactRows: the tile-product chain with every operand [M, .], one row per masked-LM slot (slots without a label carry an
+// exactly zero gradient; two labelled slots never share a row).  dz1 (db) was cleared by the opening launch; the compact result is
+// scatter-added into it (and left in dz2c for the SlotQuery attention backward).
+int ffn_bwd_compact(Step& c, int i) {
+  const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
+  const int H = c.H, I = c.I, M = c.M;
+  const int64_t* pos = c.batch.masked_lm_positions;
+  const CompactRows cr = compact_rows(w, i, M, H, I);
+  float* dz2c = c.at(w.dzc_a);                      // LayerNorm2 backward of the slot gradients
+  float* dz2d = c.od > 0.f ? c.at(w.dzc_b) : dz2c;   // ... through the output dropout
+  float* sc; RC(c.take(ln_scratch_floats(c.N, H), &sc));
+  RC(b4r_ln_bwd_launch(c.at(w.dg), c.at(w.z2[i]), c.at(w.mean2[i]), c.at(w.rstd2[i]), c.prm(pl.ln2_g[i]), M, H, dz2c, c.grd(pl.ln2_g[i]),
+                       c.grd(pl.ln2_b[i]), sc, nullptr, nullptr, nullptr, 1, 1, b4r_make_drop(nullptr, 0, 0.f, 0), c.s));
+  if (c.od > 0.f)
+    RC(b4r_slot_rows_drop(dz2c, pos, c.L, c.P, M, H, b4r_make_drop(c.rng, B4R_STREAM_FFN_OUT(i), c.od, 1), dz2d, c.s));
+  RC(gemm_f32({.A = dz2d, .lda = H, .B = c.prm(pl.w2[i]), .ldb = H, .C = c.at(w.df), .ldc = I, .M = M, .N = I, .K = H, .b_is_nk = 1,
+               .epilogue = B4R_EPI_GELU_BWD, .R = c.at(w.fpre[i]), .ldr = I, .qscale = 1.f, .c_pad_scratch = 1}, c.s));
+  RC(c.take(b4r_gemm_tn_scratch_floats(M, I, H), &sc));
+  RC(gemm_tn_f32({.A = c.at(w.f[i]), .lda = I, .B = dz2d, .ldb = H, .out = c.grd(pl.w2[i]), .ldo = H, .R = M, .Mo = I, .No = H,
+                  .colsum = c.grd(pl.b2[i])}, sc, c.s));
+  RC(c.take(ln_scratch_floats(c.N, H), &sc));
+  RC(dgrad_ln_bwd(c.at(w.df), I, c.prm(pl.w1[i]), I, dz2c, c.at(w.dz2c), M, H, c.at(cr.z1c), c.at(cr.mean1c), c.at(cr.rstd1c),
+                  c.prm(pl.ln1_g[i]), c.grd(pl.ln1_g[i]), c.grd(pl.ln1_b[i]), sc, c.s));
+  RC(c.take(b4r_gemm_tn_scratch_floats(M, H, I), &sc));
+  RC(gemm_tn_f32({.A = c.at(cr.x1c), .lda = H, .B = c.at(w.df), .ldb = I, .out = c.grd(pl.w1[i]), .ldo = I, .R = M, .Mo = H, .No = I,
+                  .colsum = c.grd(pl.b1[i])}, sc, c.s));
+  return b4r_scatter_add_rows_impl(c.at(w.dz2c), pos, c.L, c.P, M, H, c.at(w.db), H, c.batch.masked_lm_ids, c.N, 0, nullptr, c.s);
+}
+
+// FfnForm::Wide: dF and dX1 (residual included) in one launch from the records the forward packed; LayerNorm1's backward in place;
+// the two weight gradients as products
+int ffn_bwd_wide(Step& c, int i) {
+  const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
+  const int H = c.H, I = c.I, N = c.N;
+  b4r_ffn_desc fd = ffn_desc(c, i);
+  fd.dz2 = c.at(w.da);
+  RC(b4r_ffn32w_bwd(&fd, c.at(w.ffnrec[i]), c.at(w.fpre[i]), c.at(w.df), c.at(w.db), true, c.s));
+  float* sc; RC(c.take(b4r_gemm_tn_scratch_floats(N, I, H), &sc));
+  RC(gemm_tn_f32({.A = c.at(w.f[i]), .lda = I, .B = c.at(w.da), .ldb = H, .out = c.grd(pl.w2[i]), .ldo = H, .R = N, .Mo = I, .No = H,
+                  .colsum = c.grd(pl.b2[i]), .rng = c.rng, .drop_stream = B4R_STREAM_FFN_OUT(i), .drop_rate = c.od, .b_dropout = 1},
+                 sc, c.s));
+  RC(c.take(ln_scratch_floats(N, H), &sc));
+  RC(b4r_ln_bwd_launch(c.at(w.db), c.at(w.z1[i]), c.at(w.mean1[i]), c.at(w.rstd1[i]), c.prm(pl.ln1_g[i]), N, H, c.at(w.db),
+                       c.grd(pl.ln1_g[i]), c.grd(pl.ln1_b[i]), sc, nullptr, nullptr, nullptr, 1, 1, b4r_make_drop(nullptr, 0, 0.f, 0), c.s));
+  RC(c.take(b4r_gemm_tn_scratch_floats(N, H, I), &sc));
+  return gemm_tn_f32({.A = c.at(w.x1[i]), .lda = H, .B = c.at(w.df), .ldb = I, .out = c.grd(pl.w1[i]), .ldo = I, .R = N, .Mo = H,
+                      .No = I, .colsum = c.grd(pl.b1[i])}, sc, c.s);
+}
+
+// FfnForm::TileProducts: dFpre = (dropmask(dz2) . W2^T) * gelu'(fpre) with dW2 = f^T . dropmask(dz2) (+ bias gradient); then
+// dz1 = the attention LayerNorm's backward of dX1 = dFpre . W1^T + dz2, and dW1
+int ffn_bwd_tiles(Step& c, int i) {
+  const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
+  const int H = c.H, I = c.I, N = c.N;
+  RC(wgrad_with_dgrad(c, {.A = c.at(w.f[i]), .lda = I, .B = c.at(w.da), .ldb = H, .out = c.grd(pl.w2[i]), .ldo = H, .R = N, .Mo = I,
+                          .No = H, .colsum = c.grd(pl.b2[i]), .rng = c.rng, .drop_stream = B4R_STREAM_FFN_OUT(i), .drop_rate = c.od,
+                          .b_dropout = 1, .dgrad_w = c.prm(pl.w2[i]), .dgrad_ldw = H, .dgrad_out = c.at(w.df), .dgrad_ldo = I,
+                          .dgrad_gelu_pre = c.at(w.fpre[i]), .dgrad_ldg = I},
+                      {.A = c.at(w.da), .lda = H, .B = c.prm(pl.w2[i]), .ldb = H, .C = c.at(w.df), .ldc = I, .M = N, .N = I, .K = H,
+                       .b_is_nk = 1, .epilogue = B4R_EPI_GELU_BWD, .R = c.at(w.fpre[i]), .ldr = I, .qscale = 1.f, .rng = c.rng,
+                       .drop_stream = B4R_STREAM_FFN_OUT(i), .drop_rate = c.od, .a_dropout = 1, .c_pad_scratch = 1}));
+  float* sc; RC(c.take(ln_scratch_floats(N, H), &sc));
+  RC(dgrad_ln_bwd(c.at(w.df), I, c.prm(pl.w1[i]), I, c.at(w.da), c.at(w.db), N, H, c.at(w.z1[i]), c.at(w.mean1[i]), c.at(w.rstd1[i]),
+                  c.prm(pl.ln1_g[i]), c.grd(pl.ln1_g[i]), c.grd(pl.ln1_b[i]), sc, c.s));
+  RC(c.take(b4r_gemm_tn_scratch_floats(N, H, I), &sc));
+  return gemm_tn_f32({.A = c.at(w.x1[i]), .lda = H, .B = c.at(w.df), .ldb = I, .out = c.grd(pl.w1[i]), .ldo = I, .R = N, .Mo = H,
+                      .No = I, .colsum = c.grd(pl.b1[i])}, sc, c.s);
+}
+
+// AttnBwd::Block / BlockFolded: the attention block's backward in one launch -- dqkv and, through the LayerNorm in front of this layer,
+// da (for layer 0: through the embedding stage's dropout and LayerNorm).  Folded, the launch also forms every weight gradient of the
+// half; else dWo (inputs ready since the feed-forward backward) and dWqkv follow as one launch.
+int attn_bwd_block(Step& c, int i, const float* x_in) {
+  const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
+  const bool folded = c.plan.attn_bwd[i] == AttnBwd::BlockFolded;
+  float* wo_scratch = nullptr;   // dWo's slabs for the pair launch after the block
+  RC(c.take(b4r_gemm_tn_scratch_floats(c.N, c.H, c.H), &wo_scratch));
+  b4r_attn_block_bwd_desc bd{};
+  bd.B = c.B; bd.L = c.L; bd.H = c.H; bd.heads = c.cfg.num_heads;
+  bd.x = x_in; bd.dz1 = c.at(w.db); bd.ctx = c.at(w.ctx[i]); bd.lse = c.at(w.lse[i]);
+  bd.keep_bits = c.keep(i); bd.input_mask = c.batch.input_mask;
+  bd.Wqkv = c.prm(pl.wqkv[i]); bd.bqkv = c.prm(pl.bqkv[i]); bd.Wo = c.prm(pl.wo[i]);
+  bd.rng = (c.od > 0.f || c.adp > 0.f) ? c.rng : nullptr;
+  bd.probs_stream = B4R_STREAM_ATTN_PROBS(i); bd.probs_rate = c.adp; bd.out_stream = B4R_STREAM_ATTN_OUT(i); bd.out_rate = c.od;
+  if (i > 0) {
+    bd.prev_z = c.at(w.z2[i - 1]); bd.prev_mean = c.at(w.mean2[i - 1]); bd.prev_rstd = c.at(w.rstd2[i - 1]);
+    bd.prev_gamma = c.prm(pl.ln2_g[i - 1]); bd.dprev_gamma = c.grd(pl.ln2_g[i - 1]);
+  } else {
+    bd.prev_mean = c.at(w.mean0); bd.prev_rstd = c.at(w.rstd0); bd.prev_gamma = c.prm(pl.emb_ln_g); bd.dprev_gamma = c.grd(pl.emb_ln_g);
+    bd.emb_ids = c.batch.input_word_ids; bd.emb_table = c.prm(pl.word_emb); bd.emb_pos = c.prm(pl.pos_emb); bd.emb_vocab = c.V;
+    bd.emb_stream = B4R_STREAM_EMB; bd.emb_rate = c.od;
+  }
+  bd.dqkv = c.at(w.dqkv); bd.dx_prev = c.at(w.da);
+  RC(c.take(b4r_attn_block_bwd_scratch_floats(c.B), &bd.scratch));
+  if (folded) {   // dWqkv / dbqkv inside the launch: no [N, 3H] round trip, no weight-gradient launch for them, nor for dWo / dbo
+    bd.dqkv = nullptr; bd.dWqkv = c.grd(pl.wqkv[i]); bd.dbqkv = c.grd(pl.bqkv[i]);
+    RC(c.take(b4r_attn_block_bwd_dw_scratch_floats(c.B), &bd.dw_scratch));
+    bd.dWo = c.grd(pl.wo[i]); bd.dbo = c.grd(pl.bo[i]);
+  }
+  if (c.plan.slot_only_last && i == c.last) {
+    bd.dz1_slot_positions = c.batch.masked_lm_positions; bd.dz1_slot_ids = c.batch.masked_lm_ids; bd.dz1_slots = c.batch.P;
+  }
+  RC(b4r_attn_block_bwd(&bd, c.s));
+  if (folded) return B4R_OK;
+  float* sc; RC(c.take(b4r_gemm_tn_scratch_floats(c.N, c.H, 3 * c.H), &sc));
+  return attn_wgrad_pair(wo_grad_desc(c.at(w.ctx[i]), c.at(w.db), c.grd(pl.wo[i]), c.grd(pl.bo[i]), c.N, c.H, c.rng, B4R_STREAM_ATTN_OUT(i),
+                                      c.od), wo_scratch, x_in, c.at(w.dqkv), c.grd(pl.wqkv[i]), c.grd(pl.bqkv[i]), sc, c.s);
+}
+
+// AttnBwd::SlotQuery: dz1 of the slots (left in dz2c by the compact feed-forward half) -> dropout of the output projection -> dWo / dbo
+// and dctx on [M, H] rows -> the attention core's backward with the slots as its queries (dq rows of the labelled slots, dk / dv of
+// every token)
+int attn_bwd_slotq(Step& c, int i) {
+  const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
+  const int H = c.H, M = c.M;
+  const int64_t* pos = c.batch.masked_lm_positions;
+  float* dz1d = c.od > 0.f ? c.at(w.dctx + up4((int64_t)M * H)) : c.at(w.dz2c);   // (the dense dctx region is free in this form)
+  float* dctx_c = c.at(w.dctx);
+  if (c.od > 0.f)
+    RC(b4r_slot_rows_drop(c.at(w.dz2c), pos, c.L, c.P, M, H, b4r_make_drop(c.rng, B4R_STREAM_ATTN_OUT(i), c.od, 1), dz1d, c.s));
+  float* sc; RC(c.take(b4r_gemm_tn_scratch_floats(c.N, H, H), &sc));
+  RC(gemm_tn_f32({.A = c.at(w.ctx[i]), .lda = H, .B = dz1d, .ldb = H, .out = c.grd(pl.wo[i]), .ldo = H, .R = M, .Mo = H, .No = H,
+                  .colsum = c.grd(pl.bo[i])}, sc, c.s));
+  RC(gemm_f32({.A = dz1d, .lda = H, .B = c.prm(pl.wo[i]), .ldb = H, .C = dctx_c, .ldc = H, .M = M, .N = H, .K = H, .b_is_nk = 1,
+               .epilogue = B4R_EPI_NONE, .qscale = 1.f, .c_pad_scratch = 1}, c.s));
+  return b4r_attn32_slotq_bwd_launch(c.at(w.qkv[i]), c.batch.input_mask, pos, c.batch.masked_lm_ids, c.at(w.ctx[i]), c.at(w.lse[i]),
+                                     dctx_c, c.B, c.L, c.cfg.num_heads, c.P, c.qscale, c.at(w.dqkv),
+                                     b4r_make_drop(c.rng, B4R_STREAM_ATTN_PROBS(i), c.adp, 1), c.keep(i), c.s);
+}
+
+// AttnBwd::Core: dctx = dropmask(dz1) . Wo^T with dWo = ctx^T . dropmask(dz1) (+ bias gradient), then the attention core: dQ, dK, dV
+int attn_bwd_core(Step& c, int i) {
+  const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
+  const int H = c.H;
+  b4r_gemm_tn_desc d = wo_grad_desc(c.at(w.ctx[i]), c.at(w.db), c.grd(pl.wo[i]), c.grd(pl.bo[i]), c.N, H, c.rng, B4R_STREAM_ATTN_OUT(i),
+                                    c.od);
+  d.dgrad_w = c.prm(pl.wo[i]); d.dgrad_ldw = H; d.dgrad_out = c.at(w.dctx); d.dgrad_ldo = H;
+  RC(wgrad_with_dgrad(c, d, {.A = c.at(w.db), .lda = H, .B = c.prm(pl.wo[i]), .ldb = H, .C = c.at(w.dctx), .ldc = H, .M = c.N, .N = H,
+                             .K = H, .b_is_nk = 1, .epilogue = B4R_EPI_NONE, .qscale = 1.f, .rng = c.rng,
+                             .drop_stream = B4R_STREAM_ATTN_OUT(i), .drop_rate = c.od, .a_dropout = 1, .c_pad_scratch = 1}));
+  return b4r_attn_bwd_hd(c.at(w.qkv[i]), c.batch.input_mask, c.at(w.ctx[i]), c.at(w.lse[i]), c.at(w.dctx), c.B, c.L, c.cfg.num_heads,
+                         head_dim(&c.cfg), c.qscale, c.at(w.dqkv), c.rng, B4R_STREAM_ATTN_PROBS(i), c.adp, c.keep(i), c.s);
+}
+
+// the QKV projection behind SlotQuery / Core: dX_in = dqkv . Wqkv^T + dz1 and straight on through the LayerNorm in front of this
+// layer (-> da): layer i-1's output LayerNorm, or for layer 0 the embedding stage (dropout -> LayerNorm of item row + position row);
+// then dWqkv = x_in^T . dqkv (+ bias gradient)
+int qkv_bwd(Step& c, int i, const float* x_in) {
+  const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
+  const int H = c.H, N = c.N;
+  float* sc; RC(c.take(ln_scratch_floats(N, H), &sc));
+  if (i > 0)
+    RC(dgrad_ln_bwd(c.at(w.dqkv), 3 * H, c.prm(pl.wqkv[i]), 3 * H, c.at(w.db), c.at(w.da), N, H, c.at(w.z2[i - 1]), c.at(w.mean2[i - 1]),
+                    c.at(w.rstd2[i - 1]), c.prm(pl.ln2_g[i - 1]), c.grd(pl.ln2_g[i - 1]), c.grd(pl.ln2_b[i - 1]), sc, c.s));
+  else
+    RC(dgrad_ln_bwd(c.at(w.dqkv), 3 * H, c.prm(pl.wqkv[i]), 3 * H, c.at(w.db), c.at(w.da), N, H, nullptr, c.at(w.mean0), c.at(w.rstd0),
+                    c.prm(pl.emb_ln_g), c.grd(pl.emb_ln_g), c.grd(pl.emb_ln_b), sc, c.s, c.batch.input_word_ids, c.prm(pl.word_emb),
+                    c.prm(pl.pos_emb), c.L, c.V, c.rng, B4R_STREAM_EMB, c.od));
+  RC(c.take(b4r_gemm_tn_scratch_floats(N, H, 3 * H), &sc));
+  return gemm_tn_f32({.A = x_in, .lda = H, .B = c.at(w.dqkv), .ldb = 3 * H, .out = c.grd(pl.wqkv[i]), .ldo = 3 * H, .R = N, .Mo = H,
+                      .No = 3 * H, .colsum = c.grd(pl.bqkv[i])}, sc, c.s);
+}
+
+}  // namespace
+
+// *norm_np (b4r_train_step, B4R_FLAG_NORM_PARTIALS_INTERNAL): > 0 where the closing reduce launch also left that many partial sums of
+// squares of the gradients at the start of the workspace (dead by then), so that the optimizer needs no norm launch
+static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, const StepPlan& plan, const float* params, float* grads,
+                         void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags, b4r_stream_t stream,
+                         int* norm_np) {
+  B4R_CHECK_ARG(params && grads && workspace && batch->masked_lm_ids, B4R_E_BADARG, "b4r_backward: null argument");
+  B4R_CHECK_ARG(b4r_aligned16(params) && b4r_aligned16(grads) && b4r_aligned16(workspace), B4R_E_ALIGN,
+                "b4r_backward: buffers must be 16-byte aligned");
+  Step c(cfg, batch, plan, params, grads, workspace, state, flags, stream);
+  B4R_CHECK_ARG(workspace_bytes >= c.w.total * (int64_t)sizeof(float), B4R_E_NOMEM, "b4r_backward: workspace too small");
+  B4R_CHECK_ARG(!(flags & B4R_FLAG_GRAD_TAIL) || state, B4R_E_BADARG, "b4r_backward: B4R_FLAG_GRAD_TAIL needs the state");
+  B4R_CHECK_ARG(!(flags & B4R_FLAG_LOSS_SUMS) || ((flags & B4R_FLAG_FUSED_HEAD) && state && batch->masked_lm_ids), B4R_E_BADARG,
+                "b4r_backward: B4R_FLAG_LOSS_SUMS needs B4R_FLAG_FUSED_HEAD, the state and masked_lm_ids");
+  B4R_CHECK_ARG(!plan.fused_head || b4r_fused_head_supported(cfg), B4R_E_BADARG,
+                "b4r_backward: B4R_FLAG_FUSED_HEAD needs hidden size 64 / 128 / 256 and the bf16x3 mode");
+  const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
+  B4rReduceQueue queue;
+  b4r_reduce_queue_begin(&queue);   // every ordered reduction below is summed by ONE launch at the end
+  RC(head_bwd(c));
   // ---- encoder layers, last to first ---------------------------------------------------------------------------------
-  const int64_t ln_scratch = std::max(b4r_ln_bwd_scratch_floats(N, H), b4r_gemm_ln_bwd_partial_floats(N));
-  for (int i = cfg->num_layers - 1; i >= 0; --i) {
-    const float* x_in = (i == 0) ? ws + w.x0 : ws + w.x2[i - 1];
-    float* wo_scratch_of_layer = nullptr;
+  for (int i = c.last; i >= 0; --i) {
+    const float* x_in = (i == 0) ? c.at(w.x0) : c.at(w.x2[i - 1]);
     // output LayerNorm (for every layer but the last its backward rode on the QKV input-gradient product of layer i + 1)
-    const bool rows_here = head_rows && i == cfg->num_layers - 1;
-    if (i == cfg->num_layers - 1 && !rows_here)
-      RC(b4r_ln_bwd_launch(ws + w.dx, ws + w.z2[i], ws + w.mean2[i], ws + w.rstd2[i], params + pl.ln2_g[i], N, H, ws + w.da,
-                           grads + pl.ln2_g[i], grads + pl.ln2_b[i], take(ln_scratch), nullptr, nullptr, nullptr, 1, 1, nodrop, s));
-    if (ffn_fused(cfg)) {
-      // feed-forward block: dz1 (-> db), dW1 / db1 / dW2 / db2 and the attention LayerNorm's gamma / beta gradients from dz2 (da);
-      // the [N, inner] pre-activation is recomputed from x1 inside the two kernels
-      b4r_ffn_desc fd{};
-      fd.N = N; fd.H = H; fd.I = I;
-      fd.x1 = attn_fused(cfg, L) ? nullptr : ws + w.x1[i];   // as the forward of this step left it
-      fd.W1 = params + pl.w1[i]; fd.b1 = params + pl.b1[i]; fd.W2 = params + pl.w2[i]; fd.b2 = params + pl.b2[i];
-      fd.rng = od > 0.f ? rng : nullptr; fd.drop_stream = B4R_STREAM_FFN_OUT(i); fd.drop_rate = od;
-      fd.dz2 = ws + w.da; fd.z1 = ws + w.z1[i]; fd.mean1 = ws + w.mean1[i]; fd.rstd1 = ws + w.rstd1[i];
-      fd.ln1_gamma = params + pl.ln1_g[i]; fd.ln1_beta = params + pl.ln1_b[i]; fd.dz1 = ws + w.db;
-      fd.dW1 = grads + pl.w1[i]; fd.db1 = grads + pl.b1[i]; fd.dW2 = grads + pl.w2[i]; fd.db2 = grads + pl.b2[i];
-      fd.dln1_gamma = grads + pl.ln1_g[i];
-      fd.scratch = take(b4r_ffn_block_bwd_scratch_floats(N));
-      if (rows_here) {   // the output LayerNorm's backward runs inside, on the rows with a gradient; dz1 elsewhere stays zero
-        fd.dz2 = nullptr;
-        fd.slot_positions = batch->masked_lm_positions; fd.slot_ids = batch->masked_lm_ids; fd.slots_per_seq = batch->P; fd.seq_len = L;
-        fd.max_rows = (int32_t)w.maxrows;
-        fd.slot_grad = ws + w.dg; fd.z2 = ws + w.z2[i]; fd.mean2 = ws + w.mean2[i]; fd.rstd2 = ws + w.rstd2[i];
-        fd.ln_gamma = params + pl.ln2_g[i]; fd.dln_gamma = grads + pl.ln2_g[i]; fd.dz2_rows = ws + w.dz2c;
-      }
-      RC(b4r_ffn_block_bwd(&fd, stream));
-    } else if (rows_here) {
-      // the compact form of the chain below: every operand is [M, .], one row per masked-LM slot (slots without a label carry an exactly
-      // zero gradient; two labelled slots never share a row).  dz1 (db) was cleared by the opening launch; the compact result is
-      // scatter-added into it.
-      const CompactRows cr = compact_rows(w, i, M, H, I);
-      float* dz2c = ws + w.dzc_a;                 // LayerNorm2 backward of the slot gradients
-      float* dz2d = od > 0.f ? ws + w.dzc_b : dz2c;   // ... through the output dropout
-      RC(b4r_ln_bwd_launch(ws + w.dg, ws + w.z2[i], ws + w.mean2[i], ws + w.rstd2[i], params + pl.ln2_g[i], M, H, dz2c,
-                           grads + pl.ln2_g[i], grads + pl.ln2_b[i], take(ln_scratch), nullptr, nullptr, nullptr, 1, 1, nodrop, s));
-      if (od > 0.f)
-        RC(b4r_slot_rows_drop(dz2c, batch->masked_lm_positions, L, P, M, H, b4r_make_drop(rng, B4R_STREAM_FFN_OUT(i), od, 1), dz2d, s));
-      RC(gemm(dz2d, H, params + pl.w2[i], H, ws + w.df, I, M, I, H, 1, B4R_EPI_GELU_BWD, nullptr, nullptr, 0, ws + w.fpre[i], I, 1.f, 0,
-              nullptr, 0, 0.f, 0, s));
-      RC(gemm_tn(ws + w.f[i], I, dz2d, H, grads + pl.w2[i], H, M, I, H, grads + pl.b2[i], nullptr, nullptr, 0, 0.f, 0,
-                 take(b4r_gemm_tn_scratch_floats(M, I, H)), s));
-      RC(dgrad_ln_bwd(ws + w.df, I, params + pl.w1[i], I, dz2c, ws + w.dz2c, M, H, ws + cr.z1c, ws + cr.mean1c, ws + cr.rstd1c,
-                      params + pl.ln1_g[i], grads + pl.ln1_g[i], grads + pl.ln1_b[i], take(ln_scratch), s));
-      RC(gemm_tn(ws + cr.x1c, H, ws + w.df, I, grads + pl.w1[i], I, M, H, I, grads + pl.b1[i], nullptr, nullptr, 0, 0.f, 0,
-                 take(b4r_gemm_tn_scratch_floats(M, H, I)), s));
-      RC(b4r_scatter_add_rows_impl(ws + w.dz2c, batch->masked_lm_positions, L, P, M, H, ws + w.db, H, batch->masked_lm_ids, N, 0, nullptr, s));
-    } else if (ffn32w_train_ok(cfg)) {
-      // dF and dX1 (residual included) in one launch from the records the forward packed; LayerNorm1's backward in place; the two
-      // weight gradients as before
-      b4r_ffn_desc fd{};
-      fd.N = N; fd.H = H; fd.I = I;
-      fd.W1 = params + pl.w1[i]; fd.b1 = params + pl.b1[i]; fd.W2 = params + pl.w2[i]; fd.b2 = params + pl.b2[i];
-      fd.rng = od > 0.f ? rng : nullptr; fd.drop_stream = B4R_STREAM_FFN_OUT(i); fd.drop_rate = od;
-      fd.dz2 = ws + w.da;
-      RC(b4r_ffn32w_bwd(&fd, ws + w.ffnrec[i], ws + w.fpre[i], ws + w.df, ws + w.db, true, s));
-      RC(gemm_tn(ws + w.f[i], I, ws + w.da, H, grads + pl.w2[i], H, N, I, H, grads + pl.b2[i], nullptr, rng, B4R_STREAM_FFN_OUT(i), od, 1,
-                 take(b4r_gemm_tn_scratch_floats(N, I, H)), s));
-      RC(b4r_ln_bwd_launch(ws + w.db, ws + w.z1[i], ws + w.mean1[i], ws + w.rstd1[i], params + pl.ln1_g[i], N, H, ws + w.db,
-                           grads + pl.ln1_g[i], grads + pl.ln1_b[i], take(ln_scratch), nullptr, nullptr, nullptr, 1, 1, nodrop, s));
-      RC(gemm_tn(ws + w.x1[i], H, ws + w.df, I, grads + pl.w1[i], I, N, H, I, grads + pl.b1[i], nullptr, nullptr, 0, 0.f, 0,
-                 take(b4r_gemm_tn_scratch_floats(N, H, I)), s));
-    } else {
-    // FFN: dFpre = (dropmask(dz2) . W2^T) * gelu'(fpre) and dW2 = f^T . dropmask(dz2) (+ bias gradient): one pass over dz2
-    // where the pair kernel applies, else two products
-    {
-      b4r_gemm_tn_desc d{};
-      d.A = ws + w.f[i]; d.lda = I; d.B = ws + w.da; d.ldb = H; d.out = grads + pl.w2[i]; d.ldo = H; d.R = N; d.Mo = I; d.No = H;
-      d.colsum = grads + pl.b2[i]; d.rng = rng; d.drop_stream = B4R_STREAM_FFN_OUT(i); d.drop_rate = od; d.b_dropout = 1;
-      d.dgrad_w = params + pl.w2[i]; d.dgrad_ldw = H; d.dgrad_out = ws + w.df; d.dgrad_ldo = I;
-      d.dgrad_gelu_pre = ws + w.fpre[i]; d.dgrad_ldg = I;
-      if (b4r_gemm_tn_dgrad_supported(&d)) {
-        RC(b4r_gemm_tn_f32(&d, take(b4r_gemm_tn_scratch_floats(N, I, H)), (b4r_stream_t)s));
-      } else {
-        RC(gemm(ws + w.da, H, params + pl.w2[i], H, ws + w.df, I, N, I, H, 1, B4R_EPI_GELU_BWD, nullptr, nullptr, 0, ws + w.fpre[i],
-                I, 1.f, 0, rng, B4R_STREAM_FFN_OUT(i), od, 1, s));
-        RC(gemm_tn(ws + w.f[i], I, ws + w.da, H, grads + pl.w2[i], H, N, I, H, grads + pl.b2[i], nullptr, rng,
-                   B4R_STREAM_FFN_OUT(i), od, 1, take(b4r_gemm_tn_scratch_floats(N, I, H)), s));
-      }
+    if (i == c.last && !plan.rows()) {
+      float* sc; RC(c.take(ln_scratch_floats(c.N, c.H), &sc));
+      RC(b4r_ln_bwd_launch(c.at(w.dx), c.at(w.z2[i]), c.at(w.mean2[i]), c.at(w.rstd2[i]), c.prm(pl.ln2_g[i]), c.N, c.H, c.at(w.da),
+                           c.grd(pl.ln2_g[i]), c.grd(pl.ln2_b[i]), sc, nullptr, nullptr, nullptr, 1, 1, b4r_make_drop(nullptr, 0, 0.f, 0),
+                           c.s));
     }
-    // dz1 = attention LayerNorm backward of dX1 = dFpre . W1^T + dz2
-    RC(dgrad_ln_bwd(ws + w.df, I, params + pl.w1[i], I, ws + w.da, ws + w.db, N, H, ws + w.z1[i], ws + w.mean1[i], ws + w.rstd1[i],
-                    params + pl.ln1_g[i], grads + pl.ln1_g[i], grads + pl.ln1_b[i], take(ln_scratch), s));
-    RC(gemm_tn(ws + w.x1[i], H, ws + w.df, I, grads + pl.w1[i], I, N, H, I, grads + pl.b1[i], nullptr, nullptr, 0, 0.f, 0,
-               take(b4r_gemm_tn_scratch_floats(N, H, I)), s));
+    switch (plan.ffn[i]) {
+      case FfnForm::Block: RC(ffn_bwd_block(c, i)); break;
+      case FfnForm::CompactRows: RC(ffn_bwd_compact(c, i)); break;
+      case FfnForm::Wide: RC(ffn_bwd_wide(c, i)); break;
+      case FfnForm::TileProducts: RC(ffn_bwd_tiles(c, i)); break;
     }
-    const bool dw_folded = attn_bwd_fused(cfg, L) && b4r_attn32_active(H, cfg->num_heads, L);
-    if (attn_bwd_fused(cfg, L)) {
-      // dWo = ctx^T . dropmask(dz1) (+ bias gradient); then the attention block's backward in one launch: dqkv and, through the
-      // LayerNorm in front of this layer, da (for layer 0: through the embedding stage's dropout and LayerNorm)
-      wo_scratch_of_layer = take(b4r_gemm_tn_scratch_floats(N, H, H));   // dWo's slabs for the pair launch after the block
-      b4r_attn_block_bwd_desc bd{};
-      bd.B = B; bd.L = L; bd.H = H; bd.heads = cfg->num_heads;
-      bd.x = x_in; bd.dz1 = ws + w.db; bd.ctx = ws + w.ctx[i]; bd.lse = ws + w.lse[i];
-      bd.keep_bits = reinterpret_cast<const uint32_t*>(ws + w.keep[i]); bd.input_mask = batch->input_mask;
-      bd.Wqkv = params + pl.wqkv[i]; bd.bqkv = params + pl.bqkv[i]; bd.Wo = params + pl.wo[i];
-      bd.rng = (od > 0.f || adp > 0.f) ? rng : nullptr;
-      bd.probs_stream = B4R_STREAM_ATTN_PROBS(i); bd.probs_rate = adp; bd.out_stream = B4R_STREAM_ATTN_OUT(i); bd.out_rate = od;
-      if (i > 0) {
-        bd.prev_z = ws + w.z2[i - 1]; bd.prev_mean = ws + w.mean2[i - 1]; bd.prev_rstd = ws + w.rstd2[i - 1];
-        bd.prev_gamma = params + pl.ln2_g[i - 1]; bd.dprev_gamma = grads + pl.ln2_g[i - 1];
-      } else {
-        bd.prev_mean = ws + w.mean0; bd.prev_rstd = ws + w.rstd0; bd.prev_gamma = params + pl.emb_ln_g;
-        bd.dprev_gamma = grads + pl.emb_ln_g;
-        bd.emb_ids = batch->input_word_ids; bd.emb_table = params + pl.word_emb; bd.emb_pos = params + pl.pos_emb; bd.emb_vocab = V;
-        bd.emb_stream = B4R_STREAM_EMB; bd.emb_rate = od;
-      }
-      bd.dqkv = ws + w.dqkv; bd.dx_prev = ws + w.da;
-      bd.scratch = take(b4r_attn_block_bwd_scratch_floats(B));
-      if (dw_folded) {   // dWqkv / dbqkv inside the launch: no [N, 3H] round trip, no weight-gradient launch for them
-        bd.dqkv = nullptr; bd.dWqkv = grads + pl.wqkv[i]; bd.dbqkv = grads + pl.bqkv[i];
-        bd.dw_scratch = take(b4r_attn_block_bwd_dw_scratch_floats(B));
-        bd.dWo = grads + pl.wo[i]; bd.dbo = grads + pl.bo[i];   // ... nor for dWo / dbo
-      }
-      if (sparse_dz1 && i == cfg->num_layers - 1) {
-        bd.dz1_slot_positions = batch->masked_lm_positions; bd.dz1_slot_ids = batch->masked_lm_ids; bd.dz1_slots = batch->P;
-      }
-      RC(b4r_attn_block_bwd(&bd, stream));
-    } else {
-    if (slotq_layer(cfg, batch, flags, i)) {
-      // compact: dz1 of the slots (left in dz2c by the feed-forward half above) -> dropout of the output projection -> dWo / dbo and
-      // dctx on [M, H] rows -> the attention core's backward with the slots as its queries (dq rows of the labelled slots, dk / dv of
-      // every token)
-      float* dz1d = od > 0.f ? ws + w.dctx + up4((int64_t)M * H) : ws + w.dz2c;   // (the dense dctx region is free in this mode)
-      float* dctx_c = ws + w.dctx;
-      if (od > 0.f)
-        RC(b4r_slot_rows_drop(ws + w.dz2c, batch->masked_lm_positions, L, P, M, H, b4r_make_drop(rng, B4R_STREAM_ATTN_OUT(i), od, 1), dz1d, s));
-      RC(gemm_tn(ws + w.ctx[i], H, dz1d, H, grads + pl.wo[i], H, M, H, H, grads + pl.bo[i], nullptr, nullptr, 0, 0.f, 0,
-                 take(b4r_gemm_tn_scratch_floats(N, H, H)), s));
-      RC(gemm(dz1d, H, params + pl.wo[i], H, dctx_c, H, M, H, H, 1, B4R_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, 1.f, 0, nullptr, 0,
-              0.f, 0, s));
-      RC(b4r_attn32_slotq_bwd_launch(ws + w.qkv[i], batch->input_mask, batch->masked_lm_positions, batch->masked_lm_ids, ws + w.ctx[i],
-                                     ws + w.lse[i], dctx_c, B, L, cfg->num_heads, P, qscale, ws + w.dqkv,
-                                     b4r_make_drop(rng, B4R_STREAM_ATTN_PROBS(i), adp, 1),
-                                     reinterpret_cast<const uint32_t*>(ws + w.keep[i]), s));
-    } else {
-    // attention output projection: dctx = dropmask(dz1) . Wo^T and dWo = ctx^T . dropmask(dz1) (+ bias gradient) read dz1
-    // once where the pair kernel applies (hidden size 64), else as two products
-    {
-      b4r_gemm_tn_desc d{};
-      d.A = ws + w.ctx[i]; d.lda = H; d.B = ws + w.db; d.ldb = H; d.out = grads + pl.wo[i]; d.ldo = H; d.R = N; d.Mo = H; d.No = H;
-      d.colsum = grads + pl.bo[i]; d.rng = rng; d.drop_stream = B4R_STREAM_ATTN_OUT(i); d.drop_rate = od; d.b_dropout = 1;
-      d.dgrad_w = params + pl.wo[i]; d.dgrad_ldw = H; d.dgrad_out = ws + w.dctx; d.dgrad_ldo = H;
-      if (b4r_gemm_tn_dgrad_supported(&d)) {
-        RC(b4r_gemm_tn_f32(&d, take(b4r_gemm_tn_scratch_floats(N, H, H)), (b4r_stream_t)s));
-      } else {
-        RC(gemm(ws + w.db, H, params + pl.wo[i], H, ws + w.dctx, H, N, H, H, 1, B4R_EPI_NONE, nullptr, nullptr, 0, nullptr, 0, 1.f,
-                0, rng, B4R_STREAM_ATTN_OUT(i), od, 1, s));
-        RC(gemm_tn(ws + w.ctx[i], H, ws + w.db, H, grads + pl.wo[i], H, N, H, H, grads + pl.bo[i], nullptr, rng,
-                   B4R_STREAM_ATTN_OUT(i), od, 1, take(b4r_gemm_tn_scratch_floats(N, H, H)), s));
-      }
+    switch (plan.attn_bwd[i]) {
+      case AttnBwd::Block: case AttnBwd::BlockFolded: RC(attn_bwd_block(c, i, x_in)); break;
+      case AttnBwd::SlotQuery: RC(attn_bwd_slotq(c, i)); RC(qkv_bwd(c, i, x_in)); break;
+      case AttnBwd::Core: RC(attn_bwd_core(c, i)); RC(qkv_bwd(c, i, x_in)); break;
     }
-    // attention core: dQ, dK, dV
-    RC(b4r_attn_bwd_hd(ws + w.qkv[i], batch->input_mask, ws + w.ctx[i], ws + w.lse[i], ws + w.dctx, B, L, cfg->num_heads,
-                       head_dim(cfg), qscale, ws + w.dqkv, rng, B4R_STREAM_ATTN_PROBS(i), adp,
-                       reinterpret_cast<const uint32_t*>(ws + w.keep[i]), stream));
-    }
-    // QKV projection: dX_in = dqkv . Wqkv^T + dz1, and for i > 0 straight on to layer i-1's output LayerNorm backward (-> da)
-    if (i > 0)
-      RC(dgrad_ln_bwd(ws + w.dqkv, 3 * H, params + pl.wqkv[i], 3 * H, ws + w.db, ws + w.da, N, H, ws + w.z2[i - 1],
-                      ws + w.mean2[i - 1], ws + w.rstd2[i - 1], params + pl.ln2_g[i - 1], grads + pl.ln2_g[i - 1],
-                      grads + pl.ln2_b[i - 1], take(ln_scratch), s));
-    else   // ... and for layer 0 on to the embedding stage: dropout -> LayerNorm of (item row + position row)
-      RC(dgrad_ln_bwd(ws + w.dqkv, 3 * H, params + pl.wqkv[i], 3 * H, ws + w.db, ws + w.da, N, H, nullptr, ws + w.mean0, ws + w.rstd0,
-                      params + pl.emb_ln_g, grads + pl.emb_ln_g, grads + pl.emb_ln_b, take(ln_scratch), s, batch->input_word_ids,
-                      params + pl.word_emb, params + pl.pos_emb, L, V, rng, B4R_STREAM_EMB, od));
-    }
-    if (dw_folded) continue;   // every weight gradient of the attention half came out of its backward launch
-    if (attn_bwd_fused(cfg, L)) {   // dWo (inputs ready since the feed-forward backward) and dWqkv: one launch
-      const b4r_gemm_tn_desc d_wo = tn_desc(ws + w.ctx[i], H, ws + w.db, H, grads + pl.wo[i], H, N, H, H, grads + pl.bo[i], rng,
-                                            B4R_STREAM_ATTN_OUT(i), od, 1);
-      const b4r_gemm_tn_desc d_wqkv = tn_desc(x_in, H, ws + w.dqkv, 3 * H, grads + pl.wqkv[i], 3 * H, N, H, 3 * H, grads + pl.bqkv[i],
-                                              nullptr, 0, 0.f, 0);
-      RC(b4r_gemm_tn_pair(&d_wo, wo_scratch_of_layer, &d_wqkv, take(b4r_gemm_tn_scratch_floats(N, H, 3 * H)), s));
-      continue;
-    }
-    RC(gemm_tn(x_in, H, ws + w.dqkv, 3 * H, grads + pl.wqkv[i], 3 * H, N, H, 3 * H, grads + pl.bqkv[i], nullptr, nullptr, 0, 0.f,
-               0, take(b4r_gemm_tn_scratch_floats(N, H, 3 * H)), s));
   }
   // ---- embedding stage: its dropout -> LayerNorm backward ran with layer 0's QKV product (da = d(item row + position row));
   // what remains: word table scatter-add, position table batch sum
   // the item-table scatter sums in 64-bit fixed point beside the float gradient (bitwise reproducible; b4r_rowops.hip), so it
   // need not wait for the head's part of that gradient: ONE launch then sums every queued ordered reduction (weight / bias /
   // LayerNorm gradients, the position table) and adds the fixed-point sums to the item table
-  RC(b4r_embed_grads(ws + w.da, batch->input_word_ids, B, L, H, grads + pl.word_emb, V, 3, ws + w.hot /* zeroed at the top */,
-                     grads + pl.pos_emb, take((int64_t)b4r_cdiv(B, 16) * L * H), s, defer_combine ? ws + w.rowsc : nullptr, (int)w.M, state,
-                     (defer_combine && (flags & B4R_FLAG_GRAD_TAIL)) ? grads + pl.total : nullptr));
-  g_norm_np = 0;
-  if (flags & B4R_FLAG_NORM_PARTIALS_INTERNAL) {
-    // valid only when the jobs of this launch write EVERY gradient (then each value is squared exactly once, as it is stored)
-    const int64_t Hh = H, Ii = I, Vv = V;
-    const int64_t expected = Vv * Hh + (int64_t)L * Hh + 2 * Hh /* embedding LayerNorm */ +
-                             (int64_t)cfg->num_layers * (Hh * 3 * Hh + Hh * Hh + 2 * Hh * Ii + 3 * Hh + Hh + 2 * Hh + Ii + Hh + 2 * Hh) +
-                             Hh * Hh + Hh + 2 * Hh /* transform */ + Vv /* output bias */;
-    int np = 0;
-    int64_t covered = 0;
-    RC(b4r_reduce_queue_flush(s, ws, 4096, &np, &covered));
-    if (np > 0 && covered == expected) g_norm_np = np;
-  } else {
-    RC(b4r_reduce_queue_flush(s));
-  }
-  B4R_CHECK_ARG(scratch_used <= w.scratch_floats, B4R_E_NOMEM, "b4r_backward: internal scratch overflow");
+  float* sc; RC(c.take((int64_t)b4r_cdiv(c.B, 16) * c.L * c.H, &sc));
+  RC(b4r_embed_grads(c.at(w.da), batch->input_word_ids, c.B, c.L, c.H, c.grd(pl.word_emb), c.V, 3, c.at(w.hot) /* zeroed at the top */,
+                     c.grd(pl.pos_emb), sc, c.s, plan.defer_combine ? c.at(w.rowsc) : nullptr, (int)w.M, state,
+                     (plan.defer_combine && (flags & B4R_FLAG_GRAD_TAIL)) ? c.grd(pl.total) : nullptr));
+  if (norm_np) *norm_np = 0;
+  if (!(flags & B4R_FLAG_NORM_PARTIALS_INTERNAL)) return b4r_reduce_queue_flush(c.s);
+  // valid only when the jobs of this launch write EVERY gradient (then each value is squared exactly once, as it is stored)
+  const int64_t H = c.H, I = c.I, V = c.V;
+  const int64_t expected = V * H + (int64_t)c.L * H + 2 * H /* embedding LayerNorm */ +
+                           (int64_t)cfg->num_layers * (H * 3 * H + H * H + 2 * H * I + 3 * H + H + 2 * H + I + H + 2 * H) +
+                           H * H + H + 2 * H /* transform */ + V /* output bias */;
+  int np = 0;
+  int64_t covered = 0;
+  RC(b4r_reduce_queue_flush(c.s, c.ws, 4096, &np, &covered));
+  if (norm_np && np > 0 && covered == expected) *norm_np = np;
   return B4R_OK;
 }
 
@@ -1149,28 +1261,27 @@ extern "C" int b4r_optimizer_step_reduced(const b4r_model_config* cfg, const b4r
 extern "C" int b4r_train_step(const b4r_model_config* cfg, const b4r_adamw_config* hp, const b4r_batch* batch, float* params,
                               float* grads, float* adam_m, float* adam_v, void* workspace, int64_t workspace_bytes,
                               b4r_train_state* state, b4r_stream_t stream) {
+  RC(check_cfg(cfg));
+  RC(check_batch(batch, cfg, true));
   const int fused = b4r_fused_head_supported(cfg) ? 1 : 0;   // the train step never needs the logits themselves
-  const int defer = (fused && batch && b4r_head32_combine_foldable(batch->B * batch->P, cfg->vocab_size, cfg->hidden_size))
+  const int defer = (fused && b4r_head32_combine_foldable(batch->B * batch->P, cfg->vocab_size, cfg->hidden_size))
                         ? B4R_FLAG_DEFER_COMBINE_INTERNAL : 0;
   // no b4r_state_begin_step launch: the loss reduction overwrites the sums (B4R_LOSS_OVERWRITE)
   // nothing but the loss, the metrics and the gradients leave a train step: the last layer's feed-forward half runs on the rows the
-  // head gathers only (B4R_FLAG_HEAD_ROWS_ONLY; the same flag goes to forward and backward)
-  RC(forward_impl(cfg, batch, params, nullptr, workspace, workspace_bytes, state,
-                  B4R_FLAG_TRAINING | B4R_FLAG_HEAD_ROWS_ONLY | (fused ? B4R_FLAG_FUSED_HEAD : 0) | defer, stream));
+  // head gathers only (B4R_FLAG_HEAD_ROWS_ONLY)
+  const int32_t fwd_flags = B4R_FLAG_TRAINING | B4R_FLAG_HEAD_ROWS_ONLY | (fused ? B4R_FLAG_FUSED_HEAD : 0) | defer;
   // with the logits-free head the loss sums are formed inside the backward's first launch (B4R_FLAG_LOSS_SUMS), else by b4r_loss
+  const int32_t bwd_flags = fwd_flags | (fused ? B4R_FLAG_LOSS_SUMS : 0) | B4R_FLAG_NORM_PARTIALS_INTERNAL;
+  const StepPlan plan = plan_step(cfg, batch, bwd_flags);   // (the backward's flags: the forward's and what it alone reads)
+  RC(forward_impl(cfg, batch, plan, params, nullptr, workspace, workspace_bytes, state, fwd_flags, stream));
   if (!fused) RC(b4r_loss(cfg, batch, workspace, workspace_bytes, state, 1 | B4R_LOSS_OVERWRITE, stream));
-  RC(backward_impl(cfg, batch, params, grads, workspace, workspace_bytes, state,
-                   B4R_FLAG_TRAINING | B4R_FLAG_HEAD_ROWS_ONLY |
-                      (fused ? B4R_FLAG_FUSED_HEAD | B4R_FLAG_LOSS_SUMS : 0) | defer |
-                      B4R_FLAG_NORM_PARTIALS_INTERNAL, stream));
-  const int np = g_norm_np;   // > 0: the backward's last launch left the norm's partial sums at the start of the workspace
-  g_norm_np = 0;
+  int np = 0;   // > 0: the backward's last launch left the norm's partial sums at the start of the workspace
+  RC(backward_impl(cfg, batch, plan, params, grads, workspace, workspace_bytes, state, bwd_flags, stream, &np));
   if (np > 0) {
     B4R_CHECK_ARG(hp && adam_m && adam_v, B4R_E_BADARG, "b4r_train_step: null argument");
     const ParamLayout pl = make_param_layout(*cfg);
     return b4r_optimizer_fused(hp, params, grads, adam_m, adam_v, pl.total, pl.n_decay, static_cast<float*>(workspace), state,
                                (hipStream_t)stream, 0, np);
   }
-  RC(b4r_optimizer_step(cfg, hp, params, grads, adam_m, adam_v, workspace, workspace_bytes, state, stream));
-  return B4R_OK;
+  return b4r_optimizer_step(cfg, hp, params, grads, adam_m, adam_v, workspace, workspace_bytes, state, stream);
 }
