@@ -22,6 +22,12 @@ class ModelConfig(C.Structure):
                 ("output_dropout", C.c_float), ("attention_dropout", C.c_float), ("ln_eps", C.c_float)]
 
 
+class ModelConfigEx(C.Structure):
+    """b4r_model_config_ex: the classic config plus embedding_width (0 or hidden_size: unfactorised; else 64 / 128 / 256 below
+    hidden_size) and three reserved words that must be zero."""
+    _fields_ = [("base", ModelConfig), ("embedding_width", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class Batch(C.Structure):
     _fields_ = [("input_word_ids", C.c_void_p), ("input_mask", C.c_void_p), ("masked_lm_positions", C.c_void_p),
                 ("masked_lm_ids", C.c_void_p), ("B", C.c_int32), ("L", C.c_int32), ("P", C.c_int32)]
@@ -131,6 +137,29 @@ PROTOTYPES = {
     "b4r_state_begin_step": (C.c_int, [_P, _P]),
     "b4r_train_step": (C.c_int, [C.POINTER(ModelConfig), C.POINTER(AdamWConfig), C.POINTER(Batch), _P, _P, _P, _P, _P,
                                  _I64, _P, _P]),
+    "b4r_param_total_floats_ex": (_I64, [C.POINTER(ModelConfigEx)]),
+    "b4r_param_decay_floats_ex": (_I64, [C.POINTER(ModelConfigEx)]),
+    "b4r_param_count_ex": (_I32, [C.POINTER(ModelConfigEx)]),
+    "b4r_param_info_ex": (C.c_int, [C.POINTER(ModelConfigEx), _I32, C.c_char_p, C.c_size_t, C.POINTER(_I64),
+                                    C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
+    "b4r_workspace_bytes_ex": (_I64, [C.POINTER(ModelConfigEx), _I32, _I32, _I32]),
+    "b4r_workspace_bytes_encoder_ex": (_I64, [C.POINTER(ModelConfigEx), _I32, _I32, _I32]),
+    "b4r_workspace_region_ex": (C.c_int, [C.POINTER(ModelConfigEx), _I32, _I32, _I32, C.c_char_p, C.POINTER(_I64),
+                                          C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
+    "b4r_fused_head_supported_ex": (_I32, [C.POINTER(ModelConfigEx)]),
+    "b4r_forward_ex": (C.c_int, [C.POINTER(ModelConfigEx), C.POINTER(Batch), _P, _P, _P, _I64, _P, _I32, _P]),
+    "b4r_loss_ex": (C.c_int, [C.POINTER(ModelConfigEx), C.POINTER(Batch), _P, _I64, _P, _I32, _P]),
+    "b4r_backward_ex": (C.c_int, [C.POINTER(ModelConfigEx), C.POINTER(Batch), _P, _P, _P, _I64, _P, _I32, _P]),
+    "b4r_optimizer_step_ex": (C.c_int, [C.POINTER(ModelConfigEx), C.POINTER(AdamWConfig), _P, _P, _P, _P, _P, _I64, _P, _P]),
+    "b4r_optimizer_step_reduced_ex": (C.c_int, [C.POINTER(ModelConfigEx), C.POINTER(AdamWConfig), _P, _P, _P, _P, _P, _I64, _P,
+                                                _P]),
+    "b4r_train_step_ex": (C.c_int, [C.POINTER(ModelConfigEx), C.POINTER(AdamWConfig), C.POINTER(Batch), _P, _P, _P, _P, _P,
+                                    _I64, _P, _P]),
+    "b4r_mlm_transform_rows_ex": (C.c_int, [C.POINTER(ModelConfigEx), _P, _P, _I64, _P, _I32, _P, _P, _P]),
+    "b4r_embed_proj_fwd": (C.c_int, [_P, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _F, _P, _P, _I32, _P, _P, _P, _P, _F, _P]),
+    "b4r_embed_proj_bwd_scratch_floats": (_I64, [_I32, _I32, _I32]),
+    "b4r_embed_proj_bwd": (C.c_int, [_P, _P, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _P, _P, _P, _I32, _P, _F, _P, _P, _P, _P, _P,
+                                     _P]),
     "b4r_rank_scratch_bytes": (_I64, [_I32, _I32]),
     "b4r_rank_candidates": (C.c_int, [_P, _I32, _P, _P, _P, _I32, _I32, _P, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P]),
     "b4r_rank_full_scratch_bytes": (_I64, [_I32, _I32, _I32]),

@@ -61,6 +61,15 @@ int b4r_embed_grads(const float* x, const int64_t* ids, int B, int L, int H, flo
                     float* fixed, float* dpos, float* colsum_scratch, hipStream_t stream, const float* fin_rows = nullptr,
                     int fin_M = 0, b4r_train_state* state = nullptr, float* tail = nullptr);
 int64_t b4r_embed_fixed_floats(int64_t V, int H, int hot_rows);
+// b4r_embed_proj.hip: the factorised embedding stage (embedding_width E < hidden size H) and its backward, one launch each
+bool b4r_embed_proj_supported(int E, int H);
+int64_t b4r_embed_proj_bwd_scratch_floats_impl(int N, int E, int H);
+int b4r_embed_proj_fwd_launch(const int64_t* ids, int B, int L, const float* table, int V, const float* pos, const float* gamma,
+                              const float* beta, int E, float eps, const float* Wp, const float* bp, int H, float* x0, float* mean,
+                              float* rstd, DropArgs drop, hipStream_t stream);
+int b4r_embed_proj_bwd_launch(const float* dx0, const int64_t* ids, int B, int L, const float* table, int V, const float* pos,
+                              const float* gamma, const float* beta, int E, const float* mean, const float* rstd, const float* Wp, int H,
+                              DropArgs drop, float* drows, float* dWp, float* dbp, float* dln, float* scratch, hipStream_t stream);
 int b4r_gemm_tn_pair(const b4r_gemm_tn_desc* d0, float* scratch0, const b4r_gemm_tn_desc* d1, float* scratch1, hipStream_t stream);
 bool b4r_attn32_active(int H, int heads, int L);   // b4r_attn_block.hip: the 32-token-tile backward (it can form dWqkv / dbqkv itself)
 int b4r_ce_finalize_launch(const float* row_scratch, int M, b4r_train_state* state, int overwrite, hipStream_t stream);
@@ -156,6 +165,12 @@ extern "C" int b4r_timing_end(int32_t* n_launches, float* micros, char* names, i
 
 namespace {
 
+#define RC(x)                 \
+  do {                        \
+    int rc__ = (x);           \
+    if (rc__ != B4R_OK) return rc__; \
+  } while (0)
+
 inline int64_t up4(int64_t x) { return (x + 3) & ~(int64_t)3; }
 inline int64_t up32(int64_t x) { return (x + 31) & ~(int64_t)31; }
 
@@ -178,6 +193,33 @@ int check_cfg(const b4r_model_config* c) {
   return B4R_OK;
 }
 
+// The model configuration every internal function takes: the classic fields plus the resolved embedding width E (== hidden_size for
+// the unfactorised model).  The classic entry points reach the same code through b4r_model_config_ex with embedding_width = 0.
+struct ModelCfg : b4r_model_config {
+  int E;
+  bool factorised() const { return E != hidden_size; }
+};
+
+b4r_model_config_ex classic_ex(const b4r_model_config* c) {
+  b4r_model_config_ex x{};
+  if (c) x.base = *c;
+  return x;
+}
+
+// validates the extended config and resolves E; a bad width or a nonzero reserved word is an error, never a fault
+int resolve_cfg(const b4r_model_config_ex* x, ModelCfg* out) {
+  B4R_CHECK_ARG(x != nullptr, B4R_E_BADARG, "null model config");
+  RC(check_cfg(&x->base));
+  B4R_CHECK_ARG(x->reserved[0] == 0 && x->reserved[1] == 0 && x->reserved[2] == 0, B4R_E_BADARG,
+                "b4r_model_config_ex: reserved words must be zero");
+  const int H = x->base.hidden_size, E = x->embedding_width;
+  B4R_CHECK_ARG(E == 0 || E == H || ((E == 64 || E == 128 || E == 256) && E < H && b4r_embed_proj_supported(E, H)), B4R_E_SHAPE,
+                "embedding_width %d not supported with hidden_size %d (0, hidden_size, or 64 / 128 / 256 below hidden_size)", E, H);
+  static_cast<b4r_model_config&>(*out) = x->base;
+  out->E = (E == 0) ? H : E;
+  return B4R_OK;
+}
+
 struct ParamEntry {
   std::string name;
   int64_t offset;
@@ -187,6 +229,7 @@ struct ParamEntry {
 struct ParamLayout {
   int64_t total = 0, n_decay = 0;
   int64_t word_emb = 0, pos_emb = 0, emb_ln_g = 0, emb_ln_b = 0;
+  int64_t proj_w = -1, proj_b = -1;   // embedding_projection kernel [E,H] / bias [H] (factorised only)
   int64_t wqkv[B4R_MAX_LAYERS], wo[B4R_MAX_LAYERS], w1[B4R_MAX_LAYERS], w2[B4R_MAX_LAYERS];
   int64_t bqkv[B4R_MAX_LAYERS], bo[B4R_MAX_LAYERS], ln1_g[B4R_MAX_LAYERS], ln1_b[B4R_MAX_LAYERS], b1[B4R_MAX_LAYERS],
       b2[B4R_MAX_LAYERS], ln2_g[B4R_MAX_LAYERS], ln2_b[B4R_MAX_LAYERS];
@@ -194,17 +237,18 @@ struct ParamLayout {
   std::vector<ParamEntry> entries;
 };
 
-ParamLayout make_param_layout(const b4r_model_config& c) {
+ParamLayout make_param_layout(const ModelCfg& c) {
   ParamLayout p;
-  const int64_t H = c.hidden_size, I = c.inner_dim, V = c.vocab_size, Lm = c.max_seq_len;
+  const int64_t H = c.hidden_size, I = c.inner_dim, V = c.vocab_size, Lm = c.max_seq_len, E = c.E;
   int64_t off = 0;
   auto take = [&](int64_t n) { int64_t o = off; off += up4(n); return o; };
   auto add = [&](const std::string& name, int64_t o, int rows, int cols, int ld, int decay) {
     p.entries.push_back(ParamEntry{name, o, rows, cols, ld, decay});
   };
   // ---- weight-decayed region: kernels and the two embedding tables
-  p.word_emb = take(V * H); add("word_embeddings/embeddings", p.word_emb, (int)V, (int)H, (int)H, 1);
-  p.pos_emb = take(Lm * H); add("position_embedding/embeddings", p.pos_emb, (int)Lm, (int)H, (int)H, 1);
+  p.word_emb = take(V * E); add("word_embeddings/embeddings", p.word_emb, (int)V, (int)E, (int)E, 1);
+  p.pos_emb = take(Lm * E); add("position_embedding/embeddings", p.pos_emb, (int)Lm, (int)E, (int)E, 1);
+  if (c.factorised()) { p.proj_w = take(E * H); add("embedding_projection/kernel", p.proj_w, (int)E, (int)H, (int)H, 1); }
   for (int i = 0; i < c.num_layers; ++i) {
     const std::string pre = "transformer/layer_" + std::to_string(i);
     p.wqkv[i] = take(H * 3 * H);
@@ -215,11 +259,12 @@ ParamLayout make_param_layout(const b4r_model_config& c) {
     p.w1[i] = take(H * I); add(pre + "/intermediate/kernel", p.w1[i], (int)H, (int)I, (int)I, 1);
     p.w2[i] = take(I * H); add(pre + "/output/kernel", p.w2[i], (int)I, (int)H, (int)H, 1);
   }
-  p.wd = take(H * H); add("cls/predictions/transform/dense/kernel", p.wd, (int)H, (int)H, (int)H, 1);
+  p.wd = take(H * E); add("cls/predictions/transform/dense/kernel", p.wd, (int)H, (int)E, (int)E, 1);
   p.n_decay = off;
   // ---- not decayed: every bias and LayerNorm gamma/beta
-  p.emb_ln_g = take(H); add("embeddings/layer_norm/gamma", p.emb_ln_g, 1, (int)H, (int)H, 0);
-  p.emb_ln_b = take(H); add("embeddings/layer_norm/beta", p.emb_ln_b, 1, (int)H, (int)H, 0);
+  p.emb_ln_g = take(E); add("embeddings/layer_norm/gamma", p.emb_ln_g, 1, (int)E, (int)E, 0);
+  p.emb_ln_b = take(E); add("embeddings/layer_norm/beta", p.emb_ln_b, 1, (int)E, (int)E, 0);
+  if (c.factorised()) { p.proj_b = take(H); add("embedding_projection/bias", p.proj_b, 1, (int)H, (int)H, 0); }
   for (int i = 0; i < c.num_layers; ++i) {
     const std::string pre = "transformer/layer_" + std::to_string(i);
     p.bqkv[i] = take(3 * H);
@@ -234,9 +279,9 @@ ParamLayout make_param_layout(const b4r_model_config& c) {
     p.ln2_g[i] = take(H); add(pre + "/output_layer_norm/gamma", p.ln2_g[i], 1, (int)H, (int)H, 0);
     p.ln2_b[i] = take(H); add(pre + "/output_layer_norm/beta", p.ln2_b[i], 1, (int)H, (int)H, 0);
   }
-  p.bd = take(H); add("cls/predictions/transform/dense/bias", p.bd, 1, (int)H, (int)H, 0);
-  p.lnm_g = take(H); add("cls/predictions/transform/LayerNorm/gamma", p.lnm_g, 1, (int)H, (int)H, 0);
-  p.lnm_b = take(H); add("cls/predictions/transform/LayerNorm/beta", p.lnm_b, 1, (int)H, (int)H, 0);
+  p.bd = take(E); add("cls/predictions/transform/dense/bias", p.bd, 1, (int)E, (int)E, 0);
+  p.lnm_g = take(E); add("cls/predictions/transform/LayerNorm/gamma", p.lnm_g, 1, (int)E, (int)E, 0);
+  p.lnm_b = take(E); add("cls/predictions/transform/LayerNorm/beta", p.lnm_b, 1, (int)E, (int)E, 0);
   p.out_bias = take(V); add("cls/predictions/output_bias/bias", p.out_bias, 1, (int)V, (int)V, 0);
   p.total = off;
   return p;
@@ -267,9 +312,10 @@ struct WsLayout {
   int64_t scratch, scratch_floats;
 };
 
-WsLayout make_ws_layout(const b4r_model_config& c, int B, int L, int P) {
+// (the masked-LM head's [B*P, .] rows keep their width-H regions when E < H: same offsets, the head uses the first E columns' worth)
+WsLayout make_ws_layout(const ModelCfg& c, int B, int L, int P) {
   WsLayout w;
-  const int64_t H = c.hidden_size, I = c.inner_dim, V = c.vocab_size;
+  const int64_t H = c.hidden_size, I = c.inner_dim, V = c.vocab_size, E = c.E;
   const int64_t N = (int64_t)B * L, M = (int64_t)B * (P > 0 ? P : 0);
   w.N = N; w.M = M; w.Vp = up32(V);
   int64_t off = 0;
@@ -287,7 +333,7 @@ WsLayout make_ws_layout(const b4r_model_config& c, int B, int L, int P) {
   w.gath = take(M * H); w.upre = take(M * H); w.u = take(M * H); w.meanm = take(M); w.rstdm = take(M);
   w.t = take(M * H); w.logits = take(M * w.Vp); w.rowsc = take(4 * M); w.pooled = take((int64_t)B * H);
   w.head_lse = take(M); w.head_ylab = take(M);
-  w.dx = take(N * H); w.hot = take(b4r_embed_fixed_floats(c.vocab_size, (int)H, 3)); w.db = take(N * H); w.da = take(N * H); w.dctx = take(N * H);
+  w.dx = take(N * H); w.hot = take(b4r_embed_fixed_floats(c.vocab_size, (int)E, 3)); w.db = take(N * H); w.da = take(N * H); w.dctx = take(N * H);
   w.maxrows = M;
   w.dz2c = take(w.maxrows * H);
   w.dzc_a = take(M * H); w.dzc_b = take(M * H);
@@ -310,16 +356,17 @@ WsLayout make_ws_layout(const b4r_model_config& c, int B, int L, int P) {
   if (M > 0) {
     add(b4r_gemm_tn_scratch_floats((int)M, (int)H, (int)I));   // the last layer's weight gradients over the head's rows only
     add(b4r_gemm_tn_scratch_floats((int)M, (int)I, (int)H));
-    add(b4r_gemm_tn_scratch_floats((int)M, (int)V, (int)H));
-    add(b4r_gemm_tn_scratch_floats((int)M, (int)H, (int)H));
-    add(b4r_ln_bwd_scratch_floats((int)M, (int)H));
-    add((int64_t)mlm_dt_splits(M, H, V) * M * H);
-    if (b4r_head32_hidden_ok((int)H)) add(b4r_head32_dE_scratch_floats((int)M, (int)V, (int)H));
+    add(b4r_gemm_tn_scratch_floats((int)M, (int)V, (int)E));
+    add(b4r_gemm_tn_scratch_floats((int)M, (int)H, (int)E));
+    add(b4r_ln_bwd_scratch_floats((int)M, (int)E));
+    add((int64_t)mlm_dt_splits(M, E, V) * M * E);
+    if (b4r_head32_hidden_ok((int)E)) add(b4r_head32_dE_scratch_floats((int)M, (int)V, (int)E));
   }
-  add((int64_t)b4r_cdiv(B, 16) * L * H);  // position-table gradient partials
+  add((int64_t)b4r_cdiv(B, 16) * L * E);  // position-table gradient partials
+  if (c.factorised()) add(b4r_embed_proj_bwd_scratch_floats_impl((int)N, (int)E, (int)H));   // the projection's slabs
   // the fused head's forward partials live at the start of the scratch region; a train step's backward merges them itself (its dE
   // launch), so they stay reserved in front of the backward's own regions
-  if (M > 0 && b4r_head32_hidden_ok((int)H)) add(b4r_head32_fwd_scratch_floats((int)M, (int)V, (int)H));
+  if (M > 0 && b4r_head32_hidden_ok((int)E)) add(b4r_head32_fwd_scratch_floats((int)M, (int)V, (int)E));
   w.scratch = take(s); w.scratch_floats = s;
   w.total = off;
   return w;
@@ -334,12 +381,6 @@ int check_batch(const b4r_batch* b, const b4r_model_config* c, bool need_mlm) {
   B4R_CHECK_ARG(!need_mlm || (b->masked_lm_positions && b->P > 0), B4R_E_BADARG, "batch needs masked_lm_positions");
   return B4R_OK;
 }
-
-#define RC(x)                 \
-  do {                        \
-    int rc__ = (x);           \
-    if (rc__ != B4R_OK) return rc__; \
-  } while (0)
 
 int gemm_f32(const b4r_gemm_desc& d, hipStream_t s) { return b4r_gemm_f32(&d, s); }
 int gemm_tn_f32(const b4r_gemm_tn_desc& d, float* scratch, hipStream_t s) { return b4r_gemm_tn_f32(&d, scratch, s); }
@@ -419,6 +460,7 @@ enum class AttnBwd { Block, BlockFolded, SlotQuery, Core };
 enum class FfnForm { Block, CompactRows, Wide, TileProducts };
 struct StepPlan {
   bool emb_fused;         // the embedding stage runs inside the first layer's attention block
+  bool emb_proj;          // factorised: the embedding stage at width E and the E -> H projection, one launch each way (b4r_embed_proj.hip)
   bool head_rows;         // B4R_FLAG_HEAD_ROWS_ONLY honoured by the last layer's fused feed-forward block ...
   bool head_rows_dense;   // ... or by its compact products
   bool fused_head;        // B4R_FLAG_FUSED_HEAD
@@ -433,7 +475,7 @@ struct StepPlan {
   bool rows() const { return head_rows || head_rows_dense; }   // nothing but the head's rows leave the last layer
 };
 
-StepPlan plan_step(const b4r_model_config* c, const b4r_batch* b, uint32_t flags) {
+StepPlan plan_step(const ModelCfg* c, const b4r_batch* b, uint32_t flags) {
   const int H = c->hidden_size, I = c->inner_dim, L = b->L, P = b->P, heads = c->num_heads, last = c->num_layers - 1;
   const bool hro = (flags & B4R_FLAG_HEAD_ROWS_ONLY) != 0, slots = b->masked_lm_positions && b->masked_lm_ids && P > 0;
   // the halves as one launch each (attention: heads of width 32 only, the blocks stage [rows][32] head slices; its backward L <= 208)
@@ -442,7 +484,8 @@ StepPlan plan_step(const b4r_model_config* c, const b4r_batch* b, uint32_t flags
   const bool attn_bwd_fused = attn_fused && b4r_attn_block_bwd_supported(H, heads, L) != 0;
   const bool attn32 = b4r_attn32_active(H, heads, L);   // the 32-token-tile block backward: it can form the weight gradients itself
   StepPlan p{};
-  p.emb_fused = attn_fused && c->num_layers > 0;
+  p.emb_proj = c->factorised();
+  p.emb_fused = attn_fused && c->num_layers > 0 && !p.emb_proj;
   p.head_rows = hro && ffn_fused && slots;
   // where the last feed-forward half runs as dense products (every hidden size but 64): on compact [B*P, .] operands.  Worth it when
   // the head reads a minority of the rows (P = L / 5 at the benchmark shapes).  Those operands live inside the last layer's own dense
@@ -487,20 +530,20 @@ CompactRows compact_rows(const WsLayout& w, int layer, int64_t M, int64_t H, int
 
 // What every form of a layer half reads: the step's shapes, buffers, plan, dropout and stream, and the backward's scratch allocator.
 struct Step {
-  const b4r_model_config& cfg; const b4r_batch& batch; const StepPlan& plan; const int32_t flags;
+  const ModelCfg& cfg; const b4r_batch& batch; const StepPlan& plan; const int32_t flags;
   const ParamLayout pl; const WsLayout w;
   const float* const params; float* const grads; float* const ws; b4r_train_state* const state;
-  const int B, L, P, H, I, V, N, M, last;
+  const int B, L, P, H, I, V, N, M, last, E;
   const uint32_t* const rng;   // the dropout stream (training only)
   const float od, adp, qscale;
   const hipStream_t s;
   int64_t scratch_used = 0;
 
-  Step(const b4r_model_config* c, const b4r_batch* b, const StepPlan& p, const float* prm, float* g, void* workspace,
+  Step(const ModelCfg* c, const b4r_batch* b, const StepPlan& p, const float* prm, float* g, void* workspace,
        b4r_train_state* st, int32_t f, hipStream_t stream)
       : cfg(*c), batch(*b), plan(p), flags(f), pl(make_param_layout(*c)), w(make_ws_layout(*c, b->B, b->L, b->P)), params(prm),
         grads(g), ws(static_cast<float*>(workspace)), state(st), B(b->B), L(b->L), P(b->masked_lm_positions ? b->P : 0),
-        H(c->hidden_size), I(c->inner_dim), V(c->vocab_size), N(B * L), M(B * P), last(c->num_layers - 1),
+        H(c->hidden_size), I(c->inner_dim), V(c->vocab_size), N(B * L), M(B * P), last(c->num_layers - 1), E(c->E),
         rng((f & B4R_FLAG_TRAINING) ? reinterpret_cast<const uint32_t*>(st) : nullptr),
         od((f & B4R_FLAG_TRAINING) ? c->output_dropout : 0.f), adp((f & B4R_FLAG_TRAINING) ? c->attention_dropout : 0.f),
         qscale(1.0f / sqrtf((float)head_dim(c))), s(stream) {}
@@ -574,22 +617,31 @@ extern "C" int b4r_encoder_layer_bwd(const b4r_ffn_desc* ffn, const b4r_attn_blo
 }
 
 // ===============================================================================================================
-extern "C" int64_t b4r_param_total_floats(const b4r_model_config* cfg) {
-  if (check_cfg(cfg)) return -1;
-  return make_param_layout(*cfg).total;
+// Every config-taking entry point has an _ex twin (include/b4r.h, b4r_model_config_ex); the classic one is a wrapper with
+// embedding_width = 0, so both reach one code path.
+extern "C" int64_t b4r_param_total_floats_ex(const b4r_model_config_ex* cfg) {
+  ModelCfg c;
+  if (resolve_cfg(cfg, &c)) return -1;
+  return make_param_layout(c).total;
 }
-extern "C" int64_t b4r_param_decay_floats(const b4r_model_config* cfg) {
-  if (check_cfg(cfg)) return -1;
-  return make_param_layout(*cfg).n_decay;
+extern "C" int64_t b4r_param_total_floats(const b4r_model_config* cfg) { const auto x = classic_ex(cfg); return b4r_param_total_floats_ex(cfg ? &x : nullptr); }
+extern "C" int64_t b4r_param_decay_floats_ex(const b4r_model_config_ex* cfg) {
+  ModelCfg c;
+  if (resolve_cfg(cfg, &c)) return -1;
+  return make_param_layout(c).n_decay;
 }
-extern "C" int32_t b4r_param_count(const b4r_model_config* cfg) {
-  if (check_cfg(cfg)) return -1;
-  return (int32_t)make_param_layout(*cfg).entries.size();
+extern "C" int64_t b4r_param_decay_floats(const b4r_model_config* cfg) { const auto x = classic_ex(cfg); return b4r_param_decay_floats_ex(cfg ? &x : nullptr); }
+extern "C" int32_t b4r_param_count_ex(const b4r_model_config_ex* cfg) {
+  ModelCfg c;
+  if (resolve_cfg(cfg, &c)) return -1;
+  return (int32_t)make_param_layout(c).entries.size();
 }
-extern "C" int b4r_param_info(const b4r_model_config* cfg, int32_t index, char* name, size_t name_cap, int64_t* offset,
-                              int32_t* rows, int32_t* cols, int32_t* ld, int32_t* decay) {
-  RC(check_cfg(cfg));
-  const ParamLayout p = make_param_layout(*cfg);
+extern "C" int32_t b4r_param_count(const b4r_model_config* cfg) { const auto x = classic_ex(cfg); return b4r_param_count_ex(cfg ? &x : nullptr); }
+extern "C" int b4r_param_info_ex(const b4r_model_config_ex* cfg, int32_t index, char* name, size_t name_cap, int64_t* offset,
+                                 int32_t* rows, int32_t* cols, int32_t* ld, int32_t* decay) {
+  ModelCfg c;
+  RC(resolve_cfg(cfg, &c));
+  const ParamLayout p = make_param_layout(c);
   B4R_CHECK_ARG(index >= 0 && index < (int)p.entries.size(), B4R_E_BADARG, "b4r_param_info: index %d out of range", index);
   const ParamEntry& e = p.entries[index];
   if (name && name_cap) snprintf(name, name_cap, "%s", e.name.c_str());
@@ -600,31 +652,47 @@ extern "C" int b4r_param_info(const b4r_model_config* cfg, int32_t index, char* 
   if (decay) *decay = e.decay;
   return B4R_OK;
 }
+extern "C" int b4r_param_info(const b4r_model_config* cfg, int32_t index, char* name, size_t name_cap, int64_t* offset,
+                              int32_t* rows, int32_t* cols, int32_t* ld, int32_t* decay) {
+  const auto x = classic_ex(cfg);
+  return b4r_param_info_ex(cfg ? &x : nullptr, index, name, name_cap, offset, rows, cols, ld, decay);
+}
 extern "C" int64_t b4r_pooler_floats(const b4r_model_config* cfg) {
   if (check_cfg(cfg)) return -1;
   return (int64_t)cfg->hidden_size * cfg->hidden_size + cfg->hidden_size;
 }
+extern "C" int64_t b4r_workspace_bytes_ex(const b4r_model_config_ex* cfg, int32_t B, int32_t L, int32_t P) {
+  ModelCfg c;
+  if (resolve_cfg(cfg, &c) || B <= 0 || L <= 0 || P < 0) return -1;
+  return make_ws_layout(c, B, L, P).total * (int64_t)sizeof(float);
+}
 extern "C" int64_t b4r_workspace_bytes(const b4r_model_config* cfg, int32_t B, int32_t L, int32_t P) {
-  if (check_cfg(cfg) || B <= 0 || L <= 0 || P < 0) return -1;
-  return make_ws_layout(*cfg, B, L, P).total * (int64_t)sizeof(float);
+  const auto x = classic_ex(cfg);
+  return b4r_workspace_bytes_ex(cfg ? &x : nullptr, B, L, P);
+}
+extern "C" int64_t b4r_workspace_bytes_encoder_ex(const b4r_model_config_ex* cfg, int32_t B, int32_t L, int32_t P) {
+  ModelCfg c;
+  if (resolve_cfg(cfg, &c) != B4R_OK || B <= 0 || L <= 0 || P < 0) return -1;
+  return make_ws_layout(c, B, L, P).gath * (int64_t)sizeof(float);
 }
 extern "C" int64_t b4r_workspace_bytes_encoder(const b4r_model_config* cfg, int32_t B, int32_t L, int32_t P) {
-  if (check_cfg(cfg) != B4R_OK || B <= 0 || L <= 0 || P < 0) return -1;
-  return make_ws_layout(*cfg, B, L, P).gath * (int64_t)sizeof(float);
+  const auto x = classic_ex(cfg);
+  return b4r_workspace_bytes_encoder_ex(cfg ? &x : nullptr, B, L, P);
 }
 
-extern "C" int b4r_workspace_region(const b4r_model_config* cfg, int32_t B, int32_t L, int32_t P, const char* name,
-                                    int64_t* offset_floats, int32_t* rows, int32_t* cols, int32_t* ld) {
-  RC(check_cfg(cfg));
+extern "C" int b4r_workspace_region_ex(const b4r_model_config_ex* cfg, int32_t B, int32_t L, int32_t P, const char* name,
+                                       int64_t* offset_floats, int32_t* rows, int32_t* cols, int32_t* ld) {
+  ModelCfg mc;
+  RC(resolve_cfg(cfg, &mc));
   B4R_CHECK_ARG(name && B > 0 && L > 0 && P >= 0, B4R_E_BADARG, "b4r_workspace_region: bad argument");
-  const WsLayout w = make_ws_layout(*cfg, B, L, P);
-  const int H = cfg->hidden_size, nl = cfg->num_layers;
+  const WsLayout w = make_ws_layout(mc, B, L, P);
+  const int H = mc.hidden_size, nl = mc.num_layers;
   int64_t off = -1; int r = 0, c = 0, l = 0;
   const std::string n(name);
   if (n == "sequence_output") { off = w.x2[nl - 1]; r = (int)w.N; c = H; l = H; }
   else if (n == "embeddings") { off = w.x0; r = (int)w.N; c = H; l = H; }
-  else if (n == "mlm_logits") { off = w.logits; r = (int)w.M; c = cfg->vocab_size; l = (int)w.Vp; }
-  else if (n == "mlm_hidden") { off = w.t; r = (int)w.M; c = H; l = H; }
+  else if (n == "mlm_logits") { off = w.logits; r = (int)w.M; c = mc.vocab_size; l = (int)w.Vp; }
+  else if (n == "mlm_hidden") { off = w.t; r = (int)w.M; c = mc.E; l = mc.E; }
   else if (n == "pooled_output") { off = w.pooled; r = B; c = H; l = H; }
   else if (n == "grad_sequence_output") { off = w.dx; r = (int)w.N; c = H; l = H; }
   else if (n.rfind("encoder_output_", 0) == 0) {
@@ -643,37 +711,64 @@ extern "C" int b4r_workspace_region(const b4r_model_config* cfg, int32_t B, int3
   if (ld) *ld = l;
   return B4R_OK;
 }
+extern "C" int b4r_workspace_region(const b4r_model_config* cfg, int32_t B, int32_t L, int32_t P, const char* name,
+                                    int64_t* offset_floats, int32_t* rows, int32_t* cols, int32_t* ld) {
+  const auto x = classic_ex(cfg);
+  return b4r_workspace_region_ex(cfg ? &x : nullptr, B, L, P, name, offset_floats, rows, cols, ld);
+}
 
 // ===============================================================================================================
+// the logits-free head sweeps the item table: it answers on the table's width
+static bool fused_head_ok(const ModelCfg& c) { return b4r_head32_hidden_ok(c.E) && b4r_get_gemm_mode() == B4R_GEMM_BF16X3; }
+extern "C" int32_t b4r_fused_head_supported_ex(const b4r_model_config_ex* cfg) {
+  ModelCfg c;
+  if (cfg == nullptr || resolve_cfg(cfg, &c) != B4R_OK) return 0;
+  return fused_head_ok(c) ? 1 : 0;
+}
 extern "C" int32_t b4r_fused_head_supported(const b4r_model_config* cfg) {
-  return (cfg != nullptr && b4r_head32_hidden_ok(cfg->hidden_size) && b4r_get_gemm_mode() == B4R_GEMM_BF16X3) ? 1 : 0;
+  const auto x = classic_ex(cfg);
+  return b4r_fused_head_supported_ex(cfg ? &x : nullptr);
 }
 
 // The public entry points take the documented flags only: the internal bits (B4R_FLAG_*_INTERNAL) couple a forward and a backward
 // of ONE b4r_train_step call and are set there alone.  Each plans its own call; a train step plans once for both.
-static int forward_impl(const b4r_model_config* cfg, const b4r_batch* batch, const StepPlan& plan, const float* params,
+static int forward_impl(const ModelCfg* cfg, const b4r_batch* batch, const StepPlan& plan, const float* params,
                         const float* pooler, void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags,
                         b4r_stream_t stream);
-static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, const StepPlan& plan, const float* params, float* grads,
+static int backward_impl(const ModelCfg* cfg, const b4r_batch* batch, const StepPlan& plan, const float* params, float* grads,
                          void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags, b4r_stream_t stream,
                          int* norm_np);
 constexpr int32_t B4R_PUBLIC_FLAGS = 0xFFFF;
-extern "C" int b4r_forward(const b4r_model_config* cfg, const b4r_batch* batch, const float* params, const float* pooler,
-                           void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags,
-                           b4r_stream_t stream) {
-  RC(check_cfg(cfg));
+extern "C" int b4r_forward_ex(const b4r_model_config_ex* cfg_ex, const b4r_batch* batch, const float* params, const float* pooler,
+                              void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags, b4r_stream_t stream) {
+  ModelCfg mc;
+  RC(resolve_cfg(cfg_ex, &mc));
+  const ModelCfg* cfg = &mc;
   RC(check_batch(batch, cfg, false));
   flags &= B4R_PUBLIC_FLAGS;
   return forward_impl(cfg, batch, plan_step(cfg, batch, flags), params, pooler, workspace, workspace_bytes, state, flags, stream);
 }
-extern "C" int b4r_backward(const b4r_model_config* cfg, const b4r_batch* batch, const float* params, float* grads,
-                            void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags,
-                            b4r_stream_t stream) {
-  RC(check_cfg(cfg));
+extern "C" int b4r_forward(const b4r_model_config* cfg, const b4r_batch* batch, const float* params, const float* pooler,
+                           void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags,
+                           b4r_stream_t stream) {
+  const auto x = classic_ex(cfg);
+  return b4r_forward_ex(cfg ? &x : nullptr, batch, params, pooler, workspace, workspace_bytes, state, flags, stream);
+}
+extern "C" int b4r_backward_ex(const b4r_model_config_ex* cfg_ex, const b4r_batch* batch, const float* params, float* grads,
+                               void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags, b4r_stream_t stream) {
+  ModelCfg mc;
+  RC(resolve_cfg(cfg_ex, &mc));
+  const ModelCfg* cfg = &mc;
   RC(check_batch(batch, cfg, true));
   flags &= B4R_PUBLIC_FLAGS;   // (no backward follows an encoder-only forward: that flag picks forward forms only)
   return backward_impl(cfg, batch, plan_step(cfg, batch, flags & ~B4R_FLAG_ENCODER_ONLY), params, grads, workspace, workspace_bytes,
                        state, flags, stream, nullptr);
+}
+extern "C" int b4r_backward(const b4r_model_config* cfg, const b4r_batch* batch, const float* params, float* grads,
+                            void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags,
+                            b4r_stream_t stream) {
+  const auto x = classic_ex(cfg);
+  return b4r_backward_ex(cfg ? &x : nullptr, batch, params, grads, workspace, workspace_bytes, state, flags, stream);
 }
 
 // ===============================================================================================================
@@ -800,24 +895,24 @@ int ffn_fwd_tiles(const Step& c, int i) {
 // d loss_sum / d T straight from T, E and the bias)
 int head_fwd(const Step& c, const float* x) {
   const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
-  RC(transform_fwd({.A = x, .lda = c.H, .B = c.prm(pl.wd), .ldb = c.H, .C = c.at(w.u), .ldc = c.H, .M = c.M, .N = c.H, .K = c.H,
-                    .epilogue = B4R_EPI_BIAS_GELU_LN, .bias = c.prm(pl.bd), .C2 = c.at(w.t), .ldc2 = c.H, .qscale = 1.f,
+  RC(transform_fwd({.A = x, .lda = c.H, .B = c.prm(pl.wd), .ldb = c.E, .C = c.at(w.u), .ldc = c.E, .M = c.M, .N = c.E, .K = c.H,
+                    .epilogue = B4R_EPI_BIAS_GELU_LN, .bias = c.prm(pl.bd), .C2 = c.at(w.t), .ldc2 = c.E, .qscale = 1.f,
                     .c_pad_scratch = 1, .ln_gamma = c.prm(pl.lnm_g), .ln_beta = c.prm(pl.lnm_b), .ln_mean = c.at(w.meanm),
-                    .ln_rstd = c.at(w.rstdm), .ln_eps = c.cfg.ln_eps, .C3 = c.at(w.upre), .ldc3 = c.H,
+                    .ln_rstd = c.at(w.rstdm), .ln_eps = c.cfg.ln_eps, .C3 = c.at(w.upre), .ldc3 = c.E,
                     .a_gather_idx = c.batch.masked_lm_positions, .a_gather_add_per = c.L, .a_gather_per = c.P,
                     .a_copy = c.at(w.gath) /* the transform's weight-gradient operand */, .a_copy_ld = c.H}, c.at(w.gath), c.s));
   if (c.plan.fused_head)
-    return b4r_head32_fwd_launch(c.at(w.t), c.prm(pl.word_emb), c.prm(pl.out_bias), c.batch.masked_lm_ids, c.M, c.V, c.H,
+    return b4r_head32_fwd_launch(c.at(w.t), c.prm(pl.word_emb), c.prm(pl.out_bias), c.batch.masked_lm_ids, c.M, c.V, c.E,
                                  c.at(w.scratch), c.at(w.dt), c.at(w.rowsc), c.at(w.head_lse), reinterpret_cast<int32_t*>(c.at(w.head_ylab)),
                                  c.plan.defer_combine ? 1 : 0, c.s);
-  return gemm_f32({.A = c.at(w.t), .lda = c.H, .B = c.prm(pl.word_emb), .ldb = c.H, .C = c.at(w.logits), .ldc = (int)w.Vp, .M = c.M,
-                   .N = c.V, .K = c.H, .b_is_nk = 1, .epilogue = B4R_EPI_BIAS, .bias = c.prm(pl.out_bias), .qscale = 1.f,
+  return gemm_f32({.A = c.at(w.t), .lda = c.E, .B = c.prm(pl.word_emb), .ldb = c.E, .C = c.at(w.logits), .ldc = (int)w.Vp, .M = c.M,
+                   .N = c.V, .K = c.E, .b_is_nk = 1, .epilogue = B4R_EPI_BIAS, .bias = c.prm(pl.out_bias), .qscale = 1.f,
                    .c_pad_scratch = 1}, c.s);
 }
 
 }  // namespace
 
-static int forward_impl(const b4r_model_config* cfg, const b4r_batch* batch, const StepPlan& plan, const float* params,
+static int forward_impl(const ModelCfg* cfg, const b4r_batch* batch, const StepPlan& plan, const float* params,
                         const float* pooler, void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags,
                         b4r_stream_t stream) {
   B4R_CHECK_ARG(params && workspace, B4R_E_BADARG, "b4r_forward: null params/workspace");
@@ -831,13 +926,18 @@ static int forward_impl(const b4r_model_config* cfg, const b4r_batch* batch, con
   B4R_CHECK_ARG(!(flags & B4R_FLAG_TRAINING) || state || (cfg->output_dropout == 0.f && cfg->attention_dropout == 0.f), B4R_E_BADARG,
                 "b4r_forward: training with dropout needs a state (rng)");
   const bool head = c.P > 0 && !(flags & B4R_FLAG_ENCODER_ONLY);
-  B4R_CHECK_ARG(!head || !plan.fused_head || b4r_fused_head_supported(cfg), B4R_E_BADARG,
-                "b4r_forward: B4R_FLAG_FUSED_HEAD needs hidden size 64 / 128 / 256 and the bf16x3 mode");
+  B4R_CHECK_ARG(!head || !plan.fused_head || fused_head_ok(*cfg), B4R_E_BADARG,
+                "b4r_forward: B4R_FLAG_FUSED_HEAD needs an item-table width (hidden size or embedding_width) of 64 / 128 / 256 and the "
+                "bf16x3 mode");
   B4R_CHECK_ARG(!head || !plan.fused_head || batch->masked_lm_ids != nullptr, B4R_E_BADARG,
                 "b4r_forward: B4R_FLAG_FUSED_HEAD needs masked_lm_ids");
 
   // the embedding stage: inside the first layer's attention block where that runs fused, else a launch of its own
-  if (!plan.emb_fused)
+  if (plan.emb_proj)
+    RC(b4r_embed_proj_fwd_launch(batch->input_word_ids, c.B, c.L, c.prm(c.pl.word_emb), c.V, c.prm(c.pl.pos_emb), c.prm(c.pl.emb_ln_g),
+                                 c.prm(c.pl.emb_ln_b), c.E, cfg->ln_eps, c.prm(c.pl.proj_w), c.prm(c.pl.proj_b), c.H, c.at(c.w.x0),
+                                 c.at(c.w.mean0), c.at(c.w.rstd0), b4r_make_drop(c.rng, B4R_STREAM_EMB, c.od, 1), c.s));
+  else if (!plan.emb_fused)
     RC(b4r_embed_ln_fwd(batch->input_word_ids, c.B, c.L, c.prm(c.pl.word_emb), c.V, c.prm(c.pl.pos_emb), c.prm(c.pl.emb_ln_g),
                         c.prm(c.pl.emb_ln_b), c.H, cfg->ln_eps, c.at(c.w.x0), c.at(c.w.mean0), c.at(c.w.rstd0), c.rng, c.od, c.s));
   const float* x = c.at(c.w.x0);
@@ -861,27 +961,36 @@ static int forward_impl(const b4r_model_config* cfg, const b4r_batch* batch, con
   return head ? head_fwd(c, x) : B4R_OK;
 }
 
-extern "C" int b4r_mlm_transform_rows(const b4r_model_config* cfg, const float* params, const float* seq, int64_t n_seq_rows,
-                                      const int64_t* rows, int32_t R, float* out, float* scratch, b4r_stream_t stream) {
-  RC(check_cfg(cfg));
+extern "C" int b4r_mlm_transform_rows_ex(const b4r_model_config_ex* cfg_ex, const float* params, const float* seq, int64_t n_seq_rows,
+                                         const int64_t* rows, int32_t R, float* out, float* scratch, b4r_stream_t stream) {
+  ModelCfg mc;
+  RC(resolve_cfg(cfg_ex, &mc));
+  const ModelCfg* cfg = &mc;
   B4R_CHECK_ARG(params && seq && rows && out && scratch && R > 0 && n_seq_rows > 0, B4R_E_BADARG, "b4r_mlm_transform_rows: bad argument");
   B4R_CHECK_ARG(b4r_aligned16(params) && b4r_aligned16(seq) && b4r_aligned16(out) && b4r_aligned16(scratch), B4R_E_ALIGN,
                 "b4r_mlm_transform_rows: buffers must be 16-byte aligned");
   const ParamLayout pl = make_param_layout(*cfg);
-  const int H = cfg->hidden_size;
+  const int H = cfg->hidden_size, E = cfg->E;
   float* gath = scratch; float* upre = gath + up4((int64_t)R * H); float* u = upre + up4((int64_t)R * H);
   float* mean = u + up4((int64_t)R * H); float* rstd = mean + up4(R);
-  return transform_fwd({.A = seq, .lda = H, .B = params + pl.wd, .ldb = H, .C = u, .ldc = H, .M = R, .N = H, .K = H,
-                        .epilogue = B4R_EPI_BIAS_GELU_LN, .bias = params + pl.bd, .C2 = out, .ldc2 = H, .qscale = 1.f,
+  return transform_fwd({.A = seq, .lda = H, .B = params + pl.wd, .ldb = E, .C = u, .ldc = E, .M = R, .N = E, .K = H,
+                        .epilogue = B4R_EPI_BIAS_GELU_LN, .bias = params + pl.bd, .C2 = out, .ldc2 = E, .qscale = 1.f,
                         .c_pad_scratch = 0, .ln_gamma = params + pl.lnm_g, .ln_beta = params + pl.lnm_b, .ln_mean = mean,
-                        .ln_rstd = rstd, .ln_eps = cfg->ln_eps, .C3 = upre, .ldc3 = H,
+                        .ln_rstd = rstd, .ln_eps = cfg->ln_eps, .C3 = upre, .ldc3 = E,
                         .a_gather_idx = rows, .a_gather_add_per = n_seq_rows, .a_gather_per = R /* one group: row m reads seq[rows[m]] */},
                        gath, stream);
 }
+extern "C" int b4r_mlm_transform_rows(const b4r_model_config* cfg, const float* params, const float* seq, int64_t n_seq_rows,
+                                      const int64_t* rows, int32_t R, float* out, float* scratch, b4r_stream_t stream) {
+  const auto x = classic_ex(cfg);
+  return b4r_mlm_transform_rows_ex(cfg ? &x : nullptr, params, seq, n_seq_rows, rows, R, out, scratch, stream);
+}
 
-extern "C" int b4r_loss(const b4r_model_config* cfg, const b4r_batch* batch, void* workspace, int64_t workspace_bytes,
-                        b4r_train_state* state, int32_t want_grad, b4r_stream_t stream) {
-  RC(check_cfg(cfg));
+extern "C" int b4r_loss_ex(const b4r_model_config_ex* cfg_ex, const b4r_batch* batch, void* workspace, int64_t workspace_bytes,
+                           b4r_train_state* state, int32_t want_grad, b4r_stream_t stream) {
+  ModelCfg mc;
+  RC(resolve_cfg(cfg_ex, &mc));
+  const ModelCfg* cfg = &mc;
   RC(check_batch(batch, cfg, true));
   B4R_CHECK_ARG(batch->masked_lm_ids && workspace && state, B4R_E_BADARG, "b4r_loss: needs masked_lm_ids, workspace, state");
   const WsLayout w = make_ws_layout(*cfg, batch->B, batch->L, batch->P);
@@ -891,6 +1000,12 @@ extern "C" int b4r_loss(const b4r_model_config* cfg, const b4r_batch* batch, voi
     return b4r_ce_finalize_launch(ws + w.rowsc, (int)w.M, state, (want_grad & B4R_LOSS_OVERWRITE) ? 1 : 0, (hipStream_t)stream);
   return b4r_softmax_ce(ws + w.logits, (int)w.M, cfg->vocab_size, (int)w.Vp, batch->masked_lm_ids, ws + w.rowsc, state,
                         want_grad & (1 | B4R_LOSS_OVERWRITE), stream);
+}
+
+extern "C" int b4r_loss(const b4r_model_config* cfg, const b4r_batch* batch, void* workspace, int64_t workspace_bytes,
+                        b4r_train_state* state, int32_t want_grad, b4r_stream_t stream) {
+  const auto x = classic_ex(cfg);
+  return b4r_loss_ex(cfg ? &x : nullptr, batch, workspace, workspace_bytes, state, want_grad, stream);
 }
 
 // ===============================================================================================================
@@ -903,18 +1018,18 @@ namespace {
 int head_bwd(Step& c) {
   const StepPlan& p = c.plan;
   const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
-  const int H = c.H, M = c.M, V = c.V, Vp = (int)w.Vp;
+  const int H = c.H, E = c.E, M = c.M, V = c.V, Vp = (int)w.Vp;   // (the head's rows and the item table are E wide)
   const bool loss_sums = (c.flags & B4R_FLAG_LOSS_SUMS) != 0;
   // the scratch regions of the fused head are fixed here already: the records dE sweeps (the transform rows as fp16 images, -lse,
   // labels) are formed by extra workgroups of the clearing launch (b4r_zero2's rider) instead of a launch of their own.  With the
   // deferred merge the forward's partials stay where it left them, at the start of the scratch.
   float *fwd_part = nullptr, *dE_scratch = nullptr;
-  if (p.fused_head && p.defer_combine) RC(c.take(b4r_head32_fwd_scratch_floats(M, V, H), &fwd_part));
-  if (p.fused_head) RC(c.take(b4r_head32_dE_scratch_floats(M, V, H), &dE_scratch));
+  if (p.fused_head && p.defer_combine) RC(c.take(b4r_head32_fwd_scratch_floats(M, V, E), &fwd_part));
+  if (p.fused_head) RC(c.take(b4r_head32_dE_scratch_floats(M, V, E), &dE_scratch));
   alignas(8) char rider[128];
   int rider_blocks = 0;
   if (p.fused_head)
-    RC(b4r_head32_dE_pack_job(c.at(w.t), c.at(w.head_lse), reinterpret_cast<const int32_t*>(c.at(w.head_ylab)), M, V, H, dE_scratch,
+    RC(b4r_head32_dE_pack_job(c.at(w.t), c.at(w.head_lse), reinterpret_cast<const int32_t*>(c.at(w.head_ylab)), M, V, E, dE_scratch,
                               fwd_part, c.batch.masked_lm_ids, rider, sizeof(rider), &rider_blocks));
   // row-list mode with the slots' dz1 only in the last layer's attention backward (it never reads the other rows): db is not cleared
   RC(b4r_zero2(c.grads, pl.total, c.at(p.rows() ? w.hot : w.dx),
@@ -928,42 +1043,42 @@ int head_bwd(Step& c) {
     // dT came with the forward -- or (defer_combine) the forward left its per-slice partials: dE forms the lse it needs from them, the
     // transform's LayerNorm backward below merges them into dT as it reads it; dE / d output_bias recompute the logit tiles (b4r_head32.hip)
     RC(b4r_head32_dE_launch(c.at(w.t), c.prm(pl.word_emb), c.prm(pl.out_bias), c.at(w.head_lse),
-                            reinterpret_cast<const int32_t*>(c.at(w.head_ylab)), M, V, H, dE_scratch, c.grd(pl.word_emb),
+                            reinterpret_cast<const int32_t*>(c.at(w.head_ylab)), M, V, E, dE_scratch, c.grd(pl.word_emb),
                             c.grd(pl.out_bias), c.s, fwd_part, c.batch.masked_lm_ids, rider_blocks > 0 ? 1 : 0));
   } else {
     // dT = dlogits . E   (K = V is long and the output small: split K so that the whole chip streams dlogits).  The loss kernel zeroed
     // columns [V, Vp) of dlogits, and the table is followed by the position table in the flat parameter buffer, so the reduction may
     // run over whole chunks of 64 (rows V..Vp-1 of "E" meet zeros)
-    const b4r_gemm_desc d{.A = dlog, .lda = Vp, .B = c.prm(pl.word_emb), .ldb = H, .C = c.at(w.dt), .ldc = H, .M = M, .N = H, .K = V,
+    const b4r_gemm_desc d{.A = dlog, .lda = Vp, .B = c.prm(pl.word_emb), .ldb = E, .C = c.at(w.dt), .ldc = E, .M = M, .N = E, .K = V,
                           .b_is_nk = 0, .epilogue = B4R_EPI_NONE};
-    const int splits = mlm_dt_splits(M, H, V);
-    RC(c.take((int64_t)splits * M * H, &sc));
-    RC(b4r_gemm_f32_splitk(&d, splits, sc, (pl.word_emb + (int64_t)Vp * H <= pl.total) ? 1 : 0, c.s));
+    const int splits = mlm_dt_splits(M, E, V);
+    RC(c.take((int64_t)splits * M * E, &sc));
+    RC(b4r_gemm_f32_splitk(&d, splits, sc, (pl.word_emb + (int64_t)Vp * E <= pl.total) ? 1 : 0, c.s));
     // dE = dlogits^T . T ; d output_bias = column sums of dlogits
-    RC(c.take(b4r_gemm_tn_scratch_floats(M, V, H), &sc));
-    RC(gemm_tn_f32({.A = dlog, .lda = Vp, .B = c.at(w.t), .ldb = H, .out = c.grd(pl.word_emb), .ldo = H, .R = M, .Mo = V, .No = H,
+    RC(c.take(b4r_gemm_tn_scratch_floats(M, V, E), &sc));
+    RC(gemm_tn_f32({.A = dlog, .lda = Vp, .B = c.at(w.t), .ldb = E, .out = c.grd(pl.word_emb), .ldo = E, .R = M, .Mo = V, .No = E,
                     .colsum_a = c.grd(pl.out_bias)}, sc, c.s));
   }
   // LayerNorm of the transform (with the deferred merge: dT, the loss rows, lse and labels are formed here, from the forward's partials)
   // ... and straight through the GELU of the transform's dense layer
-  const B4rHeadMerge merge{fwd_part, fwd_part ? b4r_head32_fwd_slices(M, V, H) : 0, M, V, c.at(w.t), c.prm(pl.word_emb),
+  const B4rHeadMerge merge{fwd_part, fwd_part ? b4r_head32_fwd_slices(M, V, E) : 0, M, V, c.at(w.t), c.prm(pl.word_emb),
                            c.prm(pl.out_bias), c.batch.masked_lm_ids, c.at(w.rowsc), c.at(w.head_lse),
                            reinterpret_cast<int32_t*>(c.at(w.head_ylab))};
-  RC(c.take(b4r_ln_bwd_scratch_floats(M, H), &sc));
-  RC(b4r_ln_bwd_launch(c.at(w.dt), c.at(w.u), c.at(w.meanm), c.at(w.rstdm), c.prm(pl.lnm_g), M, H, c.at(w.dt), c.grd(pl.lnm_g),
+  RC(c.take(b4r_ln_bwd_scratch_floats(M, E), &sc));
+  RC(b4r_ln_bwd_launch(c.at(w.dt), c.at(w.u), c.at(w.meanm), c.at(w.rstdm), c.prm(pl.lnm_g), M, E, c.at(w.dt), c.grd(pl.lnm_g),
                        c.grd(pl.lnm_b), sc, nullptr, nullptr, nullptr, 1, 1, b4r_make_drop(nullptr, 0, 0.f, 0), c.s, c.at(w.upre),
                        fwd_part ? &merge : nullptr));
   // dense layer of the transform: dWd = gath^T . du (+ bias gradient) and dgath = du . Wd^T, one pass over du where the pair kernel
   // applies (hidden size 64), else the two products
-  b4r_gemm_tn_desc d{.A = c.at(w.gath), .lda = H, .B = c.at(w.dt), .ldb = H, .out = c.grd(pl.wd), .ldo = H, .R = M, .Mo = H, .No = H,
-                     .colsum = c.grd(pl.bd), .dgrad_w = c.prm(pl.wd), .dgrad_ldw = H, .dgrad_out = c.at(w.dg), .dgrad_ldo = H};
-  RC(c.take(b4r_gemm_tn_scratch_floats(M, H, H), &sc));
+  b4r_gemm_tn_desc d{.A = c.at(w.gath), .lda = H, .B = c.at(w.dt), .ldb = E, .out = c.grd(pl.wd), .ldo = E, .R = M, .Mo = H, .No = E,
+                     .colsum = c.grd(pl.bd), .dgrad_w = c.prm(pl.wd), .dgrad_ldw = E, .dgrad_out = c.at(w.dg), .dgrad_ldo = H};
+  RC(c.take(b4r_gemm_tn_scratch_floats(M, H, E), &sc));
   if (b4r_gemm_tn_dgrad_supported(&d)) {
     RC(gemm_tn_f32(d, sc, c.s));
   } else {
     d.dgrad_w = nullptr; d.dgrad_ldw = 0; d.dgrad_out = nullptr; d.dgrad_ldo = 0;
     RC(gemm_tn_f32(d, sc, c.s));
-    RC(gemm_f32({.A = c.at(w.dt), .lda = H, .B = c.prm(pl.wd), .ldb = H, .C = c.at(w.dg), .ldc = H, .M = M, .N = H, .K = H,
+    RC(gemm_f32({.A = c.at(w.dt), .lda = E, .B = c.prm(pl.wd), .ldb = E, .C = c.at(w.dg), .ldc = H, .M = M, .N = H, .K = E,
                  .b_is_nk = 1, .epilogue = B4R_EPI_NONE, .qscale = 1.f, .c_pad_scratch = 1}, c.s));
   }
   // scatter into d sequence_output (slots with y_true == 0 carry exactly zero gradient and are skipped); in the row-list mode the last
@@ -1159,6 +1274,9 @@ int qkv_bwd(Step& c, int i, const float* x_in) {
   if (i > 0)
     RC(dgrad_ln_bwd(c.at(w.dqkv), 3 * H, c.prm(pl.wqkv[i]), 3 * H, c.at(w.db), c.at(w.da), N, H, c.at(w.z2[i - 1]), c.at(w.mean2[i - 1]),
                     c.at(w.rstd2[i - 1]), c.prm(pl.ln2_g[i - 1]), c.grd(pl.ln2_g[i - 1]), c.grd(pl.ln2_b[i - 1]), sc, c.s));
+  else if (c.plan.emb_proj)   // factorised: plain dx0 = dqkv . Wqkv^T + dz1; embed_proj_bwd takes it from there
+    RC(gemm_f32({.A = c.at(w.dqkv), .lda = 3 * H, .B = c.prm(pl.wqkv[i]), .ldb = 3 * H, .C = c.at(w.da), .ldc = H, .M = N, .N = H,
+                 .K = 3 * H, .b_is_nk = 1, .epilogue = B4R_EPI_ADD_RES, .R = c.at(w.db), .ldr = H, .qscale = 1.f, .c_pad_scratch = 1}, c.s));
   else
     RC(dgrad_ln_bwd(c.at(w.dqkv), 3 * H, c.prm(pl.wqkv[i]), 3 * H, c.at(w.db), c.at(w.da), N, H, nullptr, c.at(w.mean0), c.at(w.rstd0),
                     c.prm(pl.emb_ln_g), c.grd(pl.emb_ln_g), c.grd(pl.emb_ln_b), sc, c.s, c.batch.input_word_ids, c.prm(pl.word_emb),
@@ -1172,7 +1290,7 @@ int qkv_bwd(Step& c, int i, const float* x_in) {
 
 // *norm_np (b4r_train_step, B4R_FLAG_NORM_PARTIALS_INTERNAL): > 0 where the closing reduce launch also left that many partial sums of
 // squares of the gradients at the start of the workspace (dead by then), so that the optimizer needs no norm launch
-static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, const StepPlan& plan, const float* params, float* grads,
+static int backward_impl(const ModelCfg* cfg, const b4r_batch* batch, const StepPlan& plan, const float* params, float* grads,
                          void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags, b4r_stream_t stream,
                          int* norm_np) {
   B4R_CHECK_ARG(params && grads && workspace && batch->masked_lm_ids, B4R_E_BADARG, "b4r_backward: null argument");
@@ -1183,8 +1301,12 @@ static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, co
   B4R_CHECK_ARG(!(flags & B4R_FLAG_GRAD_TAIL) || state, B4R_E_BADARG, "b4r_backward: B4R_FLAG_GRAD_TAIL needs the state");
   B4R_CHECK_ARG(!(flags & B4R_FLAG_LOSS_SUMS) || ((flags & B4R_FLAG_FUSED_HEAD) && state && batch->masked_lm_ids), B4R_E_BADARG,
                 "b4r_backward: B4R_FLAG_LOSS_SUMS needs B4R_FLAG_FUSED_HEAD, the state and masked_lm_ids");
-  B4R_CHECK_ARG(!plan.fused_head || b4r_fused_head_supported(cfg), B4R_E_BADARG,
-                "b4r_backward: B4R_FLAG_FUSED_HEAD needs hidden size 64 / 128 / 256 and the bf16x3 mode");
+  B4R_CHECK_ARG(!plan.fused_head || fused_head_ok(*cfg), B4R_E_BADARG,
+                "b4r_backward: B4R_FLAG_FUSED_HEAD needs an item-table width (hidden size or embedding_width) of 64 / 128 / 256 and the "
+                "bf16x3 mode");
+  // (the attention block forms only run at hidden size 64, where no embedding width below it is supported)
+  B4R_CHECK_ARG(!plan.emb_proj || (plan.attn_bwd[0] != AttnBwd::Block && plan.attn_bwd[0] != AttnBwd::BlockFolded), B4R_E_SHAPE,
+                "b4r_backward: the factorised embedding needs layer 0's attention backward as products");
   const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
   B4rReduceQueue queue;
   b4r_reduce_queue_begin(&queue);   // every ordered reduction below is summed by ONE launch at the end
@@ -1212,21 +1334,31 @@ static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, co
     }
   }
   // ---- embedding stage: its dropout -> LayerNorm backward ran with layer 0's QKV product (da = d(item row + position row));
-  // what remains: word table scatter-add, position table batch sum
+  // what remains: word table scatter-add, position table batch sum.  Factorised: da is dx0 [N, H]; the projection's backward forms
+  // dWp / dbp, the dropout and LayerNorm backward at width E and the rows d(item row + position row) [N, E] (into dctx, free by now)
+  const float* emb_rows = c.at(w.da);
+  if (plan.emb_proj) {
+    float* psc; RC(c.take(b4r_embed_proj_bwd_scratch_floats_impl(c.N, c.E, c.H), &psc));
+    RC(b4r_embed_proj_bwd_launch(c.at(w.da), batch->input_word_ids, c.B, c.L, c.prm(pl.word_emb), c.V, c.prm(pl.pos_emb), c.prm(pl.emb_ln_g),
+                                 c.prm(pl.emb_ln_b), c.E, c.at(w.mean0), c.at(w.rstd0), c.prm(pl.proj_w), c.H,
+                                 b4r_make_drop(c.rng, B4R_STREAM_EMB, c.od, 1), c.at(w.dctx), c.grd(pl.proj_w), c.grd(pl.proj_b),
+                                 c.grd(pl.emb_ln_g), psc, c.s));
+    emb_rows = c.at(w.dctx);
+  }
   // the item-table scatter sums in 64-bit fixed point beside the float gradient (bitwise reproducible; b4r_rowops.hip), so it
   // need not wait for the head's part of that gradient: ONE launch then sums every queued ordered reduction (weight / bias /
   // LayerNorm gradients, the position table) and adds the fixed-point sums to the item table
-  float* sc; RC(c.take((int64_t)b4r_cdiv(c.B, 16) * c.L * c.H, &sc));
-  RC(b4r_embed_grads(c.at(w.da), batch->input_word_ids, c.B, c.L, c.H, c.grd(pl.word_emb), c.V, 3, c.at(w.hot) /* zeroed at the top */,
+  float* sc; RC(c.take((int64_t)b4r_cdiv(c.B, 16) * c.L * c.E, &sc));
+  RC(b4r_embed_grads(emb_rows, batch->input_word_ids, c.B, c.L, c.E, c.grd(pl.word_emb), c.V, 3, c.at(w.hot) /* zeroed at the top */,
                      c.grd(pl.pos_emb), sc, c.s, plan.defer_combine ? c.at(w.rowsc) : nullptr, (int)w.M, state,
                      (plan.defer_combine && (flags & B4R_FLAG_GRAD_TAIL)) ? c.grd(pl.total) : nullptr));
   if (norm_np) *norm_np = 0;
   if (!(flags & B4R_FLAG_NORM_PARTIALS_INTERNAL)) return b4r_reduce_queue_flush(c.s);
   // valid only when the jobs of this launch write EVERY gradient (then each value is squared exactly once, as it is stored)
-  const int64_t H = c.H, I = c.I, V = c.V;
-  const int64_t expected = V * H + (int64_t)c.L * H + 2 * H /* embedding LayerNorm */ +
-                           (int64_t)cfg->num_layers * (H * 3 * H + H * H + 2 * H * I + 3 * H + H + 2 * H + I + H + 2 * H) +
-                           H * H + H + 2 * H /* transform */ + V /* output bias */;
+  // every trainable entry of the layout, rows x cols -- the position table's first L rows only (its other rows carry no gradient)
+  int64_t expected = 0;
+  for (const ParamEntry& e : pl.entries)
+    expected += (int64_t)(e.offset == pl.pos_emb ? c.L : e.rows) * e.cols;
   int np = 0;
   int64_t covered = 0;
   RC(b4r_reduce_queue_flush(c.s, c.ws, 4096, &np, &covered));
@@ -1234,10 +1366,12 @@ static int backward_impl(const b4r_model_config* cfg, const b4r_batch* batch, co
   return B4R_OK;
 }
 
-extern "C" int b4r_optimizer_step(const b4r_model_config* cfg, const b4r_adamw_config* hp, float* params, const float* grads,
-                                  float* adam_m, float* adam_v, void* workspace, int64_t workspace_bytes,
-                                  b4r_train_state* state, b4r_stream_t stream) {
-  RC(check_cfg(cfg));
+extern "C" int b4r_optimizer_step_ex(const b4r_model_config_ex* cfg_ex, const b4r_adamw_config* hp, float* params, const float* grads,
+                                     float* adam_m, float* adam_v, void* workspace, int64_t workspace_bytes,
+                                     b4r_train_state* state, b4r_stream_t stream) {
+  ModelCfg mc;
+  RC(resolve_cfg(cfg_ex, &mc));
+  const ModelCfg* cfg = &mc;
   B4R_CHECK_ARG(hp && params && grads && adam_m && adam_v && workspace && state, B4R_E_BADARG, "b4r_optimizer_step: null argument");
   B4R_CHECK_ARG(workspace_bytes >= 4096 * (int64_t)sizeof(float), B4R_E_NOMEM, "b4r_optimizer_step: workspace too small");
   const ParamLayout pl = make_param_layout(*cfg);
@@ -1247,10 +1381,19 @@ extern "C" int b4r_optimizer_step(const b4r_model_config* cfg, const b4r_adamw_c
   return b4r_optimizer_fused(hp, params, grads, adam_m, adam_v, pl.total, pl.n_decay, scratch, state, (hipStream_t)stream);
 }
 
-extern "C" int b4r_optimizer_step_reduced(const b4r_model_config* cfg, const b4r_adamw_config* hp, float* params, const float* grads,
-                                          float* adam_m, float* adam_v, void* workspace, int64_t workspace_bytes,
-                                          b4r_train_state* state, b4r_stream_t stream) {
-  RC(check_cfg(cfg));
+extern "C" int b4r_optimizer_step(const b4r_model_config* cfg, const b4r_adamw_config* hp, float* params, const float* grads,
+                                  float* adam_m, float* adam_v, void* workspace, int64_t workspace_bytes,
+                                  b4r_train_state* state, b4r_stream_t stream) {
+  const auto x = classic_ex(cfg);
+  return b4r_optimizer_step_ex(cfg ? &x : nullptr, hp, params, grads, adam_m, adam_v, workspace, workspace_bytes, state, stream);
+}
+
+extern "C" int b4r_optimizer_step_reduced_ex(const b4r_model_config_ex* cfg_ex, const b4r_adamw_config* hp, float* params,
+                                             const float* grads, float* adam_m, float* adam_v, void* workspace, int64_t workspace_bytes,
+                                             b4r_train_state* state, b4r_stream_t stream) {
+  ModelCfg mc;
+  RC(resolve_cfg(cfg_ex, &mc));
+  const ModelCfg* cfg = &mc;
   B4R_CHECK_ARG(hp && params && grads && adam_m && adam_v && workspace && state, B4R_E_BADARG, "b4r_optimizer_step_reduced: null argument");
   B4R_CHECK_ARG(workspace_bytes >= 4096 * (int64_t)sizeof(float), B4R_E_NOMEM, "b4r_optimizer_step_reduced: workspace too small");
   const ParamLayout pl = make_param_layout(*cfg);
@@ -1258,13 +1401,22 @@ extern "C" int b4r_optimizer_step_reduced(const b4r_model_config* cfg, const b4r
                              (hipStream_t)stream, 1);
 }
 
-extern "C" int b4r_train_step(const b4r_model_config* cfg, const b4r_adamw_config* hp, const b4r_batch* batch, float* params,
-                              float* grads, float* adam_m, float* adam_v, void* workspace, int64_t workspace_bytes,
-                              b4r_train_state* state, b4r_stream_t stream) {
-  RC(check_cfg(cfg));
+extern "C" int b4r_optimizer_step_reduced(const b4r_model_config* cfg, const b4r_adamw_config* hp, float* params, const float* grads,
+                                          float* adam_m, float* adam_v, void* workspace, int64_t workspace_bytes,
+                                          b4r_train_state* state, b4r_stream_t stream) {
+  const auto x = classic_ex(cfg);
+  return b4r_optimizer_step_reduced_ex(cfg ? &x : nullptr, hp, params, grads, adam_m, adam_v, workspace, workspace_bytes, state, stream);
+}
+
+extern "C" int b4r_train_step_ex(const b4r_model_config_ex* cfg_ex, const b4r_adamw_config* hp, const b4r_batch* batch, float* params,
+                                 float* grads, float* adam_m, float* adam_v, void* workspace, int64_t workspace_bytes,
+                                 b4r_train_state* state, b4r_stream_t stream) {
+  ModelCfg mc;
+  RC(resolve_cfg(cfg_ex, &mc));
+  const ModelCfg* cfg = &mc;
   RC(check_batch(batch, cfg, true));
-  const int fused = b4r_fused_head_supported(cfg) ? 1 : 0;   // the train step never needs the logits themselves
-  const int defer = (fused && b4r_head32_combine_foldable(batch->B * batch->P, cfg->vocab_size, cfg->hidden_size))
+  const int fused = fused_head_ok(*cfg) ? 1 : 0;   // the train step never needs the logits themselves
+  const int defer = (fused && b4r_head32_combine_foldable(batch->B * batch->P, cfg->vocab_size, cfg->E))
                         ? B4R_FLAG_DEFER_COMBINE_INTERNAL : 0;
   // no b4r_state_begin_step launch: the loss reduction overwrites the sums (B4R_LOSS_OVERWRITE)
   // nothing but the loss, the metrics and the gradients leave a train step: the last layer's feed-forward half runs on the rows the
@@ -1274,7 +1426,7 @@ extern "C" int b4r_train_step(const b4r_model_config* cfg, const b4r_adamw_confi
   const int32_t bwd_flags = fwd_flags | (fused ? B4R_FLAG_LOSS_SUMS : 0) | B4R_FLAG_NORM_PARTIALS_INTERNAL;
   const StepPlan plan = plan_step(cfg, batch, bwd_flags);   // (the backward's flags: the forward's and what it alone reads)
   RC(forward_impl(cfg, batch, plan, params, nullptr, workspace, workspace_bytes, state, fwd_flags, stream));
-  if (!fused) RC(b4r_loss(cfg, batch, workspace, workspace_bytes, state, 1 | B4R_LOSS_OVERWRITE, stream));
+  if (!fused) RC(b4r_loss_ex(cfg_ex, batch, workspace, workspace_bytes, state, 1 | B4R_LOSS_OVERWRITE, stream));
   int np = 0;   // > 0: the backward's last launch left the norm's partial sums at the start of the workspace
   RC(backward_impl(cfg, batch, plan, params, grads, workspace, workspace_bytes, state, bwd_flags, stream, &np));
   if (np > 0) {
@@ -1283,5 +1435,11 @@ extern "C" int b4r_train_step(const b4r_model_config* cfg, const b4r_adamw_confi
     return b4r_optimizer_fused(hp, params, grads, adam_m, adam_v, pl.total, pl.n_decay, static_cast<float*>(workspace), state,
                                (hipStream_t)stream, 0, np);
   }
-  return b4r_optimizer_step(cfg, hp, params, grads, adam_m, adam_v, workspace, workspace_bytes, state, stream);
+  return b4r_optimizer_step_ex(cfg_ex, hp, params, grads, adam_m, adam_v, workspace, workspace_bytes, state, stream);
+}
+extern "C" int b4r_train_step(const b4r_model_config* cfg, const b4r_adamw_config* hp, const b4r_batch* batch, float* params,
+                              float* grads, float* adam_m, float* adam_v, void* workspace, int64_t workspace_bytes,
+                              b4r_train_state* state, b4r_stream_t stream) {
+  const auto x = classic_ex(cfg);
+  return b4r_train_step_ex(cfg ? &x : nullptr, hp, batch, params, grads, adam_m, adam_v, workspace, workspace_bytes, state, stream);
 }

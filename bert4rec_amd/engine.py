@@ -14,7 +14,7 @@ from typing import Dict, Iterable, List, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import AdamWConfig, B4RError, Batch, ModelConfig
+from ._lib import AdamWConfig, B4RError, Batch, ModelConfig, ModelConfigEx
 
 BATCH_KEYS = ("input_word_ids", "input_mask", "masked_lm_positions", "masked_lm_ids")
 
@@ -59,18 +59,28 @@ class ParamInfo:
         self.name, self.offset, self.rows, self.cols, self.ld, self.decay = name, offset, rows, cols, ld, decay
 
 
-def param_table(cfg: ModelConfig) -> List[ParamInfo]:
+def config_api(lib, cfg: ModelConfig, embedding_width: Optional[int], name: str):
+    """The entry point `name` and the config argument it takes: the classic function with the 36-byte config for the unfactorised
+    model (embedding_width None / 0 / hidden_size), else its _ex twin with a b4r_model_config_ex.  The one place that chooses."""
+    if not embedding_width or int(embedding_width) == cfg.hidden_size:
+        return getattr(lib, name), C.byref(cfg)
+    return getattr(lib, name + "_ex"), C.pointer(ModelConfigEx(cfg, int(embedding_width), (0, 0, 0)))
+
+
+def param_table(cfg: ModelConfig, embedding_width: Optional[int] = None) -> List[ParamInfo]:
     """Named layout of the flat parameter buffer (names = the reference's Keras variable names)."""
     lib = _lib.load()
-    n = lib.b4r_param_count(C.byref(cfg))
+    fn, ref = config_api(lib, cfg, embedding_width, "b4r_param_count")
+    n = fn(ref)
     if n < 0:
         raise B4RError("invalid model config: " + _lib.last_error())
     out = []
     name = C.create_string_buffer(256)
     off, rows, cols, ld, dec = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+    info, ref = config_api(lib, cfg, embedding_width, "b4r_param_info")
     for i in range(n):
-        _lib.check(lib.b4r_param_info(C.byref(cfg), i, name, 256, C.byref(off), C.byref(rows), C.byref(cols),
-                                      C.byref(ld), C.byref(dec)), "b4r_param_info")
+        _lib.check(info(ref, i, name, 256, C.byref(off), C.byref(rows), C.byref(cols), C.byref(ld), C.byref(dec)),
+                   "b4r_param_info")
         out.append(ParamInfo(name.value.decode(), off.value, rows.value, cols.value, ld.value, dec.value))
     return out
 
@@ -147,16 +157,19 @@ def check_rank_full_args(k, exclude: Optional[torch.Tensor] = None, n_rows: Opti
 class Engine:
     """One replica of the model on one GPU."""
 
-    def __init__(self, cfg: ModelConfig, device="cuda", seed: int = 0):
+    def __init__(self, cfg: ModelConfig, device="cuda", seed: int = 0, embedding_width: Optional[int] = None):
+        """embedding_width: the item table's width E (Bert4RecEncoder(embedding_width=...)); None / 0 / hidden_size = the unfactorised
+        model.  E < hidden_size adds the learned E -> hidden projection (include/b4r.h, b4r_model_config_ex)."""
         self.lib = _lib.load()
         self.cfg = cfg
+        self.embedding_width = int(embedding_width) if embedding_width else int(cfg.hidden_size)
         self.device = torch.device(device)
-        total = self.lib.b4r_param_total_floats(C.byref(cfg))
+        total = self._api("b4r_param_total_floats")()
         if total < 0:
             raise ValueError("invalid encoder configuration: " + _lib.last_error())
         self.n_params = int(total)
-        self.n_decay = int(self.lib.b4r_param_decay_floats(C.byref(cfg)))
-        self.table = param_table(cfg)
+        self.n_decay = int(self._api("b4r_param_decay_floats")())
+        self.table = param_table(cfg, self.embedding_width)
         self.params = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
         self.pooler = torch.zeros(int(self.lib.b4r_pooler_floats(C.byref(cfg))), dtype=torch.float32, device=self.device)
         self.grads: Optional[torch.Tensor] = None
@@ -167,6 +180,16 @@ class Engine:
         self._ws: Dict[Tuple[int, int, int], torch.Tensor] = {}
         self.rehearse_collectives = False   # True: dp_train_step issues its all-reduce even in a process group of one
         self.set_seed(seed)
+
+    @property
+    def factorised(self) -> bool:
+        return self.embedding_width != self.cfg.hidden_size
+
+    def _api(self, name: str):
+        """`name` bound to this engine's config: every config-taking call goes through here (config_api), so that no call site can
+        hand the 36-byte struct to a factorised model."""
+        fn, ref = config_api(self.lib, self.cfg, self.embedding_width, name)
+        return lambda *args: fn(ref, *args)
 
     # ---- parameters -----------------------------------------------------------------------------------------------
     def view(self, name: str, buf: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -219,6 +242,9 @@ class Engine:
         """Copy variables given under the reference's names/shapes into the flat buffer."""
         for name, t in tensors.items():
             v = self.view(name)
+            if t.numel() != v.numel():
+                raise ValueError(f"{name}: {tuple(t.shape)} does not fit the model's {tuple(v.shape)} (embedding_width "
+                                 f"{self.embedding_width}, hidden_size {self.cfg.hidden_size})")
             v.copy_(t.detach().to(torch.float32).reshape(v.shape).to(self.device))
 
     def export_named(self, buf: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
@@ -269,8 +295,7 @@ class Engine:
         sizes = self.__dict__.setdefault("_ws_bytes", {})
         nbytes = sizes.get((B, L, P, encoder_only))
         if nbytes is None:
-            query = self.lib.b4r_workspace_bytes_encoder if encoder_only else self.lib.b4r_workspace_bytes
-            nbytes = query(C.byref(self.cfg), B, L, P)
+            nbytes = self._api("b4r_workspace_bytes_encoder" if encoder_only else "b4r_workspace_bytes")(B, L, P)
             if nbytes < 0:
                 raise B4RError("b4r_workspace_bytes: " + _lib.last_error())
             sizes[(B, L, P, encoder_only)] = nbytes
@@ -302,7 +327,7 @@ class Engine:
 
     def region(self, name: str, B: int, L: int, P: int, encoder_only: bool = False) -> torch.Tensor:
         off, rows, cols, ld = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32()
-        _lib.check(self.lib.b4r_workspace_region(C.byref(self.cfg), B, L, P, name.encode(), C.byref(off), C.byref(rows),
+        _lib.check(self._api("b4r_workspace_region")(B, L, P, name.encode(), C.byref(off), C.byref(rows),
                                                  C.byref(cols), C.byref(ld)), "b4r_workspace_region")
         return torch.as_strided(self.workspace(B, L, P, encoder_only), (rows.value, cols.value), (ld.value, 1), off.value)
 
@@ -336,7 +361,7 @@ class Engine:
     # ---- compute --------------------------------------------------------------------------------------------------
     def fused_head_supported(self) -> bool:
         """train-step masked-LM head that never materialises the logits (include/b4r.h, B4R_FLAG_FUSED_HEAD)"""
-        return bool(self.lib.b4r_fused_head_supported(C.byref(self.cfg)))
+        return bool(self._api("b4r_fused_head_supported")())
 
     def forward(self, cb: Batch, training: bool = False, pooler: bool = True, fused_head: bool = False,
                 head_rows_only: bool = False, encoder_only: bool = False) -> None:  # noqa: D401
@@ -347,7 +372,7 @@ class Engine:
         flags = (_lib.FLAG_TRAINING if training else 0) | (_lib.FLAG_POOLER if pooler else 0) | \
                 (_lib.FLAG_FUSED_HEAD if fused_head else 0) | (_lib.FLAG_HEAD_ROWS_ONLY if head_rows_only else 0) | \
                 (_lib.FLAG_ENCODER_ONLY if encoder_only else 0)
-        _lib.check(self.lib.b4r_forward(C.byref(self.cfg), C.byref(cb), _ptr(self.params), _ptr(self.pooler), _ptr(ws),
+        _lib.check(self._api("b4r_forward")(C.byref(cb), _ptr(self.params), _ptr(self.pooler), _ptr(ws),
                                         ws.numel() * 4, _ptr(self.state), flags, _stream(self.device)), "b4r_forward")
 
     def begin_step(self) -> None:
@@ -355,7 +380,7 @@ class Engine:
 
     def loss(self, cb: Batch, want_grad: bool, fused_head: bool = False) -> None:
         ws = self.workspace(cb.B, cb.L, cb.P)
-        _lib.check(self.lib.b4r_loss(C.byref(self.cfg), C.byref(cb), _ptr(ws), ws.numel() * 4, _ptr(self.state),
+        _lib.check(self._api("b4r_loss")(C.byref(cb), _ptr(ws), ws.numel() * 4, _ptr(self.state),
                                      (1 if want_grad else 0) | (_lib.LOSS_FUSED_HEAD if fused_head else 0),
                                      _stream(self.device)), "b4r_loss")
 
@@ -369,22 +394,22 @@ class Engine:
         flags = (_lib.FLAG_TRAINING if training else 0) | (_lib.FLAG_FUSED_HEAD if fused_head else 0) | \
                 (_lib.FLAG_GRAD_TAIL if grad_tail else 0) | (_lib.FLAG_HEAD_ROWS_ONLY if head_rows_only else 0) | \
                 (_lib.FLAG_LOSS_SUMS if loss_sums else 0)
-        _lib.check(self.lib.b4r_backward(C.byref(self.cfg), C.byref(cb), _ptr(self.params), _ptr(self.grads), _ptr(ws),
+        _lib.check(self._api("b4r_backward")(C.byref(cb), _ptr(self.params), _ptr(self.grads), _ptr(ws),
                                          ws.numel() * 4, _ptr(self.state), flags, _stream(self.device)), "b4r_backward")
 
     def optimizer_step(self, hp: AdamWConfig, cb: Batch, reduced: bool = False) -> None:
         """reduced: the gradient buffer (with its tail of sums) went through the data-parallel all-reduce"""
         self.ensure_training_buffers()
         ws = self.workspace(cb.B, cb.L, cb.P)
-        fn = self.lib.b4r_optimizer_step_reduced if reduced else self.lib.b4r_optimizer_step
-        _lib.check(fn(C.byref(self.cfg), C.byref(hp), _ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v),
+        fn = self._api("b4r_optimizer_step_reduced" if reduced else "b4r_optimizer_step")
+        _lib.check(fn(C.byref(hp), _ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v),
                       _ptr(ws), ws.numel() * 4, _ptr(self.state), _stream(self.device)), "b4r_optimizer_step")
 
     def train_step(self, hp: AdamWConfig, cb: Batch) -> None:
         """BERT4RecModel.train_step (bert4rec_model.py:151-173) as one enqueue; metrics stay on the device."""
         self.ensure_training_buffers()
         ws = self.workspace(cb.B, cb.L, cb.P)
-        _lib.check(self.lib.b4r_train_step(C.byref(self.cfg), C.byref(hp), C.byref(cb), _ptr(self.params), _ptr(self.grads),
+        _lib.check(self._api("b4r_train_step")(C.byref(hp), C.byref(cb), _ptr(self.params), _ptr(self.grads),
                                            _ptr(self.adam_m), _ptr(self.adam_v), _ptr(ws), ws.numel() * 4, _ptr(self.state),
                                            _stream(self.device)), "b4r_train_step")
 
@@ -473,7 +498,7 @@ class Engine:
         ws = self.__dict__.get("_idle_ws")
         if ws is None:
             ws = self._idle_ws = torch.empty(4096, dtype=torch.float32, device=self.device)   # the optimizer's norm partials
-        _lib.check(self.lib.b4r_optimizer_step_reduced(C.byref(self.cfg), C.byref(hp), _ptr(self.params), _ptr(self.grads),
+        _lib.check(self._api("b4r_optimizer_step_reduced")(C.byref(hp), _ptr(self.params), _ptr(self.grads),
                                                        _ptr(self.adam_m), _ptr(self.adam_v), _ptr(ws), ws.numel() * 4,
                                                        _ptr(self.state), _stream(self.device)), "b4r_optimizer_step_reduced")
 
@@ -527,19 +552,20 @@ class Engine:
         return enc
 
     def mlm_transform_rows(self, seq: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
-        """b4r_mlm_transform_rows: tfm MaskedLM's gather -> dense(gelu) -> LayerNorm on the listed rows of seq [N,H] only."""
+        """b4r_mlm_transform_rows: tfm MaskedLM's gather -> dense(gelu) -> LayerNorm on the listed rows of seq [N,H] only; the
+        result is [R, E] (E = the item table's width)."""
         rows = rows.to(device=self.device, dtype=torch.int64).contiguous()
         R, H = int(rows.numel()), self.cfg.hidden_size
-        out = torch.empty((R, H), dtype=torch.float32, device=self.device)
+        out = torch.empty((R, self.embedding_width), dtype=torch.float32, device=self.device)
         scratch = torch.empty(3 * (R * H + 4) + 2 * (R + 4), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.b4r_mlm_transform_rows(C.byref(self.cfg), _ptr(self.params), _ptr(seq), seq.shape[0], _ptr(rows), R,
+        _lib.check(self._api("b4r_mlm_transform_rows")(_ptr(self.params), _ptr(seq), seq.shape[0], _ptr(rows), R,
                                                    _ptr(out), _ptr(scratch), _stream(self.device)), "b4r_mlm_transform_rows")
         return out
 
     def rank_candidates(self, hidden: torch.Tensor, hidden_rows: Optional[torch.Tensor], cand: Optional[torch.Tensor],
                         gt: Optional[torch.Tensor], want_ranking: bool = True, want_scores: bool = False,
                         n_candidates: Optional[int] = None, n_rows: Optional[int] = None):
-        """b4r_rank_candidates on `hidden` [*,H] (ld = stride(0)); cand [R,C] int64, or None = every row ranks the items
+        """b4r_rank_candidates on `hidden` [*,E] (the transform's rows, E = the item table's width; ld = stride(0)); cand [R,C] int64, or None = every row ranks the items
         0 .. n_candidates-1 (the whole vocabulary; n_rows rows); gt [R] int64 or None."""
         if cand is None:
             R, Cn = int(n_rows), int(n_candidates)
@@ -551,7 +577,7 @@ class Engine:
         ranking = torch.empty((R, Cn), dtype=torch.int64, device=self.device) if want_ranking else None
         gt_rank = torch.empty((R,), dtype=torch.int32, device=self.device) if gt is not None else None
         scores = torch.empty((R, Cn), dtype=torch.float32, device=self.device) if want_scores else None
-        H = self.cfg.hidden_size
+        H = self.embedding_width
         need = int(self.lib.b4r_rank_scratch_bytes(R, Cn))
         scratch = None
         if need > 0:
@@ -567,14 +593,14 @@ class Engine:
 
     def rank_full(self, hidden: torch.Tensor, rows: Optional[torch.Tensor], exclude: Optional[torch.Tensor], first_item: int,
                   gt: Optional[torch.Tensor], k: int):
-        """b4r_rank_full on `hidden` [*,H] (ld = stride(0)): rows [R] (hidden row of each ranked row) or None (R = hidden rows);
+        """b4r_rank_full on `hidden` [*,E] (the transform's rows, E = the item table's width; ld = stride(0)): rows [R] (hidden row of each ranked row) or None (R = hidden rows);
         exclude [R,E] int64 ids not to rank (-1 padded) or None; gt [R] int64 or None.  Returns (ids [R,k] int64, scores [R,k] fp32,
         gt_rank [R] int32 or None): the best k allowed items of every row over the whole vocabulary, ties to the lower id, -1 / -inf
         where fewer than k are allowed.  The scratch buffer is kept between calls."""
         R = int(rows.numel()) if rows is not None else int(hidden.shape[0])
         k = check_rank_full_args(k, exclude, R)
-        if hidden.dtype != torch.float32 or hidden.ndim != 2 or hidden.stride(1) != 1 or hidden.shape[1] != self.cfg.hidden_size:
-            raise ValueError(f"hidden must be float32 [rows, {self.cfg.hidden_size}] with unit column stride")
+        if hidden.dtype != torch.float32 or hidden.ndim != 2 or hidden.stride(1) != 1 or hidden.shape[1] != self.embedding_width:
+            raise ValueError(f"hidden must be float32 [rows, {self.embedding_width}] with unit column stride")
         rows_d = None if rows is None else rows.to(device=self.device, dtype=torch.int64).contiguous()
         ex_d = None if exclude is None or exclude.shape[1] == 0 else exclude.to(device=self.device, dtype=torch.int64).contiguous()
         E = 0 if ex_d is None else int(ex_d.shape[1])
@@ -595,7 +621,7 @@ class Engine:
             sc = self._rank_full_scratch = torch.empty(want, dtype=torch.uint8, device=self.device)
         _lib.check(self.lib.b4r_rank_full(_ptr(hidden), hidden.stride(0), _ptr(rows_d),
                                           _ptr(self.view("word_embeddings/embeddings")),
-                                          _ptr(self.view("cls/predictions/output_bias/bias")), self.cfg.hidden_size, V, int(first_item),
+                                          _ptr(self.view("cls/predictions/output_bias/bias")), self.embedding_width, V, int(first_item),
                                           R, _ptr(ex_d), E, _ptr(gt_d), k, _ptr(ids), _ptr(scores), _ptr(gt_rank), _ptr(sc),
                                           sc.numel(), _stream(self.device)), "b4r_rank_full")
         return ids, scores, gt_rank

@@ -381,7 +381,16 @@ class BERT4RecModel:
         return self.engine.export_named()
 
     def set_weights(self, weights: Dict[str, torch.Tensor]) -> None:
-        self.engine.load_named(weights)
+        e = self.engine
+        table = weights.get("word_embeddings/embeddings")
+        if table is not None and tuple(table.shape)[-1] != e.embedding_width:
+            raise ValueError(f"the checkpoint's item table is {tuple(table.shape)} wide, the model's embedding_width is "
+                             f"{e.embedding_width}: build the encoder with embedding_width={tuple(table.shape)[-1]}")
+        if ("embedding_projection/kernel" in weights) != e.factorised:
+            raise ValueError("the checkpoint %s embedding_projection/* but the model is %s" %
+                             ("has" if "embedding_projection/kernel" in weights else "lacks",
+                              "factorised" if e.factorised else "not factorised"))
+        e.load_named(weights)
 
     def save_weights(self, filepath) -> None:
         from safetensors.torch import save_file

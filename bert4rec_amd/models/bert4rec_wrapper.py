@@ -27,7 +27,10 @@ class BERT4RecModelWrapper(ModelWrapper):
 
     def _encoder_json(self) -> dict:
         cfg = self.model.encoder.get_config()
-        return {k: cfg[k] for k in _JSON_KEYS}
+        out = {k: cfg[k] for k in _JSON_KEYS}
+        if cfg.get("embedding_width") not in (None, cfg["hidden_size"]):   # factorised item embeddings only
+            out["embedding_width"] = cfg["embedding_width"]
+        return out
 
     def save(self, save_path: pathlib.Path, tokenizer=None, mode: int = 0) -> bool:
         save_path = utils.determine_model_path(pathlib.Path(save_path), mode)

@@ -40,8 +40,10 @@ class Bert4RecEncoder:
             raise NotImplementedError("only inner_activation='gelu' (erf form) is implemented")
         if norm_first:
             raise NotImplementedError("norm_first=True (pre-LN) is not implemented; the reference default is post-LN")
-        if embedding_width != hidden_size:
-            raise NotImplementedError("embedding_width != hidden_size (factorised embeddings) is not implemented")
+        if embedding_width != hidden_size and not (embedding_width in (64, 128, 256) and embedding_width < hidden_size):
+            # factorised item embeddings (bert4rec_encoder.py:103-131): a [V, E] table and a learned E -> H projection
+            raise ValueError(f"embedding_width {embedding_width} is not supported with hidden_size {hidden_size}: use "
+                             f"hidden_size (None) or 64 / 128 / 256 below it")
         if output_range is not None or embedding_layer is not None or with_dense_inputs:
             raise NotImplementedError("output_range / embedding_layer / with_dense_inputs are not implemented")
         self.name = name
@@ -56,7 +58,7 @@ class Bert4RecEncoder:
         cfg = make_model_config(vocab_size, hidden_size, num_layers, num_attention_heads, max_sequence_length, inner_dim,
                                 output_dropout, attention_dropout)
         self.device = torch.device(device) if device is not None else _default_device()
-        self.engine = Engine(cfg, self.device, seed=seed)   # raises ValueError on an unsupported geometry
+        self.engine = Engine(cfg, self.device, seed=seed, embedding_width=embedding_width)   # ValueError on an unsupported geometry
         self.engine.init_parameters(seed=seed)
         self.inputs = {"input_word_ids": "int[B,L]", "input_mask": "int[B,L]"}
 
@@ -83,6 +85,7 @@ class Bert4RecEncoder:
         return dict(sequence_output=outs[-1], pooled_output=own(e.region("pooled_output", B, L, P)), encoder_outputs=outs)
 
     def get_embedding_table(self) -> torch.Tensor:
+        """[V, E]: E = embedding_width (hidden_size unless factorised)"""
         return self.engine.view("word_embeddings/embeddings")
 
     def get_config(self) -> dict:

@@ -287,12 +287,84 @@ int b4r_rank_metrics(const int32_t* gt_rank, int32_t R, const int32_t* family, c
 int b4r_mlm_transform_rows(const b4r_model_config* cfg, const float* params, const float* seq, int64_t n_seq_rows,
                            const int64_t* rows, int32_t R, float* out, float* scratch, b4r_stream_t stream);
 
+/* ---- factorised item embeddings (embedding_width < hidden_size) ------------------------------------------------
+ * Bert4RecEncoder(embedding_width=E), bert4rec_encoder.py:103-131 (layers) and :198-214 (call): the item table is [V, E] and a
+ * learned E -> H projection lifts the embeddings into the encoder; tfm MaskedLM is built from the [V, E] table, so its transform
+ * maps H -> E.  With E = embedding_width and H = base.hidden_size:
+ *   e   = dropout(LN_E(word_embeddings[ids] + position_embedding[:L]))   (dropout element index row * E + col, site B4R_STREAM_EMB)
+ *   x0  = e . embedding_projection/kernel [E,H] + embedding_projection/bias [H]       (EinsumDense '...x,xy->...y')
+ *   ... the encoder layers at width H, unchanged ...
+ *   t   = LN_E(gelu(gather(seq) . cls/predictions/transform/dense/kernel [H,E] + bias [E]))
+ *   logits = t . word_embeddings^T + cls/predictions/output_bias/bias
+ * Parameter layout (b4r_param_info_ex): word_embeddings/embeddings [V,E], position_embedding/embeddings [max_seq_len,E],
+ * embeddings/layer_norm/{gamma,beta} [E], cls/predictions/transform/dense/kernel [H,E], its bias and LayerNorm [E], plus
+ * embedding_projection/kernel [E,H] (weight-decayed: in the decayed prefix, behind the position table) and
+ * embedding_projection/bias [H] (not decayed, behind the embedding LayerNorm) -- adam_w_optimizer.py:154-168's default exclusion
+ * list.  Workspace regions: "mlm_hidden" is [B*P, E]; "embeddings" stays x0 [B*L, H] (the projection's output, layer 0's input).
+ * Supported: E in {64, 128, 256} with E < H.  embedding_width 0 or == hidden_size is the unfactorised model: the _ex entry points
+ * then do exactly what the classic ones do (same layout, same launches, same bits); the classic ones are wrappers with
+ * embedding_width = 0.  Any other E returns B4R_E_SHAPE and a nonzero reserved word B4R_E_BADARG (a -1 from the int64 queries),
+ * with the message in b4r_last_error. */
+typedef struct b4r_model_config_ex {
+  b4r_model_config base;
+  int32_t embedding_width;  /* 0 or base.hidden_size: the unfactorised model; else 64 / 128 / 256 and < hidden_size */
+  int32_t reserved[3];      /* must be zero (room for the next encoder option without another struct) */
+} b4r_model_config_ex;
+
+int64_t b4r_param_total_floats_ex(const b4r_model_config_ex* cfg);
+int64_t b4r_param_decay_floats_ex(const b4r_model_config_ex* cfg);
+int32_t b4r_param_count_ex(const b4r_model_config_ex* cfg);
+int b4r_param_info_ex(const b4r_model_config_ex* cfg, int32_t index, char* name, size_t name_cap, int64_t* offset,
+                      int32_t* rows, int32_t* cols, int32_t* ld, int32_t* decay);
+int64_t b4r_workspace_bytes_ex(const b4r_model_config_ex* cfg, int32_t B, int32_t L, int32_t P);
+int64_t b4r_workspace_bytes_encoder_ex(const b4r_model_config_ex* cfg, int32_t B, int32_t L, int32_t P);
+int b4r_workspace_region_ex(const b4r_model_config_ex* cfg, int32_t B, int32_t L, int32_t P, const char* name,
+                            int64_t* offset_floats, int32_t* rows, int32_t* cols, int32_t* ld);
+/* the logits-free head sweeps the [V, E] table: it answers on E (64 / 128 / 256) and the gemm mode */
+int32_t b4r_fused_head_supported_ex(const b4r_model_config_ex* cfg);
+int b4r_forward_ex(const b4r_model_config_ex* cfg, const b4r_batch* batch, const float* params, const float* pooler,
+                   void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags, b4r_stream_t stream);
+int b4r_loss_ex(const b4r_model_config_ex* cfg, const b4r_batch* batch, void* workspace, int64_t workspace_bytes,
+                b4r_train_state* state, int32_t want_grad, b4r_stream_t stream);
+int b4r_backward_ex(const b4r_model_config_ex* cfg, const b4r_batch* batch, const float* params, float* grads,
+                    void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags, b4r_stream_t stream);
+int b4r_optimizer_step_ex(const b4r_model_config_ex* cfg, const b4r_adamw_config* hp, float* params, const float* grads,
+                          float* adam_m, float* adam_v, void* workspace, int64_t workspace_bytes, b4r_train_state* state,
+                          b4r_stream_t stream);
+int b4r_optimizer_step_reduced_ex(const b4r_model_config_ex* cfg, const b4r_adamw_config* hp, float* params, const float* grads,
+                                  float* adam_m, float* adam_v, void* workspace, int64_t workspace_bytes, b4r_train_state* state,
+                                  b4r_stream_t stream);
+int b4r_train_step_ex(const b4r_model_config_ex* cfg, const b4r_adamw_config* hp, const b4r_batch* batch, float* params,
+                      float* grads, float* adam_m, float* adam_v, void* workspace, int64_t workspace_bytes,
+                      b4r_train_state* state, b4r_stream_t stream);
+/* out [R, E] (ld E); scratch: 3*R*H + 2*R floats as for b4r_mlm_transform_rows */
+int b4r_mlm_transform_rows_ex(const b4r_model_config_ex* cfg, const float* params, const float* seq, int64_t n_seq_rows,
+                              const int64_t* rows, int32_t R, float* out, float* scratch, b4r_stream_t stream);
+
 /* ---- op level (each is also a stage of the model-level calls; exposed for parity tests and reuse) ------------ */
 
 /* x = dropout(LN(E[ids] + P[pos]))   bert4rec_encoder.py:198-211 */
 int b4r_embed_ln_fwd(const int64_t* ids, int32_t B, int32_t L, const float* table, int32_t V, const float* pos_table,
                      const float* gamma, const float* beta, int32_t H, float eps, float* out, float* mean,
                      float* rstd, const uint32_t* rng, float dropout, b4r_stream_t stream);
+
+/* The factorised embedding stage, bert4rec_encoder.py:198-214 with embedding_width E < H, one launch each (E in {64,128,256},
+ * H a multiple of 64 up to 1024; else B4R_E_SHAPE).  Matrix-core products: bf16x3 for the forward at E = 64 in the
+ * B4R_GEMM_BF16X3 mode, exact fp32 otherwise (and in B4R_GEMM_F32); fixed summation order, no atomics.
+ *   fwd: x0 [B*L,H] = dropout(LN_E(table[ids] + pos_table[l])) . Wp [E,H] + bp [H]; mean / rstd [B*L] of the LayerNorm.  The
+ *        [B*L, E] rows stay on the chip.  Out-of-range ids read row 0.
+ *   bwd: from dx0 [B*L,H]: dWp [E,H] = e^T . dx0, dbp [H] = colsum(dx0) (e recomputed from ids, tables, mean, rstd), de = dx0 . Wp^T
+ *        back through the dropout and the LayerNorm: drows [B*L,E] = d(table row + position row), the input of the item-table scatter;
+ *        dln [2E] = d gamma then d beta.  scratch: b4r_embed_proj_bwd_scratch_floats(B*L, E, H) floats.  dWp / dbp / dln are
+ *        overwritten; their column sums join the reduce queue of a model-level backward. */
+int b4r_embed_proj_fwd(const int64_t* ids, int32_t B, int32_t L, const float* table, int32_t V, const float* pos_table,
+                       const float* gamma, const float* beta, int32_t E, float eps, const float* Wp, const float* bp, int32_t H,
+                       float* x0, float* mean, float* rstd, const uint32_t* rng, float dropout, b4r_stream_t stream);
+int64_t b4r_embed_proj_bwd_scratch_floats(int32_t N, int32_t E, int32_t H);
+int b4r_embed_proj_bwd(const float* dx0, const int64_t* ids, int32_t B, int32_t L, const float* table, int32_t V,
+                       const float* pos_table, const float* gamma, const float* beta, int32_t E, const float* mean, const float* rstd,
+                       const float* Wp, int32_t H, const uint32_t* rng, float dropout, float* drows, float* dWp, float* dbp,
+                       float* dln, float* scratch, b4r_stream_t stream);
 
 /* y = LN(z) rows of width H; saves mean / rstd */
 int b4r_ln_fwd(const float* z, int32_t rows, int32_t H, const float* gamma, const float* beta, float eps, float* y,
