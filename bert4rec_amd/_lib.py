@@ -24,8 +24,19 @@ class ModelConfig(C.Structure):
 
 class ModelConfigEx(C.Structure):
     """b4r_model_config_ex: the classic config plus embedding_width (0 or hidden_size: unfactorised; else 64 / 128 / 256 below
-    hidden_size) and three reserved words that must be zero."""
+    hidden_size) and three reserved words: word 1 is the activations word (set_activations), words 0 and 2 must be zero."""
     _fields_ = [("base", ModelConfig), ("embedding_width", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+    def set_activations(self, inner: int, mlm: int) -> "ModelConfigEx":
+        """reserved[1] = the activations word: bits 0-7 the feed-forward activation id, bits 8-15 the masked-LM transform's
+        (B4R_ACT_*, bert4rec_amd/activations.py)"""
+        self.reserved[1] = activations_word(inner, mlm)
+        return self
+
+
+def activations_word(inner: int, mlm: int) -> int:
+    """B4R_ACT_WORD of include/b4r.h"""
+    return (int(inner) & 0xFF) | ((int(mlm) & 0xFF) << 8)
 
 
 class Batch(C.Structure):
@@ -50,7 +61,7 @@ class GemmDesc(C.Structure):
                 ("ln_dgamma", C.c_void_p), ("ln_dbeta", C.c_void_p), ("ln_ids", C.c_void_p), ("ln_table", C.c_void_p),
                 ("ln_pos", C.c_void_p), ("ln_L", C.c_int32), ("ln_V", C.c_int32), ("C3", C.c_void_p), ("ldc3", C.c_int32),
                 ("a_gather_idx", C.c_void_p), ("a_gather_add_per", C.c_int64), ("a_gather_per", C.c_int32), ("a_copy", C.c_void_p),
-                ("a_copy_ld", C.c_int32)]
+                ("a_copy_ld", C.c_int32), ("activation", C.c_int32)]
 
 
 class GemmTnDesc(C.Structure):
@@ -58,7 +69,8 @@ class GemmTnDesc(C.Structure):
                 ("ldo", C.c_int32), ("R", C.c_int32), ("Mo", C.c_int32), ("No", C.c_int32), ("colsum", C.c_void_p),
                 ("colsum_a", C.c_void_p), ("rng", C.c_void_p), ("drop_stream", C.c_uint32), ("drop_rate", C.c_float),
                 ("b_dropout", C.c_int32), ("accumulate", C.c_int32), ("dgrad_w", C.c_void_p), ("dgrad_ldw", C.c_int32),
-                ("dgrad_out", C.c_void_p), ("dgrad_ldo", C.c_int32), ("dgrad_gelu_pre", C.c_void_p), ("dgrad_ldg", C.c_int32)]
+                ("dgrad_out", C.c_void_p), ("dgrad_ldo", C.c_int32), ("dgrad_gelu_pre", C.c_void_p), ("dgrad_ldg", C.c_int32),
+                ("activation", C.c_int32)]
 
 
 class AttnBlockDesc(C.Structure):
@@ -97,7 +109,7 @@ class FfnDesc(C.Structure):
                 ("rows", C.c_void_p), ("n_rows", C.c_void_p), ("max_rows", C.c_int32), ("row_slot", C.c_void_p),
                 ("slot_grad", C.c_void_p), ("dln_gamma", C.c_void_p), ("dz2_rows", C.c_void_p),
                 ("slot_positions", C.c_void_p), ("slot_ids", C.c_void_p), ("slots_per_seq", C.c_int32), ("seq_len", C.c_int32),
-                ("ln1_beta", C.c_void_p)]
+                ("ln1_beta", C.c_void_p), ("activation", C.c_int32)]
 
 
 # b4r_train_state: 16 x 32-bit words; word indices of the float fields
@@ -170,6 +182,7 @@ PROTOTYPES = {
     "b4r_ln_fwd": (C.c_int, [_P, _I32, _I32, _P, _P, _F, _P, _P, _P, _P]),
     "b4r_ln_bwd_scratch_floats": (_I64, [_I32, _I32]),
     "b4r_ln_bwd": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "b4r_ln_bwd_act": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "b4r_set_gemm_mode": (C.c_int, [C.c_int]),
     "b4r_get_gemm_mode": (C.c_int, []),
     "b4r_gemm_f32": (C.c_int, [C.POINTER(GemmDesc), _P]),

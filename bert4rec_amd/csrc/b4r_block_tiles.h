@@ -184,8 +184,10 @@ struct FfnTileP {
 
 // Feed-forward forward of the wave's 16 rows: x2 = LN(x1 + dropout(gelu(x1.W1 + b1).W2 + b2)).  Lane (i, g): row `tok` of the
 // [N, 64] tensors (pad lanes carry a valid row and store == false); w1img / w2img / sb1: the staged W1, W2 images and b1 in LDS.
+// ACT: B4R_ACT_GELU, another id, or B4R_ACT_ANY with the activation `act` in place of the GELU (b4r_common.h)
+template <int ACT>
 __device__ __forceinline__ void ffn_fwd_tile(const FfnTileP& p, const char* w1img, const char* w2img, const float* sb1, const LaneK& lk,
-                                             const DropCtx& dctx, int tok, bool store, int g) {
+                                             const DropCtx& dctx, int tok, bool store, int g, int act) {
   bf16x8 xh[2], xl[2];
   {
     f32x8 xv[2];
@@ -207,7 +209,8 @@ __device__ __forceinline__ void ffn_fwd_tile(const FfnTileP& p, const char* w1im
       const f32x4 c = fpre_tile(w1img, a ? (f32x4){bias[4], bias[5], bias[6], bias[7]} : (f32x4){bias[0], bias[1], bias[2], bias[3]},
                                 lk, kt, a, xh, xl);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) f[a][r] = (FFN_EXP & 2) ? c[r] : b4r_gelu_fast(c[r]);
+      for (int r = 0; r < 4; ++r)
+        f[a][r] = (FFN_EXP & 2) ? c[r] : (ACT == B4R_ACT_GELU) ? b4r_gelu_fast(c[r]) : b4r_act_val<true>(b4r_act_id<ACT>(act), c[r]);
     }
     bf16x8 fh, fl;
     split8(cat(f[0], f[1]), fh, fl);   // k-slot (g, j) = inner column 32 kt + 8g + j

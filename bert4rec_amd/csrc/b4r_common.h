@@ -287,6 +287,81 @@ __device__ __forceinline__ float b4r_gelu_grad_fast(float x) {
   return fmaf(x * 0.39894228040143267794f, e, 0.5f * (1.0f + er));
 }
 
+// ---------------------------------------------------------------------------------------------
+// The feed-forward and masked-LM transform activations (B4R_ACT_*, include/b4r.h), value f and derivative f' with TF semantics
+// (relu' = 0 at 0).  Kernels are templated on ACT: ACT == B4R_ACT_GELU is the erf-GELU code above, unchanged; ACT == B4R_ACT_ANY
+// is one instantiation for every other id, which it reads at run time (a kernel argument: the switch is wave-uniform); a few kernels
+// are instantiated per id instead (b4r_act_dispatch).
+// FAST = the split-precision kernels' variants (hardware exp / log / reciprocal; GELU through b4r_erf_as), else the exact-fp32
+// mode's (ocml).  Both meet |error| <= 1e-6 max(1, |f|) on [-30, 30] and stay finite at +-88 (exp(88) < FLT_MAX; beyond, the
+// exponential's inf only ever meets a reciprocal or a select).
+// ---------------------------------------------------------------------------------------------
+constexpr int B4R_ACT_ANY = -1;
+constexpr float B4R_SELU_ALPHA = 1.6732632423543772f, B4R_SELU_SCALE = 1.0507009873554805f;
+
+template <bool FAST> __device__ __forceinline__ float b4r_exp_(float x) { return FAST ? __expf(x) : expf(x); }
+template <bool FAST> __device__ __forceinline__ float b4r_rcp_(float x) { return FAST ? __builtin_amdgcn_rcpf(x) : 1.0f / x; }
+template <bool FAST> __device__ __forceinline__ float b4r_sigmoid_(float x) { return b4r_rcp_<FAST>(1.0f + b4r_exp_<FAST>(-x)); }
+template <bool FAST> __device__ __forceinline__ float b4r_tanh_(float x) {
+  if (!FAST) return tanhf(x);
+  // 1 - 2 / (exp(2|x|) + 1): no cancellation where |tanh| is near 1, an absolute error of a few 1e-8 near 0
+  const float t = 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * fabsf(x)) + 1.0f);
+  return copysignf(t, x);
+}
+template <bool FAST> __device__ __forceinline__ float b4r_expm1_(float x) { return FAST ? __expf(x) - 1.0f : expm1f(x); }
+
+// f and f' of activation `id` at x
+template <bool FAST>
+__device__ __forceinline__ void b4r_act_both(int id, float x, float& f, float& d) {
+  switch (id) {
+    case B4R_ACT_GELU:
+      if (FAST) { float e; const float er = b4r_erf_as(x * 0.70710678118654752440f, e); const float cdf = 0.5f * (1.0f + er);
+                  f = x * cdf; d = fmaf(x * 0.39894228040143267794f, e, cdf); }
+      else { f = b4r_gelu(x); d = b4r_gelu_grad(x); }
+      break;
+    case B4R_ACT_RELU: f = x > 0.f ? x : 0.f; d = x > 0.f ? 1.f : 0.f; break;
+    case B4R_ACT_SWISH: { const float s = b4r_sigmoid_<FAST>(x); f = x * s; d = s * fmaf(x, 1.0f - s, 1.0f); break; }
+    case B4R_ACT_TANH: { const float t = b4r_tanh_<FAST>(x); f = t; d = fmaf(-t, t, 1.0f); break; }
+    case B4R_ACT_SIGMOID: { const float s = b4r_sigmoid_<FAST>(x); f = s; d = s * (1.0f - s); break; }
+    case B4R_ACT_ELU: { const float e = b4r_exp_<FAST>(fminf(x, 0.f)); f = x > 0.f ? x : b4r_expm1_<FAST>(fminf(x, 0.f)); d = x > 0.f ? 1.f : e; break; }
+    case B4R_ACT_SELU: {
+      const float e = b4r_exp_<FAST>(fminf(x, 0.f));
+      f = x > 0.f ? B4R_SELU_SCALE * x : (B4R_SELU_SCALE * B4R_SELU_ALPHA) * b4r_expm1_<FAST>(fminf(x, 0.f));
+      d = x > 0.f ? B4R_SELU_SCALE : (B4R_SELU_SCALE * B4R_SELU_ALPHA) * e;
+      break;
+    }
+    case B4R_ACT_SOFTPLUS: {   // max(x, 0) + log(1 + exp(-|x|)): no overflow at either end
+      const float e = b4r_exp_<FAST>(-fabsf(x));
+      f = fmaxf(x, 0.f) + (FAST ? __logf(1.0f + e) : log1pf(e));
+      d = x >= 0.f ? b4r_rcp_<FAST>(1.0f + e) : e * b4r_rcp_<FAST>(1.0f + e);
+      break;
+    }
+    default: f = x; d = 1.f; break;   // B4R_ACT_LINEAR
+  }
+}
+template <bool FAST> __device__ __forceinline__ float b4r_act_val(int id, float x) { float f, d; b4r_act_both<FAST>(id, x, f, d); return f; }
+template <bool FAST> __device__ __forceinline__ float b4r_act_grad(int id, float x) { float f, d; b4r_act_both<FAST>(id, x, f, d); return d; }
+// the id a kernel instantiated for ACT evaluates: ACT itself (the switch folds away), or the run-time `id` for B4R_ACT_ANY
+template <int ACT> __device__ __forceinline__ int b4r_act_id(int id) { return ACT == B4R_ACT_ANY ? id : ACT; }
+
+// host: f(std::integral_constant<int, act>{}) for act in [1, B4R_ACT_COUNT): the kernels whose run-time switch would spill (the 16-wave
+// hidden-64 feed-forward kernels, 128 registers) are instantiated per activation instead
+#include <type_traits>
+template <class F>
+static inline int b4r_act_dispatch(int act, F&& f) {
+  switch (act) {
+    case B4R_ACT_RELU: return f(std::integral_constant<int, B4R_ACT_RELU>{});
+    case B4R_ACT_SWISH: return f(std::integral_constant<int, B4R_ACT_SWISH>{});
+    case B4R_ACT_TANH: return f(std::integral_constant<int, B4R_ACT_TANH>{});
+    case B4R_ACT_SIGMOID: return f(std::integral_constant<int, B4R_ACT_SIGMOID>{});
+    case B4R_ACT_ELU: return f(std::integral_constant<int, B4R_ACT_ELU>{});
+    case B4R_ACT_SELU: return f(std::integral_constant<int, B4R_ACT_SELU>{});
+    case B4R_ACT_SOFTPLUS: return f(std::integral_constant<int, B4R_ACT_SOFTPLUS>{});
+    case B4R_ACT_LINEAR: return f(std::integral_constant<int, B4R_ACT_LINEAR>{});
+    default: return f(std::integral_constant<int, B4R_ACT_GELU>{});
+  }
+}
+
 // The largest additive key mask of one sequence: 0 when at least one key is valid, -1e9 when the whole row of input_mask is zero.
 // Keras adds (1 - mask) * -1e9 in fp32; on a fully masked sequence every score rounds to -1e9 (ulp 64) and the softmax is exactly
 // uniform, but log-sum-exp = -1e9 + log(L) cannot hold its log(L) in fp32 -- a backward that recomputes exp(score - lse) would see

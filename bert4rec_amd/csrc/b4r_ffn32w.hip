@@ -112,11 +112,20 @@ __device__ __forceinline__ void f32w_barrier() {
 struct GeluPair { float x[2], v[2], d[2], t[2], e[2], q[2], g[2], keep[2]; };
 constexpr double F32W_S = 1.2011224087864498;   // sqrt(log2 e)
 // gv: the gelu values in the accumulator's register order (KEEP: they leave as f through the staged store) -- or, qdst != NULL (a
-// compile-time fact after inlining), every second pair stores its 16 bytes to qdst[8 (q >> 1) ..] at once
+// compile-time fact after inlining), every second pair stores its 16 bytes to qdst[8 (q >> 1) ..] at once.
+// ACT == B4R_ACT_ANY: the activation `act` (b4r_common.h) in place of the GELU, whole in stage 0; stage 7 splits it as above
+template <int ACT>
 __device__ __forceinline__ void f32w_gelu_stage(int st, int q, const f32x16& S, GeluPair& a, uint32_t (&hw)[8], uint32_t (&lw)[8],
-                                                f32x16& gv, float* qdst) {
+                                                f32x16& gv, float* qdst, int act) {
 #pragma unroll
   for (int e = 0; e < 2; ++e) {
+    if (ACT != B4R_ACT_GELU) {
+      if (st == 0) {
+        a.g[e] = b4r_act_val<true>(act, S[2 * q + e]);
+        asm volatile("" : "+v"(a.g[e]));
+      }
+      continue;
+    }
     switch (st) {
       case 0:
         a.x[e] = S[2 * q + e];
@@ -167,9 +176,10 @@ __device__ __forceinline__ bf16x8 f32w_frag(const uint32_t (&w)[8], int s) {
 
 // One step.  a_nxt: unit A of chunk c + 1 (row reads), b_cur: unit B of chunk c (transposed reads); S = S^T(c) complete, Sn = b1 of
 // chunk c + 1 on entry and S^T(c + 1) on exit.
-template <int NP>
+template <int NP, int ACT>
 __device__ __forceinline__ void f32w_step(const char* a_nxt, const char* b_cur, const Lane32& lk, const bf16x8 (&xh)[NP][2],
-                                          const bf16x8 (&xl)[NP][2], f32x16& Sn, f32x16 (&acc)[NP], const f32x16& S, f32x16& gv, float* qdst) {
+                                          const bf16x8 (&xl)[NP][2], f32x16& Sn, f32x16 (&acc)[NP], const f32x16& S, f32x16& gv, float* qdst,
+                                          int act) {
   constexpr int NT = 2 * NP, PER = 8 / NP;
   static_assert(PER >= 1 && 32 <= PER * 6 * NP && 64 <= PER * 9 * NP, "GELU sub-slices must meet the second product's operands");
   GeluPair gp;
@@ -179,7 +189,7 @@ __device__ __forceinline__ void f32w_step(const char* a_nxt, const char* b_cur, 
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
       const int ss = PER * m + u;
-      if (!(F32W_EXP & 1) && ss < 64) f32w_gelu_stage(ss & 7, ss >> 3, S, gp, ghw, glw, gv, qdst);
+      if (!(F32W_EXP & 1) && ss < 64) f32w_gelu_stage<ACT>(ss & 7, ss >> 3, S, gp, ghw, glw, gv, qdst, act);
     }
     ++m;
     __builtin_amdgcn_sched_barrier(0);
@@ -264,11 +274,12 @@ struct F32wP {
   DropArgs drop;
   float* z2; float* x2; float* mean2; float* rstd2;
   float* f; float* fpre; int I;            // optional [N, I]: gelu output and pre-activation for a backward
+  int act;                                 // ACT == B4R_ACT_ANY: the activation (B4R_ACT_*)
 };
 
 
 // KEEP: the launch also writes f = gelu(.) and the pre-activation [N, I] (the backward's inputs)
-template <int NP, int WAVES, bool KEEP>
+template <int NP, int WAVES, bool KEEP, int ACT>
 __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void ffn32w_fwd_kernel(F32wP p) {
   extern __shared__ __attribute__((aligned(16))) char smem_f32w[];
   constexpr int H = 32 * NP, UA = f32w_unit_a(NP), UB = f32w_unit_b(NP), REC = UA + UB, ROWS = 32 * WAVES;
@@ -315,7 +326,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void ffn32w_fwd_kernel(F32wP
     Sn = rows_of(reinterpret_cast<const float*>(slot_a(i + 1) + NP * P_TILE), h);
     f32x16 gv;
     constexpr bool STAGED = NP > 4;
-    f32w_step<NP>(slot_a(i + 1), slot_b(i), lk, xh, xl, Sn, acc, S, gv, (KEEP && !STAGED) ? p.f + mc * p.I + 32 * i + 4 * h : nullptr);
+    f32w_step<NP, ACT>(slot_a(i + 1), slot_b(i), lk, xh, xl, Sn, acc, S, gv, (KEEP && !STAGED) ? p.f + mc * p.I + 32 * i + 4 * h : nullptr,
+                       p.act);
     if (KEEP && STAGED) f32w_store_tile<true>(stg, gv, p.f + (int64_t)m0 * p.I + 32 * i, p.I, p.N - m0, lane, r, h);
   };
   for (int i = 0; i < n; i += 2) {
@@ -371,14 +383,14 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void ffn32w_fwd_kernel(F32wP
   }
 }
 
-template <int NP, int WAVES, bool KEEP>
+template <int NP, int WAVES, bool KEEP, int ACT>
 int f32w_launch_fwd(const F32wPackP& pk, const F32wP& p, hipStream_t stream) {
   hipLaunchKernelGGL(ffn32w_pack_kernel<NP>, dim3(p.n_chunks), dim3(256), 0, stream, pk);
   B4R_CHECK_LAUNCH("wide feed-forward block: weight records");
   const size_t lds = 2 * (size_t)f32w_rec(NP) + ((KEEP && NP > 4) ? (size_t)WAVES * F32W_STG_BYTES : 0);
-  int rc = b4r_raise_lds((const void*)ffn32w_fwd_kernel<NP, WAVES, KEEP>, lds, "wide feed-forward block");
+  int rc = b4r_raise_lds((const void*)ffn32w_fwd_kernel<NP, WAVES, KEEP, ACT>, lds, "wide feed-forward block");
   if (rc) return rc;
-  hipLaunchKernelGGL((ffn32w_fwd_kernel<NP, WAVES, KEEP>), dim3(b4r_cdiv(p.N, 32 * WAVES)), dim3(64 * WAVES), lds, stream, p);
+  hipLaunchKernelGGL((ffn32w_fwd_kernel<NP, WAVES, KEEP, ACT>), dim3(b4r_cdiv(p.N, 32 * WAVES)), dim3(64 * WAVES), lds, stream, p);
   B4R_CHECK_LAUNCH("wide feed-forward block forward");
   return B4R_OK;
 }
@@ -393,10 +405,19 @@ int f32w_launch_fwd(const F32wPackP& pk, const F32wP& p, hipStream_t stream) {
 // TOKENS: a different sweep), which reads f, df, x1 and dz2.
 // ===========================================================================================================================
 struct GeluGradPair { float x[2], v[2], d[2], t[2], e[2], q[2], g[2], keep[2]; };
+// ACT == B4R_ACT_ANY: G * f'(x) of the activation `act`, whole in stage 0; stage 8 splits it
+template <int ACT>
 __device__ __forceinline__ void f32w_dgelu_stage(int st, int q, const f32x16& X, const f32x16& G, GeluGradPair& a, uint32_t (&hw)[8],
-                                                 uint32_t (&lw)[8], f32x16& dv, float* qdst) {
+                                                 uint32_t (&lw)[8], f32x16& dv, float* qdst, int act) {
 #pragma unroll
   for (int e = 0; e < 2; ++e) {
+    if (ACT != B4R_ACT_GELU) {
+      if (st == 0) {
+        a.g[e] = G[2 * q + e] * b4r_act_grad<true>(act, X[2 * q + e]);
+        asm volatile("" : "+v"(a.g[e]));
+      }
+      continue;
+    }
     switch (st) {
       case 0:
         a.x[e] = X[2 * q + e];
@@ -445,10 +466,10 @@ __device__ __forceinline__ void f32w_dgelu_stage(int st, int q, const f32x16& X,
 }
 
 // One step.  b_nxt: unit B of chunk c + 1 (row reads), a_cur: unit A of chunk c (transposed reads); G = G^T(c), X = fpre tile c.
-template <int NP>
+template <int NP, int ACT>
 __device__ __forceinline__ void f32w_bstep(const char* b_nxt, const char* a_cur, const Lane32& lk, const bf16x8 (&dh)[NP][2],
                                            const bf16x8 (&dl)[NP][2], f32x16& Gn, f32x16 (&acc)[NP], const f32x16& G, const f32x16& X,
-                                           f32x16& dv, float* qdst) {
+                                           f32x16& dv, float* qdst, int act) {
   constexpr int NT = 2 * NP, PER = 8 / NP;
   static_assert(PER >= 1 && 36 <= PER * 6 * NP && 72 <= PER * 9 * NP, "GELU' sub-slices must meet the second product's operands");
   GeluGradPair gp;
@@ -458,7 +479,7 @@ __device__ __forceinline__ void f32w_bstep(const char* b_nxt, const char* a_cur,
 #pragma unroll
     for (int u = 0; u < PER; ++u) {
       const int ss = PER * m + u;
-      if (ss < 72) f32w_dgelu_stage(ss % 9, ss / 9, X, G, gp, ghw, glw, dv, qdst);
+      if (ss < 72) f32w_dgelu_stage<ACT>(ss % 9, ss / 9, X, G, gp, ghw, glw, dv, qdst, act);
     }
     ++m;
     __builtin_amdgcn_sched_barrier(0);
@@ -509,6 +530,7 @@ struct F32wBwdP {
   DropArgs drop;
   const float* fpre; float* df; int I;
   float* dx1;
+  int act;   // ACT == B4R_ACT_ANY: the activation (B4R_ACT_*)
 };
 
 __device__ __forceinline__ f32x16 f32w_tile_rows(const float* src, int h) {   // the tile's 16 values of this lane: src = row base + 32 c
@@ -522,7 +544,7 @@ __device__ __forceinline__ f32x16 f32w_tile_rows(const float* src, int h) {   //
   return v;
 }
 
-template <int NP, int WAVES>
+template <int NP, int WAVES, int ACT>
 __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void ffn32w_bwd_kernel(F32wBwdP p) {
   extern __shared__ __attribute__((aligned(16))) char smem_f32w[];
   constexpr int H = 32 * NP, UA = f32w_unit_a(NP), UB = f32w_unit_b(NP), REC = UA + UB, ROWS = 32 * WAVES;
@@ -577,7 +599,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void ffn32w_bwd_kernel(F32wB
     Gn = zero16();
     f32x16 dv;
     constexpr bool STAGED = NP > 4;
-    f32w_bstep<NP>(slot_b(i + 1), slot_a(i), lk, dh, dl, Gn, acc, G, X, dv, STAGED ? nullptr : p.df + mc * p.I + 32 * i + 4 * h);
+    f32w_bstep<NP, ACT>(slot_b(i + 1), slot_a(i), lk, dh, dl, Gn, acc, G, X, dv, STAGED ? nullptr : p.df + mc * p.I + 32 * i + 4 * h,
+                        p.act);
     if (STAGED) f32w_store_tile<true>(stg, dv, p.df + (int64_t)m0 * p.I + 32 * i, p.I, p.N - m0, lane, r, h);
   };
   for (int i = 0; i < n; i += 2) {
@@ -597,16 +620,16 @@ __global__ __launch_bounds__(64 * WAVES, WAVES / 4) void ffn32w_bwd_kernel(F32wB
   }
 }
 
-template <int NP, int WAVES>
+template <int NP, int WAVES, int ACT>
 int f32w_launch_bwd(const F32wPackP* pk, const F32wBwdP& p, hipStream_t stream) {
   if (pk != nullptr) {
     hipLaunchKernelGGL(ffn32w_pack_kernel<NP>, dim3(p.n_chunks), dim3(256), 0, stream, *pk);
     B4R_CHECK_LAUNCH("wide feed-forward block: weight records");
   }
   const size_t lds = 2 * (size_t)f32w_rec(NP) + (NP > 4 ? (size_t)WAVES * F32W_STG_BYTES : 0);
-  int rc = b4r_raise_lds((const void*)ffn32w_bwd_kernel<NP, WAVES>, lds, "wide feed-forward block");
+  int rc = b4r_raise_lds((const void*)ffn32w_bwd_kernel<NP, WAVES, ACT>, lds, "wide feed-forward block");
   if (rc) return rc;
-  hipLaunchKernelGGL((ffn32w_bwd_kernel<NP, WAVES>), dim3(b4r_cdiv(p.N, 32 * WAVES)), dim3(64 * WAVES), lds, stream, p);
+  hipLaunchKernelGGL((ffn32w_bwd_kernel<NP, WAVES, ACT>), dim3(b4r_cdiv(p.N, 32 * WAVES)), dim3(64 * WAVES), lds, stream, p);
   B4R_CHECK_LAUNCH("wide feed-forward block backward (df, dx1)");
   return B4R_OK;
 }
@@ -626,10 +649,17 @@ int b4r_ffn32w_fwd(const b4r_ffn_desc* d, float* recs, float* f, float* fpre, hi
   p.b2 = d->b2; p.gamma = d->ln_gamma; p.beta = d->ln_beta; p.eps = d->ln_eps;
   p.drop = b4r_make_drop(d->rng, d->drop_stream, d->drop_rate, 1);
   p.z2 = d->z2; p.x2 = d->x2; p.mean2 = d->mean2; p.rstd2 = d->rstd2;
-  p.f = f; p.fpre = fpre; p.I = d->I;
+  p.f = f; p.fpre = fpre; p.I = d->I; p.act = d->activation;
   B4R_CHECK_ARG((f == nullptr) == (fpre == nullptr), B4R_E_BADARG, "b4r_ffn32w_fwd: f and fpre come together");
-  if (f != nullptr) return d->H == 128 ? f32w_launch_fwd<4, 8, true>(pk, p, stream) : f32w_launch_fwd<8, 4, true>(pk, p, stream);
-  return d->H == 128 ? f32w_launch_fwd<4, 8, false>(pk, p, stream) : f32w_launch_fwd<8, 4, false>(pk, p, stream);
+  B4R_CHECK_ARG(d->activation >= 0 && d->activation < B4R_ACT_COUNT, B4R_E_BADARG, "b4r_ffn32w_fwd: unknown activation %d", d->activation);
+  if (d->activation != B4R_ACT_GELU) {
+    constexpr int A = B4R_ACT_ANY;
+    if (f != nullptr) return d->H == 128 ? f32w_launch_fwd<4, 8, true, A>(pk, p, stream) : f32w_launch_fwd<8, 4, true, A>(pk, p, stream);
+    return d->H == 128 ? f32w_launch_fwd<4, 8, false, A>(pk, p, stream) : f32w_launch_fwd<8, 4, false, A>(pk, p, stream);
+  }
+  constexpr int G = B4R_ACT_GELU;
+  if (f != nullptr) return d->H == 128 ? f32w_launch_fwd<4, 8, true, G>(pk, p, stream) : f32w_launch_fwd<8, 4, true, G>(pk, p, stream);
+  return d->H == 128 ? f32w_launch_fwd<4, 8, false, G>(pk, p, stream) : f32w_launch_fwd<8, 4, false, G>(pk, p, stream);
 }
 
 // df [N, I] and dx1 [N, H] (residual included) from dz2 and the forward's fpre; recs as left by b4r_ffn32w_fwd (records_ready) or packed here
@@ -638,9 +668,13 @@ int b4r_ffn32w_bwd(const b4r_ffn_desc* d, float* recs, const float* fpre, float*
   F32wBwdP p{};
   p.dz2 = d->dz2; p.N = d->N; p.recs = reinterpret_cast<const char*>(recs); p.n_chunks = d->I / 32;
   p.drop = b4r_make_drop(d->rng, d->drop_stream, d->drop_rate, 1);
-  p.fpre = fpre; p.df = df; p.I = d->I; p.dx1 = dx1;
-  return d->H == 128 ? f32w_launch_bwd<4, 8>(records_ready ? nullptr : &pk, p, stream)
-                     : f32w_launch_bwd<8, 4>(records_ready ? nullptr : &pk, p, stream);
+  p.fpre = fpre; p.df = df; p.I = d->I; p.dx1 = dx1; p.act = d->activation;
+  B4R_CHECK_ARG(d->activation >= 0 && d->activation < B4R_ACT_COUNT, B4R_E_BADARG, "b4r_ffn32w_bwd: unknown activation %d", d->activation);
+  if (d->activation != B4R_ACT_GELU)
+    return d->H == 128 ? f32w_launch_bwd<4, 8, B4R_ACT_ANY>(records_ready ? nullptr : &pk, p, stream)
+                       : f32w_launch_bwd<8, 4, B4R_ACT_ANY>(records_ready ? nullptr : &pk, p, stream);
+  return d->H == 128 ? f32w_launch_bwd<4, 8, B4R_ACT_GELU>(records_ready ? nullptr : &pk, p, stream)
+                     : f32w_launch_bwd<8, 4, B4R_ACT_GELU>(records_ready ? nullptr : &pk, p, stream);
 }
 
 extern "C" int32_t b4r_ffn_wide_supported(int32_t hidden_size, int32_t inner_dim) { return b4r_ffn32w_supported(hidden_size, inner_dim) ? 1 : 0; }

@@ -76,6 +76,7 @@ struct FfnP {
   const int64_t* spos; const int64_t* sids; int sP, sL, n_slots;
   float* dz2c;      // [cap,64] compact dz2 for the weight-gradient kernel
   float* ln2_part;  // [grid][128] gamma / beta partials of the output LayerNorm
+  int act;          // the activation (B4R_ACT_*) of the ACT == B4R_ACT_ANY instantiations
 };
 
 // number of (compact) rows and the actual row of compact index j
@@ -93,6 +94,10 @@ __device__ __forceinline__ int ffn_slot(const FfnP& p, int j) { return p.spos ? 
 // -----------------------------------------------------------------------------------------------------------
 // forward.  LDS: [W1 image 64 KB | W2 image 64 KB | b1]
 // -----------------------------------------------------------------------------------------------------------
+// ACT (all three kernels): B4R_ACT_GELU, or another activation in its place.  The forward is instantiated per id (its run-time
+// switch spills at 128 registers); the input-gradient kernel (8 waves for them: no spill) and the weight-gradient kernel (weight
+// fragments in LDS: no spill) read p.act (B4R_ACT_ANY)
+template <int ACT>
 __global__ __launch_bounds__(64 * FW) void ffn_fwd_kernel(FfnP p) {
   FF_MARK(0);
   extern __shared__ __attribute__((aligned(16))) char smem_ffn[];
@@ -117,7 +122,7 @@ __global__ __launch_bounds__(64 * FW) void ffn_fwd_kernel(FfnP p) {
     const int j = 16 * t + i;
     const int tok = ffn_row(p, min(j, Nn - 1));   // the row in the [N, 64] tensors; pad lanes repeat the last row
     FF_MARK(3);
-    ffn_fwd_tile(tp, w1img, w2img, sb1, lk, dctx, tok, j < Nn, g);
+    ffn_fwd_tile<ACT>(tp, w1img, w2img, sb1, lk, dctx, tok, j < Nn, g, p.act);
     FF_MARK(6);
   }
   FF_MARK(7);
@@ -128,7 +133,7 @@ __global__ __launch_bounds__(64 * FW) void ffn_fwd_kernel(FfnP p) {
 // -----------------------------------------------------------------------------------------------------------
 // NW waves per workgroup: launched with 16 (a 128-register cap, 10 registers spilled).  8 (two waves per SIMD, 256 registers, no spill,
 // a wave walks two 16-token tiles at ML-1M) was measured 3-4 us slower per layer, see the launch site
-template <int NW>
+template <int NW, int ACT>
 __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_bwd_dx_kernel(FfnP p) {
   FF_MARK(10);
   extern __shared__ __attribute__((aligned(16))) char smem_ffn[];
@@ -228,7 +233,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_bwd_dx_kernel(FfnP p) {
           d = mfma3(row_at(s0), row_at(s0 + SUB), gh[ks], gl[ks], d);
         }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) dfp[a][r] = d[r] * b4r_gelu_grad_fast(c[r]);
+        for (int r = 0; r < 4; ++r)
+          dfp[a][r] = d[r] * ((ACT == B4R_ACT_GELU) ? b4r_gelu_grad_fast(c[r]) : b4r_act_grad<true>(p.act, c[r]));
       }
       bf16x8 ph, pl;
       split8(cat(dfp[0], dfp[1]), ph, pl);   // k-slot (g, j) = inner column 32 kt + 8g + j
@@ -322,8 +328,13 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ffn_bwd_dx_kernel(FfnP p) {
 constexpr int CH_TOK = 32;
 constexpr int CH_IMG = CH_TOK * HID * 4;   // hi + lo image of one [32, 64] chunk: 8 KB
 
+// W2_LDS (the B4R_ACT_ANY form): the wave's W2 fragments and the hi halves of its W1 fragments wait in LDS, 48 bytes per lane and
+// ks, instead of 24 registers -- with the run-time switch the register form spilled 7 registers at the 128-register cap
+constexpr int DW_W2_BYTES = FW * 2 * 64 * 48;   // [wave][ks][lane] x (W2 hi 16 B | W2 lo 16 B | W1 hi 16 B): 96 KB
+template <int ACT>
 __global__ __launch_bounds__(64 * FW) void ffn_bwd_dw_kernel(FfnP p) {
-  __shared__ __attribute__((aligned(16))) char smem_dw[4 * CH_IMG];
+  constexpr bool W2_LDS = ACT == B4R_ACT_ANY;
+  __shared__ __attribute__((aligned(16))) char smem_dw[4 * CH_IMG + (W2_LDS ? DW_W2_BYTES : 0)];
   FF_MARK(30);
   const int lane = threadIdx.x & 63, ib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), i = lane & 15, g = lane >> 4;
   const LaneK lk = lane_consts(lane);
@@ -338,6 +349,12 @@ __global__ __launch_bounds__(64 * FW) void ffn_bwd_dw_kernel(FfnP p) {
     for (int j = 0; j < 8; ++j) a[j] = p.W1[(int64_t)(32 * ks + 8 * g + j) * INNER + 16 * ib + i];
     split8(a, w1h[ks], w1l[ks]);
     split8(load8(p.W2 + (int64_t)(16 * ib + i) * HID + 32 * ks + 8 * g), w2h[ks], w2l[ks]);
+    if constexpr (W2_LDS) {   // only this lane reads its slot back
+      char* slot = smem_dw + 4 * CH_IMG + ((ib * 2 + ks) * 64 + lane) * 48;
+      *reinterpret_cast<bf16x8*>(slot) = w2h[ks];
+      *reinterpret_cast<bf16x8*>(slot + 16) = w2l[ks];
+      *reinterpret_cast<bf16x8*>(slot + 32) = w1h[ks];
+    }
   }
   const float b1v = p.b1[16 * ib + i];
 
@@ -395,13 +412,21 @@ __global__ __launch_bounds__(64 * FW) void ffn_bwd_dw_kernel(FfnP p) {
       for (int ks = 0; ks < 2; ++ks) {
         const char* xa = ximg + sub_base(tt, ks, 2) + lk.row;
         const char* ga = gimg + sub_base(tt, ks, 2) + lk.row;
-        pre = mfma3(row_at(xa), row_at(xa + SUB), w1h[ks], w1l[ks], pre);   // fpre[token][inner] = x1.W1 + b1
-        d = mfma3(row_at(ga), row_at(ga + SUB), w2h[ks], w2l[ks], d);       // dF[token][inner] = dG.W2^T
+        const bf16x8 w1hi = W2_LDS ? *reinterpret_cast<const bf16x8*>(smem_dw + 4 * CH_IMG + ((ib * 2 + ks) * 64 + lane) * 48 + 32)
+                                   : w1h[ks];
+        pre = mfma3(row_at(xa), row_at(xa + SUB), w1hi, w1l[ks], pre);     // fpre[token][inner] = x1.W1 + b1
+        if constexpr (W2_LDS) {
+          const char* slot = smem_dw + 4 * CH_IMG + ((ib * 2 + ks) * 64 + lane) * 48;
+          d = mfma3(row_at(ga), row_at(ga + SUB), *reinterpret_cast<const bf16x8*>(slot), *reinterpret_cast<const bf16x8*>(slot + 16), d);
+        } else {
+          d = mfma3(row_at(ga), row_at(ga + SUB), w2h[ks], w2l[ks], d);     // dF[token][inner] = dG.W2^T
+        }
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float gl_, gr_;
-        gelu_both(pre[r], gl_, gr_);
+        if (ACT == B4R_ACT_GELU) gelu_both(pre[r], gl_, gr_);
+        else b4r_act_both<true>(b4r_act_id<ACT>(p.act), pre[r], gl_, gr_);
         f[tt][r] = gl_;
         dfp[tt][r] = d[r] * gr_;
       }
@@ -474,6 +499,7 @@ FfnP make_p(const b4r_ffn_desc* d) {
   p.drop = b4r_make_drop(d->rng, d->drop_stream, d->drop_rate, d->rng != nullptr);
   p.rows = d->rows; p.n_dev = d->n_rows;
   p.spos = d->slot_positions; p.sids = d->slot_ids; p.sP = d->slots_per_seq; p.sL = d->seq_len; p.n_slots = d->max_rows;
+  p.act = d->activation;
   return p;
 }
 
@@ -522,11 +548,18 @@ extern "C" int b4r_ffn_block_fwd(const b4r_ffn_desc* d, b4r_stream_t stream) {
                 "b4r_ffn_block_fwd: rows, n_rows and max_rows go together");
   B4R_CHECK_ARG(slot_mode_ok(d), B4R_E_BADARG,
                 "b4r_ffn_block_fwd: the slot mode needs slot_positions, slot_ids, slots_per_seq, seq_len, max_rows and no explicit list");
+  B4R_CHECK_ARG(d->activation >= 0 && d->activation < B4R_ACT_COUNT, B4R_E_BADARG, "b4r_ffn_block_fwd: unknown activation %d",
+                d->activation);
   const FfnP p = make_p(d);
   const int units = (d->rows || d->slot_positions) ? d->max_rows : d->N;
-  int rc = b4r_raise_lds((const void*)ffn_fwd_kernel, FWD_LDS, "b4r_ffn_block_fwd");
+  int rc = b4r_act_dispatch(d->activation, [&](auto a) {
+    constexpr int ACT = decltype(a)::value;
+    int r = b4r_raise_lds((const void*)ffn_fwd_kernel<ACT>, FWD_LDS, "b4r_ffn_block_fwd");
+    if (r) return r;
+    hipLaunchKernelGGL(ffn_fwd_kernel<ACT>, dim3(ffn_grid(b4r_cdiv(units, 16))), dim3(64 * FW), FWD_LDS, (hipStream_t)stream, p);
+    return (int)B4R_OK;
+  });
   if (rc) return rc;
-  hipLaunchKernelGGL(ffn_fwd_kernel, dim3(ffn_grid(b4r_cdiv(units, 16))), dim3(64 * FW), FWD_LDS, (hipStream_t)stream, p);
   B4R_CHECK_LAUNCH("b4r_ffn_block_fwd");
   return B4R_OK;
 }
@@ -552,6 +585,9 @@ extern "C" int b4r_ffn_block_bwd(const b4r_ffn_desc* d, b4r_stream_t stream) {
   B4R_CHECK_ARG(al16(d->x1) && al16(d->W1) && al16(d->W2) && al16(d->dz2) && al16(d->z1) && al16(d->ln1_gamma) && al16(d->dz1) &&
                     al16(d->scratch),
                 B4R_E_ALIGN, "b4r_ffn_block_bwd: operands must be 16-byte aligned");
+  B4R_CHECK_ARG(d->activation >= 0 && d->activation < B4R_ACT_COUNT, B4R_E_BADARG, "b4r_ffn_block_bwd: unknown activation %d",
+                d->activation);
+  const bool gelu = d->activation == B4R_ACT_GELU;
   FfnP p = make_p(d);
   hipStream_t s = (hipStream_t)stream;
   const int units = rowmode ? d->max_rows : d->N;
@@ -568,11 +604,15 @@ extern "C" int b4r_ffn_block_bwd(const b4r_ffn_desc* d, b4r_stream_t stream) {
   if (rowmode) { p.slotof = d->row_slot; p.dgr = d->slot_grad; p.dz2c = d->dz2_rows; }
   // measured (tools/bench_ffn.py, same box, dx + dw + reductions): 16 waves 81.2 / 81.4 us, 8 waves 84.0 / 85.7 us -- the spill-free
   // 256-register form loses more latency hiding (two waves per SIMD instead of four) than the 10 spilled registers cost
-  int rc = b4r_raise_lds((const void*)ffn_bwd_dx_kernel<16>, DX_LDS, "b4r_ffn_block_bwd");
+  // The other activations take the 8-wave form: at 16 waves the run-time switch would spill further
+  int rc = gelu ? b4r_raise_lds((const void*)ffn_bwd_dx_kernel<16, B4R_ACT_GELU>, DX_LDS, "b4r_ffn_block_bwd")
+                : b4r_raise_lds((const void*)ffn_bwd_dx_kernel<8, B4R_ACT_ANY>, DX_LDS, "b4r_ffn_block_bwd");
   if (rc) return rc;
-  hipLaunchKernelGGL(ffn_bwd_dx_kernel<16>, dim3(gdx), dim3(64 * 16), DX_LDS, s, p);
+  if (gelu) hipLaunchKernelGGL((ffn_bwd_dx_kernel<16, B4R_ACT_GELU>), dim3(gdx), dim3(64 * 16), DX_LDS, s, p);
+  else hipLaunchKernelGGL((ffn_bwd_dx_kernel<8, B4R_ACT_ANY>), dim3(gdx), dim3(64 * 8), DX_LDS, s, p);
   B4R_CHECK_LAUNCH("b4r_ffn_block_bwd (dx)");
-  hipLaunchKernelGGL(ffn_bwd_dw_kernel, dim3(gdw), dim3(64 * FW), 0, s, p);
+  if (gelu) hipLaunchKernelGGL(ffn_bwd_dw_kernel<B4R_ACT_GELU>, dim3(gdw), dim3(64 * FW), 0, s, p);
+  else hipLaunchKernelGGL(ffn_bwd_dw_kernel<B4R_ACT_ANY>, dim3(gdw), dim3(64 * FW), 0, s, p);
   B4R_CHECK_LAUNCH("b4r_ffn_block_bwd (dw)");
   // ordered sums over the workgroups (queued when the caller collects its reductions into one launch)
   rc = b4r_launch_slab_reduce_full(p.slab_w1, gdw, HID, INNER, d->dW1, INNER, 0, p.slab_b1, d->db1, nullptr, nullptr, s);

@@ -29,7 +29,10 @@ struct GemmP {
   int a_vec, b_vec;
   float qscale; int qcols;
   DropArgs drop;
+  int act;   // EPI_BIAS_ACT / EPI_ACT_BWD: the activation (B4R_ACT_*)
 };
+// internal: B4R_EPI_BIAS_GELU / B4R_EPI_GELU_BWD with another activation than the GELU (p.act, read at run time)
+constexpr int EPI_BIAS_ACT = 12, EPI_ACT_BWD = 13;
 
 __device__ __forceinline__ f32x4 load4_guard(const float* base, int64_t off, int n_valid, bool vec) {
   // n_valid: how many of the 4 consecutive elements are in range (<=0: none)
@@ -157,7 +160,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
     if (col >= p.N) continue;
     float bv = 0.f;
     if (EPI == B4R_EPI_BIAS || EPI == B4R_EPI_BIAS_QSCALE || EPI == B4R_EPI_BIAS_GELU || EPI == B4R_EPI_BIAS_DROP_RES ||
-        EPI == B4R_EPI_BIAS_TANH)
+        EPI == B4R_EPI_BIAS_TANH || EPI == EPI_BIAS_ACT)
       bv = p.bias[col];
     const float qs = (EPI == B4R_EPI_BIAS_QSCALE && col < p.qcols) ? p.qscale : 1.0f;
 #pragma unroll
@@ -176,12 +179,18 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
         const float pre = v + bv;
         p.C2[(int64_t)row * p.ldc2 + col] = pre;
         p.C[co] = b4r_gelu(pre);
+      } else if (EPI == EPI_BIAS_ACT) {
+        const float pre = v + bv;
+        p.C2[(int64_t)row * p.ldc2 + col] = pre;
+        p.C[co] = b4r_act_val<false>(p.act, pre);
       } else if (EPI == B4R_EPI_BIAS_DROP_RES) {
         float y = v + bv;
         y = b4r_drop(dctx, y, (uint64_t)row * (uint64_t)p.N + (uint64_t)col);
         p.C[co] = p.R[(int64_t)row * p.ldr + col] + y;
       } else if (EPI == B4R_EPI_GELU_BWD) {
         p.C[co] = v * b4r_gelu_grad(p.R[(int64_t)row * p.ldr + col]);
+      } else if (EPI == EPI_ACT_BWD) {
+        p.C[co] = v * b4r_act_grad<false>(p.act, p.R[(int64_t)row * p.ldr + col]);
       } else if (EPI == B4R_EPI_ADD_RES) {
         p.C[co] = v + p.R[(int64_t)row * p.ldr + col];
       } else if (EPI == B4R_EPI_BIAS_TANH) {
@@ -473,9 +482,15 @@ int dispatch_epi(const GemmP& p, int epi, int a_drop, dim3 grid, hipStream_t s) 
     case B4R_EPI_NONE: launch_gemm<B_NK, B4R_EPI_NONE>(p, a_drop, grid, s); break;
     case B4R_EPI_BIAS: launch_gemm<B_NK, B4R_EPI_BIAS>(p, a_drop, grid, s); break;
     case B4R_EPI_BIAS_QSCALE: launch_gemm<B_NK, B4R_EPI_BIAS_QSCALE>(p, a_drop, grid, s); break;
-    case B4R_EPI_BIAS_GELU: launch_gemm<B_NK, B4R_EPI_BIAS_GELU>(p, a_drop, grid, s); break;
+    case B4R_EPI_BIAS_GELU:
+      if (p.act != B4R_ACT_GELU) launch_gemm<B_NK, EPI_BIAS_ACT>(p, a_drop, grid, s);
+      else launch_gemm<B_NK, B4R_EPI_BIAS_GELU>(p, a_drop, grid, s);
+      break;
     case B4R_EPI_BIAS_DROP_RES: launch_gemm<B_NK, B4R_EPI_BIAS_DROP_RES>(p, a_drop, grid, s); break;
-    case B4R_EPI_GELU_BWD: launch_gemm<B_NK, B4R_EPI_GELU_BWD>(p, a_drop, grid, s); break;
+    case B4R_EPI_GELU_BWD:
+      if (p.act != B4R_ACT_GELU) launch_gemm<B_NK, EPI_ACT_BWD>(p, a_drop, grid, s);
+      else launch_gemm<B_NK, B4R_EPI_GELU_BWD>(p, a_drop, grid, s);
+      break;
     case B4R_EPI_ADD_RES: launch_gemm<B_NK, B4R_EPI_ADD_RES>(p, a_drop, grid, s); break;
     case B4R_EPI_BIAS_TANH: launch_gemm<B_NK, B4R_EPI_BIAS_TANH>(p, a_drop, grid, s); break;
     default: b4r_set_error("b4r_gemm_f32: unknown epilogue %d", epi); return B4R_E_BADARG;
@@ -628,6 +643,8 @@ extern "C" int b4r_gemm_f32(const b4r_gemm_desc* d, b4r_stream_t stream) {
   B4R_CHECK_ARG(!needs_r || (d->R && d->ldr >= d->N), B4R_E_BADARG, "b4r_gemm_f32: epilogue %d needs R", epi);
   B4R_CHECK_ARG(epi != B4R_EPI_BIAS_GELU || (d->C2 && d->ldc2 >= d->N), B4R_E_BADARG, "b4r_gemm_f32: BIAS_GELU needs C2");
   B4R_CHECK_ARG(epi >= B4R_EPI_NONE && epi <= B4R_EPI_BIAS_GELU_LN, B4R_E_BADARG, "b4r_gemm_f32: unknown epilogue %d", epi);
+  B4R_CHECK_ARG(d->activation >= 0 && d->activation < B4R_ACT_COUNT, B4R_E_BADARG, "b4r_gemm_f32: unknown activation %d",
+                d->activation);
   B4R_CHECK_ARG(d->a_gather_idx == nullptr || (epi == B4R_EPI_BIAS_GELU_LN && d->a_gather_add_per > 0 && d->a_gather_per > 0),
                 B4R_E_BADARG, "b4r_gemm_f32: a_gather_idx only with B4R_EPI_BIAS_GELU_LN (and a_gather_add_per, a_gather_per > 0)");
   B4R_CHECK_ARG(d->a_copy == nullptr || (d->a_gather_idx != nullptr && d->a_copy_ld >= d->K && d->a_copy_ld % 4 == 0 &&
@@ -672,6 +689,7 @@ extern "C" int b4r_gemm_f32(const b4r_gemm_desc* d, b4r_stream_t stream) {
   p.b_vec = (b4r_aligned16(d->B) && (d->ldb % 4 == 0)) ? 1 : 0;
   p.qscale = d->qscale; p.qcols = d->qcols;
   p.drop = b4r_make_drop(d->rng, d->drop_stream, d->drop_rate, 1);
+  p.act = d->activation;
   const int a_drop = (d->a_dropout && p.drop.rng != nullptr) ? 1 : 0;
   const int64_t tiles = (int64_t)b4r_cdiv(d->M, BM) * p.tiles_n;
   B4R_CHECK_ARG(tiles < 2147483647LL, B4R_E_SHAPE, "b4r_gemm_f32: too many tiles");
@@ -708,6 +726,7 @@ int b4r_gemm_f32_splitk(const b4r_gemm_desc* d, int splits, float* scratch, int 
   p.b_vec = (b4r_aligned16(d->B) && (d->ldb % 4 == 0)) ? 1 : 0;
   p.qscale = 1.f; p.qcols = 0;
   p.drop = b4r_make_drop(nullptr, 0, 0.f, 0);
+  p.act = B4R_ACT_GELU;
   const int64_t tiles = (int64_t)b4r_cdiv(d->M, BM) * p.tiles_n;
   dim3 grid((unsigned)tiles, (unsigned)splits);
   if (d->b_is_nk)
@@ -738,6 +757,8 @@ extern "C" int b4r_gemm_tn_f32(const b4r_gemm_tn_desc* d, float* scratch, b4r_st
   B4R_CHECK_ARG(d->R > 0 && d->Mo > 0 && d->No > 0, B4R_E_SHAPE, "b4r_gemm_tn_f32: bad shape");
   B4R_CHECK_ARG(d->lda >= d->Mo && d->ldb >= d->No && d->ldo >= d->No, B4R_E_SHAPE, "b4r_gemm_tn_f32: bad leading dimension");
   b4r_timing_detail("R=%d Mo=%d No=%d%s", d->R, d->Mo, d->No, d->dgrad_out ? " +dgrad" : "");
+  B4R_CHECK_ARG(d->activation >= 0 && d->activation < B4R_ACT_COUNT, B4R_E_BADARG, "b4r_gemm_tn_f32: unknown activation %d",
+                d->activation);
   if (d->dgrad_out != nullptr) {
     B4R_CHECK_ARG(d->dgrad_w != nullptr, B4R_E_BADARG, "b4r_gemm_tn_f32: dgrad_out needs dgrad_w");
     B4R_CHECK_ARG(b4r_gemm_tn_dgrad_supported(d), B4R_E_SHAPE,

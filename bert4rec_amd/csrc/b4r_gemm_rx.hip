@@ -67,6 +67,7 @@ struct RxP {
   // clamp(a_idx[m], 0, a_add_per - 1) + (m / a_per) * a_add_per of A, as b4r_gather_rows does; a_copy [M, a_copy_ld] (optional)
   // receives the gathered rows (the weight-gradient product of the backward pass reads them again)
   const int64_t* a_idx; int64_t a_add_per; int a_per; float* a_copy; int a_copy_ld;
+  int act;   // EPI_BIAS_ACT / EPI_ACT_BWD / EPI_BIAS_ACT_LN: the activation (B4R_ACT_*)
 };
 
 __device__ __forceinline__ void split8(const f32x8 x, bf16x8& hi, bf16x8& lo) { b4r_split8(x, hi, lo); }
@@ -112,12 +113,14 @@ __device__ __forceinline__ int xcd_logical_id(int id, int n) {
 inline unsigned xcd_grid(int64_t n) { return (unsigned)(((n + 7) >> 3) << 3); }
 
 constexpr int EPI_ADD_RES_LN_BWD_EMBED = 11;   // internal: B4R_EPI_ADD_RES_LN_BWD with ln_ids set
+// internal: B4R_EPI_BIAS_GELU / B4R_EPI_GELU_BWD / B4R_EPI_BIAS_GELU_LN with another activation than the GELU (p.act, read at run time)
+constexpr int EPI_BIAS_ACT = 12, EPI_ACT_BWD = 13, EPI_BIAS_ACT_LN = 14;
 constexpr bool epi_has_bias(int e) {
   return e == B4R_EPI_BIAS || e == B4R_EPI_BIAS_QSCALE || e == B4R_EPI_BIAS_GELU || e == B4R_EPI_BIAS_DROP_RES ||
-         e == B4R_EPI_BIAS_TANH || e == B4R_EPI_BIAS_DROP_RES_LN || e == B4R_EPI_BIAS_GELU_LN;
+         e == B4R_EPI_BIAS_TANH || e == B4R_EPI_BIAS_DROP_RES_LN || e == B4R_EPI_BIAS_GELU_LN || e == EPI_BIAS_ACT || e == EPI_BIAS_ACT_LN;
 }
 constexpr bool epi_has_r(int e) {
-  return e == B4R_EPI_BIAS_DROP_RES || e == B4R_EPI_GELU_BWD || e == B4R_EPI_ADD_RES || e == B4R_EPI_BIAS_DROP_RES_LN ||
+  return e == B4R_EPI_BIAS_DROP_RES || e == B4R_EPI_GELU_BWD || e == EPI_ACT_BWD || e == B4R_EPI_ADD_RES || e == B4R_EPI_BIAS_DROP_RES_LN ||
          e == B4R_EPI_ADD_RES_LN_BWD || e == EPI_ADD_RES_LN_BWD_EMBED;
 }
 
@@ -187,14 +190,16 @@ __device__ __forceinline__ void epilogue_tile(const RxP& p, const DropCtx& dctx,
       else if (EPI == B4R_EPI_BIAS) y = a + bv[e];
       else if (EPI == B4R_EPI_BIAS_QSCALE) y = (a + bv[e]) * ((col + e < p.qcols) ? p.qscale : 1.0f);
       else if (EPI == B4R_EPI_BIAS_GELU) { o2[e] = a + bv[e]; y = b4r_gelu_fast(o2[e]); }
+      else if (EPI == EPI_BIAS_ACT) { o2[e] = a + bv[e]; y = b4r_act_val<true>(p.act, o2[e]); }
       else if (EPI == B4R_EPI_BIAS_DROP_RES) y = rr[i][e] + dz[e];
       else if (EPI == B4R_EPI_GELU_BWD) y = a * b4r_gelu_grad_fast(rr[i][e]);
+      else if (EPI == EPI_ACT_BWD) y = a * b4r_act_grad<true>(p.act, rr[i][e]);
       else if (EPI == B4R_EPI_ADD_RES) y = a + rr[i][e];
       else y = tanhf(a + bv[e]);
       o[e] = y;
     }
     *reinterpret_cast<f32x4*>(p.C + (int64_t)row * p.ldc + col) = o;
-    if (EPI == B4R_EPI_BIAS_GELU) *reinterpret_cast<f32x4*>(p.C2 + (int64_t)row * p.ldc2 + col) = o2;
+    if (EPI == B4R_EPI_BIAS_GELU || EPI == EPI_BIAS_ACT) *reinterpret_cast<f32x4*>(p.C2 + (int64_t)row * p.ldc2 + col) = o2;
   }
 }
 
@@ -204,8 +209,9 @@ __device__ __forceinline__ void epilogue_tile(const RxP& p, const DropCtx& dctx,
 // lanes that share the row, the two waves of a row exchange them through their (now idle) staging areas and merge them
 // (Chan et al.: M2 = M2a + M2b + (ma - mb)^2 n/2 with n = 32 per half), so the variance is a two-pass one like the stand-alone
 // kernel's.  `live` = the quarter's rows exist (M % 32 == 0, so a quarter is whole or absent); every wave takes the barrier.
-// GELU: B4R_EPI_BIAS_GELU_LN instead -- z = gelu(acc + bias) (-> C), the pre-activation goes to C3, no residual / dropout
-template <bool GELU>
+// GELU: B4R_EPI_BIAS_GELU_LN instead -- z = gelu(acc + bias) (-> C), the pre-activation goes to C3, no residual / dropout;
+// with ANY (EPI_BIAS_ACT_LN) z = f(acc + bias) of the activation p.act
+template <bool GELU, bool ANY = false>
 __device__ __forceinline__ void epilogue_tile_ln(const RxP& p, const DropCtx& dctx, const f32x16& acc, const f32x4 bv,
                                                  const RTile& rt, float* stage, float* stage_other, int m0, int n0, int lane,
                                                  bool live) {
@@ -227,7 +233,7 @@ __device__ __forceinline__ void epilogue_tile_ln(const RxP& p, const DropCtx& dc
       if (GELU) {
         const f32x4 pre = vin[i] + bv;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) z[i][e] = b4r_gelu_fast(pre[e]);
+        for (int e = 0; e < 4; ++e) z[i][e] = ANY ? b4r_act_val<true>(p.act, pre[e]) : b4r_gelu_fast(pre[e]);
         *reinterpret_cast<f32x4*>(p.C3 + (int64_t)row * p.ldc3 + col) = pre;
       } else {
         z[i] = rt.v[i] + b4r_drop4(dctx, vin[i] + bv, (uint64_t)row * (uint64_t)p.N + (uint64_t)col);
@@ -803,15 +809,15 @@ __global__ __launch_bounds__(256, 2) void rx_gemm_wide_kernel(RxP p) {   // two 
     for (int c = 0; c < nchunks; ++c) step(q0, c);
   }
   const int c4 = (lane & 7) * 4;
-  if constexpr (EPI == B4R_EPI_BIAS_DROP_RES_LN || EPI == B4R_EPI_BIAS_GELU_LN) {
+  if constexpr (EPI == B4R_EPI_BIAS_DROP_RES_LN || EPI == B4R_EPI_BIAS_GELU_LN || EPI == EPI_BIAS_ACT_LN) {
     static_assert(TM == 64 && TN == 64, "the LayerNorm epilogue needs whole rows in one workgroup");
     const int ms = m0 + 32 * wm, ns = 32 * wn;   // N == 64: n0 == 0
     const bool live = ms < p.M;
     RTile rt;
     if (live) rt = load_r_tile<EPI>(p, ms, ns, lane);
     float* stage_other = reinterpret_cast<float*>(s_w + A_BYTES + B_BYTES) + (wave ^ 1) * (32 * ST_LD);
-    epilogue_tile_ln<EPI == B4R_EPI_BIAS_GELU_LN>(p, dctx, acc[0][0], load_bias4<EPI>(p, ns, c4), rt, stage, stage_other, ms, ns,
-                                                  lane, live);
+    epilogue_tile_ln<EPI == B4R_EPI_BIAS_GELU_LN || EPI == EPI_BIAS_ACT_LN, EPI == EPI_BIAS_ACT_LN>(
+        p, dctx, acc[0][0], load_bias4<EPI>(p, ns, c4), rt, stage, stage_other, ms, ns, lane, live);
   } else if constexpr (EPI == B4R_EPI_ADD_RES_LN_BWD || EPI == EPI_ADD_RES_LN_BWD_EMBED) {
     static_assert(TM == 64 && TN == 64, "the LayerNorm epilogue needs whole rows in one workgroup");
     const int ms = m0 + 32 * wm, ns = 32 * wn;
@@ -907,7 +913,8 @@ int dispatch_rx(const RxP& p, int epi, bool a_drop, dim3 grid, hipStream_t s) {
     return B4R_OK;
   }
   if (epi == B4R_EPI_BIAS_GELU_LN) {
-    launch_wide<false, B4R_EPI_BIAS_GELU_LN, false, 64>(p, s);
+    if (p.act != B4R_ACT_GELU) launch_wide<false, EPI_BIAS_ACT_LN, false, 64>(p, s);
+    else launch_wide<false, B4R_EPI_BIAS_GELU_LN, false, 64>(p, s);
     return B4R_OK;
   }
   if (epi == B4R_EPI_ADD_RES_LN_BWD) {     // N == 64, B as [N,K]
@@ -919,9 +926,15 @@ int dispatch_rx(const RxP& p, int epi, bool a_drop, dim3 grid, hipStream_t s) {
     case B4R_EPI_NONE: launch_rx<B_NK, B4R_EPI_NONE>(p, a_drop, grid, s); break;
     case B4R_EPI_BIAS: launch_rx<B_NK, B4R_EPI_BIAS>(p, a_drop, grid, s); break;
     case B4R_EPI_BIAS_QSCALE: launch_rx<B_NK, B4R_EPI_BIAS_QSCALE>(p, a_drop, grid, s); break;
-    case B4R_EPI_BIAS_GELU: launch_rx<B_NK, B4R_EPI_BIAS_GELU>(p, a_drop, grid, s); break;
+    case B4R_EPI_BIAS_GELU:
+      if (p.act != B4R_ACT_GELU) launch_rx<B_NK, EPI_BIAS_ACT>(p, a_drop, grid, s);
+      else launch_rx<B_NK, B4R_EPI_BIAS_GELU>(p, a_drop, grid, s);
+      break;
     case B4R_EPI_BIAS_DROP_RES: launch_rx<B_NK, B4R_EPI_BIAS_DROP_RES>(p, a_drop, grid, s); break;
-    case B4R_EPI_GELU_BWD: launch_rx<B_NK, B4R_EPI_GELU_BWD>(p, a_drop, grid, s); break;
+    case B4R_EPI_GELU_BWD:
+      if (p.act != B4R_ACT_GELU) launch_rx<B_NK, EPI_ACT_BWD>(p, a_drop, grid, s);
+      else launch_rx<B_NK, B4R_EPI_GELU_BWD>(p, a_drop, grid, s);
+      break;
     case B4R_EPI_ADD_RES: launch_rx<B_NK, B4R_EPI_ADD_RES>(p, a_drop, grid, s); break;
     case B4R_EPI_BIAS_TANH: launch_rx<B_NK, B4R_EPI_BIAS_TANH>(p, a_drop, grid, s); break;
     default: b4r_set_error("gemm: unknown epilogue %d", epi); return B4R_E_BADARG;
@@ -948,8 +961,10 @@ struct RxTnP {
   int tiles_i, tiles_j, S, chunk;  // chunk: rows per slice
   DropArgs drop;
   // DGRAD (No = 64, Mo a multiple of 64): dX[R, Mo] = dropout(B) . W^T with W [Mo, ldw] the weight whose gradient `out` is; the
-  // workgroup of output tile ti forms columns 64 ti .. of dX.  DGRAD == 2: dX is further multiplied by gelu'(G) (G [R, ldg])
+  // workgroup of output tile ti forms columns 64 ti .. of dX.  DGRAD == 2: dX is further multiplied by gelu'(G) (G [R, ldg]),
+  // DGRAD == 3: by f'(G) of the activation `act`
   const float* W; float* dX; const float* G; int ldw, lddx, ldg;
+  int act;
 };
 
 
@@ -1042,7 +1057,7 @@ __device__ __forceinline__ void rx_gemm_tn_body(const RxTnP& p, const int block)
     f32x16 dx, gp;
 #pragma unroll
     for (int i = 0; i < 16; ++i) dx[i] = 0.f;
-    if (DGRAD == 2) {   // the pre-activations travel while the products run (rows clamped, stores guarded)
+    if (DGRAD >= 2) {   // the pre-activations travel while the products run (rows clamped, stores guarded)
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
         const int row = min(k0 + 32 * wm + (reg & 3) + 8 * (reg >> 2) + 4 * h, p.R - 1);
@@ -1059,6 +1074,7 @@ __device__ __forceinline__ void rx_gemm_tn_body(const RxTnP& p, const int block)
       const int row = k0 + 32 * wm + (reg & 3) + 8 * (reg >> 2) + 4 * h;
       float v = dx[reg];
       if (DGRAD == 2) v *= b4r_gelu_grad_fast(gp[reg]);
+      if (DGRAD == 3) v *= b4r_act_grad<true>(p.act, gp[reg]);
       if (row < r_end) p.dX[(int64_t)row * p.lddx + i0 + 32 * wn + r] = v;
     }
   };
@@ -1334,6 +1350,7 @@ int b4r_gemm_rx_launch(const b4r_gemm_desc* d, hipStream_t stream) {
   p.C3 = d->C3; p.ldc3 = d->ldc3;
   p.a_idx = d->a_gather_idx; p.a_add_per = d->a_gather_add_per; p.a_per = d->a_gather_per > 0 ? d->a_gather_per : 1;
   p.a_copy = d->a_copy; p.a_copy_ld = d->a_copy_ld;
+  p.act = d->activation;
   p.drop = b4r_make_drop(d->rng, d->drop_stream, d->drop_rate, 1);
   p.k_chunks_per_split = d->K / 64 > 0 ? d->K / 64 : 1; p.slab_stride = 0;
   const bool a_drop = d->a_dropout && p.drop.rng != nullptr;
@@ -1413,6 +1430,7 @@ static RxTnP make_tn_params(const b4r_gemm_tn_desc* d, float* scratch, int S) {
   p.colsum_a_slab = d->colsum_a ? scratch + (int64_t)S * d->Mo * d->No + (int64_t)S * d->No : nullptr;
   p.drop = b4r_make_drop(d->rng, d->drop_stream, d->drop_rate, 1);
   p.W = d->dgrad_w; p.ldw = d->dgrad_ldw; p.dX = d->dgrad_out; p.lddx = d->dgrad_ldo; p.G = d->dgrad_gelu_pre; p.ldg = d->dgrad_ldg;
+  p.act = d->activation;
   return p;
 }
 
@@ -1420,7 +1438,8 @@ int b4r_gemm_rx_tn_launch(const b4r_gemm_tn_desc* d, float* scratch, hipStream_t
   const int S = rx_tn_split(d->R, d->Mo, d->No);
   const RxTnP p = make_tn_params(d, scratch, S);
   const bool b_drop = d->b_dropout && p.drop.rng != nullptr;
-  const int dgrad = d->dgrad_out == nullptr ? 0 : (d->dgrad_gelu_pre ? 2 : 1);   // b4r_gemm_tn_f32 has checked the shape contract
+  // b4r_gemm_tn_f32 has checked the shape contract and the activation
+  const int dgrad = d->dgrad_out == nullptr ? 0 : !d->dgrad_gelu_pre ? 1 : d->activation != B4R_ACT_GELU ? 3 : 2;
   const int64_t items = (int64_t)p.tiles_i * p.tiles_j * S;
   dim3 grid(xcd_grid(items));
   if (dgrad == 0 && tn_wide_tiles(d->Mo, d->No)) {
@@ -1440,10 +1459,13 @@ int b4r_gemm_rx_tn_launch(const b4r_gemm_tn_desc* d, float* scratch, hipStream_t
     (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     lds_raised = true;
   }
 #define B4R_TN_LAUNCH(BD, DG) hipLaunchKernelGGL((rx_gemm_tn_kernel<TN_KS, BD, DG>), grid, dim3(256), lds, stream, p)
-  if (dgrad == 2) { if (b_drop) B4R_TN_LAUNCH(true, 2); else B4R_TN_LAUNCH(false, 2); }
+  if (dgrad == 3) { if (b_drop) B4R_TN_LAUNCH(true, 3); else B4R_TN_LAUNCH(false, 3); }
+  else if (dgrad == 2) { if (b_drop) B4R_TN_LAUNCH(true, 2); else B4R_TN_LAUNCH(false, 2); }
   else if (dgrad == 1) { if (b_drop) B4R_TN_LAUNCH(true, 1); else B4R_TN_LAUNCH(false, 1); }
   else if (b_drop) B4R_TN_LAUNCH(true, 0);
   else B4R_TN_LAUNCH(false, 0);

@@ -19,7 +19,7 @@
 int b4r_ln_bwd_launch(const float* dy, const float* z, const float* mean, const float* rstd, const float* gamma,
                       int rows, int H, float* dz, float* dgamma, float* dbeta, float* scratch, const int64_t* ids,
                       const float* table, const float* pos_table, int L, int V, DropArgs drop, hipStream_t stream,
-                      const float* gelu_pre = nullptr, const B4rHeadMerge* merge = nullptr);
+                      const float* gelu_pre = nullptr, const B4rHeadMerge* merge = nullptr, int act = B4R_ACT_GELU);
 int b4r_scatter_add_rows_impl(const float* src, const int64_t* idx, int64_t idx_add_per, int per, int n, int H,
                               float* dst, int dst_ld, const int64_t* skip_if_zero, int64_t dst_rows, int hot_rows,
                               float* hot_scratch, hipStream_t stream);
@@ -197,6 +197,7 @@ int check_cfg(const b4r_model_config* c) {
 // the unfactorised model).  The classic entry points reach the same code through b4r_model_config_ex with embedding_width = 0.
 struct ModelCfg : b4r_model_config {
   int E;
+  int act_inner, act_mlm;   // the feed-forward blocks' and the masked-LM transform's activations (B4R_ACT_*)
   bool factorised() const { return E != hidden_size; }
 };
 
@@ -206,17 +207,24 @@ b4r_model_config_ex classic_ex(const b4r_model_config* c) {
   return x;
 }
 
-// validates the extended config and resolves E; a bad width or a nonzero reserved word is an error, never a fault
+// validates the extended config and resolves E and the activations; a bad width, a bad activations word or a nonzero reserved word is
+// an error, never a fault
 int resolve_cfg(const b4r_model_config_ex* x, ModelCfg* out) {
   B4R_CHECK_ARG(x != nullptr, B4R_E_BADARG, "null model config");
   RC(check_cfg(&x->base));
-  B4R_CHECK_ARG(x->reserved[0] == 0 && x->reserved[1] == 0 && x->reserved[2] == 0, B4R_E_BADARG,
+  B4R_CHECK_ARG(x->reserved[0] == 0 && x->reserved[2] == 0, B4R_E_BADARG,
                 "b4r_model_config_ex: reserved words must be zero");
+  const uint32_t acts = (uint32_t)x->reserved[1];
+  const int act_inner = (int)(acts & 0xFFu), act_mlm = (int)((acts >> 8) & 0xFFu);
+  B4R_CHECK_ARG((acts >> 16) == 0 && act_inner < B4R_ACT_COUNT && act_mlm < B4R_ACT_COUNT, B4R_E_BADARG,
+                "b4r_model_config_ex: activations word (reserved[1]) 0x%x: bits 0-7 and 8-15 must be activation ids below %d, the "
+                "other bits zero", acts, (int)B4R_ACT_COUNT);
   const int H = x->base.hidden_size, E = x->embedding_width;
   B4R_CHECK_ARG(E == 0 || E == H || ((E == 64 || E == 128 || E == 256) && E < H && b4r_embed_proj_supported(E, H)), B4R_E_SHAPE,
                 "embedding_width %d not supported with hidden_size %d (0, hidden_size, or 64 / 128 / 256 below hidden_size)", E, H);
   static_cast<b4r_model_config&>(*out) = x->base;
   out->E = (E == 0) ? H : E;
+  out->act_inner = act_inner; out->act_mlm = act_mlm;
   return B4R_OK;
 }
 
@@ -426,7 +434,8 @@ int transform_fwd(const b4r_gemm_desc& d, float* gath, hipStream_t s) {
   if (b4r_gemm_ln_supported(&d)) return gemm_f32(d, s);
   RC(b4r_gather_rows(d.A, d.lda, d.a_gather_idx, d.a_gather_add_per, d.a_gather_per, d.M, d.K, gath, s));
   RC(gemm_f32({.A = gath, .lda = d.K, .B = d.B, .ldb = d.ldb, .C = d.C, .ldc = d.ldc, .M = d.M, .N = d.N, .K = d.K,
-               .epilogue = B4R_EPI_BIAS_GELU, .bias = d.bias, .C2 = d.C3, .ldc2 = d.ldc3, .qscale = 1.f, .c_pad_scratch = 1}, s));
+               .epilogue = B4R_EPI_BIAS_GELU, .bias = d.bias, .C2 = d.C3, .ldc2 = d.ldc3, .qscale = 1.f, .c_pad_scratch = 1,
+               .activation = d.activation}, s));
   return b4r_ln_fwd(d.C, d.M, d.N, d.ln_gamma, d.ln_beta, d.ln_eps, d.C2, d.ln_mean, d.ln_rstd, s);
 }
 
@@ -565,6 +574,7 @@ b4r_ffn_desc ffn_desc(const Step& c, int i) {
   fd.N = c.N; fd.H = c.H; fd.I = c.I;
   fd.W1 = c.prm(c.pl.w1[i]); fd.b1 = c.prm(c.pl.b1[i]); fd.W2 = c.prm(c.pl.w2[i]); fd.b2 = c.prm(c.pl.b2[i]);
   fd.rng = c.od > 0.f ? c.rng : nullptr; fd.drop_stream = B4R_STREAM_FFN_OUT(i); fd.drop_rate = c.od;
+  fd.activation = c.cfg.act_inner;
   return fd;
 }
 // ... and of its forward forms: the output LayerNorm and the outputs
@@ -863,7 +873,7 @@ int ffn_fwd_compact(const Step& c, int i) {
                             c.at(cr.z1c), c.at(cr.mean1c), c.at(cr.rstd1c), c.s));
   RC(gemm_f32({.A = c.at(cr.x1c), .lda = c.H, .B = c.prm(pl.w1[i]), .ldb = c.I, .C = c.at(w.f[i]), .ldc = c.I, .M = c.M, .N = c.I,
                .K = c.H, .epilogue = B4R_EPI_BIAS_GELU, .bias = c.prm(pl.b1[i]), .C2 = c.at(w.fpre[i]), .ldc2 = c.I, .qscale = 1.f,
-               .c_pad_scratch = 1}, c.s));
+               .c_pad_scratch = 1, .activation = c.cfg.act_inner}, c.s));
   RC(gemm_f32({.A = c.at(w.f[i]), .lda = c.I, .B = c.prm(pl.w2[i]), .ldb = c.H, .C = c.at(cr.yc), .ldc = c.H, .M = c.M, .N = c.H,
                .K = c.I, .epilogue = B4R_EPI_BIAS, .bias = c.prm(pl.b2[i]), .qscale = 1.f, .c_pad_scratch = 1}, c.s));
   return b4r_slot_rows_tail(c.at(cr.yc), c.at(cr.x1c), pos, c.L, c.P, c.M, c.H, c.prm(pl.ln2_g[i]), c.prm(pl.ln2_b[i]), c.cfg.ln_eps,
@@ -885,7 +895,7 @@ int ffn_fwd_tiles(const Step& c, int i) {
   const ParamLayout& pl = c.pl; const WsLayout& w = c.w;
   RC(gemm_f32({.A = c.at(w.x1[i]), .lda = c.H, .B = c.prm(pl.w1[i]), .ldb = c.I, .C = c.at(w.f[i]), .ldc = c.I, .M = c.N, .N = c.I,
                .K = c.H, .epilogue = B4R_EPI_BIAS_GELU, .bias = c.prm(pl.b1[i]), .C2 = c.at(w.fpre[i]), .ldc2 = c.I, .qscale = 1.f,
-               .c_pad_scratch = 1}, c.s));
+               .c_pad_scratch = 1, .activation = c.cfg.act_inner}, c.s));
   return dense_res_ln(c.at(w.f[i]), c.I, c.prm(pl.w2[i]), c.at(w.z2[i]), c.at(w.x2[i]), c.at(w.mean2[i]), c.at(w.rstd2[i]), c.N, c.H,
                       c.I, c.prm(pl.b2[i]), c.at(w.x1[i]), c.prm(pl.ln2_g[i]), c.prm(pl.ln2_b[i]), c.cfg.ln_eps, c.rng,
                       B4R_STREAM_FFN_OUT(i), c.od, c.s);
@@ -900,7 +910,8 @@ int head_fwd(const Step& c, const float* x) {
                     .c_pad_scratch = 1, .ln_gamma = c.prm(pl.lnm_g), .ln_beta = c.prm(pl.lnm_b), .ln_mean = c.at(w.meanm),
                     .ln_rstd = c.at(w.rstdm), .ln_eps = c.cfg.ln_eps, .C3 = c.at(w.upre), .ldc3 = c.E,
                     .a_gather_idx = c.batch.masked_lm_positions, .a_gather_add_per = c.L, .a_gather_per = c.P,
-                    .a_copy = c.at(w.gath) /* the transform's weight-gradient operand */, .a_copy_ld = c.H}, c.at(w.gath), c.s));
+                    .a_copy = c.at(w.gath) /* the transform's weight-gradient operand */, .a_copy_ld = c.H,
+                    .activation = c.cfg.act_mlm}, c.at(w.gath), c.s));
   if (c.plan.fused_head)
     return b4r_head32_fwd_launch(c.at(w.t), c.prm(pl.word_emb), c.prm(pl.out_bias), c.batch.masked_lm_ids, c.M, c.V, c.E,
                                  c.at(w.scratch), c.at(w.dt), c.at(w.rowsc), c.at(w.head_lse), reinterpret_cast<int32_t*>(c.at(w.head_ylab)),
@@ -977,7 +988,8 @@ extern "C" int b4r_mlm_transform_rows_ex(const b4r_model_config_ex* cfg_ex, cons
                         .epilogue = B4R_EPI_BIAS_GELU_LN, .bias = params + pl.bd, .C2 = out, .ldc2 = E, .qscale = 1.f,
                         .c_pad_scratch = 0, .ln_gamma = params + pl.lnm_g, .ln_beta = params + pl.lnm_b, .ln_mean = mean,
                         .ln_rstd = rstd, .ln_eps = cfg->ln_eps, .C3 = upre, .ldc3 = E,
-                        .a_gather_idx = rows, .a_gather_add_per = n_seq_rows, .a_gather_per = R /* one group: row m reads seq[rows[m]] */},
+                        .a_gather_idx = rows, .a_gather_add_per = n_seq_rows, .a_gather_per = R /* one group: row m reads seq[rows[m]] */,
+                        .activation = cfg->act_mlm},
                        gath, stream);
 }
 extern "C" int b4r_mlm_transform_rows(const b4r_model_config* cfg, const float* params, const float* seq, int64_t n_seq_rows,
@@ -1067,7 +1079,7 @@ int head_bwd(Step& c) {
   RC(c.take(b4r_ln_bwd_scratch_floats(M, E), &sc));
   RC(b4r_ln_bwd_launch(c.at(w.dt), c.at(w.u), c.at(w.meanm), c.at(w.rstdm), c.prm(pl.lnm_g), M, E, c.at(w.dt), c.grd(pl.lnm_g),
                        c.grd(pl.lnm_b), sc, nullptr, nullptr, nullptr, 1, 1, b4r_make_drop(nullptr, 0, 0.f, 0), c.s, c.at(w.upre),
-                       fwd_part ? &merge : nullptr));
+                       fwd_part ? &merge : nullptr, c.cfg.act_mlm));
   // dense layer of the transform: dWd = gath^T . du (+ bias gradient) and dgath = du . Wd^T, one pass over du where the pair kernel
   // applies (hidden size 64), else the two products
   b4r_gemm_tn_desc d{.A = c.at(w.gath), .lda = H, .B = c.at(w.dt), .ldb = E, .out = c.grd(pl.wd), .ldo = E, .R = M, .Mo = H, .No = E,
@@ -1136,7 +1148,8 @@ int ffn_bwd_compact(Step& c, int i) {
   if (c.od > 0.f)
     RC(b4r_slot_rows_drop(dz2c, pos, c.L, c.P, M, H, b4r_make_drop(c.rng, B4R_STREAM_FFN_OUT(i), c.od, 1), dz2d, c.s));
   RC(gemm_f32({.A = dz2d, .lda = H, .B = c.prm(pl.w2[i]), .ldb = H, .C = c.at(w.df), .ldc = I, .M = M, .N = I, .K = H, .b_is_nk = 1,
-               .epilogue = B4R_EPI_GELU_BWD, .R = c.at(w.fpre[i]), .ldr = I, .qscale = 1.f, .c_pad_scratch = 1}, c.s));
+               .epilogue = B4R_EPI_GELU_BWD, .R = c.at(w.fpre[i]), .ldr = I, .qscale = 1.f, .c_pad_scratch = 1,
+               .activation = c.cfg.act_inner}, c.s));
   RC(c.take(b4r_gemm_tn_scratch_floats(M, I, H), &sc));
   RC(gemm_tn_f32({.A = c.at(w.f[i]), .lda = I, .B = dz2d, .ldb = H, .out = c.grd(pl.w2[i]), .ldo = H, .R = M, .Mo = I, .No = H,
                   .colsum = c.grd(pl.b2[i])}, sc, c.s));
@@ -1177,10 +1190,11 @@ int ffn_bwd_tiles(Step& c, int i) {
   RC(wgrad_with_dgrad(c, {.A = c.at(w.f[i]), .lda = I, .B = c.at(w.da), .ldb = H, .out = c.grd(pl.w2[i]), .ldo = H, .R = N, .Mo = I,
                           .No = H, .colsum = c.grd(pl.b2[i]), .rng = c.rng, .drop_stream = B4R_STREAM_FFN_OUT(i), .drop_rate = c.od,
                           .b_dropout = 1, .dgrad_w = c.prm(pl.w2[i]), .dgrad_ldw = H, .dgrad_out = c.at(w.df), .dgrad_ldo = I,
-                          .dgrad_gelu_pre = c.at(w.fpre[i]), .dgrad_ldg = I},
+                          .dgrad_gelu_pre = c.at(w.fpre[i]), .dgrad_ldg = I, .activation = c.cfg.act_inner},
                       {.A = c.at(w.da), .lda = H, .B = c.prm(pl.w2[i]), .ldb = H, .C = c.at(w.df), .ldc = I, .M = N, .N = I, .K = H,
                        .b_is_nk = 1, .epilogue = B4R_EPI_GELU_BWD, .R = c.at(w.fpre[i]), .ldr = I, .qscale = 1.f, .rng = c.rng,
-                       .drop_stream = B4R_STREAM_FFN_OUT(i), .drop_rate = c.od, .a_dropout = 1, .c_pad_scratch = 1}));
+                       .drop_stream = B4R_STREAM_FFN_OUT(i), .drop_rate = c.od, .a_dropout = 1, .c_pad_scratch = 1,
+                       .activation = c.cfg.act_inner}));
   float* sc; RC(c.take(ln_scratch_floats(N, H), &sc));
   RC(dgrad_ln_bwd(c.at(w.df), I, c.prm(pl.w1[i]), I, c.at(w.da), c.at(w.db), N, H, c.at(w.z1[i]), c.at(w.mean1[i]), c.at(w.rstd1[i]),
                   c.prm(pl.ln1_g[i]), c.grd(pl.ln1_g[i]), c.grd(pl.ln1_b[i]), sc, c.s));

@@ -110,12 +110,14 @@ struct LnBwdP {
   int rows, H;
   DropArgs drop;
   const float* gelu_pre;      // optional [rows,H]: dz is further multiplied by gelu'(gelu_pre) (dense+GELU before the LN)
+  int act;                    // ... by f'(gelu_pre) of this activation instead (B4R_ACT_*; the ACT == B4R_ACT_ANY instantiation)
   HeadMergeP merge;           // MERGE: dy is not read -- it is the masked-LM head's dT, merged here from the forward's V slices
 };
 
 // MERGE (LPR = 16, NV = 1: hidden size 64, the thread layout of head_combine_kernel): the LayerNorm of the masked-LM transform in a
 // train step; the lanes of a row also write the row's loss scalars, lse and label (b4r_head_merge.h)
-template <int LPR, int NV, bool EMBED, bool MERGE = false>
+// ACT: the activation whose derivative gelu_pre enters (B4R_ACT_GELU, or B4R_ACT_ANY: p.act)
+template <int LPR, int NV, bool EMBED, bool MERGE = false, int ACT = B4R_ACT_GELU>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(LnBwdP p) {
   constexpr int RPW = 64 / LPR;
   extern __shared__ float sred[];  // [4*RPW][2*H]
@@ -182,7 +184,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnBwdP p) {
         if (p.gelu_pre) {
           const f32x4 pre = *reinterpret_cast<const f32x4*>(p.gelu_pre + row * p.H + c);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] *= b4r_gelu_grad(pre[e]);
+          for (int e = 0; e < 4; ++e) o[e] *= (ACT == B4R_ACT_GELU) ? b4r_gelu_grad(pre[e]) : b4r_act_grad<false>(p.act, pre[e]);
         }
         *reinterpret_cast<f32x4*>(p.dz + row * p.H + c) = o;
       }
@@ -237,18 +239,18 @@ int launch_ln_fwd(const LnFwdP& p, hipStream_t s) {
   return B4R_OK;
 }
 
-template <bool EMBED>
+template <bool EMBED, int ACT = B4R_ACT_GELU>
 int launch_ln_bwd(const LnBwdP& p, int grid, hipStream_t s) {
   const int H = p.H;
   if (p.merge.part != nullptr) {
     if (EMBED || H != 64) { b4r_set_error("layer norm backward: the head merge needs hidden size 64"); return B4R_E_SHAPE; }
-    hipLaunchKernelGGL((ln_bwd_kernel<16, 1, false, true>), dim3(grid), dim3(256), (size_t)4 * 4 * 2 * H * sizeof(float), s, p);
+    hipLaunchKernelGGL((ln_bwd_kernel<16, 1, false, true, ACT>), dim3(grid), dim3(256), (size_t)4 * 4 * 2 * H * sizeof(float), s, p);
     return B4R_OK;
   }
 #define LN_BWD_CASE(LPR_, NV_)                                                                           \
   {                                                                                                      \
     const size_t sh = (size_t)4 * (64 / LPR_) * 2 * H * sizeof(float);                                   \
-    hipLaunchKernelGGL((ln_bwd_kernel<LPR_, NV_, EMBED>), dim3(grid), dim3(256), sh, s, p);              \
+    hipLaunchKernelGGL((ln_bwd_kernel<LPR_, NV_, EMBED, false, ACT>), dim3(grid), dim3(256), sh, s, p);  \
   }
   switch (H) {
     case 32: LN_BWD_CASE(8, 1) break;
@@ -781,9 +783,10 @@ __global__ __launch_bounds__(256) void ln_partial_reduce_kernel(const float* par
 int b4r_ln_bwd_launch(const float* dy, const float* z, const float* mean, const float* rstd, const float* gamma,
                       int rows, int H, float* dz, float* dgamma, float* dbeta, float* scratch, const int64_t* ids,
                       const float* table, const float* pos_table, int L, int V, DropArgs drop, hipStream_t stream,
-                      const float* gelu_pre, const B4rHeadMerge* merge) {
+                      const float* gelu_pre, const B4rHeadMerge* merge, int act) {
+  B4R_CHECK_ARG(act >= 0 && act < B4R_ACT_COUNT, B4R_E_BADARG, "ln_bwd: unknown activation %d", act);
   LnBwdP p{};
-  p.gelu_pre = gelu_pre;
+  p.gelu_pre = gelu_pre; p.act = act;
   if (merge != nullptr)
     p.merge = HeadMergeP{merge->part, merge->slices, merge->M, merge->V, merge->T, merge->E, merge->bias, merge->y, merge->row_out,
                          merge->lse_out, merge->ylab};
@@ -791,7 +794,8 @@ int b4r_ln_bwd_launch(const float* dy, const float* z, const float* mean, const 
   p.ids = ids; p.table = table; p.pos_table = pos_table; p.L = L; p.V = V;
   p.rows = rows; p.H = H; p.drop = drop;
   const int grid = ln_bwd_grid(rows, H);
-  int rc = ids ? launch_ln_bwd<true>(p, grid, stream) : launch_ln_bwd<false>(p, grid, stream);
+  int rc = ids ? launch_ln_bwd<true>(p, grid, stream)
+           : (gelu_pre && act != B4R_ACT_GELU) ? launch_ln_bwd<false, B4R_ACT_ANY>(p, grid, stream) : launch_ln_bwd<false>(p, grid, stream);
   if (rc) return rc;
   B4R_CHECK_LAUNCH("ln_bwd");
   if (dbeta == dgamma + H) {   // gamma and beta adjacent (always so in the flat gradient buffer): one [1, 2H] strip
@@ -811,7 +815,16 @@ extern "C" int b4r_ln_bwd(const float* dy, const float* z, const float* mean, co
                 "b4r_ln_bwd: null argument");
   B4R_CHECK_ARG(rows > 0, B4R_E_SHAPE, "b4r_ln_bwd: bad shape");
   return b4r_ln_bwd_launch(dy, z, mean, rstd, gamma, rows, H, dz, dgamma, dbeta, scratch, nullptr, nullptr, nullptr, 1,
-                           1, b4r_make_drop(nullptr, 0, 0.f, 0), (hipStream_t)stream, nullptr, nullptr);
+                           1, b4r_make_drop(nullptr, 0, 0.f, 0), (hipStream_t)stream, nullptr, nullptr, B4R_ACT_GELU);
+}
+extern "C" int b4r_ln_bwd_act(const float* dy, const float* z, const float* mean, const float* rstd, const float* gamma,
+                              int32_t rows, int32_t H, float* dz, float* dgamma, float* dbeta, float* scratch,
+                              const float* act_pre, int32_t activation, b4r_stream_t stream) {
+  B4R_CHECK_ARG(dy && z && mean && rstd && gamma && dz && dgamma && dbeta && scratch, B4R_E_BADARG,
+                "b4r_ln_bwd_act: null argument");
+  B4R_CHECK_ARG(rows > 0, B4R_E_SHAPE, "b4r_ln_bwd_act: bad shape");
+  return b4r_ln_bwd_launch(dy, z, mean, rstd, gamma, rows, H, dz, dgamma, dbeta, scratch, nullptr, nullptr, nullptr, 1,
+                           1, b4r_make_drop(nullptr, 0, 0.f, 0), (hipStream_t)stream, act_pre, nullptr, activation);
 }
 
 extern "C" int b4r_gather_rows(const float* src, int32_t src_ld, const int64_t* idx, int64_t idx_add_per, int32_t per,

@@ -13,7 +13,7 @@ from typing import Dict, Iterable, List, Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, activations
 from ._lib import AdamWConfig, B4RError, Batch, ModelConfig, ModelConfigEx
 
 BATCH_KEYS = ("input_word_ids", "input_mask", "masked_lm_positions", "masked_lm_ids")
@@ -59,12 +59,14 @@ class ParamInfo:
         self.name, self.offset, self.rows, self.cols, self.ld, self.decay = name, offset, rows, cols, ld, decay
 
 
-def config_api(lib, cfg: ModelConfig, embedding_width: Optional[int], name: str):
+def config_api(lib, cfg: ModelConfig, embedding_width: Optional[int], name: str, inner_activation: int = 0, mlm_activation: int = 0):
     """The entry point `name` and the config argument it takes: the classic function with the 36-byte config for the unfactorised
-    model (embedding_width None / 0 / hidden_size), else its _ex twin with a b4r_model_config_ex.  The one place that chooses."""
-    if not embedding_width or int(embedding_width) == cfg.hidden_size:
+    GELU model (embedding_width None / 0 / hidden_size, both activations 0), else its _ex twin with a b4r_model_config_ex (the
+    activation ids of bert4rec_amd/activations.py in its activations word).  The one place that chooses."""
+    acts = _lib.activations_word(inner_activation, mlm_activation)
+    if (not embedding_width or int(embedding_width) == cfg.hidden_size) and acts == 0:
         return getattr(lib, name), C.byref(cfg)
-    return getattr(lib, name + "_ex"), C.pointer(ModelConfigEx(cfg, int(embedding_width), (0, 0, 0)))
+    return getattr(lib, name + "_ex"), C.pointer(ModelConfigEx(cfg, int(embedding_width or 0), (0, acts, 0)))
 
 
 def param_table(cfg: ModelConfig, embedding_width: Optional[int] = None) -> List[ParamInfo]:
@@ -157,12 +159,15 @@ def check_rank_full_args(k, exclude: Optional[torch.Tensor] = None, n_rows: Opti
 class Engine:
     """One replica of the model on one GPU."""
 
-    def __init__(self, cfg: ModelConfig, device="cuda", seed: int = 0, embedding_width: Optional[int] = None):
+    def __init__(self, cfg: ModelConfig, device="cuda", seed: int = 0, embedding_width: Optional[int] = None,
+                 inner_activation: int = 0, mlm_activation: int = 0):
         """embedding_width: the item table's width E (Bert4RecEncoder(embedding_width=...)); None / 0 / hidden_size = the unfactorised
-        model.  E < hidden_size adds the learned E -> hidden projection (include/b4r.h, b4r_model_config_ex)."""
+        model.  E < hidden_size adds the learned E -> hidden projection (include/b4r.h, b4r_model_config_ex).  inner_activation /
+        mlm_activation: the feed-forward blocks' and the masked-LM transform's activation ids (bert4rec_amd/activations.py; 0 = GELU)."""
         self.lib = _lib.load()
         self.cfg = cfg
         self.embedding_width = int(embedding_width) if embedding_width else int(cfg.hidden_size)
+        self.inner_activation, self.mlm_activation = int(inner_activation), int(mlm_activation)
         self.device = torch.device(device)
         total = self._api("b4r_param_total_floats")()
         if total < 0:
@@ -188,8 +193,19 @@ class Engine:
     def _api(self, name: str):
         """`name` bound to this engine's config: every config-taking call goes through here (config_api), so that no call site can
         hand the 36-byte struct to a factorised model."""
-        fn, ref = config_api(self.lib, self.cfg, self.embedding_width, name)
+        fn, ref = config_api(self.lib, self.cfg, self.embedding_width, name, self.inner_activation, self.mlm_activation)
         return lambda *args: fn(ref, *args)
+
+    def set_mlm_activation(self, act: int) -> None:
+        """The masked-LM transform's activation id from now on (BERT4RecModel(mlm_activation=...)); the parameter and workspace
+        layouts do not depend on it."""
+        act = int(act)
+        if not 0 <= act < activations.COUNT:
+            raise ValueError(f"unknown activation id {act}")
+        if act != self.mlm_activation:
+            self.__dict__.pop("_graphs", None)   # captured steps hold the old activation
+            self.__dict__.pop("_graph_seen", None)
+        self.mlm_activation = act
 
     # ---- parameters -----------------------------------------------------------------------------------------------
     def view(self, name: str, buf: Optional[torch.Tensor] = None) -> torch.Tensor:

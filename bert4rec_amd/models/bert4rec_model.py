@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .. import activations
 from .. import engine as engine_mod
 from ..trainers import trainer_utils
 from ..trainers.optimizers import AdamWeightDecay
@@ -81,8 +82,13 @@ class BERT4RecModel:
                  special_token_ids: Optional[List[int]] = SPECIAL_TOKEN_IDS, **kwargs):
         if customized_masked_lm is not None:
             raise NotImplementedError("customized_masked_lm is not supported: the masked-LM head is a fused HIP path")
-        if mlm_activation != "gelu":
-            raise NotImplementedError("only mlm_activation='gelu' is implemented")
+        mlm_id = activations.activation_id(mlm_activation, "mlm_activation")
+        # the transform's activation lives in the encoder's engine: a second model on the same encoder may not switch it
+        bound = getattr(encoder.engine, "_mlm_activation_bound", None)   # (id, name) of the first model on this encoder
+        if bound is not None and bound[0] != mlm_id:
+            raise ValueError(f"mlm_activation={mlm_activation!r}: this encoder already serves a model with mlm_activation={bound[1]!r}")
+        encoder.engine.set_mlm_activation(mlm_id)
+        encoder.engine._mlm_activation_bound = (mlm_id, mlm_activation)
         self._config = {"encoder": encoder, "customized_masked_lm": customized_masked_lm,
                         "mlm_activation": mlm_activation, "mlm_initializer": mlm_initializer, "name": name}
         self.name = name

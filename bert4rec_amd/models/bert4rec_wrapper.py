@@ -30,6 +30,8 @@ class BERT4RecModelWrapper(ModelWrapper):
         out = {k: cfg[k] for k in _JSON_KEYS}
         if cfg.get("embedding_width") not in (None, cfg["hidden_size"]):   # factorised item embeddings only
             out["embedding_width"] = cfg["embedding_width"]
+        if cfg.get("inner_activation", "gelu") != "gelu":   # another feed-forward activation only: GELU files stay as they were
+            out["inner_activation"] = cfg["inner_activation"]
         return out
 
     def save(self, save_path: pathlib.Path, tokenizer=None, mode: int = 0) -> bool:

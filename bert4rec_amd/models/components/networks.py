@@ -6,6 +6,7 @@ from typing import Any, Dict, Optional
 
 import torch
 
+from ... import activations
 from ...engine import Engine, make_model_config
 
 
@@ -35,9 +36,12 @@ class Bert4RecEncoder:
             raise TypeError(f"unexpected keyword arguments {sorted(kwargs)}")
         if embedding_width is None:
             embedding_width = hidden_size
+        # inner_activation: a Keras identifier of bert4rec_amd/activations.py.  None keeps the GELU (Keras would make it linear; the
+        # classic behaviour of this package is kept)
+        if inner_activation is None:
+            inner_activation = "gelu"
+        inner_id = activations.activation_id(inner_activation, "inner_activation")
         # options of the reference constructor that no shipped config uses and the kernels do not implement
-        if inner_activation not in ("gelu", None):
-            raise NotImplementedError("only inner_activation='gelu' (erf form) is implemented")
         if norm_first:
             raise NotImplementedError("norm_first=True (pre-LN) is not implemented; the reference default is post-LN")
         if embedding_width != hidden_size and not (embedding_width in (64, 128, 256) and embedding_width < hidden_size):
@@ -50,7 +54,7 @@ class Bert4RecEncoder:
         self._config = {
             "vocab_size": vocab_size, "hidden_size": hidden_size, "num_layers": num_layers,
             "num_attention_heads": num_attention_heads, "max_sequence_length": max_sequence_length,
-            "inner_dim": inner_dim, "inner_activation": "gelu", "output_dropout": output_dropout,
+            "inner_dim": inner_dim, "inner_activation": inner_activation, "output_dropout": output_dropout,
             "attention_dropout": attention_dropout, "initializer": "TruncatedNormal(stddev=0.02)",
             "output_range": output_range, "embedding_width": embedding_width, "embedding_layer": embedding_layer,
             "norm_first": norm_first, "with_dense_inputs": with_dense_inputs,
@@ -58,7 +62,8 @@ class Bert4RecEncoder:
         cfg = make_model_config(vocab_size, hidden_size, num_layers, num_attention_heads, max_sequence_length, inner_dim,
                                 output_dropout, attention_dropout)
         self.device = torch.device(device) if device is not None else _default_device()
-        self.engine = Engine(cfg, self.device, seed=seed, embedding_width=embedding_width)   # ValueError on an unsupported geometry
+        self.engine = Engine(cfg, self.device, seed=seed, embedding_width=embedding_width,   # ValueError on an unsupported geometry
+                             inner_activation=inner_id)
         self.engine.init_parameters(seed=seed)
         self.inputs = {"input_word_ids": "int[B,L]", "input_mask": "int[B,L]"}
 

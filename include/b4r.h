@@ -32,6 +32,22 @@ typedef struct ihipStream_t* b4r_stream_t; /* == hipStream_t */
 
 enum { B4R_OK = 0, B4R_E_BADARG = -1, B4R_E_SHAPE = -2, B4R_E_ALIGN = -3, B4R_E_HIP = -4, B4R_E_NOMEM = -5 };
 
+/* Activations of the feed-forward blocks (Bert4RecEncoder inner_activation, bert4rec_encoder.py:70,88-89,140) and of the
+ * masked-LM transform (BERT4RecModel mlm_activation, bert4rec_model.py:42,77-81): the Keras identifiers, TF semantics for value
+ * and gradient (relu' = 0 at 0).  0 is the erf-GELU every shipped configuration uses. */
+enum {
+  B4R_ACT_GELU = 0,      /* 0.5 x (1 + erf(x / sqrt 2))                                   */
+  B4R_ACT_RELU = 1,      /* max(x, 0)                                                     */
+  B4R_ACT_SWISH = 2,     /* x sigmoid(x)  ("swish", "silu")                               */
+  B4R_ACT_TANH = 3,
+  B4R_ACT_SIGMOID = 4,
+  B4R_ACT_ELU = 5,       /* x > 0 ? x : exp(x) - 1                                        */
+  B4R_ACT_SELU = 6,      /* scale * (x > 0 ? x : alpha (exp(x) - 1)), Keras' alpha / scale */
+  B4R_ACT_SOFTPLUS = 7,  /* log(1 + exp(x)), overflow-safe                                */
+  B4R_ACT_LINEAR = 8,
+  B4R_ACT_COUNT = 9
+};
+
 /* Encoder hyper-parameters: Bert4RecEncoder.__init__ kwargs, bert4rec_encoder.py:62-80, as set by
  * bert4rec/config/bert4rec_train_configs/ *.json.  head_dim = hidden_size / num_heads must be 32 (true for every
  * shipped config) or 64. */
@@ -308,8 +324,14 @@ int b4r_mlm_transform_rows(const b4r_model_config* cfg, const float* params, con
 typedef struct b4r_model_config_ex {
   b4r_model_config base;
   int32_t embedding_width;  /* 0 or base.hidden_size: the unfactorised model; else 64 / 128 / 256 and < hidden_size */
-  int32_t reserved[3];      /* must be zero (room for the next encoder option without another struct) */
+  /* reserved[1] is the ACTIVATIONS WORD: bits 0-7 the feed-forward blocks' activation, bits 8-15 the masked-LM transform's
+   * (B4R_ACT_*), every other bit zero; 0 = GELU in both places (bit for bit the classic model).  B4R_ACT_WORD builds it.  An
+   * unknown id or a stray bit returns B4R_E_BADARG (-1 from the int64 queries).  reserved[0] and reserved[2] must be zero.
+   * Every _ex entry point takes any activation, also with embedding_width 0; the classic entry points are GELU only.  The
+   * launch plan is the same for every activation. */
+  int32_t reserved[3];
 } b4r_model_config_ex;
+#define B4R_ACT_WORD(inner, mlm) ((int32_t)(((uint32_t)(inner) & 0xFFu) | (((uint32_t)(mlm) & 0xFFu) << 8)))
 
 int64_t b4r_param_total_floats_ex(const b4r_model_config_ex* cfg);
 int64_t b4r_param_decay_floats_ex(const b4r_model_config_ex* cfg);
@@ -374,6 +396,11 @@ int64_t b4r_ln_bwd_scratch_floats(int32_t rows, int32_t H);
 int b4r_ln_bwd(const float* dy, const float* z, const float* mean, const float* rstd, const float* gamma,
                int32_t rows, int32_t H, float* dz, float* dgamma, float* dbeta, float* scratch,
                b4r_stream_t stream);
+/* ... the masked-LM transform's path: dz is further multiplied by f'(act_pre [rows, H]), f = activation (B4R_ACT_*), the dense
+ * layer's activation in front of the LayerNorm (bert4rec_model.py:77-81).  act_pre == NULL: b4r_ln_bwd */
+int b4r_ln_bwd_act(const float* dy, const float* z, const float* mean, const float* rstd, const float* gamma,
+                   int32_t rows, int32_t H, float* dz, float* dgamma, float* dbeta, float* scratch,
+                   const float* act_pre, int32_t activation, b4r_stream_t stream);
 
 /* epilogues of b4r_gemm_f32 */
 enum {
@@ -431,6 +458,8 @@ typedef struct b4r_gemm_desc {
    * reads row clamp(a_gather_idx[m], 0, a_gather_add_per - 1) + (m / a_gather_per) * a_gather_add_per of A (tfm MaskedLM gathers
    * the masked positions of every sequence, bert4rec_model.py:143); a_copy [M, a_copy_ld >= K] (optional) receives the gathered rows */
   const int64_t* a_gather_idx; int64_t a_gather_add_per; int32_t a_gather_per; float* a_copy; int32_t a_copy_ld;
+  /* B4R_EPI_BIAS_GELU, B4R_EPI_GELU_BWD and B4R_EPI_BIAS_GELU_LN: the activation (B4R_ACT_*) in place of the GELU; 0 = GELU */
+  int32_t activation;
 } b4r_gemm_desc;
 /* Arithmetic of the dense layers (process-wide switch; default B4R_GEMM_BF16X3):
  *   B4R_GEMM_F32     exact fp32 matrix cores (v_mfma_f32_32x32x2_f32), LDS-tiled
@@ -468,6 +497,7 @@ typedef struct b4r_gemm_tn_desc {
    * (b4r_gemm_tn_dgrad_supported), otherwise B4R_E_SHAPE: callers then issue b4r_gemm_f32 with a_dropout for dx */
   const float* dgrad_w; int32_t dgrad_ldw; float* dgrad_out; int32_t dgrad_ldo;
   const float* dgrad_gelu_pre; int32_t dgrad_ldg;
+  int32_t activation;   /* the activation (B4R_ACT_*) whose derivative dgrad_gelu_pre enters; 0 = GELU */
 } b4r_gemm_tn_desc;
 int64_t b4r_gemm_tn_scratch_floats(int32_t R, int32_t Mo, int32_t No);
 int b4r_gemm_tn_f32(const b4r_gemm_tn_desc* d, float* scratch, b4r_stream_t stream);
@@ -620,6 +650,9 @@ typedef struct b4r_ffn_desc {
   /* x1 == NULL: the block input is formed on load, x1 = LayerNorm(z1) * ln1_gamma + ln1_beta from z1 / mean1 / rstd1 (inputs of the
    * forward too, then) -- the attention block need not store x1 at all (b4r_attn_block_desc.x1 = NULL). */
   const float* ln1_beta;
+  /* the activation between the two dense layers (B4R_ACT_*; 0 = GELU): b4r_ffn_block_*, b4r_ffn_wide_* and b4r_encoder_layer_*
+   * (where "gelu" above reads as this activation) */
+  int32_t activation;
 } b4r_ffn_desc;
 /* The rows of the sequence output that the masked-LM head of this batch reads, one entry per masked-LM slot m = b*P + p:
  * rows[m] = b*L + clamp(position[m]) (padded slots gather position 0, as tfm MaskedLM does: their entries repeat a row, which the
