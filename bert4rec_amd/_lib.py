@@ -122,7 +122,7 @@ EPI_BIAS_DROP_RES_LN, EPI_ADD_RES_LN_BWD, EPI_BIAS_GELU_LN = 8, 9, 10
 FLAG_TRAINING, FLAG_POOLER, FLAG_FUSED_HEAD, FLAG_GRAD_TAIL, FLAG_HEAD_ROWS_ONLY, FLAG_LOSS_SUMS = 1, 2, 4, 8, 16, 32
 FLAG_ENCODER_ONLY = 64
 LOSS_FUSED_HEAD = 2
-GEMM_F32, GEMM_BF16X3 = 0, 1
+GEMM_F32, GEMM_BF16X3, GEMM_BF16 = 0, 1, 2
 
 _P, _I32, _I64, _F, _U32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint32
 
@@ -185,6 +185,8 @@ PROTOTYPES = {
     "b4r_ln_bwd_act": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P]),
     "b4r_set_gemm_mode": (C.c_int, [C.c_int]),
     "b4r_get_gemm_mode": (C.c_int, []),
+    "b4r_split_mode": (C.c_int, []),
+    "b4r_gemm_terms": (C.c_int, []),
     "b4r_gemm_f32": (C.c_int, [C.POINTER(GemmDesc), _P]),
     "b4r_gemm_ln_supported": (C.c_int, [C.POINTER(GemmDesc)]),
     "b4r_gemm_ln_bwd_partial_floats": (_I64, [_I32]),

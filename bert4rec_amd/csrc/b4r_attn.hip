@@ -355,7 +355,7 @@ extern "C" int b4r_attn_fwd(const float* qkv, const int64_t* input_mask, int32_t
   int rc = check_common("b4r_attn_fwd", qkv, input_mask, B, L, heads);
   if (rc) return rc;
   B4R_CHECK_ARG(ctx != nullptr, B4R_E_BADARG, "b4r_attn_fwd: null ctx");
-  if (b4r_get_gemm_mode() == B4R_GEMM_BF16X3) {
+  if (b4r_split_mode()) {
     const DropArgs drop = b4r_make_drop(rng, drop_stream, drop_rate, 1);
     rc = check_bits("b4r_attn_fwd", drop, keep_bits);
     if (rc) return rc;
@@ -394,7 +394,7 @@ extern "C" int b4r_attn_bwd(const float* qkv, const int64_t* input_mask, const f
   if (rc) return rc;
   B4R_CHECK_ARG(ctx && lse && dctx && dqkv, B4R_E_BADARG, "b4r_attn_bwd: null argument");
   B4R_CHECK_ARG(b4r_aligned16(ctx) && b4r_aligned16(dctx) && b4r_aligned16(dqkv), B4R_E_ALIGN, "b4r_attn_bwd: operands must be 16-byte aligned");
-  if (b4r_get_gemm_mode() == B4R_GEMM_BF16X3) {
+  if (b4r_split_mode()) {
     const DropArgs drop = b4r_make_drop(rng, drop_stream, drop_rate, 1);
     rc = check_bits("b4r_attn_bwd", drop, keep_bits);
     if (rc) return rc;

@@ -18,6 +18,7 @@
 // bert4rec/models/components/networks/bert4rec_encoder.py:136-147 and called at :220-222 (key-padding mask -1e9,
 // query scaled by 1/sqrt(d) after its bias, attention dropout on the probabilities, output dropout, residual,
 // self_attention_layer_norm); the backward is tape.gradient of that call (bert4rec_model.py:166-167).
+#include <type_traits>
 #include "b4r_tile32.h"
 
 namespace {
@@ -1345,7 +1346,7 @@ __device__ __forceinline__ f32x16 load_acc_layout(const float* row_col0, int h) 
   return v;
 }
 
-template <int NTT, bool DROP>
+template <int NTT, bool DROP, int TERMS = 3>
 __global__ __launch_bounds__(512, 2) void attn32_core_fwd_kernel(A32CoreFwdP p) {
   extern __shared__ __attribute__((aligned(16))) char smem32[];
   const int NT = p.NT, L = p.L;
@@ -1371,8 +1372,8 @@ __global__ __launch_bounds__(512, 2) void attn32_core_fwd_kernel(A32CoreFwdP p) 
 #pragma unroll
   for (int s = 0; s < 2; ++s) acc_frag(qa, s, qBh[s], qBl[s]);
   if (!live) { kacc = zero16(); vacc = zero16(); }   // pad tokens: zero rows (their keys are masked anyway; no NaN may enter P . V)
-  acc_to_rows(kimg + wave * P_TILE, lk, kacc);
-  acc_to_rows(vimg + wave * P_TILE, lk, vacc);
+  acc_to_rows<TERMS>(kimg + wave * P_TILE, lk, kacc);
+  acc_to_rows<TERMS>(vimg + wave * P_TILE, lk, vacc);
   lds_barrier();
 
   const DropCtx dcp = b4r_drop_ctx(p.drop_p);
@@ -1389,7 +1390,7 @@ __global__ __launch_bounds__(512, 2) void attn32_core_fwd_kernel(A32CoreFwdP p) 
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         const char* ka = kimg + t * P_TILE + lk.rowc[ks];
-        S[t] = mfma32x3(row_at(ka), row_at(ka + P_IMG), qBh[ks], qBl[ks], S[t]);
+        S[t] = mfma32x3<TERMS>(row_at(ka), row_at(ka + P_IMG), qBh[ks], qBl[ks], S[t]);
       }
     } else {
 #pragma unroll
@@ -1438,7 +1439,7 @@ __global__ __launch_bounds__(512, 2) void attn32_core_fwd_kernel(A32CoreFwdP p) 
       bf16x8 ph, pl;
       acc_frag(S[t], s2, ph, pl);
       const char* va = vimg + t * P_TILE;
-      O = mfma32x3(tr_pair(va + lk.trp[s2][0], va + lk.trp[s2][1]), tr_pair(va + P_IMG + lk.trp[s2][0], va + P_IMG + lk.trp[s2][1]),
+      O = mfma32x3<TERMS>(tr_pair(va + lk.trp[s2][0], va + lk.trp[s2][1]), tr_pair(va + P_IMG + lk.trp[s2][0], va + P_IMG + lk.trp[s2][1]),
                        ph, pl, O);
     }
   }
@@ -1464,7 +1465,7 @@ struct A32CoreBwdP {
 // LDS (bytes): [Q~ images NT x 4 KB | dO images | dQ accumulators (fp32, register layout) | per-wave scratch | mask adders, -lse, D, flags]
 __host__ __device__ constexpr int core_bwd_lds(int NT) { return 4 * NT * P_TILE + (3 * NT * 32 + 8) * 4; }
 
-template <bool DROP>
+template <bool DROP, int TERMS = 3>
 __global__ __launch_bounds__(512, 2) void attn32_core_bwd_kernel(A32CoreBwdP p) {
   extern __shared__ __attribute__((aligned(16))) char smem32[];
   const int NT = p.NT, L = p.L;
@@ -1512,9 +1513,9 @@ __global__ __launch_bounds__(512, 2) void attn32_core_bwd_kernel(A32CoreBwdP p) 
   bf16x8 kBh[2], kBl[2], vBh[2], vBl[2];     // K^T, V^T [feature][key] as B operands of S = Q~.K^T and dA = dO.V^T
 #pragma unroll
   for (int s = 0; s < 2; ++s) { acc_frag(kT, s, kBh[s], kBl[s]); acc_frag(vT, s, vBh[s], vBl[s]); }
-  acc_to_rows(ownA, lk, qT);
-  acc_to_rows(ownB, lk, dcT);
-  acc_to_rows(scr, lk, kT);
+  acc_to_rows<TERMS>(ownA, lk, qT);
+  acc_to_rows<TERMS>(ownB, lk, dcT);
+  acc_to_rows<TERMS>(scr, lk, kT);
   lds_barrier();                             // (the wave's own K^T image is written: its transposed reads below may start)
   bf16x8 kTh[2], kTl[2];                     // K^T[feature position][key] as the A operand of dQ^T = K^T.dS^T
 #pragma unroll
@@ -1558,9 +1559,9 @@ Lo = tr_pair(scr + P_IMG + lk.trn[ks][0], scr + P_IMG + lk.trn[ks][1])
     for (int ks = 0; ks < 2; ++ks) {
       bf16x8 ah, al;
       A32_LD_ROW(qimg, ks, ah, al);
-      S = mfma32x3(ah, al, kBh[ks], kBl[ks], S);
+      S = mfma32x3<TERMS>(ah, al, kBh[ks], kBl[ks], S);
       A32_LD_ROW(dimg, ks, ah, al);
-      dA = mfma32x3(ah, al, vBh[ks], vBl[ks], dA);
+      dA = mfma32x3<TERMS>(ah, al, vBh[ks], vBl[ks], dA);
     }
   }
   for (int s = 0; s < NT; ++s) {
@@ -1619,32 +1620,32 @@ Lo = tr_pair(scr + P_IMG + lk.trn[ks][0], scr + P_IMG + lk.trn[ks][1])
     // ---- matrix phase: ten products, fragments requested two products ahead ---------------------------------------------------
     bf16x8 f2h, f2l, f3h, f3l, f4h, f4l, f5h, f5l, f6h, f6l, f7h, f7l, f8h, f8l, f9h, f9l;
     A32_LD_TR(dimg, 1, f2h, f2l);
-    dV = mfma32x3(f0h, f0l, pdh[0], pdl[0], dV);   // dV^T[feature][key] += dO^T[feature][query] . Pd[query][key], queries 0..15
+    dV = mfma32x3<TERMS>(f0h, f0l, pdh[0], pdl[0], dV);   // dV^T[feature][key] += dO^T[feature][query] . Pd[query][key], queries 0..15
     A32_SB();
     A32_LD_TR(qimg, 1, f3h, f3l);
-    dK = mfma32x3(f1h, f1l, dsh[0], dsl[0], dK);   // dK^T += Q~^T . dS
+    dK = mfma32x3<TERMS>(f1h, f1l, dsh[0], dsl[0], dK);   // dK^T += Q~^T . dS
     A32_SB();
     A32_LD_ROW(qn, 0, f4h, f4l);
-    dV = mfma32x3(f2h, f2l, pdh[1], pdl[1], dV);
+    dV = mfma32x3<TERMS>(f2h, f2l, pdh[1], pdl[1], dV);
     A32_SB();
     A32_LD_ROW(dn, 0, f5h, f5l);
-    dK = mfma32x3(f3h, f3l, dsh[1], dsl[1], dK);
+    dK = mfma32x3<TERMS>(f3h, f3l, dsh[1], dsl[1], dK);
     A32_SB();
     A32_LD_ROW(qn, 1, f6h, f6l);
-    S = mfma32x3(f4h, f4l, kBh[0], kBl[0], S);     // S[query][key] = Q~ . K^T of the next tile
+    S = mfma32x3<TERMS>(f4h, f4l, kBh[0], kBl[0], S);     // S[query][key] = Q~ . K^T of the next tile
     A32_SB();
     A32_LD_ROW(dn, 1, f7h, f7l);
-    dA = mfma32x3(f5h, f5l, vBh[0], vBl[0], zero16());
+    dA = mfma32x3<TERMS>(f5h, f5l, vBh[0], vBl[0], zero16());
     A32_SB();
     A32_LD_SCR(0, f8h, f8l);
-    S = mfma32x3(f6h, f6l, kBh[1], kBl[1], S);
+    S = mfma32x3<TERMS>(f6h, f6l, kBh[1], kBl[1], S);
     A32_SB();
     A32_LD_SCR(1, f9h, f9l);
-    dA = mfma32x3(f7h, f7l, vBh[1], vBl[1], dA);
+    dA = mfma32x3<TERMS>(f7h, f7l, vBh[1], vBl[1], dA);
     A32_SB();
     // dQ^T[feature position][query] = K^T[.][key] . dS^T[key][query]  (B by transposed reads of the scratch image)
-    f32x16 dQp = mfma32x3(kTh[0], kTl[0], f8h, f8l, zero16());
-    dQp = mfma32x3(kTh[1], kTl[1], f9h, f9l, dQp);
+    f32x16 dQp = mfma32x3<TERMS>(kTh[0], kTl[0], f8h, f8l, zero16());
+    dQp = mfma32x3<TERMS>(kTh[1], kTl[1], f9h, f9l, dQp);
     A32_SWEEP(4 + 4 * s);
     if (s > 0) {   // the accumulator's previous addition (wave w + 1, its step s - 1) must be in place
       const volatile int* f = sflag + (wave + 1 < NT ? wave + 1 : 0);
@@ -2057,7 +2058,7 @@ bool al16(const void* q) { return q == nullptr || b4r_aligned16(q); }
 }  // namespace
 
 int32_t b4r_attn32_supported(int32_t hidden_size, int32_t num_heads, int32_t L) {
-  return (hidden_size == HID && num_heads == 2 && L > 0 && L <= 224 && b4r_get_gemm_mode() == B4R_GEMM_BF16X3) ? 1 : 0;
+  return (hidden_size == HID && num_heads == 2 && L > 0 && L <= 224 && b4r_split_mode()) ? 1 : 0;
 }
 // Sequences of at most two 32-token tiles leave five of the seven waves of a workgroup without a query / key tile: there round 2's
 // 16-token-tile kernels (one wave per 16 tokens) are faster -- Steam, L = 50: 0.408 against 0.440 ms per train step.  The 32-token-tile
@@ -2075,7 +2076,7 @@ int32_t b4r_attn32_preferred(int32_t hidden_size, int32_t num_heads, int32_t L) 
 // ---- the attention core for any number of 32-wide heads (b4r_attn_fwd / b4r_attn_bwd in the bf16x3 mode) ----------------------
 int64_t b4r_attn_rx_keep_words(int B, int L, int heads);
 bool b4r_attn32_core_preferred(int L) {
-  return L > 0 && L <= 224 && L >= g_attn32_min_len && b4r_get_gemm_mode() == B4R_GEMM_BF16X3;
+  return L > 0 && L <= 224 && L >= g_attn32_min_len && b4r_split_mode();
 }
 static int g_attn32_core_fwd = 0;
 bool b4r_attn32_core_fwd_wanted() { return g_attn32_core_fwd != 0; }
@@ -2095,18 +2096,25 @@ int b4r_attn32_core_fwd_launch(const float* qkv, const int64_t* mask, int B, int
   B4R_CHECK_ARG(!dropping || keep_bits, B4R_E_BADARG, "b4r_attn_fwd: attention dropout needs keep_bits");
   const size_t sh = (size_t)core_fwd_lds(p.NT);
   const dim3 grid((unsigned)(B * heads)), block((unsigned)(64 * p.NT));
-  int rc;
+  // the arithmetic mode picks the instances (B4R_GEMM_BF16: one term per product)
+  auto launch = [&](auto terms) -> int {
+    constexpr int TERMS = decltype(terms)::value;
+    int rc;
 #define A32_CORE_FWD_CASE(N_, D_)                                                                       \
   {                                                                                                     \
-    rc = b4r_raise_lds((const void*)attn32_core_fwd_kernel<N_, D_>, sh, "b4r_attn_fwd");                \
+    rc = b4r_raise_lds((const void*)attn32_core_fwd_kernel<N_, D_, TERMS>, sh, "b4r_attn_fwd");         \
     if (rc) return rc;                                                                                  \
-    hipLaunchKernelGGL((attn32_core_fwd_kernel<N_, D_>), grid, block, sh, stream, p);                   \
+    hipLaunchKernelGGL((attn32_core_fwd_kernel<N_, D_, TERMS>), grid, block, sh, stream, p);            \
   }
-  if (p.NT <= 2) { if (dropping) A32_CORE_FWD_CASE(2, true) else A32_CORE_FWD_CASE(2, false) }
-  else if (p.NT <= 4) { if (dropping) A32_CORE_FWD_CASE(4, true) else A32_CORE_FWD_CASE(4, false) }
-  else { if (dropping) A32_CORE_FWD_CASE(7, true) else A32_CORE_FWD_CASE(7, false) }
+    if (p.NT <= 2) { if (dropping) A32_CORE_FWD_CASE(2, true) else A32_CORE_FWD_CASE(2, false) }
+    else if (p.NT <= 4) { if (dropping) A32_CORE_FWD_CASE(4, true) else A32_CORE_FWD_CASE(4, false) }
+    else { if (dropping) A32_CORE_FWD_CASE(7, true) else A32_CORE_FWD_CASE(7, false) }
 #undef A32_CORE_FWD_CASE
-  B4R_CHECK_LAUNCH("b4r_attn_fwd (32-token tiles)");
+    return B4R_OK;
+  };
+  const int rc = b4r_gemm_terms() == 1 ? launch(std::integral_constant<int, 1>{}) : launch(std::integral_constant<int, 3>{});
+  if (rc) return rc;
+  B4R_CHECK_LAUNCH(b4r_gemm_terms() == 1 ? "b4r_attn_fwd (32-token tiles, bf16)" : "b4r_attn_fwd (32-token tiles)");
   return B4R_OK;
 }
 int b4r_attn32_core_bwd_launch(const float* qkv, const int64_t* mask, const float* ctx, const float* lse, const float* dctx, int B,
@@ -2121,17 +2129,23 @@ int b4r_attn32_core_bwd_launch(const float* qkv, const int64_t* mask, const floa
   B4R_CHECK_ARG(!dropping || keep_bits, B4R_E_BADARG, "b4r_attn_bwd: attention dropout needs the forward's keep_bits");
   const size_t sh = (size_t)core_bwd_lds(p.NT);
   const dim3 grid((unsigned)(B * heads)), block((unsigned)(64 * p.NT));
-  int rc;
-  if (dropping) {
-    rc = b4r_raise_lds((const void*)attn32_core_bwd_kernel<true>, sh, "b4r_attn_bwd");
-    if (rc) return rc;
-    hipLaunchKernelGGL((attn32_core_bwd_kernel<true>), grid, block, sh, stream, p);
-  } else {
-    rc = b4r_raise_lds((const void*)attn32_core_bwd_kernel<false>, sh, "b4r_attn_bwd");
-    if (rc) return rc;
-    hipLaunchKernelGGL((attn32_core_bwd_kernel<false>), grid, block, sh, stream, p);
-  }
-  B4R_CHECK_LAUNCH("b4r_attn_bwd (32-token tiles)");
+  auto launch = [&](auto terms) -> int {
+    constexpr int TERMS = decltype(terms)::value;
+    int rc;
+    if (dropping) {
+      rc = b4r_raise_lds((const void*)attn32_core_bwd_kernel<true, TERMS>, sh, "b4r_attn_bwd");
+      if (rc) return rc;
+      hipLaunchKernelGGL((attn32_core_bwd_kernel<true, TERMS>), grid, block, sh, stream, p);
+    } else {
+      rc = b4r_raise_lds((const void*)attn32_core_bwd_kernel<false, TERMS>, sh, "b4r_attn_bwd");
+      if (rc) return rc;
+      hipLaunchKernelGGL((attn32_core_bwd_kernel<false, TERMS>), grid, block, sh, stream, p);
+    }
+    return B4R_OK;
+  };
+  const int rc = b4r_gemm_terms() == 1 ? launch(std::integral_constant<int, 1>{}) : launch(std::integral_constant<int, 3>{});
+  if (rc) return rc;
+  B4R_CHECK_LAUNCH(b4r_gemm_terms() == 1 ? "b4r_attn_bwd (32-token tiles, bf16)" : "b4r_attn_bwd (32-token tiles)");
   return B4R_OK;
 }
 
@@ -2143,7 +2157,7 @@ int64_t b4r_attn32_keep_words(int32_t B, int32_t L, int32_t heads) {
 
 // ---- the attention core on the masked-LM slots' queries only (b4r_model.hip: the last layer under B4R_FLAG_HEAD_ROWS_ONLY) -------------
 bool b4r_attn32_slotq_supported(int L, int P) {
-  return L > 64 && L <= 224 && P > 0 && P <= 64 && 2 * P <= L && b4r_get_gemm_mode() == B4R_GEMM_BF16X3;
+  return L > 64 && L <= 224 && P > 0 && P <= 64 && 2 * P <= L && b4r_split_mode();
 }
 int64_t b4r_attn32_slotq_keep_words(int B, int L, int heads, int P) {
   return (int64_t)B * heads * b4r_cdiv(L, 32) * b4r_cdiv(P, 32) * 32;

@@ -13,6 +13,7 @@
 // the step adds sum over the 32 slots to a 16x16 accumulator (C/D map: col = lane & 15, row = 4 (lane >> 4) + reg).
 //   * B4R_GEMM_BF16X3: one v_mfma_f32_16x16x32_bf16 per split term (x = hi + lo; Alo.Bhi + Ahi.Blo + Ahi.Bhi), the operands
 //     split in registers (b4r_split8).
+//   * B4R_GEMM_BF16: the same with the hi term only (Ahi.Bhi: operands rounded once to bf16, one MFMA per step).
 //   * B4R_GEMM_F32: eight v_mfma_f32_16x16x4_f32, slot j of every lane group in the j-th (exact fp32 products).
 // A product that consumes accumulator tiles takes two of them per step: slot (g, j) is row 16 t0 + 4g + j for j < 4 and row
 // 16 t1 + 4g + j - 4 for j >= 4 (t0, t1 = an even / odd tile pair), on both operands.
@@ -41,23 +42,27 @@ struct Attn64P {
   DropArgs drop;
 };
 
-// one operand of an 8-slot step: fp32 values, or their bf16 hi / lo split
+// one operand of an 8-slot step: fp32 values, or their bf16 hi / lo split.  TERMS = bf16 MFMAs per step: 3 (B4R_GEMM_BF16X3),
+// 1 (B4R_GEMM_BF16: the lo half is never read, so its split is dead code), 0 (B4R_GEMM_F32: the exact fp32 MFMAs)
 struct Op8 {
   f32x8 v;
   b4r_bf16x8 h, l;
 };
-template <bool BF>
+template <int TERMS>
 __device__ __forceinline__ Op8 op8(const f32x8 x) {
   Op8 o;
   o.v = x;
-  if constexpr (BF) b4r_split8(x, o.h, o.l);
+  if constexpr (TERMS != 0) b4r_split8(x, o.h, o.l);
   return o;
 }
-template <bool BF>
+template <int TERMS>
 __device__ __forceinline__ f32x4 mma8(const Op8& a, const Op8& b, f32x4 c) {
-  if constexpr (BF) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.l, b.h, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.h, b.l, c, 0, 0, 0);
+  static_assert(TERMS == 0 || TERMS == 1 || TERMS == 3, "0 (fp32), 1 or 3 bf16 terms");
+  if constexpr (TERMS != 0) {
+    if constexpr (TERMS == 3) {
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.l, b.h, c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.h, b.l, c, 0, 0, 0);
+    }
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.h, b.h, c, 0, 0, 0);
   } else {
 #pragma unroll
@@ -129,7 +134,7 @@ __device__ __forceinline__ float key_add(const int64_t* mask, int64_t row0, int 
 // -----------------------------------------------------------------------------------------------------------
 // forward: workgroup = 128 queries of one (batch, head); wave = 16 queries x all keys.  LDS: [K | V | sAdd]
 // -----------------------------------------------------------------------------------------------------------
-template <bool BF, int KT>
+template <int TERMS, int KT>
 __global__ __launch_bounds__(64 * WAVES) void attn64_fwd_kernel(Attn64P p) {
   static_assert(KT % 2 == 0, "tiles are consumed in pairs");
   extern __shared__ __attribute__((aligned(16))) float smem64[];
@@ -146,7 +151,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn64_fwd_kernel(Attn64P p) {
   const int q = q0 + 16 * wave + i;
 
   const float* qrow = p.qkv + (row0 + min(q, L - 1)) * ld3 + hd * HD + 8 * g;
-  const Op8 qf0 = op8<BF>(load8(qrow)), qf1 = op8<BF>(load8(qrow + 32));
+  const Op8 qf0 = op8<TERMS>(load8(qrow)), qf1 = op8<TERMS>(load8(qrow + 32));
   stage_rows(sK, p.qkv + H + hd * HD, row0, ld3, Lp, L);
   stage_rows(sV, p.qkv + 2 * H + hd * HD, row0, ld3, Lp, L);
   for (int k = threadIdx.x; k < Lp; k += 64 * WAVES) sAdd[k] = key_add(p.mask, row0, k, L);
@@ -157,8 +162,8 @@ __global__ __launch_bounds__(64 * WAVES) void attn64_fwd_kernel(Attn64P p) {
 #pragma unroll
   for (int t = 0; t < KT; ++t) {   // S^T = K.Q^T: lane holds keys 16t + 4g + r of query i
     f32x4 c = {0.f, 0.f, 0.f, 0.f};
-    c = mma8<BF>(op8<BF>(row_frag(sK, 16 * t + i, 0, g)), qf0, c);
-    c = mma8<BF>(op8<BF>(row_frag(sK, 16 * t + i, 1, g)), qf1, c);
+    c = mma8<TERMS>(op8<TERMS>(row_frag(sK, 16 * t + i, 0, g)), qf0, c);
+    c = mma8<TERMS>(op8<TERMS>(row_frag(sK, 16 * t + i, 1, g)), qf1, c);
     acc[t] = c;
   }
   float m = -INFINITY;
@@ -200,9 +205,9 @@ __global__ __launch_bounds__(64 * WAVES) void attn64_fwd_kernel(Attn64P p) {
   for (int c = 0; c < 4; ++c) o[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int tp = 0; tp < KT / 2; ++tp) {   // O^T[dd][query] += V^T[dd][keys of two tiles] . P^T[keys][query]
-    const Op8 pb = op8<BF>(cat(acc[2 * tp], acc[2 * tp + 1]));
+    const Op8 pb = op8<TERMS>(cat(acc[2 * tp], acc[2 * tp + 1]));
 #pragma unroll
-    for (int c = 0; c < 4; ++c) o[c] = mma8<BF>(op8<BF>(col_frag(sV, tp, 16 * c + i, g)), pb, o[c]);
+    for (int c = 0; c < 4; ++c) o[c] = mma8<TERMS>(op8<TERMS>(col_frag(sV, tp, 16 * c + i, g)), pb, o[c]);
   }
   if (q < L) {
     float* dst = p.ctx_out + (row0 + q) * H + hd * HD + 4 * g;
@@ -215,7 +220,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn64_fwd_kernel(Attn64P p) {
 // backward: blocks [0, nx) form dQ of 128 queries (LDS [K | V | sAdd]); blocks [nx, 2 nx) form dK / dV of 128 keys
 // (LDS [Q | dO | sLse | sD]).  Probabilities recomputed from the saved log-sum-exp.
 // -----------------------------------------------------------------------------------------------------------
-template <bool BF>
+template <int TERMS>
 __device__ __forceinline__ void bwd_dq(const Attn64P p, float* smem, int b, int hd, int q0, float amax) {
   const int KT = p.KT, Lp = KT * 16;
   float* sK = smem;
@@ -241,8 +246,8 @@ __device__ __forceinline__ void bwd_dq(const Attn64P p, float* smem, int b, int 
     s += __shfl_xor(s, 32, 64);
     Dq = s;
   }
-  const Op8 qf0 = op8<BF>(load8(qrow)), qf1 = op8<BF>(load8(qrow + 32));
-  const Op8 df0 = op8<BF>(do0), df1 = op8<BF>(do1);
+  const Op8 qf0 = op8<TERMS>(load8(qrow)), qf1 = op8<TERMS>(load8(qrow + 32));
+  const Op8 df0 = op8<TERMS>(do0), df1 = op8<TERMS>(do1);
   stage_rows(sK, p.qkv + H + hd * HD, row0, ld3, Lp, L);
   stage_rows(sV, p.qkv + 2 * H + hd * HD, row0, ld3, Lp, L);
   for (int k = threadIdx.x; k < Lp; k += 64 * WAVES) sAdd[k] = key_add(p.mask, row0, k, L);
@@ -263,10 +268,10 @@ __device__ __forceinline__ void bwd_dq(const Attn64P p, float* smem, int b, int 
     for (int u = 0; u < 2; ++u) {
       const int t = 2 * tp + u;
       f32x4 sc = {0.f, 0.f, 0.f, 0.f}, da = {0.f, 0.f, 0.f, 0.f};
-      sc = mma8<BF>(op8<BF>(row_frag(sK, 16 * t + i, 0, g)), qf0, sc);
-      sc = mma8<BF>(op8<BF>(row_frag(sK, 16 * t + i, 1, g)), qf1, sc);
-      da = mma8<BF>(op8<BF>(row_frag(sV, 16 * t + i, 0, g)), df0, da);
-      da = mma8<BF>(op8<BF>(row_frag(sV, 16 * t + i, 1, g)), df1, da);
+      sc = mma8<TERMS>(op8<TERMS>(row_frag(sK, 16 * t + i, 0, g)), qf0, sc);
+      sc = mma8<TERMS>(op8<TERMS>(row_frag(sK, 16 * t + i, 1, g)), qf1, sc);
+      da = mma8<TERMS>(op8<TERMS>(row_frag(sV, 16 * t + i, 0, g)), df0, da);
+      da = mma8<TERMS>(op8<TERMS>(row_frag(sV, 16 * t + i, 1, g)), df1, da);
       const f32x4 ad = *reinterpret_cast<const f32x4*>(&sAdd[16 * t + 4 * g]);
       B4rKeep4 k4 = {{true, true, true, true}};
       if (dctx.on) k4 = b4r_keep4p(dctx, dbase + (uint64_t)(16 * t + 4 * g));
@@ -278,9 +283,9 @@ __device__ __forceinline__ void bwd_dq(const Attn64P p, float* smem, int b, int 
         ds[u][r] = pr * (dA - Dq);
       }
     }
-    const Op8 db = op8<BF>(cat(ds[0], ds[1]));   // dQ^T[dd][query] += K^T[dd][keys] . dS^T[keys][query]
+    const Op8 db = op8<TERMS>(cat(ds[0], ds[1]));   // dQ^T[dd][query] += K^T[dd][keys] . dS^T[keys][query]
 #pragma unroll
-    for (int c = 0; c < 4; ++c) dq[c] = mma8<BF>(op8<BF>(col_frag(sK, tp, 16 * c + i, g)), db, dq[c]);
+    for (int c = 0; c < 4; ++c) dq[c] = mma8<TERMS>(op8<TERMS>(col_frag(sK, tp, 16 * c + i, g)), db, dq[c]);
   }
   if (qlive) {
     float* dst = p.dqkv + (row0 + q) * ld3 + hd * HD + 4 * g;
@@ -289,7 +294,7 @@ __device__ __forceinline__ void bwd_dq(const Attn64P p, float* smem, int b, int 
   }
 }
 
-template <bool BF>
+template <int TERMS>
 __device__ __forceinline__ void bwd_dkv(const Attn64P p, float* smem, int b, int hd, int kb, float amax) {
   const int KT = p.KT, Lp = KT * 16;
   float* sQ = smem;
@@ -304,8 +309,8 @@ __device__ __forceinline__ void bwd_dkv(const Attn64P p, float* smem, int b, int
   const bool klive = key < L;
 
   const float* krow = p.qkv + (row0 + kc) * ld3 + H + hd * HD + 8 * g;
-  const Op8 kf0 = op8<BF>(load8(krow)), kf1 = op8<BF>(load8(krow + 32));
-  const Op8 vf0 = op8<BF>(load8(krow + H)), vf1 = op8<BF>(load8(krow + H + 32));
+  const Op8 kf0 = op8<TERMS>(load8(krow)), kf1 = op8<TERMS>(load8(krow + 32));
+  const Op8 vf0 = op8<TERMS>(load8(krow + H)), vf1 = op8<TERMS>(load8(krow + H + 32));
   stage_rows(sQ, p.qkv + hd * HD, row0, ld3, Lp, L);
   stage_rows(sdO, p.dctx + hd * HD, row0, H, Lp, L);
   rowdot_head(sD, p.dctx + hd * HD, p.ctx + hd * HD, row0, H, Lp, L);
@@ -327,10 +332,10 @@ __device__ __forceinline__ void bwd_dkv(const Attn64P p, float* smem, int b, int
     for (int u = 0; u < 2; ++u) {   // S = Q.K^T: lane holds queries 16t + 4g + r of key i
       const int t = 2 * tp + u;
       f32x4 sc = {0.f, 0.f, 0.f, 0.f}, da = {0.f, 0.f, 0.f, 0.f};
-      sc = mma8<BF>(op8<BF>(row_frag(sQ, 16 * t + i, 0, g)), kf0, sc);
-      sc = mma8<BF>(op8<BF>(row_frag(sQ, 16 * t + i, 1, g)), kf1, sc);
-      da = mma8<BF>(op8<BF>(row_frag(sdO, 16 * t + i, 0, g)), vf0, da);
-      da = mma8<BF>(op8<BF>(row_frag(sdO, 16 * t + i, 1, g)), vf1, da);
+      sc = mma8<TERMS>(op8<TERMS>(row_frag(sQ, 16 * t + i, 0, g)), kf0, sc);
+      sc = mma8<TERMS>(op8<TERMS>(row_frag(sQ, 16 * t + i, 1, g)), kf1, sc);
+      da = mma8<TERMS>(op8<TERMS>(row_frag(sdO, 16 * t + i, 0, g)), vf0, da);
+      da = mma8<TERMS>(op8<TERMS>(row_frag(sdO, 16 * t + i, 1, g)), vf1, da);
       const f32x4 ls = *reinterpret_cast<const f32x4*>(&sLse[16 * t + 4 * g]);
       const f32x4 dd = *reinterpret_cast<const f32x4*>(&sD[16 * t + 4 * g]);
 #pragma unroll
@@ -347,11 +352,11 @@ __device__ __forceinline__ void bwd_dkv(const Attn64P p, float* smem, int b, int
         ds[u][r] = pr * (dA - dd[r]);
       }
     }
-    const Op8 pb = op8<BF>(cat(pa[0], pa[1])), db = op8<BF>(cat(ds[0], ds[1]));
+    const Op8 pb = op8<TERMS>(cat(pa[0], pa[1])), db = op8<TERMS>(cat(ds[0], ds[1]));
 #pragma unroll
     for (int c = 0; c < 4; ++c) {   // dV^T[dd][key] += dO^T[dd][queries] . A[queries][key] ; dK^T += Q^T . dS
-      dv[c] = mma8<BF>(op8<BF>(col_frag(sdO, tp, 16 * c + i, g)), pb, dv[c]);
-      dk[c] = mma8<BF>(op8<BF>(col_frag(sQ, tp, 16 * c + i, g)), db, dk[c]);
+      dv[c] = mma8<TERMS>(op8<TERMS>(col_frag(sdO, tp, 16 * c + i, g)), pb, dv[c]);
+      dk[c] = mma8<TERMS>(op8<TERMS>(col_frag(sQ, tp, 16 * c + i, g)), db, dk[c]);
     }
   }
   if (klive) {
@@ -364,13 +369,13 @@ __device__ __forceinline__ void bwd_dkv(const Attn64P p, float* smem, int b, int
   }
 }
 
-template <bool BF>
+template <int TERMS>
 __global__ __launch_bounds__(64 * WAVES) void attn64_bwd_kernel(Attn64P p) {
   extern __shared__ __attribute__((aligned(16))) float smem64[];
   const int b = blockIdx.z, hd = blockIdx.y;
   const float amax = b4r_seq_amax(p.mask + (int64_t)b * p.L, p.L);   // all threads, before any early exit
-  if ((int)blockIdx.x < p.nx) bwd_dq<BF>(p, smem64, b, hd, blockIdx.x * ROWS_WG, amax);
-  else bwd_dkv<BF>(p, smem64, b, hd, blockIdx.x - p.nx, amax);
+  if ((int)blockIdx.x < p.nx) bwd_dq<TERMS>(p, smem64, b, hd, blockIdx.x * ROWS_WG, amax);
+  else bwd_dkv<TERMS>(p, smem64, b, hd, blockIdx.x - p.nx, amax);
 }
 
 // 16-row tiles of the forward's key sweep (even; compile-time: the score tiles live in registers)
@@ -395,7 +400,7 @@ int check64(const char* who, const float* qkv, const int64_t* mask, int B, int L
   return B4R_OK;
 }
 
-template <bool BF>
+template <int TERMS>
 int fwd_launch(const Attn64P& p, hipStream_t stream) {
   const int KT = fwd_tiles(p.L);
   const size_t sh = ((size_t)2 * KT * 16 * HD + KT * 16) * sizeof(float);
@@ -403,9 +408,9 @@ int fwd_launch(const Attn64P& p, hipStream_t stream) {
   int rc = B4R_OK;
 #define FWD_CASE(KT_)                                                                                    \
   case KT_:                                                                                              \
-    rc = set_lds(attn64_fwd_kernel<BF, KT_>, sh);                                                        \
+    rc = set_lds(attn64_fwd_kernel<TERMS, KT_>, sh);                                                        \
     if (rc) return rc;                                                                                   \
-    hipLaunchKernelGGL((attn64_fwd_kernel<BF, KT_>), grid, dim3(64 * WAVES), sh, stream, p);             \
+    hipLaunchKernelGGL((attn64_fwd_kernel<TERMS, KT_>), grid, dim3(64 * WAVES), sh, stream, p);             \
     break;
   switch (KT) {
     FWD_CASE(2) FWD_CASE(4) FWD_CASE(8) FWD_CASE(14) FWD_CASE(16)
@@ -415,12 +420,12 @@ int fwd_launch(const Attn64P& p, hipStream_t stream) {
   return B4R_OK;
 }
 
-template <bool BF>
+template <int TERMS>
 int bwd_launch(const Attn64P& p, hipStream_t stream) {
   const size_t sh = ((size_t)2 * p.KT * 16 * HD + 2 * p.KT * 16) * sizeof(float);
-  const int rc = set_lds(attn64_bwd_kernel<BF>, sh);
+  const int rc = set_lds(attn64_bwd_kernel<TERMS>, sh);
   if (rc) return rc;
-  hipLaunchKernelGGL(attn64_bwd_kernel<BF>, dim3(2 * p.nx, p.heads, p.B), dim3(64 * WAVES), sh, stream, p);
+  hipLaunchKernelGGL(attn64_bwd_kernel<TERMS>, dim3(2 * p.nx, p.heads, p.B), dim3(64 * WAVES), sh, stream, p);
   return B4R_OK;
 }
 
@@ -440,7 +445,9 @@ extern "C" int b4r_attn_fwd_hd(const float* qkv, const int64_t* input_mask, int3
   p.qkv = qkv; p.mask = input_mask; p.ctx_out = ctx; p.lse_out = lse;
   p.B = B; p.L = L; p.heads = heads; p.H = heads * HD;
   p.drop = b4r_make_drop(rng, drop_stream, drop_rate, 1);
-  rc = b4r_get_gemm_mode() == B4R_GEMM_BF16X3 ? fwd_launch<true>(p, (hipStream_t)stream) : fwd_launch<false>(p, (hipStream_t)stream);
+  const int terms = b4r_gemm_terms();
+  rc = terms == 3 ? fwd_launch<3>(p, (hipStream_t)stream) : terms == 1 ? fwd_launch<1>(p, (hipStream_t)stream)
+                                                                      : fwd_launch<0>(p, (hipStream_t)stream);
   if (rc) return rc;
   B4R_CHECK_LAUNCH("b4r_attn_fwd_hd");
   return B4R_OK;
@@ -462,7 +469,9 @@ extern "C" int b4r_attn_bwd_hd(const float* qkv, const int64_t* input_mask, cons
   p.B = B; p.L = L; p.heads = heads; p.H = heads * HD; p.qscale = qscale;
   p.KT = even_tiles(L); p.nx = b4r_cdiv(L, ROWS_WG);
   p.drop = b4r_make_drop(rng, drop_stream, drop_rate, 1);
-  rc = b4r_get_gemm_mode() == B4R_GEMM_BF16X3 ? bwd_launch<true>(p, (hipStream_t)stream) : bwd_launch<false>(p, (hipStream_t)stream);
+  const int terms = b4r_gemm_terms();
+  rc = terms == 3 ? bwd_launch<3>(p, (hipStream_t)stream) : terms == 1 ? bwd_launch<1>(p, (hipStream_t)stream)
+                                                                      : bwd_launch<0>(p, (hipStream_t)stream);
   if (rc) return rc;
   B4R_CHECK_LAUNCH("b4r_attn_bwd_hd");
   return B4R_OK;

@@ -735,7 +735,7 @@ int64_t b4r_attn_rx_keep_words(int B, int L, int heads);
 bool b4r_attn32_active(int H, int heads, int L) { return b4r_attn32_preferred(H, heads, L) != 0; }
 
 extern "C" int32_t b4r_attn_block_supported(int32_t hidden_size, int32_t num_heads, int32_t L) {
-  return (hidden_size == HID && num_heads == 2 && L > 0 && L <= 256 && b4r_get_gemm_mode() == B4R_GEMM_BF16X3) ? 1 : 0;
+  return (hidden_size == HID && num_heads == 2 && L > 0 && L <= 256 && b4r_split_mode()) ? 1 : 0;
 }
 
 extern "C" int32_t b4r_attn_block_bwd_supported(int32_t hidden_size, int32_t num_heads, int32_t L) {

@@ -73,7 +73,7 @@ __device__ __forceinline__ void rowdot_head(float* sD, const float* dO, const fl
 // forward: workgroup = 128 queries of one (batch, head); wave = 16 queries x all keys
 // LDS: [K hi | K lo | V hi | V lo | sAdd]
 // -----------------------------------------------------------------------------------------------------------
-template <int KT>
+template <int KT, int TERMS = 3>
 __global__ __launch_bounds__(64 * WAVES) void attn_rx_fwd_kernel(AttnRxP p) {
   extern __shared__ __attribute__((aligned(16))) char smem_rx[];
   constexpr int KTE = (KT + 1) & ~1, LPE = KTE * 16;
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_rx_fwd_kernel(AttnRxP p) {
   stage_fetch(st, p.qkv + H + hd * 32, ld3, p.qkv + 2 * H + hd * 32, ld3, row0, L);
   const int kk = min((int)threadIdx.x, L - 1);   // LPE <= 256 < workgroup size
   const float madd = (1.0f - (float)p.mask[row0 + kk]) * -1e9f;
-  stage_write(st, img, LPE, L);
+  stage_write<4, TILE_BYTES, TERMS>(st, img, LPE, L);
   if (threadIdx.x < LPE) sAdd[threadIdx.x] = (int)threadIdx.x < L ? madd : -INFINITY;
   bf16x8 qh, ql;
   split8(qx, qh, ql);
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_rx_fwd_kernel(AttnRxP p) {
   for (int t = 0; t < KTE; ++t) {
     acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const char* tile = img + fa.row + TILE_BYTES * t;
-    if (t < KT) acc[t] = mfma3(row_frag<0>(tile), row_frag<1>(tile), qh, ql, acc[t]);   // S^T = K.Q^T
+    if (t < KT) acc[t] = mfma3<TERMS>(row_frag<0>(tile), row_frag<1>(tile), qh, ql, acc[t]);   // S^T = K.Q^T
   }
   float m = -INFINITY;
 #pragma unroll
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_rx_fwd_kernel(AttnRxP p) {
 #pragma unroll
     for (int db = 0; db < 2; ++db) {
       const char* tile = img + fa.tr[db] + TILE_BYTES * 2 * tp;
-      o[db] = mfma3(tr_frag<2>(tile), tr_frag<3>(tile), ph, pl, o[db]);
+      o[db] = mfma3<TERMS>(tr_frag<2>(tile), tr_frag<3>(tile), ph, pl, o[db]);
     }
   }
   if (q < L) {
@@ -189,6 +189,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_rx_fwd_kernel(AttnRxP p) {
 // backward, dQ: same decomposition as the forward; probabilities recomputed from the saved log-sum-exp
 // LDS: [K hi | K lo | V hi | V lo | sAdd | sD]
 // -----------------------------------------------------------------------------------------------------------
+template <int TERMS = 3>
 __global__ __launch_bounds__(64 * WAVES) void attn_rx_dq_kernel(AttnRxP p) {
   extern __shared__ __attribute__((aligned(16))) char smem_rx[];
   const int KTE = p.KTE, LPE = KTE * 16;
@@ -214,7 +215,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_rx_dq_kernel(AttnRxP p) {
   const int kk = min((int)threadIdx.x, L - 1);   // LPE <= 256 < workgroup size
   const float madd = (1.0f - (float)p.mask[row0 + kk]) * -1e9f;
   rowdot_head(sD, p.dctx + hd * 32, p.ctx + hd * 32, row0 + q0, H, ROWS_WG, L - q0);
-  stage_write(st, img, LPE, L);
+  stage_write<4, TILE_BYTES, TERMS>(st, img, LPE, L);
   if (threadIdx.x < LPE) sAdd[threadIdx.x] = (int)threadIdx.x < L ? madd : -INFINITY;
   bf16x8 qh, ql, doh, dol;
   split8(qx, qh, ql);
@@ -245,8 +246,8 @@ __global__ __launch_bounds__(64 * WAVES) void attn_rx_dq_kernel(AttnRxP p) {
       const int t = 2 * tp + u;
       const f32x4 z = {0.f, 0.f, 0.f, 0.f};
       const char* tile = img + fa.row + TILE_BYTES * t;
-      const f32x4 sc = mfma3(row_frag<0>(tile), row_frag<1>(tile), qh, ql, z);     // S^T = K.Q^T
-      const f32x4 da = mfma3(row_frag<2>(tile), row_frag<3>(tile), doh, dol, z);   // dA^T = V.dO^T
+      const f32x4 sc = mfma3<TERMS>(row_frag<0>(tile), row_frag<1>(tile), qh, ql, z);     // S^T = K.Q^T
+      const f32x4 da = mfma3<TERMS>(row_frag<2>(tile), row_frag<3>(tile), doh, dol, z);   // dA^T = V.dO^T
       const f32x4 ad = *reinterpret_cast<const f32x4*>(&sAdd[16 * t + 4 * g]);
       const uint32_t nib = w[(t >> 3) & 1] >> (4 * (t & 7));
 #pragma unroll
@@ -261,7 +262,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_rx_dq_kernel(AttnRxP p) {
 #pragma unroll
     for (int db = 0; db < 2; ++db) {   // dQ^T[dk][query] += K^T[dk][keys] . dS^T[keys][query]
       const char* tile = img + fa.tr[db] + TILE_BYTES * 2 * tp;
-      dq[db] = mfma3(tr_frag<0>(tile), tr_frag<1>(tile), dsh, dsl, dq[db]);
+      dq[db] = mfma3<TERMS>(tr_frag<0>(tile), tr_frag<1>(tile), dsh, dsl, dq[db]);
     }
   }
   if (qlive) {
@@ -275,6 +276,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_rx_dq_kernel(AttnRxP p) {
 // backward, dK / dV: workgroup = 128 keys of one (batch, head); wave = 16 keys x all queries
 // LDS: [Q hi | Q lo | dO hi | dO lo | sLse | sD]
 // -----------------------------------------------------------------------------------------------------------
+template <int TERMS = 3>
 __global__ __launch_bounds__(64 * WAVES) void attn_rx_dkv_kernel(AttnRxP p) {
   extern __shared__ __attribute__((aligned(16))) char smem_rx[];
   const int KTE = p.KTE, LPE = KTE * 16;
@@ -301,7 +303,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_rx_dkv_kernel(AttnRxP p) {
   stage_fetch(st, p.qkv + hd * 32, ld3, p.dctx + hd * 32, H, row0, L);
   const float lse_k = p.lse_in[bh * L + min((int)threadIdx.x, L - 1)];   // LPE <= 256 < workgroup size
   rowdot_head(sD, p.dctx + hd * 32, p.ctx + hd * 32, row0, H, LPE, L);
-  stage_write(st, img, LPE, L);
+  stage_write<4, TILE_BYTES, TERMS>(st, img, LPE, L);
   if (threadIdx.x < LPE) sLse[threadIdx.x] = (int)threadIdx.x < L ? lse_k : INFINITY;   // +inf => probability 0 for pad queries
   bf16x8 kh, kl, vh, vl;
   split8(kx, kh, kl);
@@ -333,8 +335,8 @@ __global__ __launch_bounds__(64 * WAVES) void attn_rx_dkv_kernel(AttnRxP p) {
       if (dctx.on)   // query tiles beyond the forward's (odd KT) hold only pad queries: any word will do
         wq_n[u] = *reinterpret_cast<const u32x4*>(wbase + (int64_t)min(t, p.KT - 1) * 128);
       const char* tile = img + fa.row + TILE_BYTES * t;
-      sc_n[u] = mfma3(row_frag<0>(tile), row_frag<1>(tile), kh, kl, z);   // S = Q.K^T
-      da_n[u] = mfma3(row_frag<2>(tile), row_frag<3>(tile), vh, vl, z);   // dA = dO.V^T
+      sc_n[u] = mfma3<TERMS>(row_frag<0>(tile), row_frag<1>(tile), kh, kl, z);   // S = Q.K^T
+      da_n[u] = mfma3<TERMS>(row_frag<2>(tile), row_frag<3>(tile), vh, vl, z);   // dA = dO.V^T
     }
   };
   lookahead(0);
@@ -365,8 +367,8 @@ __global__ __launch_bounds__(64 * WAVES) void attn_rx_dkv_kernel(AttnRxP p) {
     for (int db = 0; db < 2; ++db) {
       // dV^T[dd][key] += dO^T[dd][queries] . Pd[queries][key] ;  dK^T[dk][key] += Q^T[dk][queries] . dS[queries][key]
       const char* tile = img + fa.tr[db] + TILE_BYTES * 2 * tp;
-      dv[db] = mfma3(tr_frag<2>(tile), tr_frag<3>(tile), pdh, pdl, dv[db]);
-      dk[db] = mfma3(tr_frag<0>(tile), tr_frag<1>(tile), dsh, dsl, dk[db]);
+      dv[db] = mfma3<TERMS>(tr_frag<2>(tile), tr_frag<3>(tile), pdh, pdl, dv[db]);
+      dk[db] = mfma3<TERMS>(tr_frag<0>(tile), tr_frag<1>(tile), dsh, dsl, dk[db]);
     }
   }
   if (klive) {
@@ -398,6 +400,43 @@ int b4r_attn32_core_bwd_launch(const float* qkv, const int64_t* mask, const floa
                                int L, int heads, float qscale, float* dqkv, const DropArgs& drop, const uint32_t* keep_bits,
                                hipStream_t stream);
 
+template <int TERMS>
+static int rx_fwd_launch(AttnRxP p, int KTt, hipStream_t stream) {
+  const size_t sh = (size_t)4 * p.KTE * 16 * 64 + (size_t)p.KTE * 16 * sizeof(float);
+  const dim3 grid = wg_grid(b4r_cdiv(p.L, ROWS_WG), p.heads, p.B);
+  int rc;
+#define FWD_CASE(KT_)                                                                                      \
+  case KT_:                                                                                                \
+    rc = set_lds(attn_rx_fwd_kernel<KT_, TERMS>, sh);                                                      \
+    if (rc) return rc;                                                                                     \
+    hipLaunchKernelGGL((attn_rx_fwd_kernel<KT_, TERMS>), grid, dim3(64 * WAVES), sh, stream, p);           \
+    break;
+  switch (KTt) {
+    FWD_CASE(4) FWD_CASE(8) FWD_CASE(13) FWD_CASE(16)
+    default: b4r_set_error("b4r_attn_fwd: internal"); return B4R_E_SHAPE;
+  }
+#undef FWD_CASE
+  B4R_CHECK_LAUNCH(TERMS == 1 ? "b4r_attn_fwd (bf16)" : "b4r_attn_fwd (bf16x3)");
+  return B4R_OK;
+}
+
+template <int TERMS>
+static int rx_bwd_launch(const AttnRxP& p, hipStream_t stream) {
+  const dim3 grid = wg_grid(b4r_cdiv(p.L, ROWS_WG), p.heads, p.B);
+  const size_t planes = (size_t)4 * p.KTE * 16 * 64;
+  const size_t sh_dq = planes + ((size_t)p.KTE * 16 + ROWS_WG) * sizeof(float);
+  int rc = set_lds(attn_rx_dq_kernel<TERMS>, sh_dq);
+  if (rc) return rc;
+  hipLaunchKernelGGL(attn_rx_dq_kernel<TERMS>, grid, dim3(64 * WAVES), sh_dq, stream, p);
+  B4R_CHECK_LAUNCH(TERMS == 1 ? "b4r_attn_bwd dq (bf16)" : "b4r_attn_bwd dq (bf16x3)");
+  const size_t sh_kv = planes + (size_t)2 * p.KTE * 16 * sizeof(float);
+  rc = set_lds(attn_rx_dkv_kernel<TERMS>, sh_kv);
+  if (rc) return rc;
+  hipLaunchKernelGGL(attn_rx_dkv_kernel<TERMS>, grid, dim3(64 * WAVES), sh_kv, stream, p);
+  B4R_CHECK_LAUNCH(TERMS == 1 ? "b4r_attn_bwd dkv (bf16)" : "b4r_attn_bwd dkv (bf16x3)");
+  return B4R_OK;
+}
+
 int b4r_attn_rx_fwd_launch(const float* qkv, const int64_t* mask, int B, int L, int heads, float* ctx, float* lse,
                            const DropArgs& drop, uint32_t* keep_bits, hipStream_t stream) {
   // The forward stays on the 16-token-tile kernel below (ML-20M shape: 110 us against 133 for the 32-token-tile core, whose 112
@@ -415,22 +454,7 @@ int b4r_attn_rx_fwd_launch(const float* qkv, const int64_t* mask, int B, int L, 
   const int KTt = p.KT <= 4 ? 4 : p.KT <= 8 ? 8 : p.KT <= 13 ? 13 : 16;
   p.KT = b4r_cdiv(L, 16);
   p.KTE = (KTt + 1) & ~1;
-  const size_t sh = (size_t)4 * p.KTE * 16 * 64 + (size_t)p.KTE * 16 * sizeof(float);
-  const dim3 grid = wg_grid(b4r_cdiv(L, ROWS_WG), heads, B);
-  int rc;
-#define FWD_CASE(KT_)                                                                                      \
-  case KT_:                                                                                                \
-    rc = set_lds(attn_rx_fwd_kernel<KT_>, sh);                                                             \
-    if (rc) return rc;                                                                                     \
-    hipLaunchKernelGGL((attn_rx_fwd_kernel<KT_>), grid, dim3(64 * WAVES), sh, stream, p);                  \
-    break;
-  switch (KTt) {
-    FWD_CASE(4) FWD_CASE(8) FWD_CASE(13) FWD_CASE(16)
-    default: b4r_set_error("b4r_attn_fwd: internal"); return B4R_E_SHAPE;
-  }
-#undef FWD_CASE
-  B4R_CHECK_LAUNCH("b4r_attn_fwd (bf16x3)");
-  return B4R_OK;
+  return b4r_gemm_terms() == 1 ? rx_fwd_launch<1>(p, KTt, stream) : rx_fwd_launch<3>(p, KTt, stream);
 }
 
 int b4r_attn_rx_bwd_launch(const float* qkv, const int64_t* mask, const float* ctx, const float* lse, const float* dctx,
@@ -444,17 +468,5 @@ int b4r_attn_rx_bwd_launch(const float* qkv, const int64_t* mask, const float* c
   p.KT = b4r_cdiv(L, 16);
   p.KTE = (p.KT + 1) & ~1;
   p.drop = drop;
-  const dim3 grid = wg_grid(b4r_cdiv(L, ROWS_WG), heads, B);
-  const size_t planes = (size_t)4 * p.KTE * 16 * 64;
-  const size_t sh_dq = planes + ((size_t)p.KTE * 16 + ROWS_WG) * sizeof(float);
-  int rc = set_lds(attn_rx_dq_kernel, sh_dq);
-  if (rc) return rc;
-  hipLaunchKernelGGL(attn_rx_dq_kernel, grid, dim3(64 * WAVES), sh_dq, stream, p);
-  B4R_CHECK_LAUNCH("b4r_attn_bwd dq (bf16x3)");
-  const size_t sh_kv = planes + (size_t)2 * p.KTE * 16 * sizeof(float);
-  rc = set_lds(attn_rx_dkv_kernel, sh_kv);
-  if (rc) return rc;
-  hipLaunchKernelGGL(attn_rx_dkv_kernel, grid, dim3(64 * WAVES), sh_kv, stream, p);
-  B4R_CHECK_LAUNCH("b4r_attn_bwd dkv (bf16x3)");
-  return B4R_OK;
+  return b4r_gemm_terms() == 1 ? rx_bwd_launch<1>(p, stream) : rx_bwd_launch<3>(p, stream);
 }

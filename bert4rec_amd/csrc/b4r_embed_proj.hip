@@ -341,7 +341,7 @@ int b4r_embed_proj_fwd_launch(const int64_t* ids, int B, int L, const float* tab
   const dim3 grid(b4r_cdiv(p.N, FR));
   const size_t lds = fwd_lds(E);
   // bf16x3 where K = E <= 64 in the bf16x3 mode, exact fp32 otherwise (include/b4r.h b4r_set_gemm_mode)
-  const bool bf = E == 64 && b4r_get_gemm_mode() == B4R_GEMM_BF16X3;
+  const bool bf = E == 64 && b4r_split_mode();
   const void* k = bf ? reinterpret_cast<const void*>(embed_proj_fwd_kernel<64, true>)
                   : E == 64 ? reinterpret_cast<const void*>(embed_proj_fwd_kernel<64, false>)
                   : E == 128 ? reinterpret_cast<const void*>(embed_proj_fwd_kernel<128, false>)

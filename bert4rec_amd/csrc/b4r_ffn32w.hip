@@ -637,7 +637,7 @@ int f32w_launch_bwd(const F32wPackP* pk, const F32wBwdP& p, hipStream_t stream) 
 }  // namespace
 
 bool b4r_ffn32w_supported(int H, int I) {
-  return (H == 128 || H == 256) && I >= 64 && I % 32 == 0 && b4r_get_gemm_mode() == B4R_GEMM_BF16X3;
+  return (H == 128 || H == 256) && I >= 64 && I % 32 == 0 && b4r_split_mode();
 }
 int64_t b4r_ffn32w_rec_floats(int H, int I) { return ((int64_t)(I / 32) * f32w_rec(H / 32) + 3) / 4; }
 

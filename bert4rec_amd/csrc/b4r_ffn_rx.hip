@@ -525,7 +525,7 @@ extern "C" int b4r_debug_ff_prof(long long* host_out) {
 }
 #endif
 extern "C" int32_t b4r_ffn_block_supported(int32_t hidden_size, int32_t inner_dim) {
-  return (hidden_size == HID && inner_dim == INNER && b4r_get_gemm_mode() == B4R_GEMM_BF16X3) ? 1 : 0;
+  return (hidden_size == HID && inner_dim == INNER && b4r_split_mode()) ? 1 : 0;
 }
 
 // per workgroup: dW1 + dW2 slabs, db1 + db2 strips, 128 LayerNorm partials

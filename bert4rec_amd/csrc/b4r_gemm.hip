@@ -612,15 +612,18 @@ int b4r_gemm_rx_tn_pair_launch(const b4r_gemm_tn_desc* d0, float* scratch0, cons
                                hipStream_t stream);
 static int g_gemm_mode = B4R_GEMM_BF16X3;
 extern "C" int b4r_set_gemm_mode(int mode) {
-  B4R_CHECK_ARG(mode == B4R_GEMM_F32 || mode == B4R_GEMM_BF16X3, B4R_E_BADARG, "b4r_set_gemm_mode: unknown mode %d", mode);
+  B4R_CHECK_ARG(mode == B4R_GEMM_F32 || mode == B4R_GEMM_BF16X3 || mode == B4R_GEMM_BF16, B4R_E_BADARG,
+                "b4r_set_gemm_mode: unknown mode %d", mode);
   g_gemm_mode = mode;
   return B4R_OK;
 }
 extern "C" int b4r_get_gemm_mode(void) { return g_gemm_mode; }
+extern "C" int b4r_split_mode(void) { return g_gemm_mode == B4R_GEMM_BF16X3 || g_gemm_mode == B4R_GEMM_BF16; }
+extern "C" int b4r_gemm_terms(void) { return g_gemm_mode == B4R_GEMM_BF16 ? 1 : g_gemm_mode == B4R_GEMM_BF16X3 ? 3 : 0; }
 
 extern "C" int64_t b4r_gemm_ln_bwd_partial_floats(int32_t M) { return (int64_t)b4r_cdiv(M > 0 ? M : 1, 64) * 128; }
 extern "C" int b4r_gemm_ln_supported(const b4r_gemm_desc* d) {
-  if (d == nullptr || g_gemm_mode != B4R_GEMM_BF16X3 || !d->A || !d->B || !d->C || d->M <= 0) return 0;
+  if (d == nullptr || !b4r_split_mode() || !d->A || !d->B || !d->C || d->M <= 0) return 0;
   if (d->epilogue == B4R_EPI_BIAS_GELU_LN) return b4r_gemm_rx_supported(d) ? 1 : 0;
   return ((d->epilogue == B4R_EPI_BIAS_DROP_RES_LN || d->epilogue == B4R_EPI_ADD_RES_LN_BWD) && d->R && d->ldr >= d->N &&
           b4r_gemm_rx_supported(d)) ? 1 : 0;
@@ -676,7 +679,7 @@ extern "C" int b4r_gemm_f32(const b4r_gemm_desc* d, b4r_stream_t stream) {
                   "b4r_gemm_f32: BIAS_DROP_RES_LN not available for M=%d N=%d K=%d in this mode (b4r_gemm_ln_supported)", d->M,
                   d->N, d->K);
   }
-  if (g_gemm_mode == B4R_GEMM_BF16X3 && b4r_gemm_rx_supported(d)) return b4r_gemm_rx_launch(d, (hipStream_t)stream);
+  if (b4r_split_mode() && b4r_gemm_rx_supported(d)) return b4r_gemm_rx_launch(d, (hipStream_t)stream);
 
   GemmP p;
   p.A = d->A; p.B = d->B; p.C = d->C; p.bias = d->bias; p.C2 = d->C2; p.R = d->R;
@@ -708,7 +711,7 @@ int b4r_gemm_rx_splitk_launch(const b4r_gemm_desc* d, int splits, float* slabs, 
 
 int b4r_gemm_f32_splitk(const b4r_gemm_desc* d, int splits, float* scratch, int k_pad_ok, hipStream_t stream) {
   B4R_CHECK_ARG(d && scratch && d->epilogue == B4R_EPI_NONE && !d->a_dropout, B4R_E_BADARG, "gemm_splitk: plain product only");
-  if (splits > 1 && g_gemm_mode == B4R_GEMM_BF16X3 && b4r_gemm_rx_splitk_supported(d, k_pad_ok)) {
+  if (splits > 1 && b4r_split_mode() && b4r_gemm_rx_splitk_supported(d, k_pad_ok)) {
     int used = 0;
     int rc = b4r_gemm_rx_splitk_launch(d, splits, scratch, &used, stream);
     if (rc) return rc;
@@ -746,7 +749,7 @@ extern "C" int64_t b4r_gemm_tn_scratch_floats(int32_t R, int32_t Mo, int32_t No)
 }
 
 extern "C" int b4r_gemm_tn_dgrad_supported(const b4r_gemm_tn_desc* d) {
-  return (d != nullptr && g_gemm_mode == B4R_GEMM_BF16X3 && d->Mo >= 64 && d->Mo % 64 == 0 && d->No == 64 && d->R > 0 && d->A &&
+  return (d != nullptr && b4r_split_mode() && d->Mo >= 64 && d->Mo % 64 == 0 && d->No == 64 && d->R > 0 && d->A &&
           d->B && d->dgrad_w && d->dgrad_out && d->dgrad_ldw >= 64 && d->dgrad_ldw % 4 == 0 && b4r_aligned16(d->dgrad_w) &&
           d->dgrad_ldo >= d->Mo && (d->dgrad_gelu_pre == nullptr || d->dgrad_ldg >= d->Mo) && b4r_gemm_rx_tn_supported(d)) ? 1 : 0;
 }
@@ -765,7 +768,7 @@ extern "C" int b4r_gemm_tn_f32(const b4r_gemm_tn_desc* d, float* scratch, b4r_st
                   "b4r_gemm_tn_f32: the fused input gradient needs No = 64, Mo %% 64 == 0, aligned operands and the bf16x3 mode "
                   "(b4r_gemm_tn_dgrad_supported)");
   }
-  if (g_gemm_mode == B4R_GEMM_BF16X3 && b4r_gemm_rx_tn_supported(d)) return b4r_gemm_rx_tn_launch(d, scratch, (hipStream_t)stream);
+  if (b4r_split_mode() && b4r_gemm_rx_tn_supported(d)) return b4r_gemm_rx_tn_launch(d, scratch, (hipStream_t)stream);
   const int S = tn_split(d->R, d->Mo, d->No);
   TnP p;
   p.A = d->A; p.B = d->B; p.lda = d->lda; p.ldb = d->ldb;
@@ -794,7 +797,7 @@ int b4r_gemm_tn_pair(const b4r_gemm_tn_desc* d0, float* scratch0, const b4r_gemm
   const bool plain = d0 && d1 && scratch0 && scratch1 && d0->A && d0->B && d0->out && d1->A && d1->B && d1->out && d0->R > 0 &&
                      d1->R > 0 && d0->Mo > 0 && d0->No > 0 && d1->Mo > 0 && d1->No > 0 && d0->lda >= d0->Mo && d0->ldb >= d0->No &&
                      d0->ldo >= d0->No && d1->lda >= d1->Mo && d1->ldb >= d1->No && d1->ldo >= d1->No;
-  if (plain && g_gemm_mode == B4R_GEMM_BF16X3 && b4r_gemm_rx_tn_pair_supported(d0, d1))
+  if (plain && b4r_split_mode() && b4r_gemm_rx_tn_pair_supported(d0, d1))
     return b4r_gemm_rx_tn_pair_launch(d0, scratch0, d1, scratch1, stream);
   int rc = b4r_gemm_tn_f32(d0, scratch0, (b4r_stream_t)stream);
   if (rc) return rc;

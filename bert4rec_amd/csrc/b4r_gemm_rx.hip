@@ -72,9 +72,15 @@ struct RxP {
 
 __device__ __forceinline__ void split8(const f32x8 x, bf16x8& hi, bf16x8& lo) { b4r_split8(x, hi, lo); }
 
+// TERMS = MFMAs per product: 3 (B4R_GEMM_BF16X3: Alo.Bhi + Ahi.Blo + Ahi.Bhi) or 1 (B4R_GEMM_BF16: Ahi.Bhi).  The one-term
+// instances never read a lo operand, so its split, its LDS image stores and its loads are gone from them
+template <int TERMS = 3>
 __device__ __forceinline__ f32x16 mfma3(const bf16x8 ah, const bf16x8 al, const bf16x8 bh, const bf16x8 bl, f32x16 acc) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+  static_assert(TERMS == 1 || TERMS == 3, "one or three terms");
+  if constexpr (TERMS == 3) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+  }
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
   return acc;
 }
@@ -383,7 +389,7 @@ __device__ __forceinline__ void epilogue_tile_ln_bwd(const RxP& p, const DropCtx
 // columns [N, n_store) of C (and C2) may be written, of R may be read
 
 // ---- B as [K,N]: register operands, no barriers ----------------------------------------------------------------------
-template <int EPI, bool A_DROP, int NKB>
+template <int EPI, bool A_DROP, int NKB, int TERMS = 3>
 __global__ __launch_bounds__(256) void rx_gemm_kn_kernel(RxP p) {
   extern __shared__ __attribute__((aligned(16))) float s_lds[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -431,13 +437,13 @@ __global__ __launch_bounds__(256) void rx_gemm_kn_kernel(RxP p) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) acc = mfma3(ah[kb], al[kb], bh[kb], bl[kb], acc);
+    for (int kb = 0; kb < NKB; ++kb) acc = mfma3<TERMS>(ah[kb], al[kb], bh[kb], bl[kb], acc);
     epilogue_tile<EPI>(p, dctx, acc, bv, rt, stage, m0, n0, lane);
   }
 }
 
 // ---- B as [N,K]: workgroup-shared, double-buffered bf16 hi/lo tile in LDS --------------------------------------------
-template <int EPI, bool A_DROP, int NKB>
+template <int EPI, bool A_DROP, int NKB, int TERMS = 3>
 __global__ __launch_bounds__(256) void rx_gemm_nk_kernel(RxP p) {
   extern __shared__ __attribute__((aligned(16))) float s_lds[];
   constexpr int F4_PER_ROW = 4 * NKB;                 // float4 per tile row (K / 4)
@@ -480,7 +486,7 @@ __global__ __launch_bounds__(256) void rx_gemm_nk_kernel(RxP p) {
       b4r_split4(raw[i], hi, lo);
       char* dst = bbuf + buf * (2 * PLANE) + trow * (BROW * 4) + tc4 * 2;
       *reinterpret_cast<bf16x4*>(dst) = hi;
-      *reinterpret_cast<bf16x4*>(dst + PLANE) = lo;
+      if constexpr (TERMS == 3) *reinterpret_cast<bf16x4*>(dst + PLANE) = lo;
     }
   };
 
@@ -510,7 +516,7 @@ __global__ __launch_bounds__(256) void rx_gemm_nk_kernel(RxP p) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) acc = mfma3(ah[kb], al[kb], bh[kb], bl[kb], acc);
+    for (int kb = 0; kb < NKB; ++kb) acc = mfma3<TERMS>(ah[kb], al[kb], bh[kb], bl[kb], acc);
     if (live) epilogue_tile<EPI>(p, dctx, acc, bv, rt, stage, m0, n0, lane);
     stash_b(cur ^ 1);                                  // the other buffer: nobody reads it during this step
     bv = bias_next;
@@ -524,7 +530,7 @@ __global__ __launch_bounds__(256) void rx_gemm_nk_kernel(RxP p) {
 // N is the hidden size, so a wave keeps all NT column tiles of its 32 rows in accumulators and streams K in chunks of 64:
 // A chunk = 8 x 16-byte fragment loads per lane (requested one chunk ahead); B chunk = NT tiles, either register
 // fragments of coalesced dword loads ([K,N]) or a workgroup-shared double-buffered bf16 hi/lo LDS tile ([N,K]).
-template <bool B_NK, int EPI, bool A_DROP, int NT>
+template <bool B_NK, int EPI, bool A_DROP, int NT, int TERMS = 3>
 __global__ __launch_bounds__(256) void rx_gemm_kloop_kernel(RxP p) {
   extern __shared__ __attribute__((aligned(16))) float s_lds[];
   constexpr int BROW = 36, PLANE = NT * 32 * BROW * 4;     // B planes: [NT*32 rows][64 bf16 + pad]
@@ -569,7 +575,7 @@ __global__ __launch_bounds__(256) void rx_gemm_kloop_kernel(RxP p) {
         b4r_split4(braw[i], hi, lo);
         char* dst = bbuf + buf * (2 * PLANE) + trow * (BROW * 4) + tc4 * 2;
         *reinterpret_cast<bf16x4*>(dst) = hi;
-        *reinterpret_cast<bf16x4*>(dst + PLANE) = lo;
+        if constexpr (TERMS == 3) *reinterpret_cast<bf16x4*>(dst + PLANE) = lo;
       }
     }
   };
@@ -614,7 +620,7 @@ __global__ __launch_bounds__(256) void rx_gemm_kloop_kernel(RxP p) {
           const int col = min(nb + 32 * j + r, p.N - 1);
           split8(load8_strided(p.B + (int64_t)(64 * c + 16 * kb + 8 * h) * p.ldb + col, p.ldb), bh, bl);
         }
-        acc[j] = mfma3(ah[kb], al[kb], bh, bl, acc[j]);
+        acc[j] = mfma3<TERMS>(ah[kb], al[kb], bh, bl, acc[j]);
       }
     }
     if (B_NK) {
@@ -663,7 +669,7 @@ __device__ __forceinline__ int wide_off(int row, int ch) {   // image 0 (hi); lo
 
 // TM x TN = 128 x 128 (wide N) or 64 x 64 (N = 64 with a long K: the products that reduce over the FFN width or 3H);
 // the 4 waves always form a 2 x 2 grid of (TM/2) x (TN/2) quarters
-template <bool B_NK, int EPI, bool A_DROP, int TM, int TN, int WIDE_DEPTH = 1>
+template <bool B_NK, int EPI, bool A_DROP, int TM, int TN, int WIDE_DEPTH = 1, int TERMS = 3>
 __global__ __launch_bounds__(256, 2) void rx_gemm_wide_kernel(RxP p) {   // two waves per SIMD: without the bound the 128 x 128, depth-2, [K,N] instances take 268 registers = ONE workgroup per CU
   extern __shared__ __attribute__((aligned(16))) char s_w[];
   constexpr int RB = TM / 64, CB = TN / 64;                 // 32-row / 32-column blocks per wave
@@ -723,7 +729,7 @@ __global__ __launch_bounds__(256, 2) void rx_gemm_wide_kernel(RxP p) {   // two 
       b4r_split4(va, hi, lo);
       char* da = sA + wide_off(row, c4 >> 1) + 8 * (c4 & 1);
       *reinterpret_cast<bf16x4*>(da) = hi;
-      *reinterpret_cast<bf16x4*>(da + 1024) = lo;
+      if constexpr (TERMS == 3) *reinterpret_cast<bf16x4*>(da + 1024) = lo;
     }
 #pragma unroll
     for (int it = 0; it < NB; ++it) {
@@ -734,12 +740,12 @@ __global__ __launch_bounds__(256, 2) void rx_gemm_wide_kernel(RxP p) {   // two 
         const int row = f >> 3, c4 = f & 7;
         char* db = sB + wide_off(row, c4 >> 1) + 8 * (c4 & 1);
         *reinterpret_cast<bf16x4*>(db) = hi;
-        *reinterpret_cast<bf16x4*>(db + 1024) = lo;
+        if constexpr (TERMS == 3) *reinterpret_cast<bf16x4*>(db + 1024) = lo;
       } else {
         const int krow = f / (TN / 4), c4n = f % (TN / 4);
         char* db = sB + (c4n >> 4) * KN_HALF + tn_img_off(krow, c4n & 15);
         *reinterpret_cast<bf16x4*>(db) = hi;
-        *reinterpret_cast<bf16x4*>(db + 4096) = lo;
+        if constexpr (TERMS == 3) *reinterpret_cast<bf16x4*>(db + 4096) = lo;
       }
     }
   };
@@ -795,7 +801,7 @@ __global__ __launch_bounds__(256, 2) void rx_gemm_wide_kernel(RxP p) {   // two 
 #pragma unroll
       for (int a = 0; a < RB; ++a)
 #pragma unroll
-        for (int b = 0; b < CB; ++b) acc[a][b] = mfma3(ah[a], al[a], bh[b], bl[b], acc[a][b]);
+        for (int b = 0; b < CB; ++b) acc[a][b] = mfma3<TERMS>(ah[a], al[a], bh[b], bl[b], acc[a][b]);
     }
   };
   Regs q0, q1;
@@ -855,88 +861,88 @@ inline int wide_tile(const RxP& p) {
   return 0;
 }
 
-template <bool B_NK, int EPI, bool A_DROP, int T>
+template <bool B_NK, int EPI, bool A_DROP, int T, int TERMS>
 void launch_wide(RxP p, hipStream_t s) {
   p.n_items = b4r_cdiv(p.M, T) * b4r_cdiv(p.N, T);
   const dim3 grid(xcd_grid(p.n_items));
   if constexpr (T == 128) {
     if (p.K >= WIDE_DEPTH2_K) {
-      (void)b4r_raise_lds((const void*)rx_gemm_wide_kernel<B_NK, EPI, A_DROP, T, T, 2>, wide_lds(T, T), "gemm");
-      hipLaunchKernelGGL((rx_gemm_wide_kernel<B_NK, EPI, A_DROP, T, T, 2>), grid, dim3(256), wide_lds(T, T), s, p);
+      (void)b4r_raise_lds((const void*)rx_gemm_wide_kernel<B_NK, EPI, A_DROP, T, T, 2, TERMS>, wide_lds(T, T), "gemm");
+      hipLaunchKernelGGL((rx_gemm_wide_kernel<B_NK, EPI, A_DROP, T, T, 2, TERMS>), grid, dim3(256), wide_lds(T, T), s, p);
       return;
     }
   }
-  (void)b4r_raise_lds((const void*)rx_gemm_wide_kernel<B_NK, EPI, A_DROP, T, T, 1>, wide_lds(T, T), "gemm");
-  hipLaunchKernelGGL((rx_gemm_wide_kernel<B_NK, EPI, A_DROP, T, T, 1>), grid, dim3(256), wide_lds(T, T), s, p);
+  (void)b4r_raise_lds((const void*)rx_gemm_wide_kernel<B_NK, EPI, A_DROP, T, T, 1, TERMS>, wide_lds(T, T), "gemm");
+  hipLaunchKernelGGL((rx_gemm_wide_kernel<B_NK, EPI, A_DROP, T, T, 1, TERMS>), grid, dim3(256), wide_lds(T, T), s, p);
 }
 
-template <bool B_NK, int EPI, bool A_DROP>
+template <bool B_NK, int EPI, bool A_DROP, int TERMS>
 void launch_kloop(const RxP& p, hipStream_t s) {
   const int nt = b4r_cdiv(p.N, 32);
   dim3 grid((unsigned)b4r_cdiv(p.M, 128), (unsigned)(nt <= 2 ? 1 : b4r_cdiv(nt, 4)),
             (unsigned)b4r_cdiv(p.K / 64, p.k_chunks_per_split));
   if (nt <= 2) {
     const size_t lds = STAGE_FLOATS * sizeof(float) + (B_NK ? 2 * 2 * 2 * 32 * 36 * 4 : 0);
-    hipLaunchKernelGGL((rx_gemm_kloop_kernel<B_NK, EPI, A_DROP, 2>), grid, dim3(256), lds, s, p);
+    hipLaunchKernelGGL((rx_gemm_kloop_kernel<B_NK, EPI, A_DROP, 2, TERMS>), grid, dim3(256), lds, s, p);
   } else {
     const size_t lds = STAGE_FLOATS * sizeof(float) + (B_NK ? 2 * 2 * 4 * 32 * 36 * 4 : 0);
-    (void)b4r_raise_lds((const void*)rx_gemm_kloop_kernel<B_NK, EPI, A_DROP, 4>, lds, "gemm");
-    hipLaunchKernelGGL((rx_gemm_kloop_kernel<B_NK, EPI, A_DROP, 4>), grid, dim3(256), lds, s, p);
+    (void)b4r_raise_lds((const void*)rx_gemm_kloop_kernel<B_NK, EPI, A_DROP, 4, TERMS>, lds, "gemm");
+    hipLaunchKernelGGL((rx_gemm_kloop_kernel<B_NK, EPI, A_DROP, 4, TERMS>), grid, dim3(256), lds, s, p);
   }
 }
 
-template <bool B_NK, int EPI, bool A_DROP>
+template <bool B_NK, int EPI, bool A_DROP, int TERMS>
 void launch_rx2(const RxP& p, dim3 grid, hipStream_t s) {
   const int wt = wide_tile<B_NK>(p);
-  if (wt == 128) { launch_wide<B_NK, EPI, A_DROP, 128>(p, s); return; }
-  if (wt == 64) { launch_wide<B_NK, EPI, A_DROP, 64>(p, s); return; }
-  if (p.K > 64) { launch_kloop<B_NK, EPI, A_DROP>(p, s); return; }
+  if (wt == 128) { launch_wide<B_NK, EPI, A_DROP, 128, TERMS>(p, s); return; }
+  if (wt == 64) { launch_wide<B_NK, EPI, A_DROP, 64, TERMS>(p, s); return; }
+  if (p.K > 64) { launch_kloop<B_NK, EPI, A_DROP, TERMS>(p, s); return; }
   if (B_NK) {
-    if (p.K == 64) hipLaunchKernelGGL((rx_gemm_nk_kernel<EPI, A_DROP, 4>), grid, dim3(256), NK_LDS_BYTES, s, p);
-    else hipLaunchKernelGGL((rx_gemm_nk_kernel<EPI, A_DROP, 2>), grid, dim3(256), NK_LDS_BYTES, s, p);
+    if (p.K == 64) hipLaunchKernelGGL((rx_gemm_nk_kernel<EPI, A_DROP, 4, TERMS>), grid, dim3(256), NK_LDS_BYTES, s, p);
+    else hipLaunchKernelGGL((rx_gemm_nk_kernel<EPI, A_DROP, 2, TERMS>), grid, dim3(256), NK_LDS_BYTES, s, p);
   } else {
-    if (p.K == 64) hipLaunchKernelGGL((rx_gemm_kn_kernel<EPI, A_DROP, 4>), grid, dim3(256), KN_LDS_BYTES, s, p);
-    else hipLaunchKernelGGL((rx_gemm_kn_kernel<EPI, A_DROP, 2>), grid, dim3(256), KN_LDS_BYTES, s, p);
+    if (p.K == 64) hipLaunchKernelGGL((rx_gemm_kn_kernel<EPI, A_DROP, 4, TERMS>), grid, dim3(256), KN_LDS_BYTES, s, p);
+    else hipLaunchKernelGGL((rx_gemm_kn_kernel<EPI, A_DROP, 2, TERMS>), grid, dim3(256), KN_LDS_BYTES, s, p);
   }
 }
 
-template <bool B_NK, int EPI>
+template <bool B_NK, int EPI, int TERMS>
 void launch_rx(const RxP& p, bool a_drop, dim3 grid, hipStream_t s) {
-  if (a_drop) launch_rx2<B_NK, EPI, true>(p, grid, s);
-  else launch_rx2<B_NK, EPI, false>(p, grid, s);
+  if (a_drop) launch_rx2<B_NK, EPI, true, TERMS>(p, grid, s);
+  else launch_rx2<B_NK, EPI, false, TERMS>(p, grid, s);
 }
 
-template <bool B_NK>
+template <bool B_NK, int TERMS>
 int dispatch_rx(const RxP& p, int epi, bool a_drop, dim3 grid, hipStream_t s) {
   if (epi == B4R_EPI_BIAS_DROP_RES_LN) {   // b4r_gemm_ln_supported: N == 64, B as [K,N], no operand dropout
-    launch_wide<false, B4R_EPI_BIAS_DROP_RES_LN, false, 64>(p, s);
+    launch_wide<false, B4R_EPI_BIAS_DROP_RES_LN, false, 64, TERMS>(p, s);
     return B4R_OK;
   }
   if (epi == B4R_EPI_BIAS_GELU_LN) {
-    if (p.act != B4R_ACT_GELU) launch_wide<false, EPI_BIAS_ACT_LN, false, 64>(p, s);
-    else launch_wide<false, B4R_EPI_BIAS_GELU_LN, false, 64>(p, s);
+    if (p.act != B4R_ACT_GELU) launch_wide<false, EPI_BIAS_ACT_LN, false, 64, TERMS>(p, s);
+    else launch_wide<false, B4R_EPI_BIAS_GELU_LN, false, 64, TERMS>(p, s);
     return B4R_OK;
   }
   if (epi == B4R_EPI_ADD_RES_LN_BWD) {     // N == 64, B as [N,K]
-    if (p.ln_ids) launch_wide<true, EPI_ADD_RES_LN_BWD_EMBED, false, 64>(p, s);
-    else launch_wide<true, B4R_EPI_ADD_RES_LN_BWD, false, 64>(p, s);
+    if (p.ln_ids) launch_wide<true, EPI_ADD_RES_LN_BWD_EMBED, false, 64, TERMS>(p, s);
+    else launch_wide<true, B4R_EPI_ADD_RES_LN_BWD, false, 64, TERMS>(p, s);
     return B4R_OK;
   }
   switch (epi) {
-    case B4R_EPI_NONE: launch_rx<B_NK, B4R_EPI_NONE>(p, a_drop, grid, s); break;
-    case B4R_EPI_BIAS: launch_rx<B_NK, B4R_EPI_BIAS>(p, a_drop, grid, s); break;
-    case B4R_EPI_BIAS_QSCALE: launch_rx<B_NK, B4R_EPI_BIAS_QSCALE>(p, a_drop, grid, s); break;
+    case B4R_EPI_NONE: launch_rx<B_NK, B4R_EPI_NONE, TERMS>(p, a_drop, grid, s); break;
+    case B4R_EPI_BIAS: launch_rx<B_NK, B4R_EPI_BIAS, TERMS>(p, a_drop, grid, s); break;
+    case B4R_EPI_BIAS_QSCALE: launch_rx<B_NK, B4R_EPI_BIAS_QSCALE, TERMS>(p, a_drop, grid, s); break;
     case B4R_EPI_BIAS_GELU:
-      if (p.act != B4R_ACT_GELU) launch_rx<B_NK, EPI_BIAS_ACT>(p, a_drop, grid, s);
-      else launch_rx<B_NK, B4R_EPI_BIAS_GELU>(p, a_drop, grid, s);
+      if (p.act != B4R_ACT_GELU) launch_rx<B_NK, EPI_BIAS_ACT, TERMS>(p, a_drop, grid, s);
+      else launch_rx<B_NK, B4R_EPI_BIAS_GELU, TERMS>(p, a_drop, grid, s);
       break;
-    case B4R_EPI_BIAS_DROP_RES: launch_rx<B_NK, B4R_EPI_BIAS_DROP_RES>(p, a_drop, grid, s); break;
+    case B4R_EPI_BIAS_DROP_RES: launch_rx<B_NK, B4R_EPI_BIAS_DROP_RES, TERMS>(p, a_drop, grid, s); break;
     case B4R_EPI_GELU_BWD:
-      if (p.act != B4R_ACT_GELU) launch_rx<B_NK, EPI_ACT_BWD>(p, a_drop, grid, s);
-      else launch_rx<B_NK, B4R_EPI_GELU_BWD>(p, a_drop, grid, s);
+      if (p.act != B4R_ACT_GELU) launch_rx<B_NK, EPI_ACT_BWD, TERMS>(p, a_drop, grid, s);
+      else launch_rx<B_NK, B4R_EPI_GELU_BWD, TERMS>(p, a_drop, grid, s);
       break;
-    case B4R_EPI_ADD_RES: launch_rx<B_NK, B4R_EPI_ADD_RES>(p, a_drop, grid, s); break;
-    case B4R_EPI_BIAS_TANH: launch_rx<B_NK, B4R_EPI_BIAS_TANH>(p, a_drop, grid, s); break;
+    case B4R_EPI_ADD_RES: launch_rx<B_NK, B4R_EPI_ADD_RES, TERMS>(p, a_drop, grid, s); break;
+    case B4R_EPI_BIAS_TANH: launch_rx<B_NK, B4R_EPI_BIAS_TANH, TERMS>(p, a_drop, grid, s); break;
     default: b4r_set_error("gemm: unknown epilogue %d", epi); return B4R_E_BADARG;
   }
   return B4R_OK;
@@ -968,7 +974,7 @@ struct RxTnP {
 };
 
 
-template <int KS, bool B_DROP, int DGRAD>
+template <int KS, bool B_DROP, int DGRAD, int TERMS = 3>
 __device__ __forceinline__ void rx_gemm_tn_body(const RxTnP& p, const int block) {
   constexpr int NLD = KS / 16;                       // float4 per thread per operand per chunk
   constexpr int PLANE = KS * 128;                    // bytes per image
@@ -1023,9 +1029,9 @@ __device__ __forceinline__ void rx_gemm_tn_body(const RxTnP& p, const int block)
       b4r_split4(va, ah, al);
       b4r_split4(vb, bh, bl);
       *reinterpret_cast<bf16x4*>(s_tn + off) = ah;
-      *reinterpret_cast<bf16x4*>(s_tn + PLANE + off) = al;
+      if constexpr (TERMS == 3) *reinterpret_cast<bf16x4*>(s_tn + PLANE + off) = al;
       *reinterpret_cast<bf16x4*>(s_tn + 2 * PLANE + off) = bh;
-      *reinterpret_cast<bf16x4*>(s_tn + 3 * PLANE + off) = bl;
+      if constexpr (TERMS == 3) *reinterpret_cast<bf16x4*>(s_tn + 3 * PLANE + off) = bl;
     }
   };
   // transposed fragment: 16-lane group G = lane>>4 reads the 4 x 16 block at rows 8h + 4s + (0..3) (+16*kb), columns
@@ -1067,7 +1073,7 @@ __device__ __forceinline__ void rx_gemm_tn_body(const RxTnP& p, const int block)
 #pragma unroll
     for (int kb = 0; kb < KS / 16; ++kb) {
       const char* src = s_tn + 2 * PLANE + tn_img_off(32 * wm + r, 4 * kb + 2 * h);
-      dx = mfma3(*reinterpret_cast<const bf16x8*>(src), *reinterpret_cast<const bf16x8*>(src + PLANE), wh[kb], wl[kb], dx);
+      dx = mfma3<TERMS>(*reinterpret_cast<const bf16x8*>(src), *reinterpret_cast<const bf16x8*>(src + PLANE), wh[kb], wl[kb], dx);
     }
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
@@ -1083,7 +1089,7 @@ __device__ __forceinline__ void rx_gemm_tn_body(const RxTnP& p, const int block)
   auto products = [&]() {
 #pragma unroll
     for (int kb = 0; kb < KS / 16; ++kb)
-      acc = mfma3(tr8(0, tr_a, kb), tr8(1, tr_a, kb), tr8(2, tr_b, kb), tr8(3, tr_b, kb), acc);
+      acc = mfma3<TERMS>(tr8(0, tr_a, kb), tr8(1, tr_a, kb), tr8(2, tr_b, kb), tr8(3, tr_b, kb), acc);
   };
   Chunk c0, c1;
   if (r_begin < r_end) fetch(c0, r_begin);
@@ -1129,9 +1135,9 @@ __device__ __forceinline__ void rx_gemm_tn_body(const RxTnP& p, const int block)
   }
 }
 
-template <int KS, bool B_DROP, int DGRAD>
+template <int KS, bool B_DROP, int DGRAD, int TERMS = 3>
 __global__ __launch_bounds__(256) void rx_gemm_tn_kernel(RxTnP p) {
-  rx_gemm_tn_body<KS, B_DROP, DGRAD>(p, (int)blockIdx.x);
+  rx_gemm_tn_body<KS, B_DROP, DGRAD, TERMS>(p, (int)blockIdx.x);
 }
 // two independent weight-gradient products in ONE launch (the workgroups of the second follow those of the first; n0 is a
 // multiple of 8, so both keep their XCD mapping): dWo = ctx^T.dropmask(dz1) and dWqkv = x^T.dqkv of an encoder layer are each too
@@ -1139,10 +1145,10 @@ __global__ __launch_bounds__(256) void rx_gemm_tn_kernel(RxTnP p) {
 #ifndef TN_PAIR_OCC
 #define TN_PAIR_OCC 3   // waves per SIMD the register allocation aims at (tools/build_variant.sh -DTN_PAIR_OCC=4 to compare)
 #endif
-template <int KS, bool B_DROP0, bool B_DROP1>
+template <int KS, bool B_DROP0, bool B_DROP1, int TERMS = 3>
 __global__ __launch_bounds__(256, TN_PAIR_OCC) void rx_gemm_tn_pair_kernel(RxTnP p0, RxTnP p1, int n0) {
-  if ((int)blockIdx.x < n0) rx_gemm_tn_body<KS, B_DROP0, 0>(p0, (int)blockIdx.x);
-  else rx_gemm_tn_body<KS, B_DROP1, 0>(p1, (int)blockIdx.x - n0);
+  if ((int)blockIdx.x < n0) rx_gemm_tn_body<KS, B_DROP0, 0, TERMS>(p0, (int)blockIdx.x);
+  else rx_gemm_tn_body<KS, B_DROP1, 0, TERMS>(p1, (int)blockIdx.x - n0);
 }
 
 // ---- the same product on 128 x 128 output tiles (Mo and No multiples of 128: the weight gradients of the wide configurations) ------
@@ -1155,7 +1161,7 @@ constexpr int TN128_KS = 32;
 __device__ __forceinline__ int tn128_off(int row, int c4) {   // bytes; c4 = float4 index (0..31) within the 128 columns
   return row * 256 + 32 * ((c4 >> 2) ^ (2 * (row & 3))) + 8 * (c4 & 3);
 }
-template <bool B_DROP>
+template <bool B_DROP, int TERMS = 3>
 __global__ __launch_bounds__(512, 2) void rx_gemm_tn128_kernel(RxTnP p) {
   constexpr int KS = TN128_KS, NLD = KS / 16, PLANE = KS * 256;
   extern __shared__ __attribute__((aligned(16))) char s_tn[];   // [A hi | A lo | B hi | B lo]
@@ -1205,9 +1211,9 @@ __global__ __launch_bounds__(512, 2) void rx_gemm_tn128_kernel(RxTnP p) {
       b4r_split4(va, ah, al);
       b4r_split4(vb, bh, bl);
       *reinterpret_cast<bf16x4*>(s_tn + off) = ah;
-      *reinterpret_cast<bf16x4*>(s_tn + PLANE + off) = al;
+      if constexpr (TERMS == 3) *reinterpret_cast<bf16x4*>(s_tn + PLANE + off) = al;
       *reinterpret_cast<bf16x4*>(s_tn + 2 * PLANE + off) = bh;
-      *reinterpret_cast<bf16x4*>(s_tn + 3 * PLANE + off) = bl;
+      if constexpr (TERMS == 3) *reinterpret_cast<bf16x4*>(s_tn + 3 * PLANE + off) = bl;
     }
   };
   // transposed fragments as in rx_gemm_tn_body; A block b of the wave = columns 64 wm + 32 b .. of the A image, B block = 32 wn ..
@@ -1233,7 +1239,7 @@ __global__ __launch_bounds__(512, 2) void rx_gemm_tn128_kernel(RxTnP p) {
     for (int kb = 0; kb < KS / 16; ++kb) {
       const bf16x8 bh = tr8(2, tr_b, kb), bl = tr8(3, tr_b, kb);
 #pragma unroll
-      for (int bi = 0; bi < 2; ++bi) acc[bi] = mfma3(tr8(0, tr_a[bi], kb), tr8(1, tr_a[bi], kb), bh, bl, acc[bi]);
+      for (int bi = 0; bi < 2; ++bi) acc[bi] = mfma3<TERMS>(tr8(0, tr_a[bi], kb), tr8(1, tr_a[bi], kb), bh, bl, acc[bi]);
     }
   };
   Chunk c0, c1;
@@ -1370,10 +1376,13 @@ int b4r_gemm_rx_launch(const b4r_gemm_desc* d, hipStream_t stream) {
   // many column splits = a store-dominated product (the materialising vocabulary projection: 12 splits): there the
   // mapping concentrates each XCD's writes and costs time (34 -> 40 us measured), so it is kept to the few-split products
   if (p.n_splits > 4) p.n_items = -p.n_items;
-  int rc = d->b_is_nk ? dispatch_rx<true>(p, d->epilogue, a_drop, grid, stream)
-                      : dispatch_rx<false>(p, d->epilogue, a_drop, grid, stream);
+  const bool one = b4r_gemm_terms() == 1;
+  int rc = d->b_is_nk ? (one ? dispatch_rx<true, 1>(p, d->epilogue, a_drop, grid, stream)
+                             : dispatch_rx<true, 3>(p, d->epilogue, a_drop, grid, stream))
+                      : (one ? dispatch_rx<false, 1>(p, d->epilogue, a_drop, grid, stream)
+                             : dispatch_rx<false, 3>(p, d->epilogue, a_drop, grid, stream));
   if (rc != B4R_OK) return rc;
-  B4R_CHECK_LAUNCH("b4r_gemm_f32 (bf16x3)");
+  B4R_CHECK_LAUNCH(one ? "b4r_gemm_f32 (bf16)" : "b4r_gemm_f32 (bf16x3)");
   return B4R_OK;
 }
 
@@ -1399,8 +1408,9 @@ int b4r_gemm_rx_splitk_launch(const b4r_gemm_desc* d, int splits, float* slabs, 
   p.k_chunks_per_split = b4r_cdiv(chunks, splits < 1 ? 1 : splits);
   p.slab_stride = (int64_t)d->M * d->N;
   *slabs_used = b4r_cdiv(chunks, p.k_chunks_per_split);
-  launch_kloop<false, B4R_EPI_NONE, false>(p, stream);
-  B4R_CHECK_LAUNCH("gemm_splitk (bf16x3)");
+  if (b4r_gemm_terms() == 1) launch_kloop<false, B4R_EPI_NONE, false, 1>(p, stream);
+  else launch_kloop<false, B4R_EPI_NONE, false, 3>(p, stream);
+  B4R_CHECK_LAUNCH(b4r_gemm_terms() == 1 ? "gemm_splitk (bf16)" : "gemm_splitk (bf16x3)");
   return B4R_OK;
 }
 
@@ -1434,7 +1444,8 @@ static RxTnP make_tn_params(const b4r_gemm_tn_desc* d, float* scratch, int S) {
   return p;
 }
 
-int b4r_gemm_rx_tn_launch(const b4r_gemm_tn_desc* d, float* scratch, hipStream_t stream) {
+template <int TERMS>
+static int rx_tn_launch(const b4r_gemm_tn_desc* d, float* scratch, hipStream_t stream) {
   const int S = rx_tn_split(d->R, d->Mo, d->No);
   const RxTnP p = make_tn_params(d, scratch, S);
   const bool b_drop = d->b_dropout && p.drop.rng != nullptr;
@@ -1444,33 +1455,33 @@ int b4r_gemm_rx_tn_launch(const b4r_gemm_tn_desc* d, float* scratch, hipStream_t
   dim3 grid(xcd_grid(items));
   if (dgrad == 0 && tn_wide_tiles(d->Mo, d->No)) {
     constexpr size_t lds128 = (size_t)4 * TN128_KS * 256;   // 32 KB
-    if (b_drop) hipLaunchKernelGGL((rx_gemm_tn128_kernel<true>), grid, dim3(512), lds128, stream, p);
-    else hipLaunchKernelGGL((rx_gemm_tn128_kernel<false>), grid, dim3(512), lds128, stream, p);
-    B4R_CHECK_LAUNCH("b4r_gemm_tn_f32 (bf16x3, 128 x 128 tiles)");
+    if (b_drop) hipLaunchKernelGGL((rx_gemm_tn128_kernel<true, TERMS>), grid, dim3(512), lds128, stream, p);
+    else hipLaunchKernelGGL((rx_gemm_tn128_kernel<false, TERMS>), grid, dim3(512), lds128, stream, p);
+    B4R_CHECK_LAUNCH(TERMS == 1 ? "b4r_gemm_tn_f32 (bf16, 128 x 128 tiles)" : "b4r_gemm_tn_f32 (bf16x3, 128 x 128 tiles)");
     return b4r_launch_slab_reduce_full(p.slab, S, d->Mo, d->No, d->out, d->ldo, d->accumulate, p.colsum_slab, d->colsum,
                                        p.colsum_a_slab, d->colsum_a, stream);
   }
   constexpr size_t lds = (size_t)4 * TN_KS * 128;
   static bool lds_raised = false;
   if (lds > 48 * 1024 && !lds_raised) {
-    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, true, 0, TERMS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, false, 0, TERMS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, true, 1, TERMS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, false, 1, TERMS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, true, 2, TERMS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, false, 2, TERMS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, true, 3, TERMS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_kernel<TN_KS, false, 3, TERMS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     lds_raised = true;
   }
-#define B4R_TN_LAUNCH(BD, DG) hipLaunchKernelGGL((rx_gemm_tn_kernel<TN_KS, BD, DG>), grid, dim3(256), lds, stream, p)
+#define B4R_TN_LAUNCH(BD, DG) hipLaunchKernelGGL((rx_gemm_tn_kernel<TN_KS, BD, DG, TERMS>), grid, dim3(256), lds, stream, p)
   if (dgrad == 3) { if (b_drop) B4R_TN_LAUNCH(true, 3); else B4R_TN_LAUNCH(false, 3); }
   else if (dgrad == 2) { if (b_drop) B4R_TN_LAUNCH(true, 2); else B4R_TN_LAUNCH(false, 2); }
   else if (dgrad == 1) { if (b_drop) B4R_TN_LAUNCH(true, 1); else B4R_TN_LAUNCH(false, 1); }
   else if (b_drop) B4R_TN_LAUNCH(true, 0);
   else B4R_TN_LAUNCH(false, 0);
 #undef B4R_TN_LAUNCH
-  B4R_CHECK_LAUNCH("b4r_gemm_tn_f32 (bf16x3)");
+  B4R_CHECK_LAUNCH(TERMS == 1 ? "b4r_gemm_tn_f32 (bf16)" : "b4r_gemm_tn_f32 (bf16x3)");
   return b4r_launch_slab_reduce_full(p.slab, S, d->Mo, d->No, d->out, d->ldo, d->accumulate, p.colsum_slab, d->colsum,
                                      p.colsum_a_slab, d->colsum_a, stream);
 }
@@ -1481,8 +1492,9 @@ bool b4r_gemm_rx_tn_pair_supported(const b4r_gemm_tn_desc* d0, const b4r_gemm_tn
   return b4r_gemm_rx_tn_supported(d0) && b4r_gemm_rx_tn_supported(d1) && !d0->dgrad_out && !d1->dgrad_out &&
          !(d1->b_dropout && d1->rng && d1->drop_rate > 0.f);
 }
-int b4r_gemm_rx_tn_pair_launch(const b4r_gemm_tn_desc* d0, float* scratch0, const b4r_gemm_tn_desc* d1, float* scratch1,
-                               hipStream_t stream) {
+template <int TERMS>
+static int rx_tn_pair_launch(const b4r_gemm_tn_desc* d0, float* scratch0, const b4r_gemm_tn_desc* d1, float* scratch1,
+                             hipStream_t stream) {
   const int S0 = rx_tn_split(d0->R, d0->Mo, d0->No), S1 = rx_tn_split(d1->R, d1->Mo, d1->No);
   const RxTnP p0 = make_tn_params(d0, scratch0, S0), p1 = make_tn_params(d1, scratch1, S1);
   const bool drop0 = d0->b_dropout && p0.drop.rng != nullptr;
@@ -1490,16 +1502,26 @@ int b4r_gemm_rx_tn_pair_launch(const b4r_gemm_tn_desc* d0, float* scratch0, cons
   constexpr size_t lds = (size_t)4 * TN_KS * 128;
   static bool lds_raised = false;
   if (lds > 48 * 1024 && !lds_raised) {
-    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_pair_kernel<TN_KS, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_pair_kernel<TN_KS, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_pair_kernel<TN_KS, true, false, TERMS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)rx_gemm_tn_pair_kernel<TN_KS, false, false, TERMS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     lds_raised = true;
   }
-  if (drop0) hipLaunchKernelGGL((rx_gemm_tn_pair_kernel<TN_KS, true, false>), dim3(n0 + n1), dim3(256), lds, stream, p0, p1, n0);
-  else hipLaunchKernelGGL((rx_gemm_tn_pair_kernel<TN_KS, false, false>), dim3(n0 + n1), dim3(256), lds, stream, p0, p1, n0);
-  B4R_CHECK_LAUNCH("b4r_gemm_tn_f32 pair (bf16x3)");
+  if (drop0) hipLaunchKernelGGL((rx_gemm_tn_pair_kernel<TN_KS, true, false, TERMS>), dim3(n0 + n1), dim3(256), lds, stream, p0, p1, n0);
+  else hipLaunchKernelGGL((rx_gemm_tn_pair_kernel<TN_KS, false, false, TERMS>), dim3(n0 + n1), dim3(256), lds, stream, p0, p1, n0);
+  B4R_CHECK_LAUNCH(TERMS == 1 ? "b4r_gemm_tn_f32 pair (bf16)" : "b4r_gemm_tn_f32 pair (bf16x3)");
   int rc = b4r_launch_slab_reduce_full(p0.slab, S0, d0->Mo, d0->No, d0->out, d0->ldo, d0->accumulate, p0.colsum_slab, d0->colsum,
                                        p0.colsum_a_slab, d0->colsum_a, stream);
   if (rc) return rc;
   return b4r_launch_slab_reduce_full(p1.slab, S1, d1->Mo, d1->No, d1->out, d1->ldo, d1->accumulate, p1.colsum_slab, d1->colsum,
                                      p1.colsum_a_slab, d1->colsum_a, stream);
+}
+
+// the arithmetic mode picks the instances (B4R_GEMM_BF16: one term); the launch sequence is the same in both
+int b4r_gemm_rx_tn_launch(const b4r_gemm_tn_desc* d, float* scratch, hipStream_t stream) {
+  return b4r_gemm_terms() == 1 ? rx_tn_launch<1>(d, scratch, stream) : rx_tn_launch<3>(d, scratch, stream);
+}
+int b4r_gemm_rx_tn_pair_launch(const b4r_gemm_tn_desc* d0, float* scratch0, const b4r_gemm_tn_desc* d1, float* scratch1,
+                               hipStream_t stream) {
+  return b4r_gemm_terms() == 1 ? rx_tn_pair_launch<1>(d0, scratch0, d1, scratch1, stream)
+                               : rx_tn_pair_launch<3>(d0, scratch0, d1, scratch1, stream);
 }

@@ -729,7 +729,7 @@ extern "C" int b4r_workspace_region(const b4r_model_config* cfg, int32_t B, int3
 
 // ===============================================================================================================
 // the logits-free head sweeps the item table: it answers on the table's width
-static bool fused_head_ok(const ModelCfg& c) { return b4r_head32_hidden_ok(c.E) && b4r_get_gemm_mode() == B4R_GEMM_BF16X3; }
+static bool fused_head_ok(const ModelCfg& c) { return b4r_head32_hidden_ok(c.E) && b4r_split_mode(); }
 extern "C" int32_t b4r_fused_head_supported_ex(const b4r_model_config_ex* cfg) {
   ModelCfg c;
   if (cfg == nullptr || resolve_cfg(cfg, &c) != B4R_OK) return 0;

@@ -21,9 +21,14 @@ constexpr int TILE_BYTES = 4 * IMG_BYTES;  // one 16-row tile of the four interl
 __device__ __forceinline__ f32x4 mfma_bf(const bf16x8 a, const bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
+// TERMS = MFMAs per product: 3 (B4R_GEMM_BF16X3: Alo.Bhi + Ahi.Blo + Ahi.Bhi) or 1 (B4R_GEMM_BF16: Ahi.Bhi)
+template <int TERMS = 3>
 __device__ __forceinline__ f32x4 mfma3(const bf16x8 ah, const bf16x8 al, const bf16x8 bh, const bf16x8 bl, f32x4 c) {
-  c = mfma_bf(al, bh, c);
-  c = mfma_bf(ah, bl, c);
+  static_assert(TERMS == 1 || TERMS == 3, "one or three terms");
+  if constexpr (TERMS == 3) {
+    c = mfma_bf(al, bh, c);
+    c = mfma_bf(ah, bl, c);
+  }
   c = mfma_bf(ah, bh, c);
   return c;
 }
@@ -61,8 +66,8 @@ __device__ __forceinline__ void stage_fetch(StagedRowsT<NIT>& st, const float* s
     st.v1[it] = *reinterpret_cast<const f32x4*>(src1 + (row0 + r) * ld1 + 4 * c4);
   }
 }
-// images: tensor 0 -> (0 = hi, 1 = lo), tensor 1 -> (2 = hi, 3 = lo)
-template <int NIT = 4, int TB = TILE_BYTES>
+// images: tensor 0 -> (0 = hi, 1 = lo), tensor 1 -> (2 = hi, 3 = lo); TERMS = 1 writes the hi images only
+template <int NIT = 4, int TB = TILE_BYTES, int TERMS = 3>
 __device__ __forceinline__ void stage_write(const StagedRowsT<NIT>& st, char* img, int nrows, int valid) {
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
@@ -75,9 +80,9 @@ __device__ __forceinline__ void stage_write(const StagedRowsT<NIT>& st, char* im
       b4r_split4(b, bh, bl);
       char* dst = img + img_off<TB>(r, c4 >> 1) + 8 * (c4 & 1);
       *reinterpret_cast<bf16x4*>(dst) = ah;
-      *reinterpret_cast<bf16x4*>(dst + IMG_BYTES) = al;
+      if constexpr (TERMS == 3) *reinterpret_cast<bf16x4*>(dst + IMG_BYTES) = al;
       *reinterpret_cast<bf16x4*>(dst + 2 * IMG_BYTES) = bh;
-      *reinterpret_cast<bf16x4*>(dst + 3 * IMG_BYTES) = bl;
+      if constexpr (TERMS == 3) *reinterpret_cast<bf16x4*>(dst + 3 * IMG_BYTES) = bl;
     }
   }
 }

@@ -29,9 +29,14 @@ constexpr int P_TILE = 4096;   // hi image | lo image
 __device__ __forceinline__ f32x16 mfma32(const bf16x8 a, const bf16x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
+// TERMS = MFMAs per product: 3 (B4R_GEMM_BF16X3: Alo.Bhi + Ahi.Blo + Ahi.Bhi) or 1 (B4R_GEMM_BF16: Ahi.Bhi)
+template <int TERMS = 3>
 __device__ __forceinline__ f32x16 mfma32x3(const bf16x8 ah, const bf16x8 al, const bf16x8 bh, const bf16x8 bl, f32x16 c) {
-  c = mfma32(al, bh, c);
-  c = mfma32(ah, bl, c);
+  static_assert(TERMS == 1 || TERMS == 3, "one or three terms");
+  if constexpr (TERMS == 3) {
+    c = mfma32(al, bh, c);
+    c = mfma32(ah, bl, c);
+  }
   c = mfma32(ah, bh, c);
   return c;
 }
@@ -70,14 +75,16 @@ __device__ __forceinline__ Lane32 lane32(int lane) {
   return k;
 }
 
-// accumulator (rows = the image's columns, lane = the image's row) -> rows of a tile, swapped column order
+// accumulator (rows = the image's columns, lane = the image's row) -> rows of a tile, swapped column order (TERMS = 1: the hi
+// image only)
+template <int TERMS = 3>
 __device__ __forceinline__ void acc_to_rows(char* tile, const Lane32& lk, const f32x16& v) {
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
     bf16x8 hi, lo;
     split8(regs8(v, s), hi, lo);
     *reinterpret_cast<bf16x8*>(tile + lk.rowc[s]) = hi;
-    *reinterpret_cast<bf16x8*>(tile + P_IMG + lk.rowc[s]) = lo;
+    if constexpr (TERMS == 3) *reinterpret_cast<bf16x8*>(tile + P_IMG + lk.rowc[s]) = lo;
   }
 }
 // accumulator registers 8s .. 8s+7 as the B (or A) fragment of k-step s

@@ -436,7 +436,7 @@ class Engine:
         §4); the host cost per step drops from ~0.72 ms of launches to ~0.10 ms.  The first step on a batch runs eagerly
         (one-time initialisations must not happen inside a capture), the second captures, later ones replay."""
         key = (cb.input_word_ids, cb.input_mask, cb.masked_lm_positions, cb.masked_lm_ids, cb.B, cb.L, cb.P,
-               bytes(memoryview(hp)))
+               bytes(memoryview(hp)), self.lib.b4r_get_gemm_mode())   # a graph replays the kernels of the mode it was captured in
         graphs = self.__dict__.setdefault("_graphs", {})
         seen = self.__dict__.setdefault("_graph_seen", set())
         g = graphs.get(key)
@@ -460,7 +460,7 @@ class Engine:
         is not captured) between them; same first-eager / second-capture / then-replay protocol as train_step_graphed."""
         from .distributed import allreduce_step
         key = (cb.input_word_ids, cb.input_mask, cb.masked_lm_positions, cb.masked_lm_ids, cb.B, cb.L, cb.P,
-               bytes(memoryview(hp)))
+               bytes(memoryview(hp)), self.lib.b4r_get_gemm_mode())   # a graph replays the kernels of the mode it was captured in
         graphs = self.__dict__.setdefault("_dp_graphs", {})
         seen = self.__dict__.setdefault("_dp_graph_seen", set())
         pair = graphs.get(key)

@@ -463,12 +463,28 @@ typedef struct b4r_gemm_desc {
 } b4r_gemm_desc;
 /* Arithmetic of the dense layers (process-wide switch; default B4R_GEMM_BF16X3):
  *   B4R_GEMM_F32     exact fp32 matrix cores (v_mfma_f32_32x32x2_f32), LDS-tiled
- *   B4R_GEMM_BF16X3  products with K <= 64 run on the bf16 matrix cores with a 3-term hi/lo split of both fp32 operands and
- *                    fp32 accumulation (~1e-5 of the fp32 result at 5.3x the matrix-core throughput, operands loaded
- *                    straight into registers); K > 64 and the weight-gradient products stay on the exact path */
-enum { B4R_GEMM_F32 = 0, B4R_GEMM_BF16X3 = 1 };
+ *   B4R_GEMM_BF16X3  products run on the bf16 matrix cores with a 3-term hi/lo split of both fp32 operands and
+ *                    fp32 accumulation (~1e-5 of the fp32 result at 5.3x the matrix-core throughput); every shape that
+ *                    b4r_gemm_rx_supported / b4r_gemm_rx_tn_supported accept (K loop, split-K and weight gradients included)
+ *                    runs there, the other shapes on the exact fp32 kernels
+ *   B4R_GEMM_BF16    mixed precision (Keras "mixed_bfloat16"): the same launch plan as B4R_GEMM_BF16X3, but the dense-layer
+ *                    tile products (b4r_gemm_f32 / b4r_gemm_tn_f32 on the bf16 path: every tile, K-loop, split-K and
+ *                    weight-gradient kernel, epilogues included) and the attention cores of width 32 (16- and 32-token
+ *                    tiles) and 64 (b4r_attn_fwd / b4r_attn_bwd, b4r_attn_fwd_hd / b4r_attn_bwd_hd) round each operand once to bf16 (round
+ *                    to nearest even: the split's hi) and issue one MFMA per k-slice, fp32 accumulation.  LayerNorm, softmax
+ *                    statistics, activations, dropout, residuals, loss, the item-table scatter and AdamW stay fp32; weights
+ *                    and every HBM tensor keep their dtypes.  Kernels that keep their B4R_GEMM_BF16X3 arithmetic in this
+ *                    mode: the masked-LM head, the embedding projection, the ranking kernels, the hidden-64 attention and
+ *                    feed-forward blocks (b4r_attn_block_fwd / _bwd, b4r_ffn_block_fwd / _bwd), the last layer's attention on
+ *                    the masked slots' queries inside b4r_forward / b4r_backward, and the one-launch feed-forward pair
+ *                    (b4r_ffn_wide_fwd / _bwd). */
+enum { B4R_GEMM_F32 = 0, B4R_GEMM_BF16X3 = 1, B4R_GEMM_BF16 = 2 };
 int b4r_set_gemm_mode(int mode);
 int b4r_get_gemm_mode(void);
+/* 1 in the two bf16 matrix-core modes (B4R_GEMM_BF16X3, B4R_GEMM_BF16): every launch-path decision treats them alike */
+int b4r_split_mode(void);
+/* MFMA terms per bf16 product in the current mode: 3 (B4R_GEMM_BF16X3), 1 (B4R_GEMM_BF16), 0 (B4R_GEMM_F32) */
+int b4r_gemm_terms(void);
 
 /* dense layers of the encoder / MLM head (Keras Dense / EinsumDense / MultiHeadAttention projections) on the exact
  * fp32 matrix cores (v_mfma_f32_32x32x2_f32) */
