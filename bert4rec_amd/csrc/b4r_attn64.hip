@@ -449,7 +449,7 @@ extern "C" int b4r_attn_fwd_hd(const float* qkv, const int64_t* input_mask, int3
   rc = terms == 3 ? fwd_launch<3>(p, (hipStream_t)stream) : terms == 1 ? fwd_launch<1>(p, (hipStream_t)stream)
                                                                       : fwd_launch<0>(p, (hipStream_t)stream);
   if (rc) return rc;
-  B4R_CHECK_LAUNCH("b4r_attn_fwd_hd");
+  B4R_CHECK_LAUNCH(terms == 1 ? "b4r_attn_fwd_hd (bf16)" : "b4r_attn_fwd_hd");
   return B4R_OK;
 }
 
@@ -473,6 +473,6 @@ extern "C" int b4r_attn_bwd_hd(const float* qkv, const int64_t* input_mask, cons
   rc = terms == 3 ? bwd_launch<3>(p, (hipStream_t)stream) : terms == 1 ? bwd_launch<1>(p, (hipStream_t)stream)
                                                                       : bwd_launch<0>(p, (hipStream_t)stream);
   if (rc) return rc;
-  B4R_CHECK_LAUNCH("b4r_attn_bwd_hd");
+  B4R_CHECK_LAUNCH(terms == 1 ? "b4r_attn_bwd_hd (bf16)" : "b4r_attn_bwd_hd");
   return B4R_OK;
 }

@@ -2,6 +2,7 @@
 bf16-rounded operands, the model against the oracle within bf16 bounds, the launch plan of mode 1, reproducibility and graphs.
 
 Measured errors and the bounds asserted here: DESIGN.md, "Mixed precision"."""
+import ctypes as C
 import math
 
 import pytest
@@ -341,3 +342,94 @@ def test_policy_end_to_end_training_and_evaluation():
     for k in ("NDCG@10", "HR@10"):
         p = want["HR@10"]
         assert abs(got[k] - want[k]) <= 2 * math.sqrt(2 * p * (1 - p) / n), (k, got[k], want[k])
+
+
+# ---- the runtime-activation epilogues and the activation-gradient tail at one term, every id -----------------------------------------
+def act64(act, x):
+    from tests import activation_ref as ar
+    f, d = ar.value_and_grad64(ar.NAMES[act], x.double().cpu().numpy())
+    return torch.from_numpy(f), torch.from_numpy(d)
+
+
+def check_one_term_scaled(got, A, B, s):
+    """got = (A.B) * s (s elementwise, fp64) from the one-term path: as check_one_term, with the factor on every side"""
+    scale = float(((A.double().abs() @ B.double().abs()) * s.abs()).max())
+    err_r = T.maxdiff(got, (bf(A) @ bf(B)) * s)
+    err_x = T.maxdiff(got, (A.double() @ B.double()) * s)
+    assert err_r <= 1e-4 * scale, (err_r, scale)
+    assert 10 * err_r < err_x, (err_r, err_x)
+
+
+# the register kernel, and the shapes of the compact-row feed-forward products at hidden 128 (B*P = 960 rows) and 256
+@pytest.mark.parametrize("M,N,K", [(96, 256, 64), (960, 512, 128), (384, 1024, 256)])
+@pytest.mark.parametrize("act", range(9))
+def test_activation_epilogues_are_one_term(bf16_mode, act, M, N, K):
+    """B4R_EPI_BIAS_GELU / B4R_EPI_GELU_BWD with activation `act` in mode 2: the product one term, the activation (its derivative)
+    the requested one, applied to the pre-activation the launch wrote"""
+    g = torch.Generator().manual_seed(140 + act)
+    A, B = torch.randn(M, K, generator=g) * 0.6, torch.randn(K, N, generator=g) * 0.3
+    bias = torch.randn(N, generator=g) * 0.5
+    c, c2 = T.gemm(A.to(DEV), B.to(DEV), M, N, K, epi=_lib.EPI_BIAS_GELU, bias=bias.to(DEV), want_c2=True, activation=act)
+    torch.cuda.synchronize()
+    check_one_term(c2 - bias.to(DEV), A, B)
+    f, _ = act64(act, c2)
+    assert float((c.cpu().double() - f).abs().max()) < 1e-4 * max(1.0, float(f.abs().max()))
+    # backward: C = (dY . W^T) * f'(R), W as [N, K]
+    dY, W = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) * 0.3
+    R = torch.randn(M, N, generator=g) * 2
+    cb, _ = T.gemm(dY.to(DEV), W.to(DEV), M, N, K, b_is_nk=1, epi=_lib.EPI_GELU_BWD, R=R.to(DEV), activation=act)
+    torch.cuda.synchronize()
+    _, fd = act64(act, R)
+    check_one_term_scaled(cb, dY, W.t(), fd)
+
+
+@pytest.mark.parametrize("act", range(9))
+def test_activation_layer_norm_epilogue_is_one_term(bf16_mode, act):
+    """B4R_EPI_BIAS_GELU_LN (hidden 64: the masked-LM transform) in mode 2: the pre-activation one term, then `act` and the LayerNorm
+    in fp32 on it"""
+    lib = bf16_mode
+    g = torch.Generator().manual_seed(190 + act)
+    M, N, K = 160, 64, 128
+    A, B = torch.randn(M, K, generator=g) * 0.5, torch.randn(K, N, generator=g) * 0.2
+    bias, gam, bet = torch.randn(N, generator=g) * 0.3, 1 + 0.1 * torch.randn(N, generator=g), 0.1 * torch.randn(N, generator=g)
+    Ad, Bd, bd, gd, btd = (t.to(DEV) for t in (A, B, bias, gam, bet))
+    Cm, C2, C3 = (torch.full((M, N), float("nan"), device=DEV) for _ in range(3))
+    mean, rstd = torch.empty(M, device=DEV), torch.empty(M, device=DEV)
+    d = _lib.GemmDesc()
+    d.A, d.lda, d.B, d.ldb, d.C, d.ldc, d.M, d.N, d.K = P(Ad), K, P(Bd), N, P(Cm), N, M, N, K
+    d.epilogue, d.bias, d.C2, d.ldc2, d.C3, d.ldc3, d.qscale = _lib.EPI_BIAS_GELU_LN, P(bd), P(C2), N, P(C3), N, 1.0
+    d.ln_gamma, d.ln_beta, d.ln_mean, d.ln_rstd, d.ln_eps, d.activation = P(gd), P(btd), P(mean), P(rstd), 1e-12, act
+    assert lib.b4r_gemm_ln_supported(C.byref(d)) == 1
+    _lib.check(lib.b4r_gemm_f32(C.byref(d), stream()), "b4r_gemm_f32")
+    torch.cuda.synchronize()
+    check_one_term(C3 - bd, A, B)
+    f, _ = act64(act, C3)
+    assert float((Cm.cpu().double() - f).abs().max()) < 1e-4 * max(1.0, float(f.abs().max()))
+    mu = f.mean(-1, keepdim=True)
+    var = ((f - mu) ** 2).mean(-1, keepdim=True)
+    y = (f - mu) / torch.sqrt(var + 1e-12) * gam.double() + bet.double()
+    tol = 1e-4 * max(1.0, float((1.0 / torch.sqrt(var + 1e-12)).max()))
+    assert float((C2.cpu().double() - y).abs().max()) < tol
+
+
+@pytest.mark.parametrize("act", range(9))
+def test_weight_gradient_with_activation_gradient_tail_is_one_term(bf16_mode, act):
+    """b4r_gemm_tn_f32 with dgrad_out / dgrad_gelu_pre (No = 64) in mode 2: out = A^T.B and dX = (B . W^T) * f'(G), one term each"""
+    lib = bf16_mode
+    g = torch.Generator().manual_seed(170 + act)
+    Rr, Mo, No = 200, 256, 64
+    A, Bm = torch.randn(Rr, Mo, generator=g), torch.randn(Rr, No, generator=g)
+    W, G = torch.randn(Mo, No, generator=g) * 0.3, torch.randn(Rr, Mo, generator=g) * 2
+    Ad, Bd, Wd, Gd = (t.to(DEV) for t in (A, Bm, W, G))
+    out = torch.empty(Mo, No, device=DEV)
+    dX = torch.full((Rr, Mo), float("nan"), device=DEV)
+    sc = torch.empty(lib.b4r_gemm_tn_scratch_floats(Rr, Mo, No), device=DEV)
+    d = _lib.GemmTnDesc()
+    d.A, d.lda, d.B, d.ldb, d.out, d.ldo, d.R, d.Mo, d.No = P(Ad), Mo, P(Bd), No, P(out), No, Rr, Mo, No
+    d.dgrad_w, d.dgrad_ldw, d.dgrad_out, d.dgrad_ldo, d.dgrad_gelu_pre, d.dgrad_ldg, d.activation = P(Wd), No, P(dX), Mo, P(Gd), Mo, act
+    assert lib.b4r_gemm_tn_dgrad_supported(C.byref(d)) == 1
+    _lib.check(lib.b4r_gemm_tn_f32(C.byref(d), P(sc), stream()), "b4r_gemm_tn_f32")
+    torch.cuda.synchronize()
+    check_one_term(out, A.t(), Bm)
+    _, fg = act64(act, G)
+    check_one_term_scaled(dX, Bm, W.t(), fg)

@@ -38,6 +38,15 @@ TIE = 1e-4        # top-2 oracle logits closer than this: the argmax may differ 
 F32_CASES = {"ml-1m_64", "ml-1m_128", "steam_256"}
 
 
+def set_edge_rows(batch):
+    """row 0: a valid slot at position 0 and fewer than P masks, so that the padding slots (position 0, id 0) collide with it (what
+    the reference's preprocessor produces whenever it masks position 0); row 1: a single valid slot"""
+    n0 = int(batch["input_mask"][0].sum())
+    set_row_slots(batch, 0, [0] + list(range(2, n0, max(1, n0 // 4)))[:3], orc.MASK_TOKEN_ID)
+    set_row_slots(batch, 1, [int(batch["input_mask"][1].sum()) - 1], orc.MASK_TOKEN_ID)
+    return batch
+
+
 def shipped_case(name, num_layers=None, dropout=True):
     """oracle config, batch and Adam hyper-parameters of one train step at a shipped configuration (small batch)"""
     c = get_encoder_config(name)
@@ -50,12 +59,7 @@ def shipped_case(name, num_layers=None, dropout=True):
                              num_attention_heads=c["num_attention_heads"], max_sequence_length=L, inner_dim=c["inner_dim"],
                              output_dropout=c["output_dropout"] if dropout else 0.0,
                              attention_dropout=c["attention_dropout"] if dropout else 0.0)
-    batch = orc.synthetic_batch(B, L, P, V, seed=len(name) + L, ragged=True)
-    # row 0: a valid slot at position 0 and fewer than P masks, so that the padding slots (position 0, id 0) collide with it (what
-    # the reference's preprocessor produces whenever it masks position 0); row 1: a single valid slot
-    n0 = int(batch["input_mask"][0].sum())
-    set_row_slots(batch, 0, [0] + list(range(2, n0, max(1, n0 // 4)))[:3], orc.MASK_TOKEN_ID)
-    set_row_slots(batch, 1, [int(batch["input_mask"][1].sum()) - 1], orc.MASK_TOKEN_ID)
+    batch = set_edge_rows(orc.synthetic_batch(B, L, P, V, seed=len(name) + L, ragged=True))
     clip = 1e-3 if name in CLIPPED else 5.0
     hp_o = orc.AdamWConfig(num_warmup_steps=0, num_train_steps=100, gradient_clip_norm=clip)   # lr > 0 at step 0, decays at step 1
     return cfg_o, batch, hp_o
@@ -66,14 +70,14 @@ def hip_adamw_config(hp_o):
                              hp_o.beta_1, hp_o.beta_2, hp_o.epsilon, hp_o.gradient_clip_norm)
 
 
-def assert_counts_match(st, batch, logits):
+def assert_counts_match(st, batch, logits, tie_width=TIE):
     """valid / slot counts exactly; argmax hits exactly but for slots whose two best oracle logits (nearly) tie"""
     y = batch["masked_lm_ids"]
     assert st["valid_count"] == float((y != 0).sum())
     assert st["slots_all"] == float(y.numel())
     top = logits.topk(2, dim=-1)
     hit = top.indices[..., 0] == y
-    tie = (top.values[..., 0] - top.values[..., 1]) < TIE
+    tie = (top.values[..., 0] - top.values[..., 1]) < tie_width
     valid = y != 0
     assert abs(st["correct_masked"] - float((hit & valid).sum())) <= float((tie & valid).sum()), "masked accuracy"
     assert abs(st["correct_all"] - float(hit.sum())) <= float(tie.sum()), "sparse categorical accuracy"
@@ -97,15 +101,16 @@ def launch_labels(fn):
     return [names.raw[j * stride:(j + 1) * stride].split(b"\0", 1)[0].decode() for j in range(n.value)]
 
 
-def run_and_check_train_step(eng, cfg_o, batch, cb, hp_o, step, seed, rel, labels=None):
+def run_and_check_train_step(eng, cfg_o, batch, cb, hp_o, step, seed, rel, labels=None, ref=orc.loss_and_grads):
     """one Engine.train_step (the engine's state holds `step`), checked against the oracle as the module docstring says; returns the
-    state it left and the oracle's gradient norm.  labels (a list): filled with the step's launches (launch timer)"""
+    state it left and the oracle's gradient norm.  labels (a list): filled with the step's launches (launch timer).  ref: the
+    restatement the step is checked against (ref(params, batch, cfg_o, training=, rng=) -> loss, gradients, outputs)"""
     hp = hip_adamw_config(hp_o)
     eng.ensure_training_buffers()
     names = [n for n in eng.variable_names() if orc.is_trainable(n)]
     params_now = eng.export_named()
     m_now, v_now = eng.export_named(eng.adam_m), eng.export_named(eng.adam_v)
-    loss_ref, grads_ref, out_ref = orc.loss_and_grads(params_now, batch, cfg_o, training=True, rng=(seed, step))
+    loss_ref, grads_ref, out_ref = ref(params_now, batch, cfg_o, training=True, rng=(seed, step))
     if labels is None:
         eng.train_step(hp, cb)
     else:
@@ -132,8 +137,16 @@ def run_and_check_train_step(eng, cfg_o, batch, cb, hp_o, step, seed, rel, label
     consumed = {n: (m_after[n].double() - b1 * m_now[n].double()) / (1.0 - b1) for n in names}
     compare_grads(consumed, {n: grads_ref[n] * clip_scale for n in names}, 1.0, rel=rel)
 
-    # the optimizer, exactly: the oracle's AdamW from the pre-step state, fed the step's own gradient
-    inv = torch.tensor(1.0 / cnt, dtype=torch.float32)
+    assert_adamw_exact(st, names, grads, (params_now, m_now, v_now), (params_after, m_after, v_after), step, hp_o)
+    return st, gnorm_ref
+
+
+def assert_adamw_exact(st, names, grads, before, after, step, hp_o):
+    """the optimizer, exactly: the oracle's AdamW from the pre-step state (params, m, v), fed the step's own gradient (the buffer over
+    the valid count), must give the state the device holds after it"""
+    params_now, m_now, v_now = before
+    params_after, m_after, v_after = after
+    inv = torch.tensor(1.0 / st["valid_count"], dtype=torch.float32)
     p_o = {n: params_now[n].clone() for n in names}
     m_o = {n: m_now[n].clone() for n in names}
     v_o = {n: v_now[n].clone() for n in names}
@@ -143,7 +156,6 @@ def run_and_check_train_step(eng, cfg_o, batch, cb, hp_o, step, seed, rel, label
             err = relative_error(got[n], want[n])
             assert err <= 1e-6, f"AdamW {what} of {n} at step {step}: relative error {err:.2e}"
     assert abs(st["lr"] - float(orc.learning_rate(step, hp_o))) <= 1e-6 * hp_o.init_lr
-    return st, gnorm_ref
 
 
 def two_steps(cfg_o, batch, hp_o, rel, seed=4321):
