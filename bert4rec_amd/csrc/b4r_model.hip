@@ -179,9 +179,9 @@ inline int head_dim(const b4r_model_config* c) { return c->hidden_size / c->num_
 
 int check_cfg(const b4r_model_config* c) {
   B4R_CHECK_ARG(c != nullptr, B4R_E_BADARG, "null model config");
-  B4R_CHECK_ARG(c->vocab_size > 0 && c->num_layers > 0 && c->num_layers <= B4R_MAX_LAYERS && c->num_heads > 0 &&
-                    c->inner_dim > 0 && c->max_seq_len > 0,
-                B4R_E_SHAPE, "bad model config");
+  B4R_CHECK_ARG(c->vocab_size > 0 && c->num_heads > 0 && c->inner_dim > 0 && c->max_seq_len > 0, B4R_E_SHAPE, "bad model config");
+  B4R_CHECK_ARG(c->num_layers > 0 && c->num_layers <= B4R_MAX_LAYERS, B4R_E_SHAPE, "num_layers %d not supported (1 ... %d)",
+                c->num_layers, B4R_MAX_LAYERS);
   B4R_CHECK_ARG(c->hidden_size == 32 * c->num_heads || c->hidden_size == 64 * c->num_heads, B4R_E_SHAPE,
                 "hidden_size %d / num_heads %d: head_dim must be 32 or 64", c->hidden_size, c->num_heads);
   const int H = c->hidden_size;

@@ -95,6 +95,15 @@ GEMM_DETAIL = re.compile(r"^b4r_gemm_f32\b.*\[M=(\d+) N=(\d+) K=(\d+) epi=(\d+)"
 TN_DETAIL = re.compile(r"^b4r_gemm_tn_f32\b.*\[R=(\d+) Mo=(\d+) No=(\d+)( \+dgrad)?")
 
 
+def is_wo_grad(label, N, H):
+    """the launch after an unfolded attention block backward: dWo (with dWqkv as one pair launch, or as the first of two products).
+    A folded one formed them itself, and the previous layer's feed-forward backward follows (its first weight gradient carries the
+    input gradient, "+dgrad", or comes after the dF product).  Reductions the full reduce queue no longer takes (deep stacks) run as
+    "slab_reduce" launches in between and are skipped."""
+    t = TN_DETAIL.match(label)
+    return label.startswith("b4r_gemm_tn_f32 pair") or bool(t and not t[4] and (int(t[1]), int(t[2]), int(t[3])) == (N, H, H))
+
+
 def parse_forms(labels, c, B):
     """the forms of one train step (forward, then the backward from its opening "zero fill" launch), from its launch labels.
     Feed-forward products are told apart by their shapes: the activation product of the forward (EPI_BIAS_GELU, [., inner] from
@@ -127,7 +136,8 @@ def parse_forms(labels, c, B):
     for j, l in enumerate(bwd):
         g, t = GEMM_DETAIL.match(l), TN_DETAIL.match(l)
         if l.startswith("b4r_attn_block_bwd"):
-            attn_bwd.append("Block" if bwd[j + 1].startswith("b4r_gemm_tn_f32") else "BlockFolded")
+            nxt = next(m for m in bwd[j + 1:] if not m.startswith("slab_reduce"))
+            attn_bwd.append("Block" if is_wo_grad(nxt, N, c.H) else "BlockFolded")
         elif l.startswith("attention core backward, queries = the head's slots"):
             attn_bwd.append("SlotQuery")
         elif l.startswith("b4r_attn_bwd_hd"):

@@ -340,7 +340,7 @@ def test_gemm_tn_dropout_on_b(Mo, No):
     assert T.maxdiff(cs, Bd.sum(0)) < 2e-4
 
 
-@pytest.mark.parametrize("H", [32, 64, 128, 256, 512])
+@pytest.mark.parametrize("H", [32, 64, 128, 256, 512, 1024])
 def test_layer_norm_fwd_bwd(H):
     rows = 333
     lib = _lib.load()
@@ -550,7 +550,8 @@ def _c_rank_oracle():
     return C.CDLL(so)
 
 
-@pytest.mark.parametrize("R,Cn,H,V", [(64, 101, 64, 3709), (5, 300, 256, 1000), (3, 3709, 64, 3709)])
+@pytest.mark.parametrize("R,Cn,H,V", [(64, 101, 64, 3709), (5, 300, 256, 1000), (3, 3709, 64, 3709), (7, 101, 32, 1000),
+                                      (3, 300, 1024, 2000)])
 def test_rank_candidates_bit_exact_against_c_oracle(R, Cn, H, V):
     """bert4rec_model.py:224-239 + bert4rec_evaluator.py:113-117; scores and ranked ids must be BIT-exact."""
     lib = _lib.load()

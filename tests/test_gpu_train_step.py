@@ -88,23 +88,26 @@ def relative_error(a, b):
     return float((a - b).abs().max()) / max(float(b.abs().max()), 1e-30)
 
 
-def launch_labels(fn):
-    """run fn() under the launch timer (b4r_timing_begin / b4r_timing_end): the labels of its launches in enqueue order"""
+def launch_labels(fn, cap=256):
+    """run fn() under the launch timer (b4r_timing_begin / b4r_timing_end): the labels of its launches in enqueue order.  The timer
+    records at most cap launches; a full record may have dropped some, so it fails rather than return a truncated list"""
     lib = _lib.load()
-    cap, stride = 256, 128
+    stride = 128
     n = C.c_int32(0)
     us = (C.c_float * cap)()
     names = C.create_string_buffer(cap * stride)
     _lib.check(lib.b4r_timing_begin(torch.cuda.current_stream().cuda_stream, cap), "b4r_timing_begin")
     fn()
     _lib.check(lib.b4r_timing_end(C.byref(n), us, names, stride, cap), "b4r_timing_end")
+    assert n.value < cap, f"launch timer full ({cap} launches): pass a larger cap"
     return [names.raw[j * stride:(j + 1) * stride].split(b"\0", 1)[0].decode() for j in range(n.value)]
 
 
-def run_and_check_train_step(eng, cfg_o, batch, cb, hp_o, step, seed, rel, labels=None, ref=orc.loss_and_grads):
+def run_and_check_train_step(eng, cfg_o, batch, cb, hp_o, step, seed, rel, labels=None, ref=orc.loss_and_grads, label_cap=256):
     """one Engine.train_step (the engine's state holds `step`), checked against the oracle as the module docstring says; returns the
-    state it left and the oracle's gradient norm.  labels (a list): filled with the step's launches (launch timer).  ref: the
-    restatement the step is checked against (ref(params, batch, cfg_o, training=, rng=) -> loss, gradients, outputs)"""
+    state it left and the oracle's gradient norm.  labels (a list): filled with the step's launches (launch timer, at most label_cap
+    of them).  ref: the restatement the step is checked against (ref(params, batch, cfg_o, training=, rng=) -> loss, gradients,
+    outputs)"""
     hp = hip_adamw_config(hp_o)
     eng.ensure_training_buffers()
     names = [n for n in eng.variable_names() if orc.is_trainable(n)]
@@ -114,7 +117,7 @@ def run_and_check_train_step(eng, cfg_o, batch, cb, hp_o, step, seed, rel, label
     if labels is None:
         eng.train_step(hp, cb)
     else:
-        labels[:] = launch_labels(lambda: eng.train_step(hp, cb))
+        labels[:] = launch_labels(lambda: eng.train_step(hp, cb), label_cap)
     torch.cuda.synchronize()
     st = eng.read_state()
     assert st["step"] == step + 1
