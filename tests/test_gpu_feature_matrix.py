@@ -104,16 +104,12 @@ def is_wo_grad(label, N, H):
     return label.startswith("b4r_gemm_tn_f32 pair") or bool(t and not t[4] and (int(t[1]), int(t[2]), int(t[3])) == (N, H, H))
 
 
-def parse_forms(labels, c, B):
-    """the forms of one train step (forward, then the backward from its opening "zero fill" launch), from its launch labels.
-    Feed-forward products are told apart by their shapes: the activation product of the forward (EPI_BIAS_GELU, [., inner] from
-    [., hidden]) and the activation-gradient product of the backward (EPI_GELU_BWD) run on B*L rows as tile products and on B*P
-    compact rows on the head's rows.  slot_only_last is not visible in the labels: the plan asks for it exactly where the last
-    layer runs the folded block backward with the feed-forward block (on the head's rows in a train step)."""
-    split = next(j for j, l in enumerate(labels) if l.startswith("zero fill"))
-    fwd, bwd = labels[:split], labels[split:]
+def parse_forward(fwd, c, B):
+    """the forward half of a step's forms -- or the forms of a forward alone (tests/test_gpu_inference_matrix.py) -- from its launch
+    labels: (attention form per layer, feed-forward form per layer, emb_proj, emb_fused, slotq_rows).  The activation product
+    (EPI_BIAS_GELU, [., inner] from [., hidden]) runs on B*L rows as a tile product and on B*P compact rows on the head's rows"""
     N, M = B * c.L, B * c.P
-    attn_fwd, ffn_fwd, attn_bwd, ffn_bwd = [], [], [], []
+    attn_fwd, ffn_fwd = [], []
     slotq_rows = False
     for j, l in enumerate(fwd):
         g = GEMM_DETAIL.match(l)
@@ -133,6 +129,22 @@ def parse_forms(labels, c, B):
             ffn_fwd.append("TileProducts" if int(g[1]) == N else "CompactRows")
             if int(g[1]) == M:   # no gather in front of it: the slot-query attention left the compact rows
                 slotq_rows = not fwd[j - 1].startswith("last layer on the head's rows: gather")
+    emb_proj = "embed_proj_fwd" in fwd
+    emb_fused = not emb_proj and "b4r_embed_ln_fwd" not in fwd
+    return attn_fwd, ffn_fwd, emb_proj, emb_fused, slotq_rows
+
+
+def parse_forms(labels, c, B):
+    """the forms of one train step (forward, then the backward from its opening "zero fill" launch), from its launch labels.
+    Feed-forward products are told apart by their shapes: the activation product of the forward (parse_forward) and the
+    activation-gradient product of the backward (EPI_GELU_BWD) run on B*L rows as tile products and on B*P compact rows on the
+    head's rows.  slot_only_last is not visible in the labels: the plan asks for it exactly where the last
+    layer runs the folded block backward with the feed-forward block (on the head's rows in a train step)."""
+    split = next(j for j, l in enumerate(labels) if l.startswith("zero fill"))
+    fwd, bwd = labels[:split], labels[split:]
+    N, M = B * c.L, B * c.P
+    attn_fwd, ffn_fwd, emb_proj, emb_fused, slotq_rows = parse_forward(fwd, c, B)
+    attn_bwd, ffn_bwd = [], []
     for j, l in enumerate(bwd):
         g, t = GEMM_DETAIL.match(l), TN_DETAIL.match(l)
         if l.startswith("b4r_attn_block_bwd"):
@@ -156,10 +168,8 @@ def parse_forms(labels, c, B):
             ffn_bwd.append("TileProducts")
     attn_bwd.reverse()
     ffn_bwd.reverse()
-    emb_proj = "embed_proj_fwd" in fwd
     assert emb_proj == ("embed_proj_bwd" in bwd), labels
     assert ffn_fwd == ffn_bwd, (ffn_fwd, ffn_bwd, labels)
-    emb_fused = not emb_proj and "b4r_embed_ln_fwd" not in fwd
     slot_only_last = bool(attn_bwd) and attn_bwd[-1] == "BlockFolded" and ffn_fwd[-1:] == ["Block"]
     return Forms(tuple(attn_fwd), tuple(attn_bwd), tuple(ffn_fwd), emb_proj, emb_fused, slot_only_last, slotq_rows)
 
