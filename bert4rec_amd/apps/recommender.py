@@ -8,7 +8,11 @@ differences from the reference, both documented in INTEGRATION.md: it reads ``ml
 [UNK], which are excluded here together with the seen items.
 
 recommend_batch serves many users at once: one forward over the stacked batch and one b4r_rank_full call (the best k allowed items of
-every user in one sweep over the vocabulary, no [users, V] scores, the seen items excluded on the device)."""
+every user in one sweep over the vocabulary, no [users, V] scores, the seen items excluded on the device).
+
+allowed_items / allowed_items_per_user restrict the catalogue (items in stock, one category, one allow-list per market): the lists
+become packed item filters that the same sweep applies (b4r_rank_full_ex).  similar_items returns the nearest neighbours of items in
+the learned item table (b4r_item_neighbours)."""
 import numpy as np
 import torch
 
@@ -18,7 +22,36 @@ class Recommender:
         self.model = model
         self.dataloader = dataloader
 
-    def __call__(self, sequence: list, k: int = 1):
+    def _known_tokens(self, items) -> list:
+        """Token ids of the items the vocabulary knows, in order; unknown items are ignored (and never added to the vocabulary)."""
+        tokenizer = self.dataloader.get_tokenizer()
+        extensible = getattr(tokenizer, "_extensible", False)
+        tokenizer.disable_extensibility()
+        tokens = []
+        try:
+            for item in items:
+                try:
+                    t = tokenizer.tokenize(item)
+                except (RuntimeError, ValueError):
+                    continue
+                if isinstance(t, int) and 0 <= t < self.model.vocab_size:
+                    tokens.append(t)
+        finally:
+            if extensible:
+                tokenizer.enable_extensibility()
+        return tokens
+
+    def _item_mask(self, items) -> torch.Tensor:
+        mask = torch.zeros(self.model.vocab_size, dtype=torch.bool)
+        tokens = self._known_tokens(items)
+        if tokens:
+            mask[torch.as_tensor(tokens, dtype=torch.int64)] = True
+        return mask
+
+    def __call__(self, sequence: list, k: int = 1, allowed_items=None):
+        """allowed_items: an iterable of items; only those are recommended (the filtered call goes through recommend_batch)."""
+        if allowed_items is not None:
+            return self.recommend_batch([sequence], k, allowed_items=allowed_items)[0]
         tokenizer = self.dataloader.get_tokenizer()
         batch = self.dataloader.prepare_inference(list(sequence))
         batch = {key: torch.from_numpy(np.asarray(v)) for key, v in batch.items()}
@@ -30,10 +63,22 @@ class Recommender:
         items = tokenizer.detokenize(top)
         return items[0] if k == 1 else items
 
-    def recommend_batch(self, sequences, k: int = 1) -> list:
-        """Recommender(...)(seq, k) for every sequence of `sequences`, from one batched forward and one full-catalogue top-k."""
+    def recommend_batch(self, sequences, k: int = 1, allowed_items=None, allowed_items_per_user=None) -> list:
+        """Recommender(...)(seq, k) for every sequence of `sequences`, from one batched forward and one full-catalogue top-k.
+        allowed_items: one iterable of items (detokenized values) for all users; allowed_items_per_user: one iterable per sequence
+        (identical lists share one filter).  Only allowed items are recommended; items the vocabulary does not know are ignored.
+        With k = 1 a user for whom nothing is left to recommend gets None, with or without a filter (every item seen or excluded)."""
         tokenizer = self.dataloader.get_tokenizer()
         sequences = [list(seq) for seq in sequences]
+        if allowed_items is not None and allowed_items_per_user is not None:
+            raise ValueError("give allowed_items or allowed_items_per_user, not both")
+        user_filter = None
+        if allowed_items_per_user is not None:
+            lists = [list(items) for items in allowed_items_per_user]
+            if len(lists) != len(sequences):
+                raise ValueError(f"{len(lists)} allow-lists for {len(sequences)} sequences")
+            distinct = {}
+            user_filter = [distinct.setdefault(frozenset(self._known_tokens(items)), len(distinct)) for items in lists]
         if not sequences:
             return []
         batches = [self.dataloader.prepare_inference(list(seq)) for seq in sequences]
@@ -44,7 +89,18 @@ class Recommender:
         for i, t in enumerate(seen):
             if t:
                 exclude[i, :len(t)] = torch.as_tensor(t, dtype=torch.int64)
-        ids, _, slots = self.model.recommend_tensor(batch, k=k, exclude_seen=False, exclude=exclude)
+        allow = row_filter = None
+        if allowed_items is not None:
+            allow = self._item_mask(allowed_items)
+        elif user_filter is not None:
+            allow = torch.zeros((len(distinct), self.model.vocab_size), dtype=torch.bool)
+            for tokens, f in distinct.items():
+                if tokens:
+                    allow[f, torch.as_tensor(sorted(tokens), dtype=torch.int64)] = True
+            # one filter index per ranked slot: the slots of recommend_tensor are those with masked_lm_weights != 0, in batch order
+            w = batch["masked_lm_weights"] != 0
+            row_filter = torch.as_tensor(user_filter, dtype=torch.int32)[torch.nonzero(w, as_tuple=True)[0]]
+        ids, _, slots = self.model.recommend_tensor(batch, k=k, exclude_seen=False, exclude=exclude, allow=allow, row_filter=row_filter)
         P = int(batch["masked_lm_positions"].shape[1])
         first = {}
         for i, s in enumerate(slots.cpu().tolist()):   # __call__ ranks the first weighted slot of its one-row batch
@@ -54,5 +110,20 @@ class Recommender:
         for b in range(len(sequences)):
             top = [i for i in ids_h[first[b]] if i >= 0] if b in first else []
             items = tokenizer.detokenize(top)
-            out.append(items[0] if k == 1 else items)
+            out.append((items[0] if items else None) if k == 1 else items)   # None: nothing is left to recommend (filtered or not)
         return out
+
+    def similar_items(self, items, k: int = 10, metric: str = "cosine", allowed_items=None) -> list:
+        """For every item of `items` the k nearest items of the learned item table, as detokenized lists (best first); metric
+        "cosine" or "dot".  An item the vocabulary does not know gets an empty list.  allowed_items: only those are returned."""
+        tokenizer = self.dataloader.get_tokenizer()
+        items = list(items)
+        if not items:
+            return []
+        query = []
+        for item in items:
+            t = self._known_tokens([item])
+            query.append(t[0] if t else -1)
+        allow = None if allowed_items is None else self._item_mask(allowed_items)
+        ids, _ = self.model.similar_items_tensor(torch.as_tensor(query, dtype=torch.int64), k=k, metric=metric, allow=allow)
+        return [tokenizer.detokenize([i for i in row if i >= 0]) for row in ids.cpu().tolist()]

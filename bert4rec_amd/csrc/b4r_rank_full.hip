@@ -21,6 +21,12 @@
 //   3. merge      one workgroup per row: the same radix select on (score key << 32 | ~id) over all chunks' candidates, then the
 //                 order of the K survivors by counting, descending key; gt_rank = 1 + the sum of the chunks' counts.
 // No floating-point atomics; LDS integer atomics only place or count, and the outputs do not depend on their order.
+//
+// b4r_rank_full_ex adds a catalogue filter (packed allow bits per filter, one filter per row: the sweep's per-row LDS bitmap starts
+// from the complement of the row's 32 filter words of the chunk instead of zeros), an item scale (one fp32 multiply after the
+// chain) and bias = NULL.  The sweep is a template on (filter, scale, bias); <false, false, true> is b4r_rank_full's kernel.
+// b4r_item_neighbours ranks the item table against its own rows with the same sweep: item_rnorm_kernel (cosine only) and
+// item_query_kernel stage 1 / |row| and the query rows in scratch first.
 #include <algorithm>
 
 #include "b4r_common.h"
@@ -46,10 +52,12 @@ __device__ __forceinline__ uint32_t score_key_bits(uint32_t u) {
 }
 __device__ __forceinline__ uint32_t score_key(float s) { return score_key_bits(__builtin_bit_cast(uint32_t, s)); }
 
-__device__ __forceinline__ float row_score(const float* h, const float* e, const float* bias, int64_t j, int H) {
+// bias NULL: + 0.0f; scale (NULL: none) multiplies the rounded chain once
+__device__ __forceinline__ float row_score(const float* h, const float* e, const float* bias, const float* scale, int64_t j, int H) {
   float acc = 0.f;
   for (int k = 0; k < H; ++k) acc = __builtin_fmaf(h[k], e[k], acc);   // k-ordered fp32 fma chain (the contract)
-  return acc + bias[j];
+  const float s = acc + (bias ? bias[j] : 0.f);
+  return scale ? s * scale[j] : s;
 }
 
 // state of one row's radix select over W-bit unique keys: `hi` top bits are resolved (= prefix); `rem` ids are still to be taken
@@ -132,8 +140,8 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
 // ---- 1. score key of the held-out item ----------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void full_gt_key_kernel(const float* __restrict__ hidden, int hidden_ld,
                                                           const int64_t* __restrict__ hidden_row, const float* __restrict__ table,
-                                                          const float* __restrict__ bias, int H, int V, int lo,
-                                                          const int64_t* __restrict__ gt, int64_t r0, int n,
+                                                          const float* __restrict__ bias, const float* __restrict__ scale, int H,
+                                                          int V, int lo, const int64_t* __restrict__ gt, int64_t r0, int n,
                                                           uint32_t* __restrict__ gkey) {
   const int lr = blockIdx.x * 64 + threadIdx.x;
   if (lr >= n) return;
@@ -141,7 +149,7 @@ __global__ __launch_bounds__(64) void full_gt_key_kernel(const float* __restrict
   const int64_t g = gt[r];
   if (g < lo || g >= V) { gkey[lr] = 0u; return; }
   const int64_t hr = hidden_row ? hidden_row[r] : r;
-  gkey[lr] = score_key(row_score(hidden + hr * hidden_ld, table + g * H, bias, g, H));
+  gkey[lr] = score_key(row_score(hidden + hr * hidden_ld, table + g * H, bias, scale, g, H));
 }
 
 // ---- 2. sweep: (group of FG rows) x (chunk of FCH ids) -------------------------------------------------------------------------
@@ -154,7 +162,16 @@ struct SweepArgs {
   int hidden_ld, H, V, lo, E, n, nch, cap;
 };
 
-__global__ __launch_bounds__(FT, 2) void full_sweep_kernel(SweepArgs a) {
+// what only the FILT / SCALE instances read: a kernel argument of its own, so that the unfiltered instance's argument block, and
+// with it its scalar registers and its code, stay as they were before the filter
+struct SweepExtra {
+  const float* scale;                                                // [V] (SCALE instances)
+  const uint32_t* allow; const int32_t* row_filter; int n_filters;   // [n_filters][ceil(V / 32)], [R] or NULL (FILT instances)
+};
+
+// FILT: the row bitmap starts from the row's filter words; SCALE: score = fl32((chain + bias) * scale[j]); BIAS = false: bias is +0.0f
+template <bool FILT, bool SCALE, bool BIAS>
+__global__ __launch_bounds__(FT, 2) void full_sweep_kernel(SweepArgs a, SweepExtra x) {
   __shared__ float tile[FIPT * FT * (FKB + 1)];
   __shared__ __attribute__((aligned(16))) float hsh[FG * FKB];
   __shared__ uint32_t bits[FG][FCH / 32];
@@ -180,7 +197,23 @@ __global__ __launch_bounds__(FT, 2) void full_sweep_kernel(SweepArgs a) {
     s_cnt[tid] = 0; s_beat[tid] = 0; s_out[tid] = 0;
     s_kmin[tid] = 0xFFFFFFFFu; s_kmax[tid] = 0u;
   }
-  for (int i = tid; i < FG * (FCH / 32); i += FT) (&bits[0][0])[i] = 0u;
+  if constexpr (FILT) {
+    // bit set = not ranked: the complement of the row's filter words of this chunk (no filter for the row: all ranked)
+    const int64_t W = ((int64_t)a.V + 31) >> 5;
+    for (int i = tid; i < FG * (FCH / 32); i += FT) {
+      const int g = i / (FCH / 32), w = i - g * (FCH / 32);
+      const int lr = lr0 + g;
+      const int64_t wi = (c0 >> 5) + w;
+      uint32_t word = 0u;
+      if (lr < a.n && wi < W) {
+        const int32_t f = x.row_filter ? x.row_filter[a.r0 + lr] : 0;
+        if (f >= 0 && f < x.n_filters) word = ~x.allow[(int64_t)f * W + wi];
+      }
+      bits[g][w] = word;
+    }
+  } else {
+    for (int i = tid; i < FG * (FCH / 32); i += FT) (&bits[0][0])[i] = 0u;
+  }
   __syncthreads();
   if (a.E > 0) {
     for (int f = tid; f < FG * a.E; f += FT) {
@@ -242,12 +275,15 @@ __global__ __launch_bounds__(FT, 2) void full_sweep_kernel(SweepArgs a) {
       const int l = q * FT + tid;
       const int64_t j = c0 + l;
       const bool inb = j >= a.lo && j < a.V;
-      const float b = inb ? a.bias[j] : 0.f;
+      const float b = BIAS ? (inb ? a.bias[j] : 0.f) : 0.f;
+      const float sc = SCALE ? (inb ? x.scale[j] : 1.f) : 1.f;
 #pragma unroll
       for (int g = 0; g < FG; ++g) {
         const bool ex = (bits[g][l >> 5] >> (l & 31)) & 1u;
         const bool ok = inb && s_hoff[g] >= 0 && (!ex || j == s_gt[g]);
-        raw[q][g] = ok ? __builtin_bit_cast(uint32_t, acc[ii][g] + b) : NOT_ALLOWED;
+        // (the unfiltered instance keeps the statement it had: a sum formed outside the select compiles to other code)
+        if constexpr (SCALE) raw[q][g] = ok ? __builtin_bit_cast(uint32_t, (acc[ii][g] + b) * sc) : NOT_ALLOWED;
+        else raw[q][g] = ok ? __builtin_bit_cast(uint32_t, acc[ii][g] + b) : NOT_ALLOWED;
       }
     }
   }
@@ -437,6 +473,106 @@ int64_t chunks_of(int32_t V) { return ((int64_t)V + FCH - 1) / FCH; }
 int64_t cap_of(int32_t K) { return std::min<int64_t>(K, FCH); }
 int64_t row_bytes(int32_t V, int32_t K) { return chunks_of(V) * (cap_of(K) * 8 + 8) + 4; }   // scores, ids | counts, beats | gt key
 
+
+// ---- item neighbours: 1 / |row| of every table row, and the staged query rows ------------------------------------------------
+// one thread per row, k ascending, one fp32 fma per element: a fixed order, so rnorm is bitwise reproducible
+__global__ __launch_bounds__(FT) void item_rnorm_kernel(const float* __restrict__ table, int H, int V, float* __restrict__ rnorm) {
+  const int64_t j = (int64_t)blockIdx.x * FT + threadIdx.x;
+  if (j >= V) return;
+  const float* e = table + j * H;
+  float ss = 0.f;
+  for (int k = 0; k < H; k += 4) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(e + k);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) ss = __builtin_fmaf(v[u], v[u], ss);
+  }
+  rnorm[j] = 1.0f / sqrtf(fmaxf(ss, 1e-24f));
+}
+
+// qhat[r][k] = table[q_r][k] (* rnorm[q_r] when given); qrow[r] = r, or -1 (the sweep ranks nothing for the row) when q_r is no item
+__global__ __launch_bounds__(FT) void item_query_kernel(const float* __restrict__ table, int H, int V, int lo,
+                                                        const int64_t* __restrict__ query, int R, const float* __restrict__ rnorm,
+                                                        float* __restrict__ qhat, int64_t* __restrict__ qrow) {
+  const int64_t i = (int64_t)blockIdx.x * FT + threadIdx.x;
+  if (i >= (int64_t)R * H) return;
+  const int r = (int)(i / H), k = (int)(i - (int64_t)r * H);
+  const int64_t q = query[r];
+  const bool ok = q >= lo && q < V;
+  float v = 0.f;
+  if (ok) {
+    v = table[q * H + k];
+    if (rnorm) v *= rnorm[q];
+  }
+  qhat[i] = v;
+  if (k == 0) qrow[r] = ok ? r : -1;
+}
+
+using SweepFn = void (*)(SweepArgs, SweepExtra);
+SweepFn sweep_instance(bool filt, bool scale, bool bias) {
+  static const SweepFn table[8] = {
+      full_sweep_kernel<false, false, false>, full_sweep_kernel<false, false, true>, full_sweep_kernel<false, true, false>,
+      full_sweep_kernel<false, true, true>,   full_sweep_kernel<true, false, false>, full_sweep_kernel<true, false, true>,
+      full_sweep_kernel<true, true, false>,   full_sweep_kernel<true, true, true>};
+  return table[(filt ? 4 : 0) | (scale ? 2 : 0) | (bias ? 1 : 0)];
+}
+
+// the one implementation behind b4r_rank_full (allow_bits, item_scale NULL; bias required), b4r_rank_full_ex and b4r_item_neighbours
+int rank_full_impl(const char* what, bool bias_required, const float* hidden, int32_t hidden_ld, const int64_t* hidden_row,
+                   const float* table, const float* bias, int32_t H, int32_t V, int32_t first_item, int32_t R, const int64_t* exclude,
+                   int32_t E, const int64_t* gt, int32_t K, const uint32_t* allow_bits, int32_t n_filters, const int32_t* row_filter,
+                   const float* item_scale, int64_t* topk_ids, float* topk_scores, int32_t* gt_rank, void* scratch,
+                   int64_t scratch_bytes, hipStream_t s) {
+  B4R_CHECK_ARG(R >= 0 && K >= 0 && K <= FK_MAX && E >= 0 && first_item >= 0, B4R_E_SHAPE,
+                "%s: bad shape (R = %d, K = %d in [0, %d], E = %d, first_item = %d)", what, R, K, FK_MAX, E, first_item);
+  B4R_CHECK_ARG(H > 0 && H % 4 == 0 && H <= 4096 && hidden_ld >= H && V > 0, B4R_E_SHAPE,
+                "%s: bad shape (H = %d, hidden_ld = %d, V = %d)", what, H, hidden_ld, V);
+  B4R_CHECK_ARG(!allow_bits || n_filters > 0, B4R_E_SHAPE, "%s: allow_bits with n_filters = %d", what, n_filters);
+  if (R == 0) return B4R_OK;
+  B4R_CHECK_ARG(hidden && table && (bias || !bias_required), B4R_E_BADARG, "%s: null argument", what);
+  B4R_CHECK_ARG(E == 0 || exclude, B4R_E_BADARG, "%s: exclude is NULL with E = %d", what, E);
+  B4R_CHECK_ARG(b4r_aligned16(table), B4R_E_ALIGN, "%s: the table must be 16-byte aligned", what);
+  const int64_t per_row = row_bytes(V, K);
+  const int64_t usable = scratch ? scratch_bytes - (int64_t)((16 - ((uintptr_t)scratch & 15)) & 15) : 0;
+  int64_t group = usable > 0 ? usable / per_row : 0;
+  group = std::min<int64_t>(group, R);
+  if (group < R) group = group / FG * FG;   // whole sweep groups
+  B4R_CHECK_ARG(group >= std::min<int64_t>(R, FG), B4R_E_NOMEM,
+                "%s: scratch of %lld bytes is too small: %lld bytes per row, %d rows at least (b4r_rank_full_scratch_bytes)", what,
+                (long long)scratch_bytes, (long long)per_row, std::min<int32_t>(R, FG));
+  group = std::min<int64_t>(group, 65535LL * FG);
+  const int nch = (int)chunks_of(V);
+  B4R_CHECK_ARG(nch <= 65535, B4R_E_SHAPE, "%s: V = %d is too large", what, V);
+  const int cap = (int)cap_of(K);
+  char* p = reinterpret_cast<char*>(((uintptr_t)scratch + 15) & ~(uintptr_t)15);
+  float* c_score = reinterpret_cast<float*>(p);
+  int32_t* c_id = reinterpret_cast<int32_t*>(c_score + group * nch * cap);
+  int32_t* c_cnt = c_id + group * nch * cap;
+  int32_t* c_beat = c_cnt + group * nch;
+  uint32_t* gkey = reinterpret_cast<uint32_t*>(c_beat + group * nch);
+  const SweepFn sweep = sweep_instance(allow_bits != nullptr, item_scale != nullptr, bias != nullptr);
+  for (int64_t r0 = 0; r0 < R; r0 += group) {
+    const int n = (int)std::min<int64_t>(group, R - r0);
+    if (gt) {
+      hipLaunchKernelGGL(full_gt_key_kernel, dim3(b4r_cdiv(n, 64)), dim3(64), 0, s, hidden, hidden_ld, hidden_row, table, bias,
+                         item_scale, H, V, first_item, gt, r0, n, gkey);
+    }
+    SweepArgs sa{hidden, hidden_row, table, bias, exclude, gt, gkey, c_score, c_id, c_cnt, c_beat, r0,
+                 hidden_ld, H, V, first_item, E, n, nch, cap};
+    SweepExtra sx{item_scale, allow_bits, row_filter, n_filters};
+    hipLaunchKernelGGL(sweep, dim3(b4r_cdiv(n, FG), nch), dim3(FT), 0, s, sa, sx);
+    MergeArgs ma{c_score, c_id, c_cnt, c_beat, gt, topk_ids, topk_scores, gt_rank, r0, nch, cap, K, first_item, V};
+    hipLaunchKernelGGL(full_merge_kernel, dim3(n), dim3(FT), 0, s, ma);
+  }
+  B4R_CHECK_LAUNCH(what);
+  return B4R_OK;
+}
+
+// b4r_item_neighbours' own regions in front of the sweep's scratch, each a multiple of 16 bytes: rnorm [V] | qhat [R, width] | qrow [R]
+int64_t align16(int64_t b) { return (b + 15) & ~(int64_t)15; }
+int64_t neighbour_bytes(int32_t R, int32_t V, int32_t width) {
+  return align16((int64_t)V * 4) + align16((int64_t)R * width * 4) + align16((int64_t)R * 8);
+}
+
 }  // namespace
 
 extern "C" int64_t b4r_rank_full_scratch_bytes(int32_t R, int32_t V, int32_t K) {
@@ -448,45 +584,55 @@ extern "C" int b4r_rank_full(const float* hidden, int32_t hidden_ld, const int64
                              int32_t H, int32_t V, int32_t first_item, int32_t R, const int64_t* exclude, int32_t E, const int64_t* gt,
                              int32_t K, int64_t* topk_ids, float* topk_scores, int32_t* gt_rank, void* scratch, int64_t scratch_bytes,
                              b4r_stream_t stream) {
-  B4R_CHECK_ARG(R >= 0 && K >= 0 && K <= FK_MAX && E >= 0 && first_item >= 0, B4R_E_SHAPE,
-                "b4r_rank_full: bad shape (R = %d, K = %d in [0, %d], E = %d, first_item = %d)", R, K, FK_MAX, E, first_item);
-  B4R_CHECK_ARG(H > 0 && H % 4 == 0 && H <= 4096 && hidden_ld >= H && V > 0, B4R_E_SHAPE,
-                "b4r_rank_full: bad shape (H = %d, hidden_ld = %d, V = %d)", H, hidden_ld, V);
+  return rank_full_impl("b4r_rank_full", true, hidden, hidden_ld, hidden_row, table, bias, H, V, first_item, R, exclude, E, gt, K,
+                        nullptr, 0, nullptr, nullptr, topk_ids, topk_scores, gt_rank, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+extern "C" int b4r_rank_full_ex(const float* hidden, int32_t hidden_ld, const int64_t* hidden_row, const float* table,
+                                const float* bias, int32_t H, int32_t V, int32_t first_item, int32_t R, const int64_t* exclude,
+                                int32_t E, const int64_t* gt, int32_t K, int64_t* topk_ids, float* topk_scores, int32_t* gt_rank,
+                                void* scratch, int64_t scratch_bytes, b4r_stream_t stream, const uint32_t* allow_bits,
+                                int32_t n_filters, const int32_t* row_filter, const float* item_scale) {
+  return rank_full_impl("b4r_rank_full_ex", false, hidden, hidden_ld, hidden_row, table, bias, H, V, first_item, R, exclude, E, gt, K,
+                        allow_bits, n_filters, row_filter, item_scale, topk_ids, topk_scores, gt_rank, scratch, scratch_bytes,
+                        (hipStream_t)stream);
+}
+
+extern "C" int64_t b4r_item_neighbours_scratch_bytes(int32_t R, int32_t V, int32_t K, int32_t width) {
+  if (R <= 0 || V <= 0 || K < 0 || K > FK_MAX || width <= 0) return 0;
+  return neighbour_bytes(R, V, width) + b4r_rank_full_scratch_bytes(R, V, K);
+}
+
+extern "C" int b4r_item_neighbours(const float* table, int32_t ld, int32_t width, int32_t V, int32_t first_item,
+                                   const int64_t* query_ids, int32_t R, int32_t metric, const uint32_t* allow_bits, int32_t n_filters,
+                                   const int32_t* row_filter, int32_t K, int64_t* topk_ids, float* topk_scores, void* scratch,
+                                   int64_t scratch_bytes, b4r_stream_t stream) {
+  const char* what = "b4r_item_neighbours";
+  B4R_CHECK_ARG(R >= 0 && K >= 0 && K <= FK_MAX && first_item >= 0, B4R_E_SHAPE, "%s: bad shape (R = %d, K = %d in [0, %d], first_item = %d)",
+                what, R, K, FK_MAX, first_item);
+  // the sweep reads table row j at table + j * width: a padded table (ld > width) is not taken
+  B4R_CHECK_ARG(width > 0 && width % 4 == 0 && width <= 4096 && ld == width && V > 0, B4R_E_SHAPE,
+                "%s: bad shape (width = %d: a multiple of 4 up to 4096, ld = %d: must equal width, V = %d)", what, width, ld, V);
+  B4R_CHECK_ARG(metric == B4R_SIM_DOT || metric == B4R_SIM_COSINE, B4R_E_BADARG, "%s: unknown metric %d", what, metric);
   if (R == 0) return B4R_OK;
-  B4R_CHECK_ARG(hidden && table && bias, B4R_E_BADARG, "b4r_rank_full: null argument");
-  B4R_CHECK_ARG(E == 0 || exclude, B4R_E_BADARG, "b4r_rank_full: exclude is NULL with E = %d", E);
-  B4R_CHECK_ARG(b4r_aligned16(table), B4R_E_ALIGN, "b4r_rank_full: the table must be 16-byte aligned");
-  const int64_t per_row = row_bytes(V, K);
-  const int64_t usable = scratch ? scratch_bytes - (int64_t)((16 - ((uintptr_t)scratch & 15)) & 15) : 0;
-  int64_t group = usable > 0 ? usable / per_row : 0;
-  group = std::min<int64_t>(group, R);
-  if (group < R) group = group / FG * FG;   // whole sweep groups
-  B4R_CHECK_ARG(group >= std::min<int64_t>(R, FG), B4R_E_NOMEM,
-                "b4r_rank_full: scratch of %lld bytes is too small: %lld bytes per row, %d rows at least (b4r_rank_full_scratch_bytes)",
-                (long long)scratch_bytes, (long long)per_row, std::min<int32_t>(R, FG));
-  group = std::min<int64_t>(group, 65535LL * FG);
+  B4R_CHECK_ARG(table && query_ids, B4R_E_BADARG, "%s: null argument", what);
+  B4R_CHECK_ARG(b4r_aligned16(table), B4R_E_ALIGN, "%s: the table must be 16-byte aligned", what);
+  const int64_t pad = scratch ? (int64_t)((16 - ((uintptr_t)scratch & 15)) & 15) : 0;
+  const int64_t own = neighbour_bytes(R, V, width);
+  B4R_CHECK_ARG(scratch && scratch_bytes - pad > own, B4R_E_NOMEM, "%s: scratch of %lld bytes is too small (b4r_item_neighbours_scratch_bytes)",
+                what, (long long)scratch_bytes);
+  char* p = reinterpret_cast<char*>(scratch) + pad;
+  float* rnorm = reinterpret_cast<float*>(p);
+  float* qhat = reinterpret_cast<float*>(p + align16((int64_t)V * 4));
+  int64_t* qrow = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(qhat) + align16((int64_t)R * width * 4));
+  char* rest = p + own;
   hipStream_t s = (hipStream_t)stream;
-  const int nch = (int)chunks_of(V);
-  B4R_CHECK_ARG(nch <= 65535, B4R_E_SHAPE, "b4r_rank_full: V = %d is too large", V);
-  const int cap = (int)cap_of(K);
-  char* p = reinterpret_cast<char*>(((uintptr_t)scratch + 15) & ~(uintptr_t)15);
-  float* c_score = reinterpret_cast<float*>(p);
-  int32_t* c_id = reinterpret_cast<int32_t*>(c_score + group * nch * cap);
-  int32_t* c_cnt = c_id + group * nch * cap;
-  int32_t* c_beat = c_cnt + group * nch;
-  uint32_t* gkey = reinterpret_cast<uint32_t*>(c_beat + group * nch);
-  for (int64_t r0 = 0; r0 < R; r0 += group) {
-    const int n = (int)std::min<int64_t>(group, R - r0);
-    if (gt) {
-      hipLaunchKernelGGL(full_gt_key_kernel, dim3(b4r_cdiv(n, 64)), dim3(64), 0, s, hidden, hidden_ld, hidden_row, table, bias, H, V,
-                         first_item, gt, r0, n, gkey);
-    }
-    SweepArgs sa{hidden, hidden_row, table, bias, exclude, gt, gkey, c_score, c_id, c_cnt, c_beat, r0,
-                 hidden_ld, H, V, first_item, E, n, nch, cap};
-    hipLaunchKernelGGL(full_sweep_kernel, dim3(b4r_cdiv(n, FG), nch), dim3(FT), 0, s, sa);
-    MergeArgs ma{c_score, c_id, c_cnt, c_beat, gt, topk_ids, topk_scores, gt_rank, r0, nch, cap, K, first_item, V};
-    hipLaunchKernelGGL(full_merge_kernel, dim3(n), dim3(FT), 0, s, ma);
-  }
-  B4R_CHECK_LAUNCH("b4r_rank_full");
-  return B4R_OK;
+  const bool cosine = metric == B4R_SIM_COSINE;
+  if (cosine) hipLaunchKernelGGL(item_rnorm_kernel, dim3(b4r_cdiv(V, FT)), dim3(FT), 0, s, table, width, V, rnorm);
+  hipLaunchKernelGGL(item_query_kernel, dim3(b4r_cdiv((int64_t)R * width, FT)), dim3(FT), 0, s, table, width, V, first_item, query_ids, R,
+                     cosine ? rnorm : nullptr, qhat, qrow);
+  // the query excludes itself: query_ids is the [R, 1] exclude list
+  return rank_full_impl(what, false, qhat, width, qrow, table, nullptr, width, V, first_item, R, query_ids, 1, nullptr, K, allow_bits,
+                        n_filters, row_filter, cosine ? rnorm : nullptr, topk_ids, topk_scores, nullptr, rest,
+                        scratch_bytes - pad - own, s);
 }

@@ -156,6 +156,71 @@ def check_rank_full_args(k, exclude: Optional[torch.Tensor] = None, n_rows: Opti
     return k
 
 
+SIMILARITY_METRICS = {"dot": _lib.SIM_DOT, "cosine": _lib.SIM_COSINE}
+
+
+def pack_item_filter(mask) -> torch.Tensor:
+    """Pack an item mask (bool or uint8, [V] or [F, V]; nonzero = allowed) into b4r_rank_full_ex's allow_bits: uint32 [F, ceil(V / 32)],
+    bit (j & 31) of word (j >> 5) = item j.  Packs on the device the mask lives on."""
+    m = torch.as_tensor(mask)
+    if m.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"an item mask is bool or uint8, got {m.dtype}")
+    if m.ndim == 1:
+        m = m[None]
+    if m.ndim != 2 or m.shape[0] == 0 or m.shape[1] == 0:
+        raise ValueError(f"an item mask is [V] or [F, V], got shape {tuple(torch.as_tensor(mask).shape)}")
+    F, V = m.shape
+    W = (V + 31) // 32
+    bits = torch.zeros((F, W * 32), dtype=torch.int64, device=m.device)
+    bits[:, :V] = m != 0
+    words = (bits.view(F, W, 32) << torch.arange(32, dtype=torch.int64, device=m.device)).sum(dim=2)   # 0 .. 2^32 - 1
+    words = torch.where(words >= 1 << 31, words - (1 << 32), words).to(torch.int32)
+    return words.view(torch.uint32)
+
+
+def check_item_filter(allow, row_filter, vocab_size: int, n_rows: Optional[int] = None):
+    """Argument checks of the catalogue filter that need no GPU.  allow: None, a bool / uint8 mask [V] or [F, V], or packed uint32
+    [F, ceil(V / 32)] (pack_item_filter); row_filter: None or one filter index per ranked row (only with a 2-D allow; an index outside
+    [0, F) = no filter for the row).  Returns (packed uint32 [F, W] or None, row_filter int32 [R] or None)."""
+    if allow is None:
+        if row_filter is not None:
+            raise ValueError("row_filter needs a 2-D allow ([F, V] masks or packed [F, ceil(V / 32)] words)")
+        return None, None
+    allow = torch.as_tensor(allow)
+    W = (int(vocab_size) + 31) // 32
+    two_d = allow.ndim == 2
+    if allow.dtype == torch.uint32:
+        if allow.ndim != 2 or allow.shape[0] == 0 or allow.shape[1] != W:
+            raise ValueError(f"packed allow must be uint32 [F, {W}] for {vocab_size} items, got shape {tuple(allow.shape)}")
+        packed = allow
+    elif allow.dtype in (torch.bool, torch.uint8):
+        if allow.ndim not in (1, 2) or allow.shape[-1] != vocab_size or allow.shape[0] == 0:
+            raise ValueError(f"allow must be [{vocab_size}] or [F, {vocab_size}], got shape {tuple(allow.shape)}")
+        packed = pack_item_filter(allow)
+    else:
+        raise ValueError(f"allow must be bool, uint8 or packed uint32, got {allow.dtype}")
+    if row_filter is None:
+        if packed.shape[0] > 1:
+            raise ValueError(f"allow holds {packed.shape[0]} filters: row_filter must name the filter of each ranked row")
+        return packed, None
+    if not two_d:
+        raise ValueError("row_filter needs a 2-D allow ([F, V] masks or packed [F, ceil(V / 32)] words)")
+    row_filter = torch.as_tensor(row_filter)
+    if row_filter.dtype.is_floating_point or row_filter.dtype == torch.bool or row_filter.ndim != 1:
+        raise ValueError(f"row_filter must be a 1-D integer tensor, got {row_filter.dtype} of shape {tuple(row_filter.shape)}")
+    if n_rows is not None and row_filter.numel() != n_rows:
+        raise ValueError(f"row_filter has {row_filter.numel()} entries for {n_rows} ranked rows")
+    return packed, row_filter.clamp(-1, packed.shape[0]).to(torch.int32)
+
+
+def check_similar_items_args(k, metric) -> Tuple[int, int]:
+    """(k, B4R_SIM_* id) of Engine.item_neighbours: 0 <= k <= 1024, metric "dot" or "cosine"."""
+    k = check_rank_full_args(k)
+    if metric not in SIMILARITY_METRICS:
+        raise ValueError(f"metric must be one of {sorted(SIMILARITY_METRICS)}, got {metric!r}")
+    return k, SIMILARITY_METRICS[metric]
+
+
 class Engine:
     """One replica of the model on one GPU."""
 
@@ -608,13 +673,15 @@ class Engine:
         return ranking, gt_rank, scores
 
     def rank_full(self, hidden: torch.Tensor, rows: Optional[torch.Tensor], exclude: Optional[torch.Tensor], first_item: int,
-                  gt: Optional[torch.Tensor], k: int):
+                  gt: Optional[torch.Tensor], k: int, allow=None, row_filter=None):
         """b4r_rank_full on `hidden` [*,E] (the transform's rows, E = the item table's width; ld = stride(0)): rows [R] (hidden row of each ranked row) or None (R = hidden rows);
         exclude [R,E] int64 ids not to rank (-1 padded) or None; gt [R] int64 or None.  Returns (ids [R,k] int64, scores [R,k] fp32,
         gt_rank [R] int32 or None): the best k allowed items of every row over the whole vocabulary, ties to the lower id, -1 / -inf
-        where fewer than k are allowed.  The scratch buffer is kept between calls."""
+        where fewer than k are allowed.  The scratch buffer is kept between calls.
+        allow / row_filter (check_item_filter): only the items the row's filter allows are ranked (b4r_rank_full_ex)."""
         R = int(rows.numel()) if rows is not None else int(hidden.shape[0])
         k = check_rank_full_args(k, exclude, R)
+        allow, row_filter = check_item_filter(allow, row_filter, self.cfg.vocab_size, R)
         if hidden.dtype != torch.float32 or hidden.ndim != 2 or hidden.stride(1) != 1 or hidden.shape[1] != self.embedding_width:
             raise ValueError(f"hidden must be float32 [rows, {self.embedding_width}] with unit column stride")
         rows_d = None if rows is None else rows.to(device=self.device, dtype=torch.int64).contiguous()
@@ -635,12 +702,48 @@ class Engine:
         sc = getattr(self, "_rank_full_scratch", None)
         if sc is None or sc.numel() < want:
             sc = self._rank_full_scratch = torch.empty(want, dtype=torch.uint8, device=self.device)
-        _lib.check(self.lib.b4r_rank_full(_ptr(hidden), hidden.stride(0), _ptr(rows_d),
-                                          _ptr(self.view("word_embeddings/embeddings")),
-                                          _ptr(self.view("cls/predictions/output_bias/bias")), self.embedding_width, V, int(first_item),
-                                          R, _ptr(ex_d), E, _ptr(gt_d), k, _ptr(ids), _ptr(scores), _ptr(gt_rank), _ptr(sc),
-                                          sc.numel(), _stream(self.device)), "b4r_rank_full")
+        args = (_ptr(hidden), hidden.stride(0), _ptr(rows_d), _ptr(self.view("word_embeddings/embeddings")),
+                _ptr(self.view("cls/predictions/output_bias/bias")), self.embedding_width, V, int(first_item), R, _ptr(ex_d), E,
+                _ptr(gt_d), k, _ptr(ids), _ptr(scores), _ptr(gt_rank), _ptr(sc), sc.numel(), _stream(self.device))
+        if allow is None:
+            _lib.check(self.lib.b4r_rank_full(*args), "b4r_rank_full")
+        else:
+            allow_d = allow.to(self.device).contiguous()
+            rf_d = None if row_filter is None else row_filter.to(self.device).contiguous()
+            _lib.check(self.lib.b4r_rank_full_ex(*args, _ptr(allow_d), int(allow_d.shape[0]), _ptr(rf_d), None), "b4r_rank_full_ex")
         return ids, scores, gt_rank
+
+    def item_neighbours(self, item_ids: torch.Tensor, k: int, metric: str = "cosine", first_item: int = SPECIAL_IDS, allow=None,
+                        row_filter=None):
+        """b4r_item_neighbours on the item table [V, E]: the k items nearest to each of item_ids [R] ("dot": inner product, "cosine"),
+        without the item itself and the ids below first_item; allow / row_filter as in rank_full.  Returns (ids [R,k] int64, scores
+        [R,k] fp32); an item id outside [first_item, V) gives a row of -1 / -inf.  The scratch buffer is kept between calls."""
+        k, metric_id = check_similar_items_args(k, metric)
+        q = torch.as_tensor(item_ids)
+        if q.ndim != 1 or q.dtype.is_floating_point or q.dtype == torch.bool:
+            raise ValueError(f"item_ids must be a 1-D integer tensor, got {q.dtype} of shape {tuple(q.shape)}")
+        R, V, Ew = int(q.numel()), self.cfg.vocab_size, self.embedding_width
+        allow, row_filter = check_item_filter(allow, row_filter, V, R)
+        q = q.to(device=self.device, dtype=torch.int64).contiguous()
+        ids = torch.empty((R, k), dtype=torch.int64, device=self.device)
+        scores = torch.empty((R, k), dtype=torch.float32, device=self.device)
+        if R == 0:
+            return ids, scores
+        sweep = int(self.lib.b4r_rank_full_scratch_bytes(R, V, k))
+        own = int(self.lib.b4r_item_neighbours_scratch_bytes(R, V, k, Ew)) - sweep
+        least = int(self.lib.b4r_rank_full_scratch_bytes(min(R, 16), V, k))
+        want = own + min(sweep, max(least, 2 << 30))   # the sweep's share at most 2 GiB: more rows are then ranked in groups
+        sc = getattr(self, "_neighbours_scratch", None)
+        if sc is None or sc.numel() < want:
+            sc = self._neighbours_scratch = torch.empty(want, dtype=torch.uint8, device=self.device)
+        allow_d = None if allow is None else allow.to(self.device).contiguous()
+        rf_d = None if row_filter is None else row_filter.to(self.device).contiguous()
+        table = self.view("word_embeddings/embeddings")
+        _lib.check(self.lib.b4r_item_neighbours(_ptr(table), table.stride(0), Ew, V, int(first_item), _ptr(q), R, metric_id,
+                                                _ptr(allow_d), 0 if allow_d is None else int(allow_d.shape[0]), _ptr(rf_d), k,
+                                                _ptr(ids), _ptr(scores), _ptr(sc), sc.numel(), _stream(self.device)),
+                   "b4r_item_neighbours")
+        return ids, scores
 
     def rank_metrics(self, gt_rank: torch.Tensor, families, cutoffs, gain_sums: torch.Tensor, users: torch.Tensor) -> None:
         """b4r_rank_metrics: add this batch's gain sums to the device accumulators (float64 [n], int64 [1])."""

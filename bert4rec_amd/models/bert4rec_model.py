@@ -323,13 +323,17 @@ class BERT4RecModel:
         return out
 
     def recommend_tensor(self, encoder_input: Dict[str, torch.Tensor], k: int = 10, exclude_seen: bool = True,
-                         exclude: Optional[torch.Tensor] = None):
+                         exclude: Optional[torch.Tensor] = None, allow=None, row_filter=None):
         """Top k of the whole catalogue for every slot with masked_lm_weights == 1 (all slots when the key is absent), from one
         b4r_rank_full call: no [R, V] scores.  The forward is rank_items_tensor's (encoder, then tfm MaskedLM's transform on those
         slots only).  [PAD] / [MASK] / [UNK] are never recommended; exclude_seen drops the row's own input_word_ids; exclude
         [B, E] int64 (-1 padded): more ids per batch row not to recommend.  Returns (ids [R,k] int64, scores [R,k] fp32,
-        slot_index [R] int64 = b*P+p), on the device; a row with fewer than k allowed items ends in -1 / -inf."""
+        slot_index [R] int64 = b*P+p), on the device; a row with fewer than k allowed items ends in -1 / -inf.
+        allow: restrict the catalogue -- a bool / uint8 mask [V] (nonzero = may be recommended), masks [F, V] with row_filter [R]
+        (the filter of each ranked row; an index outside [0, F) = no filter), or packed uint32 [F, ceil(V / 32)]
+        (bert4rec_amd.apps.pack_item_filter).  The filter is applied inside the sweep (b4r_rank_full_ex)."""
         k = engine_mod.check_rank_full_args(k, exclude)
+        allow, row_filter = engine_mod.check_item_filter(allow, row_filter, self.vocab_size)
         hidden, slots, _ = self._ranked_slot_hidden(encoder_input)
         dev = self.device
         if hidden is None:
@@ -346,8 +350,15 @@ class BERT4RecModel:
                 raise ValueError(f"exclude has {ex.shape[0]} rows for a batch of {B}")
             parts.append(ex[b_idx])
         ex_rows = torch.cat(parts, dim=1) if parts else None
-        ids, scores, _ = self.engine.rank_full(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, k)
+        ids, scores, _ = self.engine.rank_full(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, k, allow, row_filter)
         return ids, scores, slots
+
+    def similar_items_tensor(self, item_ids, k: int = 10, metric: str = "cosine", allow=None, row_filter=None):
+        """Item-to-item neighbours in the encoder's item table (the tied output embedding, width E when factorised): for each of
+        item_ids [R] the k nearest items by metric "cosine" or "dot", the item itself and [PAD] / [MASK] / [UNK] left out, ties to
+        the lower id; allow / row_filter as in recommend_tensor.  Returns (ids [R,k] int64, scores [R,k] fp32) on the device; an
+        id that is no item gives a row of -1 / -inf.  One b4r_item_neighbours call: no [R, V] scores."""
+        return self.engine.item_neighbours(item_ids, k, metric, engine_mod.SPECIAL_IDS, allow, row_filter)
 
     def recommend(self, encoder_input: dict, k: int = 10, exclude_seen: bool = True, exclude=None):
         """recommend_tensor as Python lists: per batch row, one list per ranked slot of (ids, scores) lists of length k."""

@@ -290,6 +290,37 @@ int64_t b4r_rank_full_scratch_bytes(int32_t R, int32_t V, int32_t K);
 int b4r_rank_full(const float* hidden, int32_t hidden_ld, const int64_t* hidden_row, const float* table, const float* bias, int32_t H,
                   int32_t V, int32_t first_item, int32_t R, const int64_t* exclude, int32_t E, const int64_t* gt, int32_t K,
                   int64_t* topk_ids, float* topk_scores, int32_t* gt_rank, void* scratch, int64_t scratch_bytes, b4r_stream_t stream);
+/* b4r_rank_full over a restricted catalogue, with an optional per-item scale.  The first 19 arguments are b4r_rank_full's (scratch
+ * from b4r_rank_full_scratch_bytes); with allow_bits = item_scale = NULL and a bias it IS b4r_rank_full: same launches, same bits.
+ *   allow_bits  [n_filters, W] uint32, W = ceil(V / 32): bit (j & 31) of word (j >> 5) of filter f set = item j is allowed under f.
+ *               Bits of ids >= V and of ids < first_item are ignored.  NULL: no filter.
+ *   row_filter  [R] int32: the filter of each row; NULL = every row uses filter 0; a value outside [0, n_filters) = no filter for
+ *               that row.
+ *   allowed(r)  = { j in [first_item, V) : bit j of filter(r) set, j not in exclude[r] } plus gt[r] when it lies in
+ *                 [first_item, V): gt is ranked among allowed(r) even when its own bit is clear, as when it is listed in exclude.
+ *   item_scale  [V] or NULL: s(r, j) = fl32(chain(r, j) * item_scale[j]), one fp32 multiply of the rounded b4r_rank_full score
+ *               (chain = the k-ascending fma chain, + bias[j]).
+ *   bias        may be NULL here (b4r_rank_full refuses it): the chain's sum + 0.0f.
+ * The filter enters where the sweep builds its per-row bitmap of the chunk: no second pass, no [R, V] buffer. */
+int b4r_rank_full_ex(const float* hidden, int32_t hidden_ld, const int64_t* hidden_row, const float* table, const float* bias, int32_t H,
+                     int32_t V, int32_t first_item, int32_t R, const int64_t* exclude, int32_t E, const int64_t* gt, int32_t K,
+                     int64_t* topk_ids, float* topk_scores, int32_t* gt_rank, void* scratch, int64_t scratch_bytes, b4r_stream_t stream,
+                     const uint32_t* allow_bits, int32_t n_filters, const int32_t* row_filter, const float* item_scale);
+/* Item-to-item neighbours: the best K rows j of table [V, width] for each query row q_r = query_ids[r], by the same sweep.
+ *   B4R_SIM_DOT     s(r, j) = fma-chain_k(table[q_r][k] * table[j][k]) + 0.0f
+ *   B4R_SIM_COSINE  rnorm[j] = 1 / sqrt(max(sum_k table[j][k]^2, 1e-24f))  (one fp32 fma per element, k ascending);
+ *                   qhat[r][k] = fl32(table[q_r][k] * rnorm[q_r]);  s(r, j) = fl32((fma-chain_k(qhat[r][k] * table[j][k]) + 0.0f) * rnorm[j])
+ * Ranked: the ids in [first_item, V) allowed by the row's filter (allow_bits / n_filters / row_filter as in b4r_rank_full_ex),
+ * without q_r itself; ties to the lower id; fewer than K: id -1 / score -inf.  A query id outside [first_item, V) gives a whole
+ * row of -1 / -inf.  width: a multiple of 4 up to 4096; ld must equal width (else B4R_E_SHAPE); K in [0, 1024].
+ * scratch: b4r_item_neighbours_scratch_bytes(R, V, K, width) at least (more than the three staging regions but less than that
+ * ranks the rows in groups of 16).  After a cosine call the first V floats of the scratch, rounded up to 16 bytes, hold rnorm.
+ * Only enqueues (one stream, no host sync, graph-capturable); bitwise reproducible. */
+enum { B4R_SIM_DOT = 0, B4R_SIM_COSINE = 1 };
+int64_t b4r_item_neighbours_scratch_bytes(int32_t R, int32_t V, int32_t K, int32_t width);
+int b4r_item_neighbours(const float* table, int32_t ld, int32_t width, int32_t V, int32_t first_item, const int64_t* query_ids,
+                        int32_t R, int32_t metric, const uint32_t* allow_bits, int32_t n_filters, const int32_t* row_filter, int32_t K,
+                        int64_t* topk_ids, float* topk_scores, void* scratch, int64_t scratch_bytes, b4r_stream_t stream);
 /* replaces the metric loop of bert4rec_evaluator.py:118-120 over evaluation_metrics.py:47-112 for a batch of ranks:
  * gain_sums[m] += sum over gt_rank[i] > 0 of gain_m(gt_rank[i]), users[0] += #{gt_rank[i] > 0}; double / int64 DEVICE
  * accumulators the caller reads once per evaluate().  family[m]: 0 count (gain 1), 1 hit@cutoff (rank <= k), 2 NDCG@cutoff
