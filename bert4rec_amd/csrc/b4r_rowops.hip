@@ -455,13 +455,16 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(float* logits, int V, i
   }
   if (want_grad) {
     __syncthreads();  // every thread has finished reading the row
+    // softmax = exp(x - max) / sum, not exp(x - lse): lse is rounded at the size of the logits (half an ulp of 100 is 4e-6, of 1e4 is 5e-4),
+    // and a confident row's largest probability would carry that whole error; x - max is exact near the maximum (sum >= 1: it holds exp(0))
+    const float inv_sum = 1.0f / sum;
     for (int v = tid; v < nv; v += 256) {
       f32x4 x = *reinterpret_cast<const f32x4*>(row + 4 * v);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int c = 4 * v + e;
         float g = 0.f;
-        if (valid && c < V) g = __expf(x[e] - lse) - ((int64_t)c == y ? 1.f : 0.f);
+        if (valid && c < V) g = __expf(x[e] - best) * inv_sum - ((int64_t)c == y ? 1.f : 0.f);
         x[e] = g;
       }
       *reinterpret_cast<f32x4*>(row + 4 * v) = x;
@@ -596,6 +599,14 @@ struct AdamP {
   b4r_train_state* st;
 };
 
+// a * b + c with the product and the sum rounded separately, as TF evaluates the schedule: contracted to one FMA (the compiler's
+// default) the learning rate is one ulp off at some steps when end_lr != 0 (with end_lr = 0 both agree)
+__device__ __forceinline__ float mul_then_add(float a, float b, float c) {
+#pragma clang fp contract(off)
+  const float prod = a * b;
+  return prod + c;
+}
+
 // WarmUp over PolynomialDecay(power 1), float32 like TF: adam_w_optimizer.py:22-36
 __device__ __forceinline__ float lr_schedule(const b4r_adamw_config& hp, int64_t step) {
   const float s = (float)step;
@@ -603,7 +614,7 @@ __device__ __forceinline__ float lr_schedule(const b4r_adamw_config& hp, int64_t
   const float T = (float)hp.num_train_steps;
   const float gs = fminf(s, T);
   const float pr = gs / T;
-  return (hp.init_lr - hp.end_lr) * (1.0f - pr) + hp.end_lr;
+  return mul_then_add(hp.init_lr - hp.end_lr, 1.0f - pr, hp.end_lr);
 }
 
 __global__ __launch_bounds__(256) void adamw_kernel(AdamP a) {

@@ -199,6 +199,12 @@ int b4r_loss(const b4r_model_config* cfg, const b4r_batch* batch, void* workspac
 int b4r_backward(const b4r_model_config* cfg, const b4r_batch* batch, const float* params, float* grads,
                  void* workspace, int64_t workspace_bytes, b4r_train_state* state, int32_t flags,
                  b4r_stream_t stream);
+/* A gradient element that is not finite (b4r_optimizer_step, b4r_train_step, b4r_adamw_step alike): state->grad_sqnorm and
+ * state->grad_norm come out non-finite, and that element's parameter and moments become NaN -- the step is never a silently finite
+ * one with the bad element dropped.  The rest of the buffer: under an Inf the clip scale is clip_norm / Inf = 0, so every finite
+ * gradient counts as 0 (the moments decay, the parameters take the step of an all-zero gradient); under a NaN, fmaxf(NaN, clip_norm)
+ * = clip_norm makes the scale 1 and the finite elements take the UNCLIPPED step of their own gradients (tf.clip_by_global_norm
+ * would turn all of them into NaN).  Watch state->grad_norm. */
 int b4r_optimizer_step(const b4r_model_config* cfg, const b4r_adamw_config* hp, float* params, const float* grads,
                        float* adam_m, float* adam_v, void* workspace, int64_t workspace_bytes,
                        b4r_train_state* state, b4r_stream_t stream);
