@@ -12,7 +12,10 @@ every user in one sweep over the vocabulary, no [users, V] scores, the seen item
 
 allowed_items / allowed_items_per_user restrict the catalogue (items in stock, one category, one allow-list per market): the lists
 become packed item filters that the same sweep applies (b4r_rank_full_ex).  similar_items returns the nearest neighbours of items in
-the learned item table (b4r_item_neighbours)."""
+the learned item table (b4r_item_neighbours).
+
+diversity (0 = the plain top k, the default; up to 1) trades relevance against similarity among the returned items: the sweep returns
+candidate_pool candidates per user and b4r_rerank_diverse picks k of them by greedy Maximal Marginal Relevance, cosine in the item table."""
 import numpy as np
 import torch
 
@@ -48,10 +51,11 @@ class Recommender:
             mask[torch.as_tensor(tokens, dtype=torch.int64)] = True
         return mask
 
-    def __call__(self, sequence: list, k: int = 1, allowed_items=None):
-        """allowed_items: an iterable of items; only those are recommended (the filtered call goes through recommend_batch)."""
-        if allowed_items is not None:
-            return self.recommend_batch([sequence], k, allowed_items=allowed_items)[0]
+    def __call__(self, sequence: list, k: int = 1, allowed_items=None, diversity=None, candidate_pool=None):
+        """allowed_items: an iterable of items; only those are recommended.  diversity / candidate_pool: as in recommend_batch.
+        A call with any of them goes through recommend_batch."""
+        if allowed_items is not None or diversity is not None or candidate_pool is not None:
+            return self.recommend_batch([sequence], k, allowed_items=allowed_items, diversity=diversity, candidate_pool=candidate_pool)[0]
         tokenizer = self.dataloader.get_tokenizer()
         batch = self.dataloader.prepare_inference(list(sequence))
         batch = {key: torch.from_numpy(np.asarray(v)) for key, v in batch.items()}
@@ -63,11 +67,14 @@ class Recommender:
         items = tokenizer.detokenize(top)
         return items[0] if k == 1 else items
 
-    def recommend_batch(self, sequences, k: int = 1, allowed_items=None, allowed_items_per_user=None) -> list:
+    def recommend_batch(self, sequences, k: int = 1, allowed_items=None, allowed_items_per_user=None, diversity=None,
+                        candidate_pool=None) -> list:
         """Recommender(...)(seq, k) for every sequence of `sequences`, from one batched forward and one full-catalogue top-k.
         allowed_items: one iterable of items (detokenized values) for all users; allowed_items_per_user: one iterable per sequence
         (identical lists share one filter).  Only allowed items are recommended; items the vocabulary does not know are ignored.
-        With k = 1 a user for whom nothing is left to recommend gets None, with or without a filter (every item seen or excluded)."""
+        With k = 1 a user for whom nothing is left to recommend gets None, with or without a filter (every item seen or excluded).
+        diversity: None or 0 = the k best items, as before; a number up to 1 = the k items are picked from the candidate_pool best
+        (default min(1024, max(10 k, 50))) by greedy Maximal Marginal Relevance, so that they are less alike (recommend_tensor)."""
         tokenizer = self.dataloader.get_tokenizer()
         sequences = [list(seq) for seq in sequences]
         if allowed_items is not None and allowed_items_per_user is not None:
@@ -100,7 +107,8 @@ class Recommender:
             # one filter index per ranked slot: the slots of recommend_tensor are those with masked_lm_weights != 0, in batch order
             w = batch["masked_lm_weights"] != 0
             row_filter = torch.as_tensor(user_filter, dtype=torch.int32)[torch.nonzero(w, as_tuple=True)[0]]
-        ids, _, slots = self.model.recommend_tensor(batch, k=k, exclude_seen=False, exclude=exclude, allow=allow, row_filter=row_filter)
+        ids, _, slots = self.model.recommend_tensor(batch, k=k, exclude_seen=False, exclude=exclude, allow=allow, row_filter=row_filter,
+                                                    diversity=diversity, pool=candidate_pool)
         P = int(batch["masked_lm_positions"].shape[1])
         first = {}
         for i, s in enumerate(slots.cpu().tolist()):   # __call__ ranks the first weighted slot of its one-row batch

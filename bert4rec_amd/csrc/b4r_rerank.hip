@@ -1,0 +1,273 @@
+// Diversity-aware re-ranking of a candidate pool: greedy Maximal Marginal Relevance (MMR) with cosine similarity in the item table.
+//
+// Serves  BERT4RecModel.recommend_tensor(diversity=...)  (the pool is b4r_rank_full's top M of the row; the K returned items are
+//                                                          picked one by one, each the best trade of relevance against similarity
+//                                                          to the items already picked)
+//
+// Contract (include/b4r.h, b4r_rerank_diverse; restated on the CPU in tests/diverse_ref.py): relevance is the pool score mapped to
+// [0, 1]; sim(c, q) is b4r_item_neighbours' cosine with the picked item q as the query (k-ascending fp32 fma chain, no MFMA);
+// mmr = fl32(fl32(lambda rel) - fl32(fl32(1 - lambda) pen)) with three separate roundings; ties go to the lower pool position.
+//
+// One launch, one 256-thread workgroup per pool row; thread tid owns the pool entries tid, tid + 256, ... (NPT = 1, 2 or 4 of
+// them: the kernel is a template on NPT).  rel, pen and the open (live and unpicked) flags stay in registers for all K steps.
+// A step is two barriers:
+//   1. every thread forms mmr of its open entries and the key (open bit | ordered integer image of mmr | M - 1 - p), unique per
+//      entry; the waves reduce it by shuffles in a fixed order and leave one key each in LDS                          -- barrier --
+//   2. every thread reads the four wave keys (LDS broadcasts): the largest names the winner p.  Its owner writes the step's outputs;
+//      all threads write qhat = table[q] * rnorm[q] of the winner's item q to LDS                                       -- barrier --
+//   3. every thread walks the table rows of its open entries with 16-byte loads in ascending k against qhat (LDS broadcast reads,
+//      one per four fmas and shared by the thread's NPT chains) and raises pen; an entry that is dead or already picked is skipped.
+//      A pool row's M table rows are M * width * 4 bytes: at most 1 MB up to width 256, which stays in L2 over the K steps; a wider
+//      table (the entry takes widths up to 4096: 16 MB at M = 1024) is streamed again from beyond L2 in each of the K steps.
+// The loop carries chains, not tiles: nothing is staged but qhat.  No atomics; bitwise reproducible.
+#include "b4r_common.h"
+
+namespace {
+
+constexpr int DT = 256;           // threads per workgroup
+constexpr int DM_MAX = 1024;      // largest pool
+constexpr int DW_MAX = 4096;      // largest table width
+constexpr int POS_BITS = 10;      // M - 1 - p < 1024
+static_assert(DM_MAX <= (1 << POS_BITS), "the pool position takes the low bits of the key");
+static_assert(DM_MAX <= 4 * DT, "at most 4 entries per thread");
+
+// order-preserving image of an fp32 value for an ascending unsigned compare; -0.0 counts as +0.0 (they compare equal): the image
+// b4r_rank_full orders its scores by
+__device__ __forceinline__ uint32_t ordered_bits(float s) {
+  uint32_t u = __builtin_bit_cast(uint32_t, s);
+  if (u == 0x80000000u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ordered_value(uint32_t k) {
+  return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+
+// fl32(fl32(la * rel) - fl32(lb * pen)): the products and the difference are rounded separately (contracted to an FMA, the
+// compiler's default, the value is an ulp off and two entries that tie by the contract no longer do)
+__device__ __forceinline__ float mmr_value(float la, float rel, float lb, float pen) {
+#pragma clang fp contract(off)
+  const float x = la * rel;
+  const float y = lb * pen;
+  return x - y;
+}
+__device__ __forceinline__ float one_minus(float la) {
+#pragma clang fp contract(off)
+  return 1.0f - la;
+}
+
+__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o);
+    const uint64_t w = ((uint64_t)hi << 32) | lo;
+    v = w > v ? w : v;
+  }
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
+  return v;
+}
+
+struct RerankArgs {
+  const float* table; const float* rnorm;
+  const int64_t* pool_ids; const float* pool_scores;
+  int64_t* out_ids; float* out_scores; float* out_mmr;
+  float lambda;
+  int width, V, M, K;
+};
+
+template <int NPT>
+__global__ __launch_bounds__(DT) void rerank_diverse_kernel(RerankArgs a) {
+  __shared__ __attribute__((aligned(16))) float qhat[DW_MAX];
+  __shared__ int32_t s_id[DM_MAX];          // the item of every pool entry, -1: not live
+  __shared__ uint64_t s_wkey[DT / 64];
+  __shared__ uint32_t s_wmin[DT / 64], s_wmax[DT / 64];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int M = a.M, K = a.K, width = a.width;
+  const int64_t r = blockIdx.x;
+  const int64_t* ids = a.pool_ids + r * M;
+  const float* scores = a.pool_scores + r * M;
+
+  // ---- the thread's entries: live = id in [0, V) and a finite score ---------------------------------------------------------
+  int32_t id[NPT];
+  float rel[NPT], pen[NPT], mmr[NPT], rn[NPT];
+  bool open[NPT];
+  const float* row[NPT];
+  uint32_t kmin = 0xFFFFFFFFu, kmax = 0u;
+#pragma unroll
+  for (int i = 0; i < NPT; ++i) {
+    const int p = i * DT + tid;
+    id[i] = -1;
+    float s = 0.f;
+    if (p < M) {
+      const int64_t j = ids[p];
+      s = scores[p];
+      const bool finite = (__builtin_bit_cast(uint32_t, s) & 0x7F800000u) != 0x7F800000u;
+      if (j >= 0 && j < a.V && finite) id[i] = (int32_t)j;
+      s_id[p] = id[i];
+    }
+    open[i] = id[i] >= 0;
+    if (open[i]) {
+      const uint32_t k = ordered_bits(s);
+      kmin = min(kmin, k); kmax = max(kmax, k);
+    }
+    rel[i] = s;   // the score, until s_min and s_max are known
+    pen[i] = 0.f;
+    mmr[i] = 0.f;
+    row[i] = a.table + (int64_t)(open[i] ? id[i] : 0) * width;   // (not live: never read)
+    rn[i] = open[i] ? a.rnorm[id[i]] : 0.f;
+  }
+  kmin = wave_min_u32(kmin); kmax = wave_max_u32(kmax);
+  if (lane == 0) { s_wmin[wave] = kmin; s_wmax[wave] = kmax; }
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < DT / 64; ++w) { kmin = min(kmin, s_wmin[w]); kmax = max(kmax, s_wmax[w]); }
+  {
+    // rel = (s - s_min) / (s_max - s_min), 1 when all live scores are equal (no live entry: nothing is open, rel is not read)
+    const float smin = ordered_value(kmin), smax = ordered_value(kmax);
+    const float span = smax - smin;
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) rel[i] = smax == smin ? 1.0f : (rel[i] - smin) / span;
+  }
+
+  const float la = a.lambda, lb = one_minus(la);
+  int filled = 0;
+  for (int t = 0; t < K; ++t) {
+    // ---- 1. the best open entry: largest mmr, then the lowest position ----------------------------------------------------
+    uint64_t best = 0;
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) {
+      mmr[i] = mmr_value(la, rel[i], lb, pen[i]);
+      const int p = i * DT + tid;
+      const uint64_t key = (1ull << (32 + POS_BITS)) | ((uint64_t)ordered_bits(mmr[i]) << POS_BITS) | (uint64_t)(M - 1 - p);
+      if (open[i] && key > best) best = key;
+    }
+    best = wave_max_u64(best);
+    if (lane == 0) s_wkey[wave] = best;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < DT / 64; ++w) best = s_wkey[w] > best ? s_wkey[w] : best;
+    if (best == 0) break;   // no open entry is left (the same for every thread)
+    const int p = M - 1 - (int)(best & ((1u << POS_BITS) - 1u));   // in [0, M): the key of an open entry
+    const int q = s_id[p];                                         // in [0, V): the entry is live
+    if (tid == (p & (DT - 1))) {
+      const int turn = p / DT;
+      float m = mmr[0];
+#pragma unroll
+      for (int i = 0; i < NPT; ++i) {
+        if (i == turn) { m = mmr[i]; open[i] = false; }
+      }
+      const int64_t o = r * K + t;
+      if (a.out_ids) a.out_ids[o] = q;
+      if (a.out_scores) a.out_scores[o] = scores[p];
+      if (a.out_mmr) a.out_mmr[o] = m;
+    }
+    filled = t + 1;
+    if (filled == K) break;
+
+    // ---- 2. the picked item as the cosine query -----------------------------------------------------------------------------
+    {
+      const float rq = a.rnorm[q];
+      const float* e = a.table + (int64_t)q * width;
+      for (int k = tid; k < width; k += DT) qhat[k] = e[k] * rq;
+    }
+    __syncthreads();
+
+    // ---- 3. pen = max over the picked q of sim(c, q) = fl32((chain_k(qhat[k] * table[c][k]) + 0.0f) * rnorm[c]) -----------------
+    // (pen of an entry that is dead or picked is never read again: only open entries walk their row)
+    bool any_open = false;
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) any_open |= open[i];
+    if (any_open) {
+      float acc[NPT];
+#pragma unroll
+      for (int i = 0; i < NPT; ++i) acc[i] = 0.f;
+#pragma unroll 4
+      for (int k = 0; k < width; k += 4) {
+        const f32x4 h = *reinterpret_cast<const f32x4*>(qhat + k);
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) {
+          if (!open[i]) continue;
+          const f32x4 e = *reinterpret_cast<const f32x4*>(row[i] + k);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) acc[i] = __builtin_fmaf(h[u], e[u], acc[i]);   // k-ordered fp32 fma chain (the contract)
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < NPT; ++i) {
+        const float sim = (acc[i] + 0.0f) * rn[i];
+        pen[i] = (t == 0 || sim > pen[i]) ? sim : pen[i];   // the earlier value stays on equality
+      }
+    }
+  }
+  for (int t = filled + tid; t < K; t += DT) {
+    const int64_t o = r * K + t;
+    if (a.out_ids) a.out_ids[o] = -1;
+    if (a.out_scores) a.out_scores[o] = -INFINITY;
+    if (a.out_mmr) a.out_mmr[o] = -INFINITY;
+  }
+}
+
+// 1 / |row| of every table row: b4r_item_neighbours' item_rnorm_kernel (b4r_rank_full.hip), statement for statement, so that both
+// give the same bits.  It is restated here, not shared: b4r_rank_full.hip is left as it is ("Instances").
+__global__ __launch_bounds__(DT) void rerank_rnorm_kernel(const float* __restrict__ table, int H, int V, float* __restrict__ rnorm) {
+  const int64_t j = (int64_t)blockIdx.x * DT + threadIdx.x;
+  if (j >= V) return;
+  const float* e = table + j * H;
+  float ss = 0.f;
+  for (int k = 0; k < H; k += 4) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(e + k);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) ss = __builtin_fmaf(v[u], v[u], ss);
+  }
+  rnorm[j] = 1.0f / sqrtf(fmaxf(ss, 1e-24f));
+}
+
+int64_t align16(int64_t b) { return (b + 15) & ~(int64_t)15; }
+
+}  // namespace
+
+extern "C" int64_t b4r_rerank_diverse_scratch_bytes(int32_t R, int32_t M, int32_t V) {
+  if (R <= 0 || M <= 0 || M > DM_MAX || V <= 0) return 0;
+  return align16((int64_t)V * 4) + 16;   // rnorm [V] + room for its 16-byte alignment
+}
+
+extern "C" int b4r_rerank_diverse(const float* table, int32_t ld, int32_t width, int32_t V, const float* item_rnorm,
+                                  const int64_t* pool_ids, const float* pool_scores, int32_t R, int32_t M, float lambda, int32_t K,
+                                  int64_t* out_ids, float* out_scores, float* out_mmr, void* scratch, int64_t scratch_bytes,
+                                  b4r_stream_t stream) {
+  const char* what = "b4r_rerank_diverse";
+  B4R_CHECK_ARG(R >= 0 && M >= 1 && M <= DM_MAX && K >= 0 && K <= M, B4R_E_SHAPE, "%s: bad shape (R = %d, M = %d in [1, %d], K = %d in [0, M])",
+                what, R, M, DM_MAX, K);
+  B4R_CHECK_ARG(width > 0 && width % 4 == 0 && width <= DW_MAX && ld == width && V > 0, B4R_E_SHAPE,
+                "%s: bad shape (width = %d: a multiple of 4 up to %d, ld = %d: must equal width, V = %d)", what, width, DW_MAX, ld, V);
+  B4R_CHECK_ARG(lambda >= 0.0f && lambda <= 1.0f, B4R_E_BADARG, "%s: lambda = %g does not lie in [0, 1]", what, (double)lambda);
+  if (R == 0 || K == 0) return B4R_OK;
+  B4R_CHECK_ARG(table && pool_ids && pool_scores, B4R_E_BADARG, "%s: null argument", what);
+  B4R_CHECK_ARG(b4r_aligned16(table), B4R_E_ALIGN, "%s: the table must be 16-byte aligned", what);
+  hipStream_t s = (hipStream_t)stream;
+  const float* rnorm = item_rnorm;
+  if (!rnorm) {
+    const int64_t pad = scratch ? (int64_t)((16 - ((uintptr_t)scratch & 15)) & 15) : 0;
+    B4R_CHECK_ARG(scratch && scratch_bytes - pad >= (int64_t)V * 4, B4R_E_NOMEM,
+                  "%s: scratch of %lld bytes is too small for rnorm [%d] (b4r_rerank_diverse_scratch_bytes)", what,
+                  (long long)scratch_bytes, V);
+    float* rn = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + pad);
+    hipLaunchKernelGGL(rerank_rnorm_kernel, dim3(b4r_cdiv(V, DT)), dim3(DT), 0, s, table, width, V, rn);
+    rnorm = rn;
+  }
+  RerankArgs a{table, rnorm, pool_ids, pool_scores, out_ids, out_scores, out_mmr, lambda, width, V, M, K};
+  if (M <= DT) hipLaunchKernelGGL(rerank_diverse_kernel<1>, dim3(R), dim3(DT), 0, s, a);
+  else if (M <= 2 * DT) hipLaunchKernelGGL(rerank_diverse_kernel<2>, dim3(R), dim3(DT), 0, s, a);
+  else hipLaunchKernelGGL(rerank_diverse_kernel<4>, dim3(R), dim3(DT), 0, s, a);
+  B4R_CHECK_LAUNCH(what);
+  return B4R_OK;
+}

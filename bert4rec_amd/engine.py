@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import numbers
 import operator
 from typing import Dict, Iterable, List, Optional, Tuple
 
@@ -219,6 +220,27 @@ def check_similar_items_args(k, metric) -> Tuple[int, int]:
     if metric not in SIMILARITY_METRICS:
         raise ValueError(f"metric must be one of {sorted(SIMILARITY_METRICS)}, got {metric!r}")
     return k, SIMILARITY_METRICS[metric]
+
+
+def check_rerank_args(k, pool, diversity) -> Tuple[int, int, float]:
+    """Argument checks of the diversity-aware re-ranking that need no GPU.  Returns (k, pool, lambda): k in [0, 1024]; pool (the
+    candidates re-ranked per row) None = min(1024, max(10 k, 50)), else an integer in [max(k, 1), 1024]; diversity a number in
+    [0, 1], lambda = 1 - diversity rounded to fp32 (b4r_rerank_diverse's weight of the relevance)."""
+    k = check_rank_full_args(k)
+    if pool is None:
+        pool = min(RANK_FULL_MAX_K, max(10 * k, 50))
+    else:
+        try:
+            pool = operator.index(pool)
+        except TypeError:
+            raise ValueError(f"pool must be an integer, got {pool!r}") from None
+        if pool < 1 or pool > RANK_FULL_MAX_K:
+            raise ValueError(f"pool must lie in [1, {RANK_FULL_MAX_K}], got {pool}")
+        if k > pool:
+            raise ValueError(f"k = {k} items cannot be picked from a pool of {pool}")
+    if isinstance(diversity, bool) or not isinstance(diversity, numbers.Real) or not 0.0 <= diversity <= 1.0:   # (NaN fails the range)
+        raise ValueError(f"diversity must be a number in [0, 1], got {diversity!r}")
+    return k, pool, C.c_float(1.0 - float(diversity)).value
 
 
 class Engine:
@@ -744,6 +766,39 @@ class Engine:
                                                 _ptr(ids), _ptr(scores), _ptr(sc), sc.numel(), _stream(self.device)),
                    "b4r_item_neighbours")
         return ids, scores
+
+    def rerank_diverse(self, pool_ids: torch.Tensor, pool_scores: torch.Tensor, k: int, diversity: float, rnorm: Optional[torch.Tensor] = None):
+        """b4r_rerank_diverse on the item table [V, E]: greedy Maximal Marginal Relevance over the candidates pool_ids / pool_scores
+        [R, M] (rank_full's output: best first, -1 / -inf where a row has fewer), cosine similarity in the item table, lambda =
+        1 - diversity.  Returns (ids [R,k] int64, scores [R,k] fp32: the pool scores of the picked items, mmr [R,k] fp32), -1 / -inf
+        where a row has fewer than k live candidates.  rnorm [V] fp32: 1 / |row| of the table (None: computed by the call, as
+        item_neighbours computes it).  The scratch buffer is kept between calls."""
+        if pool_ids.ndim != 2 or pool_ids.dtype != torch.int64 or pool_scores.dtype != torch.float32 or pool_scores.shape != pool_ids.shape:
+            raise ValueError(f"the pool is ids int64 [R, M] and scores float32 [R, M], got {pool_ids.dtype} {tuple(pool_ids.shape)} and "
+                             f"{pool_scores.dtype} {tuple(pool_scores.shape)}")
+        R, M = (int(x) for x in pool_ids.shape)
+        k, _, lam = check_rerank_args(k, M, diversity)
+        V, Ew = self.cfg.vocab_size, self.embedding_width
+        if rnorm is not None and (rnorm.dtype != torch.float32 or tuple(rnorm.shape) != (V,)):
+            raise ValueError(f"rnorm must be float32 [{V}], got {rnorm.dtype} {tuple(rnorm.shape)}")
+        ids_d, sc_d = pool_ids.to(self.device).contiguous(), pool_scores.to(self.device).contiguous()
+        rn_d = None if rnorm is None else rnorm.to(self.device).contiguous()
+        ids = torch.empty((R, k), dtype=torch.int64, device=self.device)
+        scores = torch.empty((R, k), dtype=torch.float32, device=self.device)
+        mmr = torch.empty((R, k), dtype=torch.float32, device=self.device)
+        if R == 0 or k == 0:
+            return ids, scores, mmr
+        sc = None
+        if rn_d is None:
+            want = int(self.lib.b4r_rerank_diverse_scratch_bytes(R, M, V))
+            sc = getattr(self, "_rerank_scratch", None)
+            if sc is None or sc.numel() < want:
+                sc = self._rerank_scratch = torch.empty(want, dtype=torch.uint8, device=self.device)
+        table = self.view("word_embeddings/embeddings")
+        _lib.check(self.lib.b4r_rerank_diverse(_ptr(table), table.stride(0), Ew, V, _ptr(rn_d), _ptr(ids_d), _ptr(sc_d), R, M, lam, k,
+                                               _ptr(ids), _ptr(scores), _ptr(mmr), _ptr(sc), 0 if sc is None else sc.numel(),
+                                               _stream(self.device)), "b4r_rerank_diverse")
+        return ids, scores, mmr
 
     def rank_metrics(self, gt_rank: torch.Tensor, families, cutoffs, gain_sums: torch.Tensor, users: torch.Tensor) -> None:
         """b4r_rank_metrics: add this batch's gain sums to the device accumulators (float64 [n], int64 [1])."""

@@ -323,7 +323,8 @@ class BERT4RecModel:
         return out
 
     def recommend_tensor(self, encoder_input: Dict[str, torch.Tensor], k: int = 10, exclude_seen: bool = True,
-                         exclude: Optional[torch.Tensor] = None, allow=None, row_filter=None):
+                         exclude: Optional[torch.Tensor] = None, allow=None, row_filter=None, diversity: Optional[float] = None,
+                         pool: Optional[int] = None):
         """Top k of the whole catalogue for every slot with masked_lm_weights == 1 (all slots when the key is absent), from one
         b4r_rank_full call: no [R, V] scores.  The forward is rank_items_tensor's (encoder, then tfm MaskedLM's transform on those
         slots only).  [PAD] / [MASK] / [UNK] are never recommended; exclude_seen drops the row's own input_word_ids; exclude
@@ -331,8 +332,17 @@ class BERT4RecModel:
         slot_index [R] int64 = b*P+p), on the device; a row with fewer than k allowed items ends in -1 / -inf.
         allow: restrict the catalogue -- a bool / uint8 mask [V] (nonzero = may be recommended), masks [F, V] with row_filter [R]
         (the filter of each ranked row; an index outside [0, F) = no filter), or packed uint32 [F, ceil(V / 32)]
-        (bert4rec_amd.apps.pack_item_filter).  The filter is applied inside the sweep (b4r_rank_full_ex)."""
+        (bert4rec_amd.apps.pack_item_filter).  The filter is applied inside the sweep (b4r_rank_full_ex).
+        diversity: None = the plain top k.  A number d in [0, 1]: the sweep returns the best `pool` allowed items of every row
+        (default min(1024, max(10 k, 50)); at least k) and b4r_rerank_diverse picks k of them by greedy Maximal Marginal Relevance
+        with lambda = 1 - d and cosine similarity in the item table: 0 keeps the plain order, 1 ranks by dissimilarity to the items
+        already picked alone.  The scores returned are the picked items' sweep scores (no longer descending)."""
         k = engine_mod.check_rank_full_args(k, exclude)
+        n_sweep = k
+        if diversity is not None:
+            k, n_sweep, _ = engine_mod.check_rerank_args(k, pool, diversity)
+        elif pool is not None:
+            raise ValueError("pool is the candidate count of the diversity-aware re-ranking: give diversity as well")
         allow, row_filter = engine_mod.check_item_filter(allow, row_filter, self.vocab_size)
         hidden, slots, _ = self._ranked_slot_hidden(encoder_input)
         dev = self.device
@@ -350,7 +360,9 @@ class BERT4RecModel:
                 raise ValueError(f"exclude has {ex.shape[0]} rows for a batch of {B}")
             parts.append(ex[b_idx])
         ex_rows = torch.cat(parts, dim=1) if parts else None
-        ids, scores, _ = self.engine.rank_full(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, k, allow, row_filter)
+        ids, scores, _ = self.engine.rank_full(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, n_sweep, allow, row_filter)
+        if diversity is not None:
+            ids, scores, _ = self.engine.rerank_diverse(ids, scores, k, diversity)
         return ids, scores, slots
 
     def similar_items_tensor(self, item_ids, k: int = 10, metric: str = "cosine", allow=None, row_filter=None):
@@ -360,9 +372,10 @@ class BERT4RecModel:
         id that is no item gives a row of -1 / -inf.  One b4r_item_neighbours call: no [R, V] scores."""
         return self.engine.item_neighbours(item_ids, k, metric, engine_mod.SPECIAL_IDS, allow, row_filter)
 
-    def recommend(self, encoder_input: dict, k: int = 10, exclude_seen: bool = True, exclude=None):
+    def recommend(self, encoder_input: dict, k: int = 10, exclude_seen: bool = True, exclude=None, diversity: Optional[float] = None,
+                  pool: Optional[int] = None):
         """recommend_tensor as Python lists: per batch row, one list per ranked slot of (ids, scores) lists of length k."""
-        ids, scores, slots = self.recommend_tensor(encoder_input, k, exclude_seen, exclude)
+        ids, scores, slots = self.recommend_tensor(encoder_input, k, exclude_seen, exclude, diversity=diversity, pool=pool)
         B, P = (int(x) for x in torch.as_tensor(encoder_input["masked_lm_positions"]).shape)
         out = [[] for _ in range(B)]
         for s, i_row, s_row in zip(slots.cpu().tolist(), ids.cpu().tolist(), scores.cpu().tolist()):

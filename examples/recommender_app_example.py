@@ -1,7 +1,8 @@
 """Recommend the next item for a history (the reference's examples/recommender_app_example.py): load a saved model (run
-bert4rec_ml_1m_example.py or bert4rec_lifecycle_example.py first), then ask the app."""
+bert4rec_ml_1m_example.py or bert4rec_lifecycle_example.py first), then ask the app.
+--diversity D (0 .. 1) also prints a top 5 re-ranked for diversity (greedy Maximal Marginal Relevance over the 50 best candidates)."""
+import argparse
 import pathlib
-import sys
 
 from _common import dataloaders, datasets, models
 
@@ -9,7 +10,11 @@ from bert4rec_amd.apps import Recommender
 from bert4rec_amd.models import model_utils
 
 if __name__ == "__main__":
-    path = model_utils.determine_model_path(pathlib.Path(sys.argv[1] if len(sys.argv) > 1 else "bert4rec_ml-1m_lifecycle"))
+    parser = argparse.ArgumentParser(description=__doc__)
+    parser.add_argument("model", nargs="?", default="bert4rec_ml-1m_lifecycle")
+    parser.add_argument("--diversity", type=float, default=None, help="0 = the plain top k ... 1 = dissimilarity alone")
+    args = parser.parse_args()
+    path = model_utils.determine_model_path(pathlib.Path(args.model))
     loaded = models.BERT4RecModelWrapper.load(path)
     kwargs = {"tokenizer": loaded["tokenizer"]} if "tokenizer" in loaded else {}
     if not datasets.ML1M.is_available():
@@ -20,3 +25,5 @@ if __name__ == "__main__":
     history = dataloader.get_tokenizer().detokenize([7, 19, 4, 33, 12])
     print("history:", history)
     print("next item:", app(history), " top 5:", app(history, k=5))
+    if args.diversity is not None:
+        print("top 5 at diversity %g:" % args.diversity, app(history, k=5, diversity=args.diversity))

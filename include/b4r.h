@@ -327,6 +327,32 @@ int64_t b4r_item_neighbours_scratch_bytes(int32_t R, int32_t V, int32_t K, int32
 int b4r_item_neighbours(const float* table, int32_t ld, int32_t width, int32_t V, int32_t first_item, const int64_t* query_ids,
                         int32_t R, int32_t metric, const uint32_t* allow_bits, int32_t n_filters, const int32_t* row_filter, int32_t K,
                         int64_t* topk_ids, float* topk_scores, void* scratch, int64_t scratch_bytes, b4r_stream_t stream);
+/* Diversity-aware re-ranking of a candidate pool: greedy Maximal Marginal Relevance (MMR) over pool_ids / pool_scores [R, M] (as
+ * b4r_rank_full writes its top M), similarity = cosine in table [V, width].  Row r, entries p = 0 .. M-1:
+ *   live        pool_ids[r][p] in [0, V) and pool_scores[r][p] finite; other entries (the -1 / -inf tail) are never picked.  Live
+ *               scores are expected in descending order but nothing relies on it; a repeated id is one entry per occurrence.
+ *   rel_p       = fl32(fl32(s_p - s_min) / fl32(s_max - s_min)), s_max / s_min the largest / smallest live score of the row (a
+ *               -0.0 counts as +0.0 there), correctly rounded fp32 division; 1.0f when s_max == s_min.
+ *   sim(c, q)   b4r_item_neighbours' cosine with the picked item q as the query: qhat[k] = fl32(table[q][k] * rnorm[q]),
+ *               sim = fl32((fma-chain_k(qhat[k] * table[c][k]) + 0.0f) * rnorm[c])  (k ascending, fp32, no MFMA).  Not symmetric
+ *               in bits: the picked item is always the query.
+ *   rnorm       item_rnorm [V], or NULL: computed into scratch exactly as b4r_item_neighbours(B4R_SIM_COSINE) computes it.
+ *   pen_c       the maximum of sim(c, q) over the items q picked so far, taken pick by pick (pen = sim where sim > pen: the
+ *               earlier value stays on equality); 0.0f before the first pick, sim(c, q_0) after it.
+ *   mmr_c       = fl32(fl32(lambda * rel_c) - fl32(fl32(1 - lambda) * pen_c)): three separate roundings, no FMA.
+ *   step t = 0 .. K-1 picks the live, unpicked entry with the largest mmr (-0.0 equals +0.0), ties to the lower p, and writes
+ *               out_ids[r][t] = its id, out_scores[r][t] = its pool score, out_mmr[r][t] = its mmr; when no live entry is left
+ *               the remaining outputs are -1 / -inf / -inf.  Any output may be NULL.
+ * lambda in [0, 1] (else B4R_E_BADARG): 1 keeps the pool's order, 0 ranks by dissimilarity alone.  1 <= M <= 1024, 0 <= K <= M,
+ * width a multiple of 4 up to 4096, ld == width (else B4R_E_SHAPE).  R = 0 or K = 0 succeeds and launches nothing.
+ * scratch: b4r_rerank_diverse_scratch_bytes(R, M, V) bytes when item_rnorm is NULL (less: B4R_E_NOMEM; its first V floats, rounded
+ * up to 16 bytes, then hold rnorm); not read when item_rnorm is given.  Non-finite table values are outside the contract (they
+ * are never read out of bounds).  Only enqueues (one launch, two without item_rnorm; one stream, no host sync, graph-capturable);
+ * no atomics, bitwise reproducible. */
+int64_t b4r_rerank_diverse_scratch_bytes(int32_t R, int32_t M, int32_t V);
+int b4r_rerank_diverse(const float* table, int32_t ld, int32_t width, int32_t V, const float* item_rnorm, const int64_t* pool_ids,
+                       const float* pool_scores, int32_t R, int32_t M, float lambda, int32_t K, int64_t* out_ids, float* out_scores,
+                       float* out_mmr, void* scratch, int64_t scratch_bytes, b4r_stream_t stream);
 /* replaces the metric loop of bert4rec_evaluator.py:118-120 over evaluation_metrics.py:47-112 for a batch of ranks:
  * gain_sums[m] += sum over gt_rank[i] > 0 of gain_m(gt_rank[i]), users[0] += #{gt_rank[i] > 0}; double / int64 DEVICE
  * accumulators the caller reads once per evaluate().  family[m]: 0 count (gain 1), 1 hit@cutoff (rank <= k), 2 NDCG@cutoff
