@@ -15,9 +15,13 @@ become packed item filters that the same sweep applies (b4r_rank_full_ex).  simi
 the learned item table (b4r_item_neighbours).
 
 diversity (0 = the plain top k, the default; up to 1) trades relevance against similarity among the returned items: the sweep returns
-candidate_pool candidates per user and b4r_rerank_diverse picks k of them by greedy Maximal Marginal Relevance, cosine in the item table."""
+candidate_pool candidates per user and b4r_rerank_diverse picks k of them by greedy Maximal Marginal Relevance, cosine in the item table.
+
+list_quality measures what such lists are like beyond accuracy (b4r_list_metrics): intra-list diversity, catalogue coverage, novelty."""
 import numpy as np
 import torch
+
+from ..engine import SPECIAL_IDS, item_self_information
 
 
 class Recommender:
@@ -135,3 +139,50 @@ class Recommender:
         allow = None if allowed_items is None else self._item_mask(allowed_items)
         ids, _ = self.model.similar_items_tensor(torch.as_tensor(query, dtype=torch.int64), k=k, metric=metric, allow=allow)
         return [tokenizer.detokenize([i for i in row if i >= 0]) for row in ids.cpu().tolist()]
+
+    def list_quality(self, lists, item_counts=None) -> dict:
+        """What recommendation lists are like beyond accuracy.  lists: an iterable of item lists (detokenized values, as __call__ and
+        recommend_batch return them with k > 1; items the vocabulary does not know are ignored; at most 1024 items each).
+        item_counts: how often each item was interacted with -- a mapping item -> count, or one count per token id [V].  Returns floats:
+          ild       intra-list diversity: the mean over the lists with at least 2 items of the mean 1 - cosine (in the item table)
+                    over the list's item pairs; 0.0 when no list has 2 items
+          coverage  the distinct items in the lists over the catalogue size V - 3 (the vocabulary without [PAD] / [MASK] / [UNK])
+          novelty   (with item_counts) the mean over the non-empty lists of the mean self-information -log2(count / all counts) of the
+                    list's items
+        One b4r_list_metrics call on the device; the sums are read back once."""
+        V = self.model.vocab_size
+        tokens = [self._known_tokens(list(lst)) for lst in lists]
+        out = {"ild": 0.0, "coverage": 0.0}
+        weight = None
+        if item_counts is not None:
+            if hasattr(item_counts, "items"):
+                counts = np.zeros(V, dtype=np.float64)
+                for item, c in item_counts.items():
+                    for t in self._known_tokens([item]):
+                        counts[t] += float(c)
+            else:
+                counts = np.asarray(item_counts, dtype=np.float64).reshape(-1)
+                if counts.shape[0] != V:
+                    raise ValueError(f"item_counts holds {counts.shape[0]} counts for a vocabulary of {V}")
+            weight = torch.from_numpy(item_self_information(counts))
+            out["novelty"] = 0.0
+        width = max((len(t) for t in tokens), default=0)
+        if width == 0:
+            return out
+        ids = torch.full((len(tokens), width), -1, dtype=torch.int64)
+        for i, t in enumerate(tokens):
+            if t:
+                ids[i, :len(t)] = torch.as_tensor(t, dtype=torch.int64)
+        engine = self.model.engine
+        dev = engine.params.device
+        exposure = torch.zeros(V, dtype=torch.int64, device=dev)
+        sums = torch.zeros(2, dtype=torch.float64, device=dev)
+        counts_d = torch.zeros(2, dtype=torch.int64, device=dev)
+        engine.list_metrics(ids, None, weight, exposure=exposure, sums=sums, counts=counts_d)
+        back = torch.cat([sums, counts_d.to(torch.float64), (exposure[SPECIAL_IDS:] > 0).sum().to(torch.float64).reshape(1)]).cpu().tolist()
+        if back[2] > 0:
+            out["ild"] = back[0] / back[2]
+        if weight is not None and back[3] > 0:
+            out["novelty"] = back[1] / back[3]
+        out["coverage"] = back[4] / max(V - SPECIAL_IDS, 1)
+        return out

@@ -21,6 +21,7 @@
 //      table (the entry takes widths up to 4096: 16 MB at M = 1024) is streamed again from beyond L2 in each of the K steps.
 // The loop carries chains, not tiles: nothing is staged but qhat.  No atomics; bitwise reproducible.
 #include "b4r_common.h"
+#include "b4r_cosine_chain.h"
 
 namespace {
 
@@ -174,11 +175,7 @@ __global__ __launch_bounds__(DT) void rerank_diverse_kernel(RerankArgs a) {
     if (filled == K) break;
 
     // ---- 2. the picked item as the cosine query -----------------------------------------------------------------------------
-    {
-      const float rq = a.rnorm[q];
-      const float* e = a.table + (int64_t)q * width;
-      for (int k = tid; k < width; k += DT) qhat[k] = e[k] * rq;
-    }
+    b4r_stage_qhat(qhat, a.table, a.rnorm, q, width, tid, DT);
     __syncthreads();
 
     // ---- 3. pen = max over the picked q of sim(c, q) = fl32((chain_k(qhat[k] * table[c][k]) + 0.0f) * rnorm[c]) -----------------
@@ -187,6 +184,8 @@ __global__ __launch_bounds__(DT) void rerank_diverse_kernel(RerankArgs a) {
 #pragma unroll
     for (int i = 0; i < NPT; ++i) any_open |= open[i];
     if (any_open) {
+      // b4r_cosine_chains<NPT> (b4r_cosine_chain.h), written out: called as a function the loop costs this kernel 4 more registers
+      // at 2 and 4 entries per thread and a wave of occupancy at 4
       float acc[NPT];
 #pragma unroll
       for (int i = 0; i < NPT; ++i) acc[i] = 0.f;
@@ -203,7 +202,7 @@ __global__ __launch_bounds__(DT) void rerank_diverse_kernel(RerankArgs a) {
       }
 #pragma unroll
       for (int i = 0; i < NPT; ++i) {
-        const float sim = (acc[i] + 0.0f) * rn[i];
+        const float sim = b4r_cosine_close(acc[i], rn[i]);
         pen[i] = (t == 0 || sim > pen[i]) ? sim : pen[i];   // the earlier value stays on equality
       }
     }
@@ -216,19 +215,12 @@ __global__ __launch_bounds__(DT) void rerank_diverse_kernel(RerankArgs a) {
   }
 }
 
-// 1 / |row| of every table row: b4r_item_neighbours' item_rnorm_kernel (b4r_rank_full.hip), statement for statement, so that both
-// give the same bits.  It is restated here, not shared: b4r_rank_full.hip is left as it is ("Instances").
+// 1 / |row| of every table row: b4r_item_neighbours' item_rnorm_kernel (b4r_rank_full.hip), statement for statement (b4r_cosine_chain.h),
+// so that both give the same bits.  b4r_rank_full.hip keeps its own copy: it is left as it is ("Instances").
 __global__ __launch_bounds__(DT) void rerank_rnorm_kernel(const float* __restrict__ table, int H, int V, float* __restrict__ rnorm) {
   const int64_t j = (int64_t)blockIdx.x * DT + threadIdx.x;
   if (j >= V) return;
-  const float* e = table + j * H;
-  float ss = 0.f;
-  for (int k = 0; k < H; k += 4) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(e + k);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) ss = __builtin_fmaf(v[u], v[u], ss);
-  }
-  rnorm[j] = 1.0f / sqrtf(fmaxf(ss, 1e-24f));
+  rnorm[j] = b4r_row_rnorm(table + j * H, H);
 }
 
 int64_t align16(int64_t b) { return (b + 15) & ~(int64_t)15; }

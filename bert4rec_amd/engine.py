@@ -12,6 +12,7 @@ import numbers
 import operator
 from typing import Dict, Iterable, List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib, activations
@@ -241,6 +242,14 @@ def check_rerank_args(k, pool, diversity) -> Tuple[int, int, float]:
     if isinstance(diversity, bool) or not isinstance(diversity, numbers.Real) or not 0.0 <= diversity <= 1.0:   # (NaN fails the range)
         raise ValueError(f"diversity must be a number in [0, 1], got {diversity!r}")
     return k, pool, C.c_float(1.0 - float(diversity)).value
+
+
+def item_self_information(counts) -> np.ndarray:
+    """The novelty weight of every item from its interaction count: -log2(max(c, 1) / sum(c)) (an item nobody interacted with
+    counts as seen once), computed in float64 and rounded to fp32.  counts [V]: one count per token id; returns float32 [V]."""
+    c = np.asarray(counts, dtype=np.float64).reshape(-1)
+    total = max(float(c.sum()), 1.0)
+    return (-np.log2(np.maximum(c, 1.0) / total)).astype(np.float32)
 
 
 class Engine:
@@ -799,6 +808,54 @@ class Engine:
                                                _ptr(ids), _ptr(scores), _ptr(mmr), _ptr(sc), 0 if sc is None else sc.numel(),
                                                _stream(self.device)), "b4r_rerank_diverse")
         return ids, scores, mmr
+
+    def list_metrics(self, list_ids: torch.Tensor, gt: Optional[torch.Tensor] = None, item_weight: Optional[torch.Tensor] = None,
+                     rnorm: Optional[torch.Tensor] = None, exposure: Optional[torch.Tensor] = None, sums: Optional[torch.Tensor] = None,
+                     counts: Optional[torch.Tensor] = None):
+        """b4r_list_metrics on the item table [V, E]: beyond-accuracy metrics of the lists list_ids [R, K] int64 (rank_full's or
+        rerank_diverse's ids; -1 and ids outside [0, V) are skipped).  gt [R] int64 or None; item_weight [V] fp32 or None (the items'
+        self-information, apps.item_self_information); rnorm [V] fp32 or None (computed by the call).  Returns the per-row device
+        tensors (n int32 [R]: live entries, dist int64 [R]: the pair distances 1 - cosine summed in units of 2^-30, nov int64 [R]: the
+        item weights summed in units of 2^-30, hit_pos int32 [R]: 1-based position of gt, 0 = absent).  exposure int64 [V], sums
+        float64 [2], counts int64 [2]: device accumulators the call adds to (include/b4r.h); the caller zeroes and reads them.  The
+        scratch buffer is kept between calls."""
+        if list_ids.ndim != 2 or list_ids.dtype != torch.int64:
+            raise ValueError(f"the lists are ids int64 [R, K], got {list_ids.dtype} {tuple(list_ids.shape)}")
+        R, K = (int(x) for x in list_ids.shape)
+        if K < 1 or K > RANK_FULL_MAX_K:
+            raise ValueError(f"the lists hold 1 to {RANK_FULL_MAX_K} ids, got {K}")
+        V, Ew = self.cfg.vocab_size, self.embedding_width
+        for name, t, dtype, shape in (("rnorm", rnorm, torch.float32, (V,)), ("item_weight", item_weight, torch.float32, (V,)),
+                                      ("gt", gt, torch.int64, (R,)), ("exposure", exposure, torch.int64, (V,)),
+                                      ("sums", sums, torch.float64, (2,)), ("counts", counts, torch.int64, (2,))):
+            if t is not None and (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape):
+                raise ValueError(f"{name} must be a {dtype} tensor of shape {list(shape)}, got "
+                                 f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}")
+        for name, t in (("exposure", exposure), ("sums", sums), ("counts", counts)):   # written in place: no copy may stand in for them
+            if t is not None and (t.device != self.params.device or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous tensor on {self.params.device}")
+        ids_d = list_ids.to(self.device).contiguous()
+        gt_d = None if gt is None else gt.to(self.device).contiguous()
+        w_d = None if item_weight is None else item_weight.to(self.device).contiguous()
+        rn_d = None if rnorm is None else rnorm.to(self.device).contiguous()
+        n = torch.empty((R,), dtype=torch.int32, device=self.device)
+        dist = torch.empty((R,), dtype=torch.int64, device=self.device)
+        nov = torch.empty((R,), dtype=torch.int64, device=self.device)
+        hit = torch.empty((R,), dtype=torch.int32, device=self.device)
+        if R == 0:
+            return n, dist, nov, hit
+        sc = None
+        if rn_d is None:
+            want = int(self.lib.b4r_list_metrics_scratch_bytes(R, K, V))
+            sc = getattr(self, "_list_metrics_scratch", None)
+            if sc is None or sc.numel() < want:
+                sc = self._list_metrics_scratch = torch.empty(want, dtype=torch.uint8, device=self.device)
+        table = self.view("word_embeddings/embeddings")
+        _lib.check(self.lib.b4r_list_metrics(_ptr(table), table.stride(0), Ew, V, SPECIAL_IDS, _ptr(rn_d), _ptr(ids_d), R, K, _ptr(gt_d),
+                                             _ptr(w_d), _ptr(n), _ptr(dist), _ptr(nov), _ptr(hit), _ptr(exposure), _ptr(sums),
+                                             _ptr(counts), _ptr(sc), 0 if sc is None else sc.numel(), _stream(self.device)),
+                   "b4r_list_metrics")
+        return n, dist, nov, hit
 
     def rank_metrics(self, gt_rank: torch.Tensor, families, cutoffs, gain_sums: torch.Tensor, users: torch.Tensor) -> None:
         """b4r_rank_metrics: add this batch's gain sums to the device accumulators (float64 [n], int64 [1])."""

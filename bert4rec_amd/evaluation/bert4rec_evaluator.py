@@ -14,16 +14,21 @@ when the model runs on a GPU): same distribution as the reference's per-slot np.
 full_ranking=True replaces the sampled protocol by full-catalogue ranking (the protocol of the BERT4Rec replication studies): no
 negatives are drawn, every test slot's ground truth is ranked against the whole vocabulary minus [PAD] / [MASK] / [UNK] and the ids
 in the row's `labels` (the ground truth itself always stays), by one b4r_rank_full launch per batch; the ranks feed the same metric
-sums.  The default keeps the sampled protocol exactly."""
+sums.  The default keeps the sampled protocol exactly.
+
+list_k=k (with full_ranking) evaluates the top-k LISTS as well: the same b4r_rank_full launch returns the rank of the ground truth
+and the row's best k items (or its best candidate_pool items, from which b4r_rerank_diverse picks k when diversity is a number), and
+one b4r_list_metrics call per batch adds the lists' intra-list distance, novelty and item exposure to device accumulators that are
+read back once per evaluate(), like the metric sums.  The results gain ILD@k, Novelty@k, Coverage@k and Gini@k."""
 from typing import Union
 
 import numpy as np
 import torch
 
 from ..dataloaders import samplers
-from ..engine import SPECIAL_IDS
+from ..engine import SPECIAL_IDS, check_rank_full_args, check_rerank_args, item_self_information
 from .base_evaluator import BaseEvaluator
-from .evaluation_metrics import HR, MAP, NDCG, Counter, EvaluationMetric, gain_table
+from .evaluation_metrics import GAIN_COUNT, GAIN_HIT, GAIN_NDCG, HR, MAP, NDCG, Counter, EvaluationMetric, gain_table
 
 
 def default_metrics():
@@ -31,11 +36,66 @@ def default_metrics():
     return [Counter(name="Valid Ranks"), NDCG(1), NDCG(5), NDCG(10), HR(1), HR(5), HR(10), MAP()]
 
 
+def exposure_coverage(exposure) -> float:
+    """Catalogue coverage: the share of the items of `exposure` (one recommendation count per item) that were recommended at all."""
+    c = np.asarray(exposure, dtype=np.float64).reshape(-1)
+    return float((c > 0).sum()) / c.size if c.size else 0.0
+
+
+def exposure_gini(exposure) -> float:
+    """Gini index of the exposure counts c_1 <= ... <= c_n: sum_i (2 i - n - 1) c_i / (n sum_i c_i), in float64.  0 = every item was
+    recommended equally often, (n - 1) / n = one item took every slot; 0 when nothing was recommended."""
+    c = np.sort(np.asarray(exposure, dtype=np.float64).reshape(-1))
+    n, total = c.size, float(c.sum())
+    if n == 0 or total <= 0.0:
+        return 0.0
+    i = np.arange(1, n + 1, dtype=np.float64)
+    return float(((2.0 * i - n - 1.0) * c).sum() / (n * total))
+
+
 class BERT4RecEvaluator(BaseEvaluator):
     def __init__(self, metrics: list = None, sampler: Union[str, "samplers.BaseSampler"] = "pop_random", dataloader=None,
-                 device_sampling: bool = True, seed: int = 0, full_ranking: bool = False):
+                 device_sampling: bool = True, seed: int = 0, full_ranking: bool = False, list_k: int = None, diversity: float = None,
+                 candidate_pool: int = None, item_counts=None):
+        """list_k / diversity / candidate_pool / item_counts: list evaluation (the module docstring); with list_k=None, the default,
+        nothing changes.  list_k=k needs full_ranking=True.  diversity=None evaluates the sweep's own top k and takes the accuracy
+        metrics from the full-catalogue rank, as without list_k; diversity=d in [0, 1] re-ranks the best candidate_pool items (default
+        min(1024, max(10 k, 50))) and takes the accuracy metrics from the position of the ground truth in the re-ranked list (rank
+        k + 1 where it is absent), so every metric must then be a counter or HR / NDCG with a cut-off of at most k.  item_counts: one
+        interaction count per token id [V] for Novelty@k; None takes the counts of the dataloader's tokenized item list, and without a
+        dataloader Novelty@k is not reported."""
         self.device_sampling = device_sampling
         self.full_ranking = bool(full_ranking)
+        if metrics is None:
+            metrics = default_metrics()
+        self.list_k = self._list_pool = None
+        self.diversity = diversity
+        self._item_counts = item_counts
+        self._list_dev = None      # (engine, exposure int64 [V], sums float64 [2], counts int64 [2], item weight fp32 [V] or None)
+        self._list_host = None     # what the flushes have read back so far: [exposure int64 [V], ild sum, novelty sum, rows >= 2, rows >= 1]
+        self._list_novelty = False
+        if list_k is None:
+            if diversity is not None or candidate_pool is not None or item_counts is not None:
+                raise ValueError("diversity, candidate_pool and item_counts belong to the list evaluation: give list_k as well")
+        else:
+            if not self.full_ranking:
+                raise ValueError("list_k evaluates the full-catalogue top-k lists: it needs full_ranking=True")
+            k = check_rank_full_args(list_k)
+            if k < 1:
+                raise ValueError(f"list_k must lie in [1, 1024], got {list_k}")
+            pool = k
+            if diversity is not None:
+                k, pool, _ = check_rerank_args(k, candidate_pool, diversity)
+                for m in metrics:
+                    if not (m.family == GAIN_COUNT or (m.family in (GAIN_HIT, GAIN_NDCG) and 1 <= m.cutoff <= k)):
+                        raise ValueError(f"metric {m.name} looks beyond the first {k} ranks, which a re-ranked list of {k} items does "
+                                         f"not have: with diversity every metric must be a counter or have a cut-off of at most list_k")
+            elif candidate_pool is not None:
+                raise ValueError("candidate_pool is the candidate count of the diversity-aware re-ranking: give diversity as well")
+            if len(metrics) > 32:
+                raise ValueError("the list evaluation accumulates on the device: at most 32 metrics")
+            self.list_k, self._list_pool = k, pool
+            self._list_novelty = item_counts is not None or dataloader is not None
         self._dev = None   # (engine, float64 gain sums [n_metrics], int64 user count [1]) on the GPU
         self._seed = int(seed)
         self._draws = 0
@@ -43,8 +103,6 @@ class BERT4RecEvaluator(BaseEvaluator):
         self._short = None   # device flag: some row had fewer drawable items than the sample size (checked once per evaluation)
         self._slots = None
         self._rows = None
-        if metrics is None:
-            metrics = default_metrics()
         if isinstance(sampler, str):
             sampler_config = {"sample_size": 100}
             if dataloader is not None:
@@ -56,11 +114,16 @@ class BERT4RecEvaluator(BaseEvaluator):
 
     def evaluate(self, model, test_data, group=None) -> list:
         """bert4rec_evaluator.py:46-58.  With an initialised torch.distributed process group (`group`, default WORLD) rank k
-        evaluates batches k, k + world, ... and every rank ends with the metrics of ALL users."""
+        evaluates batches k, k + world, ... and every rank ends with the metrics of ALL users.  The list evaluation (list_k) runs on
+        one rank only: merging the list sums and the exposure counts across ranks is not implemented, and more than one rank raises
+        ValueError before the first batch."""
         if not self.full_ranking and self.dataloader is None and not self.sampler.is_fully_prepared():
             raise ValueError("The evaluator has to be either initialized with a dataloader or a fully prepared sampler "
                              "has to be given.")
         rank, world = _dist_rank_world(group)
+        if self.list_k is not None and world > 1:
+            # the lists' sums and the exposure counts would have to be merged across the ranks: out of scope of the list evaluation
+            raise ValueError("list_k evaluates on one rank only: the list sums are not merged across a process group")
         before = [m.partial() for m in self._metrics]
         for i, batch in enumerate(test_data):
             if i % world == rank:
@@ -91,6 +154,7 @@ class BERT4RecEvaluator(BaseEvaluator):
         """one device -> host copy for the whole evaluation: fold the accumulated sums into the metric objects.  Returns True (or
         raises, raise_on_short) when the sampler kernel flagged a row with fewer drawable items than the sample size: nothing of
         that evaluation is then folded in."""
+        self._flush_list_sums()
         if self._dev is None:
             return False
         _, sums, users = self._dev
@@ -107,6 +171,60 @@ class BERT4RecEvaluator(BaseEvaluator):
         sums.zero_()
         users.zero_()
         return False
+
+    # ---- list evaluation (list_k) ----------------------------------------------------------------------------------------------
+    def _list_sums(self, engine):
+        """The device accumulators of the list evaluation, and the items' novelty weights (None: no counts are known)."""
+        if self._list_dev is None or self._list_dev[0] is not engine:
+            self._flush_list_sums()
+            dev, V = engine.params.device, engine.cfg.vocab_size
+            weight = None
+            counts = self._item_counts
+            if counts is None and self.dataloader is not None:
+                tokens = np.asarray(self.dataloader.create_item_list_tokenized(), dtype=np.int64)   # the list the sampler is built from
+                counts = np.bincount(tokens[(tokens >= 0) & (tokens < V)], minlength=V)
+            if counts is not None:
+                counts = np.asarray(torch.as_tensor(counts).cpu().numpy(), dtype=np.float64).reshape(-1)
+                if counts.shape[0] != V:
+                    raise ValueError(f"item_counts holds {counts.shape[0]} counts for a vocabulary of {V}")
+                weight = torch.from_numpy(item_self_information(counts)).to(dev)
+            self._list_dev = (engine, torch.zeros(V, dtype=torch.int64, device=dev), torch.zeros(2, dtype=torch.float64, device=dev),
+                              torch.zeros(2, dtype=torch.int64, device=dev), weight)
+        return self._list_dev
+
+    def _flush_list_sums(self) -> None:
+        """one device -> host copy of the list accumulators per flush: [exposure | counts] as int64, the two sums as float64"""
+        if getattr(self, "_list_dev", None) is None:
+            return
+        _, exposure, sums, counts, _ = self._list_dev
+        ints = torch.cat([exposure, counts]).cpu().numpy()
+        s = sums.cpu().tolist()
+        if self._list_host is None:
+            self._list_host = [np.zeros(exposure.numel(), dtype=np.int64), 0.0, 0.0, 0, 0]
+        h = self._list_host
+        if h[0].shape[0] != exposure.numel():
+            raise ValueError("the list evaluation saw models of different vocabulary sizes: reset_metrics() between them")
+        h[0] += ints[:-2]
+        h[1] += s[0]; h[2] += s[1]
+        h[3] += int(ints[-2]); h[4] += int(ints[-1])
+        exposure.zero_(); sums.zero_(); counts.zero_()
+
+    def list_results(self) -> dict:
+        """ILD@k, Novelty@k (when item counts are known), Coverage@k and Gini@k of everything evaluated since the last reset: the mean
+        over the lists with at least 2 items of their mean pair distance 1 - cosine, the mean over the non-empty lists of their mean
+        item self-information, and the two exposure statistics over the V - 3 items, in float64 on the host."""
+        if self.list_k is None:
+            return {}
+        self._flush_list_sums()
+        k = self.list_k
+        h = self._list_host if self._list_host is not None else [np.zeros(0, dtype=np.int64), 0.0, 0.0, 0, 0]
+        out = {f"ILD@{k}": h[1] / h[3] if h[3] else 0.0}
+        if self._list_novelty:
+            out[f"Novelty@{k}"] = h[2] / h[4] if h[4] else 0.0
+        items = h[0][SPECIAL_IDS:]
+        out[f"Coverage@{k}"] = exposure_coverage(items)
+        out[f"Gini@{k}"] = exposure_gini(items)
+        return out
 
     def _merge_across_ranks(self, before, group, short: bool = False) -> bool:
         """all-reduce what THIS evaluate() call added on each rank: [gain sums | user count | short flag] as float64.  Returns True
@@ -250,7 +368,19 @@ class BERT4RecEvaluator(BaseEvaluator):
         gt = torch.as_tensor(test_batch["masked_lm_ids"]).to(dev)[b_idx, p_idx].to(torch.int64)
         exclude = torch.as_tensor(test_batch["labels"]).to(dev)[b_idx].to(torch.int64)   # the user's whole sequence
         hidden, _, _ = model._ranked_slot_hidden(test_batch, slots)
-        _, _, gt_rank = engine.rank_full(hidden, None, exclude, SPECIAL_IDS, gt, 0)
+        if self.list_k is None:
+            _, _, gt_rank = engine.rank_full(hidden, None, exclude, SPECIAL_IDS, gt, 0)
+        else:
+            # the same sweep, asked for its best items as well: the ground truth stays rankable, so it can stand in the list
+            _, exposure, sums, counts, weight = self._list_sums(engine)
+            ids, scores, gt_rank = engine.rank_full(hidden, None, exclude, SPECIAL_IDS, gt, self._list_pool)
+            if self.diversity is not None:
+                ids, _, _ = engine.rerank_diverse(ids, scores, self.list_k, self.diversity)
+            _, _, _, hit_pos = engine.list_metrics(ids, gt, weight, exposure=exposure, sums=sums, counts=counts)
+            if self.diversity is not None:
+                # the rank in the re-ranked list; k + 1: not in it (no gain under any cut-off <= k); 0 stays "no valid ground truth"
+                absent = torch.full_like(hit_pos, self.list_k + 1)
+                gt_rank = torch.where(gt_rank > 0, torch.where(hit_pos > 0, hit_pos, absent), torch.zeros_like(hit_pos))
         if len(self._metrics) <= 32:
             _, sums, users = self._device_sums(engine)
             table = gain_table(self._metrics)
@@ -267,7 +397,9 @@ class BERT4RecEvaluator(BaseEvaluator):
 
     def get_metrics_results(self) -> dict:
         self._flush_device_sums()
-        return super().get_metrics_results()
+        results = super().get_metrics_results()
+        results.update(self.list_results())
+        return results
 
     def reset_metrics(self) -> None:
         if getattr(self, "_dev", None) is not None:
@@ -275,6 +407,10 @@ class BERT4RecEvaluator(BaseEvaluator):
             self._dev[2].zero_()
         if getattr(self, "_short", None) is not None:
             self._short.zero_()
+        if getattr(self, "_list_dev", None) is not None:
+            for t in self._list_dev[1:4]:
+                t.zero_()
+        self._list_host = None
         super().reset_metrics()
 
 

@@ -365,6 +365,26 @@ class BERT4RecModel:
             ids, scores, _ = self.engine.rerank_diverse(ids, scores, k, diversity)
         return ids, scores, slots
 
+    def list_metrics_tensor(self, ids: torch.Tensor, ground_truth: Optional[torch.Tensor] = None,
+                            item_weight: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """Beyond-accuracy metrics of recommendation lists ids [R, K] int64 (recommend_tensor's ids, re-ranked or not; -1 entries are
+        skipped), from one b4r_list_metrics call in the item table.  Returns device tensors, one entry per list:
+          n        int32: the items of the list
+          ild      float64: intra-list diversity, the mean of 1 - cosine over the list's item pairs; NaN where n < 2
+          novelty  float64: the mean item_weight of the list's items (item_weight [V] fp32: the items' self-information,
+                   bert4rec_amd.apps.item_self_information); NaN where n < 1 or item_weight is None
+          hit_pos  int32: the 1-based position of ground_truth [R] in the list, 0 where absent or ground_truth is None."""
+        ids = torch.as_tensor(ids)
+        gt = None if ground_truth is None else torch.as_tensor(ground_truth).to(torch.int64)
+        w = None if item_weight is None else torch.as_tensor(item_weight)
+        n, dist, nov, hit = self.engine.list_metrics(ids, gt, w)
+        n64 = n.to(torch.float64)
+        nan = torch.full_like(n64, float("nan"))
+        pairs = n64 * (n64 - 1.0) / 2.0
+        ild = torch.where(n >= 2, (dist.to(torch.float64) / 2.0 ** 30) / pairs.clamp(min=1.0), nan)
+        novelty = nan if w is None else torch.where(n >= 1, (nov.to(torch.float64) / 2.0 ** 30) / n64.clamp(min=1.0), nan)
+        return {"n": n, "ild": ild, "novelty": novelty, "hit_pos": hit}
+
     def similar_items_tensor(self, item_ids, k: int = 10, metric: str = "cosine", allow=None, row_filter=None):
         """Item-to-item neighbours in the encoder's item table (the tied output embedding, width E when factorised): for each of
         item_ids [R] the k nearest items by metric "cosine" or "dot", the item itself and [PAD] / [MASK] / [UNK] left out, ties to

@@ -353,6 +353,38 @@ int64_t b4r_rerank_diverse_scratch_bytes(int32_t R, int32_t M, int32_t V);
 int b4r_rerank_diverse(const float* table, int32_t ld, int32_t width, int32_t V, const float* item_rnorm, const int64_t* pool_ids,
                        const float* pool_scores, int32_t R, int32_t M, float lambda, int32_t K, int64_t* out_ids, float* out_scores,
                        float* out_mmr, void* scratch, int64_t scratch_bytes, b4r_stream_t stream);
+/* Beyond-accuracy metrics of recommendation lists list_ids [R, K] int64 (b4r_rank_full's top K or b4r_rerank_diverse's picks) in
+ * table [V, width]: intra-list distance, novelty, hit position, item exposure.  Row r, positions p = 0 .. K-1:
+ *   live        list_ids[r][p] in [0, V); the -1 tail and every other id are skipped everywhere.  A repeated id counts once per
+ *               occurrence, as in b4r_rerank_diverse.
+ *   row_n[r]    int32: the number of live entries.
+ *   row_dist[r] int64 = sum over live pairs p < p' of q30(fl32(1.0f - sim(c = item at p', q = item at p))), sim exactly
+ *               b4r_rerank_diverse's sim(c, q) (the earlier position is the query; rnorm = item_rnorm [V], or NULL: computed into
+ *               scratch exactly as b4r_item_neighbours(B4R_SIM_COSINE) computes it); the subtraction is rounded on its own, no FMA.
+ *               q30(x) = (int64) rint(x * 2^30): the product is exact in fp32, ties to even, so the sum is an integer whatever the
+ *               order of its terms.  (Two identical table rows can give a distance of a few negative units.)
+ *   row_nov[r]  int64 = sum over live p of q30(item_weight[id]); 0 when item_weight is NULL.  item_weight [V] fp32: the per-item
+ *               self-information of the novelty metric, supplied by the caller, finite with |w| < 2^20.
+ *   hit_pos[r]  int32: the 1-based position of the first live entry equal to gt[r]; 0 when gt is NULL, gt[r] lies outside
+ *               [first_item, V), or no live entry equals it.
+ * Device accumulators, zeroed by the caller and read once per evaluation (as b4r_rank_metrics'):
+ *   exposure [V] int64  += 1 per live occurrence of the item (64-bit integer atomics: exact in any order)
+ *   sums [2] double     sums[0] += sum over rows with n >= 2 of (row_dist / 2^30) / (n (n - 1) / 2)   (mean pair distance of the row)
+ *                       sums[1] += sum over rows with n >= 1 of (row_nov / 2^30) / n                  (mean item weight of the row)
+ *   counts [2] int64    += the number of rows with n >= 2, with n >= 1
+ *               sums and counts are folded by a closing one-workgroup launch in a fixed order: bitwise reproducible from run to run.
+ * Every output and accumulator may be NULL.  1 <= K <= 1024, width a multiple of 4 up to 4096, ld == width, V > 0, R >= 0 (else
+ * B4R_E_SHAPE); a NULL table or list_ids B4R_E_BADARG; all of it is checked before any launch.  R = 0 succeeds and launches nothing.
+ * scratch: b4r_list_metrics_scratch_bytes(R, K, V) bytes, 16-byte aligned (rnorm [V] rounded up to 16 bytes, then the per-row integers
+ * of the fold; 0 for R = 0 and for K outside [1, 1024]).  It is needed when item_rnorm is NULL, or when sums / counts are given without
+ * all of row_n, row_dist, row_nov; a smaller one then returns B4R_E_NOMEM.  After a call without item_rnorm its first V floats hold
+ * rnorm.  Non-finite table values are outside the contract (they are never read out of bounds).  Only enqueues (two launches with
+ * sums / counts, one more without item_rnorm; one stream, no host sync, graph-capturable); no float atomics. */
+int64_t b4r_list_metrics_scratch_bytes(int32_t R, int32_t K, int32_t V);
+int b4r_list_metrics(const float* table, int32_t ld, int32_t width, int32_t V, int32_t first_item, const float* item_rnorm,
+                     const int64_t* list_ids, int32_t R, int32_t K, const int64_t* gt, const float* item_weight, int32_t* row_n,
+                     int64_t* row_dist, int64_t* row_nov, int32_t* hit_pos, int64_t* exposure, double* sums, int64_t* counts,
+                     void* scratch, int64_t scratch_bytes, b4r_stream_t stream);
 /* replaces the metric loop of bert4rec_evaluator.py:118-120 over evaluation_metrics.py:47-112 for a batch of ranks:
  * gain_sums[m] += sum over gt_rank[i] > 0 of gain_m(gt_rank[i]), users[0] += #{gt_rank[i] > 0}; double / int64 DEVICE
  * accumulators the caller reads once per evaluate().  family[m]: 0 count (gain 1), 1 hit@cutoff (rank <= k), 2 NDCG@cutoff
