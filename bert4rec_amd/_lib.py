@@ -50,6 +50,14 @@ class AdamWConfig(C.Structure):
                 ("beta_2", C.c_float), ("epsilon", C.c_float), ("clip_norm", C.c_float), ("decay_mask", C.c_void_p)]
 
 
+QUOTA_MAX = 4   # B4R_QUOTA_MAX
+
+
+class ItemQuota(C.Structure):
+    """b4r_item_quota: one attribute of the items for b4r_rerank_quota (a host struct; item_group / group_cap are device pointers)"""
+    _fields_ = [("item_group", C.c_void_p), ("group_cap", C.c_void_p), ("n_groups", C.c_int32), ("cap", C.c_int32)]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [("A", C.c_void_p), ("lda", C.c_int32), ("B", C.c_void_p), ("ldb", C.c_int32), ("C", C.c_void_p),
                 ("ldc", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("b_is_nk", C.c_int32),
@@ -183,6 +191,9 @@ PROTOTYPES = {
     "b4r_item_neighbours": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _I32, _I32, _P, _I32, _P, _I32, _P, _P, _P, _I64, _P]),
     "b4r_rerank_diverse_scratch_bytes": (_I64, [_I32, _I32, _I32]),
     "b4r_rerank_diverse": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _F, _I32, _P, _P, _P, _P, _I64, _P]),
+    "b4r_rerank_quota_scratch_bytes": (_I64, [_I32, _I32, _I32]),
+    "b4r_rerank_quota": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _F, _I32, C.POINTER(ItemQuota), _I32, _P, _P, _P, _P, _P,
+                                   _I64, _P]),
     "b4r_list_metrics_scratch_bytes": (_I64, [_I32, _I32, _I32]),
     "b4r_list_metrics": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "b4r_rank_metrics": (C.c_int, [_P, _I32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I32, _P, _P, _P]),

@@ -17,11 +17,14 @@ the learned item table (b4r_item_neighbours).
 diversity (0 = the plain top k, the default; up to 1) trades relevance against similarity among the returned items: the sweep returns
 candidate_pool candidates per user and b4r_rerank_diverse picks k of them by greedy Maximal Marginal Relevance, cosine in the item table.
 
+max_per_group caps how many of the returned items may share a category / brand / artist: the sweep returns candidate_pool candidates
+per user and b4r_rerank_quota picks k of them under the caps, in relevance order (or by MMR when diversity is given as well).
+
 list_quality measures what such lists are like beyond accuracy (b4r_list_metrics): intra-list diversity, catalogue coverage, novelty."""
 import numpy as np
 import torch
 
-from ..engine import SPECIAL_IDS, item_self_information
+from ..engine import SPECIAL_IDS, _as_cap, item_self_information, pack_item_groups
 
 
 class Recommender:
@@ -55,11 +58,48 @@ class Recommender:
             mask[torch.as_tensor(tokens, dtype=torch.int64)] = True
         return mask
 
-    def __call__(self, sequence: list, k: int = 1, allowed_items=None, diversity=None, candidate_pool=None):
-        """allowed_items: an iterable of items; only those are recommended.  diversity / candidate_pool: as in recommend_batch.
-        A call with any of them goes through recommend_batch."""
-        if allowed_items is not None or diversity is not None or candidate_pool is not None:
-            return self.recommend_batch([sequence], k, allowed_items=allowed_items, diversity=diversity, candidate_pool=candidate_pool)[0]
+    def _item_groups(self, max_per_group) -> list:
+        """(labels, cap) or a list of such pairs -> pack_item_groups specs, through the tokenizer.  labels: a mapping (or a callable)
+        from a detokenized item to a hashable group label; an item it does not know, or maps to None, is in no group.  cap: one int
+        for every group, or a mapping label -> int (a label it does not hold is not capped).  The specs are packed for this one call
+        and live on the model's device, so nothing of them outlives the call."""
+        pairs = [max_per_group] if isinstance(max_per_group, tuple) and len(max_per_group) == 2 and \
+            not isinstance(max_per_group[0], tuple) else list(max_per_group)
+        V = self.model.vocab_size
+        tokens = list(range(SPECIAL_IDS, V))
+        items = self.dataloader.get_tokenizer().detokenize(tokens)
+        specs = []
+        for pair in pairs:
+            if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+                raise ValueError("max_per_group takes (labels, cap) or a list of such pairs")
+            labels, cap = pair
+            look = labels if callable(labels) else getattr(labels, "get", None)   # (a callable's own errors are the caller's to see)
+            if look is None:
+                raise ValueError("labels maps an item to its group label: a mapping or a callable")
+            index, groups = {}, np.full(V, -1, dtype=np.int64)
+            for t, item in zip(tokens, items):
+                label = look(item)
+                if label is not None:
+                    groups[t] = index.setdefault(label, len(index))
+            if hasattr(cap, "get"):
+                big = (1 << 31) - 1
+                caps = np.full(len(index), big, dtype=np.int64)
+                for label, g in index.items():
+                    c = cap.get(label)
+                    if c is not None:
+                        caps[g] = _as_cap(c, f"the cap of {label!r}")
+                specs.append(pack_item_groups(groups, caps, n_groups=len(index)))
+            else:
+                specs.append(pack_item_groups(groups, cap, n_groups=len(index)))
+        device = self.model.engine.params.device
+        return [spec.to(device) for spec in specs]
+
+    def __call__(self, sequence: list, k: int = 1, allowed_items=None, diversity=None, candidate_pool=None, max_per_group=None):
+        """allowed_items: an iterable of items; only those are recommended.  diversity / candidate_pool / max_per_group: as in
+        recommend_batch.  A call with any of them goes through recommend_batch."""
+        if allowed_items is not None or diversity is not None or candidate_pool is not None or max_per_group is not None:
+            return self.recommend_batch([sequence], k, allowed_items=allowed_items, diversity=diversity, candidate_pool=candidate_pool,
+                                        max_per_group=max_per_group)[0]
         tokenizer = self.dataloader.get_tokenizer()
         batch = self.dataloader.prepare_inference(list(sequence))
         batch = {key: torch.from_numpy(np.asarray(v)) for key, v in batch.items()}
@@ -72,13 +112,17 @@ class Recommender:
         return items[0] if k == 1 else items
 
     def recommend_batch(self, sequences, k: int = 1, allowed_items=None, allowed_items_per_user=None, diversity=None,
-                        candidate_pool=None) -> list:
+                        candidate_pool=None, max_per_group=None) -> list:
         """Recommender(...)(seq, k) for every sequence of `sequences`, from one batched forward and one full-catalogue top-k.
         allowed_items: one iterable of items (detokenized values) for all users; allowed_items_per_user: one iterable per sequence
         (identical lists share one filter).  Only allowed items are recommended; items the vocabulary does not know are ignored.
         With k = 1 a user for whom nothing is left to recommend gets None, with or without a filter (every item seen or excluded).
         diversity: None or 0 = the k best items, as before; a number up to 1 = the k items are picked from the candidate_pool best
-        (default min(1024, max(10 k, 50))) by greedy Maximal Marginal Relevance, so that they are less alike (recommend_tensor)."""
+        (default min(1024, max(10 k, 50))) by greedy Maximal Marginal Relevance, so that they are less alike (recommend_tensor).
+        max_per_group: (labels, cap) or a list of at most 4 such pairs -- at most cap of the k items share a group.  labels maps an
+        item to a hashable group label (a mapping or a callable; unknown or absent items are in no group), cap is an int or a mapping
+        label -> int.  The k items are picked from the candidate_pool best under the caps (b4r_rerank_quota); a user whose pool holds
+        fewer than k admissible items gets a shorter list: a larger candidate_pool is the remedy."""
         tokenizer = self.dataloader.get_tokenizer()
         sequences = [list(seq) for seq in sequences]
         if allowed_items is not None and allowed_items_per_user is not None:
@@ -90,6 +134,7 @@ class Recommender:
                 raise ValueError(f"{len(lists)} allow-lists for {len(sequences)} sequences")
             distinct = {}
             user_filter = [distinct.setdefault(frozenset(self._known_tokens(items)), len(distinct)) for items in lists]
+        quotas = None if max_per_group is None else self._item_groups(max_per_group)   # packed once per call
         if not sequences:
             return []
         batches = [self.dataloader.prepare_inference(list(seq)) for seq in sequences]
@@ -112,7 +157,7 @@ class Recommender:
             w = batch["masked_lm_weights"] != 0
             row_filter = torch.as_tensor(user_filter, dtype=torch.int32)[torch.nonzero(w, as_tuple=True)[0]]
         ids, _, slots = self.model.recommend_tensor(batch, k=k, exclude_seen=False, exclude=exclude, allow=allow, row_filter=row_filter,
-                                                    diversity=diversity, pool=candidate_pool)
+                                                    diversity=diversity, pool=candidate_pool, max_per_group=quotas)
         P = int(batch["masked_lm_positions"].shape[1])
         first = {}
         for i, s in enumerate(slots.cpu().tolist()):   # __call__ ranks the first weighted slot of its one-row batch

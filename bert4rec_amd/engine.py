@@ -244,6 +244,95 @@ def check_rerank_args(k, pool, diversity) -> Tuple[int, int, float]:
     return k, pool, C.c_float(1.0 - float(diversity)).value
 
 
+class ItemGroups(tuple):
+    """One quota of the re-ranking under caps (pack_item_groups): (item_group int32 [V], group_cap int32 [n_groups] or None,
+    n_groups, cap).  Immutable; the tensors are ready to be moved to the device as they are."""
+    __slots__ = ()
+    item_group = property(operator.itemgetter(0))
+    group_cap = property(operator.itemgetter(1))
+    n_groups = property(operator.itemgetter(2))
+    cap = property(operator.itemgetter(3))
+
+    def to(self, device) -> "ItemGroups":
+        """The same quota with its tensors on `device`: a caller that packs a spec for one call moves it itself, and the engine then
+        keeps no copy of it."""
+        return ItemGroups((self.item_group.to(device), None if self.group_cap is None else self.group_cap.to(device), self.n_groups,
+                           self.cap))
+
+
+def _as_cap(c, what: str) -> int:
+    if isinstance(c, bool):
+        raise ValueError(f"{what} must be an integer, got {c!r}")
+    try:
+        c = operator.index(c)
+    except TypeError:
+        raise ValueError(f"{what} must be an integer, got {c!r}") from None
+    return max(-1, min(c, (1 << 31) - 1))   # (a cap below 1 closes the group; one beyond int32 never binds)
+
+
+def pack_item_groups(groups, cap, n_groups: Optional[int] = None) -> ItemGroups:
+    """One quota "at most cap items per group" for recommend_tensor(max_per_group=...) / Engine.rerank_quota.  groups: an integer
+    array [V], the group of every token id (category, brand, ...); a negative value = the item is in no group and is never capped.
+    cap: one int for every group, or an integer array with one cap per group (a cap of 0 bars the group).  n_groups: the number of
+    groups (default: the largest group id + 1, or the length of the cap array); an id at or beyond it counts as no group."""
+    g = torch.as_tensor(groups)
+    if g.ndim != 1 or g.numel() == 0 or g.dtype.is_floating_point or g.dtype.is_complex or g.dtype == torch.bool:
+        raise ValueError(f"groups must be a 1-D integer array [V], got {g.dtype} of shape {tuple(g.shape)}")
+    g64 = g.to(torch.int64)
+    top = int(g64.max())
+    if top >= (1 << 31) - 1:
+        raise ValueError(f"group ids must fit int32, got {top}")
+    caps = None
+    if isinstance(cap, (numbers.Integral, np.integer)) and not isinstance(cap, bool):
+        cap_i = _as_cap(cap, "cap")
+    else:
+        try:
+            c = torch.as_tensor(cap)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"cap must be an integer or an integer array with one cap per group, got {cap!r}") from None
+        if c.ndim != 1 or c.dtype.is_floating_point or c.dtype.is_complex or c.dtype == torch.bool:
+            raise ValueError(f"cap must be an integer or a 1-D integer array with one cap per group, got {c.dtype} of shape {tuple(c.shape)}")
+        caps = c.to(torch.int64).clamp(-1, (1 << 31) - 1).to(torch.int32).contiguous()
+        cap_i = 0
+    if n_groups is None:
+        n = int(caps.numel()) if caps is not None else max(top + 1, 0)
+    else:
+        n = _as_cap(n_groups, "n_groups")
+        if n < 0:
+            raise ValueError(f"n_groups must not be negative, got {n_groups}")
+    if caps is not None and int(caps.numel()) != n:
+        raise ValueError(f"{int(caps.numel())} caps for {n} groups")
+    item_group = g64.clamp(min=-1).to(torch.int32).contiguous()
+    return ItemGroups((item_group, caps, n, cap_i))
+
+
+def check_quota_args(quotas, vocab_size: Optional[int] = None) -> List[ItemGroups]:
+    """Argument checks of the re-ranking under caps that need no GPU.  quotas: None, one pack_item_groups spec or a list of at most 4;
+    every spec's group array has one entry per token id (checked when vocab_size is given).  Returns the list of specs."""
+    if quotas is None:
+        return []
+    if isinstance(quotas, ItemGroups):
+        quotas = [quotas]
+    try:
+        quotas = list(quotas)
+    except TypeError:
+        raise ValueError(f"max_per_group takes pack_item_groups specs, got {quotas!r}") from None
+    if len(quotas) > _lib.QUOTA_MAX:
+        raise ValueError(f"at most {_lib.QUOTA_MAX} quotas, got {len(quotas)}")
+    for q in quotas:
+        if not isinstance(q, ItemGroups):
+            raise ValueError(f"max_per_group takes pack_item_groups specs, got {type(q).__name__}")
+        if vocab_size is not None and int(q.item_group.numel()) != int(vocab_size):
+            raise ValueError(f"a quota's groups hold {int(q.item_group.numel())} entries for a vocabulary of {vocab_size}")
+        if q.item_group.dtype != torch.int32 or (q.group_cap is not None and (q.group_cap.dtype != torch.int32 or
+                                                                              int(q.group_cap.numel()) != q.n_groups)):
+            raise ValueError("a quota holds int32 groups and one int32 cap per group (pack_item_groups)")
+        if isinstance(q.cap, bool) or not isinstance(q.cap, int) or isinstance(q.n_groups, bool) or not isinstance(q.n_groups, int) \
+                or q.n_groups < 0:
+            raise ValueError(f"a quota's cap and n_groups are ints, got {q.cap!r} and {q.n_groups!r}")
+    return quotas
+
+
 def item_self_information(counts) -> np.ndarray:
     """The novelty weight of every item from its interaction count: -log2(max(c, 1) / sum(c)) (an item nobody interacted with
     counts as seen once), computed in float64 and rounded to fp32.  counts [V]: one count per token id; returns float32 [V]."""
@@ -279,6 +368,7 @@ class Engine:
         # b4r_train_state: 16 words (seed, step_lo, step(int64), 8 floats, 4 reserved)
         self.state = torch.zeros(_lib.STATE_WORDS, dtype=torch.int32, device=self.device)
         self._ws: Dict[Tuple[int, int, int], torch.Tensor] = {}
+        self._quota_dev: Dict[int, tuple] = {}   # id(spec) -> (spec, its tensors on the device): the last few host-side quota specs
         self.rehearse_collectives = False   # True: dp_train_step issues its all-reduce even in a process group of one
         self.set_seed(seed)
 
@@ -808,6 +898,61 @@ class Engine:
                                                _ptr(ids), _ptr(scores), _ptr(mmr), _ptr(sc), 0 if sc is None else sc.numel(),
                                                _stream(self.device)), "b4r_rerank_diverse")
         return ids, scores, mmr
+
+    def _quota_on_device(self, spec: "ItemGroups"):
+        """The spec's tensors on this engine's device.  A spec that lives there already (ItemGroups.to) is used as it is; of a spec
+        elsewhere the copies of the last few are kept (a spec is immutable, and the entry holds it, so its id stays its own)."""
+        if spec.item_group.device == self.params.device and (spec.group_cap is None or spec.group_cap.device == self.params.device):
+            return spec.item_group.contiguous(), None if spec.group_cap is None else spec.group_cap.contiguous()
+        cache = self._quota_dev
+        hit = cache.get(id(spec))
+        if hit is None or hit[0] is not spec:
+            if len(cache) >= 8:
+                cache.pop(next(iter(cache)))
+            hit = cache[id(spec)] = (spec, spec.item_group.to(self.device).contiguous(),
+                                     None if spec.group_cap is None else spec.group_cap.to(self.device).contiguous())
+        return hit[1], hit[2]
+
+    def rerank_quota(self, pool_ids: torch.Tensor, pool_scores: torch.Tensor, k: int, diversity: float, quotas, rnorm: Optional[torch.Tensor] = None):
+        """b4r_rerank_quota on the item table [V, E]: rerank_diverse's greedy pick loop under caps "at most c items per group".
+        quotas: one pack_item_groups spec or a list of at most 4 (check_quota_args); none gives rerank_diverse's result.  An entry
+        closes once one of its groups has given its cap of picks; diversity = 0 keeps the pool's order under the caps.  Returns (ids
+        [R,k] int64, scores [R,k] fp32, mmr [R,k] fp32, pos [R,k] int32: the pool position of every pick), -1 / -inf / -inf / -1 where a
+        row has fewer than k admissible candidates.  rnorm as in rerank_diverse.  The scratch buffer is kept between calls."""
+        if pool_ids.ndim != 2 or pool_ids.dtype != torch.int64 or pool_scores.dtype != torch.float32 or pool_scores.shape != pool_ids.shape:
+            raise ValueError(f"the pool is ids int64 [R, M] and scores float32 [R, M], got {pool_ids.dtype} {tuple(pool_ids.shape)} and "
+                             f"{pool_scores.dtype} {tuple(pool_scores.shape)}")
+        R, M = (int(x) for x in pool_ids.shape)
+        k, _, lam = check_rerank_args(k, M, diversity)
+        V, Ew = self.cfg.vocab_size, self.embedding_width
+        specs = check_quota_args(quotas, V)
+        if rnorm is not None and (rnorm.dtype != torch.float32 or tuple(rnorm.shape) != (V,)):
+            raise ValueError(f"rnorm must be float32 [{V}], got {rnorm.dtype} {tuple(rnorm.shape)}")
+        ids_d, sc_d = pool_ids.to(self.device).contiguous(), pool_scores.to(self.device).contiguous()
+        rn_d = None if rnorm is None else rnorm.to(self.device).contiguous()
+        ids = torch.empty((R, k), dtype=torch.int64, device=self.device)
+        scores = torch.empty((R, k), dtype=torch.float32, device=self.device)
+        mmr = torch.empty((R, k), dtype=torch.float32, device=self.device)
+        pos = torch.empty((R, k), dtype=torch.int32, device=self.device)
+        if R == 0 or k == 0:
+            return ids, scores, mmr, pos
+        qs = (_lib.ItemQuota * max(len(specs), 1))()
+        keep = []
+        for q, spec in zip(qs, specs):
+            ig_d, gc_d = self._quota_on_device(spec)
+            keep.append((ig_d, gc_d))
+            q.item_group, q.group_cap, q.n_groups, q.cap = _ptr(ig_d), _ptr(gc_d), spec.n_groups, spec.cap
+        sc = None
+        if rn_d is None:
+            want = int(self.lib.b4r_rerank_quota_scratch_bytes(R, M, V))
+            sc = getattr(self, "_rerank_quota_scratch", None)
+            if sc is None or sc.numel() < want:
+                sc = self._rerank_quota_scratch = torch.empty(want, dtype=torch.uint8, device=self.device)
+        table = self.view("word_embeddings/embeddings")
+        _lib.check(self.lib.b4r_rerank_quota(_ptr(table), table.stride(0), Ew, V, _ptr(rn_d), _ptr(ids_d), _ptr(sc_d), R, M, lam, k,
+                                             qs, len(specs), _ptr(ids), _ptr(scores), _ptr(mmr), _ptr(pos), _ptr(sc),
+                                             0 if sc is None else sc.numel(), _stream(self.device)), "b4r_rerank_quota")
+        return ids, scores, mmr, pos
 
     def list_metrics(self, list_ids: torch.Tensor, gt: Optional[torch.Tensor] = None, item_weight: Optional[torch.Tensor] = None,
                      rnorm: Optional[torch.Tensor] = None, exposure: Optional[torch.Tensor] = None, sums: Optional[torch.Tensor] = None,

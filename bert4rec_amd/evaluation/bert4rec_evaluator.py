@@ -19,14 +19,15 @@ sums.  The default keeps the sampled protocol exactly.
 list_k=k (with full_ranking) evaluates the top-k LISTS as well: the same b4r_rank_full launch returns the rank of the ground truth
 and the row's best k items (or its best candidate_pool items, from which b4r_rerank_diverse picks k when diversity is a number), and
 one b4r_list_metrics call per batch adds the lists' intra-list distance, novelty and item exposure to device accumulators that are
-read back once per evaluate(), like the metric sums.  The results gain ILD@k, Novelty@k, Coverage@k and Gini@k."""
+read back once per evaluate(), like the metric sums.  The results gain ILD@k, Novelty@k, Coverage@k and Gini@k.
+max_per_group (pack_item_groups specs) evaluates the lists b4r_rerank_quota picks from the pool under those caps."""
 from typing import Union
 
 import numpy as np
 import torch
 
 from ..dataloaders import samplers
-from ..engine import SPECIAL_IDS, check_rank_full_args, check_rerank_args, item_self_information
+from ..engine import SPECIAL_IDS, check_quota_args, check_rank_full_args, check_rerank_args, item_self_information
 from .base_evaluator import BaseEvaluator
 from .evaluation_metrics import GAIN_COUNT, GAIN_HIT, GAIN_NDCG, HR, MAP, NDCG, Counter, EvaluationMetric, gain_table
 
@@ -56,14 +57,16 @@ def exposure_gini(exposure) -> float:
 class BERT4RecEvaluator(BaseEvaluator):
     def __init__(self, metrics: list = None, sampler: Union[str, "samplers.BaseSampler"] = "pop_random", dataloader=None,
                  device_sampling: bool = True, seed: int = 0, full_ranking: bool = False, list_k: int = None, diversity: float = None,
-                 candidate_pool: int = None, item_counts=None):
+                 candidate_pool: int = None, item_counts=None, max_per_group=None):
         """list_k / diversity / candidate_pool / item_counts: list evaluation (the module docstring); with list_k=None, the default,
         nothing changes.  list_k=k needs full_ranking=True.  diversity=None evaluates the sweep's own top k and takes the accuracy
         metrics from the full-catalogue rank, as without list_k; diversity=d in [0, 1] re-ranks the best candidate_pool items (default
         min(1024, max(10 k, 50))) and takes the accuracy metrics from the position of the ground truth in the re-ranked list (rank
         k + 1 where it is absent), so every metric must then be a counter or HR / NDCG with a cut-off of at most k.  item_counts: one
         interaction count per token id [V] for Novelty@k; None takes the counts of the dataloader's tokenized item list, and without a
-        dataloader Novelty@k is not reported."""
+        dataloader Novelty@k is not reported.  max_per_group: one bert4rec_amd.apps.pack_item_groups spec or a list of at most 4:
+        the lists are picked from the candidate_pool best under those caps (b4r_rerank_quota; in relevance order when diversity is
+        None), and the accuracy metrics come from the position in the capped list under the same rule on cut-offs as with diversity."""
         self.device_sampling = device_sampling
         self.full_ranking = bool(full_ranking)
         if metrics is None:
@@ -71,12 +74,14 @@ class BERT4RecEvaluator(BaseEvaluator):
         self.list_k = self._list_pool = None
         self.diversity = diversity
         self._item_counts = item_counts
+        self._quotas = None
         self._list_dev = None      # (engine, exposure int64 [V], sums float64 [2], counts int64 [2], item weight fp32 [V] or None)
         self._list_host = None     # what the flushes have read back so far: [exposure int64 [V], ild sum, novelty sum, rows >= 2, rows >= 1]
         self._list_novelty = False
         if list_k is None:
-            if diversity is not None or candidate_pool is not None or item_counts is not None:
-                raise ValueError("diversity, candidate_pool and item_counts belong to the list evaluation: give list_k as well")
+            if diversity is not None or candidate_pool is not None or item_counts is not None or max_per_group is not None:
+                raise ValueError("diversity, candidate_pool, item_counts and max_per_group belong to the list evaluation: give list_k "
+                                 "as well")
         else:
             if not self.full_ranking:
                 raise ValueError("list_k evaluates the full-catalogue top-k lists: it needs full_ranking=True")
@@ -84,14 +89,16 @@ class BERT4RecEvaluator(BaseEvaluator):
             if k < 1:
                 raise ValueError(f"list_k must lie in [1, 1024], got {list_k}")
             pool = k
-            if diversity is not None:
-                k, pool, _ = check_rerank_args(k, candidate_pool, diversity)
+            if max_per_group is not None:
+                self._quotas = check_quota_args(max_per_group)   # (their length is checked against the model's vocabulary per batch)
+            if diversity is not None or self._quotas is not None:
+                k, pool, _ = check_rerank_args(k, candidate_pool, 0.0 if diversity is None else diversity)
                 for m in metrics:
                     if not (m.family == GAIN_COUNT or (m.family in (GAIN_HIT, GAIN_NDCG) and 1 <= m.cutoff <= k)):
                         raise ValueError(f"metric {m.name} looks beyond the first {k} ranks, which a re-ranked list of {k} items does "
-                                         f"not have: with diversity every metric must be a counter or have a cut-off of at most list_k")
+                                         f"not have: with diversity or max_per_group every metric must be a counter or have a cut-off of at most list_k")
             elif candidate_pool is not None:
-                raise ValueError("candidate_pool is the candidate count of the diversity-aware re-ranking: give diversity as well")
+                raise ValueError("candidate_pool is the candidate count of the re-ranking: give diversity or max_per_group as well")
             if len(metrics) > 32:
                 raise ValueError("the list evaluation accumulates on the device: at most 32 metrics")
             self.list_k, self._list_pool = k, pool
@@ -374,10 +381,12 @@ class BERT4RecEvaluator(BaseEvaluator):
             # the same sweep, asked for its best items as well: the ground truth stays rankable, so it can stand in the list
             _, exposure, sums, counts, weight = self._list_sums(engine)
             ids, scores, gt_rank = engine.rank_full(hidden, None, exclude, SPECIAL_IDS, gt, self._list_pool)
-            if self.diversity is not None:
+            if self._quotas is not None:
+                ids = engine.rerank_quota(ids, scores, self.list_k, 0.0 if self.diversity is None else self.diversity, self._quotas)[0]
+            elif self.diversity is not None:
                 ids, _, _ = engine.rerank_diverse(ids, scores, self.list_k, self.diversity)
             _, _, _, hit_pos = engine.list_metrics(ids, gt, weight, exposure=exposure, sums=sums, counts=counts)
-            if self.diversity is not None:
+            if self.diversity is not None or self._quotas is not None:
                 # the rank in the re-ranked list; k + 1: not in it (no gain under any cut-off <= k); 0 stays "no valid ground truth"
                 absent = torch.full_like(hit_pos, self.list_k + 1)
                 gt_rank = torch.where(gt_rank > 0, torch.where(hit_pos > 0, hit_pos, absent), torch.zeros_like(hit_pos))

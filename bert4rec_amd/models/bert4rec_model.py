@@ -324,7 +324,7 @@ class BERT4RecModel:
 
     def recommend_tensor(self, encoder_input: Dict[str, torch.Tensor], k: int = 10, exclude_seen: bool = True,
                          exclude: Optional[torch.Tensor] = None, allow=None, row_filter=None, diversity: Optional[float] = None,
-                         pool: Optional[int] = None):
+                         pool: Optional[int] = None, max_per_group=None):
         """Top k of the whole catalogue for every slot with masked_lm_weights == 1 (all slots when the key is absent), from one
         b4r_rank_full call: no [R, V] scores.  The forward is rank_items_tensor's (encoder, then tfm MaskedLM's transform on those
         slots only).  [PAD] / [MASK] / [UNK] are never recommended; exclude_seen drops the row's own input_word_ids; exclude
@@ -336,13 +336,21 @@ class BERT4RecModel:
         diversity: None = the plain top k.  A number d in [0, 1]: the sweep returns the best `pool` allowed items of every row
         (default min(1024, max(10 k, 50)); at least k) and b4r_rerank_diverse picks k of them by greedy Maximal Marginal Relevance
         with lambda = 1 - d and cosine similarity in the item table: 0 keeps the plain order, 1 ranks by dissimilarity to the items
-        already picked alone.  The scores returned are the picked items' sweep scores (no longer descending)."""
+        already picked alone.  The scores returned are the picked items' sweep scores (no longer descending).
+        max_per_group: None, one bert4rec_amd.apps.pack_item_groups spec or a list of at most 4 -- "at most c items per category /
+        brand / ...".  The sweep returns the best `pool` allowed items of every row (the same default) and b4r_rerank_quota picks k of
+        them greedily under the caps: in relevance order when diversity is None (lambda = 1), else by MMR as above.  A row whose pool
+        holds fewer than k admissible items ends in -1 / -inf: there is no second, wider sweep (it would need a host
+        synchronisation); a larger `pool` is the remedy."""
         k = engine_mod.check_rank_full_args(k, exclude)
         n_sweep = k
-        if diversity is not None:
+        quotas = engine_mod.check_quota_args(max_per_group, self.vocab_size) if max_per_group is not None else None
+        if quotas is not None:
+            k, n_sweep, _ = engine_mod.check_rerank_args(k, pool, 0.0 if diversity is None else diversity)
+        elif diversity is not None:
             k, n_sweep, _ = engine_mod.check_rerank_args(k, pool, diversity)
         elif pool is not None:
-            raise ValueError("pool is the candidate count of the diversity-aware re-ranking: give diversity as well")
+            raise ValueError("pool is the candidate count of the re-ranking: give diversity or max_per_group as well")
         allow, row_filter = engine_mod.check_item_filter(allow, row_filter, self.vocab_size)
         hidden, slots, _ = self._ranked_slot_hidden(encoder_input)
         dev = self.device
@@ -361,7 +369,9 @@ class BERT4RecModel:
             parts.append(ex[b_idx])
         ex_rows = torch.cat(parts, dim=1) if parts else None
         ids, scores, _ = self.engine.rank_full(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, n_sweep, allow, row_filter)
-        if diversity is not None:
+        if quotas is not None:
+            ids, scores, _, _ = self.engine.rerank_quota(ids, scores, k, 0.0 if diversity is None else diversity, quotas)
+        elif diversity is not None:
             ids, scores, _ = self.engine.rerank_diverse(ids, scores, k, diversity)
         return ids, scores, slots
 
@@ -393,9 +403,10 @@ class BERT4RecModel:
         return self.engine.item_neighbours(item_ids, k, metric, engine_mod.SPECIAL_IDS, allow, row_filter)
 
     def recommend(self, encoder_input: dict, k: int = 10, exclude_seen: bool = True, exclude=None, diversity: Optional[float] = None,
-                  pool: Optional[int] = None):
+                  pool: Optional[int] = None, max_per_group=None):
         """recommend_tensor as Python lists: per batch row, one list per ranked slot of (ids, scores) lists of length k."""
-        ids, scores, slots = self.recommend_tensor(encoder_input, k, exclude_seen, exclude, diversity=diversity, pool=pool)
+        ids, scores, slots = self.recommend_tensor(encoder_input, k, exclude_seen, exclude, diversity=diversity, pool=pool,
+                                                   max_per_group=max_per_group)
         B, P = (int(x) for x in torch.as_tensor(encoder_input["masked_lm_positions"]).shape)
         out = [[] for _ in range(B)]
         for s, i_row, s_row in zip(slots.cpu().tolist(), ids.cpu().tolist(), scores.cpu().tolist()):

@@ -353,6 +353,40 @@ int64_t b4r_rerank_diverse_scratch_bytes(int32_t R, int32_t M, int32_t V);
 int b4r_rerank_diverse(const float* table, int32_t ld, int32_t width, int32_t V, const float* item_rnorm, const int64_t* pool_ids,
                        const float* pool_scores, int32_t R, int32_t M, float lambda, int32_t K, int64_t* out_ids, float* out_scores,
                        float* out_mmr, void* scratch, int64_t scratch_bytes, b4r_stream_t stream);
+/* b4r_rerank_diverse under category quotas: "at most c items per category / brand / artist / series".  Everything b4r_rerank_diverse
+ * states holds (live, rel, sim, rnorm, pen, mmr, the shapes and their error codes, the scratch), plus up to B4R_QUOTA_MAX quotas,
+ * each one attribute of the items.  Row r, pool entries c, quotas a = 0 .. n_quotas-1:
+ *   g_a(c)      the group of entry c under quota a: item_group[id of c] when that value lies in [0, n_groups), else "none" (the
+ *               entry is never capped by quota a).  left_a(c) starts at the cap of that group: group_cap[g] when group_cap is
+ *               given, else cap.
+ *   closed      a live entry with some left_a(c) <= 0 is closed before step 0 and is never picked.  It still counts in s_min /
+ *               s_max of rel: caps never change the relevance scale, and n_quotas = 0 gives b4r_rerank_diverse's bits.
+ *   step t      picks among the live, unpicked, unclosed entries: largest mmr (-0.0 equals +0.0), ties to the lower pool position.
+ *   after it    for every quota a where the picked entry q has a group, every still-open entry c with g_a(c) == g_a(q) loses one
+ *               from left_a(c) and closes when that reaches 0.  A repeated id is one entry per occurrence, so a second occurrence
+ *               that is picked counts against the cap.  pen is then raised as in b4r_rerank_diverse (a closed entry's pen is never
+ *               read, so the order of closing and raising cannot show).
+ *   outputs     out_pos[r][t] = the pool position of the pick (int32), -1 once the row has no open entry left; out_ids / out_scores
+ *               / out_mmr as in b4r_rerank_diverse (-1 / -inf / -inf in the tail).  Any output may be NULL.
+ * quotas is a HOST array read at enqueue; its item_group / group_cap are DEVICE arrays read by the kernel.  n_quotas in
+ * [0, B4R_QUOTA_MAX] (else B4R_E_SHAPE); a NULL quotas with n_quotas > 0, a NULL item_group or n_groups < 0: B4R_E_BADARG (the quota
+ * array is checked whatever R and K are).  group_cap is read only at indices in [0, n_groups) and item_group only at live ids, so
+ * garbage group ids cannot cause an out-of-bounds read.  All checks happen before any launch; R = 0 or K = 0 then succeeds and
+ * launches nothing.  scratch: b4r_rerank_quota_scratch_bytes(R, M, V) bytes when item_rnorm is NULL (its first V floats, rounded up
+ * to 16 bytes, then hold rnorm, as after b4r_rerank_diverse); not read when item_rnorm is given.  Only enqueues (one launch, two
+ * without item_rnorm; one stream, no host sync, graph-capturable); no atomics, bitwise reproducible. */
+enum { B4R_QUOTA_MAX = 4 };
+typedef struct b4r_item_quota {      /* one attribute of the items (category, brand, ...): a HOST struct, read at enqueue */
+  const int32_t* item_group;         /* device [V]: the group of item j; a value outside [0, n_groups) = j is in no group, never capped */
+  const int32_t* group_cap;          /* device [n_groups], or NULL: every group has the cap `cap` */
+  int32_t n_groups;
+  int32_t cap;
+} b4r_item_quota;
+int64_t b4r_rerank_quota_scratch_bytes(int32_t R, int32_t M, int32_t V);
+int b4r_rerank_quota(const float* table, int32_t ld, int32_t width, int32_t V, const float* item_rnorm, const int64_t* pool_ids,
+                     const float* pool_scores, int32_t R, int32_t M, float lambda, int32_t K, const b4r_item_quota* quotas,
+                     int32_t n_quotas, int64_t* out_ids, float* out_scores, float* out_mmr, int32_t* out_pos, void* scratch,
+                     int64_t scratch_bytes, b4r_stream_t stream);
 /* Beyond-accuracy metrics of recommendation lists list_ids [R, K] int64 (b4r_rank_full's top K or b4r_rerank_diverse's picks) in
  * table [V, width]: intra-list distance, novelty, hit position, item exposure.  Row r, positions p = 0 .. K-1:
  *   live        list_ids[r][p] in [0, V); the -1 tail and every other id are skipped everywhere.  A repeated id counts once per
