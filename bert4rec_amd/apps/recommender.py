@@ -20,7 +20,13 @@ candidate_pool candidates per user and b4r_rerank_diverse picks k of them by gre
 max_per_group caps how many of the returned items may share a category / brand / artist: the sweep returns candidate_pool candidates
 per user and b4r_rerank_quota picks k of them under the caps, in relevance order (or by MMR when diversity is given as well).
 
+return_probabilities / min_probability / temperature turn the scores into probabilities over the catalogue each user could have been
+served (b4r_score_dist: one more sweep, no [users, V] scores): every recommended item comes with its probability, and items below a
+threshold are dropped.
+
 list_quality measures what such lists are like beyond accuracy (b4r_list_metrics): intra-list diversity, catalogue coverage, novelty."""
+import numbers
+
 import numpy as np
 import torch
 
@@ -94,12 +100,16 @@ class Recommender:
         device = self.model.engine.params.device
         return [spec.to(device) for spec in specs]
 
-    def __call__(self, sequence: list, k: int = 1, allowed_items=None, diversity=None, candidate_pool=None, max_per_group=None):
-        """allowed_items: an iterable of items; only those are recommended.  diversity / candidate_pool / max_per_group: as in
-        recommend_batch.  A call with any of them goes through recommend_batch."""
-        if allowed_items is not None or diversity is not None or candidate_pool is not None or max_per_group is not None:
+    def __call__(self, sequence: list, k: int = 1, allowed_items=None, diversity=None, candidate_pool=None, max_per_group=None,
+                 return_probabilities: bool = False, min_probability=None, temperature: float = 1.0):
+        """allowed_items: an iterable of items; only those are recommended.  diversity / candidate_pool / max_per_group /
+        return_probabilities / min_probability / temperature: as in recommend_batch.  A call with any of them goes through
+        recommend_batch."""
+        calibrated = return_probabilities or min_probability is not None or not (isinstance(temperature, numbers.Real) and temperature == 1.0)
+        if allowed_items is not None or diversity is not None or candidate_pool is not None or max_per_group is not None or calibrated:
             return self.recommend_batch([sequence], k, allowed_items=allowed_items, diversity=diversity, candidate_pool=candidate_pool,
-                                        max_per_group=max_per_group)[0]
+                                        max_per_group=max_per_group, return_probabilities=return_probabilities,
+                                        min_probability=min_probability, temperature=temperature)[0]
         tokenizer = self.dataloader.get_tokenizer()
         batch = self.dataloader.prepare_inference(list(sequence))
         batch = {key: torch.from_numpy(np.asarray(v)) for key, v in batch.items()}
@@ -112,7 +122,8 @@ class Recommender:
         return items[0] if k == 1 else items
 
     def recommend_batch(self, sequences, k: int = 1, allowed_items=None, allowed_items_per_user=None, diversity=None,
-                        candidate_pool=None, max_per_group=None) -> list:
+                        candidate_pool=None, max_per_group=None, return_probabilities: bool = False, min_probability=None,
+                        temperature: float = 1.0) -> list:
         """Recommender(...)(seq, k) for every sequence of `sequences`, from one batched forward and one full-catalogue top-k.
         allowed_items: one iterable of items (detokenized values) for all users; allowed_items_per_user: one iterable per sequence
         (identical lists share one filter).  Only allowed items are recommended; items the vocabulary does not know are ignored.
@@ -122,7 +133,17 @@ class Recommender:
         max_per_group: (labels, cap) or a list of at most 4 such pairs -- at most cap of the k items share a group.  labels maps an
         item to a hashable group label (a mapping or a callable; unknown or absent items are in no group), cap is an int or a mapping
         label -> int.  The k items are picked from the candidate_pool best under the caps (b4r_rerank_quota); a user whose pool holds
-        fewer than k admissible items gets a shorter list: a larger candidate_pool is the remedy."""
+        fewer than k admissible items gets a shorter list: a larger candidate_pool is the remedy.
+        return_probabilities: every entry is an (item, probability) pair instead of an item: the softmax of the scores / temperature
+        over the items the user could have been served (the seen items and the filter applied), for the items actually returned.
+        min_probability: a number in [0, 1]; entries with a smaller probability are dropped (the rest keep their order), and a k = 1
+        user left with nothing gets None.  temperature (finite, > 0) needs one of the two.  Still one read-back of the lists per call."""
+        calibrated = bool(return_probabilities) or min_probability is not None
+        if min_probability is not None:
+            if isinstance(min_probability, bool) or not isinstance(min_probability, numbers.Real) or not 0.0 <= min_probability <= 1.0:
+                raise ValueError(f"min_probability must be a number in [0, 1], got {min_probability!r}")
+        if not calibrated and not (isinstance(temperature, numbers.Real) and temperature == 1.0):
+            raise ValueError("temperature scales the probabilities: give return_probabilities or min_probability as well")
         tokenizer = self.dataloader.get_tokenizer()
         sequences = [list(seq) for seq in sequences]
         if allowed_items is not None and allowed_items_per_user is not None:
@@ -156,17 +177,31 @@ class Recommender:
             # one filter index per ranked slot: the slots of recommend_tensor are those with masked_lm_weights != 0, in batch order
             w = batch["masked_lm_weights"] != 0
             row_filter = torch.as_tensor(user_filter, dtype=torch.int32)[torch.nonzero(w, as_tuple=True)[0]]
-        ids, _, slots = self.model.recommend_tensor(batch, k=k, exclude_seen=False, exclude=exclude, allow=allow, row_filter=row_filter,
-                                                    diversity=diversity, pool=candidate_pool, max_per_group=quotas)
+        got = self.model.recommend_tensor(batch, k=k, exclude_seen=False, exclude=exclude, allow=allow, row_filter=row_filter,
+                                          diversity=diversity, pool=candidate_pool, max_per_group=quotas,
+                                          return_distribution=calibrated, temperature=temperature)
+        ids, slots = got[0], got[2]
         P = int(batch["masked_lm_positions"].shape[1])
         first = {}
         for i, s in enumerate(slots.cpu().tolist()):   # __call__ ranks the first weighted slot of its one-row batch
             first.setdefault(s // P, i)
-        ids_h = ids.cpu().tolist()
+        prob_h = None
+        if calibrated:
+            # ids and probabilities in one copy: an id is exact in float64
+            both = torch.cat([ids.to(torch.float64), torch.exp(got[3]["logp"].to(torch.float64))], dim=1).cpu()
+            ids_h, prob_h = both[:, :ids.shape[1]].to(torch.int64).tolist(), both[:, ids.shape[1]:].tolist()
+        else:
+            ids_h = ids.cpu().tolist()
+        least = 0.0 if min_probability is None else float(min_probability)
         out = []
         for b in range(len(sequences)):
             top = [i for i in ids_h[first[b]] if i >= 0] if b in first else []
+            if prob_h is not None:
+                kept = [(i, p) for i, p in zip(ids_h[first[b]], prob_h[first[b]]) if i >= 0 and p >= least] if b in first else []
+                top = [i for i, _ in kept]
             items = tokenizer.detokenize(top)
+            if return_probabilities:
+                items = [(item, p) for item, (_, p) in zip(items, kept)]
             out.append((items[0] if items else None) if k == 1 else items)   # None: nothing is left to recommend (filtered or not)
         return out
 

@@ -158,6 +158,17 @@ def check_rank_full_args(k, exclude: Optional[torch.Tensor] = None, n_rows: Opti
     return k
 
 
+def check_temperature(temperature) -> float:
+    """Argument check of the softmax temperature that needs no GPU: a finite number > 0 whose inverse is finite and > 0 in fp32.
+    Returns b4r_score_dist's inv_temperature = fl32(1 / temperature)."""
+    if isinstance(temperature, bool) or not isinstance(temperature, numbers.Real) or not math.isfinite(temperature) or temperature <= 0:
+        raise ValueError(f"temperature must be a finite number > 0, got {temperature!r}")
+    inv = C.c_float(1.0 / float(temperature)).value
+    if not math.isfinite(inv) or inv <= 0.0:
+        raise ValueError(f"temperature {temperature!r} has no finite positive inverse in fp32")
+    return inv
+
+
 SIMILARITY_METRICS = {"dot": _lib.SIM_DOT, "cosine": _lib.SIM_COSINE}
 
 
@@ -833,6 +844,57 @@ class Engine:
             rf_d = None if row_filter is None else row_filter.to(self.device).contiguous()
             _lib.check(self.lib.b4r_rank_full_ex(*args, _ptr(allow_d), int(allow_d.shape[0]), _ptr(rf_d), None), "b4r_rank_full_ex")
         return ids, scores, gt_rank
+
+    def score_distribution(self, hidden: torch.Tensor, rows: Optional[torch.Tensor], exclude: Optional[torch.Tensor], first_item: int,
+                           gt: Optional[torch.Tensor], allow=None, row_filter=None, temperature: float = 1.0,
+                           query_ids: Optional[torch.Tensor] = None):
+        """b4r_score_dist on `hidden` (rank_full's hidden / rows / exclude / first_item / gt / allow / row_filter: the same scores and
+        the same allowed set): the softmax of every row's scores / temperature over its allowed items, without [R, V] scores.
+        query_ids [R, K] int64 (K <= 1024) or None.  Returns (n [R] int32, max [R] fp32, lse [R] fp64, entropy [R] fp64 in nats,
+        logp [R, K] fp32 or None): the allowed items, their largest scaled score, the log normaliser, the entropy and the log
+        probability of each queried id (-inf where the id is not allowed for the row).  A row without allowed items has n = 0,
+        max = lse = -inf, entropy = 0.  The scratch buffer is kept between calls."""
+        R = int(rows.numel()) if rows is not None else int(hidden.shape[0])
+        check_rank_full_args(0, exclude, R)
+        inv_t = check_temperature(temperature)
+        allow, row_filter = check_item_filter(allow, row_filter, self.cfg.vocab_size, R)
+        if hidden.dtype != torch.float32 or hidden.ndim != 2 or hidden.stride(1) != 1 or hidden.shape[1] != self.embedding_width:
+            raise ValueError(f"hidden must be float32 [rows, {self.embedding_width}] with unit column stride")
+        q_d, K = None, 0
+        if query_ids is not None:
+            q = torch.as_tensor(query_ids)
+            if q.ndim != 2 or q.shape[0] != R or q.dtype.is_floating_point or q.dtype == torch.bool:
+                raise ValueError(f"query_ids must be an integer tensor [{R}, K], got {q.dtype} of shape {tuple(q.shape)}")
+            K = check_rank_full_args(int(q.shape[1]))
+            q_d = q.to(device=self.device, dtype=torch.int64).contiguous()
+        rows_d = None if rows is None else rows.to(device=self.device, dtype=torch.int64).contiguous()
+        ex_d = None if exclude is None or exclude.shape[1] == 0 else exclude.to(device=self.device, dtype=torch.int64).contiguous()
+        E = 0 if ex_d is None else int(ex_d.shape[1])
+        gt_d = None if gt is None else gt.to(device=self.device, dtype=torch.int64).contiguous()
+        if gt_d is not None and gt_d.numel() != R:
+            raise ValueError(f"{gt_d.numel()} ground-truth ids for {R} rows")
+        n = torch.empty((R,), dtype=torch.int32, device=self.device)
+        mx = torch.empty((R,), dtype=torch.float32, device=self.device)
+        lse = torch.empty((R,), dtype=torch.float64, device=self.device)
+        ent = torch.empty((R,), dtype=torch.float64, device=self.device)
+        logp = None if q_d is None else torch.empty((R, K), dtype=torch.float32, device=self.device)
+        if R == 0:
+            return n, mx, lse, ent, logp
+        V = self.cfg.vocab_size
+        want = int(self.lib.b4r_score_dist_scratch_bytes(R, V))
+        sc = getattr(self, "_score_dist_scratch", None)
+        if sc is None or sc.numel() < want:
+            sc = self._score_dist_scratch = torch.empty(want, dtype=torch.uint8, device=self.device)
+        allow_d = None if allow is None else allow.to(self.device).contiguous()
+        rf_d = None if row_filter is None else row_filter.to(self.device).contiguous()
+        _lib.check(self.lib.b4r_score_dist(_ptr(hidden), hidden.stride(0), _ptr(rows_d), _ptr(self.view("word_embeddings/embeddings")),
+                                           _ptr(self.view("cls/predictions/output_bias/bias")), self.embedding_width, V,
+                                           int(first_item), R, _ptr(ex_d), E, _ptr(gt_d), _ptr(allow_d),
+                                           0 if allow_d is None else int(allow_d.shape[0]), _ptr(rf_d), None, inv_t,
+                                           _ptr(q_d) if K > 0 else None, K, _ptr(n), _ptr(mx), _ptr(lse), _ptr(ent),
+                                           _ptr(logp) if K > 0 else None, _ptr(sc), sc.numel(), _stream(self.device)),
+                   "b4r_score_dist")
+        return n, mx, lse, ent, logp
 
     def item_neighbours(self, item_ids: torch.Tensor, k: int, metric: str = "cosine", first_item: int = SPECIAL_IDS, allow=None,
                         row_filter=None):

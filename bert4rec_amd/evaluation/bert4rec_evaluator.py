@@ -20,7 +20,12 @@ list_k=k (with full_ranking) evaluates the top-k LISTS as well: the same b4r_ran
 and the row's best k items (or its best candidate_pool items, from which b4r_rerank_diverse picks k when diversity is a number), and
 one b4r_list_metrics call per batch adds the lists' intra-list distance, novelty and item exposure to device accumulators that are
 read back once per evaluate(), like the metric sums.  The results gain ILD@k, Novelty@k, Coverage@k and Gini@k.
-max_per_group (pack_item_groups specs) evaluates the lists b4r_rerank_quota picks from the pool under those caps."""
+max_per_group (pack_item_groups specs) evaluates the lists b4r_rerank_quota picks from the pool under those caps.
+
+distribution=True (with full_ranking) adds the likelihood view: one b4r_score_dist call per batch gives the log probability of every
+ground truth under the softmax over the items it was ranked against, and the row's entropy; their sums stay on the device and are
+read back once per evaluate().  The results gain NLL (the mean -log p of the ground truth), Perplexity (its exp) and Entropy (the
+mean row entropy, in nats)."""
 from typing import Union
 
 import numpy as np
@@ -57,8 +62,9 @@ def exposure_gini(exposure) -> float:
 class BERT4RecEvaluator(BaseEvaluator):
     def __init__(self, metrics: list = None, sampler: Union[str, "samplers.BaseSampler"] = "pop_random", dataloader=None,
                  device_sampling: bool = True, seed: int = 0, full_ranking: bool = False, list_k: int = None, diversity: float = None,
-                 candidate_pool: int = None, item_counts=None, max_per_group=None):
-        """list_k / diversity / candidate_pool / item_counts: list evaluation (the module docstring); with list_k=None, the default,
+                 candidate_pool: int = None, item_counts=None, max_per_group=None, distribution: bool = False):
+        """distribution: the likelihood view of the module docstring; it needs full_ranking=True and, like list_k, evaluates on one
+        rank only.  list_k / diversity / candidate_pool / item_counts: list evaluation (the module docstring); with list_k=None, the default,
         nothing changes.  list_k=k needs full_ranking=True.  diversity=None evaluates the sweep's own top k and takes the accuracy
         metrics from the full-catalogue rank, as without list_k; diversity=d in [0, 1] re-ranks the best candidate_pool items (default
         min(1024, max(10 k, 50))) and takes the accuracy metrics from the position of the ground truth in the re-ranked list (rank
@@ -69,6 +75,11 @@ class BERT4RecEvaluator(BaseEvaluator):
         None), and the accuracy metrics come from the position in the capped list under the same rule on cut-offs as with diversity."""
         self.device_sampling = device_sampling
         self.full_ranking = bool(full_ranking)
+        self.distribution = bool(distribution)
+        if self.distribution and not self.full_ranking:
+            raise ValueError("distribution evaluates the full-catalogue softmax: it needs full_ranking=True")
+        self._dist_dev = None      # (engine, float64 [2]: sum of -log p(gt), sum of the row entropies; int64 [1]: the rows)
+        self._dist_host = [0.0, 0.0, 0]
         if metrics is None:
             metrics = default_metrics()
         self.list_k = self._list_pool = None
@@ -131,6 +142,8 @@ class BERT4RecEvaluator(BaseEvaluator):
         if self.list_k is not None and world > 1:
             # the lists' sums and the exposure counts would have to be merged across the ranks: out of scope of the list evaluation
             raise ValueError("list_k evaluates on one rank only: the list sums are not merged across a process group")
+        if self.distribution and world > 1:
+            raise ValueError("distribution evaluates on one rank only: its sums are not merged across a process group")
         before = [m.partial() for m in self._metrics]
         for i, batch in enumerate(test_data):
             if i % world == rank:
@@ -162,6 +175,7 @@ class BERT4RecEvaluator(BaseEvaluator):
         raises, raise_on_short) when the sampler kernel flagged a row with fewer drawable items than the sample size: nothing of
         that evaluation is then folded in."""
         self._flush_list_sums()
+        self._flush_dist_sums()
         if self._dev is None:
             return False
         _, sums, users = self._dev
@@ -178,6 +192,33 @@ class BERT4RecEvaluator(BaseEvaluator):
         sums.zero_()
         users.zero_()
         return False
+
+    # ---- likelihood view (distribution) ----------------------------------------------------------------------------------------
+    def _dist_sums(self, engine):
+        if self._dist_dev is None or self._dist_dev[0] is not engine:
+            self._flush_dist_sums()
+            dev = engine.params.device
+            self._dist_dev = (engine, torch.zeros(2, dtype=torch.float64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev))
+        return self._dist_dev
+
+    def _flush_dist_sums(self) -> None:
+        """one device -> host copy of the likelihood accumulators per flush: [sum -log p, sum entropy, rows] as float64"""
+        if getattr(self, "_dist_dev", None) is None:
+            return
+        _, sums, rows = self._dist_dev
+        back = torch.cat([sums, rows.to(torch.float64)]).cpu().tolist()
+        h = self._dist_host
+        h[0] += back[0]; h[1] += back[1]; h[2] += int(back[2])
+        sums.zero_(); rows.zero_()
+
+    def distribution_results(self) -> dict:
+        """NLL, Perplexity and Entropy of everything evaluated since the last reset, over the rows with a rankable ground truth."""
+        if not self.distribution:
+            return {}
+        self._flush_dist_sums()
+        nll_sum, ent_sum, rows = self._dist_host
+        nll = nll_sum / rows if rows else 0.0
+        return {"NLL": nll, "Perplexity": float(np.exp(nll)), "Entropy": ent_sum / rows if rows else 0.0}
 
     # ---- list evaluation (list_k) ----------------------------------------------------------------------------------------------
     def _list_sums(self, engine):
@@ -375,6 +416,15 @@ class BERT4RecEvaluator(BaseEvaluator):
         gt = torch.as_tensor(test_batch["masked_lm_ids"]).to(dev)[b_idx, p_idx].to(torch.int64)
         exclude = torch.as_tensor(test_batch["labels"]).to(dev)[b_idx].to(torch.int64)   # the user's whole sequence
         hidden, _, _ = model._ranked_slot_hidden(test_batch, slots)
+        if self.distribution:
+            # the softmax over exactly the items the ground truth is ranked against; a ground truth that is no item has logp = -inf
+            _, dsums, drows = self._dist_sums(engine)
+            _, _, _, ent, logp = engine.score_distribution(hidden, None, exclude, SPECIAL_IDS, gt, query_ids=gt[:, None])
+            logp = logp[:, 0].to(torch.float64)
+            valid = torch.isfinite(logp)
+            zero = torch.zeros_like(logp)
+            dsums += torch.stack([torch.where(valid, -logp, zero).sum(), torch.where(valid, ent, zero).sum()])
+            drows += valid.sum()
         if self.list_k is None:
             _, _, gt_rank = engine.rank_full(hidden, None, exclude, SPECIAL_IDS, gt, 0)
         else:
@@ -408,6 +458,7 @@ class BERT4RecEvaluator(BaseEvaluator):
         self._flush_device_sums()
         results = super().get_metrics_results()
         results.update(self.list_results())
+        results.update(self.distribution_results())
         return results
 
     def reset_metrics(self) -> None:
@@ -420,6 +471,10 @@ class BERT4RecEvaluator(BaseEvaluator):
             for t in self._list_dev[1:4]:
                 t.zero_()
         self._list_host = None
+        if getattr(self, "_dist_dev", None) is not None:
+            self._dist_dev[1].zero_()
+            self._dist_dev[2].zero_()
+        self._dist_host = [0.0, 0.0, 0]
         super().reset_metrics()
 
 

@@ -8,6 +8,7 @@ The arithmetic runs in libb4r_hip.so (include/b4r.h); this class only sequences 
 (metric names and averaging rules, History, callbacks)."""
 from __future__ import annotations
 
+import numbers
 from typing import Any, Dict, Iterable, List, Optional, Sequence
 
 import numpy as np
@@ -324,7 +325,8 @@ class BERT4RecModel:
 
     def recommend_tensor(self, encoder_input: Dict[str, torch.Tensor], k: int = 10, exclude_seen: bool = True,
                          exclude: Optional[torch.Tensor] = None, allow=None, row_filter=None, diversity: Optional[float] = None,
-                         pool: Optional[int] = None, max_per_group=None):
+                         pool: Optional[int] = None, max_per_group=None, return_distribution: bool = False,
+                         temperature: float = 1.0):
         """Top k of the whole catalogue for every slot with masked_lm_weights == 1 (all slots when the key is absent), from one
         b4r_rank_full call: no [R, V] scores.  The forward is rank_items_tensor's (encoder, then tfm MaskedLM's transform on those
         slots only).  [PAD] / [MASK] / [UNK] are never recommended; exclude_seen drops the row's own input_word_ids; exclude
@@ -341,8 +343,15 @@ class BERT4RecModel:
         brand / ...".  The sweep returns the best `pool` allowed items of every row (the same default) and b4r_rerank_quota picks k of
         them greedily under the caps: in relevance order when diversity is None (lambda = 1), else by MMR as above.  A row whose pool
         holds fewer than k admissible items ends in -1 / -inf: there is no second, wider sweep (it would need a host
-        synchronisation); a larger `pool` is the remedy."""
+        synchronisation); a larger `pool` is the remedy.
+        return_distribution: a fourth value follows, score_distribution_tensor's dict for the same rows, exclusions and filter at
+        `temperature` (b4r_score_dist, one more sweep): its logp [R, k] holds the log probabilities of the ids returned,
+        after the re-ranking when one is on (-inf under the -1 tail).  ids and scores are the call's without it, bit for bit.
+        A temperature other than 1.0 without return_distribution raises ValueError."""
         k = engine_mod.check_rank_full_args(k, exclude)
+        if not return_distribution and not (isinstance(temperature, numbers.Real) and temperature == 1.0):
+            raise ValueError("temperature scales the returned distribution: give return_distribution=True as well")
+        engine_mod.check_temperature(temperature)
         n_sweep = k
         quotas = engine_mod.check_quota_args(max_per_group, self.vocab_size) if max_per_group is not None else None
         if quotas is not None:
@@ -355,7 +364,22 @@ class BERT4RecModel:
         hidden, slots, _ = self._ranked_slot_hidden(encoder_input)
         dev = self.device
         if hidden is None:
-            return (torch.empty((0, k), dtype=torch.int64, device=dev), torch.empty((0, k), dtype=torch.float32, device=dev), slots)
+            out = (torch.empty((0, k), dtype=torch.int64, device=dev), torch.empty((0, k), dtype=torch.float32, device=dev), slots)
+            return out + (self._distribution_dict(None, slots, k),) if return_distribution else out
+        ex_rows = self._excluded_rows(encoder_input, slots, exclude_seen, exclude)
+        ids, scores, _ = self.engine.rank_full(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, n_sweep, allow, row_filter)
+        if quotas is not None:
+            ids, scores, _, _ = self.engine.rerank_quota(ids, scores, k, 0.0 if diversity is None else diversity, quotas)
+        elif diversity is not None:
+            ids, scores, _ = self.engine.rerank_diverse(ids, scores, k, diversity)
+        if not return_distribution:
+            return ids, scores, slots
+        dist = self.engine.score_distribution(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, allow, row_filter, temperature, ids)
+        return ids, scores, slots, self._distribution_dict(dist, slots, k)
+
+    def _excluded_rows(self, encoder_input, slots: torch.Tensor, exclude_seen: bool, exclude) -> Optional[torch.Tensor]:
+        """The exclude list of every ranked slot [R, E]: the row's own input_word_ids (exclude_seen) and / or its row of `exclude`."""
+        dev = self.device
         P = int(torch.as_tensor(encoder_input["masked_lm_positions"]).shape[1])
         b_idx = torch.div(slots, P, rounding_mode="floor")
         parts = []
@@ -367,13 +391,41 @@ class BERT4RecModel:
             if ex.shape[0] != B:
                 raise ValueError(f"exclude has {ex.shape[0]} rows for a batch of {B}")
             parts.append(ex[b_idx])
-        ex_rows = torch.cat(parts, dim=1) if parts else None
-        ids, scores, _ = self.engine.rank_full(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, n_sweep, allow, row_filter)
-        if quotas is not None:
-            ids, scores, _, _ = self.engine.rerank_quota(ids, scores, k, 0.0 if diversity is None else diversity, quotas)
-        elif diversity is not None:
-            ids, scores, _ = self.engine.rerank_diverse(ids, scores, k, diversity)
-        return ids, scores, slots
+        return torch.cat(parts, dim=1) if parts else None
+
+    def _distribution_dict(self, dist, slots: torch.Tensor, K: Optional[int]) -> Dict[str, torch.Tensor]:
+        """Engine.score_distribution's tuple (None: no ranked slot) as score_distribution_tensor's dict"""
+        dev = self.device
+        if dist is None:
+            n = torch.empty((0,), dtype=torch.int32, device=dev)
+            lse = ent = torch.empty((0,), dtype=torch.float64, device=dev)
+            logp = None if K is None else torch.empty((0, K), dtype=torch.float32, device=dev)
+        else:
+            n, _, lse, ent, logp = dist
+        return {"n": n, "lse": lse, "entropy": ent, "perplexity": torch.exp(ent), "logp": logp, "slot_index": slots}
+
+    def score_distribution_tensor(self, encoder_input: Dict[str, torch.Tensor], query_ids=None, exclude_seen: bool = True,
+                                  exclude: Optional[torch.Tensor] = None, allow=None, row_filter=None, temperature: float = 1.0):
+        """The softmax over the catalogue each ranked slot could have been served -- recommend_tensor's forward, exclusions
+        (exclude_seen, exclude; [PAD] / [MASK] / [UNK] never count) and filter (allow, row_filter) -- from one b4r_score_dist call: no
+        [R, V] scores.  The scores are divided by `temperature` (finite, > 0).  query_ids [R, K] int64 (K <= 1024) or None: the items
+        whose log probability is wanted, one list per ranked slot.  Returns a dict of device tensors, one entry per ranked slot:
+          n           int32: the items the slot could have been served
+          lse         float64: the log normaliser of the scaled scores
+          entropy     float64: the entropy of the distribution in nats (0 where n = 0)
+          perplexity  float64: exp(entropy), between 1 (one item holds all the mass) and n (uniform)
+          logp        float32 [R, K]: the log probability of each queried id, -inf where the slot could not be served it (None
+                      without query_ids)
+          slot_index  int64: b*P+p, as recommend_tensor returns it."""
+        engine_mod.check_temperature(temperature)
+        allow, row_filter = engine_mod.check_item_filter(allow, row_filter, self.vocab_size)
+        hidden, slots, _ = self._ranked_slot_hidden(encoder_input)
+        if hidden is None:
+            return self._distribution_dict(None, slots, None if query_ids is None else int(torch.as_tensor(query_ids).shape[-1]))
+        ex_rows = self._excluded_rows(encoder_input, slots, exclude_seen, exclude)
+        dist = self.engine.score_distribution(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, allow, row_filter, temperature,
+                                              query_ids)
+        return self._distribution_dict(dist, slots, None)
 
     def list_metrics_tensor(self, ids: torch.Tensor, ground_truth: Optional[torch.Tensor] = None,
                             item_weight: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
@@ -403,15 +455,23 @@ class BERT4RecModel:
         return self.engine.item_neighbours(item_ids, k, metric, engine_mod.SPECIAL_IDS, allow, row_filter)
 
     def recommend(self, encoder_input: dict, k: int = 10, exclude_seen: bool = True, exclude=None, diversity: Optional[float] = None,
-                  pool: Optional[int] = None, max_per_group=None):
-        """recommend_tensor as Python lists: per batch row, one list per ranked slot of (ids, scores) lists of length k."""
-        ids, scores, slots = self.recommend_tensor(encoder_input, k, exclude_seen, exclude, diversity=diversity, pool=pool,
-                                                   max_per_group=max_per_group)
+                  pool: Optional[int] = None, max_per_group=None, return_distribution: bool = False,
+                  temperature: float = 1.0):
+        """recommend_tensor as Python lists: per batch row, one list per ranked slot of (ids, scores) lists of length k.
+        return_distribution: the entries are (ids, scores, log probabilities) instead, and recommend_tensor's dict follows as a second
+        return value (device tensors)."""
+        got = self.recommend_tensor(encoder_input, k, exclude_seen, exclude, diversity=diversity, pool=pool,
+                                    max_per_group=max_per_group, return_distribution=return_distribution, temperature=temperature)
+        ids, scores, slots = got[:3]
         B, P = (int(x) for x in torch.as_tensor(encoder_input["masked_lm_positions"]).shape)
         out = [[] for _ in range(B)]
-        for s, i_row, s_row in zip(slots.cpu().tolist(), ids.cpu().tolist(), scores.cpu().tolist()):
-            out[s // P].append((i_row, s_row))
-        return out
+        if not return_distribution:
+            for s, i_row, s_row in zip(slots.cpu().tolist(), ids.cpu().tolist(), scores.cpu().tolist()):
+                out[s // P].append((i_row, s_row))
+            return out
+        for s, i_row, s_row, p_row in zip(slots.cpu().tolist(), ids.cpu().tolist(), scores.cpu().tolist(), got[3]["logp"].cpu().tolist()):
+            out[s // P].append((i_row, s_row, p_row))
+        return out, got[3]
 
     def _rank_items_ragged(self, encoder_input, items):
         """Candidate lists of different lengths: one kernel call per distinct length."""

@@ -419,6 +419,32 @@ int b4r_list_metrics(const float* table, int32_t ld, int32_t width, int32_t V, i
                      const int64_t* list_ids, int32_t R, int32_t K, const int64_t* gt, const float* item_weight, int32_t* row_n,
                      int64_t* row_dist, int64_t* row_nov, int32_t* hit_pos, int64_t* exposure, double* sums, int64_t* counts,
                      void* scratch, int64_t scratch_bytes, b4r_stream_t stream);
+/* The catalogue softmax of every row over the items it could have been served, without an [R, V] buffer: normaliser, entropy and
+ * the log probability of queried items.  The first 12 arguments and allow_bits / n_filters / row_filter / item_scale are
+ * b4r_rank_full_ex's, and so are s(r, j) (bit for bit; bias may be NULL) and allowed(r) (gt[r] stays allowed when listed or filtered).
+ *   t(r, j)        = fl32(s(r, j) * inv_temperature), one fp32 multiply; inv_temperature finite and > 0 (else B4R_E_BADARG).
+ *   row_n[r]       int32: |allowed(r)|
+ *   row_max[r]     float: max of t over allowed(r)
+ *   row_lse[r]     double: log sum_{j in allowed(r)} exp(t(r, j))
+ *   row_entropy[r] double: -sum p log p of p_j = exp(t_j - lse), in nats
+ *   query_logp[r][i]  float [R, K]: fl32((double) t(r, q) - row_lse[r]) for q = query_ids[r][i] in allowed(r), else -inf (ids outside
+ *                  [first_item, V), excluded ids, filtered ids).  K in [0, 1024]; query_ids may be NULL when K = 0 or query_logp is NULL.
+ *   empty row      row_n = 0: row_max = -inf, row_lse = -inf, row_entropy = 0, every query_logp = -inf.  No NaN.
+ * Arithmetic: per (row, chunk of 1024 ids) m_c = max t, x_j = fl32(t_j - m_c), e_j = expf(x_j), S_c = sum (double) e_j,
+ * W_c = sum (double) e_j (double) x_j; per row m = max m_c, f_c = exp((double) m_c - m), S = sum S_c f_c,
+ * W = sum (W_c + (m_c - m) S_c) f_c over the chunks that hold an allowed id; row_lse = m + log S, row_entropy = log S - W / S.  All
+ * sums run in fp64 in a fixed order (no floating-point atomics): bitwise reproducible.  With fp64 sums the error is the fp32
+ * exponential's and the rounding of x: |lse error| <= 2^-21 + 2^-24 ln n for an exponential good to 3 ulp.
+ * Any output may be NULL.  scratch: b4r_score_dist_scratch_bytes(R, V) bytes for one pass over all rows (24 bytes per row and
+ * chunk); a smaller one processes the rows in groups of 16, and one too small for a group returns B4R_E_NOMEM.  Every check happens
+ * before any launch.  Only enqueues (two launches per group, three with queries; one stream, no host sync, graph-capturable).
+ * Non-finite hidden values are outside the contract (they are never read out of bounds). */
+int64_t b4r_score_dist_scratch_bytes(int32_t R, int32_t V);
+int b4r_score_dist(const float* hidden, int32_t hidden_ld, const int64_t* hidden_row, const float* table, const float* bias, int32_t H,
+                   int32_t V, int32_t first_item, int32_t R, const int64_t* exclude, int32_t E, const int64_t* gt,
+                   const uint32_t* allow_bits, int32_t n_filters, const int32_t* row_filter, const float* item_scale,
+                   float inv_temperature, const int64_t* query_ids, int32_t K, int32_t* row_n, float* row_max, double* row_lse,
+                   double* row_entropy, float* query_logp, void* scratch, int64_t scratch_bytes, b4r_stream_t stream);
 /* replaces the metric loop of bert4rec_evaluator.py:118-120 over evaluation_metrics.py:47-112 for a batch of ranks:
  * gain_sums[m] += sum over gt_rank[i] > 0 of gain_m(gt_rank[i]), users[0] += #{gt_rank[i] > 0}; double / int64 DEVICE
  * accumulators the caller reads once per evaluate().  family[m]: 0 count (gain 1), 1 hit@cutoff (rank <= k), 2 NDCG@cutoff
