@@ -30,6 +30,7 @@ import numbers
 import numpy as np
 import torch
 
+from .. import engine as engine_mod
 from ..engine import SPECIAL_IDS, _as_cap, item_self_information, pack_item_groups
 
 
@@ -123,7 +124,7 @@ class Recommender:
 
     def recommend_batch(self, sequences, k: int = 1, allowed_items=None, allowed_items_per_user=None, diversity=None,
                         candidate_pool=None, max_per_group=None, return_probabilities: bool = False, min_probability=None,
-                        temperature: float = 1.0) -> list:
+                        temperature: float = 1.0, sample_seed=None, user_streams=None) -> list:
         """Recommender(...)(seq, k) for every sequence of `sequences`, from one batched forward and one full-catalogue top-k.
         allowed_items: one iterable of items (detokenized values) for all users; allowed_items_per_user: one iterable per sequence
         (identical lists share one filter).  Only allowed items are recommended; items the vocabulary does not know are ignored.
@@ -137,13 +138,30 @@ class Recommender:
         return_probabilities: every entry is an (item, probability) pair instead of an item: the softmax of the scores / temperature
         over the items the user could have been served (the seen items and the filter applied), for the items actually returned.
         min_probability: a number in [0, 1]; entries with a smaller probability are dropped (the rest keep their order), and a k = 1
-        user left with nothing gets None.  temperature (finite, > 0) needs one of the two.  Still one read-back of the lists per call."""
+        user left with nothing gets None.  temperature (finite, > 0) needs one of the two, or sample_seed.  Still one read-back of
+        the lists per call.
+        sample_seed: None = the k best items; an integer in [0, 2^64) = the k items are DRAWN without replacement from the softmax of
+        the scores / temperature over the items the user could be served (b4r_sample_full), or over the candidate_pool best of them
+        when candidate_pool is given (b4r_sample_pool), and returned in draw order: exploration traffic, propensity-logged lists.
+        user_streams: one integer per sequence (a user id, a request counter): the user's noise stream, so that a user draws the
+        same list under the same seed whatever batch they ride in (None: the position in the batch).  return_probabilities gives the
+        probability of each drawn item over everything the user could be served (also when candidate_pool truncates the draw).  It
+        does not combine with diversity or max_per_group."""
         calibrated = bool(return_probabilities) or min_probability is not None
+        sampled = sample_seed is not None
+        if sampled:
+            sample_seed = engine_mod.check_sample_seed(sample_seed)
+            if diversity is not None or max_per_group is not None:
+                raise ValueError("sample_seed does not combine with diversity or max_per_group")
+        if user_streams is not None:
+            if not sampled:
+                raise ValueError("user_streams are the noise streams of a sampled call: give sample_seed as well")
+            user_streams = engine_mod.check_sample_streams(user_streams)
         if min_probability is not None:
             if isinstance(min_probability, bool) or not isinstance(min_probability, numbers.Real) or not 0.0 <= min_probability <= 1.0:
                 raise ValueError(f"min_probability must be a number in [0, 1], got {min_probability!r}")
-        if not calibrated and not (isinstance(temperature, numbers.Real) and temperature == 1.0):
-            raise ValueError("temperature scales the probabilities: give return_probabilities or min_probability as well")
+        if not calibrated and not sampled and not (isinstance(temperature, numbers.Real) and temperature == 1.0):
+            raise ValueError("temperature scales the probabilities: give return_probabilities, min_probability or sample_seed as well")
         tokenizer = self.dataloader.get_tokenizer()
         sequences = [list(seq) for seq in sequences]
         if allowed_items is not None and allowed_items_per_user is not None:
@@ -177,9 +195,16 @@ class Recommender:
             # one filter index per ranked slot: the slots of recommend_tensor are those with masked_lm_weights != 0, in batch order
             w = batch["masked_lm_weights"] != 0
             row_filter = torch.as_tensor(user_filter, dtype=torch.int32)[torch.nonzero(w, as_tuple=True)[0]]
+        slot_streams = None
+        if user_streams is not None:
+            if user_streams.numel() != len(sequences):
+                raise ValueError(f"{user_streams.numel()} user streams for {len(sequences)} sequences")
+            # one stream per ranked slot, as row_filter above
+            slot_streams = user_streams[torch.nonzero(batch["masked_lm_weights"] != 0, as_tuple=True)[0]]
         got = self.model.recommend_tensor(batch, k=k, exclude_seen=False, exclude=exclude, allow=allow, row_filter=row_filter,
                                           diversity=diversity, pool=candidate_pool, max_per_group=quotas,
-                                          return_distribution=calibrated, temperature=temperature)
+                                          return_distribution=calibrated, temperature=temperature, sample_seed=sample_seed,
+                                          sample_streams=slot_streams)
         ids, slots = got[0], got[2]
         P = int(batch["masked_lm_positions"].shape[1])
         first = {}

@@ -110,7 +110,7 @@ static inline DropArgs b4r_make_drop(const uint32_t* rng, uint32_t stream, float
   return d;
 }
 
-__device__ __forceinline__ uint32_t b4r_hash32(uint32_t x) {
+__host__ __device__ __forceinline__ uint32_t b4r_hash32(uint32_t x) {
   x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
   return x;
 }
@@ -120,6 +120,48 @@ __device__ __forceinline__ uint32_t b4r_hash32(uint32_t x) {
 // Restates python's random.random() in [0, 1) (dataloader_utils.py:245-253) and numpy's uniform for the Gumbel keys.
 __host__ __device__ __forceinline__ float b4r_uniform23(uint32_t h) {
   return ((float)(h >> 9) + 0.5f) * (1.0f / 8388608.0f);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Gumbel noise of the sampled recommendations (b4r_sample_full / b4r_sample_pool, include/b4r.h), the same bits on the host and on
+// the device.  logf / log differ between the device library and libm, so the value is a fixed sequence of individually rounded
+// IEEE fp64 operations: no libm, no contraction (`fp contract(off)`: hipcc would fuse a * b + c otherwise), the two divisions
+// correctly rounded.  Restated in tests/sample_ref.py.
+// ---------------------------------------------------------------------------------------------
+// the hash word of item `id` in noise stream `stream` under `seed`
+__host__ __device__ __forceinline__ uint32_t b4r_sample_word_hd(uint64_t seed, int64_t stream, int64_t id) {
+  uint32_t h = b4r_hash32((uint32_t)(uint64_t)id ^ (uint32_t)seed);
+  h = b4r_hash32((h ^ (uint32_t)(uint64_t)stream) + (uint32_t)(seed >> 32));
+  return b4r_hash32(h ^ (uint32_t)((uint64_t)stream >> 32));
+}
+
+// ln x of a positive normal x: x = 2^e m with m in [1/sqrt2, sqrt2), s = (m - 1) / (m + 1), ln m = 2 s (1 + s^2 / 3 + .. + s^14 / 15)
+// (|s| <= 0.1716: the first dropped term is below 2e-15 relative to 2 s)
+__host__ __device__ __forceinline__ double b4r_xln(double x) {
+#pragma clang fp contract(off)
+  const uint64_t b = __builtin_bit_cast(uint64_t, x);
+  int e = (int)(b >> 52) - 1023;
+  double m = __builtin_bit_cast(double, (b & 0x000FFFFFFFFFFFFFull) | 0x3FF0000000000000ull);
+  if (m > 1.4142135623730951) { m = m * 0.5; e += 1; }
+  const double s = (m - 1.0) / (m + 1.0);
+  const double z = s * s;
+  double p = 1.0 / 15.0;
+  p = p * z + 1.0 / 13.0;
+  p = p * z + 1.0 / 11.0;
+  p = p * z + 1.0 / 9.0;
+  p = p * z + 1.0 / 7.0;
+  p = p * z + 1.0 / 5.0;
+  p = p * z + 1.0 / 3.0;
+  p = p * z + 1.0;
+  return (double)e * 0.6931471805599453 + (2.0 * s) * p;
+}
+
+// g = fl32(-ln(-ln u)), u = b4r_uniform23's value (exact in fp64): within 3.9e-14 of libm's fp64 value before the rounding to fp32,
+// in [-2.8115408, 16.635532], distinct for the 2^23 distinct u
+__host__ __device__ __forceinline__ float b4r_gumbel23(uint32_t h) {
+#pragma clang fp contract(off)
+  const double u = ((double)(h >> 9) + 0.5) * (1.0 / 8388608.0);
+  return (float)(0.0 - b4r_xln(0.0 - b4r_xln(u)));
 }
 
 struct DropCtx {

@@ -169,6 +169,57 @@ def check_temperature(temperature) -> float:
     return inv
 
 
+def check_sample_seed(seed) -> int:
+    """Argument check of a sampling seed that needs no GPU: an integer in [0, 2^64)."""
+    if isinstance(seed, bool):
+        raise ValueError(f"sample_seed must be an integer in [0, 2^64), got {seed!r}")
+    try:
+        seed = operator.index(seed)
+    except TypeError:
+        raise ValueError(f"sample_seed must be an integer in [0, 2^64), got {seed!r}") from None
+    if seed < 0 or seed >= 1 << 64:
+        raise ValueError(f"sample_seed must lie in [0, 2^64), got {seed}")
+    return seed
+
+
+def check_sample_streams(streams, n_rows: Optional[int] = None) -> Optional[torch.Tensor]:
+    """Argument check of the per-row noise streams that needs no GPU: None, or [R] integers (int64 after the conversion)."""
+    if streams is None:
+        return None
+    t = torch.as_tensor(streams)
+    if t.ndim != 1 or t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError(f"sample streams are one integer per row, got {t.dtype} of shape {tuple(t.shape)}")
+    if n_rows is not None and t.numel() != n_rows:
+        raise ValueError(f"{t.numel()} sample streams for {n_rows} rows")
+    return t.to(torch.int64)
+
+
+def check_stream0(stream0) -> int:
+    """The first row's stream when none are given: an integer, wrapped to int64 as the library wraps stream0 + r."""
+    if isinstance(stream0, bool):
+        raise ValueError(f"stream0 must be an integer, got {stream0!r}")
+    try:
+        stream0 = operator.index(stream0)
+    except TypeError:
+        raise ValueError(f"stream0 must be an integer, got {stream0!r}") from None
+    stream0 &= (1 << 64) - 1
+    return stream0 - (1 << 64) if stream0 >= 1 << 63 else stream0
+
+
+def check_sample_pool_args(k, pool) -> Tuple[int, int]:
+    """Argument checks of truncated sampling that need no GPU: pool an integer in [1, 1024], k in [0, pool]."""
+    k = check_rank_full_args(k)
+    try:
+        pool = operator.index(pool)
+    except TypeError:
+        raise ValueError(f"pool must be an integer, got {pool!r}") from None
+    if pool < 1 or pool > RANK_FULL_MAX_K:
+        raise ValueError(f"pool must lie in [1, {RANK_FULL_MAX_K}], got {pool}")
+    if k > pool:
+        raise ValueError(f"k = {k} items cannot be drawn from a pool of {pool}")
+    return k, pool
+
+
 SIMILARITY_METRICS = {"dot": _lib.SIM_DOT, "cosine": _lib.SIM_COSINE}
 
 
@@ -895,6 +946,81 @@ class Engine:
                                            _ptr(logp) if K > 0 else None, _ptr(sc), sc.numel(), _stream(self.device)),
                    "b4r_score_dist")
         return n, mx, lse, ent, logp
+
+    def sample_full(self, hidden: torch.Tensor, rows: Optional[torch.Tensor], exclude: Optional[torch.Tensor], first_item: int,
+                    gt: Optional[torch.Tensor], k: int, seed: int, allow=None, row_filter=None, temperature: float = 1.0,
+                    streams=None, stream0: int = 0):
+        """b4r_sample_full on `hidden` (rank_full's hidden / rows / exclude / first_item / gt / allow / row_filter: the same scores and
+        the same allowed set): k items of every row drawn without replacement from softmax(scores / temperature) over its allowed
+        items, in draw order, without [R, V] scores.  seed: an integer in [0, 2^64); streams [R] int64: the noise stream of each row
+        (None: stream0 + row).  The same (seed, stream) draws the same list whatever else the call holds.  Returns (ids [R,k] int64,
+        scores [R,k] fp32: rank_full's bits for those ids, keys [R,k] fp32: score / temperature + Gumbel noise, descending), -1 /
+        -inf / -inf where fewer than k are allowed.  The scratch buffer is kept between calls."""
+        R = int(rows.numel()) if rows is not None else int(hidden.shape[0])
+        k = check_rank_full_args(k, exclude, R)
+        seed = check_sample_seed(seed)
+        inv_t = check_temperature(temperature)
+        streams = check_sample_streams(streams, R)
+        stream0 = check_stream0(stream0)
+        allow, row_filter = check_item_filter(allow, row_filter, self.cfg.vocab_size, R)
+        if hidden.dtype != torch.float32 or hidden.ndim != 2 or hidden.stride(1) != 1 or hidden.shape[1] != self.embedding_width:
+            raise ValueError(f"hidden must be float32 [rows, {self.embedding_width}] with unit column stride")
+        rows_d = None if rows is None else rows.to(device=self.device, dtype=torch.int64).contiguous()
+        ex_d = None if exclude is None or exclude.shape[1] == 0 else exclude.to(device=self.device, dtype=torch.int64).contiguous()
+        E = 0 if ex_d is None else int(ex_d.shape[1])
+        gt_d = None if gt is None else gt.to(device=self.device, dtype=torch.int64).contiguous()
+        if gt_d is not None and gt_d.numel() != R:
+            raise ValueError(f"{gt_d.numel()} ground-truth ids for {R} rows")
+        ids = torch.empty((R, k), dtype=torch.int64, device=self.device)
+        scores = torch.empty((R, k), dtype=torch.float32, device=self.device)
+        keys = torch.empty((R, k), dtype=torch.float32, device=self.device)
+        if R == 0 or k == 0:
+            return ids, scores, keys
+        V = self.cfg.vocab_size
+        need = int(self.lib.b4r_sample_full_scratch_bytes(R, V, k))
+        least = int(self.lib.b4r_sample_full_scratch_bytes(min(R, 16), V, k))
+        want = min(need, max(least, 2 << 30))   # at most 2 GiB: more rows are then drawn in groups
+        sc = getattr(self, "_sample_full_scratch", None)
+        if sc is None or sc.numel() < want:
+            sc = self._sample_full_scratch = torch.empty(want, dtype=torch.uint8, device=self.device)
+        allow_d = None if allow is None else allow.to(self.device).contiguous()
+        rf_d = None if row_filter is None else row_filter.to(self.device).contiguous()
+        st_d = None if streams is None else streams.to(self.device).contiguous()
+        _lib.check(self.lib.b4r_sample_full(_ptr(hidden), hidden.stride(0), _ptr(rows_d), _ptr(self.view("word_embeddings/embeddings")),
+                                            _ptr(self.view("cls/predictions/output_bias/bias")), self.embedding_width, V,
+                                            int(first_item), R, _ptr(ex_d), E, _ptr(gt_d), k, _ptr(allow_d),
+                                            0 if allow_d is None else int(allow_d.shape[0]), _ptr(rf_d), None, inv_t, seed, _ptr(st_d),
+                                            stream0, _ptr(ids), _ptr(scores), _ptr(keys), _ptr(sc), sc.numel(), _stream(self.device)),
+                   "b4r_sample_full")
+        return ids, scores, keys
+
+    def sample_pool(self, pool_ids: torch.Tensor, pool_scores: torch.Tensor, k: int, seed: int, temperature: float = 1.0, streams=None,
+                    stream0: int = 0):
+        """b4r_sample_pool: k items of every row drawn without replacement from softmax(pool_scores / temperature) over the live
+        entries of the pool [R, M] (rank_full's output: -1 / -inf where a row has fewer), in draw order.  The noise goes by the item
+        id: with the same seed and stream, a pool that holds every allowed item gives sample_full's lists.  Returns (ids [R,k] int64,
+        scores [R,k] fp32: the pool scores of the picks, keys [R,k] fp32, pos [R,k] int32: the pool position of every pick), -1 /
+        -inf / -inf / -1 where a row has fewer than k live entries."""
+        if pool_ids.ndim != 2 or pool_ids.dtype != torch.int64 or pool_scores.dtype != torch.float32 or pool_scores.shape != pool_ids.shape:
+            raise ValueError(f"the pool is ids int64 [R, M] and scores float32 [R, M], got {pool_ids.dtype} {tuple(pool_ids.shape)} and "
+                             f"{pool_scores.dtype} {tuple(pool_scores.shape)}")
+        R, M = (int(x) for x in pool_ids.shape)
+        k, _ = check_sample_pool_args(k, M)
+        seed = check_sample_seed(seed)
+        inv_t = check_temperature(temperature)
+        streams = check_sample_streams(streams, R)
+        stream0 = check_stream0(stream0)
+        ids_d, sc_d = pool_ids.to(self.device).contiguous(), pool_scores.to(self.device).contiguous()
+        st_d = None if streams is None else streams.to(self.device).contiguous()
+        ids = torch.empty((R, k), dtype=torch.int64, device=self.device)
+        scores = torch.empty((R, k), dtype=torch.float32, device=self.device)
+        keys = torch.empty((R, k), dtype=torch.float32, device=self.device)
+        pos = torch.empty((R, k), dtype=torch.int32, device=self.device)
+        if R == 0 or k == 0:
+            return ids, scores, keys, pos
+        _lib.check(self.lib.b4r_sample_pool(_ptr(ids_d), _ptr(sc_d), R, M, self.cfg.vocab_size, inv_t, seed, _ptr(st_d), stream0, k,
+                                            _ptr(ids), _ptr(scores), _ptr(keys), _ptr(pos), _stream(self.device)), "b4r_sample_pool")
+        return ids, scores, keys, pos
 
     def item_neighbours(self, item_ids: torch.Tensor, k: int, metric: str = "cosine", first_item: int = SPECIAL_IDS, allow=None,
                         row_filter=None):

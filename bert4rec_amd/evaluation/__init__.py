@@ -8,7 +8,7 @@ evaluators_map = {"bert4rec": BERT4RecEvaluator}
 
 def get(identifier: str = "bert4rec", **kwargs) -> BaseEvaluator:
     """kwargs go to the evaluator: metrics, sampler, dataloader, device_sampling, seed, full_ranking, and the list evaluation's list_k,
-    diversity, candidate_pool, item_counts and max_per_group, and distribution (BERT4RecEvaluator)."""
+    diversity, candidate_pool, item_counts, max_per_group, sample_seed and temperature, and distribution (BERT4RecEvaluator)."""
     if identifier in evaluators_map:
         return evaluators_map[identifier](**kwargs)
     raise ValueError(f"{identifier} is not known!")

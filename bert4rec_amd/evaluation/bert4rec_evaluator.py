@@ -21,6 +21,9 @@ and the row's best k items (or its best candidate_pool items, from which b4r_rer
 one b4r_list_metrics call per batch adds the lists' intra-list distance, novelty and item exposure to device accumulators that are
 read back once per evaluate(), like the metric sums.  The results gain ILD@k, Novelty@k, Coverage@k and Gini@k.
 max_per_group (pack_item_groups specs) evaluates the lists b4r_rerank_quota picks from the pool under those caps.
+sample_seed=s (with list_k) evaluates SAMPLED lists: k items drawn without replacement from softmax(scores / temperature) over the
+items the ground truth is ranked against (b4r_sample_full), or over the best candidate_pool of them (b4r_sample_pool) -- what
+exploration costs in HR / NDCG and what it buys in ILD, coverage, Gini and novelty.
 
 distribution=True (with full_ranking) adds the likelihood view: one b4r_score_dist call per batch gives the log probability of every
 ground truth under the softmax over the items it was ranked against, and the row's entropy; their sums stay on the device and are
@@ -32,7 +35,8 @@ import numpy as np
 import torch
 
 from ..dataloaders import samplers
-from ..engine import SPECIAL_IDS, check_quota_args, check_rank_full_args, check_rerank_args, item_self_information
+from ..engine import (SPECIAL_IDS, check_quota_args, check_rank_full_args, check_rerank_args, check_sample_pool_args, check_sample_seed,
+                      check_temperature, item_self_information)
 from .base_evaluator import BaseEvaluator
 from .evaluation_metrics import GAIN_COUNT, GAIN_HIT, GAIN_NDCG, HR, MAP, NDCG, Counter, EvaluationMetric, gain_table
 
@@ -62,7 +66,8 @@ def exposure_gini(exposure) -> float:
 class BERT4RecEvaluator(BaseEvaluator):
     def __init__(self, metrics: list = None, sampler: Union[str, "samplers.BaseSampler"] = "pop_random", dataloader=None,
                  device_sampling: bool = True, seed: int = 0, full_ranking: bool = False, list_k: int = None, diversity: float = None,
-                 candidate_pool: int = None, item_counts=None, max_per_group=None, distribution: bool = False):
+                 candidate_pool: int = None, item_counts=None, max_per_group=None, distribution: bool = False, sample_seed: int = None,
+                 temperature: float = 1.0):
         """distribution: the likelihood view of the module docstring; it needs full_ranking=True and, like list_k, evaluates on one
         rank only.  list_k / diversity / candidate_pool / item_counts: list evaluation (the module docstring); with list_k=None, the default,
         nothing changes.  list_k=k needs full_ranking=True.  diversity=None evaluates the sweep's own top k and takes the accuracy
@@ -72,7 +77,13 @@ class BERT4RecEvaluator(BaseEvaluator):
         interaction count per token id [V] for Novelty@k; None takes the counts of the dataloader's tokenized item list, and without a
         dataloader Novelty@k is not reported.  max_per_group: one bert4rec_amd.apps.pack_item_groups spec or a list of at most 4:
         the lists are picked from the candidate_pool best under those caps (b4r_rerank_quota; in relevance order when diversity is
-        None), and the accuracy metrics come from the position in the capped list under the same rule on cut-offs as with diversity."""
+        None), and the accuracy metrics come from the position in the capped list under the same rule on cut-offs as with diversity.
+        sample_seed: None = the deterministic lists; an integer in [0, 2^64) (with list_k) = every list is k items drawn without
+        replacement from softmax(scores / temperature) over the row's allowed items, or over its best candidate_pool items when
+        candidate_pool is given.  The accuracy metrics come from the position of the ground truth in the sampled list (the same rule on
+        cut-offs as with diversity).  The noise stream of a row is the number of rows evaluated before it since the last
+        reset_metrics(), so batches draw independent noise and an evaluation repeats bit for bit.  It does not combine with diversity or
+        max_per_group; temperature (finite, > 0) needs sample_seed."""
         self.device_sampling = device_sampling
         self.full_ranking = bool(full_ranking)
         self.distribution = bool(distribution)
@@ -84,6 +95,18 @@ class BERT4RecEvaluator(BaseEvaluator):
             metrics = default_metrics()
         self.list_k = self._list_pool = None
         self.diversity = diversity
+        self.sample_seed = None if sample_seed is None else check_sample_seed(sample_seed)
+        self.temperature = temperature
+        self._sample_pool = None
+        self._sample_rows = 0      # rows drawn so far: the next batch's stream0
+        check_temperature(temperature)
+        if self.sample_seed is None and not (isinstance(temperature, (int, float)) and temperature == 1.0):
+            raise ValueError("temperature scales the distribution the lists are drawn from: give sample_seed as well")
+        if self.sample_seed is not None:
+            if list_k is None:
+                raise ValueError("sample_seed evaluates sampled lists: give list_k (and full_ranking=True) as well")
+            if diversity is not None or max_per_group is not None:
+                raise ValueError("sample_seed does not combine with diversity or max_per_group")
         self._item_counts = item_counts
         self._quotas = None
         self._list_dev = None      # (engine, exposure int64 [V], sums float64 [2], counts int64 [2], item weight fp32 [V] or None)
@@ -108,8 +131,16 @@ class BERT4RecEvaluator(BaseEvaluator):
                     if not (m.family == GAIN_COUNT or (m.family in (GAIN_HIT, GAIN_NDCG) and 1 <= m.cutoff <= k)):
                         raise ValueError(f"metric {m.name} looks beyond the first {k} ranks, which a re-ranked list of {k} items does "
                                          f"not have: with diversity or max_per_group every metric must be a counter or have a cut-off of at most list_k")
+            elif self.sample_seed is not None:
+                if candidate_pool is not None:
+                    k, pool = check_sample_pool_args(k, candidate_pool)
+                    self._sample_pool = pool
+                for m in metrics:
+                    if not (m.family == GAIN_COUNT or (m.family in (GAIN_HIT, GAIN_NDCG) and 1 <= m.cutoff <= k)):
+                        raise ValueError(f"metric {m.name} looks beyond the first {k} ranks, which a sampled list of {k} items does "
+                                         f"not have: with sample_seed every metric must be a counter or have a cut-off of at most list_k")
             elif candidate_pool is not None:
-                raise ValueError("candidate_pool is the candidate count of the re-ranking: give diversity or max_per_group as well")
+                raise ValueError("candidate_pool is the candidate count of the re-ranking: give diversity, max_per_group or sample_seed as well")
             if len(metrics) > 32:
                 raise ValueError("the list evaluation accumulates on the device: at most 32 metrics")
             self.list_k, self._list_pool = k, pool
@@ -430,14 +461,24 @@ class BERT4RecEvaluator(BaseEvaluator):
         else:
             # the same sweep, asked for its best items as well: the ground truth stays rankable, so it can stand in the list
             _, exposure, sums, counts, weight = self._list_sums(engine)
-            ids, scores, gt_rank = engine.rank_full(hidden, None, exclude, SPECIAL_IDS, gt, self._list_pool)
-            if self._quotas is not None:
+            R = int(gt.numel())
+            if self.sample_seed is not None and self._sample_pool is None:
+                ids, _, _ = engine.sample_full(hidden, None, exclude, SPECIAL_IDS, gt, self.list_k, self.sample_seed,
+                                               temperature=self.temperature, stream0=self._sample_rows)
+                gt_rank = ((gt >= SPECIAL_IDS) & (gt < engine.cfg.vocab_size)).to(torch.int32)   # > 0: a valid ground truth
+            else:
+                ids, scores, gt_rank = engine.rank_full(hidden, None, exclude, SPECIAL_IDS, gt, self._list_pool)
+            if self.sample_seed is not None:
+                if self._sample_pool is not None:
+                    ids = engine.sample_pool(ids, scores, self.list_k, self.sample_seed, self.temperature, stream0=self._sample_rows)[0]
+                self._sample_rows += R
+            elif self._quotas is not None:
                 ids = engine.rerank_quota(ids, scores, self.list_k, 0.0 if self.diversity is None else self.diversity, self._quotas)[0]
             elif self.diversity is not None:
                 ids, _, _ = engine.rerank_diverse(ids, scores, self.list_k, self.diversity)
             _, _, _, hit_pos = engine.list_metrics(ids, gt, weight, exposure=exposure, sums=sums, counts=counts)
-            if self.diversity is not None or self._quotas is not None:
-                # the rank in the re-ranked list; k + 1: not in it (no gain under any cut-off <= k); 0 stays "no valid ground truth"
+            if self.diversity is not None or self._quotas is not None or self.sample_seed is not None:
+                # the rank in the re-ranked (or sampled) list; k + 1: not in it (no gain under any cut-off <= k); 0 stays "no valid ground truth"
                 absent = torch.full_like(hit_pos, self.list_k + 1)
                 gt_rank = torch.where(gt_rank > 0, torch.where(hit_pos > 0, hit_pos, absent), torch.zeros_like(hit_pos))
         if len(self._metrics) <= 32:
@@ -471,6 +512,7 @@ class BERT4RecEvaluator(BaseEvaluator):
             for t in self._list_dev[1:4]:
                 t.zero_()
         self._list_host = None
+        self._sample_rows = 0
         if getattr(self, "_dist_dev", None) is not None:
             self._dist_dev[1].zero_()
             self._dist_dev[2].zero_()

@@ -326,7 +326,7 @@ class BERT4RecModel:
     def recommend_tensor(self, encoder_input: Dict[str, torch.Tensor], k: int = 10, exclude_seen: bool = True,
                          exclude: Optional[torch.Tensor] = None, allow=None, row_filter=None, diversity: Optional[float] = None,
                          pool: Optional[int] = None, max_per_group=None, return_distribution: bool = False,
-                         temperature: float = 1.0):
+                         temperature: float = 1.0, sample_seed: Optional[int] = None, sample_streams=None):
         """Top k of the whole catalogue for every slot with masked_lm_weights == 1 (all slots when the key is absent), from one
         b4r_rank_full call: no [R, V] scores.  The forward is rank_items_tensor's (encoder, then tfm MaskedLM's transform on those
         slots only).  [PAD] / [MASK] / [UNK] are never recommended; exclude_seen drops the row's own input_word_ids; exclude
@@ -347,10 +347,28 @@ class BERT4RecModel:
         return_distribution: a fourth value follows, score_distribution_tensor's dict for the same rows, exclusions and filter at
         `temperature` (b4r_score_dist, one more sweep): its logp [R, k] holds the log probabilities of the ids returned,
         after the re-ranking when one is on (-inf under the -1 tail).  ids and scores are the call's without it, bit for bit.
-        A temperature other than 1.0 without return_distribution raises ValueError."""
+        A temperature other than 1.0 without return_distribution or sample_seed raises ValueError.
+        sample_seed: None = the deterministic top k.  An integer in [0, 2^64): the k items are DRAWN without replacement from
+        softmax(scores / temperature) over the slot's allowed catalogue (b4r_sample_full: one sweep with Gumbel-perturbed keys, no
+        [R, V] scores); with pool = M the draw is over the best M allowed items instead (b4r_rank_full, then b4r_sample_pool).  The
+        ids come in draw order and the scores keep b4r_rank_full's bits (not descending).  sample_streams [R] int64: the noise
+        stream of each ranked slot (None: the slot's row number 0 .. R-1); the same (sample_seed, stream) draws the same list
+        whatever else the batch holds.  With return_distribution the log probabilities are b4r_score_dist's at the same temperature:
+        they are over the slot's FULL allowed catalogue, also when `pool` truncates the draw.  sample_seed together with diversity
+        or max_per_group raises ValueError."""
         k = engine_mod.check_rank_full_args(k, exclude)
-        if not return_distribution and not (isinstance(temperature, numbers.Real) and temperature == 1.0):
-            raise ValueError("temperature scales the returned distribution: give return_distribution=True as well")
+        sampled = sample_seed is not None
+        if sampled:
+            sample_seed = engine_mod.check_sample_seed(sample_seed)
+            if diversity is not None or max_per_group is not None:
+                raise ValueError("sample_seed does not combine with diversity or max_per_group")
+            sample_streams = engine_mod.check_sample_streams(sample_streams)
+            if pool is not None:
+                k, pool = engine_mod.check_sample_pool_args(k, pool)
+        elif sample_streams is not None:
+            raise ValueError("sample_streams are the noise streams of a sampled call: give sample_seed as well")
+        if not return_distribution and not sampled and not (isinstance(temperature, numbers.Real) and temperature == 1.0):
+            raise ValueError("temperature scales the returned distribution: give return_distribution=True or sample_seed as well")
         engine_mod.check_temperature(temperature)
         n_sweep = k
         quotas = engine_mod.check_quota_args(max_per_group, self.vocab_size) if max_per_group is not None else None
@@ -358,8 +376,8 @@ class BERT4RecModel:
             k, n_sweep, _ = engine_mod.check_rerank_args(k, pool, 0.0 if diversity is None else diversity)
         elif diversity is not None:
             k, n_sweep, _ = engine_mod.check_rerank_args(k, pool, diversity)
-        elif pool is not None:
-            raise ValueError("pool is the candidate count of the re-ranking: give diversity or max_per_group as well")
+        elif pool is not None and not sampled:
+            raise ValueError("pool is the candidate count of the re-ranking: give diversity, max_per_group or sample_seed as well")
         allow, row_filter = engine_mod.check_item_filter(allow, row_filter, self.vocab_size)
         hidden, slots, _ = self._ranked_slot_hidden(encoder_input)
         dev = self.device
@@ -367,8 +385,15 @@ class BERT4RecModel:
             out = (torch.empty((0, k), dtype=torch.int64, device=dev), torch.empty((0, k), dtype=torch.float32, device=dev), slots)
             return out + (self._distribution_dict(None, slots, k),) if return_distribution else out
         ex_rows = self._excluded_rows(encoder_input, slots, exclude_seen, exclude)
-        ids, scores, _ = self.engine.rank_full(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, n_sweep, allow, row_filter)
-        if quotas is not None:
+        if sampled and pool is None:
+            ids, scores, _ = self.engine.sample_full(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, k, sample_seed, allow, row_filter,
+                                                     temperature, sample_streams)
+        else:
+            ids, scores, _ = self.engine.rank_full(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, pool if sampled else n_sweep,
+                                                   allow, row_filter)
+        if sampled and pool is not None:
+            ids, scores, _, _ = self.engine.sample_pool(ids, scores, k, sample_seed, temperature, sample_streams)
+        elif quotas is not None:
             ids, scores, _, _ = self.engine.rerank_quota(ids, scores, k, 0.0 if diversity is None else diversity, quotas)
         elif diversity is not None:
             ids, scores, _ = self.engine.rerank_diverse(ids, scores, k, diversity)
@@ -456,12 +481,13 @@ class BERT4RecModel:
 
     def recommend(self, encoder_input: dict, k: int = 10, exclude_seen: bool = True, exclude=None, diversity: Optional[float] = None,
                   pool: Optional[int] = None, max_per_group=None, return_distribution: bool = False,
-                  temperature: float = 1.0):
+                  temperature: float = 1.0, sample_seed: Optional[int] = None, sample_streams=None):
         """recommend_tensor as Python lists: per batch row, one list per ranked slot of (ids, scores) lists of length k.
         return_distribution: the entries are (ids, scores, log probabilities) instead, and recommend_tensor's dict follows as a second
         return value (device tensors)."""
         got = self.recommend_tensor(encoder_input, k, exclude_seen, exclude, diversity=diversity, pool=pool,
-                                    max_per_group=max_per_group, return_distribution=return_distribution, temperature=temperature)
+                                    max_per_group=max_per_group, return_distribution=return_distribution, temperature=temperature,
+                                    sample_seed=sample_seed, sample_streams=sample_streams)
         ids, scores, slots = got[:3]
         B, P = (int(x) for x in torch.as_tensor(encoder_input["masked_lm_positions"]).shape)
         out = [[] for _ in range(B)]

@@ -1,6 +1,7 @@
 """Recommend the next item for a history (the reference's examples/recommender_app_example.py): load a saved model (run
 bert4rec_ml_1m_example.py or bert4rec_lifecycle_example.py first), then ask the app.
---diversity D (0 .. 1) also prints a top 5 re-ranked for diversity (greedy Maximal Marginal Relevance over the 50 best candidates)."""
+--diversity D (0 .. 1) also prints a top 5 re-ranked for diversity (greedy Maximal Marginal Relevance over the 50 best candidates).
+--sample SEED also prints 5 items drawn from the softmax over the 50 best candidates, with the probability of each."""
 import argparse
 import pathlib
 
@@ -13,6 +14,7 @@ if __name__ == "__main__":
     parser = argparse.ArgumentParser(description=__doc__)
     parser.add_argument("model", nargs="?", default="bert4rec_ml-1m_lifecycle")
     parser.add_argument("--diversity", type=float, default=None, help="0 = the plain top k ... 1 = dissimilarity alone")
+    parser.add_argument("--sample", type=int, default=None, help="seed of a sampled top 5 (exploration traffic)")
     args = parser.parse_args()
     path = model_utils.determine_model_path(pathlib.Path(args.model))
     loaded = models.BERT4RecModelWrapper.load(path)
@@ -27,3 +29,6 @@ if __name__ == "__main__":
     print("next item:", app(history), " top 5:", app(history, k=5))
     if args.diversity is not None:
         print("top 5 at diversity %g:" % args.diversity, app(history, k=5, diversity=args.diversity))
+    if args.sample is not None:
+        print("5 items drawn with seed %d:" % args.sample,
+              app.recommend_batch([history], k=5, sample_seed=args.sample, user_streams=[0], candidate_pool=50, return_probabilities=True)[0])

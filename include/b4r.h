@@ -445,6 +445,58 @@ int b4r_score_dist(const float* hidden, int32_t hidden_ld, const int64_t* hidden
                    const uint32_t* allow_bits, int32_t n_filters, const int32_t* row_filter, const float* item_scale,
                    float inv_temperature, const int64_t* query_ids, int32_t K, int32_t* row_n, float* row_max, double* row_lse,
                    double* row_entropy, float* query_logp, void* scratch, int64_t scratch_bytes, b4r_stream_t stream);
+/* ---- sampled recommendations: k items drawn without replacement from the catalogue softmax -----------------------
+ * Drawing k items without replacement from softmax(t) is taking the k largest of t_j + Gumbel_j, in descending order of that key
+ * (the draw order).  logf differs between the device library and libm, so the noise is DEFINED as a fixed sequence of individually
+ * rounded IEEE fp64 operations (no libm, no fused multiply-add; b4r_common.h: b4r_gumbel23, tests/sample_ref.py restates it):
+ *   word(seed, stream, id):  h = hash32(uint32(id) ^ uint32(seed));
+ *                            h = hash32((h ^ uint32(stream)) + uint32(seed >> 32));
+ *                            h = hash32(h ^ uint32(stream >> 32))                     hash32: x ^= x >> 16; x *= 0x7FEB352D;
+ *                                                                                     x ^= x >> 15; x *= 0x846CA68B; x ^= x >> 16
+ *   u = ((double)(word >> 9) + 0.5) * 2^-23                                           (b4r_uniform_from_hash's value, exact)
+ *   xln(x): x = 2^e m, m in [1, 2);  if (m > 1.4142135623730951) { m = m * 0.5; e += 1; }
+ *           s = (m - 1.0) / (m + 1.0);  z = s * s;
+ *           p = 1/15; p = p * z + 1/13; p = p * z + 1/11; ... p = p * z + 1/3; p = p * z + 1.0    (every * and + rounded on its own)
+ *           return (double) e * 0.6931471805599453 + (2.0 * s) * p
+ *   g = (float)(0.0 - xln(0.0 - xln(u)))
+ * Over the 2^23 distinct u: |0.0 - xln(0.0 - xln(u)) - libm's fp64 -log(-log(u))| <= 3.9e-14, g in [-2.8115408, 16.635532], all
+ * values distinct.  b4r_gumbel_from_hash (host) and b4r_gumbel_noise (device: out[i] = g(words[i]), n >= 0, one launch) return
+ * the same bits; b4r_sample_word (host) is word().  All three are test surface, like b4r_uniform_from_hash. */
+float b4r_gumbel_from_hash(uint32_t hash_word);
+uint32_t b4r_sample_word(uint64_t seed, int64_t stream, int64_t id);
+int b4r_gumbel_noise(const uint32_t* words, int64_t n, float* out, b4r_stream_t stream);
+/* The sampled counterpart of b4r_rank_full_ex, without an [R, V] buffer.  The first 12 arguments (hidden .. gt) and allow_bits /
+ * n_filters / row_filter / item_scale are b4r_rank_full_ex's, and so are s(r, j) (bit for bit; bias may be NULL) and allowed(r)
+ * (gt[r] stays allowed when listed or filtered).
+ *   t(r, j)    = fl32(s(r, j) * inv_temperature): b4r_score_dist's t; inv_temperature finite and > 0 (else B4R_E_BADARG)
+ *   stream(r)  = row_stream ? row_stream[r] : stream0 + r (wrapping), r the row of the call (not the row within a group)
+ *   key(r, j)  = fl32(t(r, j) + g(word(seed, stream(r), j))): one fp32 add
+ *   out_ids / out_scores / out_keys [R, K]: the first K of allowed(r) by key descending (a -0.0 key counts as +0.0, ties go to the
+ *              lower id): the draw order of sampling K items without replacement from softmax(t) over allowed(r).  out_scores holds
+ *              the unperturbed s (the bits b4r_rank_full_ex returns for that id), out_keys the key.  With fewer than K allowed items
+ *              the tail is -1 / -inf / -inf.  Any output may be NULL.
+ * The probability of a drawn item is b4r_score_dist's query_logp at the same inv_temperature (its propensity for the first draw).
+ * K in [0, 1024]; R = 0 or K = 0 launches nothing.  scratch: b4r_sample_full_scratch_bytes(R, V, K) bytes for one pass over all
+ * rows; a smaller one processes the rows in groups of 16 (the same bits: stream(r) is absolute), and one too small for a group
+ * returns B4R_E_NOMEM.  Every check happens before any launch.  Only enqueues (two launches per group; one stream, no host sync,
+ * graph-capturable); no floating-point atomics: bitwise reproducible.  Non-finite hidden values are outside the contract. */
+int64_t b4r_sample_full_scratch_bytes(int32_t R, int32_t V, int32_t K);
+int b4r_sample_full(const float* hidden, int32_t hidden_ld, const int64_t* hidden_row, const float* table, const float* bias, int32_t H,
+                    int32_t V, int32_t first_item, int32_t R, const int64_t* exclude, int32_t E, const int64_t* gt, int32_t K,
+                    const uint32_t* allow_bits, int32_t n_filters, const int32_t* row_filter, const float* item_scale,
+                    float inv_temperature, uint64_t seed, const int64_t* row_stream, int64_t stream0, int64_t* out_ids,
+                    float* out_scores, float* out_keys, void* scratch, int64_t scratch_bytes, b4r_stream_t stream);
+/* Truncated sampling: K items drawn without replacement from softmax(score * inv_temperature) over a pool of M candidates per row
+ * (pool_ids / pool_scores [R, M], e.g. b4r_rank_full's top M).  An entry is live as in b4r_rerank_diverse: id in [0, V) and a finite
+ * score.  key = fl32(fl32(score * inv_temperature) + g(word(seed, stream(r), id))): the noise goes by the item id, not by the pool
+ * position, so a pool that holds every allowed item gives b4r_sample_full's ids, scores and keys.  Picks by key descending (-0.0
+ * as +0.0), ties to the lower id, then to the lower pool position.  out_ids / out_scores / out_keys / out_pos (int32: the pool
+ * position) are [R, K]; with fewer than K live entries the tail is -1 / -inf / -inf / -1.  Any output may be NULL.
+ * 1 <= M <= 1024, 0 <= K <= M (else B4R_E_SHAPE); inv_temperature finite and > 0 (else B4R_E_BADARG).  One workgroup per row, one
+ * launch, the order by counting: bitwise reproducible, graph-capturable. */
+int b4r_sample_pool(const int64_t* pool_ids, const float* pool_scores, int32_t R, int32_t M, int32_t V, float inv_temperature,
+                    uint64_t seed, const int64_t* row_stream, int64_t stream0, int32_t K, int64_t* out_ids, float* out_scores,
+                    float* out_keys, int32_t* out_pos, b4r_stream_t stream);
 /* replaces the metric loop of bert4rec_evaluator.py:118-120 over evaluation_metrics.py:47-112 for a batch of ranks:
  * gain_sums[m] += sum over gt_rank[i] > 0 of gain_m(gt_rank[i]), users[0] += #{gt_rank[i] > 0}; double / int64 DEVICE
  * accumulators the caller reads once per evaluate().  family[m]: 0 count (gain 1), 1 hit@cutoff (rank <= k), 2 NDCG@cutoff
