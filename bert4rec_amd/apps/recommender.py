@@ -230,6 +230,85 @@ class Recommender:
             out.append((items[0] if items else None) if k == 1 else items)   # None: nothing is left to recommend (filtered or not)
         return out
 
+    def recommend_sequences(self, sequences, steps: int, beams: int = 1, expand=None, allowed_items=None, allowed_items_per_user=None,
+                            temperature: float = 1.0, sample_seed=None, user_streams=None, return_probabilities: bool = False) -> list:
+        """The next `steps` items of every sequence IN ORDER, each one conditioned on the ones before (queue continuation, "watch
+        these three next", simulated trajectories): one batched BERT4RecModel.recommend_sequence_tensor call -- the items are
+        appended on the device between the forwards -- and one read-back.
+        beams = 1: per user a list of `steps` items, shorter when nothing was left to recommend: the greedy path (every step's best
+        item), or with sample_seed a path drawn step by step from the softmax of the scores / temperature (user_streams: one integer
+        per sequence, the user's noise stream, so that a user rolls out the same path whatever batch they ride in).
+        beams > 1: beam search with `expand` candidates per beam (default beams); per user a list of up to `beams` (items,
+        log_probability) pairs, the most probable path first.
+        allowed_items / allowed_items_per_user: as in recommend_batch, applied at every step.  An item is never recommended twice on
+        a path, nor when it occurs anywhere in the user's sequence (also before the model's window).
+        return_probabilities: every item becomes an (item, probability) pair, the probability among the items the user could be
+        served at that step."""
+        steps, beams, expand = engine_mod.check_rollout_args(steps, beams, expand, temperature, sample_seed, bool(return_probabilities))
+        if user_streams is not None:
+            if sample_seed is None:
+                raise ValueError("user_streams are the noise streams of a sampled call: give sample_seed as well")
+            user_streams = engine_mod.check_sample_streams(user_streams)
+        tokenizer = self.dataloader.get_tokenizer()
+        sequences = [list(seq) for seq in sequences]
+        if allowed_items is not None and allowed_items_per_user is not None:
+            raise ValueError("give allowed_items or allowed_items_per_user, not both")
+        if user_streams is not None and user_streams.numel() != len(sequences):
+            raise ValueError(f"{user_streams.numel()} user streams for {len(sequences)} sequences")
+        allow = row_filter = None
+        if allowed_items_per_user is not None:
+            lists = [list(items) for items in allowed_items_per_user]
+            if len(lists) != len(sequences):
+                raise ValueError(f"{len(lists)} allow-lists for {len(sequences)} sequences")
+            distinct = {}
+            row_filter = torch.as_tensor([distinct.setdefault(frozenset(self._known_tokens(items)), len(distinct)) for items in lists],
+                                         dtype=torch.int32)
+            allow = torch.zeros((max(len(distinct), 1), self.model.vocab_size), dtype=torch.bool)
+            for tokens, f in distinct.items():
+                if tokens:
+                    allow[f, torch.as_tensor(sorted(tokens), dtype=torch.int64)] = True
+        elif allowed_items is not None:
+            allow = self._item_mask(allowed_items)
+        if not sequences:
+            return []
+        batches = [self.dataloader.prepare_inference(list(seq)) for seq in sequences]
+        batch = {key: torch.from_numpy(np.concatenate([np.asarray(b[key]) for b in batches], axis=0)) for key in batches[0]}
+        seen = [tokenizer.tokenize(seq) for seq in sequences]
+        width = max(1, max(len(t) for t in seen))
+        exclude = torch.full((len(seen), width), -1, dtype=torch.int64)
+        for i, t in enumerate(seen):
+            if t:
+                exclude[i, :len(t)] = torch.as_tensor(t, dtype=torch.int64)
+        want_logp = bool(return_probabilities) or beams > 1
+        ids, step_logp, logp, _ = self.model.recommend_sequence_tensor(
+            batch, steps, beams=beams, expand=expand, exclude_seen=False, exclude=exclude, allow=allow, row_filter=row_filter,
+            temperature=temperature, sample_seed=sample_seed, sample_streams=user_streams, return_logp=want_logp)
+        U = len(sequences)
+        if want_logp:
+            # ids, probabilities and path totals in one copy: an id is exact in float64
+            both = torch.cat([ids.reshape(U, -1).to(torch.float64), torch.exp(step_logp.reshape(U, -1).to(torch.float64)),
+                              logp.reshape(U, -1).to(torch.float64)], dim=1).cpu()
+            n = beams * steps
+            ids_h = both[:, :n].to(torch.int64).reshape(U, beams, steps).tolist()
+            prob_h = both[:, n:2 * n].reshape(U, beams, steps).tolist()
+            logp_h = both[:, 2 * n:].tolist()
+        else:
+            ids_h, prob_h, logp_h = ids.cpu().tolist(), None, None
+        out = []
+        for u in range(U):
+            paths = []
+            for b in range(beams):
+                kept = [(i, None if prob_h is None else prob_h[u][b][t]) for t, i in enumerate(ids_h[u][b]) if i >= 0]
+                items = tokenizer.detokenize([i for i, _ in kept])
+                if return_probabilities:
+                    items = [(item, p) for item, (_, p) in zip(items, kept)]
+                if beams == 1:
+                    paths = items
+                elif kept:
+                    paths.append((items, logp_h[u][b]))
+            out.append(paths)
+        return out
+
     def similar_items(self, items, k: int = 10, metric: str = "cosine", allowed_items=None) -> list:
         """For every item of `items` the k nearest items of the learned item table, as detokenized lists (best first); metric
         "cosine" or "dot".  An item the vocabulary does not know gets an empty list.  allowed_items: only those are returned."""

@@ -220,6 +220,66 @@ def check_sample_pool_args(k, pool) -> Tuple[int, int]:
     return k, pool
 
 
+ROLLOUT_MAX_STEPS = 64
+BEAM_MAX_BEAMS = 64        # b4r_beam_select: Bm, Bout
+BEAM_MAX_ENTRIES = 4096    # b4r_beam_select: Bm * C
+MASK_ID = 1                # [MASK], the placeholder prepare_inference appends
+
+
+def _int_in(value, lo: int, hi: int, what: str) -> int:
+    if isinstance(value, bool):
+        raise ValueError(f"{what} must be an integer in [{lo}, {hi}], got {value!r}")
+    try:
+        value = operator.index(value)
+    except TypeError:
+        raise ValueError(f"{what} must be an integer in [{lo}, {hi}], got {value!r}") from None
+    if value < lo or value > hi:
+        raise ValueError(f"{what} must lie in [{lo}, {hi}], got {value}")
+    return value
+
+
+def check_rollout_args(steps, beams=1, expand=None, temperature=1.0, sample_seed=None, return_logp: bool = True) -> Tuple[int, int, int]:
+    """Argument checks of a multi-step roll-out that need no GPU: steps in [1, 64], beams in [1, 64], expand (the candidates per beam,
+    default beams) in [1, 1024], beams * expand <= 4096; a sampled roll-out (sample_seed) has one beam; a temperature other than 1
+    needs something that uses it (beams, a seed or the log probabilities).  Returns (steps, beams, expand)."""
+    steps = _int_in(steps, 1, ROLLOUT_MAX_STEPS, "steps")
+    beams = _int_in(beams, 1, BEAM_MAX_BEAMS, "beams")
+    expand = beams if expand is None else _int_in(expand, 1, RANK_FULL_MAX_K, "expand")
+    if beams * expand > BEAM_MAX_ENTRIES:
+        raise ValueError(f"beams * expand = {beams} * {expand} exceeds {BEAM_MAX_ENTRIES}")
+    if sample_seed is not None:
+        check_sample_seed(sample_seed)
+        if beams > 1:
+            raise ValueError("sample_seed draws one path per row: it does not combine with beams > 1 (repeat the user with other streams)")
+    check_temperature(temperature)
+    if beams == 1 and sample_seed is None and not return_logp and not (isinstance(temperature, numbers.Real) and temperature == 1.0):
+        raise ValueError("temperature scales the log probabilities: give return_logp=True, beams > 1 or sample_seed as well")
+    return steps, beams, expand
+
+
+def check_rollout_batch(input_mask: torch.Tensor, positions: torch.Tensor, weights: Optional[torch.Tensor]):
+    """A roll-out takes prepare_inference's format: input_mask [B, L] marks a prefix of len >= 1 real tokens, and every row has exactly
+    one weighted slot (weights [B, P]; None: every slot counts, so P must be 1) whose position is len - 1, the last real token.
+    Works on the tensors' own device and reads one flag back (the roll-out's only host synchronisation before its result).  Returns
+    (len [B] int64, the weighted slot of every row [B] int64)."""
+    if input_mask.ndim != 2 or positions.ndim != 2 or positions.shape[0] != input_mask.shape[0]:
+        raise ValueError(f"input_mask is [B, L] and masked_lm_positions [B, P], got {tuple(input_mask.shape)} and {tuple(positions.shape)}")
+    B, L = input_mask.shape
+    real = input_mask != 0
+    w = torch.ones_like(positions, dtype=torch.bool) if weights is None else torch.as_tensor(weights).to(positions.device).reshape(positions.shape) != 0
+    length = real.sum(dim=1)
+    slot = w.to(torch.int64).argmax(dim=1) if positions.shape[1] > 0 else torch.zeros_like(length)
+    if B > 0:
+        if positions.shape[1] == 0:
+            raise ValueError("a roll-out needs masked_lm_positions")
+        prefix = (real == (torch.arange(L, device=input_mask.device)[None, :] < length[:, None])).all(dim=1)
+        at_last = positions.gather(1, slot[:, None])[:, 0] == length - 1
+        if not bool((prefix & (w.sum(dim=1) == 1) & at_last & (length >= 1)).all()):
+            raise ValueError("a roll-out takes prepare_inference's format: every batch row has exactly one weighted slot, and it is the "
+                             "last real token of the row")
+    return length, slot
+
+
 SIMILARITY_METRICS = {"dot": _lib.SIM_DOT, "cosine": _lib.SIM_COSINE}
 
 
@@ -1021,6 +1081,71 @@ class Engine:
         _lib.check(self.lib.b4r_sample_pool(_ptr(ids_d), _ptr(sc_d), R, M, self.cfg.vocab_size, inv_t, seed, _ptr(st_d), stream0, k,
                                             _ptr(ids), _ptr(scores), _ptr(keys), _ptr(pos), _stream(self.device)), "b4r_sample_pool")
         return ids, scores, keys, pos
+
+    def beam_select(self, beam_logp: torch.Tensor, cand_ids: torch.Tensor, cand_logp: torch.Tensor, n_out: int):
+        """b4r_beam_select: beam_logp [U, Bm] fp32, cand_ids int64 / cand_logp fp32 [U * Bm, C] -> (parent [U, n_out] int32, item
+        [U, n_out] int64, logp [U, n_out] fp32, step_logp [U, n_out] fp32): the n_out best live (beam, candidate) pairs of every user
+        by beam_logp + cand_logp, ties to the lower beam, then to the lower candidate; -1 / -1 / -inf / -inf where a user has fewer."""
+        if beam_logp.ndim != 2 or beam_logp.dtype != torch.float32 or cand_ids.ndim != 2 or cand_ids.dtype != torch.int64 or \
+                cand_logp.dtype != torch.float32 or cand_logp.shape != cand_ids.shape or cand_ids.shape[0] != beam_logp.numel():
+            raise ValueError(f"beam_logp is float32 [U, Bm], the candidates int64 / float32 [U * Bm, C]; got {beam_logp.dtype} "
+                             f"{tuple(beam_logp.shape)}, {cand_ids.dtype} {tuple(cand_ids.shape)}, {cand_logp.dtype} {tuple(cand_logp.shape)}")
+        U, Bm = (int(x) for x in beam_logp.shape)
+        Cn = int(cand_ids.shape[1])
+        n_out = _int_in(n_out, 1, BEAM_MAX_BEAMS, "n_out")
+        if not 1 <= Bm <= BEAM_MAX_BEAMS or not 1 <= Cn <= RANK_FULL_MAX_K or Bm * Cn > BEAM_MAX_ENTRIES:
+            raise ValueError(f"{Bm} beams of {Cn} candidates: at most {BEAM_MAX_BEAMS} beams, {RANK_FULL_MAX_K} candidates and "
+                             f"{BEAM_MAX_ENTRIES} pairs")
+        bl, ci, cl = (x.to(self.device).contiguous() for x in (beam_logp, cand_ids, cand_logp))
+        parent = torch.empty((U, n_out), dtype=torch.int32, device=self.device)
+        item = torch.empty((U, n_out), dtype=torch.int64, device=self.device)
+        logp = torch.empty((U, n_out), dtype=torch.float32, device=self.device)
+        step = torch.empty((U, n_out), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.b4r_beam_select(_ptr(bl), _ptr(ci), _ptr(cl), U, Bm, Cn, n_out, _ptr(parent), _ptr(item), _ptr(logp), _ptr(step),
+                                            _stream(self.device)), "b4r_beam_select")
+        return parent, item, logp, step
+
+    def rollout_state(self, n_rows: int, L: int, P: int, E: int, T: int, paths: bool) -> Dict[str, Optional[torch.Tensor]]:
+        """One buffer set of a roll-out (b4r_rollout_advance writes all of it): tokens / mask [N, L] int64, len [N] int32, positions
+        [N, P] int64, exclude [N, E] int64 and, with paths, path [N, T] int64 / path_logp [N, T] fp32."""
+        dev = self.device
+        return {"tokens": torch.empty((n_rows, L), dtype=torch.int64, device=dev), "mask": torch.empty((n_rows, L), dtype=torch.int64, device=dev),
+                "len": torch.empty((n_rows,), dtype=torch.int32, device=dev), "positions": torch.empty((n_rows, P), dtype=torch.int64, device=dev),
+                "exclude": torch.empty((n_rows, E), dtype=torch.int64, device=dev),
+                "path": torch.empty((n_rows, T), dtype=torch.int64, device=dev) if paths else None,
+                "path_logp": torch.empty((n_rows, T), dtype=torch.float32, device=dev) if paths else None}
+
+    def rollout_advance(self, src: Dict[str, Optional[torch.Tensor]], dst: Dict[str, Optional[torch.Tensor]], parent: Optional[torch.Tensor],
+                        item: torch.Tensor, item_logp: Optional[torch.Tensor], group_in: int, group_out: int, step: int, ex_col: int,
+                        first_item: int = SPECIAL_IDS, mask_id: int = MASK_ID) -> None:
+        """b4r_rollout_advance from the buffer set `src` (tokens, len, exclude; path / path_logp or None) into `dst` (rollout_state):
+        row n of dst continues row (n // group_out) * group_in + parent[n] of src (parent None: row n) with item[n] -- the window
+        advances as prepare_inference(history + [item]) does, column ex_col of the exclusions and column `step` of the path take the
+        item.  A row whose parent or item is out of range copies the first row of its group and gets an empty path."""
+        tokens = src["tokens"]
+        N_in, L = (int(x) for x in tokens.shape)
+        N_out = int(dst["tokens"].shape[0])
+        E, Pn = int(src["exclude"].shape[1]), int(dst["positions"].shape[1])
+        T = int(dst["path"].shape[1]) if dst.get("path") is not None else max(int(step) + 1, 1)
+        if dst["tokens"].shape[1] != L or dst["exclude"].shape != (N_out, E) or item.numel() != N_out or \
+                (parent is not None and parent.numel() != N_out) or (item_logp is not None and item_logp.numel() != N_out):
+            raise ValueError("the roll-out buffers, parents and items disagree in their shapes")
+        for name, dt in (("tokens", torch.int64), ("len", torch.int32), ("exclude", torch.int64)):
+            if src[name].dtype != dt or not src[name].is_contiguous() or not src[name].is_cuda:
+                raise ValueError(f"roll-out buffer '{name}' must be a contiguous {dt} tensor on the device")
+        if item.dtype != torch.int64 or (parent is not None and parent.dtype != torch.int32) or \
+                (item_logp is not None and item_logp.dtype != torch.float32):
+            raise ValueError("parent is int32, item int64 and item_logp float32")
+        item_d = item.contiguous()
+        parent_d = None if parent is None else parent.contiguous()
+        logp_d = None if item_logp is None else item_logp.contiguous()
+        want_logp = dst.get("path_logp") is not None and logp_d is not None
+        _lib.check(self.lib.b4r_rollout_advance(
+            _ptr(tokens), _ptr(src["len"]), _ptr(src["exclude"]), _ptr(src.get("path")), _ptr(src.get("path_logp")), _ptr(parent_d),
+            _ptr(item_d), _ptr(logp_d), N_in, N_out, int(group_in), int(group_out), L, Pn, E, T, self.cfg.vocab_size, int(first_item),
+            int(mask_id), int(step), int(ex_col), _ptr(dst["tokens"]), _ptr(dst["mask"]), _ptr(dst["len"]), _ptr(dst["positions"]),
+            _ptr(dst["exclude"]), _ptr(dst.get("path")), _ptr(dst["path_logp"]) if want_logp else None, _stream(self.device)),
+            "b4r_rollout_advance")
 
     def item_neighbours(self, item_ids: torch.Tensor, k: int, metric: str = "cosine", first_item: int = SPECIAL_IDS, allow=None,
                         row_filter=None):

@@ -499,6 +499,126 @@ class BERT4RecModel:
             out[s // P].append((i_row, s_row, p_row))
         return out, got[3]
 
+    def recommend_sequence_tensor(self, encoder_input: Dict[str, torch.Tensor], steps: int, beams: int = 1, expand: Optional[int] = None,
+                                  exclude_seen: bool = True, exclude: Optional[torch.Tensor] = None, allow=None, row_filter=None,
+                                  temperature: float = 1.0, sample_seed: Optional[int] = None, sample_streams=None,
+                                  return_logp: bool = True):
+        """The next `steps` items of every batch row IN ORDER, each one conditioned on the ones before: after every step the chosen
+        item is appended to the row on the device (b4r_rollout_advance: the window advances as prepare_inference(history + [item])
+        does) and the forward runs again.  Nothing is read back between the steps.
+        encoder_input is prepare_inference's format: every batch row has exactly one weighted slot and it gathers the last real
+        token (the [MASK] placeholder); anything else raises ValueError.  That check is the call's one host synchronisation.
+        Every step's forward is recommend_tensor's, so its scores are the bits recommend_tensor returns for the same rows.  A row's
+        exclusions are its input_word_ids (exclude_seen), its row of `exclude` [B, E] and everything picked so far on its own path
+        (an item that slid out of the window stays excluded); allow / row_filter [B] apply at every step.
+          beams = 1, no sample_seed: greedy -- the step's item is b4r_rank_full's top 1.
+          beams = B > 1: beam search -- every beam proposes its `expand` best items (default B; B * expand <= 4096) with their log
+            probabilities at `temperature` (b4r_score_dist) and b4r_beam_select keeps the B paths with the largest summed log
+            probability, ties to the better parent, then to the better candidate.  Step 0 runs on the batch rows themselves with
+            max(expand, B) candidates.  Beams come out best first; all paths have `steps` items, so a beam that cannot be
+            extended is dropped whole.
+          sample_seed (beams = 1): step t draws one item from softmax(scores / temperature) with b4r_sample_full under the seed
+            (sample_seed + t) mod 2^64 and the row's stream (sample_streams [B] int64; None: the row number), so a user rolls out
+            the same path whatever batch they ride in, and several roll-outs of one user are that user repeated with other streams.
+        Returns (ids [B, beams, steps] int64, step_logp [B, beams, steps] fp32 or None, logp [B, beams] fp32 or None, slot_index [B]
+        int64), on the device.  Greedy and sampled paths end in -1 once nothing is left to recommend; a dropped beam is -1 in every
+        column.  step_logp holds the log probability of every item among those the row could be served at its step (-inf under a
+        -1; None with return_logp=False), logp their fp32 sum in step order, which for beams is the total the search ranked by (None
+        for a greedy or sampled call with return_logp=False, which runs no b4r_score_dist)."""
+        steps, beams, expand = engine_mod.check_rollout_args(steps, beams, expand, temperature, sample_seed, return_logp)
+        sampled = sample_seed is not None
+        if sampled:
+            sample_seed = engine_mod.check_sample_seed(sample_seed)
+        elif sample_streams is not None:
+            raise ValueError("sample_streams are the noise streams of a sampled call: give sample_seed as well")
+        if exclude is not None and torch.as_tensor(exclude).ndim != 2:
+            raise ValueError(f"exclude must be rank 2 [rows, ids], got shape {tuple(torch.as_tensor(exclude).shape)}")
+        allow, row_filter = engine_mod.check_item_filter(allow, row_filter, self.vocab_size)
+        eng, dev = self.engine, self.device
+        cb, keep = eng.prepare_batch(encoder_input)
+        if cb.P == 0:
+            raise ValueError("recommend_sequence_tensor needs masked_lm_positions")
+        U, L, P = cb.B, cb.L, cb.P
+        if L < 2:
+            raise ValueError("a roll-out needs sequences of at least 2 tokens (an item and the placeholder)")
+        if row_filter is not None and row_filter.numel() != U:
+            raise ValueError(f"row_filter has {row_filter.numel()} entries for a batch of {U}")
+        streams = engine_mod.check_sample_streams(sample_streams, U) if sampled else None
+        tokens, mask, pos = keep["input_word_ids"], keep["input_mask"], keep["masked_lm_positions"]
+        length, slot_p = engine_mod.check_rollout_batch(mask, pos, encoder_input.get("masked_lm_weights"))   # the one host synchronisation
+        slots0 = torch.arange(U, dtype=torch.int64, device=dev) * P + slot_p
+        ids_out = torch.full((U, beams, steps), -1, dtype=torch.int64, device=dev)
+        if U == 0:
+            lp = torch.empty((U, beams, steps), dtype=torch.float32, device=dev)
+            return ids_out, (lp if return_logp else None), (lp[:, :, 0] if return_logp or beams > 1 else None), slots0
+        ex0 = self._excluded_rows(encoder_input, slots0, exclude_seen, exclude)
+        E0 = 0 if ex0 is None else int(ex0.shape[1])
+        tail = torch.full((U, steps), -1, dtype=torch.int64, device=dev)   # column E0 + t takes step t's item
+        cur = {"tokens": tokens, "len": length.to(torch.int32), "exclude": tail if ex0 is None else torch.cat([ex0, tail], dim=1).contiguous(),
+               "path": None, "path_logp": None}
+        batch = {"input_word_ids": tokens, "input_mask": mask, "masked_lm_positions": pos}
+        slots = slots0
+        first = engine_mod.SPECIAL_IDS
+        N = U * beams
+        pair = [None, None]
+        rf = None if row_filter is None else row_filter.to(dev)
+        st = None if streams is None else streams.to(dev)
+        want_dist = return_logp or beams > 1
+        lp_out = torch.full((U, 1, steps), float("-inf"), dtype=torch.float32, device=dev) if want_dist and beams == 1 else None
+        beam_logp = torch.zeros((U, 1), dtype=torch.float32, device=dev)
+        for t in range(steps):
+            hidden, _, _ = self._ranked_slot_hidden(batch, slots=slots)
+            ex = cur["exclude"]
+            dst = None
+            if beams > 1 or t + 1 < steps:
+                dst = pair[t % 2] = pair[t % 2] or eng.rollout_state(N, L, P, E0 + steps, steps, paths=beams > 1)
+            if beams > 1:
+                cand, _, _ = eng.rank_full(hidden, None, ex, first, None, max(expand, beams) if t == 0 else expand, allow, rf)
+                cand_logp = eng.score_distribution(hidden, None, ex, first, None, allow, rf, temperature, cand)[4]
+                parent, item, beam_logp, step_logp = eng.beam_select(beam_logp, cand, cand_logp, beams)
+                eng.rollout_advance(cur, dst, parent.reshape(-1), item.reshape(-1), step_logp.reshape(-1), 1 if t == 0 else beams, beams,
+                                    t, E0 + t)
+                if t == 0 and rf is not None:
+                    rf = rf.repeat_interleave(beams)   # a beam row inherits its user's filter
+            else:
+                if sampled:
+                    item, _, _ = eng.sample_full(hidden, None, ex, first, None, 1, (sample_seed + t) % (1 << 64), allow, rf, temperature, st)
+                else:
+                    item, _, _ = eng.rank_full(hidden, None, ex, first, None, 1, allow, rf)
+                ids_out[:, 0, t].copy_(item[:, 0])
+                if want_dist:
+                    lp_out[:, 0, t].copy_(eng.score_distribution(hidden, None, ex, first, None, allow, rf, temperature, item)[4][:, 0])
+                if dst is not None:
+                    eng.rollout_advance(cur, dst, None, item[:, 0], None, 1, 1, t, E0 + t)
+            if dst is not None:
+                cur = dst
+                batch = {"input_word_ids": dst["tokens"], "input_mask": dst["mask"], "masked_lm_positions": dst["positions"]}
+                if t == 0:
+                    slots = torch.arange(N, dtype=torch.int64, device=dev) * P
+        if beams > 1:
+            step_all = cur["path_logp"].view(U, beams, steps)
+            return cur["path"].view(U, beams, steps), (step_all if return_logp else None), beam_logp, slots0
+        if not want_dist:
+            return ids_out, None, None, slots0
+        logp = lp_out[:, :, 0].clone()
+        for t in range(1, steps):
+            logp = logp + lp_out[:, :, t]     # the fp32 sum in step order, as b4r_beam_select forms a beam's total
+        return ids_out, lp_out, logp, slots0
+
+    def recommend_sequence(self, encoder_input: dict, steps: int, beams: int = 1, expand: Optional[int] = None, exclude_seen: bool = True,
+                           exclude=None, allow=None, row_filter=None, temperature: float = 1.0, sample_seed: Optional[int] = None,
+                           sample_streams=None, return_logp: bool = True):
+        """recommend_sequence_tensor as Python lists: per batch row one entry per beam (best first), each an (ids, logp, step_logp)
+        tuple -- the path's `steps` ids (-1 where nothing was left), its summed log probability and the log probability of every
+        step (None / None where the tensor call returns None)."""
+        ids, step_logp, logp, _ = self.recommend_sequence_tensor(encoder_input, steps, beams, expand, exclude_seen, exclude, allow, row_filter,
+                                                                 temperature, sample_seed, sample_streams, return_logp)
+        ids_h = ids.cpu().tolist()
+        step_h = None if step_logp is None else step_logp.cpu().tolist()
+        logp_h = None if logp is None else logp.cpu().tolist()
+        return [[(ids_h[u][b], None if logp_h is None else logp_h[u][b], None if step_h is None else step_h[u][b])
+                 for b in range(len(ids_h[u]))] for u in range(len(ids_h))]
+
     def _rank_items_ragged(self, encoder_input, items):
         """Candidate lists of different lengths: one kernel call per distinct length."""
         flat = [c for row in items for c in row]

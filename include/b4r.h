@@ -497,6 +497,50 @@ int b4r_sample_full(const float* hidden, int32_t hidden_ld, const int64_t* hidde
 int b4r_sample_pool(const int64_t* pool_ids, const float* pool_scores, int32_t R, int32_t M, int32_t V, float inv_temperature,
                     uint64_t seed, const int64_t* row_stream, int64_t stream0, int32_t K, int64_t* out_ids, float* out_scores,
                     float* out_keys, int32_t* out_pos, b4r_stream_t stream);
+/* Multi-step roll-outs: the step logic between two forwards, so that a greedy, beam or sampled roll-out reads nothing back between
+ * its steps.  Both calls only enqueue (one launch, one stream, no host sync, graph-capturable), use no atomics and are bitwise
+ * reproducible; every argument is checked before the launch.
+ *
+ * b4r_beam_select: the next Bout beams of every user out of Bm parent beams x C candidates.  beam_logp [U, Bm] fp32; cand_ids /
+ * cand_logp [U * Bm, C] (row u * Bm + b holds the candidates of beam b of user u, e.g. b4r_rank_full's ids and b4r_score_dist's
+ * query_logp for them).
+ *   total(b, c) = fl32(beam_logp[u][b] + cand_logp[u * Bm + b][c]): one fp32 add
+ *   live(b, c)  = beam_logp[u][b] > -inf and cand_ids >= 0 and cand_logp > -inf
+ * Outputs [U, Bout], t = 0 .. Bout-1: the live entries by total descending (-0.0 counts as +0.0), ties to the lower b, then to the
+ * lower c: out_parent (int32) = b, the beam index within the user; out_item = cand_ids; out_logp = total; out_step_logp =
+ * cand_logp.  With fewer than Bout live entries the tail is -1 / -1 / -inf / -inf.  Any output may be NULL.
+ * 1 <= Bm <= 64, 1 <= C <= 1024, Bm * C <= 4096, 1 <= Bout <= 64, U >= 0 (else B4R_E_SHAPE); a NULL input B4R_E_BADARG; U = 0
+ * succeeds and launches nothing.  One workgroup per user, the order by counting.  NaN is outside the contract (a NaN log
+ * probability makes its entries dead); nothing is read or written out of bounds. */
+int b4r_beam_select(const float* beam_logp, const int64_t* cand_ids, const float* cand_logp, int32_t U, int32_t Bm, int32_t C,
+                    int32_t Bout, int32_t* out_parent, int64_t* out_item, float* out_logp, float* out_step_logp, b4r_stream_t stream);
+/* b4r_rollout_advance: the next step's batch rows from the chosen parents and items.  The rows are grouped per user: N_in = users *
+ * G_in input rows, N_out = users * G_out output rows.  Output row n has the source row s = (n / G_out) * G_in + parent[n]; parent
+ * NULL: s = n (then G_in == G_out).
+ *   tokens_in [N_in, L] int64, len_in [N_in] int32: the row holds len tokens and the last of them is the [MASK] placeholder
+ *   exclude_in [N_in, E] int64; path_in [N_in, T] int64 and path_logp_in [N_in, T] fp32 (either may be NULL: all -1 / all -inf)
+ *   parent [N_out] int32, item [N_out] int64, item_logp [N_out] fp32 (NULL unless path_logp_out is given)
+ *   V, first_item, mask_id; t in [0, T): the step; ex_col in [0, E): the exclusion column the step writes
+ * A row is live when parent[n] lies in [0, G_in) and item[n] in [first_item, V).  For a live row, len = clamp(len_in[s], 1, L):
+ *   len < L:  out[0 .. len-2] = in[s][0 .. len-2], out[len-1] = item, out[len] = mask_id, the rest 0; len_out = len + 1
+ *   len == L: the window slides: out[p] = in[s][p+1] for p <= L-3, out[L-2] = item, out[L-1] = mask_id; len_out = L
+ *   input_mask_out [N_out, L] int64: p < len_out;  positions_out [N_out, P] int64: [len_out - 1, 0, 0, ...]
+ *   exclude_out[n] = exclude_in[s] with column ex_col = item;  path_out[n] = path_in[s] with column t = item; path_logp_out[n] =
+ *   path_logp_in[s] with column t = item_logp[n] (path_out / path_logp_out may be NULL)
+ * which is the reference's prepare_inference(history + [item]): keep the most recent L - 1 items, append the placeholder.
+ * A dead row copies the first row of its group, s = (n / G_out) * G_in, unchanged (tokens, mask, length clamped as above, positions,
+ * exclusions), so that it stays a valid sequence for the forward; its path is -1 and its path_logp -inf in every column.  A dead
+ * row never writes its item.
+ * L >= 2, P >= 1, E >= 1, T >= 1, V >= 1, first_item >= 0, t and ex_col in range, N_in / G_in == N_out / G_out without remainder
+ * (else B4R_E_SHAPE); a required pointer that is NULL, or an output that overlaps its own input (tokens, length, exclusions, path,
+ * path_logp; the rows are re-ordered, so the call needs the other buffer of a ping-pong pair): B4R_E_BADARG.  N_out = 0 succeeds
+ * and launches nothing.  One workgroup per output row. */
+int b4r_rollout_advance(const int64_t* tokens_in, const int32_t* len_in, const int64_t* exclude_in, const int64_t* path_in,
+                        const float* path_logp_in, const int32_t* parent, const int64_t* item, const float* item_logp, int32_t N_in,
+                        int32_t N_out, int32_t G_in, int32_t G_out, int32_t L, int32_t P, int32_t E, int32_t T, int32_t V,
+                        int32_t first_item, int64_t mask_id, int32_t t, int32_t ex_col, int64_t* tokens_out, int64_t* input_mask_out,
+                        int32_t* len_out, int64_t* positions_out, int64_t* exclude_out, int64_t* path_out, float* path_logp_out,
+                        b4r_stream_t stream);
 /* replaces the metric loop of bert4rec_evaluator.py:118-120 over evaluation_metrics.py:47-112 for a batch of ranks:
  * gain_sums[m] += sum over gt_rank[i] > 0 of gain_m(gt_rank[i]), users[0] += #{gt_rank[i] > 0}; double / int64 DEVICE
  * accumulators the caller reads once per evaluate().  family[m]: 0 count (gain 1), 1 hit@cutoff (rank <= k), 2 NDCG@cutoff
