@@ -24,7 +24,11 @@ return_probabilities / min_probability / temperature turn the scores into probab
 served (b4r_score_dist: one more sweep, no [users, V] scores): every recommended item comes with its probability, and items below a
 threshold are dropped.
 
-list_quality measures what such lists are like beyond accuracy (b4r_list_metrics): intra-list diversity, catalogue coverage, novelty."""
+list_quality measures what such lists are like beyond accuracy (b4r_list_metrics): intra-list diversity, catalogue coverage, novelty.
+
+explain_batch / explain say why an item is recommended ("because you watched X"): one history item, or every history item of one
+category, is removed at a time on the device (b4r_occlude_rows), the model runs again, and the history items whose removal costs the
+recommendation the most log probability come back as its reasons (b4r_attribution_select)."""
 import numbers
 
 import numpy as np
@@ -308,6 +312,132 @@ class Recommender:
                     paths.append((items, logp_h[u][b]))
             out.append(paths)
         return out
+
+    def _group_labels(self, by_group):
+        """by_group -> (labels int32 [V] with -1 = no group, the label each group index stands for).  A mapping (or a callable) from a
+        detokenized item to a hashable label, as max_per_group takes it: an item it does not know, or maps to None, is in no group.
+        Or one integer label per token id [V] (negative = no group), as pack_item_groups takes it: the labels come back as they are."""
+        V = self.model.vocab_size
+        look = by_group if callable(by_group) else getattr(by_group, "get", None)
+        if look is None:
+            groups = np.asarray(by_group)
+            if groups.ndim != 1 or groups.shape[0] != V or groups.dtype.kind not in "iu":
+                raise ValueError(f"by_group maps an item to its label (a mapping or a callable) or holds one integer label per token id [{V}]")
+            groups = np.where(groups < 0, -1, groups).astype(np.int64)
+            if groups.size and groups.max() >= 1 << 31:
+                raise ValueError("by_group labels must fit in int32")
+            return torch.from_numpy(groups.astype(np.int32)), None
+        tokens = list(range(SPECIAL_IDS, V))
+        index, groups = {}, np.full(V, -1, dtype=np.int32)
+        for t, item in zip(tokens, self.dataloader.get_tokenizer().detokenize(tokens)):
+            label = look(item)
+            if label is not None:
+                groups[t] = index.setdefault(label, len(index))
+        return torch.from_numpy(groups), list(index)
+
+    def explain_batch(self, sequences, items=None, k: int = 1, top: int = 3, window=None, by_group=None, allowed_items=None,
+                      allowed_items_per_user=None, temperature: float = 1.0) -> list:
+        """Why each item is recommended ("because you watched X"), for every sequence of `sequences`: one history item at a time is
+        removed, the model runs again, and the history items whose removal costs the recommended item the most log probability are
+        its reasons (BERT4RecModel.explain_tensor: the occluded rows are built on the device; one batched call, one read-back).
+        items: None = the user's own top k, which are recommend_batch's items under the same filters; else one list of items per
+        sequence (an item the vocabulary does not know is explained by nothing).  top: the reasons per item; window: only the
+        `window` most recent history items are tried (None: all the model sees); top <= window.
+        by_group: explain by category instead of by item -- a mapping (or a callable) from an item to its label, or one integer label
+        per token id [V]: all history items of one category are removed together.
+        allowed_items / allowed_items_per_user / temperature: as in recommend_batch; the probabilities are over the items the user
+        could be served.
+        Returns per sequence a list of (item, probability, reasons), the explained items in the order given (an own item that does not
+        exist, k beyond what is left, is dropped).  reasons = [(history_item, delta_logp), ...], or with by_group [(label, delta_logp,
+        n_items_removed), ...]: best first; delta_logp > 0 says the recommendation leans on it, < 0 that it was held back by it."""
+        engine_mod.check_temperature(temperature)
+        engine_mod.check_explain_args(top, window, engine_mod.EXPLAIN_MAX_UNITS)   # (the model checks them against its own length)
+        sequences = [list(seq) for seq in sequences]
+        if items is None:
+            k = engine_mod.check_rank_full_args(k)
+            if k < 1:
+                raise ValueError(f"k must lie in [1, {engine_mod.RANK_FULL_MAX_K}], got {k}")
+        else:
+            items = [list(row) for row in items]
+            if len(items) != len(sequences):
+                raise ValueError(f"{len(items)} item lists for {len(sequences)} sequences")
+            if sequences and not 1 <= max(len(row) for row in items) <= engine_mod.RANK_FULL_MAX_K:
+                raise ValueError(f"between 1 and {engine_mod.RANK_FULL_MAX_K} items are explained per sequence")
+        if allowed_items is not None and allowed_items_per_user is not None:
+            raise ValueError("give allowed_items or allowed_items_per_user, not both")
+        allow = row_filter = None
+        if allowed_items_per_user is not None:
+            lists = [list(row) for row in allowed_items_per_user]
+            if len(lists) != len(sequences):
+                raise ValueError(f"{len(lists)} allow-lists for {len(sequences)} sequences")
+            distinct = {}
+            row_filter = torch.as_tensor([distinct.setdefault(frozenset(self._known_tokens(row)), len(distinct)) for row in lists],
+                                         dtype=torch.int32)
+            allow = torch.zeros((max(len(distinct), 1), self.model.vocab_size), dtype=torch.bool)
+            for tokens, f in distinct.items():
+                if tokens:
+                    allow[f, torch.as_tensor(sorted(tokens), dtype=torch.int64)] = True
+        elif allowed_items is not None:
+            allow = self._item_mask(allowed_items)
+        labels = names = None
+        if by_group is not None:
+            labels, names = self._group_labels(by_group)
+        if not sequences:
+            return []
+        tokenizer = self.dataloader.get_tokenizer()
+        batches = [self.dataloader.prepare_inference(list(seq)) for seq in sequences]
+        batch = {key: torch.from_numpy(np.concatenate([np.asarray(b[key]) for b in batches], axis=0)) for key in batches[0]}
+        seen = [tokenizer.tokenize(seq) for seq in sequences]
+        width = max(1, max(len(t) for t in seen))
+        exclude = torch.full((len(seen), width), -1, dtype=torch.int64)
+        for i, t in enumerate(seen):
+            if t:
+                exclude[i, :len(t)] = torch.as_tensor(t, dtype=torch.int64)
+        if items is None:
+            target = k
+        else:
+            target = torch.full((len(items), max(len(row) for row in items)), -1, dtype=torch.int64)
+            for i, row in enumerate(items):
+                for j, item in enumerate(row):
+                    t = self._known_tokens([item])
+                    if t:
+                        target[i, j] = t[0]
+        got = self.model.explain_tensor(batch, target, top=top, labels=labels, window=window, exclude_seen=False, exclude=exclude,
+                                        allow=allow, row_filter=row_filter, temperature=temperature)
+        U, K = (int(x) for x in got["target_ids"].shape)
+        # everything in one copy: ids and counts are exact in float64
+        unit = got["top_label"] if labels is not None else got["top_item"]
+        removed = got["removed"].gather(1, got["top_w"].clamp(min=0).to(torch.int64).reshape(U, -1))
+        both = torch.cat([got["target_ids"].to(torch.float64), torch.exp(got["base_logp"].to(torch.float64)),
+                          unit.reshape(U, -1).to(torch.float64), got["top_delta"].reshape(U, -1).to(torch.float64),
+                          removed.to(torch.float64), got["top_w"].reshape(U, -1).to(torch.float64)], dim=1).cpu()
+        n = K * top
+        ids_h = both[:, :K].to(torch.int64).tolist()
+        prob_h = both[:, K:2 * K].tolist()
+        unit_h, delta_h, removed_h, w_h = (both[:, 2 * K + s * n:2 * K + (s + 1) * n].reshape(U, K, top).tolist() for s in range(4))
+        out = []
+        for u in range(U):
+            rows = []
+            for i in range(K):
+                given = items is not None and i < len(items[u])
+                if ids_h[u][i] < 0 and not given:
+                    continue                                       # nothing was left to recommend / the padding of a shorter list
+                live = [t for t in range(top) if w_h[u][i][t] >= 0]
+                if labels is not None:
+                    reasons = [(int(unit_h[u][i][t]) if names is None else names[int(unit_h[u][i][t])], delta_h[u][i][t],
+                                int(removed_h[u][i][t])) for t in live]
+                else:
+                    reasons = [(h, delta_h[u][i][t]) for h, t in zip(tokenizer.detokenize([int(unit_h[u][i][t]) for t in live]), live)]
+                name = items[u][i] if given else tokenizer.detokenize([ids_h[u][i]])[0]
+                rows.append((name, prob_h[u][i], reasons))
+            out.append(rows)
+        return out
+
+    def explain(self, sequence: list, items=None, k: int = 1, top: int = 3, window=None, by_group=None, allowed_items=None,
+                temperature: float = 1.0) -> list:
+        """explain_batch for one sequence: a list of (item, probability, reasons)."""
+        return self.explain_batch([sequence], None if items is None else [list(items)], k=k, top=top, window=window, by_group=by_group,
+                                  allowed_items=allowed_items, temperature=temperature)[0]
 
     def similar_items(self, items, k: int = 10, metric: str = "cosine", allowed_items=None) -> list:
         """For every item of `items` the k nearest items of the learned item table, as detokenized lists (best first); metric

@@ -257,11 +257,12 @@ def check_rollout_args(steps, beams=1, expand=None, temperature=1.0, sample_seed
     return steps, beams, expand
 
 
-def check_rollout_batch(input_mask: torch.Tensor, positions: torch.Tensor, weights: Optional[torch.Tensor]):
+def check_rollout_batch(input_mask: torch.Tensor, positions: torch.Tensor, weights: Optional[torch.Tensor], return_max_len: bool = False):
     """A roll-out takes prepare_inference's format: input_mask [B, L] marks a prefix of len >= 1 real tokens, and every row has exactly
     one weighted slot (weights [B, P]; None: every slot counts, so P must be 1) whose position is len - 1, the last real token.
     Works on the tensors' own device and reads one flag back (the roll-out's only host synchronisation before its result).  Returns
-    (len [B] int64, the weighted slot of every row [B] int64)."""
+    (len [B] int64, the weighted slot of every row [B] int64); with return_max_len the largest row length (0 for an empty batch)
+    travels back with the flag, in the same synchronisation, and follows as a third value."""
     if input_mask.ndim != 2 or positions.ndim != 2 or positions.shape[0] != input_mask.shape[0]:
         raise ValueError(f"input_mask is [B, L] and masked_lm_positions [B, P], got {tuple(input_mask.shape)} and {tuple(positions.shape)}")
     B, L = input_mask.shape
@@ -274,10 +275,35 @@ def check_rollout_batch(input_mask: torch.Tensor, positions: torch.Tensor, weigh
             raise ValueError("a roll-out needs masked_lm_positions")
         prefix = (real == (torch.arange(L, device=input_mask.device)[None, :] < length[:, None])).all(dim=1)
         at_last = positions.gather(1, slot[:, None])[:, 0] == length - 1
-        if not bool((prefix & (w.sum(dim=1) == 1) & at_last & (length >= 1)).all()):
+        ok = (prefix & (w.sum(dim=1) == 1) & at_last & (length >= 1)).all()
+        if return_max_len:
+            ok, max_len = torch.stack([ok.to(torch.int64), length.max()]).tolist()
+        if not bool(ok):
             raise ValueError("a roll-out takes prepare_inference's format: every batch row has exactly one weighted slot, and it is the "
                              "last real token of the row")
+    if return_max_len:
+        return length, slot, (int(max_len) if B > 0 else 0)
     return length, slot
+
+
+EXPLAIN_MAX_UNITS = 256    # b4r_attribution_select: W
+
+
+def check_explain_args(top, window, L: int, K: Optional[int] = None, rows_per_forward=None) -> Tuple[int, int]:
+    """Argument checks of an occlusion explanation that need no GPU: rows of L tokens (2 <= L <= 256: an item and the placeholder, one
+    thread per position) have at most L - 1 history units; window (default all of them) in [1, L - 1], top in [1, window], K
+    explained items per row in [1, 1024], rows_per_forward >= 1.  Returns (top, window)."""
+    if L < 2 or L > EXPLAIN_MAX_UNITS:
+        raise ValueError(f"an explanation needs sequences of 2 to {EXPLAIN_MAX_UNITS} tokens (an item and the placeholder), got {L}")
+    window = L - 1 if window is None else _int_in(window, 1, L - 1, "window")
+    top = _int_in(top, 1, EXPLAIN_MAX_UNITS, "top")
+    if top > window:
+        raise ValueError(f"top = {top} units cannot be chosen among window = {window}")
+    if K is not None and not 1 <= K <= RANK_FULL_MAX_K:
+        raise ValueError(f"between 1 and {RANK_FULL_MAX_K} items are explained per row, got {K}")
+    if rows_per_forward is not None:
+        _int_in(rows_per_forward, 1, (1 << 31) - 1, "rows_per_forward")
+    return top, window
 
 
 SIMILARITY_METRICS = {"dot": _lib.SIM_DOT, "cosine": _lib.SIM_COSINE}
@@ -1146,6 +1172,60 @@ class Engine:
             int(mask_id), int(step), int(ex_col), _ptr(dst["tokens"]), _ptr(dst["mask"]), _ptr(dst["len"]), _ptr(dst["positions"]),
             _ptr(dst["exclude"]), _ptr(dst.get("path")), _ptr(dst["path_logp"]) if want_logp else None, _stream(self.device)),
             "b4r_rollout_advance")
+
+    def explain_state(self, n_rows: int, L: int, P: int) -> Dict[str, torch.Tensor]:
+        """One buffer set of occluded rows (b4r_occlude_rows writes all of it): tokens / mask [N, L] int64, len [N] int32, positions
+        [N, P] int64, live / unit_pos / unit_label / removed [N] int32, unit_item [N] int64."""
+        dev = self.device
+        i32 = {k: torch.empty((n_rows,), dtype=torch.int32, device=dev) for k in ("len", "live", "unit_pos", "unit_label", "removed")}
+        return {"tokens": torch.empty((n_rows, L), dtype=torch.int64, device=dev), "mask": torch.empty((n_rows, L), dtype=torch.int64, device=dev),
+                "positions": torch.empty((n_rows, P), dtype=torch.int64, device=dev),
+                "unit_item": torch.empty((n_rows,), dtype=torch.int64, device=dev), **i32}
+
+    def occlude_rows(self, tokens: torch.Tensor, length: torch.Tensor, labels: Optional[torch.Tensor], w0: int, dst: Dict[str, torch.Tensor],
+                     mask_id: int = MASK_ID) -> None:
+        """b4r_occlude_rows from the rows tokens [U, L] int64 / length [U] int32 (prepare_inference's format: the last of a row's
+        `length` tokens is the placeholder) into `dst` (explain_state, U * Wc rows): row u * Wc + c of dst is row u without its
+        history unit of recency index w0 + c -- the item at position length - 2 - w0 - c, or with labels [V] int32 every history
+        item that shares its label -- as prepare_inference of the remaining items; a unit the row does not have gives the row
+        unchanged with live = 0."""
+        if tokens.ndim != 2 or tokens.dtype != torch.int64 or not tokens.is_contiguous() or not tokens.is_cuda:
+            raise ValueError("tokens must be a contiguous int64 tensor [U, L] on the device")
+        U, L = (int(x) for x in tokens.shape)
+        if length.dtype != torch.int32 or length.shape != (U,) or not length.is_contiguous() or not length.is_cuda:
+            raise ValueError(f"length must be a contiguous int32 tensor [{U}] on the device")
+        V = self.cfg.vocab_size
+        if labels is not None and (labels.dtype != torch.int32 or labels.shape != (V,) or not labels.is_contiguous() or not labels.is_cuda):
+            raise ValueError(f"labels must be a contiguous int32 tensor [{V}] on the device")
+        N = int(dst["tokens"].shape[0])
+        if dst["tokens"].shape[1] != L or N % max(U, 1) != 0 or (U > 0 and N < U) or (U == 0 and N != 0):
+            raise ValueError(f"the occluded rows [{N}, {int(dst['tokens'].shape[1])}] are no whole chunk of {U} rows of {L} tokens")
+        Wc = N // U if U > 0 else 1
+        w0 = _int_in(w0, 0, (1 << 31) - 1, "w0")
+        _lib.check(self.lib.b4r_occlude_rows(
+            _ptr(tokens), _ptr(length), _ptr(labels), U, L, int(dst["positions"].shape[1]), V, int(mask_id), w0, Wc, _ptr(dst["tokens"]),
+            _ptr(dst["mask"]), _ptr(dst["len"]), _ptr(dst["positions"]), _ptr(dst["live"]), _ptr(dst["unit_pos"]), _ptr(dst["unit_item"]),
+            _ptr(dst["unit_label"]), _ptr(dst["removed"]), _stream(self.device)), "b4r_occlude_rows")
+
+    def attribution_select(self, base_logp: torch.Tensor, occ_logp: torch.Tensor, live: torch.Tensor, m: int):
+        """b4r_attribution_select: base_logp [U, K] fp32, occ_logp [U, W, K] fp32 (the log probabilities with unit w occluded), live
+        [U, W] int32 -> (w [U, K, m] int32, delta [U, K, m] fp32): per (user, item) the m live units with the largest base_logp -
+        occ_logp, ties to the lower w; -1 / -inf where there are fewer.  Negative deltas sort after the positive ones."""
+        if base_logp.ndim != 2 or occ_logp.ndim != 3 or live.ndim != 2 or base_logp.dtype != torch.float32 or \
+                occ_logp.dtype != torch.float32 or live.dtype != torch.int32 or occ_logp.shape[0] != base_logp.shape[0] or \
+                occ_logp.shape[2] != base_logp.shape[1] or live.shape != occ_logp.shape[:2]:
+            raise ValueError(f"base_logp is float32 [U, K], occ_logp float32 [U, W, K] and live int32 [U, W]; got {base_logp.dtype} "
+                             f"{tuple(base_logp.shape)}, {occ_logp.dtype} {tuple(occ_logp.shape)}, {live.dtype} {tuple(live.shape)}")
+        U, W, K = (int(x) for x in occ_logp.shape)
+        if not 1 <= W <= EXPLAIN_MAX_UNITS or not 1 <= K <= RANK_FULL_MAX_K:
+            raise ValueError(f"{W} units and {K} items: at most {EXPLAIN_MAX_UNITS} units and {RANK_FULL_MAX_K} items, at least one of each")
+        m = _int_in(m, 1, W, "m")
+        b, o, lv = (x.to(self.device).contiguous() for x in (base_logp, occ_logp, live))
+        out_w = torch.empty((U, K, m), dtype=torch.int32, device=self.device)
+        out_d = torch.empty((U, K, m), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.b4r_attribution_select(_ptr(b), _ptr(o), _ptr(lv), U, W, K, int(m), _ptr(out_w), _ptr(out_d),
+                                                   _stream(self.device)), "b4r_attribution_select")
+        return out_w, out_d
 
     def item_neighbours(self, item_ids: torch.Tensor, k: int, metric: str = "cosine", first_item: int = SPECIAL_IDS, allow=None,
                         row_filter=None):

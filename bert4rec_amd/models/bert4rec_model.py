@@ -619,6 +619,142 @@ class BERT4RecModel:
         return [[(ids_h[u][b], None if logp_h is None else logp_h[u][b], None if step_h is None else step_h[u][b])
                  for b in range(len(ids_h[u]))] for u in range(len(ids_h))]
 
+    def explain_tensor(self, encoder_input: Dict[str, torch.Tensor], target_ids, top: int = 3, labels=None, window: Optional[int] = None,
+                       exclude_seen: bool = True, exclude: Optional[torch.Tensor] = None, allow=None, row_filter=None,
+                       temperature: float = 1.0, rows_per_forward: int = 1024) -> Dict[str, torch.Tensor]:
+        """Which history items drove each recommendation, by occlusion: one history unit is removed from the row, the same forward
+        runs, and the log probability the explained item loses is the unit's attribution.  The occluded rows are built on the device
+        (b4r_occlude_rows, exactly as prepare_inference of the remaining items), their log probabilities come from b4r_score_dist
+        with the explained items as its queries, and b4r_attribution_select keeps the `top` units per item.  Nothing is read back
+        between the launches.
+        encoder_input is prepare_inference's format, as recommend_sequence_tensor takes it; that check is the call's one host
+        synchronisation (the largest row length travels back with it, and chunks of units that no row has are skipped).
+        target_ids [B, K] int64, 1 <= K <= 1024: the items to explain per batch row, e.g. recommend_tensor's ids; a -1 entry comes
+        back dead.  An integer k instead: the row's own top k under the same exclusions and filter, from the same base forward (they
+        are returned as target_ids).
+        A unit is one history item, counted from the most recent one (w = 0), or with labels [V] int32 (an item's category, -1 = none)
+        every history item of one category, which the category's most recent item stands for.  window: only the `window` most recent
+        history items are units (None: all L - 1); 1 <= top <= window.
+        The counterfactual is taken on the window the model saw: the row as prepared, minus the unit.  An item older than the row's
+        L - 1 does not slide back in.  A removed item stays excluded: every distribution of a row has the exclusions of the full row
+        (exclude_seen, exclude) and the row's filter (allow, row_filter [B]) at `temperature`, so all of them have the same support,
+        the log probabilities are comparable and a finite base_logp has finite occluded ones.
+        The units go through the forward in chunks of max(1, rows_per_forward // B) recency indices, B rows each.  The chunking
+        regroups the same rows: the result changes only where the encoder forward itself takes another launch form at another row
+        count, and then in the last bits of a log probability.
+        Returns a dict of device tensors (W = window):
+          target_ids     int64 [B, K]
+          base_logp      float32 [B, K]: the log probability of each explained item on the row as given (-inf: it cannot be served)
+          occluded_logp  float32 [B, W, K]: the same with unit w removed; -inf for a unit the row does not have
+          live           int32 [B, W]; unit_pos / unit_label / removed int32 [B, W], unit_item int64 [B, W]: the unit's history
+                         position, label (-1 in item mode), the number of items removed and its (most recent) item; -1 / 0 where dead
+          top_w, top_pos int32, top_item, top_label int64, top_delta float32 [B, K, top]: the units with the largest base_logp -
+                         occluded_logp, best first, ties to the more recent unit; a negative delta (the removal made the item more
+                         likely) sorts after the positive ones; -1 / -inf where fewer units are live
+          slot_index     int64 [B]: b*P+p, as recommend_tensor returns it."""
+        tokens_in = encoder_input.get("input_word_ids") if hasattr(encoder_input, "get") else None
+        if tokens_in is None or torch.as_tensor(tokens_in).ndim != 2:
+            raise ValueError("explain_tensor takes prepare_inference's batch: input_word_ids [B, L], input_mask and masked_lm_positions")
+        B, L = (int(x) for x in torch.as_tensor(tokens_in).shape)
+        top, W = engine_mod.check_explain_args(top, window, L, rows_per_forward=rows_per_forward)
+        own_k = None
+        if isinstance(target_ids, numbers.Integral) and not isinstance(target_ids, bool):
+            own_k = K = int(target_ids)
+        else:
+            target_ids = torch.as_tensor(target_ids)
+            if target_ids.ndim != 2 or target_ids.shape[0] != B or target_ids.dtype.is_floating_point or target_ids.dtype == torch.bool:
+                raise ValueError(f"target_ids must be an integer tensor [{B}, K], got {target_ids.dtype} of shape {tuple(target_ids.shape)}")
+            K = int(target_ids.shape[1])
+        engine_mod.check_explain_args(top, W, L, K=K)
+        if labels is not None:
+            labels = torch.as_tensor(labels)
+            if labels.ndim != 1 or labels.numel() != self.vocab_size or labels.dtype.is_floating_point or labels.dtype == torch.bool:
+                raise ValueError(f"labels must hold one integer per item [{self.vocab_size}], got {labels.dtype} of shape {tuple(labels.shape)}")
+        engine_mod.check_temperature(temperature)
+        if exclude is not None and torch.as_tensor(exclude).ndim != 2:
+            raise ValueError(f"exclude must be rank 2 [rows, ids], got shape {tuple(torch.as_tensor(exclude).shape)}")
+        allow, row_filter = engine_mod.check_item_filter(allow, row_filter, self.vocab_size)
+        if row_filter is not None and row_filter.numel() != B:
+            raise ValueError(f"row_filter has {row_filter.numel()} entries for a batch of {B}")
+        eng, dev = self.engine, self.device
+        cb, keep = eng.prepare_batch(encoder_input)
+        if cb.P == 0:
+            raise ValueError("explain_tensor needs masked_lm_positions")
+        P = cb.P
+        tokens, mask, pos = keep["input_word_ids"], keep["input_mask"], keep["masked_lm_positions"]
+        length, slot_p, max_len = engine_mod.check_rollout_batch(mask, pos, encoder_input.get("masked_lm_weights"),
+                                                                 return_max_len=True)    # the one host synchronisation
+        slots0 = torch.arange(B, dtype=torch.int64, device=dev) * P + slot_p
+        Wc = min(W, max(1, int(rows_per_forward) // max(B, 1)))
+        n_chunks = -(-W // Wc)
+        n_run = min(n_chunks, -(-max(max_len - 1, 0) // Wc))       # chunks that start inside the longest history
+        ninf = float("-inf")
+        out = {"occluded_logp": torch.full((B, n_chunks * Wc, K), ninf, dtype=torch.float32, device=dev),
+               "live": torch.zeros((B, n_chunks * Wc), dtype=torch.int32, device=dev),
+               "unit_pos": torch.full((B, n_chunks * Wc), -1, dtype=torch.int32, device=dev),
+               "unit_item": torch.full((B, n_chunks * Wc), -1, dtype=torch.int64, device=dev),
+               "unit_label": torch.full((B, n_chunks * Wc), -1, dtype=torch.int32, device=dev),
+               "removed": torch.zeros((B, n_chunks * Wc), dtype=torch.int32, device=dev)}
+        first = engine_mod.SPECIAL_IDS
+        rf = None if row_filter is None else row_filter.to(dev)
+        if B == 0:
+            target = torch.empty((0, K), dtype=torch.int64, device=dev)
+            base = torch.empty((0, K), dtype=torch.float32, device=dev)
+            ex0 = None
+        else:
+            hidden, _, _ = self._ranked_slot_hidden({"input_word_ids": tokens, "input_mask": mask, "masked_lm_positions": pos}, slots=slots0)
+            ex0 = self._excluded_rows(encoder_input, slots0, exclude_seen, exclude)
+            if own_k is not None:
+                target, _, _ = eng.rank_full(hidden, None, ex0, first, None, own_k, allow, rf)
+            else:
+                target = target_ids.to(device=dev, dtype=torch.int64).contiguous()
+            base = eng.score_distribution(hidden, None, ex0, first, None, allow, rf, temperature, target)[4]
+        if B > 0 and n_run > 0:
+            N = B * Wc
+            st = eng.explain_state(N, L, P)
+            len32 = length.to(torch.int32)
+            labels_d = None if labels is None else labels.to(device=dev, dtype=torch.int32).contiguous()
+            q_rep = target.repeat_interleave(Wc, dim=0)            # every occluded row asks for its user's items ...
+            ex_rep = None if ex0 is None else ex0.repeat_interleave(Wc, dim=0)   # ... under the exclusions of the user's FULL row
+            rf_rep = None if rf is None else rf.repeat_interleave(Wc)
+            slots_c = torch.arange(N, dtype=torch.int64, device=dev) * P
+            chunk = {"input_word_ids": st["tokens"], "input_mask": st["mask"], "masked_lm_positions": st["positions"]}
+            dead = torch.full((), ninf, dtype=torch.float32, device=dev)
+            for j in range(n_run):
+                eng.occlude_rows(tokens, len32, labels_d, j * Wc, st)
+                hidden, _, _ = self._ranked_slot_hidden(chunk, slots=slots_c)
+                lp = eng.score_distribution(hidden, None, ex_rep, first, None, allow, rf_rep, temperature, q_rep)[4]
+                cols = slice(j * Wc, (j + 1) * Wc)
+                live = st["live"].view(B, Wc)
+                out["occluded_logp"][:, cols] = torch.where(live[:, :, None] != 0, lp.view(B, Wc, K), dead)
+                out["live"][:, cols] = live
+                for name in ("unit_pos", "unit_item", "unit_label", "removed"):
+                    out[name][:, cols] = st[name].view(B, Wc)
+        out = {name: t[:, :W].contiguous() for name, t in out.items()}   # the last chunk may run past the window
+        if B > 0:
+            top_w, top_delta = eng.attribution_select(base, out["occluded_logp"], out["live"], top)
+        else:
+            top_w = torch.empty((0, K, top), dtype=torch.int32, device=dev)
+            top_delta = torch.empty((0, K, top), dtype=torch.float32, device=dev)
+        at = top_w.clamp(min=0).to(torch.int64).reshape(B, K * top)
+        none = top_w < 0
+        for name, src, dt in (("top_pos", "unit_pos", torch.int32), ("top_item", "unit_item", torch.int64), ("top_label", "unit_label", torch.int64)):
+            out[name] = out[src].gather(1, at).reshape(B, K, top).to(dt).masked_fill(none, -1)
+        out.update(target_ids=target, base_logp=base, top_w=top_w, top_delta=top_delta, slot_index=slots0)
+        return out
+
+    def explain(self, encoder_input: dict, target_ids, top: int = 3, labels=None, window: Optional[int] = None, exclude_seen: bool = True,
+                exclude=None, allow=None, row_filter=None, temperature: float = 1.0, rows_per_forward: int = 1024):
+        """explain_tensor as Python lists: per batch row one (item id, log probability, reasons) tuple per explained item, reasons =
+        [(history item id, label, history position, delta_logp), ...] best first, dead entries dropped."""
+        got = self.explain_tensor(encoder_input, target_ids, top, labels, window, exclude_seen, exclude, allow, row_filter, temperature,
+                                  rows_per_forward)
+        ids, base = got["target_ids"].cpu().tolist(), got["base_logp"].cpu().tolist()
+        item, label, where, delta = (got[name].cpu().tolist() for name in ("top_item", "top_label", "top_pos", "top_delta"))
+        return [[(ids[b][i], base[b][i], [(item[b][i][t], label[b][i][t], where[b][i][t], delta[b][i][t])
+                                          for t in range(len(item[b][i])) if where[b][i][t] >= 0])
+                 for i in range(len(ids[b]))] for b in range(len(ids))]
+
     def _rank_items_ragged(self, encoder_input, items):
         """Candidate lists of different lengths: one kernel call per distinct length."""
         flat = [c for row in items for c in row]

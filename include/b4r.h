@@ -541,6 +541,49 @@ int b4r_rollout_advance(const int64_t* tokens_in, const int32_t* len_in, const i
                         int32_t first_item, int64_t mask_id, int32_t t, int32_t ex_col, int64_t* tokens_out, int64_t* input_mask_out,
                         int32_t* len_out, int64_t* positions_out, int64_t* exclude_out, int64_t* path_out, float* path_logp_out,
                         b4r_stream_t stream);
+/* Occlusion explanations: which history items (or categories) drove a recommendation.  One history unit is removed, the same
+ * forward runs, and the log probability the explained item loses is the unit's attribution.  The two calls are the step logic
+ * between those forwards, so that nothing is read back in between.  Both only enqueue (one launch, one stream, no host sync,
+ * graph-capturable), use no atomics and are bitwise reproducible; every argument is checked before the launch, and nothing is read
+ * or written out of bounds whatever the token ids are.
+ *
+ * b4r_occlude_rows: the occluded batch rows of one chunk of recency indices.  tokens_in [U, L] int64, len_in [U] int32: row u holds
+ * len = clamp(len_in[u], 1, L) tokens and the last of them is the [MASK] placeholder (b4r_rollout_advance's convention), so its
+ * history is the positions 0 .. len - 2.  labels [V] int32 or NULL.  Output row n = u * Wc + c belongs to the recency index
+ * w = w0 + c, that is the history position p = len - 2 - w (w = 0: the most recent history item).
+ *   item mode (labels NULL): the row is live when p >= 0; the removed set is {p}.
+ *   group mode: g(q) = labels[tok[q]] when tok[q] lies in [0, V), else -1.  The row is live when p >= 0, g(p) >= 0 and no more
+ *     recent history position q in (p, len - 2] has g(q) == g(p): the most recent occurrence stands for its group, and every group
+ *     is occluded once.  The removed set is every history position q with g(q) == g(p).
+ * A live row: the remaining history tokens in their order, compacted to the front, then mask_id, then zeros; len_out = len -
+ * removed >= 1 (a history that is removed whole leaves the placeholder alone: a valid row);
+ *   input_mask_out [U * Wc, L] int64: position < len_out;  positions_out [U * Wc, P] int64: [len_out - 1, 0, 0, ...]
+ *   live_out = 1, unit_pos_out = p (int32), unit_item_out = tok[p] (int64), unit_label_out = g(p) (-1 in item mode), removed_out =
+ *   the size of the removed set
+ * which is the reference's prepare_inference of the row's items without the removed ones.
+ * A dead row is the user's row unchanged (tokens, mask, the clamped length, positions), so that it stays a valid sequence for the
+ * forward; live_out = 0, unit_pos_out = unit_item_out = unit_label_out = -1, removed_out = 0.
+ * 2 <= L <= 256, P >= 1, V >= 1, U >= 0, w0 >= 0, Wc >= 1, U * Wc < 2^31 (else B4R_E_SHAPE); tokens_in, len_in, tokens_out,
+ * input_mask_out, len_out, positions_out or live_out NULL, or an output that overlaps tokens_in (or len_out len_in): B4R_E_BADARG;
+ * unit_pos_out, unit_item_out, unit_label_out and removed_out may be NULL.  U = 0 succeeds and launches nothing.  One workgroup of
+ * 256 threads per output row, one thread per position; the compaction is a prefix count by wave ballots and one LDS exchange. */
+int b4r_occlude_rows(const int64_t* tokens_in, const int32_t* len_in, const int32_t* labels, int32_t U, int32_t L, int32_t P, int32_t V,
+                     int64_t mask_id, int32_t w0, int32_t Wc, int64_t* tokens_out, int64_t* input_mask_out, int32_t* len_out,
+                     int64_t* positions_out, int32_t* live_out, int32_t* unit_pos_out, int64_t* unit_item_out, int32_t* unit_label_out,
+                     int32_t* removed_out, b4r_stream_t stream);
+/* b4r_attribution_select: per (user, explained item) the m history units whose removal costs the most.  base_logp [U, K] fp32;
+ * occ_logp [U * W, K] fp32 (row u * W + w: the log probabilities of user u's K explained items with unit w occluded, e.g.
+ * b4r_score_dist's query_logp); live [U * W] int32 (b4r_occlude_rows' live_out).
+ *   delta(u, w, i) = fl32(base_logp[u][i] - occ_logp[u * W + w][i]): one fp32 subtraction
+ *   live(u, w, i)  = live[u * W + w] != 0 and base_logp[u][i] > -inf and occ_logp[u * W + w][i] > -inf (a NaN in either: dead)
+ * Outputs [U, K, m], t = 0 .. m-1: the live entries by delta descending (-0.0 counts as +0.0), ties to the lower w (the more recent
+ * unit): out_w (int32) = w, out_delta (fp32) = delta.  A negative delta is a result (removing the unit made the item more likely)
+ * and sorts after the positive ones.  With fewer than m live entries the tail is -1 / -inf.  Any output may be NULL.
+ * 1 <= W <= 256, 1 <= K <= 1024, 1 <= m <= W, U >= 0 (else B4R_E_SHAPE); a NULL input B4R_E_BADARG; U = 0 succeeds and launches
+ * nothing.  One workgroup of 256 threads per (user, tile of 16 explained items), the order by counting in LDS.  +inf log
+ * probabilities are outside the contract (inf - inf); nothing is read or written out of bounds. */
+int b4r_attribution_select(const float* base_logp, const float* occ_logp, const int32_t* live, int32_t U, int32_t W, int32_t K, int32_t m,
+                           int32_t* out_w, float* out_delta, b4r_stream_t stream);
 /* replaces the metric loop of bert4rec_evaluator.py:118-120 over evaluation_metrics.py:47-112 for a batch of ranks:
  * gain_sums[m] += sum over gt_rank[i] > 0 of gain_m(gt_rank[i]), users[0] += #{gt_rank[i] > 0}; double / int64 DEVICE
  * accumulators the caller reads once per evaluate().  family[m]: 0 count (gain 1), 1 hit@cutoff (rank <= k), 2 NDCG@cutoff
