@@ -182,15 +182,31 @@ def assert_forms(labels, c, mode, B):
 
 
 # ---- the train step ---------------------------------------------------------------------------------------------------------------
-def check_bf16_step(eng, cfg_o, batch, cb, hp_o, c, labels, name):
-    """one mode-2 Engine.train_step against the fp32 restatement within the bf16 bounds; AdamW and the counts exactly as in mode 1"""
+def bf16_gradient_errors(grads, grads_ref, cnt):
+    """the worst per-tensor cosine and relative norm error (each with its tensor's name) of a mode-2 gradient buffer over the valid
+    count against the restatement's gradients"""
+    big = max(float(g.norm()) for g in grads_ref.values())
+    worst_cos, worst_norm = (1.0, ""), (0.0, "")
+    for n, g in grads_ref.items():
+        if float(g.norm()) < 1e-3 * big:   # the key-bias gradient is analytically zero: rounding noise on both sides
+            continue
+        a = grads[n].double() / cnt
+        worst_cos = min(worst_cos, (cosine(a, g), n))
+        worst_norm = max(worst_norm, (float((a - g.double()).norm() / g.double().norm()), n))
+    return worst_cos, worst_norm
+
+
+def check_bf16_step(eng, cfg_o, batch, cb, hp_o, c, labels, name, step_fn=None, ref=None):
+    """one mode-2 Engine.train_step against the fp32 restatement within the bf16 bounds; AdamW and the counts exactly as in mode 1.
+    step_fn(hp, cb): the step under test (default eng.train_step); ref: the restatement (default cell_ref(c))"""
+    step_fn = step_fn or eng.train_step
     hp = hip_adamw_config(hp_o)
     eng.ensure_training_buffers()
     names = [n for n in eng.variable_names() if orc.is_trainable(n)]
     params_now = eng.export_named()
     m_now, v_now = eng.export_named(eng.adam_m), eng.export_named(eng.adam_v)
-    loss_ref, grads_ref, out_ref = cell_ref(c)(params_now, batch, cfg_o, training=True, rng=(SEED, 0))
-    labels[:] = launch_labels(lambda: eng.train_step(hp, cb))
+    loss_ref, grads_ref, out_ref = (ref or cell_ref(c))(params_now, batch, cfg_o, training=True, rng=(SEED, 0))
+    labels[:] = launch_labels(lambda: step_fn(hp, cb))
     torch.cuda.synchronize()
     st = eng.read_state()
     assert st["step"] == 1
@@ -201,14 +217,7 @@ def check_bf16_step(eng, cfg_o, batch, cb, hp_o, c, labels, name):
     own = float(eng.grads[:eng.n_params].double().pow(2).sum().sqrt()) / cnt
     assert own > 0.0 and abs(st["grad_norm"] - own) <= 2e-6 * own, (st["grad_norm"], own)
     loss_err = abs(st["loss_sum"] / cnt - float(loss_ref)) / abs(float(loss_ref))
-    big = max(float(g.norm()) for g in grads_ref.values())
-    worst_cos, worst_norm = (1.0, ""), (0.0, "")
-    for n, g in grads_ref.items():
-        if float(g.norm()) < 1e-3 * big:   # the key-bias gradient is analytically zero: rounding noise on both sides
-            continue
-        a = grads[n].double() / cnt
-        worst_cos = min(worst_cos, (cosine(a, g), n))
-        worst_norm = max(worst_norm, (float((a - g.double()).norm() / g.double().norm()), n))
+    worst_cos, worst_norm = bf16_gradient_errors(grads, grads_ref, cnt)
     print(f"{name} mode 2: loss rel err {loss_err:.2e}, worst cosine {worst_cos[0]:.6f} ({worst_cos[1]}), "
           f"worst rel norm err {worst_norm[0]:.2e} ({worst_norm[1]})")
     b_loss, b_cos, b_norm = BF16_CELL_BOUNDS.get(name, BF16_BOUNDS[c.head_dim])

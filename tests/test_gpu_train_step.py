@@ -103,11 +103,13 @@ def launch_labels(fn, cap=256):
     return [names.raw[j * stride:(j + 1) * stride].split(b"\0", 1)[0].decode() for j in range(n.value)]
 
 
-def run_and_check_train_step(eng, cfg_o, batch, cb, hp_o, step, seed, rel, labels=None, ref=orc.loss_and_grads, label_cap=256):
+def run_and_check_train_step(eng, cfg_o, batch, cb, hp_o, step, seed, rel, labels=None, ref=orc.loss_and_grads, label_cap=256,
+                             step_fn=None):
     """one Engine.train_step (the engine's state holds `step`), checked against the oracle as the module docstring says; returns the
     state it left and the oracle's gradient norm.  labels (a list): filled with the step's launches (launch timer, at most label_cap
     of them).  ref: the restatement the step is checked against (ref(params, batch, cfg_o, training=, rng=) -> loss, gradients,
-    outputs)"""
+    outputs).  step_fn(hp, cb): the step under test (default eng.train_step; tests/test_gpu_dp_matrix.py: the data-parallel step)"""
+    step_fn = step_fn or eng.train_step
     hp = hip_adamw_config(hp_o)
     eng.ensure_training_buffers()
     names = [n for n in eng.variable_names() if orc.is_trainable(n)]
@@ -115,9 +117,9 @@ def run_and_check_train_step(eng, cfg_o, batch, cb, hp_o, step, seed, rel, label
     m_now, v_now = eng.export_named(eng.adam_m), eng.export_named(eng.adam_v)
     loss_ref, grads_ref, out_ref = ref(params_now, batch, cfg_o, training=True, rng=(seed, step))
     if labels is None:
-        eng.train_step(hp, cb)
+        step_fn(hp, cb)
     else:
-        labels[:] = launch_labels(lambda: eng.train_step(hp, cb), label_cap)
+        labels[:] = launch_labels(lambda: step_fn(hp, cb), label_cap)
     torch.cuda.synchronize()
     st = eng.read_state()
     assert st["step"] == step + 1
@@ -127,12 +129,15 @@ def run_and_check_train_step(eng, cfg_o, batch, cb, hp_o, step, seed, rel, label
 
     # scalars
     assert_counts_match(st, batch, out_ref["mlm_logits"])
-    assert abs(st["loss_sum"] / cnt - float(loss_ref)) < LOGIT_TOL
     gnorm_ref = float(sum(g.double().pow(2).sum() for g in grads_ref.values()).sqrt())
+    print(f"MEASURED step {step}: loss err {abs(st['loss_sum'] / cnt - float(loss_ref)):.2e}, "
+          f"gradient norm rel err {abs(st['grad_norm'] - gnorm_ref) / gnorm_ref:.2e}")
+    assert abs(st["loss_sum"] / cnt - float(loss_ref)) < LOGIT_TOL
     assert abs(st["grad_norm"] - gnorm_ref) <= 2e-3 * gnorm_ref, (st["grad_norm"], gnorm_ref)
 
     # the gradient buffer
-    compare_grads(grads, grads_ref, cnt, rel=rel)
+    worst = compare_grads(grads, grads_ref, cnt, rel=rel)
+    print(f"MEASURED step {step}: worst gradient tensor rel err {worst[1]:.2e} ({worst[0]})")
 
     # what the optimizer consumed: m = b1 m_before + (1 - b1) clip_scale g
     clip_scale = min(1.0, hp_o.gradient_clip_norm / gnorm_ref)
