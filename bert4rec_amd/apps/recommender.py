@@ -28,7 +28,10 @@ list_quality measures what such lists are like beyond accuracy (b4r_list_metrics
 
 explain_batch / explain say why an item is recommended ("because you watched X"): one history item, or every history item of one
 category, is removed at a time on the device (b4r_occlude_rows), the model runs again, and the history items whose removal costs the
-recommendation the most log probability come back as its reasons (b4r_attribution_select)."""
+recommendation the most log probability come back as its reasons (b4r_attribution_select).
+
+audience turns the question round: given items, which users?  The users go through the model in batches, and the k most likely users
+of every item, its reach and its expected demand are kept on the device while the batches go by (b4r_audience_merge)."""
 import numbers
 
 import numpy as np
@@ -438,6 +441,77 @@ class Recommender:
         """explain_batch for one sequence: a list of (item, probability, reasons)."""
         return self.explain_batch([sequence], None if items is None else [list(items)], k=k, top=top, window=window, by_group=by_group,
                                   allowed_items=allowed_items, temperature=temperature)[0]
+
+    def audience(self, items, sequences, k: int = 100, min_probability=None, user_ids=None, batch_size: int = 256, allowed_items=None,
+                 allowed_items_per_user=None, temperature: float = 1.0) -> list:
+        """Given items, which users?  For every item of `items` (raw item keys) the k users most likely to take it next, out of the
+        users whose histories are `sequences`: "notify the 10 000 users most likely to want this release", "how many users would
+        take it with probability >= 1 %", "what demand to expect for these titles".  The users go through the model in batches of
+        batch_size (BERT4RecModel.audience_tensor); the k best users of every item, its reach and its expected demand stay on the
+        device while the batches go by and are read back once, after the last one.
+        user_ids: the users' names, one per sequence (default 0 .. n-1).  A user who has the item anywhere in their sequence, or who
+        may not be served it (allowed_items / allowed_items_per_user, as in recommend_batch), is never in its audience.
+        min_probability: None, or a number in (0, 1]: reach counts the users with at least that probability.
+        Returns one dict per item, in the order given: {"users": [(user, probability), ...] best first (ties to the user earlier in
+        `sequences`), "reach": the users who could be served it (with min_probability: with at least that probability),
+        "expected_demand": the sum of all those users' probabilities}.  An item the vocabulary does not know has no audience."""
+        engine_mod.check_temperature(temperature)
+        k, _ = engine_mod.check_audience_args(k, min_probability)
+        batch_size = engine_mod._int_in(batch_size, 1, (1 << 31) - 1, "batch_size")
+        items = list(items)
+        sequences = [list(seq) for seq in sequences]
+        names = list(range(len(sequences))) if user_ids is None else list(user_ids)
+        if len(names) != len(sequences):
+            raise ValueError(f"{len(names)} user ids for {len(sequences)} sequences")
+        if allowed_items is not None and allowed_items_per_user is not None:
+            raise ValueError("give allowed_items or allowed_items_per_user, not both")
+        user_filter = None
+        if allowed_items_per_user is not None:
+            lists = [list(row) for row in allowed_items_per_user]
+            if len(lists) != len(sequences):
+                raise ValueError(f"{len(lists)} allow-lists for {len(sequences)} sequences")
+            distinct = {}
+            user_filter = [distinct.setdefault(frozenset(self._known_tokens(row)), len(distinct)) for row in lists]
+        if not items:
+            return []
+        item_ids = torch.full((len(items),), -1, dtype=torch.int64)
+        for j, item in enumerate(items):
+            t = self._known_tokens([item])
+            if t:
+                item_ids[j] = t[0]
+        allow = None
+        if allowed_items is not None:
+            allow = self._item_mask(allowed_items)
+        elif user_filter is not None:
+            allow = torch.zeros((max(len(distinct), 1), self.model.vocab_size), dtype=torch.bool)
+            for tokens, f in distinct.items():
+                if tokens:
+                    allow[f, torch.as_tensor(sorted(tokens), dtype=torch.int64)] = True
+        if allow is not None:
+            allow = engine_mod.pack_item_filter(allow).to(self.model.engine.params.device)   # packed once, for every batch
+        tokenizer = self.dataloader.get_tokenizer()
+        state = self.model.engine.audience_state(item_ids, k)
+        for b0 in range(0, len(sequences), batch_size):
+            part = sequences[b0:b0 + batch_size]
+            batches = [self.dataloader.prepare_inference(list(seq)) for seq in part]
+            batch = {key: torch.from_numpy(np.concatenate([np.asarray(b[key]) for b in batches], axis=0)) for key in batches[0]}
+            seen = [tokenizer.tokenize(seq) for seq in part]
+            exclude = torch.full((len(seen), max(1, max(len(t) for t in seen))), -1, dtype=torch.int64)
+            for i, t in enumerate(seen):
+                if t:
+                    exclude[i, :len(t)] = torch.as_tensor(t, dtype=torch.int64)
+            row_filter = None if user_filter is None else torch.as_tensor(user_filter[b0:b0 + batch_size], dtype=torch.int32)
+            state = self.model.audience_tensor(batch, item_ids, state=state, k=k, user_ids=torch.arange(b0, b0 + len(part)),
+                                               min_probability=min_probability, exclude_seen=False, exclude=exclude, allow=allow,
+                                               row_filter=row_filter, temperature=temperature)
+        # everything in one copy: the probabilities travel as the bits of their float64
+        both = torch.cat([state["users"], torch.exp(state["logp"].to(torch.float64)).view(torch.int64), state["reach"][:, None],
+                          state["demand"][:, None]], dim=1).cpu()
+        users_h = both[:, :k].tolist()
+        prob_h = both[:, k:2 * k].contiguous().view(torch.float64).tolist()
+        reach_h, demand_h = both[:, 2 * k].tolist(), both[:, 2 * k + 1].tolist()
+        return [{"users": [(names[u], p) for u, p in zip(users_h[j], prob_h[j]) if u >= 0], "reach": int(reach_h[j]),
+                 "expected_demand": demand_h[j] / engine_mod.AUDIENCE_DEMAND_ONE} for j in range(len(items))]
 
     def similar_items(self, items, k: int = 10, metric: str = "cosine", allowed_items=None) -> list:
         """For every item of `items` the k nearest items of the learned item table, as detokenized lists (best first); metric

@@ -306,6 +306,42 @@ def check_explain_args(top, window, L: int, K: Optional[int] = None, rows_per_fo
     return top, window
 
 
+AUDIENCE_MAX_K = 1024     # b4r_audience_merge: K
+AUDIENCE_DEMAND_ONE = float(1 << 40)   # one expected taker in the units of `demand`
+
+
+def check_audience_args(k, min_probability=None) -> Tuple[int, float]:
+    """Argument checks of an audience selection that need no GPU: k users per item in [1, 1024]; min_probability None (every live
+    user counts towards reach) or a number in (0, 1].  Returns (k, min_logp) with min_logp = fl32(log(min_probability)), -inf for
+    None: the threshold is rounded once, here, and compared as it is on the device."""
+    k = _int_in(k, 1, AUDIENCE_MAX_K, "k")
+    if min_probability is None:
+        return k, -math.inf
+    if isinstance(min_probability, bool) or not isinstance(min_probability, numbers.Real) or not 0.0 < min_probability <= 1.0:
+        raise ValueError(f"min_probability must be a number in (0, 1], got {min_probability!r}")
+    return k, C.c_float(math.log(float(min_probability))).value
+
+
+def check_audience_items(item_ids) -> torch.Tensor:
+    """item_ids of an audience selection: [Q] integers, Q >= 1 (int64 after the conversion; an id outside the vocabulary has no
+    audience)."""
+    t = torch.as_tensor(item_ids)
+    if t.ndim != 1 or t.numel() < 1 or t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError(f"item_ids are [Q] integer token ids, Q >= 1, got {t.dtype} of shape {tuple(t.shape)}")
+    return t.to(torch.int64)
+
+
+def check_audience_state(state, item_ids: torch.Tensor, k: int) -> None:
+    """A state belongs to the items and the k it was created for (compared on the host: state["item_ids"] is a host tensor)."""
+    if not hasattr(state, "get") or any(state.get(key) is None for key in ("users", "logp", "reach", "demand", "item_ids")):
+        raise ValueError("state is what audience_tensor returned: a dict with users, logp, reach, demand and item_ids")
+    if not torch.equal(torch.as_tensor(state["item_ids"]).cpu(), item_ids.cpu()):
+        raise ValueError("this state belongs to other item_ids")
+    Q = int(item_ids.numel())
+    if tuple(state["users"].shape) != (Q, k) or tuple(state["logp"].shape) != (Q, k):
+        raise ValueError(f"this state keeps k = {int(state['users'].shape[-1])} users per item, not {k}")
+
+
 SIMILARITY_METRICS = {"dot": _lib.SIM_DOT, "cosine": _lib.SIM_COSINE}
 
 
@@ -1226,6 +1262,47 @@ class Engine:
         _lib.check(self.lib.b4r_attribution_select(_ptr(b), _ptr(o), _ptr(lv), U, W, K, int(m), _ptr(out_w), _ptr(out_d),
                                                    _stream(self.device)), "b4r_attribution_select")
         return out_w, out_d
+
+    def audience_state(self, item_ids: torch.Tensor, k: int) -> Dict[str, object]:
+        """The initial state of an audience selection over item_ids [Q]: users [Q, k] int64 = -1, logp [Q, k] fp32 = -inf, reach and
+        demand [Q] int64 = 0 on the device; item_ids on the host (what the state is checked against) and on the device (query_ids);
+        next_user: the id the next unnamed batch row gets."""
+        item_ids = check_audience_items(item_ids)
+        k, _ = check_audience_args(k)
+        Q, dev = int(item_ids.numel()), self.device
+        return {"users": torch.full((Q, k), -1, dtype=torch.int64, device=dev),
+                "logp": torch.full((Q, k), -math.inf, dtype=torch.float32, device=dev),
+                "reach": torch.zeros((Q,), dtype=torch.int64, device=dev), "demand": torch.zeros((Q,), dtype=torch.int64, device=dev),
+                "item_ids": item_ids.cpu().clone(), "query_ids": item_ids.to(dev), "next_user": 0}
+
+    def audience_merge(self, logp: torch.Tensor, users: torch.Tensor, best_logp: torch.Tensor, reach: Optional[torch.Tensor] = None,
+                       demand: Optional[torch.Tensor] = None, user_ids: Optional[torch.Tensor] = None, user0: int = 0,
+                       min_logp: float = -math.inf) -> None:
+        """b4r_audience_merge: logp [R, Q] fp32 (unit column stride; row r = the log probabilities of user r for the Q items) is merged
+        into the running lists users [Q, K] int64 / best_logp [Q, K] fp32, in place: per item the K best live users by logp
+        descending, ties to the lower user id; reach [Q] int64 += the live users with logp >= min_logp, demand [Q] int64 += the sum
+        of round(exp(logp) * 2^40) over the live users.  user_ids [R] int64 or None (user0 + r); a negative id is dead."""
+        if logp.ndim != 2 or logp.dtype != torch.float32 or not logp.is_cuda or (logp.shape[1] > 0 and logp.stride(1) != 1):
+            raise ValueError(f"logp must be a float32 tensor [R, Q] on the device with unit column stride, got {logp.dtype} {tuple(logp.shape)}")
+        R, Q = (int(x) for x in logp.shape)
+        if users.ndim != 2 or users.dtype != torch.int64 or best_logp.dtype != torch.float32 or users.shape[0] != Q or \
+                best_logp.shape != users.shape or not users.is_contiguous() or not best_logp.is_contiguous() or not users.is_cuda or \
+                not best_logp.is_cuda:
+            raise ValueError(f"the running lists are contiguous int64 / float32 tensors [{Q}, K] on the device, got {users.dtype} "
+                             f"{tuple(users.shape)} and {best_logp.dtype} {tuple(best_logp.shape)}")
+        K = _int_in(int(users.shape[1]), 1, AUDIENCE_MAX_K, "K")
+        for name, t in (("reach", reach), ("demand", demand)):
+            if t is not None and (t.dtype != torch.int64 or t.shape != (Q,) or not t.is_contiguous() or not t.is_cuda):
+                raise ValueError(f"{name} must be a contiguous int64 tensor [{Q}] on the device")
+        if user_ids is not None and (user_ids.dtype != torch.int64 or user_ids.shape != (R,) or not user_ids.is_contiguous() or not user_ids.is_cuda):
+            raise ValueError(f"user_ids must be a contiguous int64 tensor [{R}] on the device")
+        if isinstance(min_logp, bool) or not isinstance(min_logp, numbers.Real) or math.isnan(min_logp):
+            raise ValueError(f"min_logp must be a number, got {min_logp!r}")
+        if R == 0:
+            return
+        ld = int(logp.stride(0)) if R > 1 else Q
+        _lib.check(self.lib.b4r_audience_merge(_ptr(logp), ld, R, Q, _ptr(user_ids), check_stream0(user0), float(min_logp), K, _ptr(users),
+                                               _ptr(best_logp), _ptr(reach), _ptr(demand), _stream(self.device)), "b4r_audience_merge")
 
     def item_neighbours(self, item_ids: torch.Tensor, k: int, metric: str = "cosine", first_item: int = SPECIAL_IDS, allow=None,
                         row_filter=None):

@@ -755,6 +755,74 @@ class BERT4RecModel:
                                           for t in range(len(item[b][i])) if where[b][i][t] >= 0])
                  for i in range(len(ids[b]))] for b in range(len(ids))]
 
+    def audience_tensor(self, encoder_input: Dict[str, torch.Tensor], item_ids, state=None, k: int = 100, user_ids=None,
+                        min_probability=None, exclude_seen: bool = True, exclude: Optional[torch.Tensor] = None, allow=None,
+                        row_filter=None, temperature: float = 1.0):
+        """Given items, which users?  One batch of users is merged into the k most likely users of each of item_ids [Q] (int64 token
+        ids): score_distribution_tensor's forward, exclusions (exclude_seen, exclude) and filter (allow, row_filter [B]) at
+        `temperature`, with the Q ids as the queries of every row (in chunks of 1024), then b4r_audience_merge of the [B, Q] log
+        probabilities into `state`.  Call it once per batch of users and read the state once, after the last batch: it keeps
+        O(Q * k) on the device, no [users, items] matrix, and nothing is read back here.
+        A user who has seen an item, may not be served it, or an id outside the vocabulary has log probability -inf and is never in
+        that item's audience.
+        state: None creates one; else what an earlier call returned for the same item_ids and k (ValueError otherwise).  A dict:
+          users   int64 [Q, k]: per item the k most likely users, best first, ties to the lower user id; -1 where there are fewer
+          logp    float32 [Q, k]: their log probabilities (-inf in the tail)
+          reach   int64 [Q]: the users with probability >= min_probability (None: every user who could be served the item)
+          demand  int64 [Q]: the sum of the users' probabilities in units of 2^-40, the expected number of takers
+          item_ids (host) / query_ids (device) int64 [Q], next_user: the id of the next unnamed row
+        The result depends only on the set of (user, log probability) pairs: not on the batches the users came in, nor on their
+        order, bit for bit (the log probabilities themselves come from the forward, which may take another launch form at another
+        batch size).
+        user_ids [B] int64 >= 0 name the batch rows (distinct over all calls); None: state["next_user"] + row, which then advances.
+        The batch is prepare_inference's: exactly one ranked slot per row (masked_lm_weights; without them P must be 1)."""
+        engine_mod.check_temperature(temperature)
+        k, min_logp = engine_mod.check_audience_args(k, min_probability)
+        item_ids = engine_mod.check_audience_items(item_ids)
+        if state is not None:
+            engine_mod.check_audience_state(state, item_ids, k)
+        tokens_in = encoder_input.get("input_word_ids") if hasattr(encoder_input, "get") else None
+        positions = encoder_input.get("masked_lm_positions") if tokens_in is not None else None
+        if tokens_in is None or positions is None or torch.as_tensor(tokens_in).ndim != 2 or torch.as_tensor(positions).ndim != 2:
+            raise ValueError("audience_tensor takes prepare_inference's batch: input_word_ids [B, L] and masked_lm_positions [B, P]")
+        B, P = int(torch.as_tensor(tokens_in).shape[0]), int(torch.as_tensor(positions).shape[1])
+        weights = encoder_input.get("masked_lm_weights")
+        if weights is None:
+            if P != 1:
+                raise ValueError(f"an audience batch has exactly one ranked slot per row: without masked_lm_weights P must be 1, got {P}")
+            slot = torch.zeros((B,), dtype=torch.int64)
+        else:
+            w = torch.as_tensor(weights).reshape(B, P) != 0          # checked where the tensor lives: a host batch costs no device sync
+            if not bool((w.sum(dim=1) == 1).all()):
+                raise ValueError("an audience batch has exactly one ranked slot per row (prepare_inference's format)")
+            slot = w.to(torch.int64).argmax(dim=1)
+        if user_ids is not None:
+            user_ids = engine_mod.check_sample_streams(user_ids, B)   # [B] integers -> int64
+        allow, row_filter = engine_mod.check_item_filter(allow, row_filter, self.vocab_size)
+        dev = self.device
+        if state is None:
+            state = self.engine.audience_state(item_ids, k)
+        if B == 0:
+            return state
+        slots = torch.arange(B, dtype=torch.int64, device=dev) * P + slot.to(dev)
+        hidden, slots, _ = self._ranked_slot_hidden(encoder_input, slots=slots)
+        ex_rows = self._excluded_rows(encoder_input, slots, exclude_seen, exclude)
+        user0 = 0
+        if user_ids is None:
+            user0 = int(state["next_user"])
+            state["next_user"] = user0 + B
+        else:
+            user_ids = user_ids.to(dev).contiguous()
+        Q = int(item_ids.numel())
+        for c0 in range(0, Q, engine_mod.RANK_FULL_MAX_K):
+            c1 = min(Q, c0 + engine_mod.RANK_FULL_MAX_K)
+            queries = state["query_ids"][c0:c1].unsqueeze(0).expand(B, c1 - c0)
+            logp = self.engine.score_distribution(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, allow, row_filter, temperature,
+                                                  queries)[4]
+            self.engine.audience_merge(logp, state["users"][c0:c1], state["logp"][c0:c1], state["reach"][c0:c1], state["demand"][c0:c1],
+                                       user_ids, user0, min_logp)
+        return state
+
     def _rank_items_ragged(self, encoder_input, items):
         """Candidate lists of different lengths: one kernel call per distinct length."""
         flat = [c for row in items for c in row]

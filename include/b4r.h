@@ -584,6 +584,37 @@ int b4r_occlude_rows(const int64_t* tokens_in, const int32_t* len_in, const int3
  * probabilities are outside the contract (inf - inf); nothing is read or written out of bounds. */
 int b4r_attribution_select(const float* base_logp, const float* occ_logp, const int32_t* live, int32_t U, int32_t W, int32_t K, int32_t m,
                            int32_t* out_w, float* out_delta, b4r_stream_t stream);
+/* Audience selection: given an item, which users?  b4r_audience_merge is the step ACROSS users: it merges one batch of users into
+ * the K most likely users of each of Q items, which stay on the device while the batches of users go by (O(Q * K) state, no
+ * [users, items] matrix), and counts reach and expected demand.  It only enqueues (one launch, one stream, no host sync,
+ * graph-capturable), uses no atomics and is bitwise reproducible; every argument is checked before the launch, and nothing is read
+ * or written out of bounds whatever the ids and values are.
+ *
+ * logp [R, ld] fp32, columns 0 .. Q-1: row r holds user r's log probability of the Q items, i.e. b4r_score_dist's query_logp when
+ * every row queries the same Q ids.  user(r) = user_ids ? user_ids[r] : user0 + r (int64, wrapping).
+ *   live(r, q) = user(r) >= 0 and logp[r][q] > -inf.  A NaN is dead; +inf and values above 0 are outside the contract.  -inf is what
+ *   b4r_score_dist returns for an item the user has seen, may not be served, or that is outside the vocabulary: a user who already
+ *   owns an item is never in its audience.
+ * Running lists best_user (int64), best_logp (fp32) [Q, K], in and out: an entry is live when best_user >= 0 and best_logp > -inf.
+ * The caller initialises best_user = -1, best_logp = -inf and reach = demand = 0; after that the lists are what the earlier calls
+ * left (sorted, the live entries first).
+ * Per item q the result is the K best of (live running entries U live new entries) in the order: logp descending (-0.0 counts as
+ * +0.0; the bits written are the entry's own), ties to the lower user id, and where logp and id are both equal the running entry
+ * before the new one.  The list is written back in that order, the tail is -1 / -inf.  User ids are meant to be distinct across
+ * calls.
+ * The merge is associative and commutative: best_user, best_logp, reach and demand after a sequence of calls depend only on the
+ * set of (user, logp) pairs, not on how the users were cut into calls nor on the order of the calls, bit for bit.
+ *   reach[q]  += #{r : live(r, q) and logp[r][q] >= min_logp};  min_logp = -inf counts every live user
+ *   demand[q] += sum over live r of llrint(exp((double) logp[r][q]) * 2^40): an int64 in units of 2^-40, the expected number of
+ *                takers; integers, so that the sum does not depend on the order.  At most 2^22 live users per item over all calls.
+ * reach and demand [Q] int64, in and out; either may be NULL.
+ * 1 <= K <= 1024, Q >= 1, 0 <= R < 2^31 - 256, ld >= Q (else B4R_E_SHAPE); logp, best_user or best_logp NULL, or a NaN min_logp:
+ * B4R_E_BADARG.  R = 0 succeeds and launches nothing.  One workgroup of 256 threads owns a tile of 4 items: the rows go by in
+ * passes of 256, an entry that is live and comes before the K-th entry of a full list is compacted into the item's pending buffer in
+ * LDS (wave ballots), and a buffer that fills up is merged into the list: the pending entries ordered by counting, their places
+ * among the running entries (and the running entries' among them) found by bisection. */
+int b4r_audience_merge(const float* logp, int32_t ld, int32_t R, int32_t Q, const int64_t* user_ids, int64_t user0, float min_logp,
+                       int32_t K, int64_t* best_user, float* best_logp, int64_t* reach, int64_t* demand, b4r_stream_t stream);
 /* replaces the metric loop of bert4rec_evaluator.py:118-120 over evaluation_metrics.py:47-112 for a batch of ranks:
  * gain_sums[m] += sum over gt_rank[i] > 0 of gain_m(gt_rank[i]), users[0] += #{gt_rank[i] > 0}; double / int64 DEVICE
  * accumulators the caller reads once per evaluate().  family[m]: 0 count (gain 1), 1 hit@cutoff (rank <= k), 2 NDCG@cutoff
