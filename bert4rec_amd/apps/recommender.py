@@ -72,6 +72,67 @@ class Recommender:
             mask[torch.as_tensor(tokens, dtype=torch.int64)] = True
         return mask
 
+    def _token_ids(self, items) -> torch.Tensor:
+        """The token id of every item, int64 [len(items)]; -1 for an item the vocabulary does not know."""
+        ids = torch.full((len(items),), -1, dtype=torch.int64)
+        for j, item in enumerate(items):
+            t = self._known_tokens([item])
+            if t:
+                ids[j] = t[0]
+        return ids
+
+    @staticmethod
+    def _padded_ids(token_lists) -> torch.Tensor:
+        """Lists of token ids as one int64 matrix, -1 padded to the longest list (at least one column)."""
+        ids = torch.full((len(token_lists), max(1, max(len(t) for t in token_lists))), -1, dtype=torch.int64)
+        for i, t in enumerate(token_lists):
+            if t:
+                ids[i, :len(t)] = torch.as_tensor(t, dtype=torch.int64)
+        return ids
+
+    def _requests(self, sequences):
+        """One request per sequence: (prepare_inference's batches stacked into one, exclude [n, longest] int64: every item of the
+        sequence, also those before the model's window, -1 padded)."""
+        batches = [self.dataloader.prepare_inference(list(seq)) for seq in sequences]
+        batch = {key: torch.from_numpy(np.concatenate([np.asarray(b[key]) for b in batches], axis=0)) for key in batches[0]}
+        return batch, self._padded_ids([self.dataloader.get_tokenizer().tokenize(seq) for seq in sequences])
+
+    def _allow_filters(self, n_sequences: int, allowed_items, allowed_items_per_user):
+        """allowed_items (one iterable of items for all users) or allowed_items_per_user (one per sequence; lists with the same known
+        items share one filter) -> (allow: a bool mask [V], masks [F, V] or None; the filter index of every sequence int32 [n] or
+        None).  The argument errors come before the tokenizer is touched."""
+        if allowed_items is not None and allowed_items_per_user is not None:
+            raise ValueError("give allowed_items or allowed_items_per_user, not both")
+        if allowed_items is not None:
+            return self._item_mask(allowed_items), None
+        if allowed_items_per_user is None:
+            return None, None
+        lists = [list(items) for items in allowed_items_per_user]
+        if len(lists) != n_sequences:
+            raise ValueError(f"{len(lists)} allow-lists for {n_sequences} sequences")
+        distinct = {}
+        user_filter = [distinct.setdefault(frozenset(self._known_tokens(items)), len(distinct)) for items in lists]
+        allow = torch.zeros((max(len(distinct), 1), self.model.vocab_size), dtype=torch.bool)
+        for tokens, f in distinct.items():
+            if tokens:
+                allow[f, torch.as_tensor(sorted(tokens), dtype=torch.int64)] = True
+        return allow, torch.as_tensor(user_filter, dtype=torch.int32)
+
+    def _label_tokens(self, look, catalogue=None):
+        """look(item) = the item's hashable group label or None, asked for every item of the vocabulary -> (the group index of every
+        token id, int64 [V] with -1 = no group; {label: group index} in order of first appearance).  catalogue: the (token, item)
+        pairs, for a caller that labels them more than once."""
+        index, groups = {}, np.full(self.model.vocab_size, -1, dtype=np.int64)
+        for t, item in catalogue or self._catalogue():
+            label = look(item)
+            if label is not None:
+                groups[t] = index.setdefault(label, len(index))
+        return groups, index
+
+    def _catalogue(self) -> list:
+        tokens = list(range(SPECIAL_IDS, self.model.vocab_size))
+        return list(zip(tokens, self.dataloader.get_tokenizer().detokenize(tokens)))
+
     def _item_groups(self, max_per_group) -> list:
         """(labels, cap) or a list of such pairs -> pack_item_groups specs, through the tokenizer.  labels: a mapping (or a callable)
         from a detokenized item to a hashable group label; an item it does not know, or maps to None, is in no group.  cap: one int
@@ -79,9 +140,7 @@ class Recommender:
         and live on the model's device, so nothing of them outlives the call."""
         pairs = [max_per_group] if isinstance(max_per_group, tuple) and len(max_per_group) == 2 and \
             not isinstance(max_per_group[0], tuple) else list(max_per_group)
-        V = self.model.vocab_size
-        tokens = list(range(SPECIAL_IDS, V))
-        items = self.dataloader.get_tokenizer().detokenize(tokens)
+        catalogue = self._catalogue()
         specs = []
         for pair in pairs:
             if not isinstance(pair, (tuple, list)) or len(pair) != 2:
@@ -90,11 +149,7 @@ class Recommender:
             look = labels if callable(labels) else getattr(labels, "get", None)   # (a callable's own errors are the caller's to see)
             if look is None:
                 raise ValueError("labels maps an item to its group label: a mapping or a callable")
-            index, groups = {}, np.full(V, -1, dtype=np.int64)
-            for t, item in zip(tokens, items):
-                label = look(item)
-                if label is not None:
-                    groups[t] = index.setdefault(label, len(index))
+            groups, index = self._label_tokens(look, catalogue)
             if hasattr(cap, "get"):
                 big = (1 << 31) - 1
                 caps = np.full(len(index), big, dtype=np.int64)
@@ -171,43 +226,20 @@ class Recommender:
             raise ValueError("temperature scales the probabilities: give return_probabilities, min_probability or sample_seed as well")
         tokenizer = self.dataloader.get_tokenizer()
         sequences = [list(seq) for seq in sequences]
-        if allowed_items is not None and allowed_items_per_user is not None:
-            raise ValueError("give allowed_items or allowed_items_per_user, not both")
-        user_filter = None
-        if allowed_items_per_user is not None:
-            lists = [list(items) for items in allowed_items_per_user]
-            if len(lists) != len(sequences):
-                raise ValueError(f"{len(lists)} allow-lists for {len(sequences)} sequences")
-            distinct = {}
-            user_filter = [distinct.setdefault(frozenset(self._known_tokens(items)), len(distinct)) for items in lists]
+        allow, user_filter = self._allow_filters(len(sequences), allowed_items, allowed_items_per_user)
         quotas = None if max_per_group is None else self._item_groups(max_per_group)   # packed once per call
         if not sequences:
             return []
-        batches = [self.dataloader.prepare_inference(list(seq)) for seq in sequences]
-        batch = {key: torch.from_numpy(np.concatenate([np.asarray(b[key]) for b in batches], axis=0)) for key in batches[0]}
-        seen = [tokenizer.tokenize(seq) for seq in sequences]
-        width = max(1, max(len(t) for t in seen))
-        exclude = torch.full((len(seen), width), -1, dtype=torch.int64)
-        for i, t in enumerate(seen):
-            if t:
-                exclude[i, :len(t)] = torch.as_tensor(t, dtype=torch.int64)
-        allow = row_filter = None
-        if allowed_items is not None:
-            allow = self._item_mask(allowed_items)
-        elif user_filter is not None:
-            allow = torch.zeros((len(distinct), self.model.vocab_size), dtype=torch.bool)
-            for tokens, f in distinct.items():
-                if tokens:
-                    allow[f, torch.as_tensor(sorted(tokens), dtype=torch.int64)] = True
-            # one filter index per ranked slot: the slots of recommend_tensor are those with masked_lm_weights != 0, in batch order
-            w = batch["masked_lm_weights"] != 0
-            row_filter = torch.as_tensor(user_filter, dtype=torch.int32)[torch.nonzero(w, as_tuple=True)[0]]
+        batch, exclude = self._requests(sequences)
+        # one filter index and one stream per ranked slot: the slots of recommend_tensor are those with masked_lm_weights != 0, in
+        # batch order
+        slot_user = torch.nonzero(batch["masked_lm_weights"] != 0, as_tuple=True)[0]
+        row_filter = None if user_filter is None else user_filter[slot_user]
         slot_streams = None
         if user_streams is not None:
             if user_streams.numel() != len(sequences):
                 raise ValueError(f"{user_streams.numel()} user streams for {len(sequences)} sequences")
-            # one stream per ranked slot, as row_filter above
-            slot_streams = user_streams[torch.nonzero(batch["masked_lm_weights"] != 0, as_tuple=True)[0]]
+            slot_streams = user_streams[slot_user]
         got = self.model.recommend_tensor(batch, k=k, exclude_seen=False, exclude=exclude, allow=allow, row_filter=row_filter,
                                           diversity=diversity, pool=candidate_pool, max_per_group=quotas,
                                           return_distribution=calibrated, temperature=temperature, sample_seed=sample_seed,
@@ -258,34 +290,12 @@ class Recommender:
             user_streams = engine_mod.check_sample_streams(user_streams)
         tokenizer = self.dataloader.get_tokenizer()
         sequences = [list(seq) for seq in sequences]
-        if allowed_items is not None and allowed_items_per_user is not None:
-            raise ValueError("give allowed_items or allowed_items_per_user, not both")
         if user_streams is not None and user_streams.numel() != len(sequences):
             raise ValueError(f"{user_streams.numel()} user streams for {len(sequences)} sequences")
-        allow = row_filter = None
-        if allowed_items_per_user is not None:
-            lists = [list(items) for items in allowed_items_per_user]
-            if len(lists) != len(sequences):
-                raise ValueError(f"{len(lists)} allow-lists for {len(sequences)} sequences")
-            distinct = {}
-            row_filter = torch.as_tensor([distinct.setdefault(frozenset(self._known_tokens(items)), len(distinct)) for items in lists],
-                                         dtype=torch.int32)
-            allow = torch.zeros((max(len(distinct), 1), self.model.vocab_size), dtype=torch.bool)
-            for tokens, f in distinct.items():
-                if tokens:
-                    allow[f, torch.as_tensor(sorted(tokens), dtype=torch.int64)] = True
-        elif allowed_items is not None:
-            allow = self._item_mask(allowed_items)
+        allow, row_filter = self._allow_filters(len(sequences), allowed_items, allowed_items_per_user)
         if not sequences:
             return []
-        batches = [self.dataloader.prepare_inference(list(seq)) for seq in sequences]
-        batch = {key: torch.from_numpy(np.concatenate([np.asarray(b[key]) for b in batches], axis=0)) for key in batches[0]}
-        seen = [tokenizer.tokenize(seq) for seq in sequences]
-        width = max(1, max(len(t) for t in seen))
-        exclude = torch.full((len(seen), width), -1, dtype=torch.int64)
-        for i, t in enumerate(seen):
-            if t:
-                exclude[i, :len(t)] = torch.as_tensor(t, dtype=torch.int64)
+        batch, exclude = self._requests(sequences)
         want_logp = bool(return_probabilities) or beams > 1
         ids, step_logp, logp, _ = self.model.recommend_sequence_tensor(
             batch, steps, beams=beams, expand=expand, exclude_seen=False, exclude=exclude, allow=allow, row_filter=row_filter,
@@ -330,13 +340,8 @@ class Recommender:
             if groups.size and groups.max() >= 1 << 31:
                 raise ValueError("by_group labels must fit in int32")
             return torch.from_numpy(groups.astype(np.int32)), None
-        tokens = list(range(SPECIAL_IDS, V))
-        index, groups = {}, np.full(V, -1, dtype=np.int32)
-        for t, item in zip(tokens, self.dataloader.get_tokenizer().detokenize(tokens)):
-            label = look(item)
-            if label is not None:
-                groups[t] = index.setdefault(label, len(index))
-        return torch.from_numpy(groups), list(index)
+        groups, index = self._label_tokens(look)
+        return torch.from_numpy(groups.astype(np.int32)), list(index)
 
     def explain_batch(self, sequences, items=None, k: int = 1, top: int = 3, window=None, by_group=None, allowed_items=None,
                       allowed_items_per_user=None, temperature: float = 1.0) -> list:
@@ -366,45 +371,15 @@ class Recommender:
                 raise ValueError(f"{len(items)} item lists for {len(sequences)} sequences")
             if sequences and not 1 <= max(len(row) for row in items) <= engine_mod.RANK_FULL_MAX_K:
                 raise ValueError(f"between 1 and {engine_mod.RANK_FULL_MAX_K} items are explained per sequence")
-        if allowed_items is not None and allowed_items_per_user is not None:
-            raise ValueError("give allowed_items or allowed_items_per_user, not both")
-        allow = row_filter = None
-        if allowed_items_per_user is not None:
-            lists = [list(row) for row in allowed_items_per_user]
-            if len(lists) != len(sequences):
-                raise ValueError(f"{len(lists)} allow-lists for {len(sequences)} sequences")
-            distinct = {}
-            row_filter = torch.as_tensor([distinct.setdefault(frozenset(self._known_tokens(row)), len(distinct)) for row in lists],
-                                         dtype=torch.int32)
-            allow = torch.zeros((max(len(distinct), 1), self.model.vocab_size), dtype=torch.bool)
-            for tokens, f in distinct.items():
-                if tokens:
-                    allow[f, torch.as_tensor(sorted(tokens), dtype=torch.int64)] = True
-        elif allowed_items is not None:
-            allow = self._item_mask(allowed_items)
+        allow, row_filter = self._allow_filters(len(sequences), allowed_items, allowed_items_per_user)
         labels = names = None
         if by_group is not None:
             labels, names = self._group_labels(by_group)
         if not sequences:
             return []
         tokenizer = self.dataloader.get_tokenizer()
-        batches = [self.dataloader.prepare_inference(list(seq)) for seq in sequences]
-        batch = {key: torch.from_numpy(np.concatenate([np.asarray(b[key]) for b in batches], axis=0)) for key in batches[0]}
-        seen = [tokenizer.tokenize(seq) for seq in sequences]
-        width = max(1, max(len(t) for t in seen))
-        exclude = torch.full((len(seen), width), -1, dtype=torch.int64)
-        for i, t in enumerate(seen):
-            if t:
-                exclude[i, :len(t)] = torch.as_tensor(t, dtype=torch.int64)
-        if items is None:
-            target = k
-        else:
-            target = torch.full((len(items), max(len(row) for row in items)), -1, dtype=torch.int64)
-            for i, row in enumerate(items):
-                for j, item in enumerate(row):
-                    t = self._known_tokens([item])
-                    if t:
-                        target[i, j] = t[0]
+        batch, exclude = self._requests(sequences)
+        target = k if items is None else self._padded_ids([self._token_ids(row).tolist() for row in items])
         got = self.model.explain_tensor(batch, target, top=top, labels=labels, window=window, exclude_seen=False, exclude=exclude,
                                         allow=allow, row_filter=row_filter, temperature=temperature)
         U, K = (int(x) for x in got["target_ids"].shape)
@@ -463,45 +438,17 @@ class Recommender:
         names = list(range(len(sequences))) if user_ids is None else list(user_ids)
         if len(names) != len(sequences):
             raise ValueError(f"{len(names)} user ids for {len(sequences)} sequences")
-        if allowed_items is not None and allowed_items_per_user is not None:
-            raise ValueError("give allowed_items or allowed_items_per_user, not both")
-        user_filter = None
-        if allowed_items_per_user is not None:
-            lists = [list(row) for row in allowed_items_per_user]
-            if len(lists) != len(sequences):
-                raise ValueError(f"{len(lists)} allow-lists for {len(sequences)} sequences")
-            distinct = {}
-            user_filter = [distinct.setdefault(frozenset(self._known_tokens(row)), len(distinct)) for row in lists]
+        allow, user_filter = self._allow_filters(len(sequences), allowed_items, allowed_items_per_user)
         if not items:
             return []
-        item_ids = torch.full((len(items),), -1, dtype=torch.int64)
-        for j, item in enumerate(items):
-            t = self._known_tokens([item])
-            if t:
-                item_ids[j] = t[0]
-        allow = None
-        if allowed_items is not None:
-            allow = self._item_mask(allowed_items)
-        elif user_filter is not None:
-            allow = torch.zeros((max(len(distinct), 1), self.model.vocab_size), dtype=torch.bool)
-            for tokens, f in distinct.items():
-                if tokens:
-                    allow[f, torch.as_tensor(sorted(tokens), dtype=torch.int64)] = True
+        item_ids = self._token_ids(items)
         if allow is not None:
             allow = engine_mod.pack_item_filter(allow).to(self.model.engine.params.device)   # packed once, for every batch
-        tokenizer = self.dataloader.get_tokenizer()
         state = self.model.engine.audience_state(item_ids, k)
         for b0 in range(0, len(sequences), batch_size):
-            part = sequences[b0:b0 + batch_size]
-            batches = [self.dataloader.prepare_inference(list(seq)) for seq in part]
-            batch = {key: torch.from_numpy(np.concatenate([np.asarray(b[key]) for b in batches], axis=0)) for key in batches[0]}
-            seen = [tokenizer.tokenize(seq) for seq in part]
-            exclude = torch.full((len(seen), max(1, max(len(t) for t in seen))), -1, dtype=torch.int64)
-            for i, t in enumerate(seen):
-                if t:
-                    exclude[i, :len(t)] = torch.as_tensor(t, dtype=torch.int64)
-            row_filter = None if user_filter is None else torch.as_tensor(user_filter[b0:b0 + batch_size], dtype=torch.int32)
-            state = self.model.audience_tensor(batch, item_ids, state=state, k=k, user_ids=torch.arange(b0, b0 + len(part)),
+            batch, exclude = self._requests(sequences[b0:b0 + batch_size])
+            row_filter = None if user_filter is None else user_filter[b0:b0 + batch_size]
+            state = self.model.audience_tensor(batch, item_ids, state=state, k=k, user_ids=torch.arange(b0, b0 + len(exclude)),
                                                min_probability=min_probability, exclude_seen=False, exclude=exclude, allow=allow,
                                                row_filter=row_filter, temperature=temperature)
         # everything in one copy: the probabilities travel as the bits of their float64
@@ -520,12 +467,8 @@ class Recommender:
         items = list(items)
         if not items:
             return []
-        query = []
-        for item in items:
-            t = self._known_tokens([item])
-            query.append(t[0] if t else -1)
         allow = None if allowed_items is None else self._item_mask(allowed_items)
-        ids, _ = self.model.similar_items_tensor(torch.as_tensor(query, dtype=torch.int64), k=k, metric=metric, allow=allow)
+        ids, _ = self.model.similar_items_tensor(self._token_ids(items), k=k, metric=metric, allow=allow)
         return [tokenizer.detokenize([i for i in row if i >= 0]) for row in ids.cpu().tolist()]
 
     def list_quality(self, lists, item_counts=None) -> dict:
@@ -554,13 +497,9 @@ class Recommender:
                     raise ValueError(f"item_counts holds {counts.shape[0]} counts for a vocabulary of {V}")
             weight = torch.from_numpy(item_self_information(counts))
             out["novelty"] = 0.0
-        width = max((len(t) for t in tokens), default=0)
-        if width == 0:
+        if not any(tokens):
             return out
-        ids = torch.full((len(tokens), width), -1, dtype=torch.int64)
-        for i, t in enumerate(tokens):
-            if t:
-                ids[i, :len(t)] = torch.as_tensor(t, dtype=torch.int64)
+        ids = self._padded_ids(tokens)
         engine = self.model.engine
         dev = engine.params.device
         exposure = torch.zeros(V, dtype=torch.int64, device=dev)

@@ -206,9 +206,7 @@ def check_stream0(stream0) -> int:
     return stream0 - (1 << 64) if stream0 >= 1 << 63 else stream0
 
 
-def check_sample_pool_args(k, pool) -> Tuple[int, int]:
-    """Argument checks of truncated sampling that need no GPU: pool an integer in [1, 1024], k in [0, pool]."""
-    k = check_rank_full_args(k)
+def _pool_size(k: int, pool, verb: str) -> int:
     try:
         pool = operator.index(pool)
     except TypeError:
@@ -216,8 +214,14 @@ def check_sample_pool_args(k, pool) -> Tuple[int, int]:
     if pool < 1 or pool > RANK_FULL_MAX_K:
         raise ValueError(f"pool must lie in [1, {RANK_FULL_MAX_K}], got {pool}")
     if k > pool:
-        raise ValueError(f"k = {k} items cannot be drawn from a pool of {pool}")
-    return k, pool
+        raise ValueError(f"k = {k} items cannot be {verb} from a pool of {pool}")
+    return pool
+
+
+def check_sample_pool_args(k, pool) -> Tuple[int, int]:
+    """Argument checks of truncated sampling that need no GPU: pool an integer in [1, 1024], k in [0, pool]."""
+    k = check_rank_full_args(k)
+    return k, _pool_size(k, pool, "drawn")
 
 
 ROLLOUT_MAX_STEPS = 64
@@ -412,17 +416,7 @@ def check_rerank_args(k, pool, diversity) -> Tuple[int, int, float]:
     candidates re-ranked per row) None = min(1024, max(10 k, 50)), else an integer in [max(k, 1), 1024]; diversity a number in
     [0, 1], lambda = 1 - diversity rounded to fp32 (b4r_rerank_diverse's weight of the relevance)."""
     k = check_rank_full_args(k)
-    if pool is None:
-        pool = min(RANK_FULL_MAX_K, max(10 * k, 50))
-    else:
-        try:
-            pool = operator.index(pool)
-        except TypeError:
-            raise ValueError(f"pool must be an integer, got {pool!r}") from None
-        if pool < 1 or pool > RANK_FULL_MAX_K:
-            raise ValueError(f"pool must lie in [1, {RANK_FULL_MAX_K}], got {pool}")
-        if k > pool:
-            raise ValueError(f"k = {k} items cannot be picked from a pool of {pool}")
+    pool = min(RANK_FULL_MAX_K, max(10 * k, 50)) if pool is None else _pool_size(k, pool, "picked")
     if isinstance(diversity, bool) or not isinstance(diversity, numbers.Real) or not 0.0 <= diversity <= 1.0:   # (NaN fails the range)
         raise ValueError(f"diversity must be a number in [0, 1], got {diversity!r}")
     return k, pool, C.c_float(1.0 - float(diversity)).value
@@ -525,6 +519,12 @@ def item_self_information(counts) -> np.ndarray:
     return (-np.log2(np.maximum(c, 1.0) / total)).astype(np.float32)
 
 
+def grouped_scratch_bytes(bytes_fn, R: int, *dims) -> int:
+    """The scratch a per-row sweep is given: what bytes_fn(R, *dims) asks for, but at most 2 GiB or what 16 rows take, whichever is
+    more -- with less than it asks for the library works through the rows in groups."""
+    return min(int(bytes_fn(R, *dims)), max(int(bytes_fn(min(R, 16), *dims)), 2 << 30))
+
+
 class Engine:
     """One replica of the model on one GPU."""
 
@@ -553,6 +553,7 @@ class Engine:
         self.state = torch.zeros(_lib.STATE_WORDS, dtype=torch.int32, device=self.device)
         self._ws: Dict[Tuple[int, int, int], torch.Tensor] = {}
         self._quota_dev: Dict[int, tuple] = {}   # id(spec) -> (spec, its tensors on the device): the last few host-side quota specs
+        self._scratch_bufs: Dict[str, torch.Tensor] = {}   # operation -> its scratch buffer, kept between calls (_scratch)
         self.rehearse_collectives = False   # True: dp_train_step issues its all-reduce even in a process group of one
         self.set_seed(seed)
 
@@ -977,6 +978,61 @@ class Engine:
                                                 _stream(self.device)), "b4r_rank_candidates")
         return ranking, gt_rank, scores
 
+    # ---- the catalogue calls: what they share ---------------------------------------------------------------------------------------
+    def _scratch(self, key: str, nbytes: int) -> torch.Tensor:
+        """The uint8 scratch buffer of the operation `key`, kept between calls and replaced by a larger one when nbytes outgrow it."""
+        sc = self._scratch_bufs.get(key)
+        if sc is None or sc.numel() < nbytes:
+            sc = self._scratch_bufs[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return sc
+
+    def _picks(self, R: int, k: int, *dtypes) -> Tuple[torch.Tensor, ...]:
+        """One uninitialised [R, k] output per dtype"""
+        return tuple(torch.empty((R, k), dtype=dt, device=self.device) for dt in dtypes)
+
+    def _filter_args(self, allow, row_filter, n_rows: int):
+        """check_item_filter for n_rows rows, on the device.  Returns the entries' four filter arguments (allow_bits, n_filters,
+        row_filter, NULL) and the tensors they point into (to be held until the call is enqueued)."""
+        allow, row_filter = check_item_filter(allow, row_filter, self.cfg.vocab_size, n_rows)
+        allow_d = None if allow is None else allow.to(self.device).contiguous()
+        rf_d = None if row_filter is None else row_filter.to(self.device).contiguous()
+        return (_ptr(allow_d), 0 if allow_d is None else int(allow_d.shape[0]), _ptr(rf_d), None), (allow_d, rf_d)
+
+    def _sweep_rows(self, hidden: torch.Tensor, rows, exclude, first_item: int, gt, allow, row_filter):
+        """The row set of a full-catalogue sweep (rank_full's hidden / rows / exclude / first_item / gt / allow / row_filter), checked
+        and on the device.  Returns (R, the entries' twelve leading arguments -- hidden, ld, rows, table, bias, width, V, first_item,
+        R, exclude, E, gt --, their four filter arguments (_filter_args), the tensors both point into: to be held until the call is
+        enqueued)."""
+        R = int(rows.numel()) if rows is not None else int(hidden.shape[0])
+        check_rank_full_args(0, exclude, R)
+        filt, keep = self._filter_args(allow, row_filter, R)
+        if hidden.dtype != torch.float32 or hidden.ndim != 2 or hidden.stride(1) != 1 or hidden.shape[1] != self.embedding_width:
+            raise ValueError(f"hidden must be float32 [rows, {self.embedding_width}] with unit column stride")
+        rows_d = None if rows is None else rows.to(device=self.device, dtype=torch.int64).contiguous()
+        ex_d = None if exclude is None or exclude.shape[1] == 0 else exclude.to(device=self.device, dtype=torch.int64).contiguous()
+        gt_d = None if gt is None else gt.to(device=self.device, dtype=torch.int64).contiguous()
+        if gt_d is not None and gt_d.numel() != R:
+            raise ValueError(f"{gt_d.numel()} ground-truth ids for {R} rows")
+        sweep = (_ptr(hidden), hidden.stride(0), _ptr(rows_d), _ptr(self.view("word_embeddings/embeddings")),
+                 _ptr(self.view("cls/predictions/output_bias/bias")), self.embedding_width, self.cfg.vocab_size, int(first_item), R,
+                 _ptr(ex_d), 0 if ex_d is None else int(ex_d.shape[1]), _ptr(gt_d))
+        return R, sweep, filt, keep + (rows_d, ex_d, gt_d)
+
+    def _pool(self, pool_ids: torch.Tensor, pool_scores: torch.Tensor):
+        """A candidate pool (rank_full's ids / scores [R, M]), checked and on the device.  Returns (R, M, ids, scores)."""
+        if pool_ids.ndim != 2 or pool_ids.dtype != torch.int64 or pool_scores.dtype != torch.float32 or pool_scores.shape != pool_ids.shape:
+            raise ValueError(f"the pool is ids int64 [R, M] and scores float32 [R, M], got {pool_ids.dtype} {tuple(pool_ids.shape)} and "
+                             f"{pool_scores.dtype} {tuple(pool_scores.shape)}")
+        R, M = (int(x) for x in pool_ids.shape)
+        return R, M, pool_ids.to(self.device).contiguous(), pool_scores.to(self.device).contiguous()
+
+    def _rnorm_or_scratch(self, rnorm: Optional[torch.Tensor], key: str, bytes_fn, *dims):
+        """The entries' (rnorm, scratch, scratch_bytes): rnorm [V] on the device and no scratch -- or, when the call has to compute the
+        item table's 1 / |row| itself, no rnorm and the scratch of operation `key`, bytes_fn(*dims) bytes, in which it does so."""
+        rn_d = None if rnorm is None else rnorm.to(self.device).contiguous()
+        sc = self._scratch(key, int(bytes_fn(*dims))) if rn_d is None else None
+        return rn_d, sc, 0 if sc is None else sc.numel()
+
     def rank_full(self, hidden: torch.Tensor, rows: Optional[torch.Tensor], exclude: Optional[torch.Tensor], first_item: int,
                   gt: Optional[torch.Tensor], k: int, allow=None, row_filter=None):
         """b4r_rank_full on `hidden` [*,E] (the transform's rows, E = the item table's width; ld = stride(0)): rows [R] (hidden row of each ranked row) or None (R = hidden rows);
@@ -984,38 +1040,18 @@ class Engine:
         gt_rank [R] int32 or None): the best k allowed items of every row over the whole vocabulary, ties to the lower id, -1 / -inf
         where fewer than k are allowed.  The scratch buffer is kept between calls.
         allow / row_filter (check_item_filter): only the items the row's filter allows are ranked (b4r_rank_full_ex)."""
-        R = int(rows.numel()) if rows is not None else int(hidden.shape[0])
-        k = check_rank_full_args(k, exclude, R)
-        allow, row_filter = check_item_filter(allow, row_filter, self.cfg.vocab_size, R)
-        if hidden.dtype != torch.float32 or hidden.ndim != 2 or hidden.stride(1) != 1 or hidden.shape[1] != self.embedding_width:
-            raise ValueError(f"hidden must be float32 [rows, {self.embedding_width}] with unit column stride")
-        rows_d = None if rows is None else rows.to(device=self.device, dtype=torch.int64).contiguous()
-        ex_d = None if exclude is None or exclude.shape[1] == 0 else exclude.to(device=self.device, dtype=torch.int64).contiguous()
-        E = 0 if ex_d is None else int(ex_d.shape[1])
-        gt_d = None if gt is None else gt.to(device=self.device, dtype=torch.int64).contiguous()
-        if gt_d is not None and gt_d.numel() != R:
-            raise ValueError(f"{gt_d.numel()} ground-truth ids for {R} rows")
-        ids = torch.empty((R, k), dtype=torch.int64, device=self.device)
-        scores = torch.empty((R, k), dtype=torch.float32, device=self.device)
-        gt_rank = torch.empty((R,), dtype=torch.int32, device=self.device) if gt_d is not None else None
+        k = check_rank_full_args(k)
+        R, sweep, filt, keep = self._sweep_rows(hidden, rows, exclude, first_item, gt, allow, row_filter)
+        ids, scores = self._picks(R, k, torch.int64, torch.float32)
+        gt_rank = torch.empty((R,), dtype=torch.int32, device=self.device) if gt is not None else None
         if R == 0:
             return ids, scores, gt_rank
-        V = self.cfg.vocab_size
-        need = int(self.lib.b4r_rank_full_scratch_bytes(R, V, k))
-        least = int(self.lib.b4r_rank_full_scratch_bytes(min(R, 16), V, k))
-        want = min(need, max(least, 2 << 30))   # at most 2 GiB: more rows are then ranked in groups
-        sc = getattr(self, "_rank_full_scratch", None)
-        if sc is None or sc.numel() < want:
-            sc = self._rank_full_scratch = torch.empty(want, dtype=torch.uint8, device=self.device)
-        args = (_ptr(hidden), hidden.stride(0), _ptr(rows_d), _ptr(self.view("word_embeddings/embeddings")),
-                _ptr(self.view("cls/predictions/output_bias/bias")), self.embedding_width, V, int(first_item), R, _ptr(ex_d), E,
-                _ptr(gt_d), k, _ptr(ids), _ptr(scores), _ptr(gt_rank), _ptr(sc), sc.numel(), _stream(self.device))
-        if allow is None:
+        sc = self._scratch("b4r_rank_full", grouped_scratch_bytes(self.lib.b4r_rank_full_scratch_bytes, R, self.cfg.vocab_size, k))
+        args = sweep + (k, _ptr(ids), _ptr(scores), _ptr(gt_rank), _ptr(sc), sc.numel(), _stream(self.device))
+        if filt[0] is None:
             _lib.check(self.lib.b4r_rank_full(*args), "b4r_rank_full")
         else:
-            allow_d = allow.to(self.device).contiguous()
-            rf_d = None if row_filter is None else row_filter.to(self.device).contiguous()
-            _lib.check(self.lib.b4r_rank_full_ex(*args, _ptr(allow_d), int(allow_d.shape[0]), _ptr(rf_d), None), "b4r_rank_full_ex")
+            _lib.check(self.lib.b4r_rank_full_ex(*args, *filt), "b4r_rank_full_ex")
         return ids, scores, gt_rank
 
     def score_distribution(self, hidden: torch.Tensor, rows: Optional[torch.Tensor], exclude: Optional[torch.Tensor], first_item: int,
@@ -1027,12 +1063,8 @@ class Engine:
         logp [R, K] fp32 or None): the allowed items, their largest scaled score, the log normaliser, the entropy and the log
         probability of each queried id (-inf where the id is not allowed for the row).  A row without allowed items has n = 0,
         max = lse = -inf, entropy = 0.  The scratch buffer is kept between calls."""
-        R = int(rows.numel()) if rows is not None else int(hidden.shape[0])
-        check_rank_full_args(0, exclude, R)
         inv_t = check_temperature(temperature)
-        allow, row_filter = check_item_filter(allow, row_filter, self.cfg.vocab_size, R)
-        if hidden.dtype != torch.float32 or hidden.ndim != 2 or hidden.stride(1) != 1 or hidden.shape[1] != self.embedding_width:
-            raise ValueError(f"hidden must be float32 [rows, {self.embedding_width}] with unit column stride")
+        R, sweep, filt, keep = self._sweep_rows(hidden, rows, exclude, first_item, gt, allow, row_filter)
         q_d, K = None, 0
         if query_ids is not None:
             q = torch.as_tensor(query_ids)
@@ -1040,12 +1072,6 @@ class Engine:
                 raise ValueError(f"query_ids must be an integer tensor [{R}, K], got {q.dtype} of shape {tuple(q.shape)}")
             K = check_rank_full_args(int(q.shape[1]))
             q_d = q.to(device=self.device, dtype=torch.int64).contiguous()
-        rows_d = None if rows is None else rows.to(device=self.device, dtype=torch.int64).contiguous()
-        ex_d = None if exclude is None or exclude.shape[1] == 0 else exclude.to(device=self.device, dtype=torch.int64).contiguous()
-        E = 0 if ex_d is None else int(ex_d.shape[1])
-        gt_d = None if gt is None else gt.to(device=self.device, dtype=torch.int64).contiguous()
-        if gt_d is not None and gt_d.numel() != R:
-            raise ValueError(f"{gt_d.numel()} ground-truth ids for {R} rows")
         n = torch.empty((R,), dtype=torch.int32, device=self.device)
         mx = torch.empty((R,), dtype=torch.float32, device=self.device)
         lse = torch.empty((R,), dtype=torch.float64, device=self.device)
@@ -1053,18 +1079,8 @@ class Engine:
         logp = None if q_d is None else torch.empty((R, K), dtype=torch.float32, device=self.device)
         if R == 0:
             return n, mx, lse, ent, logp
-        V = self.cfg.vocab_size
-        want = int(self.lib.b4r_score_dist_scratch_bytes(R, V))
-        sc = getattr(self, "_score_dist_scratch", None)
-        if sc is None or sc.numel() < want:
-            sc = self._score_dist_scratch = torch.empty(want, dtype=torch.uint8, device=self.device)
-        allow_d = None if allow is None else allow.to(self.device).contiguous()
-        rf_d = None if row_filter is None else row_filter.to(self.device).contiguous()
-        _lib.check(self.lib.b4r_score_dist(_ptr(hidden), hidden.stride(0), _ptr(rows_d), _ptr(self.view("word_embeddings/embeddings")),
-                                           _ptr(self.view("cls/predictions/output_bias/bias")), self.embedding_width, V,
-                                           int(first_item), R, _ptr(ex_d), E, _ptr(gt_d), _ptr(allow_d),
-                                           0 if allow_d is None else int(allow_d.shape[0]), _ptr(rf_d), None, inv_t,
-                                           _ptr(q_d) if K > 0 else None, K, _ptr(n), _ptr(mx), _ptr(lse), _ptr(ent),
+        sc = self._scratch("b4r_score_dist", int(self.lib.b4r_score_dist_scratch_bytes(R, self.cfg.vocab_size)))
+        _lib.check(self.lib.b4r_score_dist(*sweep, *filt, inv_t, _ptr(q_d) if K > 0 else None, K, _ptr(n), _ptr(mx), _ptr(lse), _ptr(ent),
                                            _ptr(logp) if K > 0 else None, _ptr(sc), sc.numel(), _stream(self.device)),
                    "b4r_score_dist")
         return n, mx, lse, ent, logp
@@ -1078,42 +1094,17 @@ class Engine:
         (None: stream0 + row).  The same (seed, stream) draws the same list whatever else the call holds.  Returns (ids [R,k] int64,
         scores [R,k] fp32: rank_full's bits for those ids, keys [R,k] fp32: score / temperature + Gumbel noise, descending), -1 /
         -inf / -inf where fewer than k are allowed.  The scratch buffer is kept between calls."""
-        R = int(rows.numel()) if rows is not None else int(hidden.shape[0])
-        k = check_rank_full_args(k, exclude, R)
-        seed = check_sample_seed(seed)
-        inv_t = check_temperature(temperature)
+        k = check_rank_full_args(k)
+        seed, inv_t, stream0 = check_sample_seed(seed), check_temperature(temperature), check_stream0(stream0)
+        R, sweep, filt, keep = self._sweep_rows(hidden, rows, exclude, first_item, gt, allow, row_filter)
         streams = check_sample_streams(streams, R)
-        stream0 = check_stream0(stream0)
-        allow, row_filter = check_item_filter(allow, row_filter, self.cfg.vocab_size, R)
-        if hidden.dtype != torch.float32 or hidden.ndim != 2 or hidden.stride(1) != 1 or hidden.shape[1] != self.embedding_width:
-            raise ValueError(f"hidden must be float32 [rows, {self.embedding_width}] with unit column stride")
-        rows_d = None if rows is None else rows.to(device=self.device, dtype=torch.int64).contiguous()
-        ex_d = None if exclude is None or exclude.shape[1] == 0 else exclude.to(device=self.device, dtype=torch.int64).contiguous()
-        E = 0 if ex_d is None else int(ex_d.shape[1])
-        gt_d = None if gt is None else gt.to(device=self.device, dtype=torch.int64).contiguous()
-        if gt_d is not None and gt_d.numel() != R:
-            raise ValueError(f"{gt_d.numel()} ground-truth ids for {R} rows")
-        ids = torch.empty((R, k), dtype=torch.int64, device=self.device)
-        scores = torch.empty((R, k), dtype=torch.float32, device=self.device)
-        keys = torch.empty((R, k), dtype=torch.float32, device=self.device)
+        ids, scores, keys = self._picks(R, k, torch.int64, torch.float32, torch.float32)
         if R == 0 or k == 0:
             return ids, scores, keys
-        V = self.cfg.vocab_size
-        need = int(self.lib.b4r_sample_full_scratch_bytes(R, V, k))
-        least = int(self.lib.b4r_sample_full_scratch_bytes(min(R, 16), V, k))
-        want = min(need, max(least, 2 << 30))   # at most 2 GiB: more rows are then drawn in groups
-        sc = getattr(self, "_sample_full_scratch", None)
-        if sc is None or sc.numel() < want:
-            sc = self._sample_full_scratch = torch.empty(want, dtype=torch.uint8, device=self.device)
-        allow_d = None if allow is None else allow.to(self.device).contiguous()
-        rf_d = None if row_filter is None else row_filter.to(self.device).contiguous()
+        sc = self._scratch("b4r_sample_full", grouped_scratch_bytes(self.lib.b4r_sample_full_scratch_bytes, R, self.cfg.vocab_size, k))
         st_d = None if streams is None else streams.to(self.device).contiguous()
-        _lib.check(self.lib.b4r_sample_full(_ptr(hidden), hidden.stride(0), _ptr(rows_d), _ptr(self.view("word_embeddings/embeddings")),
-                                            _ptr(self.view("cls/predictions/output_bias/bias")), self.embedding_width, V,
-                                            int(first_item), R, _ptr(ex_d), E, _ptr(gt_d), k, _ptr(allow_d),
-                                            0 if allow_d is None else int(allow_d.shape[0]), _ptr(rf_d), None, inv_t, seed, _ptr(st_d),
-                                            stream0, _ptr(ids), _ptr(scores), _ptr(keys), _ptr(sc), sc.numel(), _stream(self.device)),
-                   "b4r_sample_full")
+        _lib.check(self.lib.b4r_sample_full(*sweep, k, *filt, inv_t, seed, _ptr(st_d), stream0, _ptr(ids), _ptr(scores), _ptr(keys),
+                                            _ptr(sc), sc.numel(), _stream(self.device)), "b4r_sample_full")
         return ids, scores, keys
 
     def sample_pool(self, pool_ids: torch.Tensor, pool_scores: torch.Tensor, k: int, seed: int, temperature: float = 1.0, streams=None,
@@ -1123,21 +1114,14 @@ class Engine:
         id: with the same seed and stream, a pool that holds every allowed item gives sample_full's lists.  Returns (ids [R,k] int64,
         scores [R,k] fp32: the pool scores of the picks, keys [R,k] fp32, pos [R,k] int32: the pool position of every pick), -1 /
         -inf / -inf / -1 where a row has fewer than k live entries."""
-        if pool_ids.ndim != 2 or pool_ids.dtype != torch.int64 or pool_scores.dtype != torch.float32 or pool_scores.shape != pool_ids.shape:
-            raise ValueError(f"the pool is ids int64 [R, M] and scores float32 [R, M], got {pool_ids.dtype} {tuple(pool_ids.shape)} and "
-                             f"{pool_scores.dtype} {tuple(pool_scores.shape)}")
-        R, M = (int(x) for x in pool_ids.shape)
+        R, M, ids_d, sc_d = self._pool(pool_ids, pool_scores)
         k, _ = check_sample_pool_args(k, M)
         seed = check_sample_seed(seed)
         inv_t = check_temperature(temperature)
         streams = check_sample_streams(streams, R)
         stream0 = check_stream0(stream0)
-        ids_d, sc_d = pool_ids.to(self.device).contiguous(), pool_scores.to(self.device).contiguous()
         st_d = None if streams is None else streams.to(self.device).contiguous()
-        ids = torch.empty((R, k), dtype=torch.int64, device=self.device)
-        scores = torch.empty((R, k), dtype=torch.float32, device=self.device)
-        keys = torch.empty((R, k), dtype=torch.float32, device=self.device)
-        pos = torch.empty((R, k), dtype=torch.int32, device=self.device)
+        ids, scores, keys, pos = self._picks(R, k, torch.int64, torch.float32, torch.float32, torch.int32)
         if R == 0 or k == 0:
             return ids, scores, keys, pos
         _lib.check(self.lib.b4r_sample_pool(_ptr(ids_d), _ptr(sc_d), R, M, self.cfg.vocab_size, inv_t, seed, _ptr(st_d), stream0, k,
@@ -1314,24 +1298,15 @@ class Engine:
         if q.ndim != 1 or q.dtype.is_floating_point or q.dtype == torch.bool:
             raise ValueError(f"item_ids must be a 1-D integer tensor, got {q.dtype} of shape {tuple(q.shape)}")
         R, V, Ew = int(q.numel()), self.cfg.vocab_size, self.embedding_width
-        allow, row_filter = check_item_filter(allow, row_filter, V, R)
+        filt, keep = self._filter_args(allow, row_filter, R)
         q = q.to(device=self.device, dtype=torch.int64).contiguous()
-        ids = torch.empty((R, k), dtype=torch.int64, device=self.device)
-        scores = torch.empty((R, k), dtype=torch.float32, device=self.device)
+        ids, scores = self._picks(R, k, torch.int64, torch.float32)
         if R == 0:
             return ids, scores
-        sweep = int(self.lib.b4r_rank_full_scratch_bytes(R, V, k))
-        own = int(self.lib.b4r_item_neighbours_scratch_bytes(R, V, k, Ew)) - sweep
-        least = int(self.lib.b4r_rank_full_scratch_bytes(min(R, 16), V, k))
-        want = own + min(sweep, max(least, 2 << 30))   # the sweep's share at most 2 GiB: more rows are then ranked in groups
-        sc = getattr(self, "_neighbours_scratch", None)
-        if sc is None or sc.numel() < want:
-            sc = self._neighbours_scratch = torch.empty(want, dtype=torch.uint8, device=self.device)
-        allow_d = None if allow is None else allow.to(self.device).contiguous()
-        rf_d = None if row_filter is None else row_filter.to(self.device).contiguous()
+        own = int(self.lib.b4r_item_neighbours_scratch_bytes(R, V, k, Ew)) - int(self.lib.b4r_rank_full_scratch_bytes(R, V, k))
+        sc = self._scratch("b4r_item_neighbours", own + grouped_scratch_bytes(self.lib.b4r_rank_full_scratch_bytes, R, V, k))   # (the sweep's share)
         table = self.view("word_embeddings/embeddings")
-        _lib.check(self.lib.b4r_item_neighbours(_ptr(table), table.stride(0), Ew, V, int(first_item), _ptr(q), R, metric_id,
-                                                _ptr(allow_d), 0 if allow_d is None else int(allow_d.shape[0]), _ptr(rf_d), k,
+        _lib.check(self.lib.b4r_item_neighbours(_ptr(table), table.stride(0), Ew, V, int(first_item), _ptr(q), R, metric_id, *filt[:3], k,
                                                 _ptr(ids), _ptr(scores), _ptr(sc), sc.numel(), _stream(self.device)),
                    "b4r_item_neighbours")
         return ids, scores
@@ -1342,32 +1317,33 @@ class Engine:
         1 - diversity.  Returns (ids [R,k] int64, scores [R,k] fp32: the pool scores of the picked items, mmr [R,k] fp32), -1 / -inf
         where a row has fewer than k live candidates.  rnorm [V] fp32: 1 / |row| of the table (None: computed by the call, as
         item_neighbours computes it).  The scratch buffer is kept between calls."""
-        if pool_ids.ndim != 2 or pool_ids.dtype != torch.int64 or pool_scores.dtype != torch.float32 or pool_scores.shape != pool_ids.shape:
-            raise ValueError(f"the pool is ids int64 [R, M] and scores float32 [R, M], got {pool_ids.dtype} {tuple(pool_ids.shape)} and "
-                             f"{pool_scores.dtype} {tuple(pool_scores.shape)}")
-        R, M = (int(x) for x in pool_ids.shape)
+        return self._rerank(pool_ids, pool_scores, k, diversity, rnorm, capped=False)
+
+    def _rerank(self, pool_ids: torch.Tensor, pool_scores: torch.Tensor, k: int, diversity: float, rnorm: Optional[torch.Tensor],
+                capped: bool, quotas=None):
+        """rerank_diverse, and with `capped` rerank_quota: the same pick loop under the caps `quotas`, which also returns pos."""
+        R, M, ids_d, sc_d = self._pool(pool_ids, pool_scores)
         k, _, lam = check_rerank_args(k, M, diversity)
         V, Ew = self.cfg.vocab_size, self.embedding_width
+        specs = check_quota_args(quotas, V) if capped else []
         if rnorm is not None and (rnorm.dtype != torch.float32 or tuple(rnorm.shape) != (V,)):
             raise ValueError(f"rnorm must be float32 [{V}], got {rnorm.dtype} {tuple(rnorm.shape)}")
-        ids_d, sc_d = pool_ids.to(self.device).contiguous(), pool_scores.to(self.device).contiguous()
-        rn_d = None if rnorm is None else rnorm.to(self.device).contiguous()
-        ids = torch.empty((R, k), dtype=torch.int64, device=self.device)
-        scores = torch.empty((R, k), dtype=torch.float32, device=self.device)
-        mmr = torch.empty((R, k), dtype=torch.float32, device=self.device)
+        out = self._picks(R, k, torch.int64, torch.float32, torch.float32, *([torch.int32] if capped else []))
         if R == 0 or k == 0:
-            return ids, scores, mmr
-        sc = None
-        if rn_d is None:
-            want = int(self.lib.b4r_rerank_diverse_scratch_bytes(R, M, V))
-            sc = getattr(self, "_rerank_scratch", None)
-            if sc is None or sc.numel() < want:
-                sc = self._rerank_scratch = torch.empty(want, dtype=torch.uint8, device=self.device)
+            return out
+        name = "b4r_rerank_quota" if capped else "b4r_rerank_diverse"
+        rn_d, sc, sc_bytes = self._rnorm_or_scratch(rnorm, name, getattr(self.lib, name + "_scratch_bytes"), R, M, V)
+        caps = ()
+        if capped:
+            qs = (_lib.ItemQuota * max(len(specs), 1))()
+            keep = [self._quota_on_device(spec) for spec in specs]
+            for q, spec, (ig_d, gc_d) in zip(qs, specs, keep):
+                q.item_group, q.group_cap, q.n_groups, q.cap = _ptr(ig_d), _ptr(gc_d), spec.n_groups, spec.cap
+            caps = (qs, len(specs))
         table = self.view("word_embeddings/embeddings")
-        _lib.check(self.lib.b4r_rerank_diverse(_ptr(table), table.stride(0), Ew, V, _ptr(rn_d), _ptr(ids_d), _ptr(sc_d), R, M, lam, k,
-                                               _ptr(ids), _ptr(scores), _ptr(mmr), _ptr(sc), 0 if sc is None else sc.numel(),
-                                               _stream(self.device)), "b4r_rerank_diverse")
-        return ids, scores, mmr
+        _lib.check(getattr(self.lib, name)(_ptr(table), table.stride(0), Ew, V, _ptr(rn_d), _ptr(ids_d), _ptr(sc_d), R, M, lam, k, *caps,
+                                           *(_ptr(t) for t in out), _ptr(sc), sc_bytes, _stream(self.device)), name)
+        return out
 
     def _quota_on_device(self, spec: "ItemGroups"):
         """The spec's tensors on this engine's device.  A spec that lives there already (ItemGroups.to) is used as it is; of a spec
@@ -1389,40 +1365,7 @@ class Engine:
         closes once one of its groups has given its cap of picks; diversity = 0 keeps the pool's order under the caps.  Returns (ids
         [R,k] int64, scores [R,k] fp32, mmr [R,k] fp32, pos [R,k] int32: the pool position of every pick), -1 / -inf / -inf / -1 where a
         row has fewer than k admissible candidates.  rnorm as in rerank_diverse.  The scratch buffer is kept between calls."""
-        if pool_ids.ndim != 2 or pool_ids.dtype != torch.int64 or pool_scores.dtype != torch.float32 or pool_scores.shape != pool_ids.shape:
-            raise ValueError(f"the pool is ids int64 [R, M] and scores float32 [R, M], got {pool_ids.dtype} {tuple(pool_ids.shape)} and "
-                             f"{pool_scores.dtype} {tuple(pool_scores.shape)}")
-        R, M = (int(x) for x in pool_ids.shape)
-        k, _, lam = check_rerank_args(k, M, diversity)
-        V, Ew = self.cfg.vocab_size, self.embedding_width
-        specs = check_quota_args(quotas, V)
-        if rnorm is not None and (rnorm.dtype != torch.float32 or tuple(rnorm.shape) != (V,)):
-            raise ValueError(f"rnorm must be float32 [{V}], got {rnorm.dtype} {tuple(rnorm.shape)}")
-        ids_d, sc_d = pool_ids.to(self.device).contiguous(), pool_scores.to(self.device).contiguous()
-        rn_d = None if rnorm is None else rnorm.to(self.device).contiguous()
-        ids = torch.empty((R, k), dtype=torch.int64, device=self.device)
-        scores = torch.empty((R, k), dtype=torch.float32, device=self.device)
-        mmr = torch.empty((R, k), dtype=torch.float32, device=self.device)
-        pos = torch.empty((R, k), dtype=torch.int32, device=self.device)
-        if R == 0 or k == 0:
-            return ids, scores, mmr, pos
-        qs = (_lib.ItemQuota * max(len(specs), 1))()
-        keep = []
-        for q, spec in zip(qs, specs):
-            ig_d, gc_d = self._quota_on_device(spec)
-            keep.append((ig_d, gc_d))
-            q.item_group, q.group_cap, q.n_groups, q.cap = _ptr(ig_d), _ptr(gc_d), spec.n_groups, spec.cap
-        sc = None
-        if rn_d is None:
-            want = int(self.lib.b4r_rerank_quota_scratch_bytes(R, M, V))
-            sc = getattr(self, "_rerank_quota_scratch", None)
-            if sc is None or sc.numel() < want:
-                sc = self._rerank_quota_scratch = torch.empty(want, dtype=torch.uint8, device=self.device)
-        table = self.view("word_embeddings/embeddings")
-        _lib.check(self.lib.b4r_rerank_quota(_ptr(table), table.stride(0), Ew, V, _ptr(rn_d), _ptr(ids_d), _ptr(sc_d), R, M, lam, k,
-                                             qs, len(specs), _ptr(ids), _ptr(scores), _ptr(mmr), _ptr(pos), _ptr(sc),
-                                             0 if sc is None else sc.numel(), _stream(self.device)), "b4r_rerank_quota")
-        return ids, scores, mmr, pos
+        return self._rerank(pool_ids, pool_scores, k, diversity, rnorm, capped=True, quotas=quotas)
 
     def list_metrics(self, list_ids: torch.Tensor, gt: Optional[torch.Tensor] = None, item_weight: Optional[torch.Tensor] = None,
                      rnorm: Optional[torch.Tensor] = None, exposure: Optional[torch.Tensor] = None, sums: Optional[torch.Tensor] = None,
@@ -1452,24 +1395,17 @@ class Engine:
         ids_d = list_ids.to(self.device).contiguous()
         gt_d = None if gt is None else gt.to(self.device).contiguous()
         w_d = None if item_weight is None else item_weight.to(self.device).contiguous()
-        rn_d = None if rnorm is None else rnorm.to(self.device).contiguous()
         n = torch.empty((R,), dtype=torch.int32, device=self.device)
         dist = torch.empty((R,), dtype=torch.int64, device=self.device)
         nov = torch.empty((R,), dtype=torch.int64, device=self.device)
         hit = torch.empty((R,), dtype=torch.int32, device=self.device)
         if R == 0:
             return n, dist, nov, hit
-        sc = None
-        if rn_d is None:
-            want = int(self.lib.b4r_list_metrics_scratch_bytes(R, K, V))
-            sc = getattr(self, "_list_metrics_scratch", None)
-            if sc is None or sc.numel() < want:
-                sc = self._list_metrics_scratch = torch.empty(want, dtype=torch.uint8, device=self.device)
+        rn_d, sc, sc_bytes = self._rnorm_or_scratch(rnorm, "b4r_list_metrics", self.lib.b4r_list_metrics_scratch_bytes, R, K, V)
         table = self.view("word_embeddings/embeddings")
         _lib.check(self.lib.b4r_list_metrics(_ptr(table), table.stride(0), Ew, V, SPECIAL_IDS, _ptr(rn_d), _ptr(ids_d), R, K, _ptr(gt_d),
                                              _ptr(w_d), _ptr(n), _ptr(dist), _ptr(nov), _ptr(hit), _ptr(exposure), _ptr(sums),
-                                             _ptr(counts), _ptr(sc), 0 if sc is None else sc.numel(), _stream(self.device)),
-                   "b4r_list_metrics")
+                                             _ptr(counts), _ptr(sc), sc_bytes, _stream(self.device)), "b4r_list_metrics")
         return n, dist, nov, hit
 
     def rank_metrics(self, gt_rank: torch.Tensor, families, cutoffs, gain_sums: torch.Tensor, users: torch.Tensor) -> None:

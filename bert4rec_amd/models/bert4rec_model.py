@@ -499,6 +499,26 @@ class BERT4RecModel:
             out[s // P].append((i_row, s_row, p_row))
         return out, got[3]
 
+    def _one_slot_batch(self, caller: str, encoder_input, exclude, allow, row_filter, max_len: bool = False):
+        """What recommend_sequence_tensor and explain_tensor do before their first forward: the checks of exclude [B, E], allow and
+        row_filter [B] (before any work), the batch on the device, and check_rollout_batch (the call's one host synchronisation).
+        Returns (packed allow or None, row_filter int32 on the device or None, (tokens, mask, positions) on the device, len [B],
+        slot_index [B] = b*P+p, the largest row length or None without max_len)."""
+        if exclude is not None and torch.as_tensor(exclude).ndim != 2:
+            raise ValueError(f"exclude must be rank 2 [rows, ids], got shape {tuple(torch.as_tensor(exclude).shape)}")
+        allow, row_filter = engine_mod.check_item_filter(allow, row_filter, self.vocab_size)
+        rows = encoder_input.get("input_word_ids")
+        if row_filter is not None and rows is not None and row_filter.numel() != len(rows):
+            raise ValueError(f"row_filter has {row_filter.numel()} entries for a batch of {len(rows)}")
+        cb, keep = self.engine.prepare_batch(encoder_input)
+        if cb.P == 0:
+            raise ValueError(f"{caller} needs masked_lm_positions")
+        mask, pos = keep["input_mask"], keep["masked_lm_positions"]
+        length, slot_p, *longest = engine_mod.check_rollout_batch(mask, pos, encoder_input.get("masked_lm_weights"), return_max_len=max_len)
+        slots = torch.arange(cb.B, dtype=torch.int64, device=self.device) * cb.P + slot_p
+        rf = None if row_filter is None else row_filter.to(self.device)
+        return allow, rf, (keep["input_word_ids"], mask, pos), length, slots, (longest[0] if max_len else None)
+
     def recommend_sequence_tensor(self, encoder_input: Dict[str, torch.Tensor], steps: int, beams: int = 1, expand: Optional[int] = None,
                                   exclude_seen: bool = True, exclude: Optional[torch.Tensor] = None, allow=None, row_filter=None,
                                   temperature: float = 1.0, sample_seed: Optional[int] = None, sample_streams=None,
@@ -531,22 +551,13 @@ class BERT4RecModel:
             sample_seed = engine_mod.check_sample_seed(sample_seed)
         elif sample_streams is not None:
             raise ValueError("sample_streams are the noise streams of a sampled call: give sample_seed as well")
-        if exclude is not None and torch.as_tensor(exclude).ndim != 2:
-            raise ValueError(f"exclude must be rank 2 [rows, ids], got shape {tuple(torch.as_tensor(exclude).shape)}")
-        allow, row_filter = engine_mod.check_item_filter(allow, row_filter, self.vocab_size)
+        allow, rf, (tokens, mask, pos), length, slots0, _ = self._one_slot_batch("recommend_sequence_tensor", encoder_input, exclude, allow,
+                                                                                  row_filter)
         eng, dev = self.engine, self.device
-        cb, keep = eng.prepare_batch(encoder_input)
-        if cb.P == 0:
-            raise ValueError("recommend_sequence_tensor needs masked_lm_positions")
-        U, L, P = cb.B, cb.L, cb.P
+        (U, L), P = tokens.shape, pos.shape[1]
         if L < 2:
             raise ValueError("a roll-out needs sequences of at least 2 tokens (an item and the placeholder)")
-        if row_filter is not None and row_filter.numel() != U:
-            raise ValueError(f"row_filter has {row_filter.numel()} entries for a batch of {U}")
         streams = engine_mod.check_sample_streams(sample_streams, U) if sampled else None
-        tokens, mask, pos = keep["input_word_ids"], keep["input_mask"], keep["masked_lm_positions"]
-        length, slot_p = engine_mod.check_rollout_batch(mask, pos, encoder_input.get("masked_lm_weights"))   # the one host synchronisation
-        slots0 = torch.arange(U, dtype=torch.int64, device=dev) * P + slot_p
         ids_out = torch.full((U, beams, steps), -1, dtype=torch.int64, device=dev)
         if U == 0:
             lp = torch.empty((U, beams, steps), dtype=torch.float32, device=dev)
@@ -561,7 +572,6 @@ class BERT4RecModel:
         first = engine_mod.SPECIAL_IDS
         N = U * beams
         pair = [None, None]
-        rf = None if row_filter is None else row_filter.to(dev)
         st = None if streams is None else streams.to(dev)
         want_dist = return_logp or beams > 1
         lp_out = torch.full((U, 1, steps), float("-inf"), dtype=torch.float32, device=dev) if want_dist and beams == 1 else None
@@ -671,20 +681,9 @@ class BERT4RecModel:
             if labels.ndim != 1 or labels.numel() != self.vocab_size or labels.dtype.is_floating_point or labels.dtype == torch.bool:
                 raise ValueError(f"labels must hold one integer per item [{self.vocab_size}], got {labels.dtype} of shape {tuple(labels.shape)}")
         engine_mod.check_temperature(temperature)
-        if exclude is not None and torch.as_tensor(exclude).ndim != 2:
-            raise ValueError(f"exclude must be rank 2 [rows, ids], got shape {tuple(torch.as_tensor(exclude).shape)}")
-        allow, row_filter = engine_mod.check_item_filter(allow, row_filter, self.vocab_size)
-        if row_filter is not None and row_filter.numel() != B:
-            raise ValueError(f"row_filter has {row_filter.numel()} entries for a batch of {B}")
-        eng, dev = self.engine, self.device
-        cb, keep = eng.prepare_batch(encoder_input)
-        if cb.P == 0:
-            raise ValueError("explain_tensor needs masked_lm_positions")
-        P = cb.P
-        tokens, mask, pos = keep["input_word_ids"], keep["input_mask"], keep["masked_lm_positions"]
-        length, slot_p, max_len = engine_mod.check_rollout_batch(mask, pos, encoder_input.get("masked_lm_weights"),
-                                                                 return_max_len=True)    # the one host synchronisation
-        slots0 = torch.arange(B, dtype=torch.int64, device=dev) * P + slot_p
+        allow, rf, (tokens, mask, pos), length, slots0, max_len = self._one_slot_batch("explain_tensor", encoder_input, exclude, allow, row_filter,
+                                                                                        max_len=True)
+        eng, dev, P = self.engine, self.device, pos.shape[1]
         Wc = min(W, max(1, int(rows_per_forward) // max(B, 1)))
         n_chunks = -(-W // Wc)
         n_run = min(n_chunks, -(-max(max_len - 1, 0) // Wc))       # chunks that start inside the longest history
@@ -696,7 +695,6 @@ class BERT4RecModel:
                "unit_label": torch.full((B, n_chunks * Wc), -1, dtype=torch.int32, device=dev),
                "removed": torch.zeros((B, n_chunks * Wc), dtype=torch.int32, device=dev)}
         first = engine_mod.SPECIAL_IDS
-        rf = None if row_filter is None else row_filter.to(dev)
         if B == 0:
             target = torch.empty((0, K), dtype=torch.int64, device=dev)
             base = torch.empty((0, K), dtype=torch.float32, device=dev)
