@@ -132,6 +132,7 @@ FLAG_ENCODER_ONLY = 64
 LOSS_FUSED_HEAD = 2
 GEMM_F32, GEMM_BF16X3, GEMM_BF16 = 0, 1, 2
 SIM_DOT, SIM_COSINE = 0, 1   # B4R_SIM_*: b4r_item_neighbours' metric
+JOINT_ADDITIVE, JOINT_LEAST_MISERY, JOINT_MOST_PLEASURE = 0, 1, 2   # B4R_JOINT_*: b4r_rank_joint's mode
 
 _P, _I32, _I64, _F, _U32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint32
 
@@ -212,6 +213,9 @@ PROTOTYPES = {
     "b4r_occlude_rows": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "b4r_attribution_select": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "b4r_audience_merge": (C.c_int, [_P, _I32, _I32, _I32, _P, _I64, _F, _I32, _P, _P, _P, _P, _P]),
+    "b4r_rank_joint_scratch_bytes": (_I64, [_I32, _I32, _I32, _I32]),
+    "b4r_rank_joint": (C.c_int, [_P, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _P, _F, _P, _P, _I32, _I32, _P, _I32,
+                                 _F, _I32, _P, _P, _P, _P, _P, _I64, _P]),
     "b4r_rank_metrics": (C.c_int, [_P, _I32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I32, _P, _P, _P]),
     "b4r_mlm_transform_rows": (C.c_int, [C.POINTER(ModelConfig), _P, _P, _I64, _P, _I32, _P, _P, _P]),
     "b4r_embed_ln_fwd": (C.c_int, [_P, _I32, _I32, _P, _I32, _P, _P, _P, _I32, _F, _P, _P, _P, _P, _F, _P]),

@@ -460,6 +460,64 @@ class Recommender:
         return [{"users": [(names[u], p) for u, p in zip(users_h[j], prob_h[j]) if u >= 0], "reach": int(reach_h[j]),
                  "expected_demand": demand_h[j] / engine_mod.AUDIENCE_DEMAND_ONE} for j in range(len(items))]
 
+    def recommend_together(self, parties, k: int = 10, strategy: str = "additive", weights=None, min_member_probability=None,
+                           allowed_items=None, return_members: bool = False) -> list:
+        """Several users deciding together (a household choosing a film, friends choosing a game, a shared playlist): one list of k
+        items per PARTY.  parties: a list of parties, each a list of 1 to 16 item sequences (its members' histories).  One batched
+        BERT4RecModel.recommend_joint_tensor call over all members and one read-back.
+        An item is recommended to a party only when no member has it anywhere in their sequence (and allowed_items, one iterable of
+        items for everybody, holds it).  strategy ranks the items by the members' log probabilities of taking them next:
+        "additive" (their sum; weights: one list of numbers >= 0 per party, a member's say), "least_misery" (the least happy
+        member's), "most_pleasure" (the happiest member's).  min_member_probability q in (0, 1]: the veto -- an item some member
+        takes with probability below q is not recommended.
+        Returns per party [(item, score), ...], best first, shorter when the party could be served fewer than k items; with
+        return_members [(item, score, [p_member, ...]), ...]: the probability each member takes the item next, the one
+        recommend_batch(return_probabilities=True) gives that user for that item."""
+        parties = [[list(seq) for seq in party] for party in parties]
+        for party in parties:
+            if not 1 <= len(party) <= engine_mod.JOINT_MAX_MEMBERS:
+                raise ValueError(f"a party has between 1 and {engine_mod.JOINT_MAX_MEMBERS} members, got {len(party)}")
+        M = max((len(party) for party in parties), default=1)
+        rows = torch.full((len(parties), M), -1, dtype=torch.int64)
+        sequences = []
+        for p, party in enumerate(parties):
+            rows[p, :len(party)] = torch.arange(len(sequences), len(sequences) + len(party))
+            sequences.extend(party)
+        w = None
+        if weights is not None:
+            weights = [list(ws) for ws in weights]
+            if len(weights) != len(parties) or any(len(ws) != len(party) for ws, party in zip(weights, parties)):
+                raise ValueError("weights holds one number per member: a list per party, as long as the party")
+            w = torch.zeros((len(parties), M), dtype=torch.float32)
+            for p, ws in enumerate(weights):
+                w[p, :len(ws)] = torch.as_tensor(ws, dtype=torch.float32)
+        engine_mod.check_joint_args(rows, k, strategy, w, min_member_probability, True, 1.0, len(sequences))
+        allow, _ = self._allow_filters(len(sequences), allowed_items, None)
+        if not parties:
+            return []
+        tokenizer = self.dataloader.get_tokenizer()
+        batch, exclude = self._requests(sequences)
+        got = self.model.recommend_joint_tensor(batch, rows, k=k, strategy=strategy, weights=w, min_member_probability=min_member_probability,
+                                                exclude_seen=False, exclude=exclude, allow=allow, return_members=return_members)
+        ids, scores = got[0], got[1]
+        # everything in one copy: an id is exact in float64
+        cols = [ids.to(torch.float64), scores.to(torch.float64)]
+        if return_members:
+            cols.append(torch.exp(got[3].to(torch.float64)).reshape(len(parties), -1))
+        both = torch.cat(cols, dim=1).cpu()
+        K = int(ids.shape[1])
+        ids_h, scores_h = both[:, :K].to(torch.int64).tolist(), both[:, K:2 * K].tolist()
+        prob_h = both[:, 2 * K:].reshape(len(parties), K, M).tolist() if return_members else None
+        out = []
+        for p, party in enumerate(parties):
+            kept = [i for i, t in enumerate(ids_h[p]) if t >= 0]
+            items = tokenizer.detokenize([ids_h[p][i] for i in kept])
+            if return_members:
+                out.append([(item, scores_h[p][i], prob_h[p][i][:len(party)]) for item, i in zip(items, kept)])
+            else:
+                out.append([(item, scores_h[p][i]) for item, i in zip(items, kept)])
+        return out
+
     def similar_items(self, items, k: int = 10, metric: str = "cosine", allowed_items=None) -> list:
         """For every item of `items` the k nearest items of the learned item table, as detokenized lists (best first); metric
         "cosine" or "dot".  An item the vocabulary does not know gets an empty list.  allowed_items: only those are returned."""

@@ -346,6 +346,62 @@ def check_audience_state(state, item_ids: torch.Tensor, k: int) -> None:
         raise ValueError(f"this state keeps k = {int(state['users'].shape[-1])} users per item, not {k}")
 
 
+JOINT_MAX_MEMBERS = 16    # b4r_rank_joint: M
+JOINT_STRATEGIES = {"additive": _lib.JOINT_ADDITIVE, "least_misery": _lib.JOINT_LEAST_MISERY, "most_pleasure": _lib.JOINT_MOST_PLEASURE}
+
+
+def check_joint_args(parties, k, strategy="additive", weights=None, min_member_probability=None, calibrated: bool = True,
+                     temperature=1.0, n_rows: Optional[int] = None):
+    """Argument checks of a joint recommendation that need no GPU.  parties: integers [NP, M], 1 <= M <= 16, the ranked rows of each
+    party, negative = no member (an index >= n_rows raises when n_rows is given); k in [0, 1024]; strategy "additive" |
+    "least_misery" | "most_pleasure"; weights None or numbers [NP, M], finite and >= 0, with the additive strategy only;
+    min_member_probability None or a number in (0, 1], with calibrated scores only; a temperature other than 1 needs calibrated
+    scores too (it shapes the distribution; uncalibrated scores of different users are not comparable at any temperature).
+    Returns (parties int32 [NP, M] with -1 for the absent slots, k, b4r_rank_joint's mode, weights fp32 [NP, M] or None,
+    min_member_util = fl32(log(min_member_probability)) or -inf, inv_temperature)."""
+    k = check_rank_full_args(k)
+    if not isinstance(strategy, str) or strategy not in JOINT_STRATEGIES:
+        raise ValueError(f"strategy must be one of {sorted(JOINT_STRATEGIES)}, got {strategy!r}")
+    try:
+        p = torch.as_tensor(parties)
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError("parties must be an integer array [parties, members], -1 padded") from None
+    if p.ndim != 2 or p.dtype.is_floating_point or p.dtype.is_complex or p.dtype == torch.bool:
+        raise ValueError(f"parties must be an integer tensor [parties, members], got {p.dtype} of shape {tuple(p.shape)}")
+    NP, M = (int(x) for x in p.shape)
+    if M < 1 or M > JOINT_MAX_MEMBERS:
+        raise ValueError(f"a party has between 1 and {JOINT_MAX_MEMBERS} member slots, got {M}")
+    p = p.detach().cpu().to(torch.int64)
+    if n_rows is not None and NP > 0 and int(p.max()) >= n_rows:
+        raise ValueError(f"parties names row {int(p.max())} of {n_rows} ranked rows")
+    p = p.clamp(min=-1).to(torch.int32)
+    w = None
+    if weights is not None:
+        if strategy != "additive":
+            raise ValueError(f"weights belong to the additive strategy, not to {strategy!r}")
+        try:
+            w = torch.as_tensor(weights).detach().cpu().to(torch.float32)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError("weights must be numbers [parties, members]") from None
+        if tuple(w.shape) != (NP, M):
+            raise ValueError(f"weights must have the shape of parties [{NP}, {M}], got {tuple(w.shape)}")
+        if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+            raise ValueError("weights must be finite and >= 0")
+    inv_t = check_temperature(temperature)
+    min_util = -math.inf
+    if not calibrated:
+        if min_member_probability is not None:
+            raise ValueError("min_member_probability needs calibrated=True: an uncalibrated score is no probability")
+        if float(temperature) != 1.0:
+            raise ValueError("temperature shapes the calibrated distribution: give calibrated=True as well")
+    elif min_member_probability is not None:
+        q = min_member_probability
+        if isinstance(q, bool) or not isinstance(q, numbers.Real) or not 0.0 < q <= 1.0:
+            raise ValueError(f"min_member_probability must be a number in (0, 1], got {q!r}")
+        min_util = C.c_float(math.log(float(q))).value
+    return p, k, JOINT_STRATEGIES[strategy], w, min_util, inv_t
+
+
 SIMILARITY_METRICS = {"dot": _lib.SIM_DOT, "cosine": _lib.SIM_COSINE}
 
 
@@ -1084,6 +1140,46 @@ class Engine:
                                            _ptr(logp) if K > 0 else None, _ptr(sc), sc.numel(), _stream(self.device)),
                    "b4r_score_dist")
         return n, mx, lse, ent, logp
+
+    def rank_joint(self, hidden: torch.Tensor, rows: Optional[torch.Tensor], exclude: Optional[torch.Tensor], first_item: int, parties,
+                   k: int, strategy: str = "additive", weights=None, min_member_util: float = -math.inf,
+                   row_lse: Optional[torch.Tensor] = None, allow=None, row_filter=None, temperature: float = 1.0,
+                   return_members: bool = False):
+        """b4r_rank_joint on `hidden` (rank_full's hidden / rows / exclude / first_item / allow / row_filter: the same scores and the
+        same allowed set per row): one top-k list per party.  parties [NP, M] integers: the ranked rows of each party, negative = no
+        member (check_joint_args).  row_lse [R] fp64: score_distribution's lse of the same rows at the same temperature, which makes
+        the members' scores log probabilities; None: the raw scores (temperature must be 1).  An item is ranked for a party when
+        every member could be served it and no member's score lies below min_member_util; its aggregate is the weighted sum
+        (additive), the minimum (least_misery) or the maximum (most_pleasure) over the members.  Returns (ids [NP,k] int64, scores
+        [NP,k] fp32, n [NP] int32: the items the party could be served, member scores [NP,k,M] fp32 or None without return_members),
+        -1 / -inf / -inf where fewer than k are allowed.  The scratch buffer is kept between calls."""
+        R = int(rows.numel()) if rows is not None else int(hidden.shape[0])
+        parties, k, mode, w, _, inv_t = check_joint_args(parties, k, strategy, weights, None, row_lse is not None, temperature, R)
+        if isinstance(min_member_util, bool) or not isinstance(min_member_util, numbers.Real) or math.isnan(min_member_util):
+            raise ValueError(f"min_member_util must be a number, got {min_member_util!r}")
+        if row_lse is not None and (row_lse.dtype != torch.float64 or tuple(row_lse.shape) != (R,)):
+            raise ValueError(f"row_lse must be float64 [{R}], got {row_lse.dtype} of shape {tuple(row_lse.shape)}")
+        R, sweep, filt, keep = self._sweep_rows(hidden, rows, exclude, first_item, None, allow, row_filter)
+        NP, M = (int(x) for x in parties.shape)
+        ids, scores = self._picks(NP, k, torch.int64, torch.float32)
+        n = torch.empty((NP,), dtype=torch.int32, device=self.device)
+        util = torch.empty((NP, k, M), dtype=torch.float32, device=self.device) if return_members else None
+        if NP == 0:
+            return ids, scores, n, util
+        if k == 0:
+            # the library launches nothing for K = 0; the count comes from a sweep that keeps one item
+            n = self.rank_joint(hidden, rows, exclude, first_item, parties, 1, strategy, weights, min_member_util, row_lse, allow,
+                                row_filter, temperature)[2]
+            return ids, scores, n, util
+        pr_d = parties.to(self.device).contiguous()
+        w_d = None if w is None else w.to(self.device).contiguous()
+        lse_d = None if row_lse is None else row_lse.to(self.device).contiguous()
+        V = self.cfg.vocab_size
+        sc = self._scratch("b4r_rank_joint", grouped_scratch_bytes(lambda np_, *d: self.lib.b4r_rank_joint_scratch_bytes(np_, M, *d), NP, V, k))
+        _lib.check(self.lib.b4r_rank_joint(*sweep[:11], *filt, inv_t, _ptr(lse_d), _ptr(pr_d), NP, M, _ptr(w_d), mode,
+                                           float(min_member_util), k, _ptr(ids), _ptr(scores), _ptr(n), _ptr(util), _ptr(sc), sc.numel(),
+                                           _stream(self.device)), "b4r_rank_joint")
+        return ids, scores, n, util
 
     def sample_full(self, hidden: torch.Tensor, rows: Optional[torch.Tensor], exclude: Optional[torch.Tensor], first_item: int,
                     gt: Optional[torch.Tensor], k: int, seed: int, allow=None, row_filter=None, temperature: float = 1.0,

@@ -821,6 +821,58 @@ class BERT4RecModel:
                                        user_ids, user0, min_logp)
         return state
 
+    def recommend_joint_tensor(self, encoder_input: Dict[str, torch.Tensor], parties, k: int = 10, strategy: str = "additive", weights=None,
+                               min_member_probability=None, calibrated: bool = True, exclude_seen: bool = True,
+                               exclude: Optional[torch.Tensor] = None, allow=None, row_filter=None, temperature: float = 1.0,
+                               return_members: bool = False):
+        """Several users deciding together: one top-k list of the whole catalogue per PARTY of batch rows (a household, friends, a
+        shared playlist), from one b4r_rank_joint sweep: no [B, V] scores.  parties [NP, M] integers, M <= 16: the batch rows of each
+        party, -1 padded; a row may belong to several parties.  An item is ranked for a party when every member could be served it
+        (recommend_tensor's exclusions -- exclude_seen, exclude -- and filter -- allow, row_filter [B] -- per member: an item any
+        member has seen is out).  strategy, over the members' scores of the item:
+          "additive"       their sum, each times its entry of weights [NP, M] (None: 1)
+          "least_misery"   their minimum: nobody is left with an item they dislike
+          "most_pleasure"  their maximum
+        calibrated (default): a member's score is the log probability of the item under the member's catalogue softmax at
+        `temperature` (score_distribution_tensor's logp: one b4r_score_dist sweep for the normalisers first), which is what makes the
+        scores of different users comparable; the additive aggregate is then the log of the product of the probabilities.
+        min_member_probability q in (0, 1]: the veto -- an item some member takes with probability below q is out.
+        calibrated=False skips the distribution sweep and aggregates the raw scores (min_member_probability must be None, temperature
+        1).  Returns device tensors (ids [NP,k] int64, scores [NP,k] fp32: the aggregates, descending, ties to the lower id, n [NP]
+        int32: the items the party could be served), -1 / -inf where there are fewer than k; with return_members a fourth,
+        member_logp [NP,k,M] fp32: each member's own score of each returned item (-inf for an absent slot and under the -1 tail).
+        A party without members, or with a member who can be served nothing, gets an empty list.
+        The batch is prepare_inference's: exactly one ranked slot per row."""
+        rows_in = encoder_input.get("input_word_ids") if hasattr(encoder_input, "get") else None
+        if rows_in is None or torch.as_tensor(rows_in).ndim != 2:
+            raise ValueError("recommend_joint_tensor takes prepare_inference's batch: input_word_ids [B, L] and masked_lm_positions [B, P]")
+        B = int(torch.as_tensor(rows_in).shape[0])
+        parties, k, _, w, min_util, _ = engine_mod.check_joint_args(parties, k, strategy, weights, min_member_probability, calibrated,
+                                                                    temperature, B)
+        allow, rf, (tokens, mask, pos), _, slots, _ = self._one_slot_batch("recommend_joint_tensor", encoder_input, exclude, allow, row_filter)
+        NP, M = (int(x) for x in parties.shape)
+        dev, first = self.device, engine_mod.SPECIAL_IDS
+        if B == 0 or NP == 0:
+            out = (torch.full((NP, k), -1, dtype=torch.int64, device=dev), torch.full((NP, k), float("-inf"), dtype=torch.float32, device=dev),
+                   torch.zeros((NP,), dtype=torch.int32, device=dev))
+            return out + (torch.full((NP, k, M), float("-inf"), dtype=torch.float32, device=dev),) if return_members else out
+        hidden, _, _ = self._ranked_slot_hidden({"input_word_ids": tokens, "input_mask": mask, "masked_lm_positions": pos}, slots=slots)
+        ex_rows = self._excluded_rows(encoder_input, slots, exclude_seen, exclude)
+        lse = self.engine.score_distribution(hidden, None, ex_rows, first, None, allow, rf, temperature)[2] if calibrated else None
+        ids, scores, n, util = self.engine.rank_joint(hidden, None, ex_rows, first, parties, k, strategy, w, min_util, lse, allow, rf,
+                                                      temperature, return_members)
+        return (ids, scores, n, util) if return_members else (ids, scores, n)
+
+    def recommend_joint(self, encoder_input: dict, parties, k: int = 10, strategy: str = "additive", weights=None,
+                        min_member_probability=None, calibrated: bool = True, exclude_seen: bool = True, exclude=None, allow=None,
+                        row_filter=None, temperature: float = 1.0, return_members: bool = False):
+        """recommend_joint_tensor as Python lists: per party (ids, scores, n), or (ids, scores, n, member_logp) with return_members;
+        ids and scores have length k (-1 / -inf where the party could be served fewer)."""
+        got = self.recommend_joint_tensor(encoder_input, parties, k, strategy, weights, min_member_probability, calibrated, exclude_seen,
+                                          exclude, allow, row_filter, temperature, return_members)
+        cols = [t.cpu().tolist() for t in got]
+        return [tuple(col[p] for col in cols) for p in range(len(cols[0]))]
+
     def _rank_items_ragged(self, encoder_input, items):
         """Candidate lists of different lengths: one kernel call per distinct length."""
         flat = [c for row in items for c in row]

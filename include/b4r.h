@@ -615,6 +615,45 @@ int b4r_attribution_select(const float* base_logp, const float* occ_logp, const 
  * among the running entries (and the running entries' among them) found by bisection. */
 int b4r_audience_merge(const float* logp, int32_t ld, int32_t R, int32_t Q, const int64_t* user_ids, int64_t user0, float min_logp,
                        int32_t K, int64_t* best_user, float* best_logp, int64_t* reach, int64_t* demand, b4r_stream_t stream);
+/* Joint recommendations: several users deciding together get ONE full-catalogue top-K list per party (the word "group" means an
+ * item category in this library, so the set of users is a party), without an [R, V] buffer.  The first 11 arguments (hidden .. E)
+ * and allow_bits / n_filters / row_filter / item_scale are b4r_rank_full_ex's, there is no gt.  Per row r:
+ *   s(r, j), allowed(r)  b4r_rank_full_ex's with gt = NULL, bit for bit (bias may be NULL)
+ *   t(r, j) = fl32(s(r, j) * inv_temperature): b4r_score_dist's t; inv_temperature finite and > 0 (else B4R_E_BADARG)
+ *   u(r, j) = fl32((double) t(r, j) - row_lse[r]): b4r_score_dist's query_logp with row_lse [R] (double) taken as given, which is what
+ *             makes the scores of different users comparable; row_lse = NULL: u = t (uncalibrated).
+ * party_rows [NP, M] int32, 1 <= M <= 16 (else B4R_E_SHAPE): the members of party p are the entries of party_rows[p] in [0, R), in
+ * slot order m = 0 .. M-1; any other value is an absent slot; a row may belong to several parties.
+ *   allowed(p) = the j that lie in allowed(r) of EVERY member, minus the vetoed ones: j is vetoed when some member has
+ *                u(r, j) < min_member_util (-inf: no veto; NaN: B4R_E_BADARG).  A party without members has an empty allowed set,
+ *                and so has a party with a member whose row_lse is -inf (or NaN) or whose hidden_row is negative: a member with
+ *                nothing to be served.  No NaN anywhere.
+ *   a(p, j)    B4R_JOINT_ADDITIVE       acc = 0.0f; for the present members, m ascending: acc = fmaf(w, u, acc) with
+ *                                       w = member_weight[p][m] ([NP, M] fp32) or 1.0f when member_weight is NULL
+ *              B4R_JOINT_LEAST_MISERY   the minimum of u over the members   (equal values, -0.0 and +0.0: the earlier member's bits)
+ *              B4R_JOINT_MOST_PLEASURE  the maximum of u over the members   (the same)
+ *              member_weight is read by the additive mode only; non-finite or negative weights are outside the contract.  Another
+ *              mode: B4R_E_BADARG.
+ *   topk_ids int64 / topk_scores fp32 [NP, K]: the first K of allowed(p) by a descending (-0.0 counts as +0.0), ties to the lower
+ *              id; the tail is -1 / -inf.  K in [0, 1024].
+ *   party_n [NP] int32 = |allowed(p)|
+ *   member_util [NP, K, M] fp32: u(member m, topk_ids[p][i]); -inf for an absent slot and for the -1 tail.
+ * Any output may be NULL.  NP = 0 or K = 0 succeeds and launches nothing.  scratch: b4r_rank_joint_scratch_bytes(NP, M, V, K) bytes
+ * for one pass over all parties; a smaller one processes the parties tile by tile (a tile is 16 / MP parties, MP the smallest of
+ * 1, 2, 4, 8, 16 that is >= M), and one too small for a tile returns B4R_E_NOMEM.  Every check happens before any launch.  Only
+ * enqueues (two launches per group of parties, three with member_util; one stream, no host sync, graph-capturable); integer
+ * counting and no floating-point atomics: bitwise reproducible, whatever the order of the parties, the tile a party lands in and
+ * the rows it shares with others.  The sweep keeps b4r_rank_full's tile (16 row slots x 1024 ids per 256-thread workgroup, the
+ * table chunk staged through LDS once for all slots) and reduces over a party's members in registers before it selects.
+ * Non-finite hidden values are outside the contract (they are never read out of bounds). */
+enum { B4R_JOINT_ADDITIVE = 0, B4R_JOINT_LEAST_MISERY = 1, B4R_JOINT_MOST_PLEASURE = 2 };
+int64_t b4r_rank_joint_scratch_bytes(int32_t NP, int32_t M, int32_t V, int32_t K);
+int b4r_rank_joint(const float* hidden, int32_t hidden_ld, const int64_t* hidden_row, const float* table, const float* bias, int32_t H,
+                   int32_t V, int32_t first_item, int32_t R, const int64_t* exclude, int32_t E, const uint32_t* allow_bits,
+                   int32_t n_filters, const int32_t* row_filter, const float* item_scale, float inv_temperature, const double* row_lse,
+                   const int32_t* party_rows, int32_t NP, int32_t M, const float* member_weight, int32_t mode, float min_member_util,
+                   int32_t K, int64_t* topk_ids, float* topk_scores, int32_t* party_n, float* member_util, void* scratch,
+                   int64_t scratch_bytes, b4r_stream_t stream);
 /* replaces the metric loop of bert4rec_evaluator.py:118-120 over evaluation_metrics.py:47-112 for a batch of ranks:
  * gain_sums[m] += sum over gt_rank[i] > 0 of gain_m(gt_rank[i]), users[0] += #{gt_rank[i] > 0}; double / int64 DEVICE
  * accumulators the caller reads once per evaluate().  family[m]: 0 count (gain 1), 1 hit@cutoff (rank <= k), 2 NDCG@cutoff
