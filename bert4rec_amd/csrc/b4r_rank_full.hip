@@ -10,8 +10,8 @@
 //
 // Three launches per group of rows that fits the scratch:
 //   1. gt key     one thread per row: s_gt by the same chain, as the order-preserving integer image ("key") of the score.
-//   2. sweep      grid (group of FG = 16 rows) x (chunk of FCH = 1024 ids).  Each 256-thread workgroup stages its chunk's table
-//                 rows through LDS in k-blocks of FKB floats (16-byte loads), once for all 16 rows, and forms 16 x 1024 scores
+//   2. sweep      grid (group of 16 rows) x (chunk of 1024 ids): the tile of b4r_catalogue_tile.h.  Each 256-thread workgroup stages
+//                 its chunk's table rows through LDS in k-blocks of 16 floats (16-byte loads), once for all 16 rows, and forms 16 x 1024 scores
 //                 with the fma chain on the VALU (the hidden rows are LDS broadcasts; 2 ids per thread per k-block halve those).
 //                 Scores stay in registers (4 ids x 16 rows per thread).  Excluded ids come from a per-row LDS bitmap built from
 //                 exclude[r].  Per row it counts, in integers, the allowed ids that beat gt, and selects the chunk's best
@@ -30,112 +30,9 @@
 #include <algorithm>
 
 #include "b4r_common.h"
+#include "b4r_catalogue_tile.h"
 
 namespace {
-
-constexpr int FT = 256;          // threads per workgroup
-constexpr int FG = 16;           // rows per sweep workgroup
-constexpr int FQ = 4;            // ids per thread per chunk
-constexpr int FIPT = 2;          // ids scored together per k-block (FQ / FIPT steps)
-constexpr int FCH = FT * FQ;     // ids per chunk
-constexpr int FKB = 16;          // k-block (floats of a table row staged at a time)
-constexpr int FK_MAX = 1024;     // largest K
-constexpr uint32_t NOT_ALLOWED = 0xFFFFFFFFu;   // raw-bits marker of an id that is not ranked (a NaN pattern: out of contract)
-
-static_assert(FT == FG * 16, "digit search: 16 threads per row");
-static_assert(FCH <= 65536, "the local id takes the low 16 bits of the sweep key");
-
-// order-preserving image of a score for an ascending unsigned compare; -0.0 counts as +0.0 (they compare equal)
-__device__ __forceinline__ uint32_t score_key_bits(uint32_t u) {
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ uint32_t score_key(float s) { return score_key_bits(__builtin_bit_cast(uint32_t, s)); }
-
-// bias NULL: + 0.0f; scale (NULL: none) multiplies the rounded chain once
-__device__ __forceinline__ float row_score(const float* h, const float* e, const float* bias, const float* scale, int64_t j, int H) {
-  float acc = 0.f;
-  for (int k = 0; k < H; ++k) acc = __builtin_fmaf(h[k], e[k], acc);   // k-ordered fp32 fma chain (the contract)
-  const float s = acc + (bias ? bias[j] : 0.f);
-  return scale ? s * scale[j] : s;
-}
-
-// state of one row's radix select over W-bit unique keys: `hi` top bits are resolved (= prefix); `rem` ids are still to be taken
-// from those whose top bits equal the prefix; done: every key >= thr is taken (take = 0: none)
-struct Sel {
-  uint64_t prefix, thr;
-  int hi, rem, done, take;
-};
-
-// init: n allowed keys, `need` to take; kmin / kmax over the allowed score keys (the top 32 bits of every W-bit key)
-__device__ __forceinline__ void sel_init(Sel& s, int n, int need, uint32_t kmin, uint32_t kmax, int W) {
-  s.take = need > 0;
-  s.rem = need;
-  s.thr = 0;
-  if (need <= 0 || need >= n) {
-    s.done = 1; s.hi = 0; s.prefix = 0;   // none, or every allowed id (thr = 0)
-    return;
-  }
-  const uint32_t diff = kmin ^ kmax;
-  s.hi = diff ? __clz(diff) : 32;
-  s.prefix = (uint64_t)kmax >> (32 - s.hi);
-  s.done = 0;
-  (void)W;
-}
-
-__device__ __forceinline__ bool sel_match(const Sel& s, uint64_t key, int W) {
-  return s.hi == 0 || (key >> (W - s.hi)) == s.prefix;
-}
-
-__device__ __forceinline__ int sel_nb(const Sel& s, int W) { return min(8, W - s.hi); }
-
-// the 16 threads qq = 0..15 of a row: part[qq] = count of digits 255-16qq .. 240-16qq (descending)
-__device__ __forceinline__ void sel_part(const uint32_t* hist, uint32_t* part, int qq) {
-  uint32_t c = 0;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) c += hist[255 - 16 * qq - i];
-  part[qq] = c;
-}
-
-// the thread whose 16 digits hold the rem-th key from the top writes the advanced state `s` (a copy taken before the barrier
-// that precedes this call) to `out`; the other threads of the row leave it alone
-__device__ __forceinline__ void sel_advance(Sel s, Sel& out, const uint32_t* hist, const uint32_t* part, int qq, int W) {
-  uint32_t above = 0;
-  for (int i = 0; i < qq; ++i) above += part[i];
-  const uint32_t rem = (uint32_t)s.rem;
-  if (!(above < rem && above + part[qq] >= rem)) return;
-  const int nb = sel_nb(s, W);
-  for (int i = 0; i < 16; ++i) {
-    const int d = 255 - 16 * qq - i;
-    const uint32_t c = hist[d];
-    if (above + c >= rem) {
-      const uint32_t left = rem - above;
-      s.prefix = (s.prefix << nb) | (uint64_t)d;
-      s.hi += nb;
-      s.rem = (int)left;
-      if (c == left || s.hi >= W) {
-        s.done = 1;
-        s.thr = s.hi >= W ? s.prefix : (s.prefix << (W - s.hi));
-      }
-      out = s;
-      return;
-    }
-    above += c;
-  }
-}
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-  return v;
-}
 
 // ---- 1. score key of the held-out item ----------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void full_gt_key_kernel(const float* __restrict__ hidden, int hidden_ld,
@@ -152,7 +49,7 @@ __global__ __launch_bounds__(64) void full_gt_key_kernel(const float* __restrict
   gkey[lr] = score_key(row_score(hidden + hr * hidden_ld, table + g * H, bias, scale, g, H));
 }
 
-// ---- 2. sweep: (group of FG rows) x (chunk of FCH ids) -------------------------------------------------------------------------
+// ---- 2. sweep: (group of TILE_G rows) x (chunk of TILE_CH ids) -----------------------------------------------------------------
 struct SweepArgs {
   const float* hidden; const int64_t* hidden_row; const float* table; const float* bias;
   const int64_t* exclude; const int64_t* gt;
@@ -171,114 +68,83 @@ struct SweepExtra {
 
 // FILT: the row bitmap starts from the row's filter words; SCALE: score = fl32((chain + bias) * scale[j]); BIAS = false: bias is +0.0f
 template <bool FILT, bool SCALE, bool BIAS>
-__global__ __launch_bounds__(FT, 2) void full_sweep_kernel(SweepArgs a, SweepExtra x) {
-  __shared__ float tile[FIPT * FT * (FKB + 1)];
-  __shared__ __attribute__((aligned(16))) float hsh[FG * FKB];
-  __shared__ uint32_t bits[FG][FCH / 32];
-  __shared__ uint32_t hist[FG][256];
-  __shared__ uint32_t part[FG][16];
-  __shared__ Sel st[FG];
-  __shared__ uint32_t s_cnt[FG], s_beat[FG], s_kmin[FG], s_kmax[FG], s_out[FG];
-  __shared__ int64_t s_hoff[FG], s_gt[FG];
+__global__ __launch_bounds__(TILE_T, 2) void full_sweep_kernel(SweepArgs a, SweepExtra x) {
+  __shared__ float tile[TILE_IPT * TILE_T * (TILE_KB + 1)];
+  __shared__ __attribute__((aligned(16))) float hsh[TILE_G * TILE_KB];
+  __shared__ uint32_t bits[TILE_G][TILE_CH / 32];
+  __shared__ uint32_t hist[TILE_G][256];
+  __shared__ uint32_t part[TILE_G][16];
+  __shared__ Sel st[TILE_G];
+  __shared__ uint32_t s_cnt[TILE_G], s_beat[TILE_G], s_kmin[TILE_G], s_kmax[TILE_G], s_out[TILE_G];
   __shared__ int s_alldone;
+  __shared__ int64_t s_hoff[TILE_G], s_gt[TILE_G];
 
   const int tid = threadIdx.x, lane = tid & 63;
-  const int lr0 = blockIdx.x * FG;
+  const int lr0 = blockIdx.x * TILE_G;
   const int chunk = blockIdx.y;
-  const int64_t c0 = (int64_t)chunk * FCH;
+  const int64_t c0 = (int64_t)chunk * TILE_CH;
   const int H = a.H;
 
-  if (tid < FG) {
-    const int lr = lr0 + tid;
-    const bool rv = lr < a.n;
-    const int64_t r = a.r0 + lr;
-    s_hoff[tid] = rv ? (a.hidden_row ? a.hidden_row[r] : r) * a.hidden_ld : -1;
-    s_gt[tid] = (rv && a.gt) ? a.gt[r] : -1;
+  if (tid < TILE_G) {
+    tile_row_setup(tid, lr0, a.n, a.r0, a.hidden_row, a.hidden_ld, a.gt, s_hoff, s_gt);
     s_cnt[tid] = 0; s_beat[tid] = 0; s_out[tid] = 0;
     s_kmin[tid] = 0xFFFFFFFFu; s_kmax[tid] = 0u;
   }
-  if constexpr (FILT) {
-    // bit set = not ranked: the complement of the row's filter words of this chunk (no filter for the row: all ranked)
-    const int64_t W = ((int64_t)a.V + 31) >> 5;
-    for (int i = tid; i < FG * (FCH / 32); i += FT) {
-      const int g = i / (FCH / 32), w = i - g * (FCH / 32);
-      const int lr = lr0 + g;
-      const int64_t wi = (c0 >> 5) + w;
-      uint32_t word = 0u;
-      if (lr < a.n && wi < W) {
-        const int32_t f = x.row_filter ? x.row_filter[a.r0 + lr] : 0;
-        if (f >= 0 && f < x.n_filters) word = ~x.allow[(int64_t)f * W + wi];
-      }
-      bits[g][w] = word;
-    }
-  } else {
-    for (int i = tid; i < FG * (FCH / 32); i += FT) (&bits[0][0])[i] = 0u;
-  }
-  __syncthreads();
-  if (a.E > 0) {
-    for (int f = tid; f < FG * a.E; f += FT) {
-      const int g = f / a.E, e = f - g * a.E;
-      if (s_hoff[g] < 0) continue;
-      const int64_t id = a.exclude[(a.r0 + lr0 + g) * (int64_t)a.E + e];
-      if (id >= c0 && id < c0 + FCH) {
-        const int l = (int)(id - c0);
-        atomicOr(&bits[g][l >> 5], 1u << (l & 31));
-      }
-    }
-  }
+  tile_row_bitmap(bits, FILT, x.allow, x.row_filter, x.n_filters, a.exclude, a.E, s_hoff, a.r0, lr0, a.n, a.V, c0);
 
   // ---- scores: raw fp32 bits in registers, NOT_ALLOWED where the id is not ranked -----------------------------------------------
-  uint32_t raw[FQ][FG];
+  uint32_t raw[TILE_Q][TILE_G];
 #pragma unroll
-  for (int ps = 0; ps < FQ / FIPT; ++ps) {
-    float acc[FIPT][FG];
+  for (int ps = 0; ps < TILE_Q / TILE_IPT; ++ps) {
+    // (the k-block loop is written out in each of the four sweeps: stated once as a function it changed their registers)
+    float acc[TILE_IPT][TILE_G];
 #pragma unroll
-    for (int ii = 0; ii < FIPT; ++ii)
+    for (int ii = 0; ii < TILE_IPT; ++ii)
 #pragma unroll
-      for (int g = 0; g < FG; ++g) acc[ii][g] = 0.f;
-    const int64_t cj0 = c0 + (int64_t)ps * FIPT * FT;   // first id of this step
-    for (int kb = 0; kb < H; kb += FKB) {
-      const int kn = min(FKB, H - kb);   // a multiple of 4 (H % 4 == 0)
+      for (int g = 0; g < TILE_G; ++g) acc[ii][g] = 0.f;
+    const int64_t cj0 = c0 + (int64_t)ps * TILE_IPT * TILE_T;   // first id of this step
+    for (int kb = 0; kb < H; kb += TILE_KB) {
+      const int kn = min(TILE_KB, H - kb);   // a multiple of 4 (H % 4 == 0)
       const int k4 = kn >> 2;
       __syncthreads();   // the previous block is consumed (and, the first time, the bitmap is complete)
-      for (int f = tid; f < FIPT * FT * k4; f += FT) {
+      for (int f = tid; f < TILE_IPT * TILE_T * k4; f += TILE_T) {
         const int i = f / k4, c4 = f - i * k4;
         const int64_t j = cj0 + i;
         const f32x4 v = j < a.V ? *reinterpret_cast<const f32x4*>(a.table + j * H + kb + 4 * c4) : (f32x4){0.f, 0.f, 0.f, 0.f};
-        float* dst = tile + i * (FKB + 1) + 4 * c4;
+        float* dst = tile + i * (TILE_KB + 1) + 4 * c4;
         dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3];
       }
       {
-        const int g = tid / FKB, k = tid - g * FKB;   // FG * FKB == FT
+        const int g = tid / TILE_KB, k = tid - g * TILE_KB;   // TILE_G * TILE_KB == TILE_T
         hsh[tid] = (k < kn && s_hoff[g] >= 0) ? a.hidden[s_hoff[g] + kb + k] : 0.f;
       }
       __syncthreads();
       for (int k = 0; k < kn; k += 4) {
-        float e[FIPT][4];
+        float e[TILE_IPT][4];
 #pragma unroll
-        for (int ii = 0; ii < FIPT; ++ii)
+        for (int ii = 0; ii < TILE_IPT; ++ii)
 #pragma unroll
-          for (int u = 0; u < 4; ++u) e[ii][u] = tile[(ii * FT + tid) * (FKB + 1) + k + u];
+          for (int u = 0; u < 4; ++u) e[ii][u] = tile[(ii * TILE_T + tid) * (TILE_KB + 1) + k + u];
 #pragma unroll
-        for (int g = 0; g < FG; ++g) {
-          const f32x4 h = *reinterpret_cast<const f32x4*>(hsh + g * FKB + k);
+        for (int g = 0; g < TILE_G; ++g) {
+          const f32x4 h = *reinterpret_cast<const f32x4*>(hsh + g * TILE_KB + k);
 #pragma unroll
           for (int u = 0; u < 4; ++u)
 #pragma unroll
-            for (int ii = 0; ii < FIPT; ++ii) acc[ii][g] = __builtin_fmaf(h[u], e[ii][u], acc[ii][g]);
+            for (int ii = 0; ii < TILE_IPT; ++ii) acc[ii][g] = __builtin_fmaf(h[u], e[ii][u], acc[ii][g]);
         }
       }
     }
 #pragma unroll
-    for (int ii = 0; ii < FIPT; ++ii) {
-      const int q = ps * FIPT + ii;
-      const int l = q * FT + tid;
+    for (int ii = 0; ii < TILE_IPT; ++ii) {
+      const int q = ps * TILE_IPT + ii;
+      const int l = q * TILE_T + tid;
       const int64_t j = c0 + l;
       const bool inb = j >= a.lo && j < a.V;
       const float b = BIAS ? (inb ? a.bias[j] : 0.f) : 0.f;
       const float sc = SCALE ? (inb ? x.scale[j] : 1.f) : 1.f;
 #pragma unroll
-      for (int g = 0; g < FG; ++g) {
+      for (int g = 0; g < TILE_G; ++g) {
         const bool ex = (bits[g][l >> 5] >> (l & 31)) & 1u;
         const bool ok = inb && s_hoff[g] >= 0 && (!ex || j == s_gt[g]);
         // (the unfiltered instance keeps the statement it had: a sum formed outside the select compiles to other code)
@@ -289,17 +155,19 @@ __global__ __launch_bounds__(FT, 2) void full_sweep_kernel(SweepArgs a, SweepExt
   }
 
   // ---- per row: allowed count, ids that beat gt, key range ------------------------------------------------------------------
+  // (this loop and the select after it are written out in the three sweeps that select: stated once as a function they changed the
+  // sweeps' registers and this kernel measured 0.5-1.1 % slower)
 #pragma unroll
-  for (int g = 0; g < FG; ++g) {
+  for (int g = 0; g < TILE_G; ++g) {
     const bool gv = a.gt && s_gt[g] >= a.lo && s_gt[g] < a.V && s_hoff[g] >= 0;
     const uint32_t gk = gv ? a.gkey[lr0 + g] : 0u;
     const int64_t gid = s_gt[g];
     uint32_t cnt = 0, beat = 0, kmin = 0xFFFFFFFFu, kmax = 0u;
 #pragma unroll
-    for (int q = 0; q < FQ; ++q) {
+    for (int q = 0; q < TILE_Q; ++q) {
       if (raw[q][g] == NOT_ALLOWED) continue;
       const uint32_t k = score_key_bits(raw[q][g]);
-      const int64_t j = c0 + q * FT + tid;
+      const int64_t j = c0 + q * TILE_T + tid;
       cnt += 1;
       beat += (gv && (k > gk || (k == gk && j < gid))) ? 1u : 0u;
       kmin = min(kmin, k); kmax = max(kmax, k);
@@ -312,36 +180,36 @@ __global__ __launch_bounds__(FT, 2) void full_sweep_kernel(SweepArgs a, SweepExt
     }
   }
   __syncthreads();
-  if (tid < FG && lr0 + tid < a.n) {
+  if (tid < TILE_G && lr0 + tid < a.n) {
     const int64_t o = (int64_t)(lr0 + tid) * a.nch + chunk;
     a.c_beat[o] = (int32_t)s_beat[tid];
     const int n = (int)s_cnt[tid];
-    sel_init(st[tid], n, min(a.cap, n), s_kmin[tid], s_kmax[tid], 48);
-  } else if (tid < FG) {
-    sel_init(st[tid], 0, 0, 0u, 0u, 48);
+    sel_init(st[tid], n, min(a.cap, n), s_kmin[tid], s_kmax[tid]);
+  } else if (tid < TILE_G) {
+    sel_init(st[tid], 0, 0, 0u, 0u);
   }
   if (tid == 0) s_alldone = 0;
 
-  // ---- radix select over (score key << 16 | FCH-1 - local id) --------------------------------------------------------------
+  // ---- radix select over (score key << 16 | TILE_CH-1 - local id) --------------------------------------------------------------
   for (int pass = 0; pass < 6; ++pass) {
     __syncthreads();
     if (tid == 0) {
       int all = 1;
-      for (int g = 0; g < FG; ++g) all &= st[g].done;
+      for (int g = 0; g < TILE_G; ++g) all &= st[g].done;
       s_alldone = all;
     }
-    for (int i = tid; i < FG * 256; i += FT) (&hist[0][0])[i] = 0u;
+    for (int i = tid; i < TILE_G * 256; i += TILE_T) (&hist[0][0])[i] = 0u;
     __syncthreads();
     if (s_alldone) break;
 #pragma unroll
-    for (int g = 0; g < FG; ++g) {
+    for (int g = 0; g < TILE_G; ++g) {
       const Sel s = st[g];
       if (s.done) continue;
       const int nb = sel_nb(s, 48), sh = 48 - s.hi - nb;
 #pragma unroll
-      for (int q = 0; q < FQ; ++q) {
+      for (int q = 0; q < TILE_Q; ++q) {
         if (raw[q][g] == NOT_ALLOWED) continue;
-        const uint64_t key = ((uint64_t)score_key_bits(raw[q][g]) << 16) | (uint64_t)(FCH - 1 - (q * FT + tid));
+        const uint64_t key = ((uint64_t)score_key_bits(raw[q][g]) << 16) | (uint64_t)(TILE_CH - 1 - (q * TILE_T + tid));
         if (sel_match(s, key, 48)) atomicAdd(&hist[g][(key >> sh) & ((1u << nb) - 1u)], 1u);
       }
     }
@@ -356,15 +224,15 @@ __global__ __launch_bounds__(FT, 2) void full_sweep_kernel(SweepArgs a, SweepExt
 
   // ---- emit the selected ids of each row (any order: the merge orders them) ------------------------------------------------
 #pragma unroll
-  for (int g = 0; g < FG; ++g) {
+  for (int g = 0; g < TILE_G; ++g) {
     const Sel s = st[g];
     if (!s.take || !s.done) continue;
     const int64_t base = ((int64_t)(lr0 + g) * a.nch + chunk) * a.cap;
 #pragma unroll
-    for (int q = 0; q < FQ; ++q) {
+    for (int q = 0; q < TILE_Q; ++q) {
       if (raw[q][g] == NOT_ALLOWED) continue;
-      const int l = q * FT + tid;
-      const uint64_t key = ((uint64_t)score_key_bits(raw[q][g]) << 16) | (uint64_t)(FCH - 1 - l);
+      const int l = q * TILE_T + tid;
+      const uint64_t key = ((uint64_t)score_key_bits(raw[q][g]) << 16) | (uint64_t)(TILE_CH - 1 - l);
       if (key < s.thr) continue;
       const uint32_t slot = atomicAdd(&s_out[g], 1u);
       if (slot < (uint32_t)a.cap) {
@@ -374,7 +242,7 @@ __global__ __launch_bounds__(FT, 2) void full_sweep_kernel(SweepArgs a, SweepExt
     }
   }
   __syncthreads();
-  if (tid < FG && lr0 + tid < a.n) a.c_cnt[(int64_t)(lr0 + tid) * a.nch + chunk] = (int32_t)min(s_out[tid], (uint32_t)a.cap);
+  if (tid < TILE_G && lr0 + tid < a.n) a.c_cnt[(int64_t)(lr0 + tid) * a.nch + chunk] = (int32_t)min(s_out[tid], (uint32_t)a.cap);
 }
 
 // ---- 3. merge: one workgroup per row ------------------------------------------------------------------------------------------
@@ -386,98 +254,34 @@ struct MergeArgs {
   int nch, cap, K, lo, V;
 };
 
-__global__ __launch_bounds__(FT) void full_merge_kernel(MergeArgs a) {
+__global__ __launch_bounds__(TILE_T) void full_merge_kernel(MergeArgs a) {
   __shared__ uint32_t hist[256];
   __shared__ uint32_t part[16];
   __shared__ Sel st;
   __shared__ uint32_t s_n, s_kmin, s_kmax, s_out, s_beat;
-  __shared__ uint64_t sel_key[FK_MAX];
-  __shared__ float sel_score[FK_MAX];
-  const int tid = threadIdx.x, lane = tid & 63;
+  __shared__ uint64_t sel_key[SEL_K_MAX];
+  __shared__ float sel_val[SEL_K_MAX];
+  const MergeSel L{hist, part, st, s_n, s_kmin, s_kmax, s_out, &s_beat, sel_key, sel_val};
   const int lr = blockIdx.x;
   const int64_t r = a.r0 + lr;
-  const int32_t* cnt = a.c_cnt + (int64_t)lr * a.nch;
-  const int64_t base = (int64_t)lr * a.nch * a.cap;
-  const int64_t total_slots = (int64_t)a.nch * a.cap;
-
-  if (tid == 0) { s_n = 0; s_kmin = 0xFFFFFFFFu; s_kmax = 0u; s_out = 0; s_beat = 0; }
-  __syncthreads();
-  {
-    uint32_t n = 0, beat = 0, kmin = 0xFFFFFFFFu, kmax = 0u;
-    for (int c = tid; c < a.nch; c += FT) { n += (uint32_t)cnt[c]; beat += (uint32_t)a.c_beat[(int64_t)lr * a.nch + c]; }
-    for (int64_t e = tid; e < total_slots; e += FT) {
-      const int c = (int)(e / a.cap), i = (int)(e - (int64_t)c * a.cap);
-      if (i >= cnt[c]) continue;
-      const uint32_t k = score_key(a.c_score[base + e]);
-      kmin = min(kmin, k); kmax = max(kmax, k);
-    }
-    n = wave_sum_u32(n); beat = wave_sum_u32(beat);
-    kmin = wave_min_u32(kmin); kmax = wave_max_u32(kmax);
-    if (lane == 0) { atomicAdd(&s_n, n); atomicAdd(&s_beat, beat); atomicMin(&s_kmin, kmin); atomicMax(&s_kmax, kmax); }
-  }
-  __syncthreads();
-  const int n = (int)s_n;
-  const int need = min(a.K, n);
-  if (tid == 0) sel_init(st, n, need, s_kmin, s_kmax, 64);
-  for (int pass = 0; pass < 8; ++pass) {
-    __syncthreads();
-    if (st.done) break;
-    for (int i = tid; i < 256; i += FT) hist[i] = 0u;
-    __syncthreads();
-    const Sel s = st;
-    const int nb = sel_nb(s, 64), sh = 64 - s.hi - nb;
-    for (int64_t e = tid; e < total_slots; e += FT) {
-      const int c = (int)(e / a.cap), i = (int)(e - (int64_t)c * a.cap);
-      if (i >= cnt[c]) continue;
-      const uint64_t key = ((uint64_t)score_key(a.c_score[base + e]) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)a.c_id[base + e]);
-      if (sel_match(s, key, 64)) atomicAdd(&hist[(key >> sh) & ((1u << nb) - 1u)], 1u);
-    }
-    __syncthreads();
-    if (tid < 16) sel_part(hist, part, tid);
-    __syncthreads();
-    if (tid < 16) sel_advance(s, st, hist, part, tid, 64);
-  }
-  __syncthreads();
-  if (st.take && st.done) {
-    const uint64_t thr = st.thr;
-    for (int64_t e = tid; e < total_slots; e += FT) {
-      const int c = (int)(e / a.cap), i = (int)(e - (int64_t)c * a.cap);
-      if (i >= cnt[c]) continue;
-      const float sc = a.c_score[base + e];
-      const uint64_t key = ((uint64_t)score_key(sc) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)a.c_id[base + e]);
-      if (key < thr) continue;
-      const uint32_t slot = atomicAdd(&s_out, 1u);
-      if (slot < (uint32_t)FK_MAX) { sel_key[slot] = key; sel_score[slot] = sc; }
-    }
-  }
-  __syncthreads();
-  const int m = min((int)s_out, min(a.K, FK_MAX));
-  for (int i = tid; i < m; i += FT) {
-    const uint64_t ki = sel_key[i];
-    int pos = 0;
-    for (int j = 0; j < m; ++j) pos += sel_key[j] > ki ? 1 : 0;   // keys are unique: a permutation of 0 .. m-1
-    if (a.topk_ids) a.topk_ids[r * a.K + pos] = (int64_t)(0xFFFFFFFFu - (uint32_t)(ki & 0xFFFFFFFFu));
-    if (a.topk_scores) a.topk_scores[r * a.K + pos] = sel_score[i];
-  }
-  for (int p = m + tid; p < a.K; p += FT) {
-    if (a.topk_ids) a.topk_ids[r * a.K + p] = -1;
-    if (a.topk_scores) a.topk_scores[r * a.K + p] = -INFINITY;
-  }
-  if (tid == 0 && a.gt_rank) {
+  const int64_t row = (int64_t)lr * a.nch;
+  const int m = merge_select<TILE_T>(L, a.c_score, a.c_id, a.c_cnt, a.c_beat, row, a.nch, a.cap, a.K);
+  merge_order<TILE_T>(L, m, a.K, [&](int pos, int64_t id, float score) {
+    if (a.topk_ids) a.topk_ids[r * a.K + pos] = id;
+    if (a.topk_scores) a.topk_scores[r * a.K + pos] = score;
+  });
+  if (threadIdx.x == 0 && a.gt_rank) {
     const int64_t g = a.gt ? a.gt[r] : -1;
     a.gt_rank[r] = (a.gt && g >= a.lo && g < a.V) ? (int32_t)(1 + s_beat) : 0;
   }
 }
 
-int64_t chunks_of(int32_t V) { return ((int64_t)V + FCH - 1) / FCH; }
-int64_t cap_of(int32_t K) { return std::min<int64_t>(K, FCH); }
-int64_t row_bytes(int32_t V, int32_t K) { return chunks_of(V) * (cap_of(K) * 8 + 8) + 4; }   // scores, ids | counts, beats | gt key
-
+int64_t row_bytes(int32_t V, int32_t K) { return tile_chunks_of(V) * (tile_cap_of(K) * 8 + 8) + 4; }   // scores, ids | counts, beats | gt key
 
 // ---- item neighbours: 1 / |row| of every table row, and the staged query rows ------------------------------------------------
 // one thread per row, k ascending, one fp32 fma per element: a fixed order, so rnorm is bitwise reproducible
-__global__ __launch_bounds__(FT) void item_rnorm_kernel(const float* __restrict__ table, int H, int V, float* __restrict__ rnorm) {
-  const int64_t j = (int64_t)blockIdx.x * FT + threadIdx.x;
+__global__ __launch_bounds__(TILE_T) void item_rnorm_kernel(const float* __restrict__ table, int H, int V, float* __restrict__ rnorm) {
+  const int64_t j = (int64_t)blockIdx.x * TILE_T + threadIdx.x;
   if (j >= V) return;
   const float* e = table + j * H;
   float ss = 0.f;
@@ -490,10 +294,10 @@ __global__ __launch_bounds__(FT) void item_rnorm_kernel(const float* __restrict_
 }
 
 // qhat[r][k] = table[q_r][k] (* rnorm[q_r] when given); qrow[r] = r, or -1 (the sweep ranks nothing for the row) when q_r is no item
-__global__ __launch_bounds__(FT) void item_query_kernel(const float* __restrict__ table, int H, int V, int lo,
+__global__ __launch_bounds__(TILE_T) void item_query_kernel(const float* __restrict__ table, int H, int V, int lo,
                                                         const int64_t* __restrict__ query, int R, const float* __restrict__ rnorm,
                                                         float* __restrict__ qhat, int64_t* __restrict__ qrow) {
-  const int64_t i = (int64_t)blockIdx.x * FT + threadIdx.x;
+  const int64_t i = (int64_t)blockIdx.x * TILE_T + threadIdx.x;
   if (i >= (int64_t)R * H) return;
   const int r = (int)(i / H), k = (int)(i - (int64_t)r * H);
   const int64_t q = query[r];
@@ -522,8 +326,8 @@ int rank_full_impl(const char* what, bool bias_required, const float* hidden, in
                    int32_t E, const int64_t* gt, int32_t K, const uint32_t* allow_bits, int32_t n_filters, const int32_t* row_filter,
                    const float* item_scale, int64_t* topk_ids, float* topk_scores, int32_t* gt_rank, void* scratch,
                    int64_t scratch_bytes, hipStream_t s) {
-  B4R_CHECK_ARG(R >= 0 && K >= 0 && K <= FK_MAX && E >= 0 && first_item >= 0, B4R_E_SHAPE,
-                "%s: bad shape (R = %d, K = %d in [0, %d], E = %d, first_item = %d)", what, R, K, FK_MAX, E, first_item);
+  B4R_CHECK_ARG(R >= 0 && K >= 0 && K <= SEL_K_MAX && E >= 0 && first_item >= 0, B4R_E_SHAPE,
+                "%s: bad shape (R = %d, K = %d in [0, %d], E = %d, first_item = %d)", what, R, K, SEL_K_MAX, E, first_item);
   B4R_CHECK_ARG(H > 0 && H % 4 == 0 && H <= 4096 && hidden_ld >= H && V > 0, B4R_E_SHAPE,
                 "%s: bad shape (H = %d, hidden_ld = %d, V = %d)", what, H, hidden_ld, V);
   B4R_CHECK_ARG(!allow_bits || n_filters > 0, B4R_E_SHAPE, "%s: allow_bits with n_filters = %d", what, n_filters);
@@ -532,19 +336,14 @@ int rank_full_impl(const char* what, bool bias_required, const float* hidden, in
   B4R_CHECK_ARG(E == 0 || exclude, B4R_E_BADARG, "%s: exclude is NULL with E = %d", what, E);
   B4R_CHECK_ARG(b4r_aligned16(table), B4R_E_ALIGN, "%s: the table must be 16-byte aligned", what);
   const int64_t per_row = row_bytes(V, K);
-  const int64_t usable = scratch ? scratch_bytes - (int64_t)((16 - ((uintptr_t)scratch & 15)) & 15) : 0;
-  int64_t group = usable > 0 ? usable / per_row : 0;
-  group = std::min<int64_t>(group, R);
-  if (group < R) group = group / FG * FG;   // whole sweep groups
-  B4R_CHECK_ARG(group >= std::min<int64_t>(R, FG), B4R_E_NOMEM,
+  const int64_t group = tile_group_of(scratch, scratch_bytes, per_row, R, TILE_G);   // whole sweep groups
+  B4R_CHECK_ARG(group >= std::min<int64_t>(R, TILE_G), B4R_E_NOMEM,
                 "%s: scratch of %lld bytes is too small: %lld bytes per row, %d rows at least (b4r_rank_full_scratch_bytes)", what,
-                (long long)scratch_bytes, (long long)per_row, std::min<int32_t>(R, FG));
-  group = std::min<int64_t>(group, 65535LL * FG);
-  const int nch = (int)chunks_of(V);
+                (long long)scratch_bytes, (long long)per_row, std::min<int32_t>(R, TILE_G));
+  const int nch = (int)tile_chunks_of(V);
   B4R_CHECK_ARG(nch <= 65535, B4R_E_SHAPE, "%s: V = %d is too large", what, V);
-  const int cap = (int)cap_of(K);
-  char* p = reinterpret_cast<char*>(((uintptr_t)scratch + 15) & ~(uintptr_t)15);
-  float* c_score = reinterpret_cast<float*>(p);
+  const int cap = (int)tile_cap_of(K);
+  float* c_score = reinterpret_cast<float*>(tile_scratch_base(scratch));
   int32_t* c_id = reinterpret_cast<int32_t*>(c_score + group * nch * cap);
   int32_t* c_cnt = c_id + group * nch * cap;
   int32_t* c_beat = c_cnt + group * nch;
@@ -559,9 +358,9 @@ int rank_full_impl(const char* what, bool bias_required, const float* hidden, in
     SweepArgs sa{hidden, hidden_row, table, bias, exclude, gt, gkey, c_score, c_id, c_cnt, c_beat, r0,
                  hidden_ld, H, V, first_item, E, n, nch, cap};
     SweepExtra sx{item_scale, allow_bits, row_filter, n_filters};
-    hipLaunchKernelGGL(sweep, dim3(b4r_cdiv(n, FG), nch), dim3(FT), 0, s, sa, sx);
+    hipLaunchKernelGGL(sweep, dim3(b4r_cdiv(n, TILE_G), nch), dim3(TILE_T), 0, s, sa, sx);
     MergeArgs ma{c_score, c_id, c_cnt, c_beat, gt, topk_ids, topk_scores, gt_rank, r0, nch, cap, K, first_item, V};
-    hipLaunchKernelGGL(full_merge_kernel, dim3(n), dim3(FT), 0, s, ma);
+    hipLaunchKernelGGL(full_merge_kernel, dim3(n), dim3(TILE_T), 0, s, ma);
   }
   B4R_CHECK_LAUNCH(what);
   return B4R_OK;
@@ -576,7 +375,7 @@ int64_t neighbour_bytes(int32_t R, int32_t V, int32_t width) {
 }  // namespace
 
 extern "C" int64_t b4r_rank_full_scratch_bytes(int32_t R, int32_t V, int32_t K) {
-  if (R <= 0 || V <= 0 || K < 0 || K > FK_MAX) return 0;
+  if (R <= 0 || V <= 0 || K < 0 || K > SEL_K_MAX) return 0;
   return (int64_t)R * row_bytes(V, K) + 64;   // + room for the 16-byte alignment of the regions
 }
 
@@ -599,7 +398,7 @@ extern "C" int b4r_rank_full_ex(const float* hidden, int32_t hidden_ld, const in
 }
 
 extern "C" int64_t b4r_item_neighbours_scratch_bytes(int32_t R, int32_t V, int32_t K, int32_t width) {
-  if (R <= 0 || V <= 0 || K < 0 || K > FK_MAX || width <= 0) return 0;
+  if (R <= 0 || V <= 0 || K < 0 || K > SEL_K_MAX || width <= 0) return 0;
   return neighbour_bytes(R, V, width) + b4r_rank_full_scratch_bytes(R, V, K);
 }
 
@@ -608,8 +407,8 @@ extern "C" int b4r_item_neighbours(const float* table, int32_t ld, int32_t width
                                    const int32_t* row_filter, int32_t K, int64_t* topk_ids, float* topk_scores, void* scratch,
                                    int64_t scratch_bytes, b4r_stream_t stream) {
   const char* what = "b4r_item_neighbours";
-  B4R_CHECK_ARG(R >= 0 && K >= 0 && K <= FK_MAX && first_item >= 0, B4R_E_SHAPE, "%s: bad shape (R = %d, K = %d in [0, %d], first_item = %d)",
-                what, R, K, FK_MAX, first_item);
+  B4R_CHECK_ARG(R >= 0 && K >= 0 && K <= SEL_K_MAX && first_item >= 0, B4R_E_SHAPE, "%s: bad shape (R = %d, K = %d in [0, %d], first_item = %d)",
+                what, R, K, SEL_K_MAX, first_item);
   // the sweep reads table row j at table + j * width: a padded table (ld > width) is not taken
   B4R_CHECK_ARG(width > 0 && width % 4 == 0 && width <= 4096 && ld == width && V > 0, B4R_E_SHAPE,
                 "%s: bad shape (width = %d: a multiple of 4 up to 4096, ld = %d: must equal width, V = %d)", what, width, ld, V);
@@ -628,8 +427,8 @@ extern "C" int b4r_item_neighbours(const float* table, int32_t ld, int32_t width
   char* rest = p + own;
   hipStream_t s = (hipStream_t)stream;
   const bool cosine = metric == B4R_SIM_COSINE;
-  if (cosine) hipLaunchKernelGGL(item_rnorm_kernel, dim3(b4r_cdiv(V, FT)), dim3(FT), 0, s, table, width, V, rnorm);
-  hipLaunchKernelGGL(item_query_kernel, dim3(b4r_cdiv((int64_t)R * width, FT)), dim3(FT), 0, s, table, width, V, first_item, query_ids, R,
+  if (cosine) hipLaunchKernelGGL(item_rnorm_kernel, dim3(b4r_cdiv(V, TILE_T)), dim3(TILE_T), 0, s, table, width, V, rnorm);
+  hipLaunchKernelGGL(item_query_kernel, dim3(b4r_cdiv((int64_t)R * width, TILE_T)), dim3(TILE_T), 0, s, table, width, V, first_item, query_ids, R,
                      cosine ? rnorm : nullptr, qhat, qrow);
   // the query excludes itself: query_ids is the [R, 1] exclude list
   return rank_full_impl(what, false, qhat, width, qrow, table, nullptr, width, V, first_item, R, query_ids, 1, nullptr, K, allow_bits,

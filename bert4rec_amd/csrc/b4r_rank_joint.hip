@@ -9,8 +9,8 @@
 // member's u < min_member_util); its aggregate a(p, j) is the fma chain over the members (additive), the minimum or the maximum.
 //
 // Launches per group of parties that fits the scratch:
-//   1. sweep   grid (tile of 16 row slots) x (chunk of JCH = 1024 ids): b4r_rank_full's tile and staging (table rows through LDS in
-//              k-blocks of JKB floats, once for all 16 slots; 2 ids x 16 slots of accumulators per thread).  A template on MP, the
+//   1. sweep   grid (tile of 16 row slots) x (chunk of 1024 ids): the tile of b4r_catalogue_tile.h, staged as in
+//              b4r_rank_full.hip (table rows through LDS in k-blocks of 16 floats, once for all 16 slots; 2 ids x 16 slots of accumulators per thread).  A template on MP, the
 //              smallest of {1, 2, 4, 8, 16} that holds the M members: a tile is 16 / MP parties of MP slots, so the reduction over a
 //              party's members runs over statically indexed registers of one thread.  The party's not-allowed bitmap is the OR of its
 //              members' (LDS atomicOr).  Each thread is left with 4 x 16 / MP aggregates; per party the chunk's best min(K, 1024) go
@@ -23,103 +23,9 @@
 #include <cmath>
 
 #include "b4r_common.h"
+#include "b4r_catalogue_tile.h"
 
 namespace {
-
-constexpr int JT = 256;          // threads per workgroup
-constexpr int JG = 16;           // row slots per sweep workgroup
-constexpr int JQ = 4;            // ids per thread per chunk
-constexpr int JIPT = 2;          // ids scored together per k-block (JQ / JIPT steps)
-constexpr int JCH = JT * JQ;     // ids per chunk
-constexpr int JKB = 16;          // k-block (floats of a table row staged at a time)
-constexpr int JK_MAX = 1024;     // largest K
-constexpr uint32_t NOT_ALLOWED = 0xFFFFFFFFu;   // raw-bits marker of an id that is not ranked (a NaN pattern: out of contract)
-
-static_assert(JT == JG * 16, "digit search: 16 threads per party; one thread per staged hidden value");
-static_assert(JCH <= 65536, "the local id takes the low 16 bits of the sweep key");
-
-// ---- b4r_rank_full's select helpers (a copy: that file's kernels keep their code) ------------------------------------------------
-// order-preserving image of a score for an ascending unsigned compare; -0.0 counts as +0.0 (they compare equal)
-__device__ __forceinline__ uint32_t score_key_bits(uint32_t u) {
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ uint32_t score_key(float s) { return score_key_bits(__builtin_bit_cast(uint32_t, s)); }
-
-// state of one party's radix select over W-bit unique keys: `hi` top bits are resolved (= prefix); `rem` ids are still to be taken
-// from those whose top bits equal the prefix; done: every key >= thr is taken (take = 0: none)
-struct Sel {
-  uint64_t prefix, thr;
-  int hi, rem, done, take;
-};
-
-__device__ __forceinline__ void sel_init(Sel& s, int n, int need, uint32_t kmin, uint32_t kmax) {
-  s.take = need > 0;
-  s.rem = need;
-  s.thr = 0;
-  if (need <= 0 || need >= n) {
-    s.done = 1; s.hi = 0; s.prefix = 0;   // none, or every allowed id (thr = 0)
-    return;
-  }
-  const uint32_t diff = kmin ^ kmax;
-  s.hi = diff ? __clz(diff) : 32;
-  s.prefix = (uint64_t)kmax >> (32 - s.hi);
-  s.done = 0;
-}
-
-__device__ __forceinline__ bool sel_match(const Sel& s, uint64_t key, int W) {
-  return s.hi == 0 || (key >> (W - s.hi)) == s.prefix;
-}
-
-__device__ __forceinline__ int sel_nb(const Sel& s, int W) { return min(8, W - s.hi); }
-
-// the 16 threads qq = 0..15 of a party: part[qq] = count of digits 255-16qq .. 240-16qq (descending)
-__device__ __forceinline__ void sel_part(const uint32_t* hist, uint32_t* part, int qq) {
-  uint32_t c = 0;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) c += hist[255 - 16 * qq - i];
-  part[qq] = c;
-}
-
-// the thread whose 16 digits hold the rem-th key from the top writes the advanced state `s` (a copy taken before the barrier
-// that precedes this call) to `out`; the other threads of the party leave it alone
-__device__ __forceinline__ void sel_advance(Sel s, Sel& out, const uint32_t* hist, const uint32_t* part, int qq, int W) {
-  uint32_t above = 0;
-  for (int i = 0; i < qq; ++i) above += part[i];
-  const uint32_t rem = (uint32_t)s.rem;
-  if (!(above < rem && above + part[qq] >= rem)) return;
-  const int nb = sel_nb(s, W);
-  for (int i = 0; i < 16; ++i) {
-    const int d = 255 - 16 * qq - i;
-    const uint32_t c = hist[d];
-    if (above + c >= rem) {
-      const uint32_t left = rem - above;
-      s.prefix = (s.prefix << nb) | (uint64_t)d;
-      s.hi += nb;
-      s.rem = (int)left;
-      if (c == left || s.hi >= W) {
-        s.done = 1;
-        s.thr = s.hi >= W ? s.prefix : (s.prefix << (W - s.hi));
-      }
-      out = s;
-      return;
-    }
-    above += c;
-  }
-}
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-  return v;
-}
 
 // b4r_score_dist's scalar t: the k-ordered fp32 fma chain (the contract), + bias (NULL: + 0.0f), one multiply by scale (NULL:
 // none), one by inv_t
@@ -132,7 +38,7 @@ __device__ __forceinline__ float joint_row_t(const float* h, const float* e, con
   return s * inv_t;
 }
 
-// ---- 1. sweep: (tile of JG row slots = JG / MP parties) x (chunk of JCH ids) ---------------------------------------------------
+// ---- 1. sweep: (tile of TILE_G row slots = TILE_G / MP parties) x (chunk of TILE_CH ids) ---------------------------------------------------
 struct JointArgs {
   const float* hidden; const int64_t* hidden_row; const float* table; const float* bias; const float* scale;
   const int64_t* exclude;
@@ -147,7 +53,7 @@ struct JointArgs {
 
 // the reduction over the MP slots of party pp for one id: false when a present member vetoes the id
 template <int MP, int MODE>
-__device__ __forceinline__ bool joint_reduce(const float (&acc)[JG], int pp, float b, float sc, bool scaled, float inv_t, bool has_lse,
+__device__ __forceinline__ bool joint_reduce(const float (&acc)[TILE_G], int pp, float b, float sc, bool scaled, float inv_t, bool has_lse,
                                              const double* s_lse, const float* s_w, uint32_t present, float min_util, float& out) {
   float agg = MODE == B4R_JOINT_ADDITIVE ? 0.f : (MODE == B4R_JOINT_LEAST_MISERY ? INFINITY : -INFINITY);
   bool veto = false;
@@ -170,31 +76,31 @@ __device__ __forceinline__ bool joint_reduce(const float (&acc)[JG], int pp, flo
 }
 
 template <int MP>
-__global__ __launch_bounds__(JT, 2) void joint_sweep_kernel(JointArgs a) {
-  constexpr int NPT = JG / MP;   // parties per tile
-  __shared__ float tile[JIPT * JT * (JKB + 1)];
-  __shared__ __attribute__((aligned(16))) float hsh[JG * JKB];
-  __shared__ uint32_t bits[NPT][JCH / 32];
+__global__ __launch_bounds__(TILE_T, 2) void joint_sweep_kernel(JointArgs a) {
+  constexpr int NPT = TILE_G / MP;   // parties per tile
+  __shared__ float tile[TILE_IPT * TILE_T * (TILE_KB + 1)];
+  __shared__ __attribute__((aligned(16))) float hsh[TILE_G * TILE_KB];
+  __shared__ uint32_t bits[NPT][TILE_CH / 32];
   __shared__ uint32_t hist[NPT][256];
   __shared__ uint32_t part[NPT][16];
   __shared__ Sel st[NPT];
   __shared__ uint32_t s_cnt[NPT], s_kmin[NPT], s_kmax[NPT], s_out[NPT];
-  __shared__ int64_t s_hoff[JG], s_row[JG];
-  __shared__ double s_lse[JG];
-  __shared__ float s_w[JG];
+  __shared__ int64_t s_hoff[TILE_G], s_row[TILE_G];
+  __shared__ double s_lse[TILE_G];
+  __shared__ float s_w[TILE_G];
   __shared__ uint32_t s_present, s_bad, s_live;
   __shared__ int s_alldone;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int lp0 = blockIdx.x * NPT;   // first party of the tile, within the group
   const int chunk = blockIdx.y;
-  const int64_t c0 = (int64_t)chunk * JCH;
+  const int64_t c0 = (int64_t)chunk * TILE_CH;
   const int H = a.H;
 
   if (tid == 0) { s_present = 0u; s_bad = 0u; }
-  for (int i = tid; i < NPT * (JCH / 32); i += JT) (&bits[0][0])[i] = 0u;
+  for (int i = tid; i < NPT * (TILE_CH / 32); i += TILE_T) (&bits[0][0])[i] = 0u;
   __syncthreads();
-  if (tid < JG) {
+  if (tid < TILE_G) {
     const int pp = tid / MP, m = tid - pp * MP;
     const int lp = lp0 + pp;
     int64_t r = -1;
@@ -221,8 +127,8 @@ __global__ __launch_bounds__(JT, 2) void joint_sweep_kernel(JointArgs a) {
   // bit set = not ranked for the party: the OR over its members of the complement of the member's filter words of this chunk ...
   if (a.allow) {
     const int64_t W = ((int64_t)a.V + 31) >> 5;
-    for (int i = tid; i < JG * (JCH / 32); i += JT) {
-      const int g = i / (JCH / 32), w = i - g * (JCH / 32);
+    for (int i = tid; i < TILE_G * (TILE_CH / 32); i += TILE_T) {
+      const int g = i / (TILE_CH / 32), w = i - g * (TILE_CH / 32);
       const int64_t r = s_row[g];
       const int64_t wi = (c0 >> 5) + w;
       if (r < 0 || wi >= W) continue;
@@ -235,12 +141,12 @@ __global__ __launch_bounds__(JT, 2) void joint_sweep_kernel(JointArgs a) {
   }
   // ... and of the member's excluded ids
   if (a.E > 0) {
-    for (int f = tid; f < JG * a.E; f += JT) {
+    for (int f = tid; f < TILE_G * a.E; f += TILE_T) {
       const int g = f / a.E, e = f - g * a.E;
       const int64_t r = s_row[g];
       if (r < 0) continue;
       const int64_t id = a.exclude[r * (int64_t)a.E + e];
-      if (id >= c0 && id < c0 + JCH) {
+      if (id >= c0 && id < c0 + TILE_CH) {
         const int l = (int)(id - c0);
         atomicOr(&bits[g / MP][l >> 5], 1u << (l & 31));
       }
@@ -257,53 +163,53 @@ __global__ __launch_bounds__(JT, 2) void joint_sweep_kernel(JointArgs a) {
   }
 
   // ---- aggregates: raw fp32 bits in registers, NOT_ALLOWED where the id is not ranked for the party -----------------------------
-  uint32_t raw[JQ][NPT];
+  uint32_t raw[TILE_Q][NPT];
 #pragma unroll
-  for (int ps = 0; ps < JQ / JIPT; ++ps) {
-    float acc[JIPT][JG];
+  for (int ps = 0; ps < TILE_Q / TILE_IPT; ++ps) {
+    float acc[TILE_IPT][TILE_G];
 #pragma unroll
-    for (int ii = 0; ii < JIPT; ++ii)
+    for (int ii = 0; ii < TILE_IPT; ++ii)
 #pragma unroll
-      for (int g = 0; g < JG; ++g) acc[ii][g] = 0.f;
-    const int64_t cj0 = c0 + (int64_t)ps * JIPT * JT;   // first id of this step
-    for (int kb = 0; kb < H; kb += JKB) {
-      const int kn = min(JKB, H - kb);   // a multiple of 4 (H % 4 == 0)
+      for (int g = 0; g < TILE_G; ++g) acc[ii][g] = 0.f;
+    const int64_t cj0 = c0 + (int64_t)ps * TILE_IPT * TILE_T;   // first id of this step
+    for (int kb = 0; kb < H; kb += TILE_KB) {
+      const int kn = min(TILE_KB, H - kb);   // a multiple of 4 (H % 4 == 0)
       const int k4 = kn >> 2;
       __syncthreads();   // the previous block is consumed (and, the first time, the bitmap and s_live are complete)
-      for (int f = tid; f < JIPT * JT * k4; f += JT) {
+      for (int f = tid; f < TILE_IPT * TILE_T * k4; f += TILE_T) {
         const int i = f / k4, c4 = f - i * k4;
         const int64_t j = cj0 + i;
         const f32x4 v = j < a.V ? *reinterpret_cast<const f32x4*>(a.table + j * H + kb + 4 * c4) : (f32x4){0.f, 0.f, 0.f, 0.f};
-        float* dst = tile + i * (JKB + 1) + 4 * c4;
+        float* dst = tile + i * (TILE_KB + 1) + 4 * c4;
         dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3];
       }
       {
-        const int g = tid / JKB, k = tid - g * JKB;   // JG * JKB == JT
+        const int g = tid / TILE_KB, k = tid - g * TILE_KB;   // TILE_G * TILE_KB == TILE_T
         hsh[tid] = (k < kn && s_hoff[g] >= 0) ? a.hidden[s_hoff[g] + kb + k] : 0.f;
       }
       __syncthreads();
       for (int k = 0; k < kn; k += 4) {
-        float e[JIPT][4];
+        float e[TILE_IPT][4];
 #pragma unroll
-        for (int ii = 0; ii < JIPT; ++ii)
+        for (int ii = 0; ii < TILE_IPT; ++ii)
 #pragma unroll
-          for (int u = 0; u < 4; ++u) e[ii][u] = tile[(ii * JT + tid) * (JKB + 1) + k + u];
+          for (int u = 0; u < 4; ++u) e[ii][u] = tile[(ii * TILE_T + tid) * (TILE_KB + 1) + k + u];
 #pragma unroll
-        for (int g = 0; g < JG; ++g) {
-          const f32x4 h = *reinterpret_cast<const f32x4*>(hsh + g * JKB + k);
+        for (int g = 0; g < TILE_G; ++g) {
+          const f32x4 h = *reinterpret_cast<const f32x4*>(hsh + g * TILE_KB + k);
 #pragma unroll
           for (int u = 0; u < 4; ++u)
 #pragma unroll
-            for (int ii = 0; ii < JIPT; ++ii) acc[ii][g] = __builtin_fmaf(h[u], e[ii][u], acc[ii][g]);
+            for (int ii = 0; ii < TILE_IPT; ++ii) acc[ii][g] = __builtin_fmaf(h[u], e[ii][u], acc[ii][g]);
         }
       }
     }
     const uint32_t present = s_present, live = s_live;
     const bool has_lse = a.row_lse != nullptr, scaled = a.scale != nullptr;
 #pragma unroll
-    for (int ii = 0; ii < JIPT; ++ii) {
-      const int q = ps * JIPT + ii;
-      const int l = q * JT + tid;
+    for (int ii = 0; ii < TILE_IPT; ++ii) {
+      const int q = ps * TILE_IPT + ii;
+      const int l = q * TILE_T + tid;
       const int64_t j = c0 + l;
       const bool inb = j >= a.lo && j < a.V;
       const float b = (a.bias && inb) ? a.bias[j] : 0.f;
@@ -329,7 +235,7 @@ __global__ __launch_bounds__(JT, 2) void joint_sweep_kernel(JointArgs a) {
   for (int pp = 0; pp < NPT; ++pp) {
     uint32_t cnt = 0, kmin = 0xFFFFFFFFu, kmax = 0u;
 #pragma unroll
-    for (int q = 0; q < JQ; ++q) {
+    for (int q = 0; q < TILE_Q; ++q) {
       if (raw[q][pp] == NOT_ALLOWED) continue;
       const uint32_t k = score_key_bits(raw[q][pp]);
       cnt += 1;
@@ -346,7 +252,7 @@ __global__ __launch_bounds__(JT, 2) void joint_sweep_kernel(JointArgs a) {
   }
   if (tid == 0) s_alldone = 0;
 
-  // ---- radix select over (score key << 16 | JCH-1 - local id) ----------------------------------------------------------------
+  // ---- radix select over (score key << 16 | TILE_CH-1 - local id) ----------------------------------------------------------------
   for (int pass = 0; pass < 6; ++pass) {
     __syncthreads();
     if (tid == 0) {
@@ -354,7 +260,7 @@ __global__ __launch_bounds__(JT, 2) void joint_sweep_kernel(JointArgs a) {
       for (int pp = 0; pp < NPT; ++pp) all &= st[pp].done;
       s_alldone = all;
     }
-    for (int i = tid; i < NPT * 256; i += JT) (&hist[0][0])[i] = 0u;
+    for (int i = tid; i < NPT * 256; i += TILE_T) (&hist[0][0])[i] = 0u;
     __syncthreads();
     if (s_alldone) break;
 #pragma unroll
@@ -363,9 +269,9 @@ __global__ __launch_bounds__(JT, 2) void joint_sweep_kernel(JointArgs a) {
       if (s.done) continue;
       const int nb = sel_nb(s, 48), sh = 48 - s.hi - nb;
 #pragma unroll
-      for (int q = 0; q < JQ; ++q) {
+      for (int q = 0; q < TILE_Q; ++q) {
         if (raw[q][pp] == NOT_ALLOWED) continue;
-        const uint64_t key = ((uint64_t)score_key_bits(raw[q][pp]) << 16) | (uint64_t)(JCH - 1 - (q * JT + tid));
+        const uint64_t key = ((uint64_t)score_key_bits(raw[q][pp]) << 16) | (uint64_t)(TILE_CH - 1 - (q * TILE_T + tid));
         if (sel_match(s, key, 48)) atomicAdd(&hist[pp][(key >> sh) & ((1u << nb) - 1u)], 1u);
       }
     }
@@ -386,10 +292,10 @@ __global__ __launch_bounds__(JT, 2) void joint_sweep_kernel(JointArgs a) {
     if (!s.take || !s.done) continue;
     const int64_t base = ((int64_t)(lp0 + pp) * a.nch + chunk) * a.cap;
 #pragma unroll
-    for (int q = 0; q < JQ; ++q) {
+    for (int q = 0; q < TILE_Q; ++q) {
       if (raw[q][pp] == NOT_ALLOWED) continue;
-      const int l = q * JT + tid;
-      const uint64_t key = ((uint64_t)score_key_bits(raw[q][pp]) << 16) | (uint64_t)(JCH - 1 - l);
+      const int l = q * TILE_T + tid;
+      const uint64_t key = ((uint64_t)score_key_bits(raw[q][pp]) << 16) | (uint64_t)(TILE_CH - 1 - l);
       if (key < s.thr) continue;
       const uint32_t slot = atomicAdd(&s_out[pp], 1u);
       if (slot < (uint32_t)a.cap) {
@@ -414,84 +320,23 @@ struct JointMergeArgs {
   int nch, cap, K;
 };
 
-__global__ __launch_bounds__(JT) void joint_merge_kernel(JointMergeArgs a) {
+__global__ __launch_bounds__(TILE_T) void joint_merge_kernel(JointMergeArgs a) {
   __shared__ uint32_t hist[256];
   __shared__ uint32_t part[16];
   __shared__ Sel st;
-  __shared__ uint32_t s_n, s_all, s_kmin, s_kmax, s_out;
-  __shared__ uint64_t sel_key[JK_MAX];
-  __shared__ float sel_score[JK_MAX];
-  const int tid = threadIdx.x, lane = tid & 63;
+  __shared__ uint32_t s_n, s_kmin, s_kmax, s_out, s_all;
+  __shared__ uint64_t sel_key[SEL_K_MAX];
+  __shared__ float sel_val[SEL_K_MAX];
+  const MergeSel L{hist, part, st, s_n, s_kmin, s_kmax, s_out, &s_all, sel_key, sel_val};
   const int lp = blockIdx.x;
   const int64_t p = a.p0 + lp;
-  const int32_t* cnt = a.c_cnt + (int64_t)lp * a.nch;
-  const int64_t base = (int64_t)lp * a.nch * a.cap;
-  const int64_t total_slots = (int64_t)a.nch * a.cap;
-
-  if (tid == 0) { s_n = 0; s_all = 0; s_kmin = 0xFFFFFFFFu; s_kmax = 0u; s_out = 0; }
-  __syncthreads();
-  {
-    uint32_t n = 0, all = 0, kmin = 0xFFFFFFFFu, kmax = 0u;
-    for (int c = tid; c < a.nch; c += JT) { n += (uint32_t)cnt[c]; all += (uint32_t)a.c_n[(int64_t)lp * a.nch + c]; }
-    for (int64_t e = tid; e < total_slots; e += JT) {
-      const int c = (int)(e / a.cap), i = (int)(e - (int64_t)c * a.cap);
-      if (i >= cnt[c]) continue;
-      const uint32_t k = score_key(a.c_score[base + e]);
-      kmin = min(kmin, k); kmax = max(kmax, k);
-    }
-    n = wave_sum_u32(n); all = wave_sum_u32(all);
-    kmin = wave_min_u32(kmin); kmax = wave_max_u32(kmax);
-    if (lane == 0) { atomicAdd(&s_n, n); atomicAdd(&s_all, all); atomicMin(&s_kmin, kmin); atomicMax(&s_kmax, kmax); }
-  }
-  __syncthreads();
-  const int n = (int)s_n;
-  const int need = min(a.K, n);
-  if (tid == 0) sel_init(st, n, need, s_kmin, s_kmax);
-  for (int pass = 0; pass < 8; ++pass) {
-    __syncthreads();
-    if (st.done) break;
-    for (int i = tid; i < 256; i += JT) hist[i] = 0u;
-    __syncthreads();
-    const Sel s = st;
-    const int nb = sel_nb(s, 64), sh = 64 - s.hi - nb;
-    for (int64_t e = tid; e < total_slots; e += JT) {
-      const int c = (int)(e / a.cap), i = (int)(e - (int64_t)c * a.cap);
-      if (i >= cnt[c]) continue;
-      const uint64_t key = ((uint64_t)score_key(a.c_score[base + e]) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)a.c_id[base + e]);
-      if (sel_match(s, key, 64)) atomicAdd(&hist[(key >> sh) & ((1u << nb) - 1u)], 1u);
-    }
-    __syncthreads();
-    if (tid < 16) sel_part(hist, part, tid);
-    __syncthreads();
-    if (tid < 16) sel_advance(s, st, hist, part, tid, 64);
-  }
-  __syncthreads();
-  if (st.take && st.done) {
-    const uint64_t thr = st.thr;
-    for (int64_t e = tid; e < total_slots; e += JT) {
-      const int c = (int)(e / a.cap), i = (int)(e - (int64_t)c * a.cap);
-      if (i >= cnt[c]) continue;
-      const float sc = a.c_score[base + e];
-      const uint64_t key = ((uint64_t)score_key(sc) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)a.c_id[base + e]);
-      if (key < thr) continue;
-      const uint32_t slot = atomicAdd(&s_out, 1u);
-      if (slot < (uint32_t)JK_MAX) { sel_key[slot] = key; sel_score[slot] = sc; }
-    }
-  }
-  __syncthreads();
-  const int m = min((int)s_out, min(a.K, JK_MAX));
-  for (int i = tid; i < m; i += JT) {
-    const uint64_t ki = sel_key[i];
-    int pos = 0;
-    for (int j = 0; j < m; ++j) pos += sel_key[j] > ki ? 1 : 0;   // keys are unique: a permutation of 0 .. m-1
-    if (a.ids) a.ids[(int64_t)lp * a.K + pos] = (int64_t)(0xFFFFFFFFu - (uint32_t)(ki & 0xFFFFFFFFu));
-    if (a.topk_scores) a.topk_scores[p * a.K + pos] = sel_score[i];
-  }
-  for (int q = m + tid; q < a.K; q += JT) {
-    if (a.ids) a.ids[(int64_t)lp * a.K + q] = -1;
-    if (a.topk_scores) a.topk_scores[p * a.K + q] = -INFINITY;
-  }
-  if (tid == 0 && a.party_n) a.party_n[p] = (int32_t)s_all;
+  const int64_t row = (int64_t)lp * a.nch;
+  const int m = merge_select<TILE_T>(L, a.c_score, a.c_id, a.c_cnt, a.c_n, row, a.nch, a.cap, a.K);
+  merge_order<TILE_T>(L, m, a.K, [&](int pos, int64_t id, float score) {
+    if (a.ids) a.ids[(int64_t)lp * a.K + pos] = id;
+    if (a.topk_scores) a.topk_scores[p * a.K + pos] = score;
+  });
+  if (threadIdx.x == 0 && a.party_n) a.party_n[p] = (int32_t)s_all;
 }
 
 // ---- 3. member utilities: one thread per (party, place, member) ----------------------------------------------------------------
@@ -505,8 +350,8 @@ struct JointUtilArgs {
   int hidden_ld, H, V, lo, R, M, n, K;
 };
 
-__global__ __launch_bounds__(JT) void joint_util_kernel(JointUtilArgs a) {
-  const int64_t i = (int64_t)blockIdx.x * JT + threadIdx.x;
+__global__ __launch_bounds__(TILE_T) void joint_util_kernel(JointUtilArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * TILE_T + threadIdx.x;
   const int64_t per = (int64_t)a.K * a.M;
   if (i >= (int64_t)a.n * per) return;
   const int lp = (int)(i / per);
@@ -526,10 +371,8 @@ __global__ __launch_bounds__(JT) void joint_util_kernel(JointUtilArgs a) {
   a.member_util[p * per + rest] = out;
 }
 
-int64_t joint_chunks_of(int32_t V) { return ((int64_t)V + JCH - 1) / JCH; }
-int64_t joint_cap_of(int32_t K) { return std::min<int64_t>(K, JCH); }
 // scores, ids of the chunks' candidates | their counts, the allowed counts | the ordered ids of the party (what the util launch reads)
-int64_t joint_party_bytes(int32_t V, int32_t K) { return joint_chunks_of(V) * (joint_cap_of(K) * 8 + 8) + (int64_t)K * 8; }
+int64_t joint_party_bytes(int32_t V, int32_t K) { return tile_chunks_of(V) * (tile_cap_of(K) * 8 + 8) + (int64_t)K * 8; }
 int joint_mp_of(int32_t M) { return M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16; }
 
 using JointSweepFn = void (*)(JointArgs);
@@ -546,7 +389,7 @@ JointSweepFn joint_sweep_instance(int mp) {
 }  // namespace
 
 extern "C" int64_t b4r_rank_joint_scratch_bytes(int32_t NP, int32_t M, int32_t V, int32_t K) {
-  if (NP <= 0 || M < 1 || M > JG || V <= 0 || K < 0 || K > JK_MAX) return 0;
+  if (NP <= 0 || M < 1 || M > TILE_G || V <= 0 || K < 0 || K > SEL_K_MAX) return 0;
   return (int64_t)NP * joint_party_bytes(V, K) + 64;   // + room for the 16-byte alignment of the regions
 }
 
@@ -558,9 +401,9 @@ extern "C" int b4r_rank_joint(const float* hidden, int32_t hidden_ld, const int6
                               float* topk_scores, int32_t* party_n, float* member_util, void* scratch, int64_t scratch_bytes,
                               b4r_stream_t stream) {
   const char* what = "b4r_rank_joint";
-  B4R_CHECK_ARG(R >= 0 && NP >= 0 && K >= 0 && K <= JK_MAX && E >= 0 && first_item >= 0, B4R_E_SHAPE,
-                "%s: bad shape (R = %d, NP = %d, K = %d in [0, %d], E = %d, first_item = %d)", what, R, NP, K, JK_MAX, E, first_item);
-  B4R_CHECK_ARG(M >= 1 && M <= JG, B4R_E_SHAPE, "%s: M = %d members per party must lie in [1, %d]", what, M, JG);
+  B4R_CHECK_ARG(R >= 0 && NP >= 0 && K >= 0 && K <= SEL_K_MAX && E >= 0 && first_item >= 0, B4R_E_SHAPE,
+                "%s: bad shape (R = %d, NP = %d, K = %d in [0, %d], E = %d, first_item = %d)", what, R, NP, K, SEL_K_MAX, E, first_item);
+  B4R_CHECK_ARG(M >= 1 && M <= TILE_G, B4R_E_SHAPE, "%s: M = %d members per party must lie in [1, %d]", what, M, TILE_G);
   B4R_CHECK_ARG(H > 0 && H % 4 == 0 && H <= 4096 && hidden_ld >= H && V > 0, B4R_E_SHAPE,
                 "%s: bad shape (H = %d, hidden_ld = %d, V = %d)", what, H, hidden_ld, V);
   B4R_CHECK_ARG(!allow_bits || n_filters > 0, B4R_E_SHAPE, "%s: allow_bits with n_filters = %d", what, n_filters);
@@ -573,22 +416,17 @@ extern "C" int b4r_rank_joint(const float* hidden, int32_t hidden_ld, const int6
   B4R_CHECK_ARG(hidden && table && party_rows, B4R_E_BADARG, "%s: null argument", what);
   B4R_CHECK_ARG(E == 0 || exclude, B4R_E_BADARG, "%s: exclude is NULL with E = %d", what, E);
   B4R_CHECK_ARG(b4r_aligned16(table), B4R_E_ALIGN, "%s: the table must be 16-byte aligned", what);
-  const int nch = (int)joint_chunks_of(V);
+  const int nch = (int)tile_chunks_of(V);
   B4R_CHECK_ARG(nch <= 65535, B4R_E_SHAPE, "%s: V = %d is too large", what, V);
   const int mp = joint_mp_of(M);
-  const int npt = JG / mp;   // parties per tile
+  const int npt = TILE_G / mp;   // parties per tile
   const int64_t per_party = joint_party_bytes(V, K);
-  const int64_t usable = scratch ? scratch_bytes - (int64_t)((16 - ((uintptr_t)scratch & 15)) & 15) : 0;
-  int64_t group = usable > 0 ? usable / per_party : 0;
-  group = std::min<int64_t>(group, NP);
-  if (group < NP) group = group / npt * npt;   // whole tiles
+  const int64_t group = tile_group_of(scratch, scratch_bytes, per_party, NP, npt);   // whole tiles
   B4R_CHECK_ARG(group >= std::min<int64_t>(NP, npt), B4R_E_NOMEM,
                 "%s: scratch of %lld bytes is too small: %lld bytes per party, %d parties at least (b4r_rank_joint_scratch_bytes)", what,
                 (long long)scratch_bytes, (long long)per_party, std::min<int32_t>(NP, npt));
-  group = std::min<int64_t>(group, 65535LL * JG);   // whole tiles still; keeps every grid of a group within 2^31 workgroups
-  const int cap = (int)joint_cap_of(K);
-  char* p = reinterpret_cast<char*>(((uintptr_t)scratch + 15) & ~(uintptr_t)15);
-  int64_t* s_ids = reinterpret_cast<int64_t*>(p);
+  const int cap = (int)tile_cap_of(K);
+  int64_t* s_ids = reinterpret_cast<int64_t*>(tile_scratch_base(scratch));
   float* c_score = reinterpret_cast<float*>(s_ids + group * K);
   int32_t* c_id = reinterpret_cast<int32_t*>(c_score + group * nch * cap);
   int32_t* c_cnt = c_id + group * nch * cap;
@@ -600,14 +438,14 @@ extern "C" int b4r_rank_joint(const float* hidden, int32_t hidden_ld, const int6
     JointArgs sa{hidden, hidden_row, table, bias, item_scale, exclude, allow_bits, row_filter, row_lse, party_rows, member_weight,
                  c_score, c_id, c_cnt, c_n, p0, inv_temperature, min_member_util, hidden_ld, H, V, first_item, E, R, M, mode, n, nch, cap,
                  n_filters};
-    hipLaunchKernelGGL(sweep, dim3(b4r_cdiv(n, npt), nch), dim3(JT), 0, s, sa);
+    hipLaunchKernelGGL(sweep, dim3(b4r_cdiv(n, npt), nch), dim3(TILE_T), 0, s, sa);
     int64_t* ids = topk_ids ? topk_ids + p0 * K : (member_util ? s_ids : nullptr);
     JointMergeArgs ma{c_score, c_id, c_cnt, c_n, ids, topk_scores, party_n, p0, nch, cap, K};
-    hipLaunchKernelGGL(joint_merge_kernel, dim3(n), dim3(JT), 0, s, ma);
+    hipLaunchKernelGGL(joint_merge_kernel, dim3(n), dim3(TILE_T), 0, s, ma);
     if (member_util) {
       JointUtilArgs ua{hidden, hidden_row, table, bias, item_scale, row_lse, party_rows, ids, member_util, p0, inv_temperature,
                        hidden_ld, H, V, first_item, R, M, n, K};
-      hipLaunchKernelGGL(joint_util_kernel, dim3(b4r_cdiv((int64_t)n * K * M, JT)), dim3(JT), 0, s, ua);
+      hipLaunchKernelGGL(joint_util_kernel, dim3(b4r_cdiv((int64_t)n * K * M, TILE_T)), dim3(TILE_T), 0, s, ua);
     }
   }
   B4R_CHECK_LAUNCH(what);

@@ -11,7 +11,7 @@
 // (-0.0 as +0.0, ties to the lower id), with the unperturbed score of each.
 //
 // Two launches per group of rows that fits the scratch:
-//   1. sweep   grid (group of SG = 16 rows) x (chunk of SCH = 1024 ids), staged as b4r_rank_full's sweep stages its table rows.  The
+//   1. sweep   grid (group of 16 rows) x (chunk of 1024 ids): the tile of b4r_catalogue_tile.h, staged and selected as in b4r_rank_full.hip.  The
 //              noise is added to the 4 ids x 16 rows of scores a thread holds in registers (skipped where the id is not allowed);
 //              the chunk's best min(K, 1024) keys are chosen by the radix select on (key bits << 16 | 1023 - local id) and go to
 //              scratch as (key, id) pairs in any order.
@@ -23,37 +23,9 @@
 #include <cmath>
 
 #include "b4r_common.h"
+#include "b4r_catalogue_tile.h"
 
 namespace {
-
-constexpr int ST = 256;          // threads per workgroup
-constexpr int SG = 16;           // rows per sweep workgroup
-constexpr int SQ = 4;            // ids per thread per chunk
-constexpr int SIPT = 2;          // ids scored together per k-block (SQ / SIPT steps)
-constexpr int SCH = ST * SQ;     // ids per chunk
-constexpr int SKB = 16;          // k-block (floats of a table row staged at a time)
-constexpr int SK_MAX = 1024;     // largest K, largest pool
-constexpr uint32_t NOT_ALLOWED = 0xFFFFFFFFu;   // raw-bits marker of an id that is not drawn (a NaN pattern: out of contract)
-
-static_assert(ST == SG * 16, "digit search: 16 threads per row");
-static_assert(SG * SKB == ST, "one thread per staged hidden value");
-static_assert(SCH <= 65536, "the local id takes the low 16 bits of the sweep key");
-
-// ---- the select helpers of b4r_rank_full.hip, verbatim ----------------------------------------------------------------------------
-// order-preserving image of a key for an ascending unsigned compare; -0.0 counts as +0.0 (they compare equal)
-__device__ __forceinline__ uint32_t score_key_bits(uint32_t u) {
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ uint32_t score_key(float s) { return score_key_bits(__builtin_bit_cast(uint32_t, s)); }
-
-// bias NULL: + 0.0f; scale (NULL: none) multiplies the rounded chain once
-__device__ __forceinline__ float row_score(const float* h, const float* e, const float* bias, const float* scale, int64_t j, int H) {
-  float acc = 0.f;
-  for (int k = 0; k < H; ++k) acc = __builtin_fmaf(h[k], e[k], acc);   // k-ordered fp32 fma chain (the contract)
-  const float s = acc + (bias ? bias[j] : 0.f);
-  return scale ? s * scale[j] : s;
-}
 
 // key = fl32(fl32(s * inv_t) + g): two rounded fp32 operations (never one fma)
 __device__ __forceinline__ float sample_key(float s, float inv_t, float g) {
@@ -62,89 +34,13 @@ __device__ __forceinline__ float sample_key(float s, float inv_t, float g) {
   return t + g;
 }
 
-// state of one row's radix select over W-bit unique keys: `hi` top bits are resolved (= prefix); `rem` ids are still to be taken
-// from those whose top bits equal the prefix; done: every key >= thr is taken (take = 0: none)
-struct Sel {
-  uint64_t prefix, thr;
-  int hi, rem, done, take;
-};
-
-// init: n allowed keys, `need` to take; kmin / kmax over the allowed key images (the top 32 bits of every W-bit key)
-__device__ __forceinline__ void sel_init(Sel& s, int n, int need, uint32_t kmin, uint32_t kmax) {
-  s.take = need > 0;
-  s.rem = need;
-  s.thr = 0;
-  if (need <= 0 || need >= n) {
-    s.done = 1; s.hi = 0; s.prefix = 0;   // none, or every allowed id (thr = 0)
-    return;
-  }
-  const uint32_t diff = kmin ^ kmax;
-  s.hi = diff ? __clz(diff) : 32;
-  s.prefix = (uint64_t)kmax >> (32 - s.hi);
-  s.done = 0;
-}
-
-__device__ __forceinline__ bool sel_match(const Sel& s, uint64_t key, int W) {
-  return s.hi == 0 || (key >> (W - s.hi)) == s.prefix;
-}
-
-__device__ __forceinline__ int sel_nb(const Sel& s, int W) { return min(8, W - s.hi); }
-
-// the 16 threads qq = 0..15 of a row: part[qq] = count of digits 255-16qq .. 240-16qq (descending)
-__device__ __forceinline__ void sel_part(const uint32_t* hist, uint32_t* part, int qq) {
-  uint32_t c = 0;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) c += hist[255 - 16 * qq - i];
-  part[qq] = c;
-}
-
-// the thread whose 16 digits hold the rem-th key from the top writes the advanced state `s` (a copy taken before the barrier
-// that precedes this call) to `out`; the other threads of the row leave it alone
-__device__ __forceinline__ void sel_advance(Sel s, Sel& out, const uint32_t* hist, const uint32_t* part, int qq, int W) {
-  uint32_t above = 0;
-  for (int i = 0; i < qq; ++i) above += part[i];
-  const uint32_t rem = (uint32_t)s.rem;
-  if (!(above < rem && above + part[qq] >= rem)) return;
-  const int nb = sel_nb(s, W);
-  for (int i = 0; i < 16; ++i) {
-    const int d = 255 - 16 * qq - i;
-    const uint32_t c = hist[d];
-    if (above + c >= rem) {
-      const uint32_t left = rem - above;
-      s.prefix = (s.prefix << nb) | (uint64_t)d;
-      s.hi += nb;
-      s.rem = (int)left;
-      if (c == left || s.hi >= W) {
-        s.done = 1;
-        s.thr = s.hi >= W ? s.prefix : (s.prefix << (W - s.hi));
-      }
-      out = s;
-      return;
-    }
-    above += c;
-  }
-}
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-  return v;
-}
-
 // ---- the noise alone (test surface): one thread per word, grid-stride ---------------------------------------------------------------
-__global__ __launch_bounds__(ST) void gumbel_noise_kernel(const uint32_t* __restrict__ words, int64_t n, float* __restrict__ out) {
-  const int64_t step = (int64_t)gridDim.x * ST;
-  for (int64_t i = (int64_t)blockIdx.x * ST + threadIdx.x; i < n; i += step) out[i] = b4r_gumbel23(words[i]);
+__global__ __launch_bounds__(TILE_T) void gumbel_noise_kernel(const uint32_t* __restrict__ words, int64_t n, float* __restrict__ out) {
+  const int64_t step = (int64_t)gridDim.x * TILE_T;
+  for (int64_t i = (int64_t)blockIdx.x * TILE_T + threadIdx.x; i < n; i += step) out[i] = b4r_gumbel23(words[i]);
 }
 
-// ---- 1. sweep: (group of SG rows) x (chunk of SCH ids) -------------------------------------------------------------------------
+// ---- 1. sweep: (group of TILE_G rows) x (chunk of TILE_CH ids) -----------------------------------------------------------------
 struct SampleArgs {
   const float* hidden; const int64_t* hidden_row; const float* table; const float* bias; const float* scale;
   const int64_t* exclude; const int64_t* gt;
@@ -157,24 +53,24 @@ struct SampleArgs {
   int hidden_ld, H, V, lo, E, n, nch, cap, n_filters;
 };
 
-__global__ __launch_bounds__(ST, 2) void sample_sweep_kernel(SampleArgs a) {
-  __shared__ float tile[SIPT * ST * (SKB + 1)];
-  __shared__ __attribute__((aligned(16))) float hsh[SG * SKB];
-  __shared__ uint32_t bits[SG][SCH / 32];
-  __shared__ uint32_t hist[SG][256];
-  __shared__ uint32_t part[SG][16];
-  __shared__ Sel st[SG];
-  __shared__ uint32_t s_cnt[SG], s_kmin[SG], s_kmax[SG], s_out[SG], s_slo[SG], s_shi[SG];
-  __shared__ int64_t s_hoff[SG], s_gt[SG];
+__global__ __launch_bounds__(TILE_T, 2) void sample_sweep_kernel(SampleArgs a) {
+  __shared__ float tile[TILE_IPT * TILE_T * (TILE_KB + 1)];
+  __shared__ __attribute__((aligned(16))) float hsh[TILE_G * TILE_KB];
+  __shared__ uint32_t bits[TILE_G][TILE_CH / 32];
+  __shared__ uint32_t hist[TILE_G][256];
+  __shared__ uint32_t part[TILE_G][16];
+  __shared__ Sel st[TILE_G];
+  __shared__ uint32_t s_cnt[TILE_G], s_kmin[TILE_G], s_kmax[TILE_G], s_out[TILE_G], s_slo[TILE_G], s_shi[TILE_G];
+  __shared__ int64_t s_hoff[TILE_G], s_gt[TILE_G];
   __shared__ int s_alldone;
 
   const int tid = threadIdx.x, lane = tid & 63;
-  const int lr0 = blockIdx.x * SG;
+  const int lr0 = blockIdx.x * TILE_G;
   const int chunk = blockIdx.y;
-  const int64_t c0 = (int64_t)chunk * SCH;
+  const int64_t c0 = (int64_t)chunk * TILE_CH;
   const int H = a.H;
 
-  if (tid < SG) {
+  if (tid < TILE_G) {
     const int lr = lr0 + tid;
     const bool rv = lr < a.n;
     const int64_t r = a.r0 + lr;   // the absolute row of the call: the noise does not depend on the grouping
@@ -185,89 +81,61 @@ __global__ __launch_bounds__(ST, 2) void sample_sweep_kernel(SampleArgs a) {
     s_cnt[tid] = 0; s_out[tid] = 0;
     s_kmin[tid] = 0xFFFFFFFFu; s_kmax[tid] = 0u;
   }
-  if (a.allow) {
-    // bit set = not drawn: the complement of the row's filter words of this chunk (no filter for the row: all allowed)
-    const int64_t W = ((int64_t)a.V + 31) >> 5;
-    for (int i = tid; i < SG * (SCH / 32); i += ST) {
-      const int g = i / (SCH / 32), w = i - g * (SCH / 32);
-      const int lr = lr0 + g;
-      const int64_t wi = (c0 >> 5) + w;
-      uint32_t word = 0u;
-      if (lr < a.n && wi < W) {
-        const int32_t f = a.row_filter ? a.row_filter[a.r0 + lr] : 0;
-        if (f >= 0 && f < a.n_filters) word = ~a.allow[(int64_t)f * W + wi];
-      }
-      bits[g][w] = word;
-    }
-  } else {
-    for (int i = tid; i < SG * (SCH / 32); i += ST) (&bits[0][0])[i] = 0u;
-  }
-  __syncthreads();
-  if (a.E > 0) {
-    for (int f = tid; f < SG * a.E; f += ST) {
-      const int g = f / a.E, e = f - g * a.E;
-      if (s_hoff[g] < 0) continue;
-      const int64_t id = a.exclude[(a.r0 + lr0 + g) * (int64_t)a.E + e];
-      if (id >= c0 && id < c0 + SCH) {
-        const int l = (int)(id - c0);
-        atomicOr(&bits[g][l >> 5], 1u << (l & 31));
-      }
-    }
-  }
+  tile_row_bitmap(bits, a.allow != nullptr, a.allow, a.row_filter, a.n_filters, a.exclude, a.E, s_hoff, a.r0, lr0, a.n, a.V, c0);
 
   // ---- keys: raw fp32 bits in registers, NOT_ALLOWED where the id is not drawn -----------------------------------------------------
-  uint32_t raw[SQ][SG];
+  uint32_t raw[TILE_Q][TILE_G];
 #pragma unroll
-  for (int ps = 0; ps < SQ / SIPT; ++ps) {
-    float acc[SIPT][SG];
+  for (int ps = 0; ps < TILE_Q / TILE_IPT; ++ps) {
+    float acc[TILE_IPT][TILE_G];
 #pragma unroll
-    for (int ii = 0; ii < SIPT; ++ii)
+    for (int ii = 0; ii < TILE_IPT; ++ii)
 #pragma unroll
-      for (int g = 0; g < SG; ++g) acc[ii][g] = 0.f;
-    const int64_t cj0 = c0 + (int64_t)ps * SIPT * ST;   // first id of this step
-    for (int kb = 0; kb < H; kb += SKB) {
-      const int kn = min(SKB, H - kb);   // a multiple of 4 (H % 4 == 0)
+      for (int g = 0; g < TILE_G; ++g) acc[ii][g] = 0.f;
+    const int64_t cj0 = c0 + (int64_t)ps * TILE_IPT * TILE_T;   // first id of this step
+    for (int kb = 0; kb < H; kb += TILE_KB) {
+      const int kn = min(TILE_KB, H - kb);   // a multiple of 4 (H % 4 == 0)
       const int k4 = kn >> 2;
       __syncthreads();   // the previous block is consumed (and, the first time, the bitmap is complete)
-      for (int f = tid; f < SIPT * ST * k4; f += ST) {
+      for (int f = tid; f < TILE_IPT * TILE_T * k4; f += TILE_T) {
         const int i = f / k4, c4 = f - i * k4;
         const int64_t j = cj0 + i;
         const f32x4 v = j < a.V ? *reinterpret_cast<const f32x4*>(a.table + j * H + kb + 4 * c4) : (f32x4){0.f, 0.f, 0.f, 0.f};
-        float* dst = tile + i * (SKB + 1) + 4 * c4;
+        float* dst = tile + i * (TILE_KB + 1) + 4 * c4;
         dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3];
       }
       {
-        const int g = tid / SKB, k = tid - g * SKB;
+        const int g = tid / TILE_KB, k = tid - g * TILE_KB;
         hsh[tid] = (k < kn && s_hoff[g] >= 0) ? a.hidden[s_hoff[g] + kb + k] : 0.f;
       }
       __syncthreads();
       for (int k = 0; k < kn; k += 4) {
-        float e[SIPT][4];
+        float e[TILE_IPT][4];
 #pragma unroll
-        for (int ii = 0; ii < SIPT; ++ii)
+        for (int ii = 0; ii < TILE_IPT; ++ii)
 #pragma unroll
-          for (int u = 0; u < 4; ++u) e[ii][u] = tile[(ii * ST + tid) * (SKB + 1) + k + u];
+          for (int u = 0; u < 4; ++u) e[ii][u] = tile[(ii * TILE_T + tid) * (TILE_KB + 1) + k + u];
 #pragma unroll
-        for (int g = 0; g < SG; ++g) {
-          const f32x4 h = *reinterpret_cast<const f32x4*>(hsh + g * SKB + k);
+        for (int g = 0; g < TILE_G; ++g) {
+          const f32x4 h = *reinterpret_cast<const f32x4*>(hsh + g * TILE_KB + k);
 #pragma unroll
           for (int u = 0; u < 4; ++u)
 #pragma unroll
-            for (int ii = 0; ii < SIPT; ++ii) acc[ii][g] = __builtin_fmaf(h[u], e[ii][u], acc[ii][g]);
+            for (int ii = 0; ii < TILE_IPT; ++ii) acc[ii][g] = __builtin_fmaf(h[u], e[ii][u], acc[ii][g]);
         }
       }
     }
 #pragma unroll
-    for (int ii = 0; ii < SIPT; ++ii) {
-      const int q = ps * SIPT + ii;
-      const int l = q * ST + tid;
+    for (int ii = 0; ii < TILE_IPT; ++ii) {
+      const int q = ps * TILE_IPT + ii;
+      const int l = q * TILE_T + tid;
       const int64_t j = c0 + l;
       const bool inb = j >= a.lo && j < a.V;
       const float b = (a.bias && inb) ? a.bias[j] : 0.f;
       const float sc = (a.scale && inb) ? a.scale[j] : 1.f;
       const uint32_t h0 = b4r_hash32((uint32_t)(uint64_t)j ^ a.seed_lo);   // the row-independent round of b4r_sample_word_hd
 #pragma unroll
-      for (int g = 0; g < SG; ++g) {
+      for (int g = 0; g < TILE_G; ++g) {
         const bool ex = (bits[g][l >> 5] >> (l & 31)) & 1u;
         const bool ok = inb && s_hoff[g] >= 0 && (!ex || j == s_gt[g]);
         uint32_t kbits = NOT_ALLOWED;
@@ -285,10 +153,10 @@ __global__ __launch_bounds__(ST, 2) void sample_sweep_kernel(SampleArgs a) {
 
   // ---- per row: allowed count, key range ------------------------------------------------------------------------------------------
 #pragma unroll
-  for (int g = 0; g < SG; ++g) {
+  for (int g = 0; g < TILE_G; ++g) {
     uint32_t cnt = 0, kmin = 0xFFFFFFFFu, kmax = 0u;
 #pragma unroll
-    for (int q = 0; q < SQ; ++q) {
+    for (int q = 0; q < TILE_Q; ++q) {
       if (raw[q][g] == NOT_ALLOWED) continue;
       const uint32_t k = score_key_bits(raw[q][g]);
       cnt += 1;
@@ -302,34 +170,34 @@ __global__ __launch_bounds__(ST, 2) void sample_sweep_kernel(SampleArgs a) {
     }
   }
   __syncthreads();
-  if (tid < SG && lr0 + tid < a.n) {
+  if (tid < TILE_G && lr0 + tid < a.n) {
     const int n = (int)s_cnt[tid];
     sel_init(st[tid], n, min(a.cap, n), s_kmin[tid], s_kmax[tid]);
-  } else if (tid < SG) {
+  } else if (tid < TILE_G) {
     sel_init(st[tid], 0, 0, 0u, 0u);
   }
   if (tid == 0) s_alldone = 0;
 
-  // ---- radix select over (key image << 16 | SCH-1 - local id) ------------------------------------------------------------------
+  // ---- radix select over (key image << 16 | TILE_CH-1 - local id) ------------------------------------------------------------------
   for (int pass = 0; pass < 6; ++pass) {
     __syncthreads();
     if (tid == 0) {
       int all = 1;
-      for (int g = 0; g < SG; ++g) all &= st[g].done;
+      for (int g = 0; g < TILE_G; ++g) all &= st[g].done;
       s_alldone = all;
     }
-    for (int i = tid; i < SG * 256; i += ST) (&hist[0][0])[i] = 0u;
+    for (int i = tid; i < TILE_G * 256; i += TILE_T) (&hist[0][0])[i] = 0u;
     __syncthreads();
     if (s_alldone) break;
 #pragma unroll
-    for (int g = 0; g < SG; ++g) {
+    for (int g = 0; g < TILE_G; ++g) {
       const Sel s = st[g];
       if (s.done) continue;
       const int nb = sel_nb(s, 48), sh = 48 - s.hi - nb;
 #pragma unroll
-      for (int q = 0; q < SQ; ++q) {
+      for (int q = 0; q < TILE_Q; ++q) {
         if (raw[q][g] == NOT_ALLOWED) continue;
-        const uint64_t key = ((uint64_t)score_key_bits(raw[q][g]) << 16) | (uint64_t)(SCH - 1 - (q * ST + tid));
+        const uint64_t key = ((uint64_t)score_key_bits(raw[q][g]) << 16) | (uint64_t)(TILE_CH - 1 - (q * TILE_T + tid));
         if (sel_match(s, key, 48)) atomicAdd(&hist[g][(key >> sh) & ((1u << nb) - 1u)], 1u);
       }
     }
@@ -344,15 +212,15 @@ __global__ __launch_bounds__(ST, 2) void sample_sweep_kernel(SampleArgs a) {
 
   // ---- emit the selected ids of each row (any order: the merge orders them) ------------------------------------------------
 #pragma unroll
-  for (int g = 0; g < SG; ++g) {
+  for (int g = 0; g < TILE_G; ++g) {
     const Sel s = st[g];
     if (!s.take || !s.done) continue;
     const int64_t base = ((int64_t)(lr0 + g) * a.nch + chunk) * a.cap;
 #pragma unroll
-    for (int q = 0; q < SQ; ++q) {
+    for (int q = 0; q < TILE_Q; ++q) {
       if (raw[q][g] == NOT_ALLOWED) continue;
-      const int l = q * ST + tid;
-      const uint64_t key = ((uint64_t)score_key_bits(raw[q][g]) << 16) | (uint64_t)(SCH - 1 - l);
+      const int l = q * TILE_T + tid;
+      const uint64_t key = ((uint64_t)score_key_bits(raw[q][g]) << 16) | (uint64_t)(TILE_CH - 1 - l);
       if (key < s.thr) continue;
       const uint32_t slot = atomicAdd(&s_out[g], 1u);
       if (slot < (uint32_t)a.cap) {
@@ -362,7 +230,7 @@ __global__ __launch_bounds__(ST, 2) void sample_sweep_kernel(SampleArgs a) {
     }
   }
   __syncthreads();
-  if (tid < SG && lr0 + tid < a.n) a.c_cnt[(int64_t)(lr0 + tid) * a.nch + chunk] = (int32_t)min(s_out[tid], (uint32_t)a.cap);
+  if (tid < TILE_G && lr0 + tid < a.n) a.c_cnt[(int64_t)(lr0 + tid) * a.nch + chunk] = (int32_t)min(s_out[tid], (uint32_t)a.cap);
 }
 
 // ---- 2. merge: one workgroup per row ------------------------------------------------------------------------------------------
@@ -374,88 +242,26 @@ struct SampleMergeArgs {
   int nch, cap, K, hidden_ld, H;
 };
 
-__global__ __launch_bounds__(ST) void sample_merge_kernel(SampleMergeArgs a) {
+__global__ __launch_bounds__(TILE_T) void sample_merge_kernel(SampleMergeArgs a) {
   __shared__ uint32_t hist[256];
   __shared__ uint32_t part[16];
   __shared__ Sel st;
   __shared__ uint32_t s_n, s_kmin, s_kmax, s_out;
-  __shared__ uint64_t sel_key[SK_MAX];
-  __shared__ float sel_raw[SK_MAX];
-  const int tid = threadIdx.x, lane = tid & 63;
+  __shared__ uint64_t sel_key[SEL_K_MAX];
+  __shared__ float sel_val[SEL_K_MAX];
+  const MergeSel L{hist, part, st, s_n, s_kmin, s_kmax, s_out, nullptr, sel_key, sel_val};
   const int lr = blockIdx.x;
   const int64_t r = a.r0 + lr;
-  const int32_t* cnt = a.c_cnt + (int64_t)lr * a.nch;
-  const int64_t base = (int64_t)lr * a.nch * a.cap;
-  const int64_t total_slots = (int64_t)a.nch * a.cap;
-
-  if (tid == 0) { s_n = 0; s_kmin = 0xFFFFFFFFu; s_kmax = 0u; s_out = 0; }
-  __syncthreads();
-  {
-    uint32_t n = 0, kmin = 0xFFFFFFFFu, kmax = 0u;
-    for (int c = tid; c < a.nch; c += ST) n += (uint32_t)cnt[c];
-    for (int64_t e = tid; e < total_slots; e += ST) {
-      const int c = (int)(e / a.cap), i = (int)(e - (int64_t)c * a.cap);
-      if (i >= cnt[c]) continue;
-      const uint32_t k = score_key(a.c_key[base + e]);
-      kmin = min(kmin, k); kmax = max(kmax, k);
-    }
-    n = wave_sum_u32(n);
-    kmin = wave_min_u32(kmin); kmax = wave_max_u32(kmax);
-    if (lane == 0) { atomicAdd(&s_n, n); atomicMin(&s_kmin, kmin); atomicMax(&s_kmax, kmax); }
-  }
-  __syncthreads();
-  const int n = (int)s_n;
-  const int need = min(a.K, n);
-  if (tid == 0) sel_init(st, n, need, s_kmin, s_kmax);
-  for (int pass = 0; pass < 8; ++pass) {
-    __syncthreads();
-    if (st.done) break;
-    for (int i = tid; i < 256; i += ST) hist[i] = 0u;
-    __syncthreads();
-    const Sel s = st;
-    const int nb = sel_nb(s, 64), sh = 64 - s.hi - nb;
-    for (int64_t e = tid; e < total_slots; e += ST) {
-      const int c = (int)(e / a.cap), i = (int)(e - (int64_t)c * a.cap);
-      if (i >= cnt[c]) continue;
-      const uint64_t key = ((uint64_t)score_key(a.c_key[base + e]) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)a.c_id[base + e]);
-      if (sel_match(s, key, 64)) atomicAdd(&hist[(key >> sh) & ((1u << nb) - 1u)], 1u);
-    }
-    __syncthreads();
-    if (tid < 16) sel_part(hist, part, tid);
-    __syncthreads();
-    if (tid < 16) sel_advance(s, st, hist, part, tid, 64);
-  }
-  __syncthreads();
-  if (st.take && st.done) {
-    const uint64_t thr = st.thr;
-    for (int64_t e = tid; e < total_slots; e += ST) {
-      const int c = (int)(e / a.cap), i = (int)(e - (int64_t)c * a.cap);
-      if (i >= cnt[c]) continue;
-      const float kf = a.c_key[base + e];
-      const uint64_t key = ((uint64_t)score_key(kf) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)a.c_id[base + e]);
-      if (key < thr) continue;
-      const uint32_t slot = atomicAdd(&s_out, 1u);
-      if (slot < (uint32_t)SK_MAX) { sel_key[slot] = key; sel_raw[slot] = kf; }
-    }
-  }
-  __syncthreads();
-  const int m = min((int)s_out, min(a.K, SK_MAX));
+  const int64_t row = (int64_t)lr * a.nch;
+  const int m = merge_select<TILE_T>(L, a.c_key, a.c_id, a.c_cnt, nullptr, row, a.nch, a.cap, a.K);
   const int64_t hr = a.hidden_row ? a.hidden_row[r] : r;
-  for (int i = tid; i < m; i += ST) {
-    const uint64_t ki = sel_key[i];
-    int pos = 0;
-    for (int j = 0; j < m; ++j) pos += sel_key[j] > ki ? 1 : 0;   // keys are unique: a permutation of 0 .. m-1
-    const int64_t id = (int64_t)(0xFFFFFFFFu - (uint32_t)(ki & 0xFFFFFFFFu));
+  merge_order<TILE_T>(L, m, a.K, [&](int pos, int64_t id, float key) {
     if (a.out_ids) a.out_ids[r * a.K + pos] = id;
-    if (a.out_keys) a.out_keys[r * a.K + pos] = sel_raw[i];
-    // the unperturbed score, by the chain every sweep uses: b4r_rank_full's bits for this id
-    if (a.out_scores) a.out_scores[r * a.K + pos] = row_score(a.hidden + hr * a.hidden_ld, a.table + id * a.H, a.bias, a.scale, id, a.H);
-  }
-  for (int p = m + tid; p < a.K; p += ST) {
-    if (a.out_ids) a.out_ids[r * a.K + p] = -1;
-    if (a.out_scores) a.out_scores[r * a.K + p] = -INFINITY;
-    if (a.out_keys) a.out_keys[r * a.K + p] = -INFINITY;
-  }
+    if (a.out_keys) a.out_keys[r * a.K + pos] = key;
+    // the unperturbed score, by the chain every sweep uses: b4r_rank_full's bits for this id (id = -1: merge_order's padding call)
+    if (a.out_scores)
+      a.out_scores[r * a.K + pos] = id >= 0 ? row_score(a.hidden + hr * a.hidden_ld, a.table + id * a.H, a.bias, a.scale, id, a.H) : -INFINITY;
+  });
 }
 
 // ---- b4r_sample_pool: one workgroup per row --------------------------------------------------------------------------------------
@@ -467,10 +273,10 @@ struct PoolArgs {
   int M, V, K;
 };
 
-__global__ __launch_bounds__(ST) void sample_pool_kernel(PoolArgs a) {
-  __shared__ int64_t p_id[SK_MAX];
-  __shared__ uint32_t p_img[SK_MAX];   // the key's order-preserving image; dead entries are marked in p_id (-1)
-  __shared__ float p_key[SK_MAX];
+__global__ __launch_bounds__(TILE_T) void sample_pool_kernel(PoolArgs a) {
+  __shared__ int64_t p_id[SEL_K_MAX];
+  __shared__ uint32_t p_img[SEL_K_MAX];   // the key's order-preserving image; dead entries are marked in p_id (-1)
+  __shared__ float p_key[SEL_K_MAX];
   __shared__ uint32_t s_live;
   const int tid = threadIdx.x;
   const int64_t r = blockIdx.x;
@@ -478,7 +284,7 @@ __global__ __launch_bounds__(ST) void sample_pool_kernel(PoolArgs a) {
   if (tid == 0) s_live = 0;
   __syncthreads();
   uint32_t live = 0;
-  for (int i = tid; i < a.M; i += ST) {
+  for (int i = tid; i < a.M; i += TILE_T) {
     const int64_t id = a.pool_ids[r * a.M + i];
     const float s = a.pool_scores[r * a.M + i];
     const bool ok = id >= 0 && id < a.V && isfinite(s);
@@ -493,7 +299,7 @@ __global__ __launch_bounds__(ST) void sample_pool_kernel(PoolArgs a) {
   if ((tid & 63) == 0) atomicAdd(&s_live, live);
   __syncthreads();
   const int n = (int)s_live;
-  for (int i = tid; i < a.M; i += ST) {
+  for (int i = tid; i < a.M; i += TILE_T) {
     const int64_t id = p_id[i];
     if (id < 0) continue;
     const uint32_t ki = p_img[i];
@@ -510,7 +316,7 @@ __global__ __launch_bounds__(ST) void sample_pool_kernel(PoolArgs a) {
     if (a.out_keys) a.out_keys[r * a.K + pos] = p_key[i];
     if (a.out_pos) a.out_pos[r * a.K + pos] = i;
   }
-  for (int p = n + tid; p < a.K; p += ST) {
+  for (int p = n + tid; p < a.K; p += TILE_T) {
     if (a.out_ids) a.out_ids[r * a.K + p] = -1;
     if (a.out_scores) a.out_scores[r * a.K + p] = -INFINITY;
     if (a.out_keys) a.out_keys[r * a.K + p] = -INFINITY;
@@ -518,9 +324,7 @@ __global__ __launch_bounds__(ST) void sample_pool_kernel(PoolArgs a) {
   }
 }
 
-int64_t chunks_of(int32_t V) { return ((int64_t)V + SCH - 1) / SCH; }
-int64_t cap_of(int32_t K) { return std::min<int64_t>(K, SCH); }
-int64_t row_bytes(int32_t V, int32_t K) { return chunks_of(V) * (cap_of(K) * 8 + 4); }   // keys, ids | counts
+int64_t row_bytes(int32_t V, int32_t K) { return tile_chunks_of(V) * (tile_cap_of(K) * 8 + 4); }   // keys, ids | counts
 
 }  // namespace
 
@@ -533,14 +337,14 @@ extern "C" int b4r_gumbel_noise(const uint32_t* words, int64_t n, float* out, b4
   B4R_CHECK_ARG(n >= 0, B4R_E_SHAPE, "%s: n = %lld", what, (long long)n);
   if (n == 0) return B4R_OK;
   B4R_CHECK_ARG(words && out, B4R_E_BADARG, "%s: null argument", what);
-  const int blocks = (int)std::min<int64_t>(((int64_t)n + ST - 1) / ST, 8192);
-  hipLaunchKernelGGL(gumbel_noise_kernel, dim3(blocks), dim3(ST), 0, (hipStream_t)stream, words, n, out);
+  const int blocks = (int)std::min<int64_t>(((int64_t)n + TILE_T - 1) / TILE_T, 8192);
+  hipLaunchKernelGGL(gumbel_noise_kernel, dim3(blocks), dim3(TILE_T), 0, (hipStream_t)stream, words, n, out);
   B4R_CHECK_LAUNCH(what);
   return B4R_OK;
 }
 
 extern "C" int64_t b4r_sample_full_scratch_bytes(int32_t R, int32_t V, int32_t K) {
-  if (R <= 0 || V <= 0 || K < 0 || K > SK_MAX) return 0;
+  if (R <= 0 || V <= 0 || K < 0 || K > SEL_K_MAX) return 0;
   return (int64_t)R * row_bytes(V, K) + 64;   // + room for the 16-byte alignment of the regions
 }
 
@@ -551,8 +355,8 @@ extern "C" int b4r_sample_full(const float* hidden, int32_t hidden_ld, const int
                                int64_t stream0, int64_t* out_ids, float* out_scores, float* out_keys, void* scratch,
                                int64_t scratch_bytes, b4r_stream_t stream) {
   const char* what = "b4r_sample_full";
-  B4R_CHECK_ARG(R >= 0 && K >= 0 && K <= SK_MAX && E >= 0 && first_item >= 0, B4R_E_SHAPE,
-                "%s: bad shape (R = %d, K = %d in [0, %d], E = %d, first_item = %d)", what, R, K, SK_MAX, E, first_item);
+  B4R_CHECK_ARG(R >= 0 && K >= 0 && K <= SEL_K_MAX && E >= 0 && first_item >= 0, B4R_E_SHAPE,
+                "%s: bad shape (R = %d, K = %d in [0, %d], E = %d, first_item = %d)", what, R, K, SEL_K_MAX, E, first_item);
   B4R_CHECK_ARG(H > 0 && H % 4 == 0 && H <= 4096 && hidden_ld >= H && V > 0, B4R_E_SHAPE,
                 "%s: bad shape (H = %d, hidden_ld = %d, V = %d)", what, H, hidden_ld, V);
   B4R_CHECK_ARG(!allow_bits || n_filters > 0, B4R_E_SHAPE, "%s: allow_bits with n_filters = %d", what, n_filters);
@@ -563,19 +367,14 @@ extern "C" int b4r_sample_full(const float* hidden, int32_t hidden_ld, const int
   B4R_CHECK_ARG(E == 0 || exclude, B4R_E_BADARG, "%s: exclude is NULL with E = %d", what, E);
   B4R_CHECK_ARG(b4r_aligned16(table), B4R_E_ALIGN, "%s: the table must be 16-byte aligned", what);
   const int64_t per_row = row_bytes(V, K);
-  const int64_t usable = scratch ? scratch_bytes - (int64_t)((16 - ((uintptr_t)scratch & 15)) & 15) : 0;
-  int64_t group = usable > 0 ? usable / per_row : 0;
-  group = std::min<int64_t>(group, R);
-  if (group < R) group = group / SG * SG;   // whole sweep groups
-  B4R_CHECK_ARG(group >= std::min<int64_t>(R, SG), B4R_E_NOMEM,
+  const int64_t group = tile_group_of(scratch, scratch_bytes, per_row, R, TILE_G);   // whole sweep groups
+  B4R_CHECK_ARG(group >= std::min<int64_t>(R, TILE_G), B4R_E_NOMEM,
                 "%s: scratch of %lld bytes is too small: %lld bytes per row, %d rows at least (b4r_sample_full_scratch_bytes)", what,
-                (long long)scratch_bytes, (long long)per_row, std::min<int32_t>(R, SG));
-  group = std::min<int64_t>(group, 65535LL * SG);
-  const int nch = (int)chunks_of(V);
+                (long long)scratch_bytes, (long long)per_row, std::min<int32_t>(R, TILE_G));
+  const int nch = (int)tile_chunks_of(V);
   B4R_CHECK_ARG(nch <= 65535, B4R_E_SHAPE, "%s: V = %d is too large", what, V);
-  const int cap = (int)cap_of(K);
-  char* p = reinterpret_cast<char*>(((uintptr_t)scratch + 15) & ~(uintptr_t)15);
-  float* c_key = reinterpret_cast<float*>(p);
+  const int cap = (int)tile_cap_of(K);
+  float* c_key = reinterpret_cast<float*>(tile_scratch_base(scratch));
   int32_t* c_id = reinterpret_cast<int32_t*>(c_key + group * nch * cap);
   int32_t* c_cnt = c_id + group * nch * cap;
   hipStream_t s = (hipStream_t)stream;
@@ -584,10 +383,10 @@ extern "C" int b4r_sample_full(const float* hidden, int32_t hidden_ld, const int
     SampleArgs sa{hidden, hidden_row, table, bias, item_scale, exclude, gt, allow_bits, row_filter, row_stream, c_key, c_id, c_cnt,
                   r0, stream0, (uint32_t)seed, (uint32_t)(seed >> 32), inv_temperature, hidden_ld, H, V, first_item, E, n, nch, cap,
                   n_filters};
-    hipLaunchKernelGGL(sample_sweep_kernel, dim3(b4r_cdiv(n, SG), nch), dim3(ST), 0, s, sa);
+    hipLaunchKernelGGL(sample_sweep_kernel, dim3(b4r_cdiv(n, TILE_G), nch), dim3(TILE_T), 0, s, sa);
     SampleMergeArgs ma{c_key, c_id, c_cnt, hidden, hidden_row, table, bias, item_scale, out_ids, out_scores, out_keys, r0,
                        nch, cap, K, hidden_ld, H};
-    hipLaunchKernelGGL(sample_merge_kernel, dim3(n), dim3(ST), 0, s, ma);
+    hipLaunchKernelGGL(sample_merge_kernel, dim3(n), dim3(TILE_T), 0, s, ma);
   }
   B4R_CHECK_LAUNCH(what);
   return B4R_OK;
@@ -597,14 +396,14 @@ extern "C" int b4r_sample_pool(const int64_t* pool_ids, const float* pool_scores
                                uint64_t seed, const int64_t* row_stream, int64_t stream0, int32_t K, int64_t* out_ids,
                                float* out_scores, float* out_keys, int32_t* out_pos, b4r_stream_t stream) {
   const char* what = "b4r_sample_pool";
-  B4R_CHECK_ARG(R >= 0 && M >= 1 && M <= SK_MAX && K >= 0 && K <= M && V > 0, B4R_E_SHAPE,
-                "%s: bad shape (R = %d, M = %d in [1, %d], K = %d in [0, M], V = %d)", what, R, M, SK_MAX, K, V);
+  B4R_CHECK_ARG(R >= 0 && M >= 1 && M <= SEL_K_MAX && K >= 0 && K <= M && V > 0, B4R_E_SHAPE,
+                "%s: bad shape (R = %d, M = %d in [1, %d], K = %d in [0, M], V = %d)", what, R, M, SEL_K_MAX, K, V);
   B4R_CHECK_ARG(std::isfinite(inv_temperature) && inv_temperature > 0.f, B4R_E_BADARG,
                 "%s: inv_temperature = %g must be finite and > 0", what, (double)inv_temperature);
   if (R == 0 || K == 0) return B4R_OK;
   B4R_CHECK_ARG(pool_ids && pool_scores, B4R_E_BADARG, "%s: null argument", what);
   PoolArgs pa{pool_ids, pool_scores, row_stream, out_ids, out_scores, out_keys, out_pos, seed, stream0, inv_temperature, M, V, K};
-  hipLaunchKernelGGL(sample_pool_kernel, dim3(R), dim3(ST), 0, (hipStream_t)stream, pa);
+  hipLaunchKernelGGL(sample_pool_kernel, dim3(R), dim3(TILE_T), 0, (hipStream_t)stream, pa);
   B4R_CHECK_LAUNCH(what);
   return B4R_OK;
 }

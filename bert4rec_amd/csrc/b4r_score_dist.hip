@@ -9,9 +9,9 @@
 // multiply by item_scale), t = fl32(s * inv_temperature), allowed(r) is b4r_rank_full_ex's set.
 //
 // Three launches per group of rows that fits the scratch:
-//   1. sweep    grid (group of DG = 16 rows) x (chunk of DCH = 1024 ids), staged as b4r_rank_full's sweep stages its table rows
-//               (k-blocks of DKB floats through LDS, once for all 16 rows; 4 ids x 16 rows of t per thread in registers).  Per
-//               (row, chunk): n_c = #allowed, m_c = max t, S_c = sum (double) e_j, W_c = sum (double) e_j (double) x_j with
+//   1. sweep    grid (group of 16 rows) x (chunk of 1024 ids): the tile of b4r_catalogue_tile.h, staged as b4r_rank_full's sweep
+//               stages its table rows (k-blocks of 16 floats through LDS, once for all 16 rows; 4 ids x 16 rows of t per thread
+//               in registers).  Per (row, chunk): n_c = #allowed, m_c = max t, S_c = sum (double) e_j, W_c = sum (double) e_j (double) x_j with
 //               x_j = fl32(t_j - m_c), e_j = expf(x_j).  The sums run in fp64 in a fixed order: a thread's 4 ids in ascending id,
 //               the xor butterfly over the wave, the 4 waves in ascending order.
 //   2. merge    one wave per row: m = max m_c; f_c = exp(m_c - m) in fp64; S = sum S_c f_c, W = sum (W_c + (m_c - m) S_c) f_c, each
@@ -22,28 +22,14 @@
 #include <cmath>
 
 #include "b4r_common.h"
+#include "b4r_catalogue_tile.h"
 
 namespace {
 
-constexpr int DT = 256;          // threads per workgroup
-constexpr int DG = 16;           // rows per sweep workgroup
-constexpr int DQ = 4;            // ids per thread per chunk
-constexpr int DIPT = 2;          // ids scored together per k-block (DQ / DIPT steps)
-constexpr int DCH = DT * DQ;     // ids per chunk
-constexpr int DKB = 16;          // k-block (floats of a table row staged at a time)
-constexpr int DW = DT / 64;      // waves per workgroup
-constexpr int DK_MAX = 1024;     // most queries per row
+constexpr int DW = TILE_T / 64;   // waves per workgroup
+constexpr int DK_MAX = 1024;      // most queries per row
 
-static_assert(DG * DKB == DT, "one thread per staged hidden value");
-static_assert(DG <= 32, "a row's allowed ids of one q are one bit of a 32-bit mask");
-
-// b4r_rank_full's row_score: bias NULL: + 0.0f; scale (NULL: none) multiplies the rounded chain once
-__device__ __forceinline__ float dist_row_score(const float* h, const float* e, const float* bias, const float* scale, int64_t j, int H) {
-  float acc = 0.f;
-  for (int k = 0; k < H; ++k) acc = __builtin_fmaf(h[k], e[k], acc);   // k-ordered fp32 fma chain (the contract)
-  const float s = acc + (bias ? bias[j] : 0.f);
-  return scale ? s * scale[j] : s;
-}
+static_assert(TILE_G <= 32, "a row's allowed ids of one q are one bit of a 32-bit mask");
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
@@ -61,113 +47,80 @@ struct DistArgs {
   int hidden_ld, H, V, lo, E, n, nch, n_filters;
 };
 
-// ---- 1. sweep: (group of DG rows) x (chunk of DCH ids) -------------------------------------------------------------------------
-__global__ __launch_bounds__(DT, 2) void dist_sweep_kernel(DistArgs a) {
-  __shared__ float tile[DIPT * DT * (DKB + 1)];
-  __shared__ __attribute__((aligned(16))) float hsh[DG * DKB];
-  __shared__ uint32_t bits[DG][DCH / 32];
-  __shared__ int64_t s_hoff[DG], s_gt[DG];
-  __shared__ float s_wm[DG][DW];
-  __shared__ int s_wn[DG][DW];
-  __shared__ double s_wS[DG][DW], s_wW[DG][DW];
+// ---- 1. sweep: (group of TILE_G rows) x (chunk of TILE_CH ids) -------------------------------------------------------------------------
+__global__ __launch_bounds__(TILE_T, 2) void dist_sweep_kernel(DistArgs a) {
+  __shared__ float tile[TILE_IPT * TILE_T * (TILE_KB + 1)];
+  __shared__ __attribute__((aligned(16))) float hsh[TILE_G * TILE_KB];
+  __shared__ uint32_t bits[TILE_G][TILE_CH / 32];
+  __shared__ int64_t s_hoff[TILE_G], s_gt[TILE_G];
+  __shared__ float s_wm[TILE_G][DW];
+  __shared__ int s_wn[TILE_G][DW];
+  __shared__ double s_wS[TILE_G][DW], s_wW[TILE_G][DW];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr0 = blockIdx.x * DG;
+  const int lr0 = blockIdx.x * TILE_G;
   const int chunk = blockIdx.y;
-  const int64_t c0 = (int64_t)chunk * DCH;
+  const int64_t c0 = (int64_t)chunk * TILE_CH;
   const int H = a.H;
 
-  if (tid < DG) {
-    const int lr = lr0 + tid;
-    const bool rv = lr < a.n;
-    const int64_t r = a.r0 + lr;
-    s_hoff[tid] = rv ? (a.hidden_row ? a.hidden_row[r] : r) * a.hidden_ld : -1;
-    s_gt[tid] = (rv && a.gt) ? a.gt[r] : -1;
-  }
-  if (a.allow) {
-    // bit set = not allowed: the complement of the row's filter words of this chunk (no filter for the row: all allowed)
-    const int64_t W = ((int64_t)a.V + 31) >> 5;
-    for (int i = tid; i < DG * (DCH / 32); i += DT) {
-      const int g = i / (DCH / 32), w = i - g * (DCH / 32);
-      const int lr = lr0 + g;
-      const int64_t wi = (c0 >> 5) + w;
-      uint32_t word = 0u;
-      if (lr < a.n && wi < W) {
-        const int32_t f = a.row_filter ? a.row_filter[a.r0 + lr] : 0;
-        if (f >= 0 && f < a.n_filters) word = ~a.allow[(int64_t)f * W + wi];
-      }
-      bits[g][w] = word;
-    }
-  } else {
-    for (int i = tid; i < DG * (DCH / 32); i += DT) (&bits[0][0])[i] = 0u;
-  }
-  __syncthreads();
-  if (a.E > 0) {
-    for (int f = tid; f < DG * a.E; f += DT) {
-      const int g = f / a.E, e = f - g * a.E;
-      if (s_hoff[g] < 0) continue;
-      const int64_t id = a.exclude[(a.r0 + lr0 + g) * (int64_t)a.E + e];
-      if (id >= c0 && id < c0 + DCH) {
-        const int l = (int)(id - c0);
-        atomicOr(&bits[g][l >> 5], 1u << (l & 31));
-      }
-    }
-  }
+  if (tid < TILE_G) tile_row_setup(tid, lr0, a.n, a.r0, a.hidden_row, a.hidden_ld, a.gt, s_hoff, s_gt);
+  tile_row_bitmap(bits, a.allow != nullptr, a.allow, a.row_filter, a.n_filters, a.exclude, a.E, s_hoff, a.r0, lr0, a.n, a.V, c0);
 
   // ---- t = fl32(s * inv_temperature) in registers; okm[q] bit g: id q of this thread is allowed for row g --------------------
-  float t[DQ][DG];
-  uint32_t okm[DQ];
+  float t[TILE_Q][TILE_G];
+  uint32_t okm[TILE_Q];
 #pragma unroll
-  for (int ps = 0; ps < DQ / DIPT; ++ps) {
-    float acc[DIPT][DG];
+  for (int ps = 0; ps < TILE_Q / TILE_IPT; ++ps) {
+    // (the k-block loop is written out in each of the four sweeps: stated once as a function it changed their registers)
+    float acc[TILE_IPT][TILE_G];
 #pragma unroll
-    for (int ii = 0; ii < DIPT; ++ii)
+    for (int ii = 0; ii < TILE_IPT; ++ii)
 #pragma unroll
-      for (int g = 0; g < DG; ++g) acc[ii][g] = 0.f;
-    const int64_t cj0 = c0 + (int64_t)ps * DIPT * DT;   // first id of this step
-    for (int kb = 0; kb < H; kb += DKB) {
-      const int kn = min(DKB, H - kb);   // a multiple of 4 (H % 4 == 0)
+      for (int g = 0; g < TILE_G; ++g) acc[ii][g] = 0.f;
+    const int64_t cj0 = c0 + (int64_t)ps * TILE_IPT * TILE_T;   // first id of this step
+    for (int kb = 0; kb < H; kb += TILE_KB) {
+      const int kn = min(TILE_KB, H - kb);   // a multiple of 4 (H % 4 == 0)
       const int k4 = kn >> 2;
       __syncthreads();   // the previous block is consumed (and, the first time, the bitmap is complete)
-      for (int f = tid; f < DIPT * DT * k4; f += DT) {
+      for (int f = tid; f < TILE_IPT * TILE_T * k4; f += TILE_T) {
         const int i = f / k4, c4 = f - i * k4;
         const int64_t j = cj0 + i;
         const f32x4 v = j < a.V ? *reinterpret_cast<const f32x4*>(a.table + j * H + kb + 4 * c4) : (f32x4){0.f, 0.f, 0.f, 0.f};
-        float* dst = tile + i * (DKB + 1) + 4 * c4;
+        float* dst = tile + i * (TILE_KB + 1) + 4 * c4;
         dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3];
       }
       {
-        const int g = tid / DKB, k = tid - g * DKB;
+        const int g = tid / TILE_KB, k = tid - g * TILE_KB;
         hsh[tid] = (k < kn && s_hoff[g] >= 0) ? a.hidden[s_hoff[g] + kb + k] : 0.f;
       }
       __syncthreads();
       for (int k = 0; k < kn; k += 4) {
-        float e[DIPT][4];
+        float e[TILE_IPT][4];
 #pragma unroll
-        for (int ii = 0; ii < DIPT; ++ii)
+        for (int ii = 0; ii < TILE_IPT; ++ii)
 #pragma unroll
-          for (int u = 0; u < 4; ++u) e[ii][u] = tile[(ii * DT + tid) * (DKB + 1) + k + u];
+          for (int u = 0; u < 4; ++u) e[ii][u] = tile[(ii * TILE_T + tid) * (TILE_KB + 1) + k + u];
 #pragma unroll
-        for (int g = 0; g < DG; ++g) {
-          const f32x4 h = *reinterpret_cast<const f32x4*>(hsh + g * DKB + k);
+        for (int g = 0; g < TILE_G; ++g) {
+          const f32x4 h = *reinterpret_cast<const f32x4*>(hsh + g * TILE_KB + k);
 #pragma unroll
           for (int u = 0; u < 4; ++u)
 #pragma unroll
-            for (int ii = 0; ii < DIPT; ++ii) acc[ii][g] = __builtin_fmaf(h[u], e[ii][u], acc[ii][g]);
+            for (int ii = 0; ii < TILE_IPT; ++ii) acc[ii][g] = __builtin_fmaf(h[u], e[ii][u], acc[ii][g]);
         }
       }
     }
 #pragma unroll
-    for (int ii = 0; ii < DIPT; ++ii) {
-      const int q = ps * DIPT + ii;
-      const int l = q * DT + tid;
+    for (int ii = 0; ii < TILE_IPT; ++ii) {
+      const int q = ps * TILE_IPT + ii;
+      const int l = q * TILE_T + tid;
       const int64_t j = c0 + l;
       const bool inb = j >= a.lo && j < a.V;
       const float b = (a.bias && inb) ? a.bias[j] : 0.f;
       const float sc = (a.scale && inb) ? a.scale[j] : 1.f;
       uint32_t m = 0u;
 #pragma unroll
-      for (int g = 0; g < DG; ++g) {
+      for (int g = 0; g < TILE_G; ++g) {
         const bool ex = (bits[g][l >> 5] >> (l & 31)) & 1u;
         const bool ok = inb && s_hoff[g] >= 0 && (!ex || j == s_gt[g]);
         float s = acc[ii][g] + b;
@@ -181,11 +134,11 @@ __global__ __launch_bounds__(DT, 2) void dist_sweep_kernel(DistArgs a) {
 
   // ---- per (row, chunk): the count and the maximum ---------------------------------------------------------------------------
 #pragma unroll
-  for (int g = 0; g < DG; ++g) {
+  for (int g = 0; g < TILE_G; ++g) {
     float mx = -INFINITY;
     int cnt = 0;
 #pragma unroll
-    for (int q = 0; q < DQ; ++q) {
+    for (int q = 0; q < TILE_Q; ++q) {
       const bool ok = (okm[q] >> g) & 1u;
       cnt += __popcll(__ballot(ok));
       if (ok) mx = fmaxf(mx, t[q][g]);
@@ -197,13 +150,13 @@ __global__ __launch_bounds__(DT, 2) void dist_sweep_kernel(DistArgs a) {
 
   // ---- per (row, chunk): S_c, W_c in fp64, a fixed order -------------------------------------------------------------------------
 #pragma unroll
-  for (int g = 0; g < DG; ++g) {
+  for (int g = 0; g < TILE_G; ++g) {
     float mc = s_wm[g][0];
 #pragma unroll
     for (int w = 1; w < DW; ++w) mc = fmaxf(mc, s_wm[g][w]);
     double S = 0.0, W = 0.0;
 #pragma unroll
-    for (int q = 0; q < DQ; ++q) {
+    for (int q = 0; q < TILE_Q; ++q) {
       if (!((okm[q] >> g) & 1u)) continue;
       const float x = t[q][g] - mc;
       const float e = expf(x);
@@ -215,7 +168,7 @@ __global__ __launch_bounds__(DT, 2) void dist_sweep_kernel(DistArgs a) {
     if (lane == 0) { s_wS[g][wave] = S; s_wW[g][wave] = W; }
   }
   __syncthreads();
-  if (tid < DG && lr0 + tid < a.n) {
+  if (tid < TILE_G && lr0 + tid < a.n) {
     const int64_t o = (int64_t)(lr0 + tid) * a.nch + chunk;
     float mc = s_wm[tid][0];
     int n = s_wn[tid][0];
@@ -287,8 +240,8 @@ struct DistQueryArgs {
   int hidden_ld, H, V, lo, E, n, K, n_filters;
 };
 
-__global__ __launch_bounds__(DT) void dist_query_kernel(DistQueryArgs a) {
-  const int64_t i = (int64_t)blockIdx.x * DT + threadIdx.x;
+__global__ __launch_bounds__(TILE_T) void dist_query_kernel(DistQueryArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * TILE_T + threadIdx.x;
   if (i >= (int64_t)a.n * a.K) return;
   const int lr = (int)(i / a.K);
   const int64_t r = a.r0 + lr;
@@ -307,15 +260,14 @@ __global__ __launch_bounds__(DT) void dist_query_kernel(DistQueryArgs a) {
     if (!ok && a.gt && a.gt[r] == q) ok = true;
     const double lse = a.lse[lr];
     if (ok && lse > -INFINITY) {
-      const float t = dist_row_score(a.hidden + hr * a.hidden_ld, a.table + q * a.H, a.bias, a.scale, q, a.H) * a.inv_t;
+      const float t = row_score(a.hidden + hr * a.hidden_ld, a.table + q * a.H, a.bias, a.scale, q, a.H) * a.inv_t;
       out = (float)((double)t - lse);
     }
   }
   a.query_logp[at] = out;
 }
 
-int64_t dist_chunks_of(int32_t V) { return ((int64_t)V + DCH - 1) / DCH; }
-int64_t dist_row_bytes(int32_t V) { return dist_chunks_of(V) * 24 + 8; }   // S, W (double), m (float), n (int32) per chunk | lse
+int64_t dist_row_bytes(int32_t V) { return tile_chunks_of(V) * 24 + 8; }   // S, W (double), m (float), n (int32) per chunk | lse
 
 }  // namespace
 
@@ -344,18 +296,13 @@ extern "C" int b4r_score_dist(const float* hidden, int32_t hidden_ld, const int6
   B4R_CHECK_ARG(K == 0 || !query_logp || query_ids, B4R_E_BADARG, "%s: query_ids is NULL with K = %d", what, K);
   B4R_CHECK_ARG(b4r_aligned16(table), B4R_E_ALIGN, "%s: the table must be 16-byte aligned", what);
   const int64_t per_row = dist_row_bytes(V);
-  const int64_t usable = scratch ? scratch_bytes - (int64_t)((16 - ((uintptr_t)scratch & 15)) & 15) : 0;
-  int64_t group = usable > 0 ? usable / per_row : 0;
-  group = std::min<int64_t>(group, R);
-  if (group < R) group = group / DG * DG;   // whole sweep groups
-  B4R_CHECK_ARG(group >= std::min<int64_t>(R, DG), B4R_E_NOMEM,
+  const int64_t group = tile_group_of(scratch, scratch_bytes, per_row, R, TILE_G);   // whole sweep groups
+  B4R_CHECK_ARG(group >= std::min<int64_t>(R, TILE_G), B4R_E_NOMEM,
                 "%s: scratch of %lld bytes is too small: %lld bytes per row, %d rows at least (b4r_score_dist_scratch_bytes)", what,
-                (long long)scratch_bytes, (long long)per_row, std::min<int32_t>(R, DG));
-  group = std::min<int64_t>(group, 65535LL * DG);
-  const int nch = (int)dist_chunks_of(V);
+                (long long)scratch_bytes, (long long)per_row, std::min<int32_t>(R, TILE_G));
+  const int nch = (int)tile_chunks_of(V);
   B4R_CHECK_ARG(nch <= 65535, B4R_E_SHAPE, "%s: V = %d is too large", what, V);
-  char* p = reinterpret_cast<char*>(((uintptr_t)scratch + 15) & ~(uintptr_t)15);
-  double* c_S = reinterpret_cast<double*>(p);
+  double* c_S = reinterpret_cast<double*>(tile_scratch_base(scratch));
   double* c_W = c_S + group * nch;
   double* lse = c_W + group * nch;
   float* c_m = reinterpret_cast<float*>(lse + group);
@@ -365,13 +312,13 @@ extern "C" int b4r_score_dist(const float* hidden, int32_t hidden_ld, const int6
     const int n = (int)std::min<int64_t>(group, R - r0);
     DistArgs sa{hidden, hidden_row, table, bias, item_scale, exclude, gt, allow_bits, row_filter, c_S, c_W, c_m, c_n, r0,
                 inv_temperature, hidden_ld, H, V, first_item, E, n, nch, n_filters};
-    hipLaunchKernelGGL(dist_sweep_kernel, dim3(b4r_cdiv(n, DG), nch), dim3(DT), 0, s, sa);
+    hipLaunchKernelGGL(dist_sweep_kernel, dim3(b4r_cdiv(n, TILE_G), nch), dim3(TILE_T), 0, s, sa);
     DistMergeArgs ma{c_S, c_W, c_m, c_n, lse, row_n, row_max, row_lse, row_entropy, r0, nch};
     hipLaunchKernelGGL(dist_merge_kernel, dim3(n), dim3(64), 0, s, ma);
     if (K > 0 && query_logp) {
       DistQueryArgs qa{hidden, hidden_row, table, bias, item_scale, exclude, gt, allow_bits, row_filter, query_ids, lse, query_logp,
                        r0, inv_temperature, hidden_ld, H, V, first_item, E, n, K, n_filters};
-      hipLaunchKernelGGL(dist_query_kernel, dim3(b4r_cdiv((int64_t)n * K, DT)), dim3(DT), 0, s, qa);
+      hipLaunchKernelGGL(dist_query_kernel, dim3(b4r_cdiv((int64_t)n * K, TILE_T)), dim3(TILE_T), 0, s, qa);
     }
   }
   B4R_CHECK_LAUNCH(what);

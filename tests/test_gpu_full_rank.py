@@ -226,6 +226,37 @@ def test_rank_full_edges():
     assert lib.b4r_rank_full_scratch_bytes(256, 335423, 100) < 256 * 335423 * 4 // 4
 
 
+@pytest.mark.parametrize("K", (100, 1024))
+def test_rank_full_rows_of_equal_scores(K):
+    """A zero hidden row under a constant bias: every score of the row is the bias, so the 32 score bits are resolved at once
+    (kmin == kmax) and the id bits alone decide: the sweep's two 8-bit passes over the local id (K = 100: each chunk holds more than
+    K) and the merge's four over the id (K = 1024).  17 rows (a
+    second, partly filled tile), three chunks with the last partly beyond V; one row keeps five ids (K beyond the allowed set), one
+    none."""
+    R, H, V = 17, 8, 2049 + 3
+    hidden, table, bias, ex, gt = make_case(R, H, V, seed=77)
+    bias[:] = 0.5
+    hidden[0] = 0.0
+    hidden[16] = 0.0
+    ex_all = np.full((R, V), -1, np.int64)
+    ex_all[:, :ex.shape[1]] = ex
+    ex_all[2, :V - 5] = np.arange(5, V)          # row 2: ids 3 and 4 (of 0 .. 4) are left, and gt
+    ex_all[3] = np.arange(V)                     # row 3: nothing but gt
+    gt[3] = -1
+    sc = oracle_scores(hidden.numpy(), table.numpy(), bias.numpy())
+    assert (sc[0].view(np.uint32) == np.float32(0.5).view(np.uint32)).all() and (sc[16] == sc[0]).all()
+    ok = allowed_mask(V, 3, ex_all, gt)
+    want_ids, want_rank = expected(sc, ok, gt, K)
+    rc, ids, scores, ranks = run_full(hidden.to(DEV), H, table.to(DEV), bias.to(DEV), V, 3, ex_all, gt, K)
+    assert rc == 0, _lib.last_error()
+    assert np.array_equal(ids, want_ids) and np.array_equal(ranks, want_rank)
+    valid = ids >= 0
+    assert np.array_equal(scores[valid].view(np.uint32), sc[np.nonzero(valid)[0], ids[valid]].view(np.uint32))
+    assert (scores[~valid] == -np.inf).all()
+    assert (np.diff(ids[0]) > 0).all() and valid[0].all()          # equal scores: ascending ids
+    assert valid[2].sum() == ok[2].sum() <= 3 and not valid[3].any()
+
+
 def test_recommend_tensor_against_op_and_oracle():
     V = 300
     model = make_model(V, seed=17)

@@ -183,6 +183,27 @@ def test_rank_joint_against_the_restatement(R, H, V, NP, M, K):
         assert any(ids[p, i] < 1024 <= ids[p, i + 1] for p, i in tied), "no tie across the chunk boundary"
 
 
+@pytest.mark.parametrize("K", (100, 1024))
+def test_parties_of_equal_aggregates(K):
+    """A party of zero hidden rows without bias, scale or row_lse: every aggregate is +0.0 in every mode, so the 32 score bits are
+    resolved at once (kmin == kmax) and the id bits alone decide: the sweep's two 8-bit passes over the local id (K = 100: each chunk
+    holds more than K) and the merge's four over the id (K = 1024).  M = 3 (slots of four, one absent), five parties (a second, partly filled tile), three chunks, the last partly beyond V."""
+    key = (17, 8, 2049 + FIRST, 5, 3)
+    c = dict(planted(*key))
+    c["hidden"] = c["hidden"].copy()
+    c["hidden"][:3] = 0.0
+    assert c["parties"][0].tolist() == [0, 1, 2]
+    t, ok = jr.row_quantities(c["hidden"], c["table"], None, None, 1.0, FIRST, c["ex"], None, None)
+    assert (t[:3].view(np.uint32) == 0).all()
+    for mode in MODES:
+        rc, got = run_joint(c, mode, K, None, 1.0, False, False, False, c["weights"])
+        assert rc == 0, _lib.last_error()
+        want = jr.rank_joint(t, ok, c["parties"], mode, K, None, c["weights"])
+        assert_equals_ref(got, want, f"mode {mode}")
+        n0 = int(want[2][0])
+        assert n0 > 1024 and (np.diff(got["ids"][0]) > 0).all() and (got["scores"][0].view(np.uint32) == 0).all()
+
+
 def test_null_outputs_and_weights_are_ignored_outside_the_additive_mode():
     key = (9, 32, 1027, 9, 3)
     c = planted(*key)
