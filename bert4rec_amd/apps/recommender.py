@@ -31,7 +31,11 @@ category, is removed at a time on the device (b4r_occlude_rows), the model runs 
 recommendation the most log probability come back as its reasons (b4r_attribution_select).
 
 audience turns the question round: given items, which users?  The users go through the model in batches, and the k most likely users
-of every item, its reach and its expected demand are kept on the device while the batches go by (b4r_audience_merge)."""
+of every item, its reach and its expected demand are kept on the device while the batches go by (b4r_audience_merge).
+
+category_affinity gives each user's probability of picking from every category next (b4r_group_mass: the catalogue softmax summed
+per item group on the device, no [users, V] probabilities); category_audience is `audience` with categories in place of items, and
+recommend_shelves returns the categories a user is most likely to pick from, each with its best items."""
 import numbers
 
 import numpy as np
@@ -459,6 +463,127 @@ class Recommender:
         reach_h, demand_h = both[:, 2 * k].tolist(), both[:, 2 * k + 1].tolist()
         return [{"users": [(names[u], p) for u, p in zip(users_h[j], prob_h[j]) if u >= 0], "reach": int(reach_h[j]),
                  "expected_demand": demand_h[j] / engine_mod.AUDIENCE_DEMAND_ONE} for j in range(len(items))]
+
+    def _affinity_labels(self, by_group):
+        """by_group (as _group_labels takes it) -> (labels int32 [V], the number of groups G, the name of each group or None)"""
+        labels, names = self._group_labels(by_group)
+        labels, G = engine_mod.check_item_group_labels(labels, self.model.vocab_size, None if names is None else (len(names) or None))
+        return labels, G, names
+
+    def category_affinity(self, sequences, by_group, top=None, allowed_items=None, temperature: float = 1.0) -> list:
+        """P(next item is of category c | user) for every sequence: which shelf to show first, what share of a user's taste a genre
+        holds (BERT4RecModel.group_affinity_tensor: one batched forward, two sweeps over the catalogue, no [users, V] probabilities,
+        one read-back).  by_group: a mapping (or a callable) from an item to its label, or one integer label per token id [V], as
+        explain_batch takes it.  The probabilities are over the items the user could be served: not the items of their own
+        sequence, and with allowed_items only those.  Returns per sequence [(label, probability), ...], best first (ties in the order
+        the labels first appear), the `top` best when given; a category the user can be served nothing of is left out.  The
+        probabilities of one user sum to at most 1: the rest belongs to the items without a label."""
+        engine_mod.check_temperature(temperature)
+        if top is not None:
+            top = engine_mod._int_in(top, 1, engine_mod.GROUP_MASS_MAX_G, "top")
+        sequences = [list(seq) for seq in sequences]
+        allow, _ = self._allow_filters(len(sequences), allowed_items, None)
+        labels, G, names = self._affinity_labels(by_group)
+        if not sequences:
+            return []
+        batch, exclude = self._requests(sequences)
+        got = self.model.group_affinity_tensor(batch, labels, G, exclude_seen=False, exclude=exclude, allow=allow, temperature=temperature)
+        both = torch.cat([got["group_mass"], got["group_n"].to(torch.int64), got["slot_index"][:, None]], dim=1).cpu()
+        return self._affinity_lists(both[:, :G], both[:, G:2 * G], both[:, 2 * G], int(batch["masked_lm_positions"].shape[1]),
+                                    len(sequences), names, top)
+
+    @staticmethod
+    def _affinity_lists(mass, n, slots, P: int, n_users: int, names, top) -> list:
+        """category_affinity's lists from the host copies of group_mass / group_n [R, G] and slot_index [R]: a user's first ranked slot
+        counts, groups with n = 0 are dropped, the order is mass descending with ties to the lower group index."""
+        first = {}
+        for i, s in enumerate(slots.tolist()):
+            first.setdefault(s // P, i)
+        out = []
+        for b in range(n_users):
+            if b not in first:
+                out.append([])
+                continue
+            m, c = mass[first[b]].tolist(), n[first[b]].tolist()
+            order = sorted((g for g in range(len(m)) if c[g] > 0), key=lambda g: (-m[g], g))
+            out.append([(g if names is None else names[g], m[g] / engine_mod.GROUP_MASS_ONE) for g in order[:top]])
+        return out
+
+    def category_audience(self, by_group, sequences, k: int = 100, min_probability=None, user_ids=None, batch_size: int = 256,
+                          allowed_items=None, allowed_items_per_user=None, temperature: float = 1.0) -> list:
+        """Given categories, which users?  `audience` with the categories of by_group in place of single items: for every category
+        the k users most likely to take one of its items next, its reach and its expected demand -- the users of a genre campaign.
+        The users go through the model in batches of batch_size (BERT4RecModel.group_audience_tensor) and the result is read back
+        once; it does not depend on batch_size.  by_group: as category_affinity takes it; the other arguments are `audience`'s.
+        Returns one dict per category, in the order the labels first appear (or by integer label): {"label", "users": [(user,
+        probability), ...] best first, "reach", "expected_demand"}."""
+        engine_mod.check_temperature(temperature)
+        k, _ = engine_mod.check_audience_args(k, min_probability)
+        batch_size = engine_mod._int_in(batch_size, 1, (1 << 31) - 1, "batch_size")
+        sequences = [list(seq) for seq in sequences]
+        names = list(range(len(sequences))) if user_ids is None else list(user_ids)
+        if len(names) != len(sequences):
+            raise ValueError(f"{len(names)} user ids for {len(sequences)} sequences")
+        allow, user_filter = self._allow_filters(len(sequences), allowed_items, allowed_items_per_user)
+        labels, G, group_names = self._affinity_labels(by_group)
+        if allow is not None:
+            allow = engine_mod.pack_item_filter(allow).to(self.model.engine.params.device)   # packed once, for every batch
+        state = None
+        for b0 in range(0, len(sequences), batch_size):
+            batch, exclude = self._requests(sequences[b0:b0 + batch_size])
+            row_filter = None if user_filter is None else user_filter[b0:b0 + batch_size]
+            state = self.model.group_audience_tensor(batch, labels, G, state=state, k=k, user_ids=torch.arange(b0, b0 + len(exclude)),
+                                                     min_probability=min_probability, exclude_seen=False, exclude=exclude,
+                                                     allow=allow, row_filter=row_filter, temperature=temperature)
+        if state is None:
+            return [{"label": g if group_names is None else group_names[g], "users": [], "reach": 0, "expected_demand": 0.0}
+                    for g in range(G)]
+        both = torch.cat([state["users"], torch.exp(state["logp"].to(torch.float64)).view(torch.int64), state["reach"][:, None],
+                          state["demand"][:, None]], dim=1).cpu()
+        users_h = both[:, :k].tolist()
+        prob_h = both[:, k:2 * k].contiguous().view(torch.float64).tolist()
+        reach_h, demand_h = both[:, 2 * k].tolist(), both[:, 2 * k + 1].tolist()
+        return [{"label": g if group_names is None else group_names[g],
+                 "users": [(names[u], p) for u, p in zip(users_h[g], prob_h[g]) if u >= 0], "reach": int(reach_h[g]),
+                 "expected_demand": demand_h[g] / engine_mod.AUDIENCE_DEMAND_ONE} for g in range(G)]
+
+    def recommend_shelves(self, sequences, by_group, shelves: int = 3, k: int = 10, allowed_items=None, temperature: float = 1.0) -> list:
+        """A page per user: the `shelves` categories the user is most likely to pick from next, each with its k best items
+        (BERT4RecModel.recommend_shelves_tensor: one batched forward, the categories' item filters built once, ONE full-catalogue
+        top-k over the users x shelves rows, one read-back).  by_group: as category_affinity takes it, at most 1024 categories.
+        Each shelf's items are what recommend_batch returns with that category as the allow-list.  Returns per sequence
+        [(label, probability, [item, ...]), ...], best category first; a user with fewer categories to be served from gets fewer
+        shelves."""
+        engine_mod.check_temperature(temperature)
+        sequences = [list(seq) for seq in sequences]
+        allow, _ = self._allow_filters(len(sequences), allowed_items, None)
+        labels, G, names = self._affinity_labels(by_group)
+        shelves, k = engine_mod.check_shelf_args(shelves, k, G)
+        if not sequences:
+            return []
+        tokenizer = self.dataloader.get_tokenizer()
+        batch, exclude = self._requests(sequences)
+        group, mass, ids, _, slots = self.model.recommend_shelves_tensor(batch, labels, G, shelves=shelves, k=k, exclude_seen=False,
+                                                                         exclude=exclude, allow=allow, temperature=temperature)
+        R = int(slots.numel())
+        both = torch.cat([group, mass, ids.reshape(R, shelves * k), slots[:, None]], dim=1).cpu()   # everything in one copy
+        group_h, mass_h = both[:, :shelves].tolist(), both[:, shelves:2 * shelves].tolist()
+        ids_h = both[:, 2 * shelves:2 * shelves + shelves * k].reshape(R, shelves, k).tolist()
+        P = int(batch["masked_lm_positions"].shape[1])
+        first = {}
+        for i, s in enumerate(both[:, -1].tolist()):
+            first.setdefault(s // P, i)
+        out = []
+        for b in range(len(sequences)):
+            page = []
+            for s in range(shelves if b in first else 0):
+                g = group_h[first[b]][s]
+                if g < 0:
+                    continue
+                items = tokenizer.detokenize([i for i in ids_h[first[b]][s] if i >= 0])
+                page.append((g if names is None else names[g], mass_h[first[b]][s] / engine_mod.GROUP_MASS_ONE, items))
+            out.append(page)
+        return out
 
     def recommend_together(self, parties, k: int = 10, strategy: str = "additive", weights=None, min_member_probability=None,
                            allowed_items=None, return_members: bool = False) -> list:

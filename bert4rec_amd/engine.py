@@ -346,6 +346,59 @@ def check_audience_state(state, item_ids: torch.Tensor, k: int) -> None:
         raise ValueError(f"this state keeps k = {int(state['users'].shape[-1])} users per item, not {k}")
 
 
+GROUP_MASS_MAX_G = 65536         # b4r_group_mass: G
+GROUP_MASS_MAX_V = 1 << 22       # b4r_group_mass: V
+GROUP_MASS_ONE = AUDIENCE_DEMAND_ONE   # probability 1 in the units of `group_mass`
+
+
+def check_item_group_labels(item_groups, vocab_size: int, n_groups=None) -> Tuple[torch.Tensor, int]:
+    """The labels of a category affinity, checked without a GPU: item_groups is [V] int32 / int64 (a tensor, an array or a list), one
+    label per token id; a negative label means no group.  n_groups None: the largest label + 1 (ValueError when no item has a
+    group); else an integer in [1, 65536], and a label >= n_groups counts as no group too (its mass is reported as `rest`).
+    Returns (labels int32 [V] on the host, n_groups)."""
+    t = torch.as_tensor(item_groups)
+    if t.ndim != 1 or t.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"item_groups are int32 / int64 labels [V], got {t.dtype} of shape {tuple(t.shape)}")
+    if int(t.numel()) != int(vocab_size):
+        raise ValueError(f"item_groups holds {int(t.numel())} labels for a vocabulary of {int(vocab_size)}")
+    if vocab_size > GROUP_MASS_MAX_V:
+        raise ValueError(f"group sums take a vocabulary of at most {GROUP_MASS_MAX_V} items, got {vocab_size}")
+    t = t.detach().cpu()
+    top = int(t.max()) if t.numel() else -1
+    if top > (1 << 31) - 1:
+        raise ValueError(f"a label must fit int32, got {top}")
+    if n_groups is None:
+        if top < 0:
+            raise ValueError("no item has a group: every label is negative")
+        n_groups = top + 1
+    n_groups = _int_in(n_groups, 1, GROUP_MASS_MAX_G, "n_groups")
+    return t.clamp(min=-1).to(torch.int32).contiguous(), n_groups
+
+
+SHELF_MAX_GROUPS = 1024          # recommend_shelves: one item filter of V / 32 words per group
+
+
+def check_shelf_args(shelves, k, n_groups: int) -> Tuple[int, int]:
+    """(shelves, k) of a shelf recommendation: 1 <= shelves <= n_groups <= 1024 groups (one item filter per group), 1 <= k <= 1024."""
+    if n_groups > SHELF_MAX_GROUPS:
+        raise ValueError(f"shelves take at most {SHELF_MAX_GROUPS} groups (one item filter per group), got {n_groups}")
+    return _int_in(shelves, 1, n_groups, "shelves"), _int_in(k, 1, RANK_FULL_MAX_K, "k")
+
+
+def pack_group_filters(labels: torch.Tensor, n_groups: int, allow=None) -> torch.Tensor:
+    """The item filters of a shelf recommendation, packed as pack_item_filter packs them: uint32 [n_groups + 1, ceil(V / 32)], filter
+    g = the items labelled g (check_item_group_labels' labels) that the bool mask `allow` [V] admits (None: all of them), and the
+    last filter admits nothing: the filter of a shelf that does not exist."""
+    lab = labels.to(torch.int64)
+    if allow is not None:
+        lab = torch.where(torch.as_tensor(allow).to(device=lab.device, dtype=torch.bool), lab, torch.full_like(lab, -1))
+    packed = []
+    for g0 in range(0, n_groups + 1, 64):   # 64 filters at a time: the packing works on one int64 per (filter, item)
+        g = torch.arange(g0, min(g0 + 64, n_groups + 1), dtype=torch.int64, device=lab.device)
+        packed.append(pack_item_filter((lab[None, :] == g[:, None]) & (g[:, None] < n_groups)).view(torch.int32))
+    return torch.cat(packed, dim=0).view(torch.uint32)
+
+
 JOINT_MAX_MEMBERS = 16    # b4r_rank_joint: M
 JOINT_STRATEGIES = {"additive": _lib.JOINT_ADDITIVE, "least_misery": _lib.JOINT_LEAST_MISERY, "most_pleasure": _lib.JOINT_MOST_PLEASURE}
 
@@ -1383,6 +1436,40 @@ class Engine:
         ld = int(logp.stride(0)) if R > 1 else Q
         _lib.check(self.lib.b4r_audience_merge(_ptr(logp), ld, R, Q, _ptr(user_ids), check_stream0(user0), float(min_logp), K, _ptr(users),
                                                _ptr(best_logp), _ptr(reach), _ptr(demand), _stream(self.device)), "b4r_audience_merge")
+
+    def group_mass(self, hidden: torch.Tensor, rows: Optional[torch.Tensor], exclude: Optional[torch.Tensor], first_item: int,
+                   row_lse: torch.Tensor, item_groups, n_groups=None, allow=None, row_filter=None, temperature: float = 1.0):
+        """b4r_group_mass on `hidden` (rank_full's hidden / rows / exclude / first_item / allow / row_filter: the same scores and the
+        same allowed set per row): the probability mass of every item group under each row's catalogue softmax, without [R, V]
+        scores.  row_lse [R] fp64: score_distribution's lse of the same rows at the same temperature.  item_groups / n_groups:
+        check_item_group_labels (an int32 tensor [V] already on the device is taken as it is; n_groups is then required).
+        Returns (group_mass [R, G] int64 in units of 2^-40, group_n [R, G] int32: the allowed items of each group, rest_mass [R]
+        int64, rest_n [R] int32: the same for the allowed items without a group).  Integer sums: the bits do not depend on the
+        order of the rows or the batching.  A row with row_lse = -inf (nothing allowed) is all zeros."""
+        inv_t = check_temperature(temperature)
+        V = self.cfg.vocab_size
+        lab = item_groups
+        if torch.is_tensor(lab) and lab.is_cuda and lab.dtype == torch.int32 and tuple(lab.shape) == (V,) and n_groups is not None:
+            G, lab_d = _int_in(n_groups, 1, GROUP_MASS_MAX_G, "n_groups"), lab.contiguous()
+        else:
+            lab, G = check_item_group_labels(lab, V, n_groups)
+            lab_d = lab.to(self.device)
+        R = int(rows.numel()) if rows is not None else int(hidden.shape[0])
+        if not torch.is_tensor(row_lse) or row_lse.dtype != torch.float64 or tuple(row_lse.shape) != (R,):
+            raise ValueError(f"row_lse must be a float64 tensor [{R}], got {getattr(row_lse, 'dtype', type(row_lse))} of shape "
+                             f"{tuple(getattr(row_lse, 'shape', ()))}")
+        R, sweep, filt, keep = self._sweep_rows(hidden, rows, exclude, first_item, None, allow, row_filter)
+        dev = self.device
+        mass = torch.empty((R, G), dtype=torch.int64, device=dev)
+        n = torch.empty((R, G), dtype=torch.int32, device=dev)
+        rest_mass = torch.empty((R,), dtype=torch.int64, device=dev)
+        rest_n = torch.empty((R,), dtype=torch.int32, device=dev)
+        if R == 0:
+            return mass, n, rest_mass, rest_n
+        lse_d = row_lse.to(dev).contiguous()
+        _lib.check(self.lib.b4r_group_mass(*sweep[:11], *filt, inv_t, _ptr(lse_d), _ptr(lab_d), G, _ptr(mass), _ptr(n), _ptr(rest_mass),
+                                           _ptr(rest_n), _stream(dev)), "b4r_group_mass")
+        return mass, n, rest_mass, rest_n
 
     def item_neighbours(self, item_ids: torch.Tensor, k: int, metric: str = "cosine", first_item: int = SPECIAL_IDS, allow=None,
                         row_filter=None):

@@ -779,10 +779,30 @@ class BERT4RecModel:
         item_ids = engine_mod.check_audience_items(item_ids)
         if state is not None:
             engine_mod.check_audience_state(state, item_ids, k)
+        B, P, slot, user_ids, allow, row_filter = self._audience_batch("audience_tensor", encoder_input, user_ids, allow, row_filter)
+        if state is None:
+            state = self.engine.audience_state(item_ids, k)
+        if B == 0:
+            return state
+        hidden, ex_rows, user_ids, user0 = self._audience_rows(encoder_input, B, P, slot, exclude_seen, exclude, user_ids, state)
+        Q = int(item_ids.numel())
+        for c0 in range(0, Q, engine_mod.RANK_FULL_MAX_K):
+            c1 = min(Q, c0 + engine_mod.RANK_FULL_MAX_K)
+            queries = state["query_ids"][c0:c1].unsqueeze(0).expand(B, c1 - c0)
+            logp = self.engine.score_distribution(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, allow, row_filter, temperature,
+                                                  queries)[4]
+            self.engine.audience_merge(logp, state["users"][c0:c1], state["logp"][c0:c1], state["reach"][c0:c1], state["demand"][c0:c1],
+                                       user_ids, user0, min_logp)
+        return state
+
+    def _audience_batch(self, caller: str, encoder_input, user_ids, allow, row_filter):
+        """The checks of an audience batch that need no forward: prepare_inference's format with exactly one ranked slot per row,
+        user_ids [B], allow / row_filter.  Returns (B, P, the ranked slot of every row [B] int64 on the host side of the weights,
+        user_ids int64 [B] or None, packed allow or None, row_filter or None)."""
         tokens_in = encoder_input.get("input_word_ids") if hasattr(encoder_input, "get") else None
         positions = encoder_input.get("masked_lm_positions") if tokens_in is not None else None
         if tokens_in is None or positions is None or torch.as_tensor(tokens_in).ndim != 2 or torch.as_tensor(positions).ndim != 2:
-            raise ValueError("audience_tensor takes prepare_inference's batch: input_word_ids [B, L] and masked_lm_positions [B, P]")
+            raise ValueError(f"{caller} takes prepare_inference's batch: input_word_ids [B, L] and masked_lm_positions [B, P]")
         B, P = int(torch.as_tensor(tokens_in).shape[0]), int(torch.as_tensor(positions).shape[1])
         weights = encoder_input.get("masked_lm_weights")
         if weights is None:
@@ -797,13 +817,20 @@ class BERT4RecModel:
         if user_ids is not None:
             user_ids = engine_mod.check_sample_streams(user_ids, B)   # [B] integers -> int64
         allow, row_filter = engine_mod.check_item_filter(allow, row_filter, self.vocab_size)
+        return B, P, slot, user_ids, allow, row_filter
+
+    def _audience_rows(self, encoder_input, B: int, P: int, slot: torch.Tensor, exclude_seen: bool, exclude, user_ids, state,
+                       forward_rows: Optional[int] = None):
+        """The forward of an audience batch (B >= 1) and the names of its rows.  Returns (hidden [B, H], exclude rows or None,
+        user_ids on the device or None, user0: the id of row 0 when the rows are unnamed; state["next_user"] then advances).
+        forward_rows: None = one forward over the batch as it comes; else _hidden_in_blocks of that many rows, placed by user id."""
         dev = self.device
-        if state is None:
-            state = self.engine.audience_state(item_ids, k)
-        if B == 0:
-            return state
         slots = torch.arange(B, dtype=torch.int64, device=dev) * P + slot.to(dev)
-        hidden, slots, _ = self._ranked_slot_hidden(encoder_input, slots=slots)
+        if forward_rows is None:
+            hidden, slots, _ = self._ranked_slot_hidden(encoder_input, slots=slots)
+        else:
+            users = user_ids.cpu() if user_ids is not None else int(state["next_user"]) + torch.arange(B, dtype=torch.int64)
+            hidden = self._hidden_in_blocks(encoder_input, B, P, slot, forward_rows, users)
         ex_rows = self._excluded_rows(encoder_input, slots, exclude_seen, exclude)
         user0 = 0
         if user_ids is None:
@@ -811,14 +838,160 @@ class BERT4RecModel:
             state["next_user"] = user0 + B
         else:
             user_ids = user_ids.to(dev).contiguous()
-        Q = int(item_ids.numel())
-        for c0 in range(0, Q, engine_mod.RANK_FULL_MAX_K):
-            c1 = min(Q, c0 + engine_mod.RANK_FULL_MAX_K)
-            queries = state["query_ids"][c0:c1].unsqueeze(0).expand(B, c1 - c0)
-            logp = self.engine.score_distribution(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, allow, row_filter, temperature,
-                                                  queries)[4]
-            self.engine.audience_merge(logp, state["users"][c0:c1], state["logp"][c0:c1], state["reach"][c0:c1], state["demand"][c0:c1],
-                                       user_ids, user0, min_logp)
+        return hidden, ex_rows, user_ids, user0
+
+    # ---- category affinity --------------------------------------------------------------------------------------------------
+    def _group_affinity(self, hidden, ex_rows, labels_d: torch.Tensor, G: int, allow, row_filter, temperature):
+        """One b4r_score_dist sweep for the rows' normalisers and one b4r_group_mass: group_affinity_tensor's dict without slot_index."""
+        n, _, lse, _, _ = self.engine.score_distribution(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, allow, row_filter, temperature)
+        mass, gn, rest_mass, rest_n = self.engine.group_mass(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, lse, labels_d, G, allow,
+                                                             row_filter, temperature)
+        logp = torch.log(mass.to(torch.float64) * (1.0 / engine_mod.GROUP_MASS_ONE)).to(torch.float32)   # log(0) = -inf
+        return {"group_mass": mass, "group_n": gn, "group_logp": logp, "rest_mass": rest_mass, "rest_n": rest_n, "row_lse": lse,
+                "row_n": n}
+
+    def group_affinity_tensor(self, encoder_input: Dict[str, torch.Tensor], item_groups, n_groups=None, exclude_seen: bool = True,
+                              exclude: Optional[torch.Tensor] = None, allow=None, row_filter=None, temperature: float = 1.0):
+        """P(next item in group g | user) for every ranked slot and every item group: the sum of the catalogue softmax over the items
+        of the group the slot could be served -- score_distribution_tensor's forward, exclusions, filter and temperature -- from one
+        b4r_score_dist sweep (the normalisers) and one b4r_group_mass sweep: no [R, V] probabilities anywhere.
+        item_groups: int32 / int64 [V], one label per token id, negative = no group; n_groups: None = the largest label + 1, at most
+        65536; a label >= n_groups counts as no group (engine.check_item_group_labels).  Returns a dict of device tensors:
+          group_mass  int64 [R, G]: the mass of each group in units of 2^-40 (engine.GROUP_MASS_ONE = probability 1), an integer sum
+                      of the items' rounded probabilities: it does not depend on the order of the rows or on the batching
+          group_n     int32 [R, G]: the items of the group the slot could be served
+          group_logp  float32 [R, G]: fl32(log(group_mass * 2^-40)), -inf where the mass is 0
+          rest_mass / rest_n  int64 / int32 [R]: the same for the items without a group; sum(group_n) + rest_n = row_n
+          row_lse     float64 [R], row_n int32 [R]: score_distribution_tensor's lse and n
+          slot_index  int64 [R]: b*P+p, as recommend_tensor returns it
+        Resolution: one unit is 2^-40 (9.1e-13).  Every item's probability is rounded to a whole number of units, so a mass is off by
+        up to half a unit per item of the group: a group whose mass is below about 1e-9 holds few units, and a group whose items all
+        lie below 2^-41 reads 0 (group_logp = -inf) while group_n > 0."""
+        engine_mod.check_temperature(temperature)
+        labels, G = engine_mod.check_item_group_labels(item_groups, self.vocab_size, n_groups)
+        allow, row_filter = engine_mod.check_item_filter(allow, row_filter, self.vocab_size)
+        hidden, slots, _ = self._ranked_slot_hidden(encoder_input)
+        dev = self.device
+        if hidden is None:
+            z = lambda dt, *shape: torch.empty(shape, dtype=dt, device=dev)
+            return {"group_mass": z(torch.int64, 0, G), "group_n": z(torch.int32, 0, G), "group_logp": z(torch.float32, 0, G),
+                    "rest_mass": z(torch.int64, 0), "rest_n": z(torch.int32, 0), "row_lse": z(torch.float64, 0),
+                    "row_n": z(torch.int32, 0), "slot_index": slots}
+        ex_rows = self._excluded_rows(encoder_input, slots, exclude_seen, exclude)
+        out = self._group_affinity(hidden, ex_rows, labels.to(dev), G, allow, row_filter, temperature)
+        out["slot_index"] = slots
+        return out
+
+    def recommend_shelves_tensor(self, encoder_input: Dict[str, torch.Tensor], item_groups, n_groups=None, shelves: int = 3, k: int = 10,
+                                 exclude_seen: bool = True, exclude: Optional[torch.Tensor] = None, allow=None,
+                                 temperature: float = 1.0):
+        """A page of shelves for every ranked slot: the `shelves` item groups with the largest affinity ("Top in Horror" before "Top in
+        Comedy" for this user), each with its k best items.  A composition: group_affinity_tensor's two sweeps, the choice of the
+        groups on the device (mass descending, ties to the lower group; a group with group_n = 0 is never a shelf), and ONE
+        b4r_rank_full_ex call over the R * shelves rows, each pointing at its slot's hidden row and at its group's item filter
+        (engine.pack_group_filters, built once per call).  allow: None or one bool / uint8 mask [V] for all rows.  At most 1024 groups.
+        Returns (shelf_group [R, shelves] int64: the group of each shelf, -1 where the slot has fewer groups to be served from;
+        shelf_mass [R, shelves] int64 in units of 2^-40; ids [R, shelves, k] int64 and scores [R, shelves, k] fp32: b4r_rank_full's
+        within the group, -1 / -inf in the tail; slot_index [R]), on the device: nothing is read back here."""
+        engine_mod.check_temperature(temperature)
+        labels, G = engine_mod.check_item_group_labels(item_groups, self.vocab_size, n_groups)
+        shelves, k = engine_mod.check_shelf_args(shelves, k, G)
+        if allow is not None:
+            allow = torch.as_tensor(allow)
+            if allow.dtype not in (torch.bool, torch.uint8) or tuple(allow.shape) != (self.vocab_size,):
+                raise ValueError(f"allow is one bool / uint8 mask [{self.vocab_size}] here, got {allow.dtype} of shape {tuple(allow.shape)}")
+        hidden, slots, _ = self._ranked_slot_hidden(encoder_input)
+        dev = self.device
+        R = int(slots.numel())
+        if hidden is None:
+            return (torch.empty((0, shelves), dtype=torch.int64, device=dev), torch.empty((0, shelves), dtype=torch.int64, device=dev),
+                    torch.empty((0, shelves, k), dtype=torch.int64, device=dev), torch.empty((0, shelves, k), dtype=torch.float32, device=dev),
+                    slots)
+        labels_d = labels.to(dev)
+        filters = engine_mod.pack_group_filters(labels_d, G, None if allow is None else allow.to(dev))   # [G + 1, W]: built once
+        ex_rows = self._excluded_rows(encoder_input, slots, exclude_seen, exclude)
+        aff = self._group_affinity(hidden, ex_rows, labels_d, G, None if allow is None else allow, None, temperature)
+        key = torch.where(aff["group_n"] > 0, aff["group_mass"], torch.full_like(aff["group_mass"], -1))
+        mass, group = torch.sort(key, dim=1, descending=True, stable=True)       # ties keep the lower group first
+        mass, group = mass[:, :shelves], group[:, :shelves]
+        group = torch.where(mass >= 0, group, torch.full_like(group, -1))
+        rows = torch.arange(R, dtype=torch.int64, device=dev).repeat_interleave(shelves)
+        row_filter = torch.where(group >= 0, group, torch.full_like(group, G)).reshape(-1).to(torch.int32)   # G: the empty filter
+        ex = None if ex_rows is None else ex_rows.repeat_interleave(shelves, dim=0)
+        ids, scores, _ = self.engine.rank_full(hidden, rows, ex, engine_mod.SPECIAL_IDS, None, k, filters, row_filter)
+        return group, mass.clamp(min=0), ids.reshape(R, shelves, k), scores.reshape(R, shelves, k), slots
+
+    def _hidden_in_blocks(self, encoder_input, B: int, P: int, slot: torch.Tensor, block: int, users: torch.Tensor) -> torch.Tensor:
+        """_ranked_slot_hidden of a one-slot-per-row batch whose rows are named by users [B] (int64, host), such that a user's hidden
+        state has the same bits in whatever batch the user comes.  Two things stand in the way otherwise: the
+        encoder takes another launch form at another row count, and in the hidden-64 kernels, which work on tiles of 32 rows, a row's
+        last bits follow its place in the tile.  So the forward runs on blocks of exactly `block` rows and user u always sits at
+        place u mod block of a block (rows that share a place go to successive blocks; the empty places hold copies of row 0, which
+        are dropped).  What a row shares its block with does not matter.  Consecutive ids fill the blocks without gaps.
+        Returns hidden [B, H]."""
+        dev = self.device
+        tensors = {key: torch.as_tensor(v) for key, v in encoder_input.items() if v is not None}
+        place = torch.remainder(users, block)
+        order = torch.argsort(place, stable=True)
+        run_start = torch.searchsorted(place[order], place[order])           # where the rows of the same place begin, in that order
+        nth = torch.empty(B, dtype=torch.int64)
+        nth[order] = torch.arange(B) - run_start                             # row r is the nth[r]-th of its place, in row order
+        at = nth * block + place
+        n_blocks = int(nth.max()) + 1
+        src = torch.zeros(n_blocks * block, dtype=torch.int64)
+        src[at] = torch.arange(B)
+        parts = []
+        for j in range(n_blocks):
+            idx = src[j * block:(j + 1) * block]
+            part = {key: v[idx.to(v.device)] if v.ndim >= 1 and v.shape[0] == B else v for key, v in tensors.items()}
+            slots = torch.arange(block, dtype=torch.int64, device=dev) * P + slot[idx.to(slot.device)].to(dev)
+            hidden, _, _ = self._ranked_slot_hidden(part, slots=slots)
+            parts.append(hidden.clone())                   # (the next block's forward reuses the buffers)
+        return torch.cat(parts, dim=0)[at.to(dev)]
+
+    def group_audience_tensor(self, encoder_input: Dict[str, torch.Tensor], item_groups, n_groups, state=None, k: int = 100, user_ids=None,
+                              min_probability=None, exclude_seen: bool = True, exclude: Optional[torch.Tensor] = None, allow=None,
+                              row_filter=None, temperature: float = 1.0, forward_rows: Optional[int] = 256):
+        """Given item groups, which users?  audience_tensor with the G groups in place of the Q items: one batch of users is merged
+        into the k users most likely to take an item of each group next.  group_affinity_tensor's group_logp [B, G] goes straight into
+        b4r_audience_merge.  state: None creates one; else what an earlier call returned for the same n_groups and k.  The dict is
+        audience_tensor's (users, logp [G, k]; reach, demand [G]; item_ids holds the group indices 0 .. G-1), plus "labels": the
+        labels on the device, uploaded once.  Later calls must bring the same item_groups.
+        The state depends only on the set of (user, group_logp) pairs, and group_logp comes from integer sums over a fixed-order
+        normaliser: given a user's hidden state it does not depend on the batch the user came in.
+        forward_rows (default 256): the encoder runs on blocks of exactly that many rows with user u at place u mod forward_rows of
+        its block (the places left empty hold copies of a row), so that it takes the same launch form at every batch size and a row
+        keeps its place in the kernels' row tiles: a user's hidden state does not depend on the batch either.  The state is then the
+        same in every bit however the users are cut into calls and in whatever order the calls arrive; the price is the padding (a
+        call with one user costs a forward of forward_rows; consecutive ids fill the blocks without gaps) and a host copy of
+        user_ids.  None: one forward over the batch as it comes, audience_tensor's way: the same batches in another order give the
+        same bits, other batch sizes may differ in a log probability's last bits.
+        A user who can be served nothing of a group has -inf there and is never in that group's audience.  demand [G] sums
+        llrint(exp(group_logp) * 2^40) over the users: the expected number of users whose next item is of the group."""
+        engine_mod.check_temperature(temperature)
+        k, min_logp = engine_mod.check_audience_args(k, min_probability)
+        if forward_rows is not None:
+            forward_rows = engine_mod._int_in(forward_rows, 1, 1 << 20, "forward_rows")
+        if n_groups is None:
+            raise ValueError("n_groups names the groups of the state: give it")
+        if state is None or state.get("labels") is None:
+            labels, G = engine_mod.check_item_group_labels(item_groups, self.vocab_size, n_groups)
+        else:
+            labels, G = None, engine_mod._int_in(n_groups, 1, engine_mod.GROUP_MASS_MAX_G, "n_groups")
+        group_ids = torch.arange(G, dtype=torch.int64)
+        if state is not None:
+            engine_mod.check_audience_state(state, group_ids, k)
+        B, P, slot, user_ids, allow, row_filter = self._audience_batch("group_audience_tensor", encoder_input, user_ids, allow, row_filter)
+        if state is None:
+            state = self.engine.audience_state(group_ids, k)
+        if state.get("labels") is None:
+            state["labels"] = labels.to(self.device)
+        if B == 0:
+            return state
+        hidden, ex_rows, user_ids, user0 = self._audience_rows(encoder_input, B, P, slot, exclude_seen, exclude, user_ids, state,
+                                                               forward_rows)
+        logp = self._group_affinity(hidden, ex_rows, state["labels"], G, allow, row_filter, temperature)["group_logp"]
+        self.engine.audience_merge(logp, state["users"], state["logp"], state["reach"], state["demand"], user_ids, user0, min_logp)
         return state
 
     def recommend_joint_tensor(self, encoder_input: Dict[str, torch.Tensor], parties, k: int = 10, strategy: str = "additive", weights=None,

@@ -654,6 +654,38 @@ int b4r_rank_joint(const float* hidden, int32_t hidden_ld, const int64_t* hidden
                    const int32_t* party_rows, int32_t NP, int32_t M, const float* member_weight, int32_t mode, float min_member_util,
                    int32_t K, int64_t* topk_ids, float* topk_scores, int32_t* party_n, float* member_util, void* scratch,
                    int64_t scratch_bytes, b4r_stream_t stream);
+/* Category affinity: the probability mass of every item group under each row's catalogue softmax, P(next item in g | row r), without
+ * an [R, V] buffer.  The first 11 arguments (hidden .. E) and allow_bits / n_filters / row_filter / item_scale are b4r_rank_full_ex's,
+ * there is no gt.  Per row r:
+ *   s(r, j), allowed(r)  b4r_rank_full_ex's with gt = NULL, bit for bit (bias may be NULL)
+ *   t(r, j) = fl32(s(r, j) * inv_temperature): b4r_score_dist's t; inv_temperature finite and > 0 (else B4R_E_BADARG)
+ *   u(r, j) = fl32((double) t(r, j) - row_lse[r]): b4r_score_dist's query_logp bits, with row_lse [R] (double) required and taken as given
+ *   c(r, j) = llrint(exp(min((double) u, 0.0)) * 2^40): b4r_audience_merge's demand term, an integer in units of 2^-40.  The min
+ *             clamps the exponent at 0, so that a row_lse that is too small cannot overflow the sums.
+ * item_group [V] int32: the label of every item (may be NULL when G = 0).
+ *   group_mass[r][g]  int64 [R, G]: sum of c(r, j) over the j in allowed(r) with item_group[j] == g
+ *   group_n[r][g]     int32 [R, G]: the number of those items
+ *   rest_mass[r], rest_n[r]  int64 / int32 [R]: the same over the j in allowed(r) whose label lies outside [0, G), so that per row
+ *                     sum_g group_n + rest_n = b4r_score_dist's row_n
+ *   dead row          hidden_row[r] < 0, or row_lse[r] = -inf or NaN: all zeros.  No NaN anywhere.
+ * The sums are integer sums: they do not depend on the order, the chunking or the launch grid, and two runs give the same bits.
+ * Against a sum of exponentials good to 1 ulp each, a mass is off by at most one unit per item.  A group whose mass is below about
+ * 1e-9 holds few units, and an item below 2^-41 adds 0 (group_n counts it all the same).
+ * Any output may be NULL.  0 <= G <= 65536, 1 <= V <= 2^22 (a sum stays below 2^62), H as in b4r_rank_full (else B4R_E_SHAPE);
+ * hidden, table, row_lse NULL, item_group NULL with G > 0, exclude NULL with E > 0: B4R_E_BADARG.  R = 0, or no output to write
+ * (G = 0 or no group_* output, and no rest_* output), succeeds and launches nothing.  Every check happens before any launch.
+ * Only enqueues (a memset per output and one launch; one stream, no host sync, no scratch, graph-capturable); no floating-point
+ * atomics.  One 256-thread workgroup takes 16 rows x 1024 ids: the sums of a window of 256 consecutive groups live in LDS and are
+ * flushed with one global integer atomic per non-zero (row, group).  G > 256: the workgroup makes one pass per window that has a
+ * label among its 1024 ids.  The products are formed once and every item's exponential once; what grows with the windows met per
+ * chunk (at most ceil(G / 256): labels spread over the catalogue; labels that follow the ids meet few) is the zeroing and the flush
+ * of the LDS windows and the number of global atomics.  The bits are the same for every G.
+ * Non-finite hidden values are outside the contract (they are never read out of bounds). */
+int b4r_group_mass(const float* hidden, int32_t hidden_ld, const int64_t* hidden_row, const float* table, const float* bias, int32_t H,
+                   int32_t V, int32_t first_item, int32_t R, const int64_t* exclude, int32_t E, const uint32_t* allow_bits,
+                   int32_t n_filters, const int32_t* row_filter, const float* item_scale, float inv_temperature, const double* row_lse,
+                   const int32_t* item_group, int32_t G, int64_t* group_mass, int32_t* group_n, int64_t* rest_mass, int32_t* rest_n,
+                   b4r_stream_t stream);
 /* replaces the metric loop of bert4rec_evaluator.py:118-120 over evaluation_metrics.py:47-112 for a batch of ranks:
  * gain_sums[m] += sum over gt_rank[i] > 0 of gain_m(gt_rank[i]), users[0] += #{gt_rank[i] > 0}; double / int64 DEVICE
  * accumulators the caller reads once per evaluate().  family[m]: 0 count (gain 1), 1 hit@cutoff (rank <= k), 2 NDCG@cutoff
