@@ -18,6 +18,7 @@
 #include <cmath>
 
 #include "b4r_common.h"
+#include "b4r_wave.h"   // order_image
 
 namespace {
 
@@ -26,13 +27,6 @@ constexpr int AM_TILE = 4;       // items per workgroup
 constexpr int AM_PASS = 256;     // rows per pass: 4 per thread
 constexpr int AM_PEND = 512;     // pending entries per item
 constexpr int AM_MAX_K = 1024;
-
-// order-preserving image of a float: a > b <=> img(a) > img(b), -0.0 counts as +0.0
-__device__ __forceinline__ uint32_t order_image(float x) {
-  if (x == 0.0f) x = 0.0f;
-  const uint32_t u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // (ia, ua) comes strictly before (ib, ub): the larger log probability, then the lower user id
 __device__ __forceinline__ bool before(uint32_t ia, int64_t ua, uint32_t ib, int64_t ub) { return ia > ib || (ia == ib && ua < ub); }

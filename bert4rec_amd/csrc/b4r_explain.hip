@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "b4r_common.h"
+#include "b4r_wave.h"   // order_image
 
 namespace {
 
@@ -25,14 +26,6 @@ constexpr int AS_MAX_W = 256;
 constexpr int AS_MAX_K = 1024;
 constexpr int AS_TILE = 16;    // explained items per workgroup
 constexpr int AS_LD = AS_MAX_W + 1;   // row stride of the image tile: rows of one wave fall into different banks
-
-// order-preserving image of a float: a > b <=> img(a) > img(b), -0.0 counts as +0.0.  Never 0 for a non-NaN value (-inf gives
-// 0x007FFFFF), so 0 is free to mark a dead entry.
-__device__ __forceinline__ uint32_t order_image(float x) {
-  if (x == 0.0f) x = 0.0f;
-  const uint32_t u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 struct OccludeArgs {
   const int64_t* tokens_in; const int32_t* len_in; const int32_t* labels;

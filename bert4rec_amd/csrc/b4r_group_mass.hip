@@ -40,12 +40,6 @@ constexpr int GM_MAX_V = 1 << 22; // 2^22 items of at most 2^40 units each: a su
 static_assert(sizeof(int64_t) * TILE_G * GM_SLOTS <= sizeof(float) * TILE_IPT * TILE_T * (TILE_KB + 1),
               "the window of sums lives in the dead staging buffer");
 
-__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 struct GroupMassArgs {
   const float* hidden; const int64_t* hidden_row; const float* table; const float* bias; const float* scale;
   const int64_t* exclude;

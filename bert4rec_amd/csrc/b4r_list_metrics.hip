@@ -9,16 +9,17 @@
 // the subtraction rounded on its own; distances and item weights enter the sums as q30(x) = (int64) rint(x * 2^30), so every per-row
 // sum is an integer and does not depend on the order of its terms.
 //
-// Two launches (three without item_rnorm):
+// Two launches (three without item_rnorm: b4r_item_rnorm_launch, b4r_cosine_chain.h, fills it first):
 //   list_metrics_kernel<NPT>  one 256-thread workgroup per list; thread tid owns the positions tid, tid + 256, ... (NPT = 1, 2 or 4).
 //      Loop over the query position p: qhat = table[q] * rnorm[q] to LDS (two barriers per p), then every thread walks the table rows
-//      of its live positions p' > p with 16-byte loads in ascending k -- the inner step of rerank_diverse_kernel.  Per-thread int64
+//      of its live positions p' > p with 16-byte loads in ascending k -- the inner step of mmr_kernel (b4r_rerank.hip).  Per-thread int64
 //      partial sums, reduced once at the end by shuffles and LDS.  exposure: one 64-bit integer atomic add per live entry.
 //   list_fold_kernel          one workgroup: thread t adds the per-row terms of rows t, t + 256, ... in ascending order, a fixed tree over
 //      the 256 partial sums follows: the double sums are bitwise reproducible from run to run, as b4r_rank_metrics' are.
 // No float atomics anywhere.
 #include "b4r_common.h"
 #include "b4r_cosine_chain.h"
+#include "b4r_wave.h"
 
 namespace {
 
@@ -34,25 +35,6 @@ __device__ __forceinline__ float distance_of(float sim) {
 }
 // (int64) rint(x * 2^30): the product is exact in fp32 (a power of two; |x| < 2^20 by the contract), rint rounds ties to even
 __device__ __forceinline__ int64_t q30(float x) { return (int64_t)rintf(x * 1073741824.0f); }
-
-__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)((uint64_t)v >> 32), o);
-    v += (int64_t)(((uint64_t)hi << 32) | lo);
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ int wave_min_i32(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-  return v;
-}
 
 struct ListArgs {
   const float* table; const float* rnorm;
@@ -173,18 +155,9 @@ __global__ __launch_bounds__(LT) void list_fold_kernel(const int32_t* row_n, con
   }
 }
 
-// 1 / |row| of every table row, as b4r_item_neighbours and b4r_rerank_diverse compute it (b4r_cosine_chain.h)
-__global__ __launch_bounds__(LT) void list_rnorm_kernel(const float* __restrict__ table, int H, int V, float* __restrict__ rnorm) {
-  const int64_t j = (int64_t)blockIdx.x * LT + threadIdx.x;
-  if (j >= V) return;
-  rnorm[j] = b4r_row_rnorm(table + j * H, H);
-}
-
-int64_t align16(int64_t b) { return (b + 15) & ~(int64_t)15; }
-
 // scratch regions, each a multiple of 16 bytes: rnorm [V] fp32 | n [R] int32 | dist [R] int64 | nov [R] int64
-int64_t rnorm_bytes(int32_t V) { return align16((int64_t)V * 4); }
-int64_t rows_bytes(int32_t R) { return align16((int64_t)R * 4) + 2 * align16((int64_t)R * 8); }
+int64_t rnorm_bytes(int32_t V) { return b4r_align16((int64_t)V * 4); }
+int64_t rows_bytes(int32_t R) { return b4r_align16((int64_t)R * 4) + 2 * b4r_align16((int64_t)R * 8); }
 
 }  // namespace
 
@@ -210,23 +183,22 @@ extern "C" int b4r_list_metrics(const float* table, int32_t ld, int32_t width, i
   const bool stage_rows = fold && !(row_n && row_dist && row_nov);
   char* base = nullptr;
   if (!item_rnorm || stage_rows) {
-    const int64_t pad = scratch ? (int64_t)((16 - ((uintptr_t)scratch & 15)) & 15) : 0;
-    B4R_CHECK_ARG(scratch && scratch_bytes - pad >= rnorm_bytes(V) + rows_bytes(R), B4R_E_NOMEM,
+    base = b4r_scratch_carve(scratch, scratch_bytes, rnorm_bytes(V) + rows_bytes(R));
+    B4R_CHECK_ARG(base, B4R_E_NOMEM,
                   "%s: scratch of %lld bytes is too small for rnorm [%d] and the sums of %d rows (b4r_list_metrics_scratch_bytes)", what,
                   (long long)scratch_bytes, V, R);
-    base = reinterpret_cast<char*>(scratch) + pad;
   }
   const float* rnorm = item_rnorm;
   if (!rnorm) {
     float* rn = reinterpret_cast<float*>(base);
-    hipLaunchKernelGGL(list_rnorm_kernel, dim3(b4r_cdiv(V, LT)), dim3(LT), 0, s, table, width, V, rn);
+    b4r_item_rnorm_launch(table, width, V, rn, s);
     rnorm = rn;
   }
   if (stage_rows) {   // the outputs the caller did not ask for
     char* rows = base + rnorm_bytes(V);
     if (!row_n) row_n = reinterpret_cast<int32_t*>(rows);
-    if (!row_dist) row_dist = reinterpret_cast<int64_t*>(rows + align16((int64_t)R * 4));
-    if (!row_nov) row_nov = reinterpret_cast<int64_t*>(rows + align16((int64_t)R * 4) + align16((int64_t)R * 8));
+    if (!row_dist) row_dist = reinterpret_cast<int64_t*>(rows + b4r_align16((int64_t)R * 4));
+    if (!row_nov) row_nov = reinterpret_cast<int64_t*>(rows + b4r_align16((int64_t)R * 4) + b4r_align16((int64_t)R * 8));
   }
   ListArgs a{table, rnorm, list_ids, gt, item_weight, row_n, row_dist, row_nov, hit_pos, exposure, width, V, K, first_item};
   if (K <= LT) hipLaunchKernelGGL(list_metrics_kernel<1>, dim3(R), dim3(LT), 0, s, a);

@@ -31,6 +31,7 @@
 
 #include "b4r_common.h"
 #include "b4r_catalogue_tile.h"
+#include "b4r_cosine_chain.h"
 
 namespace {
 
@@ -279,18 +280,11 @@ __global__ __launch_bounds__(TILE_T) void full_merge_kernel(MergeArgs a) {
 int64_t row_bytes(int32_t V, int32_t K) { return tile_chunks_of(V) * (tile_cap_of(K) * 8 + 8) + 4; }   // scores, ids | counts, beats | gt key
 
 // ---- item neighbours: 1 / |row| of every table row, and the staged query rows ------------------------------------------------
-// one thread per row, k ascending, one fp32 fma per element: a fixed order, so rnorm is bitwise reproducible
+// one thread per row (b4r_cosine_chain.h); b4r_item_rnorm_launch below serves every entry point that needs rnorm
 __global__ __launch_bounds__(TILE_T) void item_rnorm_kernel(const float* __restrict__ table, int H, int V, float* __restrict__ rnorm) {
   const int64_t j = (int64_t)blockIdx.x * TILE_T + threadIdx.x;
   if (j >= V) return;
-  const float* e = table + j * H;
-  float ss = 0.f;
-  for (int k = 0; k < H; k += 4) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(e + k);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) ss = __builtin_fmaf(v[u], v[u], ss);
-  }
-  rnorm[j] = 1.0f / sqrtf(fmaxf(ss, 1e-24f));
+  rnorm[j] = b4r_row_rnorm(table + j * H, H);
 }
 
 // qhat[r][k] = table[q_r][k] (* rnorm[q_r] when given); qrow[r] = r, or -1 (the sweep ranks nothing for the row) when q_r is no item
@@ -367,12 +361,15 @@ int rank_full_impl(const char* what, bool bias_required, const float* hidden, in
 }
 
 // b4r_item_neighbours' own regions in front of the sweep's scratch, each a multiple of 16 bytes: rnorm [V] | qhat [R, width] | qrow [R]
-int64_t align16(int64_t b) { return (b + 15) & ~(int64_t)15; }
 int64_t neighbour_bytes(int32_t R, int32_t V, int32_t width) {
-  return align16((int64_t)V * 4) + align16((int64_t)R * width * 4) + align16((int64_t)R * 8);
+  return b4r_align16((int64_t)V * 4) + b4r_align16((int64_t)R * width * 4) + b4r_align16((int64_t)R * 8);
 }
 
 }  // namespace
+
+void b4r_item_rnorm_launch(const float* table, int width, int V, float* rnorm, hipStream_t stream) {
+  hipLaunchKernelGGL(item_rnorm_kernel, dim3(b4r_cdiv(V, TILE_T)), dim3(TILE_T), 0, stream, table, width, V, rnorm);
+}
 
 extern "C" int64_t b4r_rank_full_scratch_bytes(int32_t R, int32_t V, int32_t K) {
   if (R <= 0 || V <= 0 || K < 0 || K > SEL_K_MAX) return 0;
@@ -422,12 +419,12 @@ extern "C" int b4r_item_neighbours(const float* table, int32_t ld, int32_t width
                 what, (long long)scratch_bytes);
   char* p = reinterpret_cast<char*>(scratch) + pad;
   float* rnorm = reinterpret_cast<float*>(p);
-  float* qhat = reinterpret_cast<float*>(p + align16((int64_t)V * 4));
-  int64_t* qrow = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(qhat) + align16((int64_t)R * width * 4));
+  float* qhat = reinterpret_cast<float*>(p + b4r_align16((int64_t)V * 4));
+  int64_t* qrow = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(qhat) + b4r_align16((int64_t)R * width * 4));
   char* rest = p + own;
   hipStream_t s = (hipStream_t)stream;
   const bool cosine = metric == B4R_SIM_COSINE;
-  if (cosine) hipLaunchKernelGGL(item_rnorm_kernel, dim3(b4r_cdiv(V, TILE_T)), dim3(TILE_T), 0, s, table, width, V, rnorm);
+  if (cosine) b4r_item_rnorm_launch(table, width, V, rnorm, s);
   hipLaunchKernelGGL(item_query_kernel, dim3(b4r_cdiv((int64_t)R * width, TILE_T)), dim3(TILE_T), 0, s, table, width, V, first_item, query_ids, R,
                      cosine ? rnorm : nullptr, qhat, qrow);
   // the query excludes itself: query_ids is the [R, 1] exclude list

@@ -15,6 +15,7 @@
 #include <cmath>
 
 #include "b4r_common.h"
+#include "b4r_wave.h"   // order_image
 
 namespace {
 
@@ -22,14 +23,6 @@ constexpr int RT = 256;            // threads per workgroup (4 waves), both kern
 constexpr int BS_MAX_BEAMS = 64;   // Bm, Bout
 constexpr int BS_MAX_CAND = 1024;  // C
 constexpr int BS_MAX_ENTRIES = 4096;
-
-// order-preserving image of a float: a > b <=> img(a) > img(b), -0.0 counts as +0.0.  Never 0 for a non-NaN value (-inf gives
-// 0x007FFFFF), so 0 is free to mark a dead entry.
-__device__ __forceinline__ uint32_t order_image(float x) {
-  if (x == 0.0f) x = 0.0f;
-  const uint32_t u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 struct BeamArgs {
   const float* beam_logp; const int64_t* cand_ids; const float* cand_logp;

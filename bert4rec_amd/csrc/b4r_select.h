@@ -1,21 +1,15 @@
-// The radix select of the full-catalogue kernels, stated once: the order-preserving image of a score, the state of one row's select
-// and its digit search.  b4r_rank_full.hip, b4r_sample_full.hip and b4r_rank_joint.hip select the best K of a chunk in their sweeps
+// The radix select of the full-catalogue kernels, stated once: the state of one row's select and its digit search (the
+// order-preserving image of a score, score_key, and the wave reductions are b4r_wave.h's).  b4r_rank_full.hip, b4r_sample_full.hip and b4r_rank_joint.hip select the best K of a chunk in their sweeps
 // (48-bit keys: image << 16 | 1023 - local id) and the best K of a row in their merges (64-bit keys: image << 32 | ~id) with it.
 // The keys are unique and their ascending order is "score descending, then id ascending" read from the top, so the outputs do not
 // depend on the order in which LDS atomics place or count.
 #pragma once
 #include "b4r_common.h"
+#include "b4r_wave.h"
 
 namespace {
 
 constexpr uint32_t NOT_ALLOWED = 0xFFFFFFFFu;   // raw-bits marker of an id that is not ranked (a NaN pattern: out of contract)
-
-// order-preserving image of a score for an ascending unsigned compare; -0.0 counts as +0.0 (they compare equal)
-__device__ __forceinline__ uint32_t score_key_bits(uint32_t u) {
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ uint32_t score_key(float s) { return score_key_bits(__builtin_bit_cast(uint32_t, s)); }
 
 // state of one row's radix select over W-bit unique keys: `hi` top bits are resolved (= prefix); `rem` ids are still to be taken
 // from those whose top bits equal the prefix; done: every key >= thr is taken (take = 0: none)
@@ -78,19 +72,6 @@ __device__ __forceinline__ void sel_advance(Sel s, Sel& out, const uint32_t* his
     }
     above += c;
   }
-}
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-  return v;
 }
 
 // ---- the merge: the best K of one row over all chunks' candidates, by one workgroup of T threads ------------------------------
