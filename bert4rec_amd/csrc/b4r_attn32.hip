@@ -14,6 +14,17 @@
 //   * attention-dropout decisions travel as one 32-bit word per (query, key tile): the backward loads them with scalar loads and
 //     uses them as lane masks (v_cndmask with an SGPR pair): one instruction per element.
 //
+// Six kernels, three pairs; each keeps its own prologue (what it stages, its LDS map, its host side) and is built from the shared
+// functions that follow the helpers below:
+//   attn32_fwd_kernel        the resident block: a32_fwd_dense_head per head; CQ: a32_fwd_compact_tile + a32_fwd_owner_merge
+//   attn32_bwd_kernel        the resident block: a32_bwd_dense_sweep per head; CQ: a32_bwd_compact_tile + a32_bwd_owner_sum
+//   attn32_core_fwd_kernel   the core alone, one (sequence, head) per workgroup: a32_fwd_dense_head
+//   attn32_core_bwd_kernel   ... a32_bwd_dense_sweep
+//   attn32_slotq_fwd_kernel  the core on the slots' queries: a32_fwd_compact_tile + a32_fwd_owner_merge
+//   attn32_slotq_bwd_kernel  ... a32_bwd_compact_tile + a32_bwd_owner_sum
+// All of them: a32_mask_value / a32_mask_adders (key mask), a32_bwd_vector (the backward's vector phase, in both sweeps),
+// a32_slot_perm (decision-word order), a32_lse, the a32_ld_* fragment loaders and acc_store_cols (b4r_tile32.h).
+//
 // Reference: tfm TransformerEncoderBlock / Keras MultiHeadAttention as constructed at
 // bert4rec/models/components/networks/bert4rec_encoder.py:136-147 and called at :220-222 (key-padding mask -1e9,
 // query scaled by 1/sqrt(d) after its bias, attention dropout on the probabilities, output dropout, residual,
@@ -135,7 +146,403 @@ __device__ __forceinline__ void acc_rows_at(char* tile, int row, int h, const f3
     *reinterpret_cast<bf16x8*>(d + P_IMG) = lo;
   }
 }
-__device__ __forceinline__ int a32_slot_perm(int r) { return (r & 24) | ((r & 3) << 1) | ((r >> 2) & 1); }   // query r of a tile -> its decision word
+// query r of a tile -> its decision word: query 16s + 8a + 4h' + b -> 16s + 8a + 2b + h' (the backward's register pairs)
+__device__ __forceinline__ int a32_slot_perm(int r) { return (r & 24) | ((r & 3) << 1) | ((r >> 2) & 1); }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// What the six kernels share.  Their prologues stay apart (what is staged, the LDS map and the host side differ); the mask
+// adders, the sweeps of the backward and the softmax / P.V sections of the forward are stated here once.
+// ---------------------------------------------------------------------------------------------------------------------------
+// hi / lo fragments of one product operand from a tile in LDS: transposed read in accumulator slot order (trp), read by rows,
+// transposed read in natural slot order (trn: the wave's scratch image)
+__device__ __forceinline__ void a32_ld_tr(const char* img, const Lane32& lk, int s2, bf16x8& H, bf16x8& Lo) {
+  H = tr_pair(img + lk.trp[s2][0], img + lk.trp[s2][1]);
+  Lo = tr_pair(img + P_IMG + lk.trp[s2][0], img + P_IMG + lk.trp[s2][1]);
+}
+__device__ __forceinline__ void a32_ld_row(const char* img, const Lane32& lk, int ks, bf16x8& H, bf16x8& Lo) {
+  H = row_at(img + lk.rowc[ks]);
+  Lo = row_at(img + P_IMG + lk.rowc[ks]);
+}
+__device__ __forceinline__ void a32_ld_trn(const char* img, const Lane32& lk, int ks, bf16x8& H, bf16x8& Lo) {
+  H = tr_pair(img + lk.trn[ks][0], img + lk.trn[ks][1]);
+  Lo = tr_pair(img + P_IMG + lk.trn[ks][0], img + P_IMG + lk.trn[ks][1]);
+}
+__device__ __forceinline__ void a32_sb() { __builtin_amdgcn_sched_barrier(0); }
+// lse of a softmax whose maximum is m (in log2 units) and whose sum of 2^(s - m) is `sum`: m ln 2 + log(sum), stated as the ONE fma
+// that hipcc had made of the written-out expression at every site -- it contracts a product and a sum only while both stay in one
+// basic block, which a shared function around them does not promise
+__device__ __forceinline__ float a32_lse(float m, float sum) { return fmaf(m, LN2, __logf(sum)); }
+// an accumulator in register layout -> a 4 KB tile (conflict-free 16-byte stores): a key owner's partial of a compact query tile
+__device__ __forceinline__ void a32_put_partial(char* tile, int lane, const f32x16& v) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    *reinterpret_cast<f32x4*>(tile + j * 1024 + lane * 16) = (f32x4){v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]};
+}
+
+// key mask of the sequence: one turn (at least 32 threads per 32 tokens).  The kernels request the value early and turn it into
+// the adders behind their other loads.
+__device__ __forceinline__ int64_t a32_mask_value(const int64_t* mask_row0, int L) { return (int)threadIdx.x < L ? mask_row0[threadIdx.x] : 0; }
+// sAdd[key] = (mask adder - amax) * log2e, -inf beyond L.  dead: every key masked -- Keras' -1e9 absorbs the scores, the softmax is
+// uniform over all L keys (lse = log L).  Holds a workgroup barrier.
+struct A32Keys { float amax; bool dead; };
+__device__ __forceinline__ A32Keys a32_mask_adders(int64_t mval, int L, int NT, float* sAdd) {
+  const float amax = __syncthreads_or(mval != 0 ? 1 : 0) ? 0.0f : -1e9f;
+  if ((int)threadIdx.x < NT * 32)
+    sAdd[threadIdx.x] = (int)threadIdx.x < L ? (((1.0f - (float)mval) * -1e9f) - amax) * LOG2E : -INFINITY;
+  return {amax, amax != 0.0f};
+}
+
+// ---- backward --------------------------------------------------------------------------------------------------------------
+// VECTOR phase of one 32 x 32 block: S, dA -> Pd, dS as operand fragments (hi / lo), dS also to the wave's [key][query] scratch
+// image.  km: keep decisions of the block, register tt's lane mask over the keys (read when DROP).
+template <bool DROP>
+__device__ __forceinline__ void a32_bwd_vector(const f32x16& S, const f32x16& dA, const f32x16& Dq, const uint64_t (&km)[16], float pscale,
+                                               char* scr, int r, int h, bf16x8 (&pdh)[2], bf16x8 (&pdl)[2], bf16x8 (&dsh)[2],
+                                               bf16x8 (&dsl)[2]) {
+#pragma unroll
+  for (int s2 = 0; s2 < 2; ++s2) {
+    f32x8 pd, ds;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int tt = 8 * s2 + j;
+      const float pr = (A32_EXP & 1) ? S[tt] : __builtin_amdgcn_exp2f(S[tt]);
+      if (A32_EXP & 1) { pd[j] = pr; ds[j] = dA[tt]; } else
+      if (DROP) {
+        const float kf = __builtin_amdgcn_inverse_ballot_w64(km[tt]) ? pscale : 0.f;
+        pd[j] = pr * kf;
+        ds[j] = pr * fmaf(dA[tt], kf, -Dq[tt]);
+      } else {
+        pd[j] = pr;
+        ds[j] = pr * (dA[tt] - Dq[tt]);
+      }
+    }
+    split8(pd, pdh[s2], pdl[s2]);
+    split8(ds, dsh[s2], dsl[s2]);
+    // dS -> the wave's [key][query] scratch image: registers 4a .. 4a+3 of this half are queries 16 s2 + 8a + 4h + (0..3)
+    const s16x8 hv = __builtin_bit_cast(s16x8, dsh[s2]), lv = __builtin_bit_cast(s16x8, dsl[s2]);
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      char* w8 = scr + p_chunk(r, 2 * s2 + a) + 8 * h;
+      *reinterpret_cast<s16x4*>(w8) = a ? __builtin_shufflevector(hv, hv, 4, 5, 6, 7) : __builtin_shufflevector(hv, hv, 0, 1, 2, 3);
+      *reinterpret_cast<s16x4*>(w8 + P_IMG) = a ? __builtin_shufflevector(lv, lv, 4, 5, 6, 7) : __builtin_shufflevector(lv, lv, 0, 1, 2, 3);
+    }
+  }
+}
+
+// S = Q~ . K^T (starting from -lse per query + the key's mask adder) and dA = dO . V^T of one query tile
+template <int TERMS>
+__device__ __forceinline__ void a32_bwd_scores(const Lane32& lk, const char* qimg, const char* dimg, const float* cs_t, float adk,
+                                               const bf16x8 (&kBh)[2], const bf16x8 (&kBl)[2], const bf16x8 (&vBh)[2],
+                                               const bf16x8 (&vBl)[2], f32x16& S, f32x16& dA) {
+  S = rows_of(cs_t, lk.h);
+#pragma unroll
+  for (int e = 0; e < 16; ++e) S[e] += adk;
+  dA = zero16();
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    bf16x8 ah, al;
+    a32_ld_row(qimg, lk, ks, ah, al);
+    S = mfma32x3<TERMS>(ah, al, kBh[ks], kBl[ks], S);
+    a32_ld_row(dimg, lk, ks, ah, al);
+    dA = mfma32x3<TERMS>(ah, al, vBh[ks], vBl[ks], dA);
+  }
+}
+
+// The DENSE key-owner sweep of one head (attn32_bwd_kernel without CQ, attn32_core_bwd_kernel): wave w (key tile w) x query tile
+// (w + s) mod NT.  A step is a VECTOR phase (S, dA of this tile -> Pd, dS as operand fragments; dS also to the wave's scratch image)
+// and a MATRIX phase of ten 3-instruction products issued back to back: dV, dK (two query halves each), S, dA of the NEXT tile (two
+// feature halves each), the dQ partial (two key halves).  Every product's LDS fragments are requested two products ahead (hipcc
+// otherwise puts each read next to its use: a wave then waits out the LDS latency in front of every product, and two waves per SIMD
+// cannot cover that).  No barrier inside the sweep: the dQ accumulator of tile t was last touched by wave w + 1 in ITS previous
+// step, a flag per wave orders that (fixed order of the additions => bitwise reproducible).
+// In LDS: Q~ / dO images and zeroed dQ accumulators of every tile, -lse (sCS) and D (sD) per query, sflag[wave] = 0; scr = the wave's
+// scratch tile.  bits / bh: the decision words of this (sequence, head).  hd: the head the A32_SWEEP stamps belong to.  Ends with the
+// barrier behind which every accumulator is complete.
+template <bool DROP, int TERMS>
+__device__ __forceinline__ void a32_bwd_dense_sweep(const Lane32& lk, int lane, int wave, int NT, const char* QIMG, const char* DOIMG,
+                                                    char* DQACC, char* scr, const float* sCS, const float* sD, float adk, int* sflag,
+                                                    const uint32_t* bits, int64_t bh, int hd, float pscale, const bf16x8 (&kBh)[2],
+                                                    const bf16x8 (&kBl)[2], const bf16x8 (&vBh)[2], const bf16x8 (&vBl)[2],
+                                                    const bf16x8 (&kTh)[2], const bf16x8 (&kTl)[2], f32x16& dK, f32x16& dV) {
+  (void)hd;
+  const int r = lk.r, h = lk.h;
+  auto tile_of = [&](int s) __attribute__((always_inline)) { const int t = wave + s; return t >= NT ? t - NT : t; };
+  typedef const __attribute__((address_space(4))) uint64_t* kmask_ptr;   // constant address space: scalar loads
+  f32x16 S, dA;
+  // S, dA of the first tile
+  a32_bwd_scores<TERMS>(lk, QIMG + wave * P_TILE, DOIMG + wave * P_TILE, sCS + 32 * wave, adk, kBh, kBl, vBh, vBl, S, dA);
+  for (int s = 0; s < NT; ++s) {
+    const int t = tile_of(s), tn = tile_of(s + 1);   // (the last step forms S / dA of a tile nobody uses: no branch in the body)
+    const char* qimg = QIMG + t * P_TILE;
+    const char* dimg = DOIMG + t * P_TILE;
+    const char* qn = QIMG + tn * P_TILE;
+    const char* dn = DOIMG + tn * P_TILE;
+    A32_SWEEP(2 + 4 * s);
+    // ---- vector phase ------------------------------------------------------------------------------------------------------
+    bf16x8 f0h, f0l, f1h, f1l;
+    a32_ld_tr(dimg, lk, 0, f0h, f0l);   // the first two products' fragments travel during the vector phase
+    a32_ld_tr(qimg, lk, 0, f1h, f1l);
+    const f32x16 Dq = rows_of(sD + 32 * t, h);
+    uint64_t km[16];   // keep decisions of the 32 x 32 block: register tt's lane mask over the keys
+    if (DROP) {
+      kmask_ptr mp = (kmask_ptr)(reinterpret_cast<const uint64_t*>(bits) + ((bh * NT + wave) * NT + t) * 16);
+#pragma unroll
+      for (int tt = 0; tt < 16; ++tt) km[tt] = mp[tt];
+    }
+    bf16x8 pdh[2], pdl[2], dsh[2], dsl[2];
+    a32_bwd_vector<DROP>(S, dA, Dq, km, pscale, scr, r, h, pdh, pdl, dsh, dsl);
+    // S of the next tile starts from -lse (per query) + the key's mask adder
+    S = rows_of(sCS + 32 * tn, h);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) S[e] += adk;
+    A32_SWEEP(3 + 4 * s);
+    a32_sb();
+    // ---- matrix phase: ten products, fragments requested two products ahead ---------------------------------------------------
+    bf16x8 f2h, f2l, f3h, f3l, f4h, f4l, f5h, f5l, f6h, f6l, f7h, f7l, f8h, f8l, f9h, f9l;
+    a32_ld_tr(dimg, lk, 1, f2h, f2l);
+    dV = mfma32x3<TERMS>(f0h, f0l, pdh[0], pdl[0], dV);   // dV^T[feature][key] += dO^T[feature][query] . Pd[query][key], queries 0..15
+    a32_sb();
+    a32_ld_tr(qimg, lk, 1, f3h, f3l);
+    dK = mfma32x3<TERMS>(f1h, f1l, dsh[0], dsl[0], dK);   // dK^T += Q~^T . dS
+    a32_sb();
+    a32_ld_row(qn, lk, 0, f4h, f4l);
+    dV = mfma32x3<TERMS>(f2h, f2l, pdh[1], pdl[1], dV);
+    a32_sb();
+    a32_ld_row(dn, lk, 0, f5h, f5l);
+    dK = mfma32x3<TERMS>(f3h, f3l, dsh[1], dsl[1], dK);
+    a32_sb();
+    a32_ld_row(qn, lk, 1, f6h, f6l);
+    S = mfma32x3<TERMS>(f4h, f4l, kBh[0], kBl[0], S);     // S[query][key] = Q~ . K^T of the next tile
+    a32_sb();
+    a32_ld_row(dn, lk, 1, f7h, f7l);
+    dA = mfma32x3<TERMS>(f5h, f5l, vBh[0], vBl[0], zero16());
+    a32_sb();
+    a32_ld_trn(scr, lk, 0, f8h, f8l);
+    S = mfma32x3<TERMS>(f6h, f6l, kBh[1], kBl[1], S);
+    a32_sb();
+    a32_ld_trn(scr, lk, 1, f9h, f9l);
+    dA = mfma32x3<TERMS>(f7h, f7l, vBh[1], vBl[1], dA);
+    a32_sb();
+    // dQ^T[feature position][query] = K^T[.][key] . dS^T[key][query]  (B by transposed reads of the scratch image)
+    f32x16 dQp = mfma32x3<TERMS>(kTh[0], kTl[0], f8h, f8l, zero16());
+    dQp = mfma32x3<TERMS>(kTh[1], kTl[1], f9h, f9l, dQp);
+    A32_SWEEP(4 + 4 * s);
+    if (s > 0) {   // the accumulator's previous addition (wave w + 1, its step s - 1) must be in place
+      const volatile int* f = sflag + (wave + 1 < NT ? wave + 1 : 0);
+      while (*f < s) __builtin_amdgcn_s_sleep(1);
+      asm volatile("" ::: "memory");
+    }
+    char* acc = DQACC + t * P_TILE + lane * 16;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      f32x4* a4 = reinterpret_cast<f32x4*>(acc + j * 1024);
+      *a4 = *a4 + (f32x4){dQp[4 * j], dQp[4 * j + 1], dQp[4 * j + 2], dQp[4 * j + 3]};
+    }
+    asm volatile("" ::: "memory");
+    *reinterpret_cast<volatile int*>(sflag + wave) = s + 1;   // LDS operations of a wave complete in order: the sums are in place
+    A32_SWEEP(5 + 4 * s);
+  }
+  lds_barrier();   // every accumulator is complete
+}
+
+// One COMPACT query tile of a key owner (attn32_bwd_kernel's CQ form, attn32_slotq_bwd_kernel): S / dA, the vector phase, dV and dK
+// of the wave's keys, and the wave's dQ partial of the tile.  cs_t, d_t: -lse and D of the tile's 32 queries; km as a32_bwd_vector's,
+// filled by the caller from wherever its decision words are.
+template <bool DROP>
+__device__ __forceinline__ void a32_bwd_compact_tile(const Lane32& lk, const char* qimg, const char* dimg, char* scr, const float* cs_t,
+                                                     const float* d_t, float adk, const uint64_t (&km)[16], float pscale,
+                                                     const bf16x8 (&kBh)[2], const bf16x8 (&kBl)[2], const bf16x8 (&vBh)[2],
+                                                     const bf16x8 (&vBl)[2], const bf16x8 (&kTh)[2], const bf16x8 (&kTl)[2], f32x16& dK,
+                                                     f32x16& dV, f32x16& dQp) {
+  f32x16 S, dA;
+  a32_bwd_scores<3>(lk, qimg, dimg, cs_t, adk, kBh, kBl, vBh, vBl, S, dA);
+  const f32x16 Dq = rows_of(d_t, lk.h);
+  bf16x8 pdh[2], pdl[2], dsh[2], dsl[2];
+  a32_bwd_vector<DROP>(S, dA, Dq, km, pscale, scr, lk.r, lk.h, pdh, pdl, dsh, dsl);
+#pragma unroll
+  for (int s2 = 0; s2 < 2; ++s2) {
+    bf16x8 fh, fl;
+    a32_ld_tr(dimg, lk, s2, fh, fl);
+    dV = mfma32x3(fh, fl, pdh[s2], pdl[s2], dV);   // dV^T[feature][key] += dO^T[feature][query] . Pd[query][key]
+    a32_ld_tr(qimg, lk, s2, fh, fl);
+    dK = mfma32x3(fh, fl, dsh[s2], dsl[s2], dK);   // dK^T += Q~^T . dS
+  }
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    bf16x8 fh, fl;
+    a32_ld_trn(scr, lk, ks, fh, fl);
+    dQp = mfma32x3(kTh[ks], kTl[ks], fh, fl, dQp);   // dQ^T[feature position][query] = K^T . dS^T
+  }
+}
+
+// dQ of one compact tile = the key owners' partials in wave order, through the scratch tiles (ordered: bitwise reproducible).  Every
+// wave calls it; the sum comes back in register layout to the wave that asks for it (`mine`), zeros to the others.  The first barrier
+// waits for the previous use of the scratch tiles (the sweep's last reads, or the previous tile's sum).
+__device__ __forceinline__ f32x16 a32_bwd_owner_sum(const f32x16& part, char* scr, const char* SCRALL, int NT, int lane, bool mine) {
+  lds_barrier();
+  a32_put_partial(scr, lane, part);
+  lds_barrier();
+  f32x16 gsum = zero16();
+  if (mine) {
+    for (int w = 0; w < NT; ++w)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const f32x4 a4 = *reinterpret_cast<const f32x4*>(SCRALL + w * P_TILE + j * 1024 + lane * 16);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) gsum[4 * j + e] += a4[e];
+      }
+  }
+  return gsum;
+}
+
+// ---- forward ---------------------------------------------------------------------------------------------------------------
+// The DENSE head of a wave's 32 queries (attn32_fwd_kernel without CQ, once per head; attn32_core_fwd_kernel): S^T[key][query] =
+// K . Q~^T over the NT key tiles (NTT: their compile-time bound) -- the score row of a query lives in one lane's registers and its
+// partner half: softmax without LDS -- maximum, sum, lse out, dropout decisions from the counter hash (one hash per 4 keys) and their
+// words out, O^T = V^T . Pd^T.  Returns O.  qBh / qBl: Q~^T as the B operand; tok / live: the lane's query; mark: the first of the
+// two A32F_MARK stamps.
+template <int NTT, bool DROP, int TERMS>
+__device__ __forceinline__ f32x16 a32_fwd_dense_head(const Lane32& lk, int wave, int NT, int L, const char* kimg, const char* vimg,
+                                                     const float* sAdd, const bf16x8 (&qBh)[2], const bf16x8 (&qBl)[2], const DropCtx& dcp,
+                                                     int64_t bh, int tok, bool live, float* lse, uint32_t* bits, int mark) {
+  (void)mark;
+  const int r = lk.r, h = lk.h;
+  f32x16 S[NTT];
+  float m = -INFINITY;
+#pragma unroll
+  for (int t = 0; t < NTT; ++t) {
+    if (t < NT) {   // (wave-uniform; NTT is the compile-time bound of the token tiles)
+      S[t] = rows_of(sAdd + 32 * t, h);
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const char* ka = kimg + t * P_TILE + lk.rowc[ks];
+        S[t] = mfma32x3<TERMS>(row_at(ka), row_at(ka + P_IMG), qBh[ks], qBl[ks], S[t]);
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) S[t][e] = -INFINITY;
+    }
+  }
+  A32F_MARK(mark);
+#pragma unroll
+  for (int t = 0; t < NTT; ++t)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) m = fmaxf(m, S[t][e]);
+  m = fmaxf(m, other_half(m, h));
+  float sum = 0.f;
+#pragma unroll
+  for (int t = 0; t < NTT; ++t)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) { S[t][e] = __builtin_amdgcn_exp2f(S[t][e] - m); sum += S[t][e]; }
+  sum += other_half(sum, h);
+  const float inv = 1.0f / sum;
+  if (h == 0 && live && lse) lse[bh * L + tok] = a32_lse(m, sum);
+  A32F_MARK(mark + 1);
+  f32x16 O = zero16();
+  const uint64_t dbase = ((uint64_t)bh * L + (uint64_t)(live ? tok : 0)) * (uint64_t)B4R_ATTN_PITCH;
+#pragma unroll
+  for (int t = 0; t < NTT; ++t) {
+    if (t >= NT) continue;
+    if (DROP) {
+      uint32_t word = 0;
+      const float sc = inv * dcp.scale;
+#pragma unroll
+      for (int gp = 0; gp < 4; ++gp) {
+        const B4rKeep4 k4 = b4r_keep4p(dcp, dbase + (uint64_t)(32 * t + 8 * gp + 4 * h));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) S[t][4 * gp + e] = k4.k[e] ? S[t][4 * gp + e] * sc : 0.f;
+        word |= k4.bits() << (8 * gp + 4 * h);
+      }
+      word |= other_half_u(word, h);
+      if (h == 0 && live) bits[((bh * NT + t) * NT + wave) * 32 + a32_slot_perm(r)] = word;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) S[t][e] *= inv;
+    }
+    // O^T[feature][query] += V^T[feature][keys of tile t] . Pd^T[key][query]
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+      bf16x8 ph, pl;
+      acc_frag(S[t], s2, ph, pl);
+      bf16x8 vh, vl;
+      a32_ld_tr(vimg + t * P_TILE, lk, s2, vh, vl);
+      O = mfma32x3<TERMS>(vh, vl, ph, pl, O);
+    }
+  }
+  return O;
+}
+
+// One COMPACT query tile of a key owner (attn32_fwd_kernel's CQ form, attn32_slotq_fwd_kernel): S^T[key][query] = K_w . Q~_t^T, a
+// local softmax over the wave's 32 keys whose (max, sum) of the lane's query go to ms[0], ms[1], the decisions of (query token qtok,
+// the wave's keys) and their word to words[word_i] (where word_on), the O^T partial over the wave's own V tile.  add: the keys' mask adders.
+template <bool DROP>
+__device__ __forceinline__ f32x16 a32_fwd_compact_tile(const Lane32& lk, int wave, int L, const f32x16& add, const bf16x8 (&kAh)[2],
+                                                       const bf16x8 (&kAl)[2], const char* qimg, const char* vown, float* ms,
+                                                       const DropCtx& dcp, int64_t bh, int qtok, uint32_t* words, int word_i, bool word_on) {
+  const int h = lk.h;
+  f32x16 S = add;
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    const char* qi = qimg + lk.rowc[ks];
+    S = mfma32x3(kAh[ks], kAl[ks], row_at(qi), row_at(qi + P_IMG), S);   // S^T[key][query] = K_w . Q~_t^T
+  }
+  float m = S[0];
+#pragma unroll
+  for (int e = 1; e < 16; ++e) m = fmaxf(m, S[e]);
+  m = fmaxf(m, other_half(m, h));
+  const float mref = m == -INFINITY ? 0.0f : m;   // a tile of pad keys only: every term is 0
+  float sum = 0.f;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) { S[e] = __builtin_amdgcn_exp2f(S[e] - mref); sum += S[e]; }
+  sum += other_half(sum, h);
+  if (h == 0) { ms[0] = m; ms[1] = sum; }
+  if (DROP) {
+    uint32_t word = 0;
+    const uint64_t dbase = ((uint64_t)bh * L + (uint64_t)qtok) * (uint64_t)B4R_ATTN_PITCH;
+#pragma unroll
+    for (int gp = 0; gp < 4; ++gp) {
+      const B4rKeep4 k4 = b4r_keep4p(dcp, dbase + (uint64_t)(32 * wave + 8 * gp + 4 * h));
+#pragma unroll
+      for (int e = 0; e < 4; ++e) S[4 * gp + e] = k4.k[e] ? S[4 * gp + e] : 0.f;
+      word |= k4.bits() << (8 * gp + 4 * h);
+    }
+    word |= other_half_u(word, h);
+    if (h == 0 && word_on) words[word_i] = word;
+  }
+  f32x16 Op = zero16();
+#pragma unroll
+  for (int s2 = 0; s2 < 2; ++s2) {
+    bf16x8 ph, pl;
+    acc_frag(S, s2, ph, pl);
+    bf16x8 vh, vl;
+    a32_ld_tr(vown, lk, s2, vh, vl);
+    Op = mfma32x3(vh, vl, ph, pl, Op);
+  }
+  return Op;
+}
+
+// Merge of one compact query tile over the NT key owners: M = max_w m_w, tot = sum_w 2^(m_w - M) sum_w, returns sum_w 2^(m_w - M) O_w.
+// ms0 + w * ms_pitch: owner w's (max, sum) of the lane's query; part0 + w * P_TILE: its O^T partial (register layout).
+__device__ __forceinline__ f32x16 a32_fwd_owner_merge(const float* ms0, int ms_pitch, const char* part0, int NT, int lane, float& M,
+                                                      float& tot) {
+  M = -INFINITY;
+  for (int w = 0; w < NT; ++w) M = fmaxf(M, ms0[w * ms_pitch]);
+  tot = 0.f;
+  f32x16 O = zero16();
+  for (int w = 0; w < NT; ++w) {
+    const float* ms = ms0 + w * ms_pitch;
+    const float a = ms[0] == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(ms[0] - M);
+    tot = fmaf(a, ms[1], tot);
+    const char* srcp = part0 + w * P_TILE + lane * 16;
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      const f32x4 o4 = *reinterpret_cast<const f32x4*>(srcp + jj * 1024);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) O[4 * jj + e] = fmaf(a, o4[e], O[4 * jj + e]);
+    }
+  }
+  return O;
+}
 
 struct A32BwdP {
   const float* x; const float* dz1; const float* ctx; const float* lse; const uint32_t* bits; const int64_t* mask;
@@ -214,14 +621,10 @@ __global__ __launch_bounds__(512, 2) void attn32_bwd_kernel(A32BwdP p) {
   };                                                                                \
   (void)dz_row
 
-  // key mask: one turn (at least 32 threads per 32 tokens)
-  const int64_t mval = (int)threadIdx.x < L ? p.mask[row0 + threadIdx.x] : 0;
-  const int any_key = mval != 0 ? 1 : 0;
+  const int64_t mval = a32_mask_value(p.mask + row0, L);
   for (int k = threadIdx.x; k < 192; k += nthreads) sbq[k] = p.bqkv[k];
-  const float amax = __syncthreads_or(any_key) ? 0.0f : -1e9f;
-  const bool dead = amax != 0.0f;   // every key masked: Keras' -1e9 absorbs the scores, the softmax is uniform over all L keys
+  const bool dead = a32_mask_adders(mval, L, NT, sAdd).dead;
   if ((int)threadIdx.x < NT * 32) {
-    sAdd[threadIdx.x] = (int)threadIdx.x < L ? (((1.0f - (float)mval) * -1e9f) - amax) * LOG2E : -INFINITY;
     sHas[threadIdx.x] = p.slot_pos != nullptr ? 0.f : 1.f;
     if (CQ) { sSlot[threadIdx.x] = -1; if (threadIdx.x < 64) sTok[threadIdx.x] = -1; }
   }
@@ -436,14 +839,9 @@ __global__ __launch_bounds__(512, 2) void attn32_bwd_kernel(A32BwdP p) {
     lds_barrier();   // images, D, -lse of every tile in place; accumulators zero; (the K^T reads above have landed: lgkmcnt(0))
     A32_MARK(7 + 10 * hd);
 
-    // ---- the sweep: wave w (key tile w) x query tile (w + s) mod NT.  A step is a VECTOR phase (S, dA of this tile -> Pd, dS as
-    // operand fragments; dS also to the wave's scratch image) and a MATRIX phase of ten 3-instruction products issued back to back:
-    // dV, dK (two query halves each), S, dA of the NEXT tile (two feature halves each), the dQ partial (two key halves).  Every
-    // product's LDS fragments are requested two products ahead (hipcc otherwise puts each read next to its use: a wave then waits
-    // out the LDS latency in front of every product, and two waves per SIMD cannot cover that).  No barrier inside the sweep: the dQ
-    // accumulator of tile t was last touched by wave w + 1 in ITS previous step, a flag per wave orders that (fixed order of the
-    // additions => bitwise reproducible).
-    f32x16 dK = zero16(), dV = zero16(), S, dA;
+    // ---- the sweep: the key owners' dense sweep over the NT query tiles (a32_bwd_dense_sweep), or, CQ, the compact query tiles
+    // (a32_bwd_compact_tile) and the ordered sum of their dQ partials (a32_bwd_owner_sum)
+    f32x16 dK = zero16(), dV = zero16();
     const float adk = sAdd[tok];
     if (dead) {   // S = -lse for every key: the scores are absorbed by the mask adder
 #pragma unroll
@@ -451,40 +849,13 @@ __global__ __launch_bounds__(512, 2) void attn32_bwd_kernel(A32BwdP p) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) { kBh[ks][e] = (__bf16)0.f; kBl[ks][e] = (__bf16)0.f; }
     }
-#define A32_LD_TR(img, s2, H, Lo)                                                \
-  H = tr_pair((img) + lk.trp[s2][0], (img) + lk.trp[s2][1]);                     \
-  Lo = tr_pair((img) + P_IMG + lk.trp[s2][0], (img) + P_IMG + lk.trp[s2][1])
-#define A32_LD_ROW(img, ks, H, Lo)                                               \
-  H = row_at((img) + lk.rowc[ks]);                                               \
-  Lo = row_at((img) + P_IMG + lk.rowc[ks])
-#define A32_LD_SCR(ks, H, Lo)                                                    \
-  H = tr_pair(scr + lk.trn[ks][0], scr + lk.trn[ks][1]);                         \
-  Lo = tr_pair(scr + P_IMG + lk.trn[ks][0], scr + P_IMG + lk.trn[ks][1])
-#define A32_SB() __builtin_amdgcn_sched_barrier(0)
-    auto tile_of = [&](int s) __attribute__((always_inline)) { const int t = wave + s; return t >= NT ? t - NT : t; };
-    typedef const __attribute__((address_space(4))) uint64_t* kmask_ptr;   // constant address space: scalar loads
     if (CQ) {
       f32x16 dQp[2];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         dQp[t] = zero16();
         if (t >= NQ) continue;   // (block-uniform)
-        const char* qimg = QIMG + t * P_TILE;
-        const char* dimg = DOIMG + t * P_TILE;
-        S = rows_of(sCS + 32 * t, h);
-        dA = zero16();
-#pragma unroll
-        for (int e = 0; e < 16; ++e) S[e] += adk;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          bf16x8 ah, al;
-          A32_LD_ROW(qimg, ks, ah, al);
-          S = mfma32x3(ah, al, kBh[ks], kBl[ks], S);
-          A32_LD_ROW(dimg, ks, ah, al);
-          dA = mfma32x3(ah, al, vBh[ks], vBl[ks], dA);
-        }
-        const f32x16 Dq = rows_of(sD + 32 * t, h);
-        uint64_t km[16];
+        uint64_t km[16];   // from the regathered words in LDS, made wave-uniform
         if (DROP) {
           const uint32_t* cw = sCW + (wave * 2 + t) * 32;
 #pragma unroll
@@ -493,188 +864,21 @@ __global__ __launch_bounds__(512, 2) void attn32_bwd_kernel(A32BwdP p) {
             km[tt] = ((uint64_t)hi_ << 32) | lo_;
           }
         }
-        bf16x8 pdh[2], pdl[2], dsh[2], dsl[2];
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          f32x8 pd, ds;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const int tt = 8 * s2 + j;
-            const float pr = __builtin_amdgcn_exp2f(S[tt]);
-            if (DROP) {
-              const float kf = __builtin_amdgcn_inverse_ballot_w64(km[tt]) ? pscale : 0.f;
-              pd[j] = pr * kf;
-              ds[j] = pr * fmaf(dA[tt], kf, -Dq[tt]);
-            } else {
-              pd[j] = pr;
-              ds[j] = pr * (dA[tt] - Dq[tt]);
-            }
-          }
-          split8(pd, pdh[s2], pdl[s2]);
-          split8(ds, dsh[s2], dsl[s2]);
-          const s16x8 hv = __builtin_bit_cast(s16x8, dsh[s2]), lv = __builtin_bit_cast(s16x8, dsl[s2]);
-#pragma unroll
-          for (int a = 0; a < 2; ++a) {
-            char* w8 = scr + p_chunk(r, 2 * s2 + a) + 8 * h;
-            *reinterpret_cast<s16x4*>(w8) = a ? __builtin_shufflevector(hv, hv, 4, 5, 6, 7) : __builtin_shufflevector(hv, hv, 0, 1, 2, 3);
-            *reinterpret_cast<s16x4*>(w8 + P_IMG) = a ? __builtin_shufflevector(lv, lv, 4, 5, 6, 7) : __builtin_shufflevector(lv, lv, 0, 1, 2, 3);
-          }
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          bf16x8 fh, fl;
-          A32_LD_TR(dimg, s2, fh, fl);
-          dV = mfma32x3(fh, fl, pdh[s2], pdl[s2], dV);
-          A32_LD_TR(qimg, s2, fh, fl);
-          dK = mfma32x3(fh, fl, dsh[s2], dsl[s2], dK);
-        }
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          bf16x8 fh, fl;
-          A32_LD_SCR(ks, fh, fl);
-          dQp[t] = mfma32x3(kTh[ks], kTl[ks], fh, fl, dQp[t]);
-        }
+        a32_bwd_compact_tile<DROP>(lk, QIMG + t * P_TILE, DOIMG + t * P_TILE, scr, sCS + 32 * t, sD + 32 * t, adk, km, pscale, kBh, kBl,
+                                   vBh, vBl, kTh, kTl, dK, dV, dQp[t]);
       }
       // dQ of compact tile t = the key owners' partials in wave order, left in accumulator tile t (register layout)
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         if (t >= NQ) continue;
-        lds_barrier();   // (t == 0: every sweep is over; t > 0: the previous tile's partials have been read)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          *reinterpret_cast<f32x4*>(scr + j * 1024 + lane * 16) = (f32x4){dQp[t][4 * j], dQp[t][4 * j + 1], dQp[t][4 * j + 2], dQp[t][4 * j + 3]};
-        lds_barrier();
-        if (wave == t) {
-          f32x16 gsum = zero16();
-          for (int w_ = 0; w_ < NT; ++w_)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              const f32x4 a4 = *reinterpret_cast<const f32x4*>(SCRALL + w_ * P_TILE + j * 1024 + lane * 16);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) gsum[4 * j + e] += a4[e];
-            }
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            *reinterpret_cast<f32x4*>(DQACC + t * P_TILE + j * 1024 + lane * 16) = (f32x4){gsum[4 * j], gsum[4 * j + 1], gsum[4 * j + 2], gsum[4 * j + 3]};
-        }
+        const f32x16 gsum = a32_bwd_owner_sum(dQp[t], scr, SCRALL, NT, lane, wave == t);
+        if (wave == t) a32_put_partial(DQACC + t * P_TILE, lane, gsum);
       }
+      lds_barrier();   // every accumulator is complete
     } else {
-    {   // S, dA of the first tile
-      const char* qimg = QIMG + wave * P_TILE;
-      const char* dimg = DOIMG + wave * P_TILE;
-      S = rows_of(sCS + 32 * wave, h);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) S[e] += adk;
-      dA = zero16();
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        bf16x8 ah, al;
-        A32_LD_ROW(qimg, ks, ah, al);
-        S = mfma32x3(ah, al, kBh[ks], kBl[ks], S);
-        A32_LD_ROW(dimg, ks, ah, al);
-        dA = mfma32x3(ah, al, vBh[ks], vBl[ks], dA);
-      }
+      a32_bwd_dense_sweep<DROP, 3>(lk, lane, wave, NT, QIMG, DOIMG, DQACC, scr, sCS, sD, adk, sflag, p.bits, bh, hd, pscale, kBh, kBl,
+                                   vBh, vBl, kTh, kTl, dK, dV);
     }
-    for (int s = 0; s < NT; ++s) {
-      const int t = tile_of(s), tn = tile_of(s + 1);   // (the last step forms S / dA of a tile nobody uses: no branch in the body)
-      const char* qimg = QIMG + t * P_TILE;
-      const char* dimg = DOIMG + t * P_TILE;
-      const char* qn = QIMG + tn * P_TILE;
-      const char* dn = DOIMG + tn * P_TILE;
-      A32_SWEEP(2 + 4 * s);
-      // ---- vector phase ------------------------------------------------------------------------------------------------------
-      bf16x8 f0h, f0l, f1h, f1l;
-      A32_LD_TR(dimg, 0, f0h, f0l);   // the first two products' fragments travel during the vector phase
-      A32_LD_TR(qimg, 0, f1h, f1l);
-      const f32x16 Dq = rows_of(sD + 32 * t, h);
-      uint64_t km[16];   // keep decisions of the 32 x 32 block: register tt's lane mask over the keys
-      if (DROP) {
-        kmask_ptr mp = (kmask_ptr)(reinterpret_cast<const uint64_t*>(p.bits) + ((bh * NT + wave) * NT + t) * 16);
-#pragma unroll
-        for (int tt = 0; tt < 16; ++tt) km[tt] = mp[tt];
-      }
-      bf16x8 pdh[2], pdl[2], dsh[2], dsl[2];
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        f32x8 pd, ds;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int tt = 8 * s2 + j;
-          const float pr = (A32_EXP & 1) ? S[tt] : __builtin_amdgcn_exp2f(S[tt]);
-          if (A32_EXP & 1) { pd[j] = pr; ds[j] = dA[tt]; } else
-          if (DROP) {
-            const float kf = __builtin_amdgcn_inverse_ballot_w64(km[tt]) ? pscale : 0.f;
-            pd[j] = pr * kf;
-            ds[j] = pr * fmaf(dA[tt], kf, -Dq[tt]);
-          } else {
-            pd[j] = pr;
-            ds[j] = pr * (dA[tt] - Dq[tt]);
-          }
-        }
-        split8(pd, pdh[s2], pdl[s2]);
-        split8(ds, dsh[s2], dsl[s2]);
-        // dS -> the wave's [key][query] scratch image: registers 4a .. 4a+3 of this half are queries 16 s2 + 8a + 4h + (0..3)
-        const s16x8 hv = __builtin_bit_cast(s16x8, dsh[s2]), lv = __builtin_bit_cast(s16x8, dsl[s2]);
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-          char* w8 = scr + p_chunk(r, 2 * s2 + a) + 8 * h;
-          *reinterpret_cast<s16x4*>(w8) = a ? __builtin_shufflevector(hv, hv, 4, 5, 6, 7) : __builtin_shufflevector(hv, hv, 0, 1, 2, 3);
-          *reinterpret_cast<s16x4*>(w8 + P_IMG) = a ? __builtin_shufflevector(lv, lv, 4, 5, 6, 7) : __builtin_shufflevector(lv, lv, 0, 1, 2, 3);
-        }
-      }
-      // S of the next tile starts from -lse (per query) + the key's mask adder
-      S = rows_of(sCS + 32 * tn, h);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) S[e] += adk;
-      A32_SWEEP(3 + 4 * s);
-      A32_SB();
-      // ---- matrix phase: ten products, fragments requested two products ahead ---------------------------------------------------
-      bf16x8 f2h, f2l, f3h, f3l, f4h, f4l, f5h, f5l, f6h, f6l, f7h, f7l, f8h, f8l, f9h, f9l;
-      A32_LD_TR(dimg, 1, f2h, f2l);
-      dV = mfma32x3(f0h, f0l, pdh[0], pdl[0], dV);   // dV^T[feature][key] += dO^T[feature][query] . Pd[query][key], queries 0..15
-      A32_SB();
-      A32_LD_TR(qimg, 1, f3h, f3l);
-      dK = mfma32x3(f1h, f1l, dsh[0], dsl[0], dK);   // dK^T += Q~^T . dS
-      A32_SB();
-      A32_LD_ROW(qn, 0, f4h, f4l);
-      dV = mfma32x3(f2h, f2l, pdh[1], pdl[1], dV);
-      A32_SB();
-      A32_LD_ROW(dn, 0, f5h, f5l);
-      dK = mfma32x3(f3h, f3l, dsh[1], dsl[1], dK);
-      A32_SB();
-      A32_LD_ROW(qn, 1, f6h, f6l);
-      S = mfma32x3(f4h, f4l, kBh[0], kBl[0], S);     // S[query][key] = Q~ . K^T of the next tile
-      A32_SB();
-      A32_LD_ROW(dn, 1, f7h, f7l);
-      dA = mfma32x3(f5h, f5l, vBh[0], vBl[0], zero16());
-      A32_SB();
-      A32_LD_SCR(0, f8h, f8l);
-      S = mfma32x3(f6h, f6l, kBh[1], kBl[1], S);
-      A32_SB();
-      A32_LD_SCR(1, f9h, f9l);
-      dA = mfma32x3(f7h, f7l, vBh[1], vBl[1], dA);
-      A32_SB();
-      // dQ^T[feature position][query] = K^T[.][key] . dS^T[key][query]  (B by transposed reads of the scratch image)
-      f32x16 dQp = mfma32x3(kTh[0], kTl[0], f8h, f8l, zero16());
-      dQp = mfma32x3(kTh[1], kTl[1], f9h, f9l, dQp);
-      A32_SWEEP(4 + 4 * s);
-      if (s > 0) {   // the accumulator's previous addition (wave w + 1, its step s - 1) must be in place
-        const volatile int* f = sflag + (wave + 1 < NT ? wave + 1 : 0);
-        while (*f < s) __builtin_amdgcn_s_sleep(1);
-        asm volatile("" ::: "memory");
-      }
-      char* acc = DQACC + t * P_TILE + lane * 16;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        f32x4* a4 = reinterpret_cast<f32x4*>(acc + j * 1024);
-        *a4 = *a4 + (f32x4){dQp[4 * j], dQp[4 * j + 1], dQp[4 * j + 2], dQp[4 * j + 3]};
-      }
-      asm volatile("" ::: "memory");
-      *reinterpret_cast<volatile int*>(sflag + wave) = s + 1;   // LDS operations of a wave complete in order: the sums are in place
-      A32_SWEEP(5 + 4 * s);
-    }
-    }
-    lds_barrier();   // every accumulator is complete
 
     // ---- results of this head for the wave's tokens: registers 8s .. 8s+7 = features 16s + 8h + (0..7) ----------------------------
     A32_MARK(8 + 10 * hd);
@@ -698,17 +902,10 @@ __global__ __launch_bounds__(512, 2) void attn32_bwd_kernel(A32BwdP p) {
     const f32x16 gk = dK * LN2;   // Q~ carries log2(e)
     const bool fold = p.dw_slab != nullptr;   // dWqkv / dbqkv formed here instead of writing dqkv for a weight-gradient launch
     if (live && p.dqkv != nullptr) {
-      const uint32_t dst = (uint32_t)(tok * (3 * HID) + 32 * hd + 8 * h);
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-#pragma unroll
-        for (int hf = 0; hf < 2; ++hf) {
-          const int o = 8 * s + 4 * hf;
-          st4(dqkvb, dst + 16 * s + 4 * hf, (f32x4){gq[o], gq[o + 1], gq[o + 2], gq[o + 3]});
-          st4(dqkvb, dst + HID + 16 * s + 4 * hf, (f32x4){gk[o], gk[o + 1], gk[o + 2], gk[o + 3]});
-          st4(dqkvb, dst + 2 * HID + 16 * s + 4 * hf, (f32x4){dV[o], dV[o + 1], dV[o + 2], dV[o + 3]});
-        }
-      }
+      float* dst = dqkvb + (uint32_t)(tok * (3 * HID) + 32 * hd + 8 * h);
+      acc_store_cols(dst, gq);
+      acc_store_cols(dst + HID, gk);
+      acc_store_cols(dst + 2 * HID, dV);
     }
     // dX^T[hidden][token] += W_j[hidden][feature] . g_j^T[feature][token], j = q, k, v: A by rows of the weight slices
     dx[0] = zero16(); dx[1] = zero16();
@@ -933,8 +1130,7 @@ __global__ __launch_bounds__(512, 2) void attn32_fwd_kernel(A32FwdP p) {
   }
   // (s_setprio(1) for waves 4.., the younger wave of every SIMD, was measured: forward 42.7 / 42.9 us with, 43.0 / 42.2 without)
 
-  const int64_t mval = (int)threadIdx.x < L ? p.mask[row0 + threadIdx.x] : 0;
-  const int any_key = mval != 0 ? 1 : 0;
+  const int64_t mval = a32_mask_value(p.mask + row0, L);
   for (int k = threadIdx.x; k < 192; k += nthreads) sbq[k] = p.bqkv[k];
 
   A32F_MARK(0);
@@ -985,10 +1181,8 @@ __global__ __launch_bounds__(512, 2) void attn32_fwd_kernel(A32FwdP p) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) rl_to_panels(rl, XIMG + wave * 2 * P_TILE, XIMG + wave * 2 * P_TILE + P_TILE, i, xr[i]);
   A32F_MARK(2);
-  const float amax = __syncthreads_or(any_key) ? 0.0f : -1e9f;   // (barrier: the weight images and sbq are in place)
+  const bool dead = a32_mask_adders(mval, L, NT, sAdd).dead;   // (its barrier: the weight images and sbq are in place)
   A32F_MARK(3);
-  if ((int)threadIdx.x < NT * 32)
-    sAdd[threadIdx.x] = (int)threadIdx.x < L ? (((1.0f - (float)mval) * -1e9f) - amax) * LOG2E : -INFINITY;
 
   // ---- q~, k, v of both heads (transposed), the wave's tokens ------------------------------------------------------------------
   bf16x8 qBh[2][2], qBl[2][2];     // [head][k-step]: Q~^T[feature][query] as the B operand of S^T = K . Q~^T
@@ -1025,7 +1219,7 @@ __global__ __launch_bounds__(512, 2) void attn32_fwd_kernel(A32FwdP p) {
       acc[0] = acc[0] * LOG2E;
       if (CQ) {   // (every key masked: zero, as the dense form's operand)
         const int js_ = live ? sSlot[tok] : -1;
-        if (js_ >= 0) acc_rows_at(QC + (2 * hd + (js_ >> 5)) * P_TILE, js_ & 31, h, acc[0] * (amax != 0.0f ? 0.0f : 1.0f));
+        if (js_ >= 0) acc_rows_at(QC + (2 * hd + (js_ >> 5)) * P_TILE, js_ & 31, h, acc[0] * (dead ? 0.0f : 1.0f));
       } else {
 #pragma unroll
         for (int s = 0; s < 2; ++s) acc_frag(acc[0], s, qBh[hd][s], qBl[hd][s]);
@@ -1033,7 +1227,7 @@ __global__ __launch_bounds__(512, 2) void attn32_fwd_kernel(A32FwdP p) {
       kT[hd] = acc[1]; vT[hd] = acc[2];
     }
   }
-  if (amax != 0.0f) {   // every key masked: Keras' -1e9 absorbs the scores -> a uniform softmax over the L keys (lse = log L)
+  if (dead) {   // every key masked: Keras' -1e9 absorbs the scores -> a uniform softmax over the L keys (lse = log L)
 #pragma unroll
     for (int hd = 0; hd < 2; ++hd)
 #pragma unroll
@@ -1058,9 +1252,7 @@ __global__ __launch_bounds__(512, 2) void attn32_fwd_kernel(A32FwdP p) {
   // ---- attention, one head at a time --------------------------------------------------------------------------------------
   const DropCtx dcp = b4r_drop_ctx(p.drop_p);
   f32x16 O[2];
-  const int qt = wave;
-  const int slot = (r & 24) | ((r & 3) << 1) | ((r >> 2) & 1);   // query 16s + 8a + 4h' + b -> 16s + 8a + 2b + h' (the backward's register pairs)
-  if (CQ) {
+  if (CQ) {   // a32_fwd_compact_tile per (head, compact tile), then a32_fwd_owner_merge by waves 0 .. NQ - 1
     const f32x16 add = rows_of(sAdd + 32 * wave, h);
     const bool qwave = wave < NQ;
 #pragma unroll
@@ -1071,153 +1263,43 @@ __global__ __launch_bounds__(512, 2) void attn32_fwd_kernel(A32FwdP p) {
       float* const ms_h = sMS + hd * (NT * 2 * 64);
       bf16x8 kAh[2], kAl[2];
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) { kAh[ks] = row_at(kown + lk.rowc[ks]); kAl[ks] = row_at(kown + P_IMG + lk.rowc[ks]); }
+      for (int ks = 0; ks < 2; ++ks) a32_ld_row(kown, lk, ks, kAh[ks], kAl[ks]);
       f32x16 Op[2];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         Op[t] = zero16();
         if (t >= NQ) continue;   // (block-uniform)
         const int tq = sTok[32 * t + r];   // this lane's query: the token of slot 32 t + r, -1: empty
-        f32x16 S = add;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const char* qi = QC + (2 * hd + t) * P_TILE + lk.rowc[ks];
-          S = mfma32x3(kAh[ks], kAl[ks], row_at(qi), row_at(qi + P_IMG), S);   // S^T[key][query] = K_w . Q~_t^T
-        }
-        float m = S[0];
-#pragma unroll
-        for (int e = 1; e < 16; ++e) m = fmaxf(m, S[e]);
-        m = fmaxf(m, other_half(m, h));
-        const float mref = m == -INFINITY ? 0.0f : m;   // a tile of pad keys only: every term is 0
-        float sum = 0.f;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { S[e] = __builtin_amdgcn_exp2f(S[e] - mref); sum += S[e]; }
-        sum += other_half(sum, h);
-        if (h == 0) { float* ms = ms_h + ((wave * 2 + t) * 32 + r) * 2; ms[0] = m; ms[1] = sum; }
-        if (DROP) {
-          uint32_t word = 0;
-          const uint64_t dbase = ((uint64_t)bh * L + (uint64_t)max(tq, 0)) * (uint64_t)B4R_ATTN_PITCH;
-#pragma unroll
-          for (int gp = 0; gp < 4; ++gp) {
-            const B4rKeep4 k4 = b4r_keep4p(dcp, dbase + (uint64_t)(32 * wave + 8 * gp + 4 * h));
-#pragma unroll
-            for (int e = 0; e < 4; ++e) S[4 * gp + e] = k4.k[e] ? S[4 * gp + e] : 0.f;
-            word |= k4.bits() << (8 * gp + 4 * h);
-          }
-          word |= other_half_u(word, h);
-          if (h == 0 && tq >= 0) p.bits[((bh * NT + wave) * NT + (tq >> 5)) * 32 + a32_slot_perm(tq & 31)] = word;
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          bf16x8 ph, pl;
-          acc_frag(S, s2, ph, pl);
-          Op[t] = mfma32x3(tr_pair(vown + lk.trp[s2][0], vown + lk.trp[s2][1]), tr_pair(vown + P_IMG + lk.trp[s2][0], vown + P_IMG + lk.trp[s2][1]),
-                           ph, pl, Op[t]);
-        }
+        Op[t] = a32_fwd_compact_tile<DROP>(lk, wave, L, add, kAh, kAl, QC + (2 * hd + t) * P_TILE, vown, ms_h + ((wave * 2 + t) * 32 + r) * 2,
+                                           dcp, bh, max(tq, 0), p.bits + ((bh * NT + wave) * NT + (max(tq, 0) >> 5)) * 32, a32_slot_perm(max(tq, 0) & 31), tq >= 0);
       }
       // the partials go over the wave's own K / V tile of this head (its reads of them above are the wave's own, consumed by products)
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         if (t >= NQ) continue;
-        char* dst = (t == 0 ? kown : vown) + lane * 16;
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj)
-          *reinterpret_cast<f32x4*>(dst + jj * 1024) = (f32x4){Op[t][4 * jj], Op[t][4 * jj + 1], Op[t][4 * jj + 2], Op[t][4 * jj + 3]};
+        a32_put_partial(t == 0 ? kown : vown, lane, Op[t]);
       }
       lds_barrier();
       O[hd] = zero16();
       if (qwave) {   // merge of compact tile t = wave
         const int tq = sTok[32 * wave + r];
-        float M = -INFINITY;
-        for (int w_ = 0; w_ < NT; ++w_) M = fmaxf(M, ms_h[((w_ * 2 + wave) * 32 + r) * 2]);
-        float tot = 0.f;
-        for (int w_ = 0; w_ < NT; ++w_) {
-          const float* ms = ms_h + ((w_ * 2 + wave) * 32 + r) * 2;
-          const float a = ms[0] == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(ms[0] - M);
-          tot = fmaf(a, ms[1], tot);
-          const char* srcp = KV + ((2 * hd + (wave == 0 ? 0 : 1)) * NT + w_) * P_TILE + lane * 16;
-#pragma unroll
-          for (int jj = 0; jj < 4; ++jj) {
-            const f32x4 o4 = *reinterpret_cast<const f32x4*>(srcp + jj * 1024);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) O[hd][4 * jj + e] = fmaf(a, o4[e], O[hd][4 * jj + e]);
-          }
-        }
+        float M, tot;
+        O[hd] = a32_fwd_owner_merge(ms_h + (wave * 32 + r) * 2, 2 * 64, KV + (2 * hd + (wave == 0 ? 0 : 1)) * NT * P_TILE, NT, lane, M, tot);
         const float inv = (DROP ? dcp.scale : 1.0f) / tot;
         O[hd] = O[hd] * inv;
-        if (h == 0 && tq >= 0 && p.lse) p.lse[bh * L + tq] = M * LN2 + __logf(tot);
+        if (h == 0 && tq >= 0 && p.lse) p.lse[bh * L + tq] = a32_lse(M, tot);
       }
     }
   } else {
-#pragma unroll
-  for (int hd = 0; hd < 2; ++hd) {
-    const char* kimg = KV + (2 * hd) * NT * P_TILE;
-    const char* vimg = KV + (2 * hd + 1) * NT * P_TILE;
-    const int64_t bh = (int64_t)b * 2 + hd;
-    f32x16 S[NTT];
-    float m = -INFINITY;
-#pragma unroll
-    for (int t = 0; t < NTT; ++t) {
-      if (t < NT) {   // (wave-uniform; NTT is the compile-time bound of the token tiles)
-        S[t] = rows_of(sAdd + 32 * t, h);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const char* ka = kimg + t * P_TILE + lk.rowc[ks];
-          S[t] = mfma32x3(row_at(ka), row_at(ka + P_IMG), qBh[hd][ks], qBl[hd][ks], S[t]);
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) S[t][e] = -INFINITY;
-      }
-    }
-    A32F_MARK(8 + 4 * hd);
-#pragma unroll
-    for (int t = 0; t < NTT; ++t)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) m = fmaxf(m, S[t][e]);
-    m = fmaxf(m, other_half(m, h));
-    float sum = 0.f;
-#pragma unroll
-    for (int t = 0; t < NTT; ++t)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) { S[t][e] = __builtin_amdgcn_exp2f(S[t][e] - m); sum += S[t][e]; }
-    sum += other_half(sum, h);
-    const float inv = 1.0f / sum;
-    if (h == 0 && live && p.lse) p.lse[bh * L + tok] = m * LN2 + __logf(sum);
-    A32F_MARK(9 + 4 * hd);
-    O[hd] = zero16();
-    const uint64_t dbase = ((uint64_t)bh * L + (uint64_t)(live ? tok : 0)) * (uint64_t)B4R_ATTN_PITCH;
-#pragma unroll
-    for (int t = 0; t < NTT; ++t) {
-      if (t >= NT) continue;
-      if (DROP) {
-        uint32_t word = 0;
-        const float sc = inv * dcp.scale;
-#pragma unroll
-        for (int gp = 0; gp < 4; ++gp) {
-          const B4rKeep4 k4 = b4r_keep4p(dcp, dbase + (uint64_t)(32 * t + 8 * gp + 4 * h));
-#pragma unroll
-          for (int e = 0; e < 4; ++e) S[t][4 * gp + e] = k4.k[e] ? S[t][4 * gp + e] * sc : 0.f;
-          word |= k4.bits() << (8 * gp + 4 * h);
-        }
-        word |= other_half_u(word, h);
-        if (h == 0 && live) p.bits[((bh * NT + t) * NT + qt) * 32 + slot] = word;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) S[t][e] *= inv;
-      }
-      // O^T[feature][query] += V^T[feature][keys of tile t] . Pd^T[key][query]
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        bf16x8 ph, pl;
-        acc_frag(S[t], s2, ph, pl);
-        const char* va = vimg + t * P_TILE;
-        O[hd] = mfma32x3(tr_pair(va + lk.trp[s2][0], va + lk.trp[s2][1]), tr_pair(va + P_IMG + lk.trp[s2][0], va + P_IMG + lk.trp[s2][1]),
-                         ph, pl, O[hd]);
-      }
-    }
-  }
-
+    // Two calls, not a loop over the heads: the function's own loops are unrolled before it is inlined here, and out of a loop
+    // around it hipcc hoists every offset that is the same for both heads (27 LDS addresses, 27 64-bit hash indices) and keeps
+    // them in registers across the first head: <7, true> then spills.
+    auto head = [&](int hd) __attribute__((always_inline)) {
+      return a32_fwd_dense_head<NTT, DROP, 3>(lk, wave, NT, L, KV + (2 * hd) * NT * P_TILE, KV + (2 * hd + 1) * NT * P_TILE, sAdd, qBh[hd],
+                                              qBl[hd], dcp, (int64_t)b * 2 + hd, tok, live, p.lse, p.bits, 8 + 4 * hd);
+    };
+    O[0] = head(0);
+    O[1] = head(1);
   }
   A32F_MARK(16);
   // ---- y^T[hidden][token] = Wo^T . ctx^T: registers 8s .. 8s+7 of O are context columns 16s + 8h + .. of the head: natural k order
@@ -1322,8 +1404,9 @@ __global__ __launch_bounds__(512, 2) void attn32_fwd_kernel(A32FwdP p) {
 // ---------------------------------------------------------------------------------------------------------------------------
 // The attention CORE alone on 32-token tiles, for every hidden size with 32-wide heads (H = 128: 4 heads, H = 256: 8 heads; the
 // layers around it are tile products there): one workgroup per (sequence, head), q | k | v read from the [N, 3H] projection output
-// (q pre-scaled by 1/sqrt(d): b4r_attn_fwd's contract), the same score / softmax / dropout / sweep code as the resident kernels above
-// -- K and V images in LDS, the score row of a query in one lane pair, dK / dV in registers, the dQ partials ordered by flags.
+// (q pre-scaled by 1/sqrt(d): b4r_attn_fwd's contract), then the resident kernels' own score / softmax / dropout / sweep code
+// (a32_fwd_dense_head, a32_bwd_dense_sweep; TERMS = 1 in the bf16 mode) -- K and V images in LDS, the score row of a query in one
+// lane pair, dK / dV in registers, the dQ partials ordered by flags.
 // Replaces round 1's attn_rx_fwd / attn_rx_dq / attn_rx_dkv kernels (16-token tiles, three launches) where L <= 224.
 // ---------------------------------------------------------------------------------------------------------------------------
 struct A32CoreFwdP {
@@ -1359,15 +1442,12 @@ __global__ __launch_bounds__(512, 2) void attn32_core_fwd_kernel(A32CoreFwdP p) 
   const int64_t bh = (int64_t)b * p.heads + head;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   A32_LANE_CONSTS();
-  const int64_t mval = (int)threadIdx.x < L ? p.mask[row0 + threadIdx.x] : 0;
-  const int any_key = mval != 0 ? 1 : 0;
+  const int64_t mval = a32_mask_value(p.mask + row0, L);
   // the wave's tokens: q~ = q . log2(e) as the B operand of S^T = K . Q~^T, k and v rows -> the images every wave reads
   const float* const src = p.qkv + (row0 + tokc) * (3 * Hh) + 32 * head;
   f32x16 qa = load_acc_layout(src, h), kacc = load_acc_layout(src + Hh, h), vacc = load_acc_layout(src + 2 * Hh, h);
-  const float amax = __syncthreads_or(any_key) ? 0.0f : -1e9f;
-  if ((int)threadIdx.x < NT * 32)
-    sAdd[threadIdx.x] = (int)threadIdx.x < L ? (((1.0f - (float)mval) * -1e9f) - amax) * LOG2E : -INFINITY;
-  qa = qa * (amax != 0.0f ? 0.0f : LOG2E);   // every key masked: Keras' -1e9 absorbs the scores -> a uniform softmax over the L keys
+  const bool dead = a32_mask_adders(mval, L, NT, sAdd).dead;
+  qa = qa * (dead ? 0.0f : LOG2E);   // every key masked: Keras' -1e9 absorbs the scores -> a uniform softmax over the L keys
   bf16x8 qBh[2], qBl[2];
 #pragma unroll
   for (int s = 0; s < 2; ++s) acc_frag(qa, s, qBh[s], qBl[s]);
@@ -1377,82 +1457,9 @@ __global__ __launch_bounds__(512, 2) void attn32_core_fwd_kernel(A32CoreFwdP p) 
   lds_barrier();
 
   const DropCtx dcp = b4r_drop_ctx(p.drop_p);
-  f32x16 O;
-  const int qt = wave;
-  const int slot = (r & 24) | ((r & 3) << 1) | ((r >> 2) & 1);   // query 16s + 8a + 4h' + b -> 16s + 8a + 2b + h' (the backward's register pairs)
-  {
-  f32x16 S[NTT];
-  float m = -INFINITY;
-#pragma unroll
-  for (int t = 0; t < NTT; ++t) {
-    if (t < NT) {   // (wave-uniform; NTT is the compile-time bound of the token tiles)
-      S[t] = rows_of(sAdd + 32 * t, h);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const char* ka = kimg + t * P_TILE + lk.rowc[ks];
-        S[t] = mfma32x3<TERMS>(row_at(ka), row_at(ka + P_IMG), qBh[ks], qBl[ks], S[t]);
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) S[t][e] = -INFINITY;
-    }
-  }
-  
-#pragma unroll
-  for (int t = 0; t < NTT; ++t)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) m = fmaxf(m, S[t][e]);
-  m = fmaxf(m, other_half(m, h));
-  float sum = 0.f;
-#pragma unroll
-  for (int t = 0; t < NTT; ++t)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { S[t][e] = __builtin_amdgcn_exp2f(S[t][e] - m); sum += S[t][e]; }
-  sum += other_half(sum, h);
-  const float inv = 1.0f / sum;
-  if (h == 0 && live && p.lse) p.lse[bh * L + tok] = m * LN2 + __logf(sum);
-  
-  O = zero16();
-  const uint64_t dbase = ((uint64_t)bh * L + (uint64_t)(live ? tok : 0)) * (uint64_t)B4R_ATTN_PITCH;
-#pragma unroll
-  for (int t = 0; t < NTT; ++t) {
-    if (t >= NT) continue;
-    if (DROP) {
-      uint32_t word = 0;
-      const float sc = inv * dcp.scale;
-#pragma unroll
-      for (int gp = 0; gp < 4; ++gp) {
-        const B4rKeep4 k4 = b4r_keep4p(dcp, dbase + (uint64_t)(32 * t + 8 * gp + 4 * h));
-#pragma unroll
-        for (int e = 0; e < 4; ++e) S[t][4 * gp + e] = k4.k[e] ? S[t][4 * gp + e] * sc : 0.f;
-        word |= k4.bits() << (8 * gp + 4 * h);
-      }
-      word |= other_half_u(word, h);
-      if (h == 0 && live) p.bits[((bh * NT + t) * NT + qt) * 32 + slot] = word;
-    } else {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) S[t][e] *= inv;
-    }
-    // O^T[feature][query] += V^T[feature][keys of tile t] . Pd^T[key][query]
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      bf16x8 ph, pl;
-      acc_frag(S[t], s2, ph, pl);
-      const char* va = vimg + t * P_TILE;
-      O = mfma32x3<TERMS>(tr_pair(va + lk.trp[s2][0], va + lk.trp[s2][1]), tr_pair(va + P_IMG + lk.trp[s2][0], va + P_IMG + lk.trp[s2][1]),
-                       ph, pl, O);
-    }
-  }
-  }
+  const f32x16 O = a32_fwd_dense_head<NTT, DROP, TERMS>(lk, wave, NT, L, kimg, vimg, sAdd, qBh, qBl, dcp, bh, tok, live, p.lse, p.bits, 8);
   // O's registers 8s .. 8s+7 are context columns 16s + 8h + (0..7) of the head (V image in swapped column order, transposed reads)
-  if (live) {
-    float* dst = p.ctx + (row0 + tok) * Hh + 32 * head + 8 * h;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      *reinterpret_cast<f32x4*>(dst + 16 * s) = (f32x4){O[8 * s], O[8 * s + 1], O[8 * s + 2], O[8 * s + 3]};
-      *reinterpret_cast<f32x4*>(dst + 16 * s + 4) = (f32x4){O[8 * s + 4], O[8 * s + 5], O[8 * s + 6], O[8 * s + 7]};
-    }
-  }
+  if (live) acc_store_cols(p.ctx + (row0 + tok) * Hh + 32 * head + 8 * h, O);
 }
 
 struct A32CoreBwdP {
@@ -1481,25 +1488,20 @@ __global__ __launch_bounds__(512, 2) void attn32_core_bwd_kernel(A32CoreBwdP p) 
   const int Hh = 32 * p.heads;
   const int64_t row0 = (int64_t)b * L;
   const int64_t bh = (int64_t)b * p.heads + head;
-  constexpr int hd = 0; (void)hd;                     // (the stamp macros of the resident kernel name a head)
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   char* const scr = SCRALL + wave * P_TILE;
   char* const ownA = QIMG + wave * P_TILE;
   char* const ownB = DOIMG + wave * P_TILE;
   char* const ownC = DQACC + wave * P_TILE;
   A32_LANE_CONSTS();
-  const int64_t mval = (int)threadIdx.x < L ? p.mask[row0 + threadIdx.x] : 0;
-  const int any_key = mval != 0 ? 1 : 0;
+  const int64_t mval = a32_mask_value(p.mask + row0, L);
   // the wave's tokens in accumulator layout: q~, k, v of the head, dctx and ctx columns of the head, the query's lse
   const float* const src = p.qkv + (row0 + tokc) * (3 * Hh) + 32 * head;
   f32x16 qT = load_acc_layout(src, h), kT = load_acc_layout(src + Hh, h), vT = load_acc_layout(src + 2 * Hh, h);
   const f32x16 dcT = load_acc_layout(p.dctx + (row0 + tokc) * Hh + 32 * head, h);
   const f32x16 cxT = load_acc_layout(p.ctx + (row0 + tokc) * Hh + 32 * head, h);
   const float lse_q = live ? p.lse[bh * L + tok] : INFINITY;
-  const float amax = __syncthreads_or(any_key) ? 0.0f : -1e9f;
-  const bool dead = amax != 0.0f;   // every key masked: Keras' -1e9 absorbs the scores, the softmax is uniform over all L keys
-  if ((int)threadIdx.x < NT * 32)
-    sAdd[threadIdx.x] = (int)threadIdx.x < L ? (((1.0f - (float)mval) * -1e9f) - amax) * LOG2E : -INFINITY;
+  const bool dead = a32_mask_adders(mval, L, NT, sAdd).dead;
   const DropCtx dcp = b4r_drop_ctx(p.drop_p);
   const float pscale = DROP ? dcp.scale : 1.0f;
   qT = qT * LOG2E;
@@ -1528,7 +1530,7 @@ __global__ __launch_bounds__(512, 2) void attn32_core_bwd_kernel(A32CoreBwdP p) 
   if (lane == 0) sflag[wave] = 0;
   lds_barrier();   // images, D, -lse of every tile in place; accumulators zero; (the K^T reads above have landed: lgkmcnt(0))
 
-  f32x16 dK = zero16(), dV = zero16(), S, dA;
+  f32x16 dK = zero16(), dV = zero16();
   const float adk = sAdd[tok];
   if (dead) {   // S = -lse for every key: the scores are absorbed by the mask adder
 #pragma unroll
@@ -1536,133 +1538,8 @@ __global__ __launch_bounds__(512, 2) void attn32_core_bwd_kernel(A32CoreBwdP p) 
 #pragma unroll
       for (int e = 0; e < 8; ++e) { kBh[ks][e] = (__bf16)0.f; kBl[ks][e] = (__bf16)0.f; }
   }
-#define A32_LD_TR(img, s2, H, Lo)                                                \
-H = tr_pair((img) + lk.trp[s2][0], (img) + lk.trp[s2][1]);                     \
-Lo = tr_pair((img) + P_IMG + lk.trp[s2][0], (img) + P_IMG + lk.trp[s2][1])
-#define A32_LD_ROW(img, ks, H, Lo)                                               \
-H = row_at((img) + lk.rowc[ks]);                                               \
-Lo = row_at((img) + P_IMG + lk.rowc[ks])
-#define A32_LD_SCR(ks, H, Lo)                                                    \
-H = tr_pair(scr + lk.trn[ks][0], scr + lk.trn[ks][1]);                         \
-Lo = tr_pair(scr + P_IMG + lk.trn[ks][0], scr + P_IMG + lk.trn[ks][1])
-#define A32_SB() __builtin_amdgcn_sched_barrier(0)
-  auto tile_of = [&](int s) __attribute__((always_inline)) { const int t = wave + s; return t >= NT ? t - NT : t; };
-  typedef const __attribute__((address_space(4))) uint64_t* kmask_ptr;   // constant address space: scalar loads
-  {   // S, dA of the first tile
-    const char* qimg = QIMG + wave * P_TILE;
-    const char* dimg = DOIMG + wave * P_TILE;
-    S = rows_of(sCS + 32 * wave, h);
-#pragma unroll
-    for (int e = 0; e < 16; ++e) S[e] += adk;
-    dA = zero16();
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 ah, al;
-      A32_LD_ROW(qimg, ks, ah, al);
-      S = mfma32x3<TERMS>(ah, al, kBh[ks], kBl[ks], S);
-      A32_LD_ROW(dimg, ks, ah, al);
-      dA = mfma32x3<TERMS>(ah, al, vBh[ks], vBl[ks], dA);
-    }
-  }
-  for (int s = 0; s < NT; ++s) {
-    const int t = tile_of(s), tn = tile_of(s + 1);   // (the last step forms S / dA of a tile nobody uses: no branch in the body)
-    const char* qimg = QIMG + t * P_TILE;
-    const char* dimg = DOIMG + t * P_TILE;
-    const char* qn = QIMG + tn * P_TILE;
-    const char* dn = DOIMG + tn * P_TILE;
-    A32_SWEEP(2 + 4 * s);
-    // ---- vector phase ------------------------------------------------------------------------------------------------------
-    bf16x8 f0h, f0l, f1h, f1l;
-    A32_LD_TR(dimg, 0, f0h, f0l);   // the first two products' fragments travel during the vector phase
-    A32_LD_TR(qimg, 0, f1h, f1l);
-    const f32x16 Dq = rows_of(sD + 32 * t, h);
-    uint64_t km[16];   // keep decisions of the 32 x 32 block: register tt's lane mask over the keys
-    if (DROP) {
-      kmask_ptr mp = (kmask_ptr)(reinterpret_cast<const uint64_t*>(p.bits) + ((bh * NT + wave) * NT + t) * 16);
-#pragma unroll
-      for (int tt = 0; tt < 16; ++tt) km[tt] = mp[tt];
-    }
-    bf16x8 pdh[2], pdl[2], dsh[2], dsl[2];
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      f32x8 pd, ds;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int tt = 8 * s2 + j;
-        const float pr = (A32_EXP & 1) ? S[tt] : __builtin_amdgcn_exp2f(S[tt]);
-        if (A32_EXP & 1) { pd[j] = pr; ds[j] = dA[tt]; } else
-        if (DROP) {
-          const float kf = __builtin_amdgcn_inverse_ballot_w64(km[tt]) ? pscale : 0.f;
-          pd[j] = pr * kf;
-          ds[j] = pr * fmaf(dA[tt], kf, -Dq[tt]);
-        } else {
-          pd[j] = pr;
-          ds[j] = pr * (dA[tt] - Dq[tt]);
-        }
-      }
-      split8(pd, pdh[s2], pdl[s2]);
-      split8(ds, dsh[s2], dsl[s2]);
-      // dS -> the wave's [key][query] scratch image: registers 4a .. 4a+3 of this half are queries 16 s2 + 8a + 4h + (0..3)
-      const s16x8 hv = __builtin_bit_cast(s16x8, dsh[s2]), lv = __builtin_bit_cast(s16x8, dsl[s2]);
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        char* w8 = scr + p_chunk(r, 2 * s2 + a) + 8 * h;
-        *reinterpret_cast<s16x4*>(w8) = a ? __builtin_shufflevector(hv, hv, 4, 5, 6, 7) : __builtin_shufflevector(hv, hv, 0, 1, 2, 3);
-        *reinterpret_cast<s16x4*>(w8 + P_IMG) = a ? __builtin_shufflevector(lv, lv, 4, 5, 6, 7) : __builtin_shufflevector(lv, lv, 0, 1, 2, 3);
-      }
-    }
-    // S of the next tile starts from -lse (per query) + the key's mask adder
-    S = rows_of(sCS + 32 * tn, h);
-#pragma unroll
-    for (int e = 0; e < 16; ++e) S[e] += adk;
-    A32_SWEEP(3 + 4 * s);
-    A32_SB();
-    // ---- matrix phase: ten products, fragments requested two products ahead ---------------------------------------------------
-    bf16x8 f2h, f2l, f3h, f3l, f4h, f4l, f5h, f5l, f6h, f6l, f7h, f7l, f8h, f8l, f9h, f9l;
-    A32_LD_TR(dimg, 1, f2h, f2l);
-    dV = mfma32x3<TERMS>(f0h, f0l, pdh[0], pdl[0], dV);   // dV^T[feature][key] += dO^T[feature][query] . Pd[query][key], queries 0..15
-    A32_SB();
-    A32_LD_TR(qimg, 1, f3h, f3l);
-    dK = mfma32x3<TERMS>(f1h, f1l, dsh[0], dsl[0], dK);   // dK^T += Q~^T . dS
-    A32_SB();
-    A32_LD_ROW(qn, 0, f4h, f4l);
-    dV = mfma32x3<TERMS>(f2h, f2l, pdh[1], pdl[1], dV);
-    A32_SB();
-    A32_LD_ROW(dn, 0, f5h, f5l);
-    dK = mfma32x3<TERMS>(f3h, f3l, dsh[1], dsl[1], dK);
-    A32_SB();
-    A32_LD_ROW(qn, 1, f6h, f6l);
-    S = mfma32x3<TERMS>(f4h, f4l, kBh[0], kBl[0], S);     // S[query][key] = Q~ . K^T of the next tile
-    A32_SB();
-    A32_LD_ROW(dn, 1, f7h, f7l);
-    dA = mfma32x3<TERMS>(f5h, f5l, vBh[0], vBl[0], zero16());
-    A32_SB();
-    A32_LD_SCR(0, f8h, f8l);
-    S = mfma32x3<TERMS>(f6h, f6l, kBh[1], kBl[1], S);
-    A32_SB();
-    A32_LD_SCR(1, f9h, f9l);
-    dA = mfma32x3<TERMS>(f7h, f7l, vBh[1], vBl[1], dA);
-    A32_SB();
-    // dQ^T[feature position][query] = K^T[.][key] . dS^T[key][query]  (B by transposed reads of the scratch image)
-    f32x16 dQp = mfma32x3<TERMS>(kTh[0], kTl[0], f8h, f8l, zero16());
-    dQp = mfma32x3<TERMS>(kTh[1], kTl[1], f9h, f9l, dQp);
-    A32_SWEEP(4 + 4 * s);
-    if (s > 0) {   // the accumulator's previous addition (wave w + 1, its step s - 1) must be in place
-      const volatile int* f = sflag + (wave + 1 < NT ? wave + 1 : 0);
-      while (*f < s) __builtin_amdgcn_s_sleep(1);
-      asm volatile("" ::: "memory");
-    }
-    char* acc = DQACC + t * P_TILE + lane * 16;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      f32x4* a4 = reinterpret_cast<f32x4*>(acc + j * 1024);
-      *a4 = *a4 + (f32x4){dQp[4 * j], dQp[4 * j + 1], dQp[4 * j + 2], dQp[4 * j + 3]};
-    }
-    asm volatile("" ::: "memory");
-    *reinterpret_cast<volatile int*>(sflag + wave) = s + 1;   // LDS operations of a wave complete in order: the sums are in place
-    A32_SWEEP(5 + 4 * s);
-  }
-  lds_barrier();   // every accumulator is complete
+  a32_bwd_dense_sweep<DROP, TERMS>(lk, lane, wave, NT, QIMG, DOIMG, DQACC, scr, sCS, sD, adk, sflag, p.bits, bh, 0, pscale, kBh, kBl, vBh,
+                                   vBl, kTh, kTl, dK, dV);
 
   // results for the wave's tokens: registers 8s .. 8s+7 = features 16s + 8h + (0..7)
   if (live) {
@@ -1673,18 +1550,10 @@ Lo = tr_pair(scr + P_IMG + lk.trn[ks][0], scr + P_IMG + lk.trn[ks][1])
 #pragma unroll
       for (int e = 0; e < 4; ++e) gq[4 * j + e] = a4[e] * p.qscale;
     }
-    const f32x16 gk = dK * LN2;   // Q~ carries log2(e)
     float* dst = p.dqkv + (row0 + tok) * (3 * Hh) + 32 * head + 8 * h;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-        const int o = 8 * s + 4 * hf;
-        *reinterpret_cast<f32x4*>(dst + 16 * s + 4 * hf) = (f32x4){gq[o], gq[o + 1], gq[o + 2], gq[o + 3]};
-        *reinterpret_cast<f32x4*>(dst + Hh + 16 * s + 4 * hf) = (f32x4){gk[o], gk[o + 1], gk[o + 2], gk[o + 3]};
-        *reinterpret_cast<f32x4*>(dst + 2 * Hh + 16 * s + 4 * hf) = (f32x4){dV[o], dV[o + 1], dV[o + 2], dV[o + 3]};
-      }
-    }
+    acc_store_cols(dst, gq);
+    acc_store_cols(dst + Hh, dK, LN2);   // Q~ carries log2(e)
+    acc_store_cols(dst + 2 * Hh, dV);
   }
 }
 
@@ -1692,10 +1561,15 @@ Lo = tr_pair(scr + P_IMG + lk.trn[ks][0], scr + P_IMG + lk.trn[ks][1])
 // The attention core with the QUERIES restricted to the masked-LM slots (the last encoder layer of a train step or of an evaluation
 // forward: only the rows the head gathers are read downstream, B4R_FLAG_HEAD_ROWS_ONLY).  Keys and values are all L tokens of the
 // sequence, queries the P <= 64 slot positions: one or two COMPACT query tiles (query j of a sequence = its slot j, token
-// clamp(position[b, j])), outputs in compact [B * P, .] tensors.  Forks of the two kernels above:
-//   forward  -- every wave still writes the K / V images of its 32 tokens; waves 0 .. NQ - 1 then each sweep one compact query tile;
-//   backward -- key owners as above, but a wave walks the NQ compact query tiles itself (no rotation, no step barrier) and keeps its dQ
-//               partials in registers; they are summed over the key owners in wave order afterwards (ordered: bitwise reproducible).
+// clamp(position[b, j])), outputs in compact [B * P, .] tensors.  The core kernels' prologue, then the compact sweeps that the
+// resident kernels' CQ form runs too:
+//   forward  -- every wave writes the K / V images of its 32 tokens and owns those keys for every compact query tile
+//               (a32_fwd_compact_tile); waves 0 .. NQ - 1 then merge the key owners' partials of their tile (a32_fwd_owner_merge);
+//   backward -- key owners as above, but a wave walks the NQ compact query tiles itself (a32_bwd_compact_tile: no rotation, no step
+//               barrier) and keeps its dQ partials in registers; they are summed over the key owners in wave order afterwards
+//               (a32_bwd_owner_sum; ordered: bitwise reproducible).
+// What differs from the CQ form is where things come from and go: the query's token from `pos` (there: the slot table in LDS), the
+// keep masks by scalar loads from bits_c (there: regathered words in LDS), sMS of pitch NQ (there: 2), results in compact tensors.
 // Dropout decisions are those of the (token query, key) pairs (the same counter hash index); the decision words live in a compact
 // buffer of their own, [B][head][key tile][compact query tile][32].  Padded slots repeat position 0 with zero gradient; their dq rows
 // are not written (a labelled slot may share that token).
@@ -1729,8 +1603,7 @@ __global__ __launch_bounds__(512, 2) void attn32_slotq_fwd_kernel(A32SlotFwdP p)
   const int64_t bh = (int64_t)b * p.heads + head;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   A32_LANE_CONSTS();
-  const int64_t mval = (int)threadIdx.x < L ? p.mask[row0 + threadIdx.x] : 0;
-  const int any_key = mval != 0 ? 1 : 0;
+  const int64_t mval = a32_mask_value(p.mask + row0, L);
   const float* const src = p.qkv + (row0 + tokc) * (3 * Hh) + 32 * head;
   f32x16 kacc = load_acc_layout(src + Hh, h), vacc = load_acc_layout(src + 2 * Hh, h);
   // the wave's compact queries (waves 0 .. NQ - 1)
@@ -1743,10 +1616,8 @@ __global__ __launch_bounds__(512, 2) void attn32_slotq_fwd_kernel(A32SlotFwdP p)
     const int posq = (int)(pq < 0 ? 0 : (pq >= L ? L - 1 : pq));
     qa = load_acc_layout(p.qkv + (row0 + posq) * (3 * Hh) + 32 * head, h);
   }
-  const float amax = __syncthreads_or(any_key) ? 0.0f : -1e9f;
-  if ((int)threadIdx.x < NT * 32)
-    sAdd[threadIdx.x] = (int)threadIdx.x < L ? (((1.0f - (float)mval) * -1e9f) - amax) * LOG2E : -INFINITY;
-  qa = qa * (amax != 0.0f ? 0.0f : LOG2E);   // every key masked: Keras' -1e9 absorbs the scores -> a uniform softmax over the L keys
+  const bool dead = a32_mask_adders(mval, L, NT, sAdd).dead;
+  qa = qa * (dead ? 0.0f : LOG2E);   // every key masked: Keras' -1e9 absorbs the scores -> a uniform softmax over the L keys
   if (qwave) acc_to_rows(QIMG + wave * P_TILE, lk, qa);
   if (!live) { kacc = zero16(); vacc = zero16(); }
   char* const kown = kimg + wave * P_TILE;
@@ -1756,96 +1627,39 @@ __global__ __launch_bounds__(512, 2) void attn32_slotq_fwd_kernel(A32SlotFwdP p)
   lds_barrier();
 
   const DropCtx dcp = b4r_drop_ctx(p.drop_p);
-  const int slot = (r & 24) | ((r & 3) << 1) | ((r >> 2) & 1);
   bf16x8 kAh[2], kAl[2];
 #pragma unroll
-  for (int ks = 0; ks < 2; ++ks) { kAh[ks] = row_at(kown + lk.rowc[ks]); kAl[ks] = row_at(kown + P_IMG + lk.rowc[ks]); }
+  for (int ks = 0; ks < 2; ++ks) a32_ld_row(kown, lk, ks, kAh[ks], kAl[ks]);
   const f32x16 add = rows_of(sAdd + 32 * wave, h);
-  f32x16 O[NQT];
-#pragma unroll
-  for (int t = 0; t < NQT; ++t) {
-    O[t] = zero16();
-    if (t >= NQ) continue;   // (wave-uniform)
+  // One call per tile, not a loop over the tiles (as for the heads of attn32_fwd_kernel: out of a loop around the inlined function
+  // hipcc hoists what both tiles share, and <2, true> then loses a wave per SIMD: 93 -> 97 registers)
+  auto tile = [&](int t) __attribute__((always_inline)) -> f32x16 {
+    if (t >= NQ) return zero16();   // (wave-uniform)
     // the token of this lane's query in tile t (for the decisions' hash index)
     const int jt = min(32 * t + r, p.P - 1);
     const int64_t pq = p.pos[(int64_t)b * p.P + jt];
     const int post = (int)(pq < 0 ? 0 : (pq >= L ? L - 1 : pq));
-    f32x16 S = add;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const char* qi = QIMG + t * P_TILE + lk.rowc[ks];
-      S = mfma32x3(kAh[ks], kAl[ks], row_at(qi), row_at(qi + P_IMG), S);   // S^T[key][query] = K_w . Q~_t^T
-    }
-    float m = S[0];
-#pragma unroll
-    for (int e = 1; e < 16; ++e) m = fmaxf(m, S[e]);
-    m = fmaxf(m, other_half(m, h));
-    const float mref = m == -INFINITY ? 0.0f : m;    // a tile of pad keys only: every term is 0
-    float sum = 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { S[e] = __builtin_amdgcn_exp2f(S[e] - mref); sum += S[e]; }
-    sum += other_half(sum, h);
-    if (h == 0) { float* ms = sMS + ((wave * NQ + t) * 32 + r) * 2; ms[0] = m; ms[1] = sum; }
-    if (DROP) {
-      uint32_t word = 0;
-      const uint64_t dbase = ((uint64_t)bh * L + (uint64_t)post) * (uint64_t)B4R_ATTN_PITCH;
-#pragma unroll
-      for (int gp = 0; gp < 4; ++gp) {
-        const B4rKeep4 k4 = b4r_keep4p(dcp, dbase + (uint64_t)(32 * wave + 8 * gp + 4 * h));
-#pragma unroll
-        for (int e = 0; e < 4; ++e) S[4 * gp + e] = k4.k[e] ? S[4 * gp + e] : 0.f;
-        word |= k4.bits() << (8 * gp + 4 * h);
-      }
-      word |= other_half_u(word, h);
-      if (h == 0) p.bits_c[((bh * NT + wave) * NQ + t) * 32 + slot] = word;
-    }
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      bf16x8 ph, pl;
-      acc_frag(S, s2, ph, pl);
-      O[t] = mfma32x3(tr_pair(vown + lk.trp[s2][0], vown + lk.trp[s2][1]), tr_pair(vown + P_IMG + lk.trp[s2][0], vown + P_IMG + lk.trp[s2][1]),
-                      ph, pl, O[t]);
-    }
-  }
+    return a32_fwd_compact_tile<DROP>(lk, wave, L, add, kAh, kAl, QIMG + t * P_TILE, vown, sMS + ((wave * NQ + t) * 32 + r) * 2, dcp, bh, post,
+                                      p.bits_c + ((bh * NT + wave) * NQ + t) * 32, a32_slot_perm(r), true);
+  };
+  f32x16 O[NQT];
+  O[0] = tile(0);
+  if constexpr (NQT > 1) O[1] = tile(1);
   // the partials over the wave's own images (every read of them above was the wave's own and has been consumed by a product)
 #pragma unroll
   for (int t = 0; t < NQT; ++t) {
     if (t >= NQ) continue;
-    char* dst = (t == 0 ? kown : vown) + lane * 16;
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj)
-      *reinterpret_cast<f32x4*>(dst + jj * 1024) = (f32x4){O[t][4 * jj], O[t][4 * jj + 1], O[t][4 * jj + 2], O[t][4 * jj + 3]};
+    a32_put_partial(t == 0 ? kown : vown, lane, O[t]);
   }
   lds_barrier();
   if (!qwave) return;
-  // merge of query tile t = wave: M = max_w m_w, sum = sum_w 2^(m_w - M) sum_w, O = sum_w 2^(m_w - M) O_w
-  float M = -INFINITY;
-  for (int w = 0; w < NT; ++w) M = fmaxf(M, sMS[((w * NQ + wave) * 32 + r) * 2]);
-  float tot = 0.f;
-  f32x16 Om = zero16();
-  for (int w = 0; w < NT; ++w) {
-    const float* ms = sMS + ((w * NQ + wave) * 32 + r) * 2;
-    const float a = ms[0] == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(ms[0] - M);
-    tot = fmaf(a, ms[1], tot);
-    const char* srcp = (wave == 0 ? kimg : vimg) + w * P_TILE + lane * 16;
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      const f32x4 o4 = *reinterpret_cast<const f32x4*>(srcp + jj * 1024);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) Om[4 * jj + e] = fmaf(a, o4[e], Om[4 * jj + e]);
-    }
-  }
+  // merge of query tile t = wave
+  float M, tot;
+  const f32x16 Om = a32_fwd_owner_merge(sMS + (wave * 32 + r) * 2, NQ * 64, wave == 0 ? kimg : vimg, NT, lane, M, tot);
   const float inv = (DROP ? dcp.scale : 1.0f) / tot;
-  if (h == 0 && livej) p.lse_c[bh * p.P + j] = M * LN2 + __logf(tot);
+  if (h == 0 && livej) p.lse_c[bh * p.P + j] = a32_lse(M, tot);
   // O's registers 8s .. 8s+7 are context columns 16s + 8h + (0..7) of the head (V image in swapped column order, transposed reads)
-  if (livej) {
-    float* dst = p.ctx_c + ((int64_t)b * p.P + j) * Hh + 32 * head + 8 * h;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      *reinterpret_cast<f32x4*>(dst + 16 * s) = (f32x4){Om[8 * s] * inv, Om[8 * s + 1] * inv, Om[8 * s + 2] * inv, Om[8 * s + 3] * inv};
-      *reinterpret_cast<f32x4*>(dst + 16 * s + 4) = (f32x4){Om[8 * s + 4] * inv, Om[8 * s + 5] * inv, Om[8 * s + 6] * inv, Om[8 * s + 7] * inv};
-    }
-  }
+  if (livej) acc_store_cols(p.ctx_c + ((int64_t)b * p.P + j) * Hh + 32 * head + 8 * h, Om, inv);
 }
 
 struct A32SlotBwdP {
@@ -1876,19 +1690,11 @@ __global__ __launch_bounds__(512, 2) void attn32_slotq_bwd_kernel(A32SlotBwdP p)
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   char* const scr = SCRALL + wave * P_TILE;
   A32_LANE_CONSTS();
-  const int64_t mval = (int)threadIdx.x < L ? p.mask[row0 + threadIdx.x] : 0;
-  const int any_key = mval != 0 ? 1 : 0;
+  const int64_t mval = a32_mask_value(p.mask + row0, L);
   // key side: k, v of the wave's tokens; the q part of their dqkv rows is zero unless a labelled slot writes it below
   const float* const src = p.qkv + (row0 + tokc) * (3 * Hh) + 32 * head;
   f32x16 kT = load_acc_layout(src + Hh, h), vT = load_acc_layout(src + 2 * Hh, h);
-  if (live) {
-    float* dz = p.dqkv + (row0 + tok) * (3 * Hh) + 32 * head + 8 * h;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      *reinterpret_cast<f32x4*>(dz + 16 * s) = (f32x4){0.f, 0.f, 0.f, 0.f};
-      *reinterpret_cast<f32x4*>(dz + 16 * s + 4) = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-  }
+  if (live) acc_store_cols(p.dqkv + (row0 + tok) * (3 * Hh) + 32 * head + 8 * h, zero16());
   // query side (waves 0 .. NQ - 1): the compact rows
   const bool qwave = wave < NQ;
   const int j = 32 * wave + r, jc = min(j, p.P - 1);
@@ -1911,10 +1717,7 @@ __global__ __launch_bounds__(512, 2) void attn32_slotq_bwd_kernel(A32SlotBwdP p)
     acc_to_rows(QIMG + wave * P_TILE, lk, qT);
     acc_to_rows(DOIMG + wave * P_TILE, lk, dcT);
   }
-  const float amax = __syncthreads_or(any_key) ? 0.0f : -1e9f;
-  const bool dead = amax != 0.0f;
-  if ((int)threadIdx.x < NT * 32)
-    sAdd[threadIdx.x] = (int)threadIdx.x < L ? (((1.0f - (float)mval) * -1e9f) - amax) * LOG2E : -INFINITY;
+  const bool dead = a32_mask_adders(mval, L, NT, sAdd).dead;
   const DropCtx dcp = b4r_drop_ctx(p.drop_p);
   const float pscale = DROP ? dcp.scale : 1.0f;
   if (!live) { kT = zero16(); vT = zero16(); }
@@ -1943,80 +1746,20 @@ __global__ __launch_bounds__(512, 2) void attn32_slotq_bwd_kernel(A32SlotBwdP p)
   for (int t = 0; t < NQT; ++t) {
     dQp[t] = zero16();
     if (t >= NQ) continue;   // (wave-uniform)
-    const char* qimg = QIMG + t * P_TILE;
-    const char* dimg = DOIMG + t * P_TILE;
-    f32x16 S = rows_of(sCS + 32 * t, h), dA = zero16();
-#pragma unroll
-    for (int e = 0; e < 16; ++e) S[e] += adk;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 ah, al;
-      A32_LD_ROW(qimg, ks, ah, al);
-      S = mfma32x3(ah, al, kBh[ks], kBl[ks], S);
-      A32_LD_ROW(dimg, ks, ah, al);
-      dA = mfma32x3(ah, al, vBh[ks], vBl[ks], dA);
-    }
-    const f32x16 Dq = rows_of(sD + 32 * t, h);
-    uint64_t km[16];
+    uint64_t km[16];   // scalar loads of the compact decision buffer
     if (DROP) {
       kmask_ptr mp = (kmask_ptr)(reinterpret_cast<const uint64_t*>(p.bits_c) + ((bh * NT + wave) * NQ + t) * 16);
 #pragma unroll
       for (int tt = 0; tt < 16; ++tt) km[tt] = mp[tt];
     }
-    bf16x8 pdh[2], pdl[2], dsh[2], dsl[2];
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      f32x8 pd, ds;
-#pragma unroll
-      for (int jj = 0; jj < 8; ++jj) {
-        const int tt = 8 * s2 + jj;
-        const float pr = __builtin_amdgcn_exp2f(S[tt]);
-        if (DROP) {
-          const float kf = __builtin_amdgcn_inverse_ballot_w64(km[tt]) ? pscale : 0.f;
-          pd[jj] = pr * kf;
-          ds[jj] = pr * fmaf(dA[tt], kf, -Dq[tt]);
-        } else {
-          pd[jj] = pr;
-          ds[jj] = pr * (dA[tt] - Dq[tt]);
-        }
-      }
-      split8(pd, pdh[s2], pdl[s2]);
-      split8(ds, dsh[s2], dsl[s2]);
-      const s16x8 hv = __builtin_bit_cast(s16x8, dsh[s2]), lv = __builtin_bit_cast(s16x8, dsl[s2]);
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        char* w8 = scr + p_chunk(r, 2 * s2 + a) + 8 * h;
-        *reinterpret_cast<s16x4*>(w8) = a ? __builtin_shufflevector(hv, hv, 4, 5, 6, 7) : __builtin_shufflevector(hv, hv, 0, 1, 2, 3);
-        *reinterpret_cast<s16x4*>(w8 + P_IMG) = a ? __builtin_shufflevector(lv, lv, 4, 5, 6, 7) : __builtin_shufflevector(lv, lv, 0, 1, 2, 3);
-      }
-    }
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      bf16x8 fh, fl;
-      A32_LD_TR(dimg, s2, fh, fl);
-      dV = mfma32x3(fh, fl, pdh[s2], pdl[s2], dV);   // dV^T[feature][key] += dO^T[feature][query] . Pd[query][key]
-      A32_LD_TR(qimg, s2, fh, fl);
-      dK = mfma32x3(fh, fl, dsh[s2], dsl[s2], dK);   // dK^T += Q~^T . dS
-    }
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 fh, fl;
-      A32_LD_SCR(ks, fh, fl);
-      dQp[t] = mfma32x3(kTh[ks], kTl[ks], fh, fl, dQp[t]);   // dQ^T[feature position][query] = K^T . dS^T
-    }
+    a32_bwd_compact_tile<DROP>(lk, QIMG + t * P_TILE, DOIMG + t * P_TILE, scr, sCS + 32 * t, sD + 32 * t, adk, km, pscale, kBh, kBl, vBh,
+                               vBl, kTh, kTl, dK, dV, dQp[t]);
   }
   // results of the wave's tokens as keys: registers 8s .. 8s+7 = features 16s + 8h + (0..7)
   if (live) {
-    const f32x16 gk = dK * LN2;   // Q~ carries log2(e)
     float* dst = p.dqkv + (row0 + tok) * (3 * Hh) + 32 * head + 8 * h;
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-        const int o = 8 * s + 4 * hf;
-        *reinterpret_cast<f32x4*>(dst + Hh + 16 * s + 4 * hf) = (f32x4){gk[o], gk[o + 1], gk[o + 2], gk[o + 3]};
-        *reinterpret_cast<f32x4*>(dst + 2 * Hh + 16 * s + 4 * hf) = (f32x4){dV[o], dV[o + 1], dV[o + 2], dV[o + 3]};
-      }
+    acc_store_cols(dst + Hh, dK, LN2);   // Q~ carries log2(e)
+    acc_store_cols(dst + 2 * Hh, dV);
   }
   // dQ of compact tile t = the key owners' partials in wave order (through the scratch tiles, one compact tile at a time); the zero
   // fill of the q parts above is complete before the first labelled row is written (vmcnt(0) in front of the barrier)
@@ -2024,32 +1767,9 @@ __global__ __launch_bounds__(512, 2) void attn32_slotq_bwd_kernel(A32SlotBwdP p)
 #pragma unroll
   for (int t = 0; t < NQT; ++t) {
     if (t >= NQ) continue;
-    lds_barrier();   // (t == 0: the sweep's last scratch reads; t > 0: the previous tile's sums have been read)
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj)
-      *reinterpret_cast<f32x4*>(scr + jj * 1024 + lane * 16) = (f32x4){dQp[t][4 * jj], dQp[t][4 * jj + 1], dQp[t][4 * jj + 2], dQp[t][4 * jj + 3]};
-    lds_barrier();
-    if (wave == t) {
-      f32x16 gq = zero16();
-      for (int w = 0; w < NT; ++w)
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-          const f32x4 a4 = *reinterpret_cast<const f32x4*>(SCRALL + w * P_TILE + jj * 1024 + lane * 16);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) gq[4 * jj + e] += a4[e];
-        }
-      if (livej && p.ids[(int64_t)b * p.P + j] != 0) {
-        float* dst = p.dqkv + (row0 + posq) * (3 * Hh) + 32 * head + 8 * h;
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-          for (int hf = 0; hf < 2; ++hf) {
-            const int o = 8 * s + 4 * hf;
-            *reinterpret_cast<f32x4*>(dst + 16 * s + 4 * hf) =
-                (f32x4){gq[o] * p.qscale, gq[o + 1] * p.qscale, gq[o + 2] * p.qscale, gq[o + 3] * p.qscale};
-          }
-      }
-    }
+    const f32x16 gq = a32_bwd_owner_sum(dQp[t], scr, SCRALL, NT, lane, wave == t);
+    if (wave == t && livej && p.ids[(int64_t)b * p.P + j] != 0)
+      acc_store_cols(p.dqkv + (row0 + posq) * (3 * Hh) + 32 * head + 8 * h, gq, p.qscale);
   }
 }
 

@@ -89,6 +89,18 @@ __device__ __forceinline__ void acc_to_rows(char* tile, const Lane32& lk, const 
 }
 // accumulator registers 8s .. 8s+7 as the B (or A) fragment of k-step s
 __device__ __forceinline__ void acc_frag(const f32x16& v, int s, bf16x8& hi, bf16x8& lo) { split8(regs8(v, s), hi, lo); }
+// accumulator whose registers 8s .. 8s+7 are columns 16s + 8h + (0..7) of the lane's row (the output of a product whose A operand
+// was a transposed read of an image in swapped column order), times `scale`, -> that row of a [N, ld] tensor: four 16-byte stores.
+// dst = column 8h of the row's 32-column slice.
+__device__ __forceinline__ void acc_store_cols(float* dst, const f32x16& v, float scale = 1.0f) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+      const int o = 8 * s + 4 * hf;
+      *reinterpret_cast<f32x4*>(dst + 16 * s + 4 * hf) = (f32x4){v[o] * scale, v[o + 1] * scale, v[o + 2] * scale, v[o + 3] * scale};
+    }
+}
 
 // the four floats src[4 (2 g' + h) .. +3], g' = 0..3, of a [32] array in LDS: the values of rows (t & 3) + 8 (t >> 2) + 4h in register t
 __device__ __forceinline__ f32x16 rows_of(const float* src, int h) {
