@@ -195,6 +195,7 @@ PROTOTYPES = {
     "b4r_rerank_quota_scratch_bytes": (_I64, [_I32, _I32, _I32]),
     "b4r_rerank_quota": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _F, _I32, C.POINTER(ItemQuota), _I32, _P, _P, _P, _P, _P,
                                    _I64, _P]),
+    "b4r_rerank_calibrated": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _I32, _P, _F, C.c_double, _P, _P, _P, _P, _P, _P]),
     "b4r_list_metrics_scratch_bytes": (_I64, [_I32, _I32, _I32]),
     "b4r_list_metrics": (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "b4r_score_dist_scratch_bytes": (_I64, [_I32, _I32]),

@@ -35,7 +35,11 @@ of every item, its reach and its expected demand are kept on the device while th
 
 category_affinity gives each user's probability of picking from every category next (b4r_group_mass: the catalogue softmax summed
 per item group on the device, no [users, V] probabilities); category_audience is `audience` with categories in place of items, and
-recommend_shelves returns the categories a user is most likely to pick from, each with its best items."""
+recommend_shelves returns the categories a user is most likely to pick from, each with its best items.
+
+calibrate_by / calibrate_to / calibration give every user a list with their own category mix: the sweep returns candidate_pool
+candidates per user and b4r_rerank_calibrated picks k of them so that the list's category shares follow the shares of the user's
+history, or the user's category affinity."""
 import numbers
 
 import numpy as np
@@ -190,7 +194,8 @@ class Recommender:
 
     def recommend_batch(self, sequences, k: int = 1, allowed_items=None, allowed_items_per_user=None, diversity=None,
                         candidate_pool=None, max_per_group=None, return_probabilities: bool = False, min_probability=None,
-                        temperature: float = 1.0, sample_seed=None, user_streams=None) -> list:
+                        temperature: float = 1.0, sample_seed=None, user_streams=None, calibrate_by=None, calibrate_to: str = "history",
+                        calibration=None) -> list:
         """Recommender(...)(seq, k) for every sequence of `sequences`, from one batched forward and one full-catalogue top-k.
         allowed_items: one iterable of items (detokenized values) for all users; allowed_items_per_user: one iterable per sequence
         (identical lists share one filter).  Only allowed items are recommended; items the vocabulary does not know are ignored.
@@ -212,9 +217,25 @@ class Recommender:
         user_streams: one integer per sequence (a user id, a request counter): the user's noise stream, so that a user draws the
         same list under the same seed whatever batch they ride in (None: the position in the batch).  return_probabilities gives the
         probability of each drawn item over everything the user could be served (also when candidate_pool truncates the draw).  It
-        does not combine with diversity or max_per_group."""
+        does not combine with diversity or max_per_group.
+        calibrate_by: None, or the items' categories as category_affinity takes them (a mapping or a callable from an item to its
+        label, or one integer label per token id [V]; at most 1024 categories) -- the k items are picked from the candidate_pool best
+        so that the list's category mix follows the user's own (b4r_rerank_calibrated: a user with 70 % drama and 30 % comedy gets
+        about 7 and 3 of 10, not 10 dramas).  calibrate_to: "history" = the category counts of the user's sequence inside the model's
+        window, "affinity" = the user's probability of picking from each category next (category_affinity's).  calibration: the
+        weight of the category mix against the relevance, a number in [0, 1] (default 0.5; 0 = the k best items).  It does not
+        combine with diversity, max_per_group or sample_seed."""
         calibrated = bool(return_probabilities) or min_probability is not None
         sampled = sample_seed is not None
+        if calibrate_by is None:
+            if calibration is not None:
+                raise ValueError("calibration is the weight of the calibrated re-ranking: give calibrate_by as well")
+        else:
+            if diversity is not None or max_per_group is not None or sampled:
+                raise ValueError("calibrate_by does not combine with diversity, max_per_group or sample_seed")
+            if calibrate_to not in engine_mod.CALIBRATION_TARGETS:
+                raise ValueError(f"calibrate_to is one of {list(engine_mod.CALIBRATION_TARGETS)}, got {calibrate_to!r}")
+            engine_mod.check_calibration_args(k, candidate_pool, 0.5 if calibration is None else calibration)
         if sampled:
             sample_seed = engine_mod.check_sample_seed(sample_seed)
             if diversity is not None or max_per_group is not None:
@@ -232,6 +253,10 @@ class Recommender:
         sequences = [list(seq) for seq in sequences]
         allow, user_filter = self._allow_filters(len(sequences), allowed_items, allowed_items_per_user)
         quotas = None if max_per_group is None else self._item_groups(max_per_group)   # packed once per call
+        calibrate = None
+        if calibrate_by is not None:
+            labels, G, _ = self._affinity_labels(calibrate_by)
+            calibrate = (labels, G, calibrate_to)
         if not sequences:
             return []
         batch, exclude = self._requests(sequences)
@@ -247,7 +272,8 @@ class Recommender:
         got = self.model.recommend_tensor(batch, k=k, exclude_seen=False, exclude=exclude, allow=allow, row_filter=row_filter,
                                           diversity=diversity, pool=candidate_pool, max_per_group=quotas,
                                           return_distribution=calibrated, temperature=temperature, sample_seed=sample_seed,
-                                          sample_streams=slot_streams)
+                                          sample_streams=slot_streams, calibrate=calibrate,
+                                          calibration=None if calibrate is None else (0.5 if calibration is None else calibration))
         ids, slots = got[0], got[2]
         P = int(batch["masked_lm_positions"].shape[1])
         first = {}

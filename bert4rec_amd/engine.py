@@ -620,6 +620,58 @@ def check_quota_args(quotas, vocab_size: Optional[int] = None) -> List[ItemGroup
     return quotas
 
 
+CALIBRATED_MAX_G = 1024          # b4r_rerank_calibrated: G
+CALIBRATION_TARGETS = ("history", "affinity")
+
+
+def check_calibration_args(k, pool, calibration, alpha=0.01, n_groups=None) -> Tuple[int, int, float, float]:
+    """Argument checks of the calibrated re-ranking that need no GPU.  Returns (k, pool, lambda, alpha): k and pool as
+    check_rerank_args gives them (pool None = min(1024, max(10 k, 50))); calibration a number in [0, 1], rounded to fp32
+    (b4r_rerank_calibrated's lambda: 0 keeps the relevance order, 1 picks by the calibration gain alone); alpha a number in (0, 1),
+    the smoothing of the list's shares towards the target; n_groups (when given) an integer in [1, 1024]."""
+    k, pool, _ = check_rerank_args(k, pool, 0.0)
+    if isinstance(calibration, bool) or not isinstance(calibration, numbers.Real) or not 0.0 <= calibration <= 1.0:   # (NaN fails the range)
+        raise ValueError(f"calibration must be a number in [0, 1], got {calibration!r}")
+    if isinstance(alpha, bool) or not isinstance(alpha, numbers.Real) or not 0.0 < alpha < 1.0:
+        raise ValueError(f"calibration_alpha must be a number in (0, 1), got {alpha!r}")
+    if n_groups is not None:
+        _int_in(n_groups, 1, CALIBRATED_MAX_G, "n_groups of a calibration")
+    return k, pool, C.c_float(float(calibration)).value, float(alpha)
+
+
+def check_calibrate(calibrate, vocab_size: int):
+    """recommend_tensor's calibrate=(item_groups, n_groups, target), checked without a GPU: the labels go through
+    check_item_group_labels (at most 1024 groups here); target is "history", "affinity" or an int64 tensor [R, G] of non-negative
+    masses.  Returns (labels int32 [V] on the host, G, target)."""
+    if not isinstance(calibrate, (tuple, list)) or len(calibrate) != 3:
+        raise ValueError("calibrate takes (item_groups, n_groups, target)")
+    item_groups, n_groups, target = calibrate
+    labels, G = check_item_group_labels(item_groups, vocab_size, n_groups)
+    if G > CALIBRATED_MAX_G:
+        raise ValueError(f"a calibration takes at most {CALIBRATED_MAX_G} groups, got {G}")
+    if isinstance(target, str):
+        if target not in CALIBRATION_TARGETS:
+            raise ValueError(f"a calibration target is one of {list(CALIBRATION_TARGETS)} or an int64 tensor [R, {G}], got {target!r}")
+    elif not torch.is_tensor(target) or target.dtype != torch.int64 or target.ndim != 2 or int(target.shape[1]) != G:
+        raise ValueError(f"a calibration target is one of {list(CALIBRATION_TARGETS)} or an int64 tensor [R, {G}], got "
+                         f"{getattr(target, 'dtype', type(target).__name__)} of shape {tuple(getattr(target, 'shape', ()))}")
+    return labels, G, target
+
+
+def group_history_counts(tokens: torch.Tensor, labels: torch.Tensor, n_groups: int) -> torch.Tensor:
+    """The "history" target of a calibration: tokens [R, L] integer ids, labels [V] integer labels on the same device -> int64
+    [R, n_groups], the number of tokens of every row with each label.  The special ids ([PAD] / [MASK] / [UNK]), ids outside the
+    vocabulary and items whose label lies outside [0, n_groups) are not counted.  Plain torch on the tokens' device, no
+    synchronisation."""
+    V = int(labels.numel())
+    tok = tokens.to(torch.int64)
+    lab = labels.to(torch.int64)[tok.clamp(0, V - 1)]
+    ok = (tok >= SPECIAL_IDS) & (tok < V) & (lab >= 0) & (lab < n_groups)
+    counts = torch.zeros((int(tok.shape[0]), n_groups + 1), dtype=torch.int64, device=tok.device)
+    counts.scatter_add_(1, torch.where(ok, lab, torch.full_like(lab, n_groups)), torch.ones_like(lab))   # (slot n_groups: not counted)
+    return counts[:, :n_groups].contiguous()
+
+
 def item_self_information(counts) -> np.ndarray:
     """The novelty weight of every item from its interaction count: -log2(max(c, 1) / sum(c)) (an item nobody interacted with
     counts as seen once), computed in float64 and rounded to fp32.  counts [V]: one count per token id; returns float32 [V]."""
@@ -1549,6 +1601,39 @@ class Engine:
         [R,k] int64, scores [R,k] fp32, mmr [R,k] fp32, pos [R,k] int32: the pool position of every pick), -1 / -inf / -inf / -1 where a
         row has fewer than k admissible candidates.  rnorm as in rerank_diverse.  The scratch buffer is kept between calls."""
         return self._rerank(pool_ids, pool_scores, k, diversity, rnorm, capped=True, quotas=quotas)
+
+    def rerank_calibrated(self, pool_ids: torch.Tensor, pool_scores: torch.Tensor, k: int, calibration: float, item_groups, n_groups,
+                          target_mass: torch.Tensor, alpha: float = 0.01):
+        """b4r_rerank_calibrated: pick k of the candidates pool_ids / pool_scores [R, M] (rank_full's output) so that the list's shares
+        of the item groups follow the row's target distribution (Steck's calibrated recommendations).  item_groups / n_groups:
+        check_item_group_labels, at most 1024 groups (an int32 tensor [V] already on the device is taken as it is; n_groups is then
+        required).  target_mass [R, G] int64: the target in any non-negative unit (history counts, group_mass's masses); a negative
+        entry counts as 0 and a row that sums to 0 has no target.  calibration in [0, 1]: 0 keeps the pool's order, 1 picks by the
+        calibration gain alone; alpha in (0, 1) smooths the list's shares towards the target.  Returns (ids [R,k] int64, scores [R,k]
+        fp32: the pool scores of the picks, value [R,k] fp32: the objective each pick won with, pos [R,k] int32: its pool position,
+        kl [R] fp64: KL(target || smoothed shares of the list), NaN for a row without a target or without a pick), -1 / -inf / -inf /
+        -1 where a row has fewer than k live candidates."""
+        R, M, ids_d, sc_d = self._pool(pool_ids, pool_scores)
+        k, _, lam, alpha = check_calibration_args(k, M, calibration, alpha)
+        V = self.cfg.vocab_size
+        lab = item_groups
+        if torch.is_tensor(lab) and lab.is_cuda and lab.dtype == torch.int32 and tuple(lab.shape) == (V,) and n_groups is not None:
+            G, lab_d = _int_in(n_groups, 1, CALIBRATED_MAX_G, "n_groups of a calibration"), lab.contiguous()
+        else:
+            lab, G = check_item_group_labels(lab, V, n_groups)
+            G = _int_in(G, 1, CALIBRATED_MAX_G, "n_groups of a calibration")
+            lab_d = lab.to(self.device)
+        if not torch.is_tensor(target_mass) or target_mass.dtype != torch.int64 or tuple(target_mass.shape) != (R, G):
+            raise ValueError(f"target_mass must be an int64 tensor [{R}, {G}], got {getattr(target_mass, 'dtype', type(target_mass).__name__)} "
+                             f"of shape {tuple(getattr(target_mass, 'shape', ()))}")
+        out = self._picks(R, k, torch.int64, torch.float32, torch.float32, torch.int32)
+        kl = torch.empty((R,), dtype=torch.float64, device=self.device)
+        if R == 0:
+            return out + (kl,)
+        t_d = target_mass.to(self.device).contiguous()
+        _lib.check(self.lib.b4r_rerank_calibrated(_ptr(ids_d), _ptr(sc_d), R, M, k, V, _ptr(lab_d), G, _ptr(t_d), lam, alpha,
+                                                  *(_ptr(t) for t in out), _ptr(kl), _stream(self.device)), "b4r_rerank_calibrated")
+        return out + (kl,)
 
     def list_metrics(self, list_ids: torch.Tensor, gt: Optional[torch.Tensor] = None, item_weight: Optional[torch.Tensor] = None,
                      rnorm: Optional[torch.Tensor] = None, exposure: Optional[torch.Tensor] = None, sums: Optional[torch.Tensor] = None,

@@ -8,7 +8,8 @@ evaluators_map = {"bert4rec": BERT4RecEvaluator}
 
 def get(identifier: str = "bert4rec", **kwargs) -> BaseEvaluator:
     """kwargs go to the evaluator: metrics, sampler, dataloader, device_sampling, seed, full_ranking, and the list evaluation's list_k,
-    diversity, candidate_pool, item_counts, max_per_group, sample_seed and temperature, and distribution (BERT4RecEvaluator)."""
+    diversity, candidate_pool, item_counts, max_per_group, sample_seed and temperature, the calibrated lists' calibrate_by, calibrate_to,
+    calibration and calibration_alpha, and distribution (BERT4RecEvaluator)."""
     if identifier in evaluators_map:
         return evaluators_map[identifier](**kwargs)
     raise ValueError(f"{identifier} is not known!")

@@ -24,6 +24,8 @@ max_per_group (pack_item_groups specs) evaluates the lists b4r_rerank_quota pick
 sample_seed=s (with list_k) evaluates SAMPLED lists: k items drawn without replacement from softmax(scores / temperature) over the
 items the ground truth is ranked against (b4r_sample_full), or over the best candidate_pool of them (b4r_sample_pool) -- what
 exploration costs in HR / NDCG and what it buys in ILD, coverage, Gini and novelty.
+calibrate_by=labels (with list_k) evaluates CALIBRATED lists: b4r_rerank_calibrated picks k of the pool so that the list's category
+shares follow the row's history or affinity; the results gain Miscalibration@k, the mean KL divergence of the target from the lists.
 
 distribution=True (with full_ranking) adds the likelihood view: one b4r_score_dist call per batch gives the log probability of every
 ground truth under the softmax over the items it was ranked against, and the row's entropy; their sums stay on the device and are
@@ -35,8 +37,9 @@ import numpy as np
 import torch
 
 from ..dataloaders import samplers
-from ..engine import (SPECIAL_IDS, check_quota_args, check_rank_full_args, check_rerank_args, check_sample_pool_args, check_sample_seed,
-                      check_temperature, item_self_information)
+from ..engine import (CALIBRATION_TARGETS, SPECIAL_IDS, check_calibrate, check_calibration_args, check_quota_args, check_rank_full_args,
+                      check_rerank_args, check_sample_pool_args, check_sample_seed, check_temperature, group_history_counts,
+                      item_self_information)
 from .base_evaluator import BaseEvaluator
 from .evaluation_metrics import GAIN_COUNT, GAIN_HIT, GAIN_NDCG, HR, MAP, NDCG, Counter, EvaluationMetric, gain_table
 
@@ -67,8 +70,17 @@ class BERT4RecEvaluator(BaseEvaluator):
     def __init__(self, metrics: list = None, sampler: Union[str, "samplers.BaseSampler"] = "pop_random", dataloader=None,
                  device_sampling: bool = True, seed: int = 0, full_ranking: bool = False, list_k: int = None, diversity: float = None,
                  candidate_pool: int = None, item_counts=None, max_per_group=None, distribution: bool = False, sample_seed: int = None,
-                 temperature: float = 1.0):
-        """distribution: the likelihood view of the module docstring; it needs full_ranking=True and, like list_k, evaluates on one
+                 temperature: float = 1.0, calibrate_by=None, calibrate_to: str = "history", calibration: float = None,
+                 calibration_alpha: float = 0.01):
+        """calibrate_by / calibrate_to / calibration / calibration_alpha (with list_k): evaluate CALIBRATED lists.  calibrate_by: one
+        integer label per token id [V] (negative = no group; at most 1024 groups), or (labels, n_groups); calibrate_to "history" (the
+        label counts of the row's input_word_ids) or "affinity" (the row's probability mass per group over the items the ground truth
+        is ranked against); calibration: lambda in [0, 1] (default 0.5; 0 evaluates the plain top k and its miscalibration).  The
+        lists are picked from the candidate_pool best by b4r_rerank_calibrated, the accuracy metrics come from the position of the
+        ground truth in the re-ranked list (the same rule on cut-offs as with diversity), and the results gain Miscalibration@k: the
+        mean KL(target || smoothed shares of the list) over the rows where it is defined.  It does not combine with diversity,
+        max_per_group or sample_seed.
+        distribution: the likelihood view of the module docstring; it needs full_ranking=True and, like list_k, evaluates on one
         rank only.  list_k / diversity / candidate_pool / item_counts: list evaluation (the module docstring); with list_k=None, the default,
         nothing changes.  list_k=k needs full_ranking=True.  diversity=None evaluates the sweep's own top k and takes the accuracy
         metrics from the full-catalogue rank, as without list_k; diversity=d in [0, 1] re-ranks the best candidate_pool items (default
@@ -107,6 +119,24 @@ class BERT4RecEvaluator(BaseEvaluator):
                 raise ValueError("sample_seed evaluates sampled lists: give list_k (and full_ranking=True) as well")
             if diversity is not None or max_per_group is not None:
                 raise ValueError("sample_seed does not combine with diversity or max_per_group")
+        self._calibrate = None     # (labels as given, n_groups or None, target kind, lambda, alpha)
+        self._cal_labels = None    # (engine, labels int32 [V] on its device, G): checked against the model's vocabulary at the first batch
+        self._cal_dev = None       # (engine, float64 [1]: the sum of the defined kl values, int64 [1]: their number)
+        self._cal_host = [0.0, 0]
+        if calibrate_by is None:
+            if calibration is not None:
+                raise ValueError("calibration is the weight of the calibrated re-ranking: give calibrate_by as well")
+        else:
+            if list_k is None:
+                raise ValueError("calibrate_by evaluates calibrated lists: give list_k (and full_ranking=True) as well")
+            if diversity is not None or max_per_group is not None or sample_seed is not None:
+                raise ValueError("calibrate_by does not combine with diversity, max_per_group or sample_seed")
+            if calibrate_to not in CALIBRATION_TARGETS:
+                raise ValueError(f"calibrate_to is one of {list(CALIBRATION_TARGETS)}, got {calibrate_to!r}")
+            by, n_groups = calibrate_by if isinstance(calibrate_by, tuple) and len(calibrate_by) == 2 else (calibrate_by, None)
+            _, _, lam, alpha = check_calibration_args(list_k, candidate_pool, 0.5 if calibration is None else calibration,
+                                                      calibration_alpha, n_groups)
+            self._calibrate = (by, n_groups, calibrate_to, lam, alpha)
         self._item_counts = item_counts
         self._quotas = None
         self._list_dev = None      # (engine, exposure int64 [V], sums float64 [2], counts int64 [2], item weight fp32 [V] or None)
@@ -125,12 +155,12 @@ class BERT4RecEvaluator(BaseEvaluator):
             pool = k
             if max_per_group is not None:
                 self._quotas = check_quota_args(max_per_group)   # (their length is checked against the model's vocabulary per batch)
-            if diversity is not None or self._quotas is not None:
+            if diversity is not None or self._quotas is not None or self._calibrate is not None:
                 k, pool, _ = check_rerank_args(k, candidate_pool, 0.0 if diversity is None else diversity)
                 for m in metrics:
                     if not (m.family == GAIN_COUNT or (m.family in (GAIN_HIT, GAIN_NDCG) and 1 <= m.cutoff <= k)):
                         raise ValueError(f"metric {m.name} looks beyond the first {k} ranks, which a re-ranked list of {k} items does "
-                                         f"not have: with diversity or max_per_group every metric must be a counter or have a cut-off of at most list_k")
+                                         f"not have: with diversity, max_per_group or calibrate_by every metric must be a counter or have a cut-off of at most list_k")
             elif self.sample_seed is not None:
                 if candidate_pool is not None:
                     k, pool = check_sample_pool_args(k, candidate_pool)
@@ -207,6 +237,7 @@ class BERT4RecEvaluator(BaseEvaluator):
         that evaluation is then folded in."""
         self._flush_list_sums()
         self._flush_dist_sums()
+        self._flush_calibration_sums()
         if self._dev is None:
             return False
         _, sums, users = self._dev
@@ -250,6 +281,40 @@ class BERT4RecEvaluator(BaseEvaluator):
         nll_sum, ent_sum, rows = self._dist_host
         nll = nll_sum / rows if rows else 0.0
         return {"NLL": nll, "Perplexity": float(np.exp(nll)), "Entropy": ent_sum / rows if rows else 0.0}
+
+    # ---- calibrated lists (calibrate_by) -----------------------------------------------------------------------------------------
+    def _calibration_labels(self, engine):
+        """(labels int32 [V] on the engine's device, G): checked against the model's vocabulary once per engine"""
+        if self._cal_labels is None or self._cal_labels[0] is not engine:
+            by, n_groups = self._calibrate[:2]
+            labels, G, _ = check_calibrate((by, n_groups, "history"), engine.cfg.vocab_size)
+            self._cal_labels = (engine, labels.to(engine.params.device), G)
+        return self._cal_labels[1:]
+
+    def _calibration_sums(self, engine):
+        if self._cal_dev is None or self._cal_dev[0] is not engine:
+            self._flush_calibration_sums()
+            dev = engine.params.device
+            self._cal_dev = (engine, torch.zeros(1, dtype=torch.float64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev))
+        return self._cal_dev
+
+    def _flush_calibration_sums(self) -> None:
+        """one device -> host copy of the miscalibration accumulators per flush: [sum of kl, rows] as float64"""
+        if getattr(self, "_cal_dev", None) is None:
+            return
+        _, csum, crows = self._cal_dev
+        back = torch.cat([csum, crows.to(torch.float64)]).cpu().tolist()
+        self._cal_host[0] += back[0]; self._cal_host[1] += int(back[1])
+        csum.zero_(); crows.zero_()
+
+    def calibration_results(self) -> dict:
+        """Miscalibration@k of everything evaluated since the last reset: the mean kl over the lists where it is defined (a row with a
+        target and at least one item)."""
+        if getattr(self, "_calibrate", None) is None:
+            return {}
+        self._flush_calibration_sums()
+        total, rows = self._cal_host
+        return {f"Miscalibration@{self.list_k}": total / rows if rows else 0.0}
 
     # ---- list evaluation (list_k) ----------------------------------------------------------------------------------------------
     def _list_sums(self, engine):
@@ -476,8 +541,21 @@ class BERT4RecEvaluator(BaseEvaluator):
                 ids = engine.rerank_quota(ids, scores, self.list_k, 0.0 if self.diversity is None else self.diversity, self._quotas)[0]
             elif self.diversity is not None:
                 ids, _, _ = engine.rerank_diverse(ids, scores, self.list_k, self.diversity)
+            elif self._calibrate is not None:
+                labels_d, G = self._calibration_labels(engine)
+                _, _, kind, lam, alpha = self._calibrate
+                if kind == "history":
+                    target = group_history_counts(torch.as_tensor(test_batch["input_word_ids"]).to(dev)[b_idx], labels_d, G)
+                else:   # (over the items the ground truth is ranked against: the ground truth itself stays in)
+                    seen = torch.where(exclude == gt[:, None], torch.full_like(exclude, -1), exclude)
+                    target = model._group_affinity(hidden, seen, labels_d, G, None, None, 1.0)["group_mass"]
+                ids, _, _, _, kl = engine.rerank_calibrated(ids, scores, self.list_k, lam, labels_d, G, target, alpha)
+                _, csum, crows = self._calibration_sums(engine)
+                defined = ~torch.isnan(kl)
+                csum += torch.where(defined, kl, torch.zeros_like(kl)).sum()
+                crows += defined.sum()
             _, _, _, hit_pos = engine.list_metrics(ids, gt, weight, exposure=exposure, sums=sums, counts=counts)
-            if self.diversity is not None or self._quotas is not None or self.sample_seed is not None:
+            if self.diversity is not None or self._quotas is not None or self.sample_seed is not None or self._calibrate is not None:
                 # the rank in the re-ranked (or sampled) list; k + 1: not in it (no gain under any cut-off <= k); 0 stays "no valid ground truth"
                 absent = torch.full_like(hit_pos, self.list_k + 1)
                 gt_rank = torch.where(gt_rank > 0, torch.where(hit_pos > 0, hit_pos, absent), torch.zeros_like(hit_pos))
@@ -500,6 +578,7 @@ class BERT4RecEvaluator(BaseEvaluator):
         results = super().get_metrics_results()
         results.update(self.list_results())
         results.update(self.distribution_results())
+        results.update(self.calibration_results())
         return results
 
     def reset_metrics(self) -> None:
@@ -517,6 +596,10 @@ class BERT4RecEvaluator(BaseEvaluator):
             self._dist_dev[1].zero_()
             self._dist_dev[2].zero_()
         self._dist_host = [0.0, 0.0, 0]
+        if getattr(self, "_cal_dev", None) is not None:
+            self._cal_dev[1].zero_()
+            self._cal_dev[2].zero_()
+        self._cal_host = [0.0, 0]
         super().reset_metrics()
 
 

@@ -326,7 +326,8 @@ class BERT4RecModel:
     def recommend_tensor(self, encoder_input: Dict[str, torch.Tensor], k: int = 10, exclude_seen: bool = True,
                          exclude: Optional[torch.Tensor] = None, allow=None, row_filter=None, diversity: Optional[float] = None,
                          pool: Optional[int] = None, max_per_group=None, return_distribution: bool = False,
-                         temperature: float = 1.0, sample_seed: Optional[int] = None, sample_streams=None):
+                         temperature: float = 1.0, sample_seed: Optional[int] = None, sample_streams=None, calibrate=None,
+                         calibration: Optional[float] = None, calibration_alpha: float = 0.01, return_calibration: bool = False):
         """Top k of the whole catalogue for every slot with masked_lm_weights == 1 (all slots when the key is absent), from one
         b4r_rank_full call: no [R, V] scores.  The forward is rank_items_tensor's (encoder, then tfm MaskedLM's transform on those
         slots only).  [PAD] / [MASK] / [UNK] are never recommended; exclude_seen drops the row's own input_word_ids; exclude
@@ -355,8 +356,27 @@ class BERT4RecModel:
         stream of each ranked slot (None: the slot's row number 0 .. R-1); the same (sample_seed, stream) draws the same list
         whatever else the batch holds.  With return_distribution the log probabilities are b4r_score_dist's at the same temperature:
         they are over the slot's FULL allowed catalogue, also when `pool` truncates the draw.  sample_seed together with diversity
-        or max_per_group raises ValueError."""
+        or max_per_group raises ValueError.
+        calibrate: None, or (item_groups, n_groups, target) -- the k items are picked from the best `pool` allowed items of every row
+        (the same default) so that the list's shares of the item groups follow the row's target distribution (b4r_rerank_calibrated:
+        Steck's calibrated recommendations; "70 % drama and 30 % comedy in, 70 / 30 out").  item_groups / n_groups: one label per
+        token id as group_affinity_tensor takes them, at most 1024 groups.  target: "history" = per ranked slot the count of each
+        label among the row's input_word_ids (special ids and unlabelled items are not counted; formed on the device without a
+        synchronisation); "affinity" = group_affinity_tensor's group_mass of the same forward, exclusions and filter (two more
+        sweeps); or an int64 tensor [R, G] of non-negative masses in any unit.  calibration: lambda in [0, 1] (default 0.5): 0
+        returns the plain top k, 1 picks by the calibration gain alone.  calibration_alpha in (0, 1): the smoothing of the list's
+        shares towards the target.  return_calibration: one more value follows (after the distribution's dict when both are asked
+        for): {"kl": float64 [R], the miscalibration KL(target || smoothed shares of the list) of every returned list, NaN for a row
+        without a target or without an item; "target_mass": int64 [R, G], the target used}.  calibrate together with diversity,
+        max_per_group or sample_seed raises ValueError, and so do calibration or return_calibration without calibrate."""
         k = engine_mod.check_rank_full_args(k, exclude)
+        cal = None
+        if calibrate is not None:
+            if diversity is not None or max_per_group is not None or sample_seed is not None:
+                raise ValueError("calibrate does not combine with diversity, max_per_group or sample_seed")
+            cal = engine_mod.check_calibrate(calibrate, self.vocab_size)
+        elif calibration is not None or return_calibration:
+            raise ValueError("calibration and return_calibration belong to the calibrated re-ranking: give calibrate as well")
         sampled = sample_seed is not None
         if sampled:
             sample_seed = engine_mod.check_sample_seed(sample_seed)
@@ -376,14 +396,22 @@ class BERT4RecModel:
             k, n_sweep, _ = engine_mod.check_rerank_args(k, pool, 0.0 if diversity is None else diversity)
         elif diversity is not None:
             k, n_sweep, _ = engine_mod.check_rerank_args(k, pool, diversity)
+        elif cal is not None:
+            k, n_sweep, cal_lambda, cal_alpha = engine_mod.check_calibration_args(k, pool, 0.5 if calibration is None else calibration,
+                                                                                  calibration_alpha)
         elif pool is not None and not sampled:
-            raise ValueError("pool is the candidate count of the re-ranking: give diversity, max_per_group or sample_seed as well")
+            raise ValueError("pool is the candidate count of the re-ranking: give diversity, max_per_group, calibrate or sample_seed as well")
         allow, row_filter = engine_mod.check_item_filter(allow, row_filter, self.vocab_size)
         hidden, slots, _ = self._ranked_slot_hidden(encoder_input)
         dev = self.device
         if hidden is None:
             out = (torch.empty((0, k), dtype=torch.int64, device=dev), torch.empty((0, k), dtype=torch.float32, device=dev), slots)
-            return out + (self._distribution_dict(None, slots, k),) if return_distribution else out
+            if return_distribution:
+                out += (self._distribution_dict(None, slots, k),)
+            if return_calibration:
+                out += ({"kl": torch.empty((0,), dtype=torch.float64, device=dev),
+                         "target_mass": torch.empty((0, cal[1]), dtype=torch.int64, device=dev)},)
+            return out
         ex_rows = self._excluded_rows(encoder_input, slots, exclude_seen, exclude)
         if sampled and pool is None:
             ids, scores, _ = self.engine.sample_full(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, k, sample_seed, allow, row_filter,
@@ -397,10 +425,32 @@ class BERT4RecModel:
             ids, scores, _, _ = self.engine.rerank_quota(ids, scores, k, 0.0 if diversity is None else diversity, quotas)
         elif diversity is not None:
             ids, scores, _ = self.engine.rerank_diverse(ids, scores, k, diversity)
-        if not return_distribution:
-            return ids, scores, slots
-        dist = self.engine.score_distribution(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, allow, row_filter, temperature, ids)
-        return ids, scores, slots, self._distribution_dict(dist, slots, k)
+        elif cal is not None:
+            labels_d = cal[0].to(dev)
+            target = self._calibration_target(cal[2], encoder_input, slots, hidden, ex_rows, labels_d, cal[1], allow, row_filter, temperature)
+            ids, scores, _, _, kl = self.engine.rerank_calibrated(ids, scores, k, cal_lambda, labels_d, cal[1], target, cal_alpha)
+        out = (ids, scores, slots)
+        if return_distribution:
+            dist = self.engine.score_distribution(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, None, allow, row_filter, temperature, ids)
+            out += (self._distribution_dict(dist, slots, k),)
+        if return_calibration:
+            out += ({"kl": kl, "target_mass": target},)
+        return out
+
+    def _calibration_target(self, target, encoder_input, slots: torch.Tensor, hidden, ex_rows, labels_d: torch.Tensor, G: int, allow,
+                            row_filter, temperature) -> torch.Tensor:
+        """The target masses int64 [R, G] of a calibrated re-ranking on the device: the label counts of every ranked slot's own
+        input_word_ids ("history"), _group_affinity's masses of the same rows ("affinity"), or the caller's tensor."""
+        R = int(slots.numel())
+        if isinstance(target, str) and target == "history":
+            P = int(torch.as_tensor(encoder_input["masked_lm_positions"]).shape[1])
+            tokens = torch.as_tensor(encoder_input["input_word_ids"]).to(device=self.device, dtype=torch.int64)
+            return engine_mod.group_history_counts(tokens[torch.div(slots, P, rounding_mode="floor")], labels_d, G)
+        if isinstance(target, str):
+            return self._group_affinity(hidden, ex_rows, labels_d, G, allow, row_filter, temperature)["group_mass"]
+        if int(target.shape[0]) != R:
+            raise ValueError(f"the calibration target holds {int(target.shape[0])} rows for {R} ranked slots")
+        return target.to(self.device).contiguous()
 
     def _excluded_rows(self, encoder_input, slots: torch.Tensor, exclude_seen: bool, exclude) -> Optional[torch.Tensor]:
         """The exclude list of every ranked slot [R, E]: the row's own input_word_ids (exclude_seen) and / or its row of `exclude`."""
@@ -481,23 +531,26 @@ class BERT4RecModel:
 
     def recommend(self, encoder_input: dict, k: int = 10, exclude_seen: bool = True, exclude=None, diversity: Optional[float] = None,
                   pool: Optional[int] = None, max_per_group=None, return_distribution: bool = False,
-                  temperature: float = 1.0, sample_seed: Optional[int] = None, sample_streams=None):
+                  temperature: float = 1.0, sample_seed: Optional[int] = None, sample_streams=None, calibrate=None,
+                  calibration: Optional[float] = None, calibration_alpha: float = 0.01, return_calibration: bool = False):
         """recommend_tensor as Python lists: per batch row, one list per ranked slot of (ids, scores) lists of length k.
         return_distribution: the entries are (ids, scores, log probabilities) instead, and recommend_tensor's dict follows as a second
-        return value (device tensors)."""
+        return value (device tensors).  calibrate / calibration / calibration_alpha: recommend_tensor's; return_calibration: its
+        dict of device tensors follows as the last return value."""
         got = self.recommend_tensor(encoder_input, k, exclude_seen, exclude, diversity=diversity, pool=pool,
                                     max_per_group=max_per_group, return_distribution=return_distribution, temperature=temperature,
-                                    sample_seed=sample_seed, sample_streams=sample_streams)
+                                    sample_seed=sample_seed, sample_streams=sample_streams, calibrate=calibrate, calibration=calibration,
+                                    calibration_alpha=calibration_alpha, return_calibration=return_calibration)
         ids, scores, slots = got[:3]
         B, P = (int(x) for x in torch.as_tensor(encoder_input["masked_lm_positions"]).shape)
         out = [[] for _ in range(B)]
         if not return_distribution:
             for s, i_row, s_row in zip(slots.cpu().tolist(), ids.cpu().tolist(), scores.cpu().tolist()):
                 out[s // P].append((i_row, s_row))
-            return out
+            return (out, got[3]) if return_calibration else out
         for s, i_row, s_row, p_row in zip(slots.cpu().tolist(), ids.cpu().tolist(), scores.cpu().tolist(), got[3]["logp"].cpu().tolist()):
             out[s // P].append((i_row, s_row, p_row))
-        return out, got[3]
+        return (out,) + tuple(got[3:]) if return_calibration else (out, got[3])
 
     def _one_slot_batch(self, caller: str, encoder_input, exclude, allow, row_filter, max_len: bool = False):
         """What recommend_sequence_tensor and explain_tensor do before their first forward: the checks of exclude [B, E], allow and

@@ -387,6 +387,38 @@ int b4r_rerank_quota(const float* table, int32_t ld, int32_t width, int32_t V, c
                      const float* pool_scores, int32_t R, int32_t M, float lambda, int32_t K, const b4r_item_quota* quotas,
                      int32_t n_quotas, int64_t* out_ids, float* out_scores, float* out_mmr, int32_t* out_pos, void* scratch,
                      int64_t scratch_bytes, b4r_stream_t stream);
+/* Calibrated re-ranking (Steck, "Calibrated Recommendations", RecSys 2018): pick K of the pool's M candidates so that the list's
+ * shares of the item groups follow a per-row target distribution.  pool_ids / pool_scores [R, M] as in b4r_rerank_quota (there is no
+ * item table and no rnorm, hence no scratch).  item_group [V] int32: one label per item, a value outside [0, G) = the item is in
+ * no group.  target_mass [R, G] int64 in any non-negative unit (history counts, b4r_group_mass's units of 2^-40); a negative value
+ * counts as 0.  Every arithmetic step below is one IEEE operation rounded on its own (no contraction), ln = the fixed fp64 sequence
+ * of the Gumbel noise (b4r_gumbel_from_hash), so the host restatement in tests/calibrated_ref.py has the same bits.  Row r:
+ *   live, rel_c   b4r_rerank_quota's: id in [0, V) and a finite score; rel = (s - s_min) / (s_max - s_min), 1.0f when all are equal.
+ *   T, p_g        T = the exact integer sum of the row's clamped masses (the caller keeps it below 2^63), p_g = fl64((double) mass_g /
+ *                 (double) T); T = 0: every p_g is 0.
+ *   n_g, n        the number of picks so far with label g; the number of picks so far (items in no group count in n).
+ *   qt(g, c, m)   = fl64(fl64(fl64(A * (double) c) / (double) m) + fl64(alpha * p_g)), A = fl64(1 - alpha): the share c / m of the
+ *                 list, smoothed towards the target (Steck's q~ = (1 - alpha) q + alpha p).
+ *   gain_g        at the step that makes pick number n + 1: fl32(fl64(p_g * fl64(ln qt(g, n_g + 1, n + 1) - ln qt(g, n_g, n + 1)))),
+ *                 and 0.0f when p_g = 0 and for an item in no group: the part of -KL(p || q~(list + c)) that differs between the
+ *                 candidates c of one step.
+ *   val_c         = fl32(fl32(fl32(1 - lambda) * rel_c) + fl32(lambda * gain_g(c))).
+ *   step t = 0 .. K-1 picks the live, unpicked entry with the largest val (-0.0 equals +0.0), ties to the lower pool position, and
+ *                 writes out_ids[r][t] = its id, out_scores[r][t] = its pool score, out_value[r][t] = its val, out_pos[r][t] = its
+ *                 pool position (int32); when no live entry is left the remaining outputs are -1 / -inf / -inf / -1.
+ *   out_kl[r]     double: the miscalibration of the final list, sum over the g with p_g > 0 of fl64(p_g * fl64(ln p_g - ln qt(g, n_g,
+ *                 n))), added in ascending g with one fp64 add each; NaN when T = 0 or nothing was picked.
+ * lambda = 0 picks by rel alone: for a pool that is sorted best first (b4r_rank_full's) the result is the pool's live entries in pool
+ * order, and out_kl the miscalibration of the plain top K.  lambda in [0, 1], alpha in (0, 1) (else B4R_E_BADARG; alpha * p_g must
+ * be a normal double: with the masses of the two sources named above it is for every alpha >= 1e-280); 1 <= M <= 1024,
+ * 0 <= K <= M, V >= 1, 1 <= G <= 1024 (else B4R_E_SHAPE); pool_ids, pool_scores, item_group or target_mass NULL with R > 0:
+ * B4R_E_BADARG.  Any output may be NULL.  All checks happen before any launch and before an empty call returns; a refused call
+ * leaves the outputs untouched.  R = 0, or no output to write (K = 0 without out_kl), succeeds and launches nothing.  item_group is
+ * read only at live ids.  Only enqueues (one launch of one 256-thread workgroup per row; one stream, no host sync, no scratch,
+ * graph-capturable); no atomics, bitwise reproducible. */
+int b4r_rerank_calibrated(const int64_t* pool_ids, const float* pool_scores, int32_t R, int32_t M, int32_t K, int32_t V,
+                          const int32_t* item_group, int32_t G, const int64_t* target_mass, float lambda, double alpha,
+                          int64_t* out_ids, float* out_scores, float* out_value, int32_t* out_pos, double* out_kl, b4r_stream_t stream);
 /* Beyond-accuracy metrics of recommendation lists list_ids [R, K] int64 (b4r_rank_full's top K or b4r_rerank_diverse's picks) in
  * table [V, width]: intra-list distance, novelty, hit position, item exposure.  Row r, positions p = 0 .. K-1:
  *   live        list_ids[r][p] in [0, V); the -1 tail and every other id are skipped everywhere.  A repeated id counts once per
