@@ -20,6 +20,7 @@
 // columns x rows 4g+s (A operand of the products that consume an accumulator tile).  A workgroup is 8 waves = 128 queries
 // (or keys): K and V (52 KB at L = 200) are staged once per 128 rows and two workgroups fit a CU (16 waves).
 #include "b4r_common.h"
+#include "b4r_internal.h"
 
 namespace {
 
@@ -335,14 +336,6 @@ int check_bits(const char* who, const DropArgs& drop, const uint32_t* keep_bits)
 
 }  // namespace
 
-int64_t b4r_attn_rx_keep_words(int B, int L, int heads);
-int b4r_attn_rx_fwd_launch(const float* qkv, const int64_t* mask, int B, int L, int heads, float* ctx, float* lse,
-                           const DropArgs& drop, uint32_t* keep_bits, hipStream_t stream);
-int b4r_attn_rx_bwd_launch(const float* qkv, const int64_t* mask, const float* ctx, const float* lse, const float* dctx,
-                           int B, int L, int heads, float qscale, float* dqkv, const DropArgs& drop,
-                           const uint32_t* keep_bits, hipStream_t stream);
-
-int64_t b4r_attn32_keep_words(int32_t B, int32_t L, int32_t heads);
 extern "C" int64_t b4r_attn_keep_words(int32_t B, int32_t L, int32_t heads) {
   if (B <= 0 || L <= 0 || heads <= 0) return 0;
   // round 1's layout (b4r_attn_rx.hip), then one word per (query, 32-key tile) for b4r_attn32.hip's backward

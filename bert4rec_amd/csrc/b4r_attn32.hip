@@ -31,6 +31,7 @@
 // self_attention_layer_norm); the backward is tape.gradient of that call (bert4rec_model.py:166-167).
 #include <type_traits>
 #include "b4r_tile32.h"
+#include "b4r_internal.h"
 
 namespace {
 
@@ -1794,7 +1795,6 @@ int32_t b4r_attn32_preferred(int32_t hidden_size, int32_t num_heads, int32_t L) 
 }
 
 // ---- the attention core for any number of 32-wide heads (b4r_attn_fwd / b4r_attn_bwd in the bf16x3 mode) ----------------------
-int64_t b4r_attn_rx_keep_words(int B, int L, int heads);
 bool b4r_attn32_core_preferred(int L) {
   return L > 0 && L <= 224 && L >= g_attn32_min_len && b4r_split_mode();
 }
@@ -1941,9 +1941,6 @@ extern "C" int b4r_debug_a32_sweep(long long* host_out) {   // [2 waves][64] sta
   return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_a32_sweep), 128 * sizeof(long long)) == hipSuccess ? 0 : -4;
 }
 #endif
-int64_t b4r_attn_rx_keep_words(int B, int L, int heads);
-int b4r_launch_slab_reduce_full(const float* slab, int S, int Mo, int No, float* out, int ldo, int accumulate,
-                                const float* cslab, float* colsum, const float* caslab, float* colsum_a, hipStream_t stream);
 
 int b4r_attn32_bwd(const b4r_attn_block_bwd_desc* d, b4r_stream_t stream) {
   B4R_CHECK_ARG(d != nullptr, B4R_E_BADARG, "b4r_attn_block_bwd: null descriptor");

@@ -30,8 +30,6 @@ constexpr int HD = 64;            // head width
 constexpr int WAVES = 8;          // waves per workgroup
 constexpr int ROWS_WG = 16 * WAVES;
 
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-
 struct Attn64P {
   const float* qkv; const int64_t* mask; const float* ctx; const float* lse_in; const float* dctx;
   float* ctx_out; float* lse_out; float* dqkv;

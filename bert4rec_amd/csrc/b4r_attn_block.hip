@@ -20,6 +20,7 @@
 //   4. y^T = Wo^T.ctx^T straight from the two heads' accumulators, bias, dropout, residual, LayerNorm (two 4-lane shuffles).
 // LDS: Wo image 16 KB + max(Wqkv image 48 KB, K / V images of both heads: 8 KB per 16 tokens) + the key mask.
 #include "b4r_block_tiles.h"
+#include "b4r_internal.h"
 
 namespace {
 
@@ -728,10 +729,6 @@ bool al16(const void* q) { return q == nullptr || b4r_aligned16(q); }
 
 }  // namespace
 
-int32_t b4r_attn32_supported(int32_t hidden_size, int32_t num_heads, int32_t L);
-int32_t b4r_attn32_preferred(int32_t hidden_size, int32_t num_heads, int32_t L);   // supported AND long enough to pay (b4r_attn32.hip)
-int b4r_attn32_bwd(const b4r_attn_block_bwd_desc* d, b4r_stream_t stream);
-int64_t b4r_attn_rx_keep_words(int B, int L, int heads);
 bool b4r_attn32_active(int H, int heads, int L) { return b4r_attn32_preferred(H, heads, L) != 0; }
 
 extern "C" int32_t b4r_attn_block_supported(int32_t hidden_size, int32_t num_heads, int32_t L) {
@@ -753,9 +750,6 @@ extern "C" int64_t b4r_attn_block_bwd_scratch_floats(int32_t B) { return (int64_
 extern "C" int64_t b4r_attn_block_bwd_dw_scratch_floats(int32_t B) {
   return (int64_t)(B > 0 ? B : 0) * (HID * 3 * HID + 3 * HID + HID * HID + HID);   // dWqkv, dbqkv, dWo, dbo partials per sequence
 }
-
-int b4r_launch_slab_reduce_full(const float* slab, int S, int Mo, int No, float* out, int ldo, int accumulate,
-                                const float* cslab, float* colsum, const float* caslab, float* colsum_a, hipStream_t stream);
 
 extern "C" int b4r_attn_block_bwd(const b4r_attn_block_bwd_desc* d, b4r_stream_t stream) {
   B4R_CHECK_ARG(d != nullptr, B4R_E_BADARG, "b4r_attn_block_bwd: null descriptor");
@@ -807,7 +801,6 @@ extern "C" int b4r_attn_block_bwd(const b4r_attn_block_bwd_desc* d, b4r_stream_t
   return b4r_launch_slab_reduce_full(d->scratch, d->B, 1, 128, d->dprev_gamma, 128, 0, nullptr, nullptr, nullptr, nullptr, s);
 }
 
-int b4r_attn32_fwd(const b4r_attn_block_desc* d, b4r_stream_t stream);
 extern "C" int b4r_attn_block_fwd(const b4r_attn_block_desc* d, b4r_stream_t stream) {
   B4R_CHECK_ARG(d != nullptr, B4R_E_BADARG, "b4r_attn_block_fwd: null descriptor");
   // The 32-token-tile forward writes the attention-dropout decisions in the 32-key-tile layout ONLY.  Its readers are the

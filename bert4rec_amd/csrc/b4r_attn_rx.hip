@@ -18,6 +18,7 @@
 //     kernels read them back instead of hashing every (query, key) pair twice more.  Word layout: [b, head, query tile of
 //     16, key-tile group of 8][forward lane]; nibble (t & 7) of the word holds keys 16t + 4g .. +3 of query (lane & 15).
 #include "b4r_rx_tiles.h"
+#include "b4r_internal.h"
 
 namespace {
 
@@ -390,15 +391,6 @@ int set_lds(K kernel, size_t bytes) { return b4r_raise_lds((const void*)kernel, 
 int64_t b4r_attn_rx_keep_words(int B, int L, int heads) { return (int64_t)B * heads * b4r_cdiv(L, 16) * 128; }
 
 // called by b4r_attn_fwd / b4r_attn_bwd (argument checks already done there) in the bf16x3 mode
-// b4r_attn32.hip: the core on 32-token tiles (one workgroup per sequence and head, one launch each way), preferred from L = 65 to 224
-bool b4r_attn32_core_preferred(int L);
-bool b4r_attn32_core_fwd_wanted();
-int64_t b4r_attn_rx_keep_words(int B, int L, int heads);
-int b4r_attn32_core_fwd_launch(const float* qkv, const int64_t* mask, int B, int L, int heads, float* ctx, float* lse,
-                               const DropArgs& drop, uint32_t* keep_bits, hipStream_t stream);
-int b4r_attn32_core_bwd_launch(const float* qkv, const int64_t* mask, const float* ctx, const float* lse, const float* dctx, int B,
-                               int L, int heads, float qscale, float* dqkv, const DropArgs& drop, const uint32_t* keep_bits,
-                               hipStream_t stream);
 
 template <int TERMS>
 static int rx_fwd_launch(AttnRxP p, int KTt, hipStream_t stream) {

@@ -1,7 +1,7 @@
 // The cosine of two item-table rows as b4r_item_neighbours(B4R_SIM_COSINE) defines it (include/b4r.h), for the kernels that walk
 // table rows against one query held in LDS: b4r_rerank_diverse / b4r_rerank_quota (the picked item is the query) and b4r_list_metrics
 // (the earlier list position is the query).  One convention, stated once (mmr_kernel keeps b4r_cosine_chains' loop written out:
-// DESIGN.md 6.3), and one launch that fills rnorm for all four entry points:
+// DESIGN.md 6.3), and one launch that fills rnorm for all four entry points (b4r_item_rnorm_launch, b4r_internal.h):
 //   rnorm[j]  = 1 / sqrt(max(sum_k table[j][k]^2, 1e-24f))                       one fp32 fma per element, k ascending
 //   qhat[k]   = fl32(table[q][k] * rnorm[q])
 //   sim(c, q) = fl32((fma-chain_k(qhat[k] * table[c][k]) + 0.0f) * rnorm[c])     k ascending, fp32, no MFMA
@@ -17,10 +17,6 @@ inline char* b4r_scratch_carve(void* scratch, int64_t scratch_bytes, int64_t nee
   const int64_t pad = scratch ? (int64_t)((16 - ((uintptr_t)scratch & 15)) & 15) : 0;
   return scratch && scratch_bytes - pad >= need ? reinterpret_cast<char*>(scratch) + pad : nullptr;
 }
-
-// rnorm[j] = 1 / |table row j| for j < V, one thread per row (b4r_rank_full.hip): enqueues the one launch and checks nothing; the
-// caller's B4R_CHECK_LAUNCH after its own kernels covers it
-void b4r_item_rnorm_launch(const float* table, int width, int V, float* rnorm, hipStream_t stream);
 
 // ---- device ----------------------------------------------------------------------------------------------------------------------
 // 1 / |row| of one table row of H floats (H % 4 == 0, 16-byte aligned): k ascending, one fp32 fma per element, a fixed order, so

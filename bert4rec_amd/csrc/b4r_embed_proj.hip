@@ -16,9 +16,7 @@
 // and in the B4R_GEMM_F32 mode, the backward's de = dx0 . Wp^T (K = H) and dWp = e^T . dx0 (K = rows) always.  No atomics: the
 // backward's column sums go through per-workgroup slabs and the caller's ordered reduce queue, bitwise reproducible.
 #include "b4r_common.h"
-
-int b4r_launch_slab_reduce_full(const float* slab, int S, int Mo, int No, float* out, int ldo, int accumulate,
-                                const float* cslab, float* colsum, const float* caslab, float* colsum_a, hipStream_t stream);
+#include "b4r_internal.h"
 
 namespace {
 
@@ -42,8 +40,6 @@ struct EmbProjP {
   float* ln_part;      // [nA][2E]
   int nA, S, rows_per_s;
 };
-
-typedef float f32x8 __attribute__((ext_vector_type(8)));
 
 // one 32-k operand fragment of a 16 x 16 block: lane l holds k = 8 (l / 16) .. + 7 of its row (A) or column (B) of the block, as fp32
 // values and (BF) their bf16 hi / lo split.  The accumulator: rows 4 (l / 16) + i, column l % 16.

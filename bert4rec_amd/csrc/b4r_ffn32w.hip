@@ -17,6 +17,7 @@
 // instruction (the waves issue in order: see the notes in b4r_head32.hip).  The second product runs k-step 0 over all panels first, so
 // the GELU of accumulator registers 8..15 still overlaps its first half.  Epilogue in registers: + b2, dropout, + x1, LayerNorm.
 #include "b4r_tile32.h"
+#include "b4r_internal.h"
 
 // timing experiments only (tools/build_variant.sh x b4r_ffn32w.hip -DF32W_EXP=n): 1 no GELU arithmetic, 2 no first product, 4 no second
 // product, 8 no copies inside the loop, 16 no barrier inside the loop, 32 fragment reads once per step

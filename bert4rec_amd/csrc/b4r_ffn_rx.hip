@@ -33,6 +33,7 @@
 // tiles needed two 8-byte reads per fragment; hipcc fused the hi / lo pair into ds_read2st64_b64, which banks modulo 32 and
 // ran the input-gradient kernel at 72 % LDS bank-conflict cycles.)
 #include "b4r_block_tiles.h"
+#include "b4r_internal.h"
 
 namespace {
 
@@ -563,9 +564,6 @@ extern "C" int b4r_ffn_block_fwd(const b4r_ffn_desc* d, b4r_stream_t stream) {
   B4R_CHECK_LAUNCH("b4r_ffn_block_fwd");
   return B4R_OK;
 }
-
-int b4r_launch_slab_reduce_full(const float* slab, int S, int Mo, int No, float* out, int ldo, int accumulate,
-                                const float* cslab, float* colsum, const float* caslab, float* colsum_a, hipStream_t stream);
 
 extern "C" int b4r_ffn_block_bwd(const b4r_ffn_desc* d, b4r_stream_t stream) {
   B4R_CHECK_ARG(d != nullptr, B4R_E_BADARG, "b4r_ffn_block_bwd: null descriptor");

@@ -11,6 +11,7 @@
 // The k index fed to the two lane halves is permuted (half h takes k = 8t+4h+r) so that one ds_read_b128 serves four
 // MFMA steps; A and B use the same permutation, so the sum over k is unchanged.
 #include "b4r_common.h"
+#include "b4r_internal.h"
 
 namespace {
 
@@ -602,14 +603,6 @@ int b4r_launch_slab_reduce_full(const float* slab, int S, int Mo, int No, float*
 }
 
 // ---- arithmetic mode of the dense layers ------------------------------------------------------------------------------
-int b4r_gemm_rx_launch(const b4r_gemm_desc* d, hipStream_t stream);
-bool b4r_gemm_rx_supported(const b4r_gemm_desc* d);
-bool b4r_gemm_rx_tn_supported(const b4r_gemm_tn_desc* d);
-int64_t b4r_gemm_rx_tn_scratch_floats(int R, int Mo, int No);
-int b4r_gemm_rx_tn_launch(const b4r_gemm_tn_desc* d, float* scratch, hipStream_t stream);
-bool b4r_gemm_rx_tn_pair_supported(const b4r_gemm_tn_desc* d0, const b4r_gemm_tn_desc* d1);
-int b4r_gemm_rx_tn_pair_launch(const b4r_gemm_tn_desc* d0, float* scratch0, const b4r_gemm_tn_desc* d1, float* scratch1,
-                               hipStream_t stream);
 static int g_gemm_mode = B4R_GEMM_BF16X3;
 extern "C" int b4r_set_gemm_mode(int mode) {
   B4R_CHECK_ARG(mode == B4R_GEMM_F32 || mode == B4R_GEMM_BF16X3 || mode == B4R_GEMM_BF16, B4R_E_BADARG,
@@ -706,9 +699,6 @@ extern "C" int b4r_gemm_f32(const b4r_gemm_desc* d, b4r_stream_t stream) {
 
 // C[M,N] = A.B with the K range split over `splits` workgroups per tile: partial products go to slabs in `scratch`
 // (>= splits*M*N floats) and are summed in a fixed order.  Used where M*N is small and K is long (dT = dlogits.E, K = V).
-bool b4r_gemm_rx_splitk_supported(const b4r_gemm_desc* d, int k_pad_ok);
-int b4r_gemm_rx_splitk_launch(const b4r_gemm_desc* d, int splits, float* slabs, int* slabs_used, hipStream_t stream);
-
 int b4r_gemm_f32_splitk(const b4r_gemm_desc* d, int splits, float* scratch, int k_pad_ok, hipStream_t stream) {
   B4R_CHECK_ARG(d && scratch && d->epilogue == B4R_EPI_NONE && !d->a_dropout, B4R_E_BADARG, "gemm_splitk: plain product only");
   if (splits > 1 && b4r_split_mode() && b4r_gemm_rx_splitk_supported(d, k_pad_ok)) {

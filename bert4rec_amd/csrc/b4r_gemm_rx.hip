@@ -30,11 +30,7 @@
 #include <stdlib.h>
 
 #include "b4r_common.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
+#include "b4r_internal.h"
 
 namespace {
 
@@ -1413,9 +1409,6 @@ int b4r_gemm_rx_splitk_launch(const b4r_gemm_desc* d, int splits, float* slabs, 
   B4R_CHECK_LAUNCH(b4r_gemm_terms() == 1 ? "gemm_splitk (bf16)" : "gemm_splitk (bf16x3)");
   return B4R_OK;
 }
-
-int b4r_launch_slab_reduce_full(const float* slab, int S, int Mo, int No, float* out, int ldo, int accumulate,
-                                const float* cslab, float* colsum, const float* caslab, float* colsum_a, hipStream_t stream);
 
 bool b4r_gemm_rx_tn_supported(const b4r_gemm_tn_desc* d) {
   if (!vec_ok(d->A, d->lda) || !vec_ok(d->B, d->ldb)) return false;

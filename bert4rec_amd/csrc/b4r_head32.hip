@@ -29,6 +29,7 @@
 // dE sweep and the transform's LayerNorm backward: b4r_head_merge.h) merges the slices flash-decoding style into loss rows, lse and dT.
 // dE's partial tiles per M slice go to slabs that the backward's ordered reduction sums.
 #include "b4r_head32_pack.h"
+#include "b4r_internal.h"
 
 // H32_PROF (tools/build_variant.sh h32prof b4r_head32.hip -DH32_PROF): lane 0 of waves 0 and 5 of two workgroups stamps the shader clock
 #ifdef H32_PROF
@@ -948,9 +949,6 @@ int b4r_head32_dE_pack_job(const float* T, const float* lse, const int32_t* ylab
   *blocks = b4r_cdiv(M, 32);
   return B4R_OK;
 }
-
-int b4r_launch_slab_reduce_full(const float* slab, int S, int Mo, int No, float* out, int ldo, int accumulate,
-                                const float* cslab, float* colsum, const float* caslab, float* colsum_a, hipStream_t stream);
 
 // dE [V,H] and db [V] (overwritten, through the ordered slab reduction) from T, E, bias and the forward's lse / labels.
 // fwd_part != NULL: the forward ran with only_sweep = 1 and left its per-slice partials there; lse / ylab are not read (y: the labels),

@@ -18,6 +18,7 @@
 //      the 256 partial sums follows: the double sums are bitwise reproducible from run to run, as b4r_rank_metrics' are.
 // No float atomics anywhere.
 #include "b4r_common.h"
+#include "b4r_internal.h"
 #include "b4r_cosine_chain.h"
 #include "b4r_wave.h"
 

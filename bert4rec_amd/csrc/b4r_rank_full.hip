@@ -30,6 +30,7 @@
 #include <algorithm>
 
 #include "b4r_common.h"
+#include "b4r_internal.h"
 #include "b4r_catalogue_tile.h"
 #include "b4r_cosine_chain.h"
 

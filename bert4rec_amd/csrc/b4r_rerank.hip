@@ -35,6 +35,7 @@
 #include <type_traits>
 
 #include "b4r_common.h"
+#include "b4r_internal.h"
 #include "b4r_cosine_chain.h"
 #include "b4r_wave.h"
 

@@ -7,11 +7,7 @@
 #include "b4r_common.h"
 #include "b4r_head_merge.h"
 #include "b4r_head32_pack.h"
-
-int b4r_launch_slab_reduce_full(const float* slab, int S, int Mo, int No, float* out, int ldo, int accumulate,
-                                const float* cslab, float* colsum, const float* caslab, float* colsum_a, hipStream_t stream);
-int b4r_launch_slab_reduce(const float* slab, int S, int Mo, int No, float* out, int ldo, int accumulate,
-                           hipStream_t stream);
+#include "b4r_internal.h"
 
 namespace {
 
@@ -1314,9 +1310,6 @@ __global__ __launch_bounds__(256) void sample_candidates_kernel(const float* log
   if (tid == 0) out[C] = g;
 }
 
-extern "C" int b4r_sample_candidates_flagged(const float* logp, int32_t V, const int64_t* exclude, int32_t E, const int64_t* gt,
-                                             int32_t R, int32_t C, uint64_t seed, int64_t* cand, uint8_t* short_flag,
-                                             b4r_stream_t stream);
 extern "C" int b4r_sample_candidates(const float* logp, int32_t V, const int64_t* exclude, int32_t E, const int64_t* gt,
                                      int32_t R, int32_t C, uint64_t seed, int64_t* cand, b4r_stream_t stream) {
   return b4r_sample_candidates_flagged(logp, V, exclude, E, gt, R, C, seed, cand, nullptr, stream);

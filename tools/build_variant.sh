@@ -9,6 +9,6 @@ mkdir -p $root/gpurun_variants
 obj=$root/gpurun_variants/${name}.o
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC "$@" -c $root/bert4rec_amd/csrc/$src -o $obj
 others=$(ls $root/bert4rec_amd/csrc/*.o | grep -v "/${src%.hip}.o")
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $root/gpurun_variants/libb4r_${name}.so $obj $others
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,--no-undefined -o ${obj%/*}/libb4r_${name}.so $obj $others
 rm -f $obj
 echo built gpurun_variants/libb4r_${name}.so
