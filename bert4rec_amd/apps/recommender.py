@@ -299,6 +299,57 @@ class Recommender:
             out.append((items[0] if items else None) if k == 1 else items)   # None: nothing is left to recommend (filtered or not)
         return out
 
+    def item_ranks(self, sequences, items=None, items_per_user=None, allowed_items=None, allowed_items_per_user=None) -> list:
+        """Where given items stand for every user: "X is at 312 of 26 000 for this user" -- the position the item has in
+        recommend_batch's order (the same exclusions: every item of the user's sequence; the same filters), from one batched forward,
+        one b4r_item_ranks sweep and one read-back, however many items are asked about.  items: one iterable of items for all users,
+        or items_per_user: one iterable per sequence.  Returns per user a list with one dict per asked item, in the order given:
+          item   the item as given
+          rank   its 1-based position among the items the user could be served; None for an item the vocabulary does not know,
+                 that the user has seen, or that the filter does not allow
+          of     the number of items the user could be served
+          score  the item's score (None for an item the vocabulary does not know)."""
+        if (items is None) == (items_per_user is None):
+            raise ValueError("give items or items_per_user, one of them")
+        sequences = [list(seq) for seq in sequences]
+        if items is not None:
+            asked = [list(items)] * len(sequences)
+        else:
+            asked = [list(it) for it in items_per_user]
+            if len(asked) != len(sequences):
+                raise ValueError(f"{len(asked)} item lists for {len(sequences)} sequences")
+        allow, user_filter = self._allow_filters(len(sequences), allowed_items, allowed_items_per_user)
+        if not sequences:
+            return []
+        if items is not None:
+            tokens = [self._token_ids(asked[0]).tolist()] * len(sequences)
+        else:
+            tokens = [self._token_ids(it).tolist() for it in asked]
+        batch, exclude = self._requests(sequences)
+        slot_user = torch.nonzero(batch["masked_lm_weights"] != 0, as_tuple=True)[0]
+        row_filter = None if user_filter is None else user_filter[slot_user]
+        query = self._padded_ids(tokens)[slot_user]
+        got = self.model.item_ranks_tensor(batch, query, exclude_seen=False, exclude=exclude, allow=allow, row_filter=row_filter)
+        Q = int(query.shape[1])
+        # ranks, scores, n and the slots in one copy: an int32 and an fp32 are exact in float64
+        both = torch.cat([got["ranks"].to(torch.float64), got["scores"].to(torch.float64), got["n"].to(torch.float64)[:, None],
+                          got["slot_index"].to(torch.float64)[:, None]], dim=1).cpu()
+        P = int(batch["masked_lm_positions"].shape[1])
+        first = {}
+        for i, s in enumerate(both[:, 2 * Q + 1].to(torch.int64).tolist()):   # the first weighted slot of the user's row, as recommend_batch
+            first.setdefault(s // P, i)
+        rows = both.tolist()
+        out = []
+        for b, its in enumerate(asked):
+            if b not in first:
+                out.append([{"item": item, "rank": None, "of": 0, "score": None} for item in its])
+                continue
+            row = rows[first[b]]
+            n = int(row[2 * Q])
+            out.append([{"item": item, "rank": int(row[j]) if row[j] > 0 else None, "of": n,
+                         "score": row[Q + j] if tokens[b][j] >= 0 else None} for j, item in enumerate(its)])
+        return out
+
     def recommend_sequences(self, sequences, steps: int, beams: int = 1, expand=None, allowed_items=None, allowed_items_per_user=None,
                             temperature: float = 1.0, sample_seed=None, user_streams=None, return_probabilities: bool = False) -> list:
         """The next `steps` items of every sequence IN ORDER, each one conditioned on the ones before (queue continuation, "watch

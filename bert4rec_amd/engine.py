@@ -158,6 +158,30 @@ def check_rank_full_args(k, exclude: Optional[torch.Tensor] = None, n_rows: Opti
     return k
 
 
+ITEM_RANKS_MAX_Q = 256
+ITEM_RANKS_MEMBERS = {"strict": 0, "self": 1, "joint": 2}   # B4R_RANKS_*
+
+
+def check_item_ranks_args(query_ids, n_rows: Optional[int] = None, members="strict", max_columns: Optional[int] = ITEM_RANKS_MAX_Q):
+    """Argument checks of Engine.item_ranks that need no GPU: query_ids an integer tensor [R, Q] with Q <= 256 (max_columns None: any
+    Q), members one of "strict" / "self" / "joint".  Returns (query_ids as an int64 tensor, Q, the B4R_RANKS_* value)."""
+    if not isinstance(members, str) or members not in ITEM_RANKS_MEMBERS:
+        raise ValueError(f"members must be one of {sorted(ITEM_RANKS_MEMBERS)}, got {members!r}")
+    q = torch.as_tensor(query_ids)
+    if q.ndim != 2 or q.dtype.is_floating_point or q.dtype == torch.bool or q.dtype.is_complex:
+        raise ValueError(f"query_ids must be an integer tensor [rows, Q], got {q.dtype} of shape {tuple(q.shape)}")
+    if n_rows is not None and q.shape[0] != n_rows:
+        raise ValueError(f"query_ids has {q.shape[0]} rows for {n_rows} ranked rows")
+    Q = int(q.shape[1])
+    if max_columns is not None and Q > max_columns:
+        raise ValueError(f"at most {max_columns} query ids per row in one call, got {Q}")
+    return q.to(torch.int64), Q, ITEM_RANKS_MEMBERS[members]
+
+
+# b4r_rank_metrics_multi's families (B4R_MGAIN_*)
+MGAIN_COUNT, MGAIN_HIT, MGAIN_NDCG, MGAIN_MRR, MGAIN_RECALL, MGAIN_MAP, MGAIN_AUC = range(7)
+
+
 def check_temperature(temperature) -> float:
     """Argument check of the softmax temperature that needs no GPU: a finite number > 0 whose inverse is finite and > 0 in fp32.
     Returns b4r_score_dist's inv_temperature = fl32(1 / temperature)."""
@@ -1245,6 +1269,47 @@ class Engine:
                                            _ptr(logp) if K > 0 else None, _ptr(sc), sc.numel(), _stream(self.device)),
                    "b4r_score_dist")
         return n, mx, lse, ent, logp
+
+    def item_ranks(self, hidden: torch.Tensor, rows: Optional[torch.Tensor], exclude: Optional[torch.Tensor], first_item: int,
+                   query_ids, members: str = "strict", allow=None, row_filter=None):
+        """b4r_item_ranks on `hidden` (rank_full's hidden / rows / exclude / first_item / allow / row_filter: the same scores, the same
+        allowed set and the same order): where the ids query_ids [R, Q] (Q <= 256; any padding outside [first_item, V)) stand among
+        the row's allowed items, from one sweep.  members: "strict" (an id the row may not be served gets rank 0), "self" (every valid
+        id is ranked against the allowed items, as rank_full ranks gt) or "joint" (the row's valid ids are ranked in one list with the
+        allowed items).  Returns (ranks [R, Q] int32, 1-based, 0 = none; scores [R, Q] fp32, -inf for an id outside the vocabulary;
+        n [R] int32, the size of the ranked set; member [R, Q] uint8).  The scratch buffer is kept between calls."""
+        R, sweep, filt, keep = self._sweep_rows(hidden, rows, exclude, first_item, None, allow, row_filter)
+        q, Q, mode = check_item_ranks_args(query_ids, R, members)
+        q_d = q.to(self.device).contiguous()
+        ranks = torch.empty((R, Q), dtype=torch.int32, device=self.device)
+        scores = torch.empty((R, Q), dtype=torch.float32, device=self.device)
+        n = torch.empty((R,), dtype=torch.int32, device=self.device)
+        member = torch.empty((R, Q), dtype=torch.uint8, device=self.device)
+        if R == 0:
+            return ranks, scores, n, member
+        sc = self._scratch("b4r_item_ranks", int(self.lib.b4r_item_ranks_scratch_bytes(R, self.cfg.vocab_size, Q)))
+        _lib.check(self.lib.b4r_item_ranks(*sweep[:11], *filt, _ptr(q_d) if Q > 0 else None, Q, mode, _ptr(ranks) if Q > 0 else None,
+                                           _ptr(scores) if Q > 0 else None, _ptr(n), _ptr(member) if Q > 0 else None, _ptr(sc), sc.numel(),
+                                           _stream(self.device)), "b4r_item_ranks")
+        return ranks, scores, n, member
+
+    def rank_metrics_multi(self, ranks: torch.Tensor, row_n: Optional[torch.Tensor], families, cutoffs, gain_sums: torch.Tensor,
+                           users: torch.Tensor) -> None:
+        """b4r_rank_metrics_multi: add the gain sums of this batch's target ranks [R, Q] int32 (item_ranks', "joint") to the device
+        accumulators (float64 [n], int64 [1]).  row_n [R] int32 (item_ranks' n) is needed by the AUC family only."""
+        if ranks.ndim != 2 or ranks.dtype != torch.int32 or not ranks.is_contiguous():
+            raise ValueError(f"ranks must be a contiguous int32 tensor [R, Q], got {ranks.dtype} of shape {tuple(ranks.shape)}")
+        R, Q = (int(x) for x in ranks.shape)
+        if row_n is not None and (row_n.dtype != torch.int32 or row_n.numel() != R or not row_n.is_contiguous()):
+            raise ValueError(f"row_n must be a contiguous int32 tensor [{R}], got {row_n.dtype} of shape {tuple(row_n.shape)}")
+        if len(families) != len(cutoffs):
+            raise ValueError(f"{len(families)} families for {len(cutoffs)} cut-offs")
+        if R == 0 or Q == 0:
+            return
+        fam = (C.c_int32 * len(families))(*families)
+        cut = (C.c_int32 * len(cutoffs))(*cutoffs)
+        _lib.check(self.lib.b4r_rank_metrics_multi(_ptr(ranks), _ptr(row_n), R, Q, fam, cut, len(families), _ptr(gain_sums), _ptr(users),
+                                                   _stream(self.device)), "b4r_rank_metrics_multi")
 
     def rank_joint(self, hidden: torch.Tensor, rows: Optional[torch.Tensor], exclude: Optional[torch.Tensor], first_item: int, parties,
                    k: int, strategy: str = "additive", weights=None, min_member_util: float = -math.inf,

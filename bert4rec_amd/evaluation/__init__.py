@@ -9,7 +9,48 @@ evaluators_map = {"bert4rec": BERT4RecEvaluator}
 def get(identifier: str = "bert4rec", **kwargs) -> BaseEvaluator:
     """kwargs go to the evaluator: metrics, sampler, dataloader, device_sampling, seed, full_ranking, and the list evaluation's list_k,
     diversity, candidate_pool, item_counts, max_per_group, sample_seed and temperature, the calibrated lists' calibrate_by, calibrate_to,
-    calibration and calibration_alpha, and distribution (BERT4RecEvaluator)."""
+    calibration and calibration_alpha, distribution, and multi_target (BERT4RecEvaluator)."""
     if identifier in evaluators_map:
         return evaluators_map[identifier](**kwargs)
     raise ValueError(f"{identifier} is not known!")
+
+
+def next_n_batches(dataloader, sequences, n: int, batch_size: int = 256):
+    """Test batches of the next-n protocol for evaluation.get(full_ranking=True, multi_target=True): a sequence longer than n becomes
+    dataloader.prepare_inference(seq[:-n]) (the history, with the slot to predict appended) plus target_ids = the token ids of
+    seq[-n:], -1 for an item the vocabulary does not know (never added to it).  Shorter sequences are left out.  Returns (a list of
+    batches of at most batch_size rows: numpy int64 arrays, target_ids [rows, n]; the number of sequences left out)."""
+    import numpy as np
+
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"n must be an integer >= 1, got {n!r}")
+    if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+        raise ValueError(f"batch_size must be an integer >= 1, got {batch_size!r}")
+    tokenizer = dataloader.get_tokenizer()
+    rows, skipped = [], 0
+    for seq in sequences:
+        seq = list(seq)
+        if len(seq) <= n:
+            skipped += 1
+            continue
+        row = dataloader.prepare_inference(seq[:-n])
+        extensible = getattr(tokenizer, "_extensible", False)
+        tokenizer.disable_extensibility()
+        targets = np.full((1, n), -1, dtype=np.int64)
+        try:
+            for j, item in enumerate(seq[-n:]):
+                try:
+                    t = tokenizer.tokenize(item)
+                except (RuntimeError, ValueError):
+                    continue
+                if isinstance(t, (int, np.integer)) and t >= 0:
+                    targets[0, j] = int(t)
+        finally:
+            if extensible:
+                tokenizer.enable_extensibility()
+        row = {key: np.asarray(v) for key, v in row.items()}
+        row["target_ids"] = targets
+        rows.append(row)
+    batches = [{key: np.concatenate([r[key] for r in rows[i:i + batch_size]], axis=0) for key in rows[i]}
+               for i in range(0, len(rows), batch_size)]
+    return batches, skipped

@@ -30,7 +30,13 @@ shares follow the row's history or affinity; the results gain Miscalibration@k, 
 distribution=True (with full_ranking) adds the likelihood view: one b4r_score_dist call per batch gives the log probability of every
 ground truth under the softmax over the items it was ranked against, and the row's entropy; their sums stay on the device and are
 read back once per evaluate().  The results gain NLL (the mean -log p of the ground truth), Perplexity (its exp) and Entropy (the
-mean row entropy, in nats)."""
+mean row entropy, in nats).
+
+multi_target=True (with full_ranking) evaluates next-n / next-basket protocols: every test row carries target_ids [B, n] (int64, -1
+padded; next_n_batches builds such batches) and one ranked slot.  Per batch one forward, one b4r_item_ranks call (all targets of a row
+ranked in one list with the items the row could be served: the vocabulary minus the specials and the row's `labels`) and one
+b4r_rank_metrics_multi launch add Recall / HR / NDCG / MAP at the evaluator's cut-offs, MRR and AUC to device accumulators that are
+read back once per evaluate() and merged across a process group."""
 from typing import Union
 
 import numpy as np
@@ -39,7 +45,8 @@ import torch
 from ..dataloaders import samplers
 from ..engine import (CALIBRATION_TARGETS, SPECIAL_IDS, check_calibrate, check_calibration_args, check_quota_args, check_rank_full_args,
                       check_rerank_args, check_sample_pool_args, check_sample_seed, check_temperature, group_history_counts,
-                      item_self_information)
+                      item_self_information, ITEM_RANKS_MAX_Q, MGAIN_AUC, MGAIN_COUNT, MGAIN_HIT, MGAIN_MAP, MGAIN_MRR, MGAIN_NDCG,
+                      MGAIN_RECALL)
 from .base_evaluator import BaseEvaluator
 from .evaluation_metrics import GAIN_COUNT, GAIN_HIT, GAIN_NDCG, HR, MAP, NDCG, Counter, EvaluationMetric, gain_table
 
@@ -71,8 +78,11 @@ class BERT4RecEvaluator(BaseEvaluator):
                  device_sampling: bool = True, seed: int = 0, full_ranking: bool = False, list_k: int = None, diversity: float = None,
                  candidate_pool: int = None, item_counts=None, max_per_group=None, distribution: bool = False, sample_seed: int = None,
                  temperature: float = 1.0, calibrate_by=None, calibrate_to: str = "history", calibration: float = None,
-                 calibration_alpha: float = 0.01):
-        """calibrate_by / calibrate_to / calibration / calibration_alpha (with list_k): evaluate CALIBRATED lists.  calibrate_by: one
+                 calibration_alpha: float = 0.01, multi_target: bool = False):
+        """multi_target: the next-n evaluation of the module docstring; it needs full_ranking=True and does not combine with list_k,
+        distribution, sample_seed, calibrate_by, diversity or max_per_group.  Its cut-offs are those of the HR / NDCG metrics given
+        (1, 5, 10 by default); the single-target metrics themselves are not fed.
+        calibrate_by / calibrate_to / calibration / calibration_alpha (with list_k): evaluate CALIBRATED lists.  calibrate_by: one
         integer label per token id [V] (negative = no group; at most 1024 groups), or (labels, n_groups); calibrate_to "history" (the
         label counts of the row's input_word_ids) or "affinity" (the row's probability mass per group over the items the ground truth
         is ranked against); calibration: lambda in [0, 1] (default 0.5; 0 evaluates the plain top k and its miscalibration).  The
@@ -101,6 +111,17 @@ class BERT4RecEvaluator(BaseEvaluator):
         self.distribution = bool(distribution)
         if self.distribution and not self.full_ranking:
             raise ValueError("distribution evaluates the full-catalogue softmax: it needs full_ranking=True")
+        self.multi_target = bool(multi_target)
+        if self.multi_target:
+            if not self.full_ranking:
+                raise ValueError("multi_target ranks the targets against the whole catalogue: it needs full_ranking=True")
+            if list_k is not None or distribution or sample_seed is not None or calibrate_by is not None or diversity is not None or \
+                    max_per_group is not None:
+                raise ValueError("multi_target does not combine with list_k, distribution, sample_seed, calibrate_by, diversity or "
+                                 "max_per_group")
+        self._mt_dev = None        # (engine, float64 gain sums [len(table)], int64 rows [1])
+        self._mt_table = None      # [(result name or None, family, cut-off)]
+        self._mt_host = None       # [gain sums, rows] read back so far
         self._dist_dev = None      # (engine, float64 [2]: sum of -log p(gt), sum of the row entropies; int64 [1]: the rows)
         self._dist_host = [0.0, 0.0, 0]
         if metrics is None:
@@ -175,6 +196,15 @@ class BERT4RecEvaluator(BaseEvaluator):
                 raise ValueError("the list evaluation accumulates on the device: at most 32 metrics")
             self.list_k, self._list_pool = k, pool
             self._list_novelty = item_counts is not None or dataloader is not None
+        if self.multi_target:
+            ks = sorted({int(m.cutoff) for m in metrics if m.family in (GAIN_HIT, GAIN_NDCG) and m.cutoff >= 1}) or [1, 5, 10]
+            table = [(f"{name}@{k}", fam, k) for k in ks
+                     for name, fam in (("Recall", MGAIN_RECALL), ("HR", MGAIN_HIT), ("NDCG", MGAIN_NDCG), ("MAP", MGAIN_MAP))]
+            table += [("MRR", MGAIN_MRR, 0), ("AUC", MGAIN_AUC, 0), ("Valid Ranks", MGAIN_COUNT, 0)]
+            if len(table) > 32:
+                raise ValueError(f"multi_target accumulates on the device: at most 7 cut-offs, got {ks}")
+            self._mt_table = table
+            self._mt_host = [[0.0] * len(table), 0]
         self._dev = None   # (engine, float64 gain sums [n_metrics], int64 user count [1]) on the GPU
         self._seed = int(seed)
         self._draws = 0
@@ -206,6 +236,9 @@ class BERT4RecEvaluator(BaseEvaluator):
         if self.distribution and world > 1:
             raise ValueError("distribution evaluates on one rank only: its sums are not merged across a process group")
         before = [m.partial() for m in self._metrics]
+        if self.multi_target:
+            self._flush_multi_sums()
+            mt_before = [list(self._mt_host[0]), self._mt_host[1]]
         for i, batch in enumerate(test_data):
             if i % world == rank:
                 self.evaluate_batch(model, batch)
@@ -217,6 +250,8 @@ class BERT4RecEvaluator(BaseEvaluator):
             short = self._merge_across_ranks(before, group, short)
             if short:
                 raise ValueError(self._short_message())
+            if self.multi_target:
+                self._merge_multi_across_ranks(mt_before, group)
         return self._metrics
 
     # ---- device-side accumulation ---------------------------------------------------------------------------------------
@@ -238,6 +273,7 @@ class BERT4RecEvaluator(BaseEvaluator):
         self._flush_list_sums()
         self._flush_dist_sums()
         self._flush_calibration_sums()
+        self._flush_multi_sums()
         if self._dev is None:
             return False
         _, sums, users = self._dev
@@ -254,6 +290,82 @@ class BERT4RecEvaluator(BaseEvaluator):
         sums.zero_()
         users.zero_()
         return False
+
+    # ---- next-n evaluation (multi_target) --------------------------------------------------------------------------------------
+    def _multi_sums(self, engine):
+        if self._mt_dev is None or self._mt_dev[0] is not engine:
+            self._flush_multi_sums()
+            dev = engine.params.device
+            self._mt_dev = (engine, torch.zeros(len(self._mt_table), dtype=torch.float64, device=dev),
+                            torch.zeros(1, dtype=torch.int64, device=dev))
+        return self._mt_dev
+
+    def _flush_multi_sums(self) -> None:
+        """one device -> host copy of the multi-target accumulators per flush: [gain sums | rows] as float64"""
+        if getattr(self, "_mt_dev", None) is None:
+            return
+        _, sums, rows = self._mt_dev
+        back = torch.cat([sums, rows.to(torch.float64)]).cpu().tolist()
+        h = self._mt_host
+        h[0] = [a + b for a, b in zip(h[0], back[:-1])]
+        h[1] += int(back[-1])
+        sums.zero_(); rows.zero_()
+
+    def _merge_multi_across_ranks(self, before, group) -> None:
+        """all-reduce what THIS evaluate() call added on each rank to the multi-target sums: [gain sums | rows] as float64"""
+        import torch.distributed as dist
+        h = self._mt_host
+        dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend(group) == "nccl" else "cpu"
+        buf = torch.tensor([a - b for a, b in zip(h[0], before[0])] + [float(h[1] - before[1])], dtype=torch.float64, device=dev)
+        dist.all_reduce(buf, group=group)
+        tot = buf.cpu().tolist()
+        h[0] = [b + g for b, g in zip(before[0], tot[:-1])]
+        h[1] = before[1] + int(round(tot[-1]))
+
+    def multi_target_results(self) -> dict:
+        """Recall@k, HR@k, NDCG@k, MAP@k at the evaluator's cut-offs, MRR and AUC: the means over the rows with at least one rankable
+        target of everything evaluated since the last reset; Valid Ranks: the number of targets ranked."""
+        if not getattr(self, "multi_target", False):
+            return {}
+        self._flush_multi_sums()
+        sums, rows = self._mt_host
+        out = {}
+        for (name, fam, _), s in zip(self._mt_table, sums):
+            out[name] = int(round(s)) if fam == MGAIN_COUNT else (s / rows if rows else 0.0)
+        return out
+
+    def _evaluate_batch_multi(self, model, test_batch: dict):
+        """multi_target: the ranks of every row's targets, all in one list with the items the row could be served."""
+        engine = getattr(model, "engine", None)
+        if engine is None or engine.device.type != "cuda":
+            raise ValueError("multi_target needs a model on the GPU (b4r_item_ranks)")
+        if "target_ids" not in test_batch or test_batch["target_ids"] is None:
+            raise ValueError("multi_target evaluates batches that carry target_ids [B, n] (evaluation.next_n_batches)")
+        dev = engine.device
+        w = torch.as_tensor(test_batch["masked_lm_weights"])
+        targets = torch.as_tensor(test_batch["target_ids"])
+        if targets.ndim != 2 or targets.dtype.is_floating_point or targets.dtype == torch.bool or targets.shape[0] != w.shape[0]:
+            raise ValueError(f"target_ids must be an integer tensor [{w.shape[0]}, n], got {targets.dtype} of shape {tuple(targets.shape)}")
+        if targets.shape[1] > ITEM_RANKS_MAX_Q:
+            raise ValueError(f"at most {ITEM_RANKS_MAX_Q} targets per row, got {targets.shape[1]}")
+        if w.ndim != 2 or not bool(((w != 0).sum(dim=1) == 1).all()):
+            raise ValueError("multi_target evaluates one ranked slot per row (the mask prepare_inference appends): every row of "
+                             "masked_lm_weights must hold exactly one non-zero weight")
+        if w.shape[0] == 0 or targets.shape[1] == 0:
+            return []
+        b_idx, p_idx = torch.nonzero(w != 0, as_tuple=True)   # one slot per row: b_idx = 0 .. B-1
+        slots = (b_idx * w.shape[1] + p_idx).to(dev)
+        t = targets.to(device=dev, dtype=torch.int64)
+        n = int(t.shape[1])
+        # a repeated target id counts once: -1 after its first occurrence
+        earlier = torch.ones((n, n), dtype=torch.bool, device=dev).tril(-1)
+        t = torch.where(((t[:, :, None] == t[:, None, :]) & earlier).any(dim=2), torch.full_like(t, -1), t)
+        exclude = torch.as_tensor(test_batch["labels"]).to(dev).to(torch.int64)   # the row's own sequence, as the full-ranking path
+        hidden, _, _ = model._ranked_slot_hidden(test_batch, slots)
+        ranks, _, row_n, _ = engine.item_ranks(hidden, None, exclude, SPECIAL_IDS, t, "joint")
+        _, sums, rows = self._multi_sums(engine)
+        engine.rank_metrics_multi(ranks, row_n, [f for _, f, _ in self._mt_table], [k for _, _, k in self._mt_table], sums, rows)
+        return ranks
 
     # ---- likelihood view (distribution) ----------------------------------------------------------------------------------------
     def _dist_sums(self, engine):
@@ -472,6 +584,8 @@ class BERT4RecEvaluator(BaseEvaluator):
         """bert4rec_evaluator.py:60-120 for one batch.  Returns the ground-truth ranks: a device int32 tensor when the metric
         sums are accumulated on the GPU (flushed by evaluate() / get_metrics_results()), else a numpy array."""
         slots = None
+        if getattr(self, "multi_target", False):
+            return self._evaluate_batch_multi(model, test_batch)
         if self.full_ranking and candidates is None:
             return self._evaluate_batch_full(model, test_batch)
         if candidates is None:
@@ -575,7 +689,9 @@ class BERT4RecEvaluator(BaseEvaluator):
 
     def get_metrics_results(self) -> dict:
         self._flush_device_sums()
-        results = super().get_metrics_results()
+        # (multi_target feeds no single-target metric: its HR@k / NDCG@k / Valid Ranks stand in their places)
+        results = {} if getattr(self, "multi_target", False) else super().get_metrics_results()
+        results.update(self.multi_target_results())
         results.update(self.list_results())
         results.update(self.distribution_results())
         results.update(self.calibration_results())
@@ -600,6 +716,11 @@ class BERT4RecEvaluator(BaseEvaluator):
             self._cal_dev[1].zero_()
             self._cal_dev[2].zero_()
         self._cal_host = [0.0, 0]
+        if getattr(self, "_mt_dev", None) is not None:
+            self._mt_dev[1].zero_()
+            self._mt_dev[2].zero_()
+        if getattr(self, "_mt_table", None) is not None:
+            self._mt_host = [[0.0] * len(self._mt_table), 0]
         super().reset_metrics()
 
 

@@ -502,6 +502,58 @@ class BERT4RecModel:
                                               query_ids)
         return self._distribution_dict(dist, slots, None)
 
+    def item_ranks_tensor(self, encoder_input: Dict[str, torch.Tensor], query_ids, exclude_seen: bool = True,
+                          exclude: Optional[torch.Tensor] = None, allow=None, row_filter=None, members: str = "strict"):
+        """Where given items stand for every ranked slot -- recommend_tensor's forward, exclusions (exclude_seen, exclude; [PAD] /
+        [MASK] / [UNK] never count) and filter (allow, row_filter) -- from one forward and one b4r_item_ranks call: no [R, V] scores
+        and no sweep per item.  query_ids: int64 [R, Q], one list per ranked slot (any id outside the vocabulary, such as -1, is
+        padding), or [Q] for all slots.  members: "strict" (an item the slot could not be served has no rank), "self" (every item is
+        ranked against the servable ones, as the full-ranking evaluation ranks its target) or "joint" (the slot's items are ranked
+        in one list together with the servable ones; at most 256 columns).  More than 256 columns are served in blocks of 256 under
+        "strict" / "self", whose columns do not depend on each other.  Returns a dict of device tensors, one entry per ranked slot:
+          ranks       int32 [R, Q]: the 1-based position of the item in recommend_tensor's order (ties to the lower id); 0 = none
+          scores      float32 [R, Q]: the item's score, -inf for an id outside the vocabulary
+          n           int32 [R]: the size of the ranked set ("of n")
+          member      uint8 [R, Q]: 1 where the slot could be served the item
+          slot_index  int64 [R]: b*P+p, as recommend_tensor returns it."""
+        q = torch.as_tensor(query_ids)
+        flat = q.ndim == 1
+        q, Q, _ = engine_mod.check_item_ranks_args(q.reshape(1, -1) if flat else q, None, members, None)
+        if members == "joint" and Q > engine_mod.ITEM_RANKS_MAX_Q:
+            raise ValueError(f'members="joint" ranks at most {engine_mod.ITEM_RANKS_MAX_Q} items per slot in one list, got {Q}')
+        allow, row_filter = engine_mod.check_item_filter(allow, row_filter, self.vocab_size)
+        hidden, slots, _ = self._ranked_slot_hidden(encoder_input)
+        R = int(slots.numel())
+        if flat:
+            q = q.expand(R, Q)
+        elif q.shape[0] != R:
+            raise ValueError(f"query_ids has {q.shape[0]} rows for {R} ranked slots")
+        dev = self.device
+        if hidden is None:
+            return {"ranks": torch.empty((0, Q), dtype=torch.int32, device=dev), "scores": torch.empty((0, Q), dtype=torch.float32, device=dev),
+                    "n": torch.empty((0,), dtype=torch.int32, device=dev), "member": torch.empty((0, Q), dtype=torch.uint8, device=dev),
+                    "slot_index": slots}
+        ex_rows = self._excluded_rows(encoder_input, slots, exclude_seen, exclude)
+        q = q.to(dev)
+        block = engine_mod.ITEM_RANKS_MAX_Q
+        parts = [self.engine.item_ranks(hidden, None, ex_rows, engine_mod.SPECIAL_IDS, q[:, c:c + block].contiguous(), members, allow, row_filter)
+                 for c in range(0, max(Q, 1), block)]
+        if len(parts) == 1:
+            ranks, scores, n, member = parts[0]
+        else:
+            ranks, scores, member = (torch.cat([p[i] for p in parts], dim=1) for i in (0, 1, 3))
+            n = parts[0][2]
+        return {"ranks": ranks, "scores": scores, "n": n, "member": member, "slot_index": slots}
+
+    def item_ranks(self, encoder_input: dict, items):
+        """item_ranks_tensor for one sequence with one ranked slot, as Python values: a list with one {"item", "rank", "of", "score"}
+        per id of `items` (rank None for an id the slot cannot be served or the vocabulary does not hold)."""
+        got = self.item_ranks_tensor(encoder_input, torch.as_tensor(list(items), dtype=torch.int64).reshape(-1))
+        if got["ranks"].shape[0] != 1:
+            raise ValueError(f"item_ranks serves one ranked slot, the input has {got['ranks'].shape[0]}; use item_ranks_tensor")
+        ranks, scores, n = got["ranks"][0].cpu().tolist(), got["scores"][0].cpu().tolist(), int(got["n"][0])
+        return [{"item": int(i), "rank": r if r > 0 else None, "of": n, "score": s} for i, r, s in zip(items, ranks, scores)]
+
     def list_metrics_tensor(self, ids: torch.Tensor, ground_truth: Optional[torch.Tensor] = None,
                             item_weight: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """Beyond-accuracy metrics of recommendation lists ids [R, K] int64 (recommend_tensor's ids, re-ranked or not; -1 entries are

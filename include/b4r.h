@@ -718,6 +718,54 @@ int b4r_group_mass(const float* hidden, int32_t hidden_ld, const int64_t* hidden
                    int32_t n_filters, const int32_t* row_filter, const float* item_scale, float inv_temperature, const double* row_lse,
                    const int32_t* item_group, int32_t G, int64_t* group_mass, int32_t* group_n, int64_t* rest_mass, int32_t* rest_n,
                    b4r_stream_t stream);
+/* Item ranks: where Q given items stand for each row among the items it could be served, from one sweep over the catalogue (not Q
+ * of them, and no [R, V] buffer).  The first 11 arguments and allow_bits / n_filters / row_filter / item_scale are b4r_rank_full_ex's,
+ * and so is s(r, j) bit for bit (bias may be NULL); there is no gt.  With q = query_ids[r][i] (query_ids [R, Q] int64):
+ *   valid(q)          q in [first_item, V); padding such as -1, V or +-2^40 is not valid.
+ *   A(r)              { j in [first_item, V): the row's filter bit is set (or the row has no filter), j not in exclude[r] }
+ *   A'(r)             A(r) for B4R_RANKS_STRICT and B4R_RANKS_SELF; A(r) + { the valid queries of row r } for B4R_RANKS_JOINT: all
+ *                     targets of a row are ranked in one list, each as b4r_rank_full keeps gt rankable.
+ *   member[r][i]      uint8: 1 iff valid(q) and q in A(r), else 0.
+ *   query_scores[r][i]  float: s(r, q) for a valid q whatever its membership, else -inf.
+ *   ranks[r][i]       int32: 0 for an invalid q, 0 under STRICT when member = 0, otherwise 1 + #{ j in A'(r), j != q: j stands before
+ *                     q } in b4r_rank_full's order for gt_rank (score descending through the same integer image, -0.0 equal to +0.0,
+ *                     ties to the lower id).  SELF is gt_rank of b4r_rank_full_ex(gt = that column, K = 0) in every bit.  A repeated
+ *                     query id gets the same rank at each occurrence.
+ *   row_n[r]          int32: |A'(r)|.  A row without an allowed item gives 0 and, under STRICT, rank 0 in every column.
+ *   dead row          hidden_row[r] < 0: no query is valid, row_n = 0.
+ * Any output may be NULL.  Q in [0, 256], H as in b4r_rank_full (else B4R_E_SHAPE); a members value outside the enum, hidden or table
+ * NULL, query_ids NULL with Q > 0, exclude NULL with E > 0: B4R_E_BADARG.  scratch: b4r_item_ranks_scratch_bytes(R, V, Q) bytes serve
+ * all rows in one pass (17 Q + 4 bytes per row); a smaller one works in groups of 16 rows, and one too small for a group returns
+ * B4R_E_NOMEM.  Every check happens before any launch.  Only enqueues (three launches per group: the queries' keys in descending
+ * order, the sweep, the prefix sums; one stream, no host sync, graph-capturable).  The sweep is b4r_rank_full's tile of 16 rows x 1024
+ * ids per 256-thread workgroup: each allowed (row, id) finds its bucket among the row's sorted query keys and adds 1 to a histogram of
+ * Q + 1 buckets in LDS; non-zero buckets leave with global integer atomics.  Integer counting only: bitwise reproducible whatever the
+ * order, the chunking or the grouping.  Non-finite hidden values are outside the contract (they are never read out of bounds). */
+enum { B4R_RANKS_STRICT = 0, B4R_RANKS_SELF = 1, B4R_RANKS_JOINT = 2 };
+int64_t b4r_item_ranks_scratch_bytes(int32_t R, int32_t V, int32_t Q);
+int b4r_item_ranks(const float* hidden, int32_t hidden_ld, const int64_t* hidden_row, const float* table, const float* bias, int32_t H,
+                   int32_t V, int32_t first_item, int32_t R, const int64_t* exclude, int32_t E, const uint32_t* allow_bits,
+                   int32_t n_filters, const int32_t* row_filter, const float* item_scale, const int64_t* query_ids, int32_t Q,
+                   int32_t members, int32_t* ranks, float* query_scores, int32_t* row_n, uint8_t* member, void* scratch,
+                   int64_t scratch_bytes, b4r_stream_t stream);
+/* The multi-target twin of b4r_rank_metrics below, with the same device accumulators: ranks [R, Q] int32 (b4r_item_ranks'), row_n [R]
+ * int32 (its row_n; may be NULL unless an AUC family is asked for, else B4R_E_BADARG).  Row r has the targets rho_1 .. rho_n, its
+ * entries > 0, expected pairwise distinct (B4R_RANKS_JOINT ranks of distinct ids are; nothing checks it).  Rows with n = 0 are
+ * skipped; every other row adds 1 to users[0] and gain_m(row) to gain_sums[m].  family[m] with the cut-off k = cutoff[m]:
+ *   B4R_MGAIN_COUNT   n
+ *   B4R_MGAIN_HIT     [min rho <= k]
+ *   B4R_MGAIN_NDCG    sum_{rho_i <= k} 1 / log2(rho_i + 1)  /  sum_{i = 1 .. min(n, k)} 1 / log2(i + 1)
+ *   B4R_MGAIN_MRR     1 / min rho
+ *   B4R_MGAIN_RECALL  #{rho_i <= k} / n
+ *   B4R_MGAIN_MAP     (1 / min(n, k)) sum_{rho_i <= k} #{j: rho_j <= rho_i} / rho_i
+ *   B4R_MGAIN_AUC     the mean over i of 1 - (rho_i - 1 - #{j: rho_j < rho_i}) / (row_n - n), and 1 when row_n <= n
+ * A cut-off below 1 gives 0 for HIT / NDCG / RECALL / MAP.  With n = 1, COUNT / HIT / NDCG / MRR (the same numbers 0 .. 3) are
+ * b4r_rank_metrics' families, and MAP@k is the reciprocal rank inside the cut-off.  R >= 1, Q in [1, 256], 1 .. 32 metrics (else
+ * B4R_E_SHAPE).  One workgroup, fixed summation order: bitwise reproducible. */
+enum { B4R_MGAIN_COUNT = 0, B4R_MGAIN_HIT = 1, B4R_MGAIN_NDCG = 2, B4R_MGAIN_MRR = 3, B4R_MGAIN_RECALL = 4, B4R_MGAIN_MAP = 5,
+       B4R_MGAIN_AUC = 6 };
+int b4r_rank_metrics_multi(const int32_t* ranks, const int32_t* row_n, int32_t R, int32_t Q, const int32_t* family,
+                           const int32_t* cutoff, int32_t n_metrics, double* gain_sums, int64_t* users, b4r_stream_t stream);
 /* replaces the metric loop of bert4rec_evaluator.py:118-120 over evaluation_metrics.py:47-112 for a batch of ranks:
  * gain_sums[m] += sum over gt_rank[i] > 0 of gain_m(gt_rank[i]), users[0] += #{gt_rank[i] > 0}; double / int64 DEVICE
  * accumulators the caller reads once per evaluate().  family[m]: 0 count (gain 1), 1 hit@cutoff (rank <= k), 2 NDCG@cutoff
