@@ -225,6 +225,20 @@ class Recommender:
         window, "affinity" = the user's probability of picking from each category next (category_affinity's).  calibration: the
         weight of the category mix against the relevance, a number in [0, 1] (default 0.5; 0 = the k best items).  It does not
         combine with diversity, max_per_group or sample_seed."""
+        sequences = [list(seq) for seq in sequences]
+        serve = self._recommend_options(len(sequences), k, allowed_items, allowed_items_per_user, diversity, candidate_pool, max_per_group,
+                                        return_probabilities, min_probability, temperature, sample_seed, user_streams, calibrate_by,
+                                        calibrate_to, calibration)
+        if not sequences:
+            return []
+        batch, exclude = self._requests(sequences)
+        return self._recommend_requests(batch, exclude, len(sequences), serve)
+
+    def _recommend_options(self, n: int, k, allowed_items, allowed_items_per_user, diversity, candidate_pool, max_per_group,
+                           return_probabilities, min_probability, temperature, sample_seed, user_streams, calibrate_by, calibrate_to,
+                           calibration) -> dict:
+        """recommend_batch's keywords for n users, checked and made ready for the model (the filters, the quota specs and the labels
+        are packed once per call): what _recommend_requests takes."""
         calibrated = bool(return_probabilities) or min_probability is not None
         sampled = sample_seed is not None
         if calibrate_by is None:
@@ -249,31 +263,36 @@ class Recommender:
                 raise ValueError(f"min_probability must be a number in [0, 1], got {min_probability!r}")
         if not calibrated and not sampled and not (isinstance(temperature, numbers.Real) and temperature == 1.0):
             raise ValueError("temperature scales the probabilities: give return_probabilities, min_probability or sample_seed as well")
-        tokenizer = self.dataloader.get_tokenizer()
-        sequences = [list(seq) for seq in sequences]
-        allow, user_filter = self._allow_filters(len(sequences), allowed_items, allowed_items_per_user)
+        allow, user_filter = self._allow_filters(n, allowed_items, allowed_items_per_user)
         quotas = None if max_per_group is None else self._item_groups(max_per_group)   # packed once per call
         calibrate = None
         if calibrate_by is not None:
             labels, G, _ = self._affinity_labels(calibrate_by)
             calibrate = (labels, G, calibrate_to)
-        if not sequences:
-            return []
-        batch, exclude = self._requests(sequences)
+        return dict(k=k, allow=allow, user_filter=user_filter, user_streams=user_streams, min_probability=min_probability,
+                    return_probabilities=return_probabilities,
+                    model=dict(diversity=diversity, pool=candidate_pool, max_per_group=quotas, return_distribution=calibrated,
+                               temperature=temperature, sample_seed=sample_seed, calibrate=calibrate,
+                               calibration=None if calibrate is None else (0.5 if calibration is None else calibration)))
+
+    def _recommend_requests(self, batch, exclude, n: int, serve: dict) -> list:
+        """The n users' lists from their requests (batch, exclude: _requests' pair, on the host or on the device) under the options
+        `serve` (_recommend_options): one recommend_tensor call, one read-back of the lists, the ids back to items."""
+        k, user_filter, user_streams = serve["k"], serve["user_filter"], serve["user_streams"]
+        min_probability, return_probabilities = serve["min_probability"], serve["return_probabilities"]
+        calibrated = serve["model"]["return_distribution"]
+        tokenizer = self.dataloader.get_tokenizer()
         # one filter index and one stream per ranked slot: the slots of recommend_tensor are those with masked_lm_weights != 0, in
         # batch order
-        slot_user = torch.nonzero(batch["masked_lm_weights"] != 0, as_tuple=True)[0]
-        row_filter = None if user_filter is None else user_filter[slot_user]
-        slot_streams = None
-        if user_streams is not None:
-            if user_streams.numel() != len(sequences):
-                raise ValueError(f"{user_streams.numel()} user streams for {len(sequences)} sequences")
-            slot_streams = user_streams[slot_user]
-        got = self.model.recommend_tensor(batch, k=k, exclude_seen=False, exclude=exclude, allow=allow, row_filter=row_filter,
-                                          diversity=diversity, pool=candidate_pool, max_per_group=quotas,
-                                          return_distribution=calibrated, temperature=temperature, sample_seed=sample_seed,
-                                          sample_streams=slot_streams, calibrate=calibrate,
-                                          calibration=None if calibrate is None else (0.5 if calibration is None else calibration))
+        row_filter = slot_streams = None
+        if user_streams is not None and user_streams.numel() != n:
+            raise ValueError(f"{user_streams.numel()} user streams for {n} sequences")
+        if user_filter is not None or user_streams is not None:
+            slot_user = torch.nonzero(batch["masked_lm_weights"] != 0, as_tuple=True)[0].cpu()
+            row_filter = None if user_filter is None else user_filter[slot_user]
+            slot_streams = None if user_streams is None else user_streams[slot_user]
+        got = self.model.recommend_tensor(batch, k=k, exclude_seen=False, exclude=exclude, allow=serve["allow"], row_filter=row_filter,
+                                          sample_streams=slot_streams, **serve["model"])
         ids, slots = got[0], got[2]
         P = int(batch["masked_lm_positions"].shape[1])
         first = {}
@@ -288,7 +307,7 @@ class Recommender:
             ids_h = ids.cpu().tolist()
         least = 0.0 if min_probability is None else float(min_probability)
         out = []
-        for b in range(len(sequences)):
+        for b in range(n):
             top = [i for i in ids_h[first[b]] if i >= 0] if b in first else []
             if prob_h is not None:
                 kept = [(i, p) for i, p in zip(ids_h[first[b]], prob_h[first[b]]) if i >= 0 and p >= least] if b in first else []
@@ -298,6 +317,14 @@ class Recommender:
                 items = [(item, p) for item, (_, p) in zip(items, kept)]
             out.append((items[0] if items else None) if k == 1 else items)   # None: nothing is left to recommend (filtered or not)
         return out
+
+    def open_sessions(self, max_users: int, history_capacity=None):
+        """A SessionStore (apps/session_store.py) for max_users users: their histories stay on the device, `append` adds events and
+        `recommend(user_keys)` serves recommend_batch's lists without preparing the histories on the host.  history_capacity: the
+        items kept per user (default max(max_seq_len - 1, 256); below max_seq_len - 1 raises ValueError) -- a user's exclusions are
+        their last history_capacity items, the full history as long as it is no longer than that."""
+        from .session_store import SessionStore
+        return SessionStore(self, max_users, history_capacity)
 
     def item_ranks(self, sequences, items=None, items_per_user=None, allowed_items=None, allowed_items_per_user=None) -> list:
         """Where given items stand for every user: "X is at 312 of 26 000 for this user" -- the position the item has in

@@ -314,6 +314,62 @@ def check_rollout_batch(input_mask: torch.Tensor, positions: torch.Tensor, weigh
     return length, slot
 
 
+HISTORY_MAX_EVENTS = 65536     # b4r_history_append: N
+HISTORY_MAX_CAPACITY = 4096    # b4r_history_append / b4r_history_batch: C
+HISTORY_MAX_LEN = 256          # b4r_history_batch: L
+HISTORY_MAX_CELLS = 1 << 40    # U * C
+
+
+def check_history_state_args(max_users, capacity) -> Tuple[int, int]:
+    """Argument checks of a session store that need no GPU: max_users >= 1 rows of capacity in [1, 4096] items, fewer than 2^40 cells.
+    Returns (max_users, capacity)."""
+    capacity = _int_in(capacity, 1, HISTORY_MAX_CAPACITY, "capacity")
+    max_users = _int_in(max_users, 1, (HISTORY_MAX_CELLS - 1) // capacity, "max_users")
+    return max_users, capacity
+
+
+def check_history_state(state) -> Tuple[int, int]:
+    """A session store's state (Engine.history_state): hist [U, C] int64 and count [U] int64, contiguous, on one device.  Returns
+    (U, C)."""
+    try:
+        hist, count = state["hist"], state["count"]
+    except (KeyError, TypeError):
+        raise ValueError("a history state is a dict with 'hist' [U, C] and 'count' [U] (Engine.history_state)") from None
+    for name, t, nd in (("hist", hist, 2), ("count", count, 1)):
+        if not torch.is_tensor(t) or t.dtype != torch.int64 or t.ndim != nd or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"history state '{name}' must be a contiguous int64 tensor of rank {nd} on the device")
+    if hist.device != count.device or hist.shape[0] != count.shape[0]:
+        raise ValueError(f"history state: hist {tuple(hist.shape)} on {hist.device} and count {tuple(count.shape)} on {count.device} disagree")
+    return check_history_state_args(int(hist.shape[0]), int(hist.shape[1]))
+
+
+def check_history_events(users, items, accepted=None) -> int:
+    """The events of one b4r_history_append call: users int32 [N] and items int64 [N] on the device, in arrival order, at most 65 536
+    of them; accepted (optional) int32 [N].  Returns N."""
+    for name, t, dt in (("users", users, torch.int32), ("items", items, torch.int64), ("accepted", accepted, torch.int32)):
+        if t is None and name == "accepted":
+            continue
+        if not torch.is_tensor(t) or t.dtype != dt or t.ndim != 1 or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"history events: {name} must be a contiguous {dt} tensor [N] on the device")
+    N = int(users.numel())
+    if items.numel() != N or (accepted is not None and accepted.numel() != N):
+        raise ValueError(f"history events: {N} users, {items.numel()} items" + ("" if accepted is None else f", {accepted.numel()} accepted flags"))
+    if N > HISTORY_MAX_EVENTS:
+        raise ValueError(f"history events: at most {HISTORY_MAX_EVENTS} per call, got {N}")
+    return N
+
+
+def check_history_batch_args(users, L, P, E, capacity: int) -> Tuple[int, int, int, int]:
+    """The requests of one b4r_history_batch call: users int32 [R] on the device; rows of L in [2, 256] tokens, P >= 1 prediction
+    slots, E >= 1 exclusion columns (default: the capacity).  Returns (R, L, P, E)."""
+    if not torch.is_tensor(users) or users.dtype != torch.int32 or users.ndim != 1 or not users.is_contiguous() or not users.is_cuda:
+        raise ValueError("history requests: users must be a contiguous torch.int32 tensor [R] on the device")
+    L = _int_in(L, 2, HISTORY_MAX_LEN, "L")
+    P = _int_in(P, 1, (1 << 31) - 1, "P")
+    E = capacity if E is None else _int_in(E, 1, (1 << 31) - 1, "E")
+    return int(users.numel()), L, P, E
+
+
 EXPLAIN_MAX_UNITS = 256    # b4r_attribution_select: W
 
 
@@ -1458,6 +1514,46 @@ class Engine:
             int(mask_id), int(step), int(ex_col), _ptr(dst["tokens"]), _ptr(dst["mask"]), _ptr(dst["len"]), _ptr(dst["positions"]),
             _ptr(dst["exclude"]), _ptr(dst.get("path")), _ptr(dst["path_logp"]) if want_logp else None, _stream(self.device)),
             "b4r_rollout_advance")
+
+    def history_state(self, max_users: int, capacity: int) -> Dict[str, torch.Tensor]:
+        """The state of a session store: hist [max_users, capacity] int64 (uninitialised: the counts say what is held) and count
+        [max_users] int64 = 0 on the device.  The n-th accepted event of user u lives at hist[u][n mod capacity]."""
+        U, C = check_history_state_args(max_users, capacity)
+        return {"hist": torch.empty((U, C), dtype=torch.int64, device=self.device),
+                "count": torch.zeros((U,), dtype=torch.int64, device=self.device)}
+
+    def history_append(self, state: Dict[str, torch.Tensor], users: torch.Tensor, items: torch.Tensor,
+                       accepted: Optional[torch.Tensor] = None, first_item: int = SPECIAL_IDS) -> None:
+        """b4r_history_append: the events (users int32 [N], items int64 [N], in arrival order) go into `state` as if they were applied
+        one at a time; an event whose user lies outside [0, max_users) or whose item outside [first_item, vocab_size) is dropped.
+        accepted (optional) int32 [N] receives 1 / 0 per event.  Only enqueues: no host synchronisation."""
+        U, C = check_history_state(state)
+        N = check_history_events(users, items, accepted)
+        if N == 0:
+            return
+        sc = self._scratch("b4r_history_append", int(self.lib.b4r_history_append_scratch_bytes(N)))
+        _lib.check(self.lib.b4r_history_append(_ptr(state["hist"]), _ptr(state["count"]), U, C, self.cfg.vocab_size, int(first_item),
+                                               _ptr(users), _ptr(items), N, _ptr(accepted), _ptr(sc), sc.numel(), _stream(self.device)),
+                   "b4r_history_append")
+
+    def history_batch(self, state: Dict[str, torch.Tensor], users: torch.Tensor, L: int, P: int, E: Optional[int] = None,
+                      mask_id: int = MASK_ID) -> Dict[str, torch.Tensor]:
+        """b4r_history_batch: the batch rows of the users int32 [R] out of `state`, as prepare_inference of their most recent L - 1
+        items.  Returns the buffer set in rollout_state's naming -- tokens / mask [R, L] int64, len [R] int32, positions [R, P] int64,
+        exclude [R, E] int64 (the user's most recent min(capacity, E) items, -1 padded; E defaults to the capacity) -- plus weights
+        [R, P] int64 and live [R] int32 (0: a user outside the store, served as a cold user)."""
+        U, C = check_history_state(state)
+        R, L, P, E = check_history_batch_args(users, L, P, E, C)
+        dev = self.device
+        out = {"tokens": torch.empty((R, L), dtype=torch.int64, device=dev), "mask": torch.empty((R, L), dtype=torch.int64, device=dev),
+               "len": torch.empty((R,), dtype=torch.int32, device=dev), "positions": torch.empty((R, P), dtype=torch.int64, device=dev),
+               "weights": torch.empty((R, P), dtype=torch.int64, device=dev), "exclude": torch.empty((R, E), dtype=torch.int64, device=dev),
+               "live": torch.empty((R,), dtype=torch.int32, device=dev)}
+        _lib.check(self.lib.b4r_history_batch(_ptr(state["hist"]), _ptr(state["count"]), U, C, _ptr(users), R, L, P, E, int(mask_id),
+                                              _ptr(out["tokens"]), _ptr(out["mask"]), _ptr(out["len"]), _ptr(out["positions"]),
+                                              _ptr(out["weights"]), _ptr(out["exclude"]), _ptr(out["live"]), _stream(self.device)),
+                   "b4r_history_batch")
+        return out
 
     def explain_state(self, n_rows: int, L: int, P: int) -> Dict[str, torch.Tensor]:
         """One buffer set of occluded rows (b4r_occlude_rows writes all of it): tokens / mask [N, L] int64, len [N] int32, positions

@@ -616,6 +616,49 @@ int b4r_occlude_rows(const int64_t* tokens_in, const int32_t* len_in, const int3
  * probabilities are outside the contract (inf - inf); nothing is read or written out of bounds. */
 int b4r_attribution_select(const float* base_logp, const float* occ_logp, const int32_t* live, int32_t U, int32_t W, int32_t K, int32_t m,
                            int32_t* out_w, float* out_delta, b4r_stream_t stream);
+/* Session store: user histories that stay on the device between calls, so that an event appends one item to one user's history and
+ * a request names users instead of sending their histories.  The state is two plain device buffers the caller owns:
+ *   hist [U, C] int64, count [U] int64.  Row u is one user; count[u] is the number of events accepted for the user so far, and the
+ *   n-th accepted event (0-based, over the user's life) lives at hist[u][n mod C]: a ring of capacity C, an append never moves old
+ *   data.  A zeroed count is an empty store; hist needs no initialisation.
+ * Both calls only enqueue (one stream, no host sync, graph-capturable), use no atomics and are bitwise reproducible; every argument
+ * is checked before the first launch, and nothing is read or written out of bounds whatever the user ids, the items and the counts
+ * are (a negative count is outside the contract).
+ *
+ * b4r_history_append: N events in arrival order, ev_user [N] int32 / ev_item [N] int64.  Event n is accepted when 0 <= ev_user[n] <
+ * U and first_item <= ev_item[n] < V; any other event is dropped and changes nothing.  accepted_out [N] int32 (may be NULL): 1 or 0.
+ * For an accepted event of user u, before(n) / after(n) = the number of accepted events m < n / m > n of the same user:
+ *   hist[u][(count_old[u] + before(n)) mod C] = ev_item[n]  when after(n) < C (an event that the same call overwrites anyway does not
+ *                                                           write, so every cell is written at most once per call)
+ *   count[u] = count_old[u] + before(n) + 1                 by the event with after(n) == 0
+ * which is the result of applying the events one at a time in order.  Two launches: the first reads count and writes the plan of
+ * every event (its cell, the count it leaves) to the scratch, the second reads the plan and writes hist and count, so that no thread
+ * reads a cell another thread of the same launch may write.  The counts before / after: a workgroup owns 256 events and streams the
+ * whole event list through LDS in tiles of 256 (N^2 integer compares in all; meant for hundreds to thousands of events per call).
+ * 0 <= N <= 65536, 1 <= C <= 4096, U >= 1, U * C < 2^40 (else B4R_E_SHAPE); hist, count, ev_user, ev_item or scratch NULL, a scratch
+ * that is not 8-byte aligned, or accepted_out overlapping the events: B4R_E_BADARG; scratch_bytes below
+ * b4r_history_append_scratch_bytes(N) (16 bytes per event; -1 for an N outside the limits): B4R_E_NOMEM.  N = 0 succeeds and launches
+ * nothing.
+ *
+ * b4r_history_batch: R requests req_user [R] int32 -> the batch rows of those users.  Row r with u = req_user[r] in [0, U) is live;
+ * the same user may be requested several times.  With n = count[u] and h = min(n, L - 1, C):
+ *   tokens_out [R, L] int64: the h most recent items, oldest first (event n - h + i from hist[u][(n - h + i) mod C]), then mask_id,
+ *                            the rest 0;  len_out [R] int32 = h + 1;  input_mask_out [R, L] int64: p < len
+ *   positions_out [R, P] int64 = [len - 1, 0, ...];  weights_out [R, P] int64 = [1, 0, ...]
+ *   exclude_out [R, E] int64: the min(n, C, E) most recent items, oldest first, then -1
+ * which is the reference's prepare_inference of the user's items, in b4r_rollout_advance's conventions.  A dead row (user out of
+ * range) and a user without events both give the lone placeholder [mask_id, 0, ...], len = 1, exclusions all -1: still a valid
+ * sequence for the forward; live_out [R] int32 (may be NULL) tells the two apart.
+ * 2 <= L <= 256, P >= 1, E >= 1, R >= 0, C and U as above (else B4R_E_SHAPE); a NULL pointer other than live_out: B4R_E_BADARG.
+ * R = 0 succeeds and launches nothing.  One workgroup of 256 threads per row, one launch; the ring is read as two contiguous
+ * segments. */
+int64_t b4r_history_append_scratch_bytes(int32_t N);
+int b4r_history_append(int64_t* hist, int64_t* count, int64_t U, int32_t C, int32_t V, int32_t first_item, const int32_t* ev_user,
+                       const int64_t* ev_item, int32_t N, int32_t* accepted_out, void* scratch, int64_t scratch_bytes,
+                       b4r_stream_t stream);
+int b4r_history_batch(const int64_t* hist, const int64_t* count, int64_t U, int32_t C, const int32_t* req_user, int32_t R, int32_t L,
+                      int32_t P, int32_t E, int64_t mask_id, int64_t* tokens_out, int64_t* input_mask_out, int32_t* len_out,
+                      int64_t* positions_out, int64_t* weights_out, int64_t* exclude_out, int32_t* live_out, b4r_stream_t stream);
 /* Audience selection: given an item, which users?  b4r_audience_merge is the step ACROSS users: it merges one batch of users into
  * the K most likely users of each of Q items, which stay on the device while the batches of users go by (O(Q * K) state, no
  * [users, items] matrix), and counts reach and expected demand.  It only enqueues (one launch, one stream, no host sync,
