@@ -216,6 +216,8 @@ PROTOTYPES = {
     "b4r_history_append_scratch_bytes": (_I64, [_I32]),
     "b4r_history_append": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _I64, _P]),
     "b4r_history_batch": (C.c_int, [_P, _P, _I64, _I32, _P, _I32, _I32, _I32, _I32, _I64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "b4r_allocate_scratch_bytes": (_I64, [_I32, _I32, _I32, _I32]),
+    "b4r_allocate": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "b4r_audience_merge": (C.c_int, [_P, _I32, _I32, _I32, _P, _I64, _F, _I32, _P, _P, _P, _P, _P]),
     "b4r_rank_joint_scratch_bytes": (_I64, [_I32, _I32, _I32, _I32]),
     "b4r_rank_joint": (C.c_int, [_P, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _P, _F, _P, _P, _I32, _I32, _P, _I32,

@@ -39,7 +39,11 @@ recommend_shelves returns the categories a user is most likely to pick from, eac
 
 calibrate_by / calibrate_to / calibration give every user a list with their own category mix: the sweep returns candidate_pool
 candidates per user and b4r_rerank_calibrated picks k of them so that the list's category shares follow the shares of the user's
-history, or the user's category affinity."""
+history, or the user's category affinity.
+
+allocate shares limited items out among the users of one call (a stock of coupons, listings that exist once, seats): no item is handed
+out more often than its stock, a contended item goes to the users most likely to take it, and whoever loses it gets the next item of
+their own pool (b4r_allocate over the users' candidate pools, which stay on the device)."""
 import numbers
 
 import numpy as np
@@ -317,6 +321,76 @@ class Recommender:
                 items = [(item, p) for item, (_, p) in zip(items, kept)]
             out.append((items[0] if items else None) if k == 1 else items)   # None: nothing is left to recommend (filtered or not)
         return out
+
+    def allocate(self, sequences, stock, k: int = 10, candidate_pool=None, allowed_items=None, user_ids=None,
+                 return_probabilities: bool = True):
+        """recommend_batch when some items are limited: `stock` maps each limited item to the units on offer (500 coupons, a listing
+        that exists once, the seats of an event, "this campaign reaches at most c users"); an item it does not name is unlimited, an
+        item the vocabulary does not know is ignored.  Every user gets at most k items and no item is handed out more often than its
+        stock, over all users of the call: a contended item goes to the users most likely to take it, and a user who loses it gets
+        the next item of their own candidate_pool best (default min(1024, max(10 k, 50))) instead -- a user whose pool yields fewer
+        than k under the stock gets a shorter list, and a larger candidate_pool is the remedy.  The utilities are the items'
+        probabilities under each user's catalogue softmax (the seen items and allowed_items applied), which is what makes different
+        users comparable; ties go to the lower entry of user_ids (one integer per sequence; None: the position in the batch).
+        Returns (lists, remaining): one list per user of (item, probability) pairs -- of items with return_probabilities=False --
+        in the user's own order of preference, and {item: units left} for the items of `stock` the vocabulary knows.  Passing
+        `remaining` as the stock of the next call serves the stock first come, first served: the result then depends on how the users
+        are cut into calls.  One batched call (model.allocate_tensor); the pools are never read back, only the lists are."""
+        sequences = [list(seq) for seq in sequences]
+        serve = self._allocate_options(len(sequences), stock, k, candidate_pool, allowed_items, user_ids, return_probabilities)
+        if not sequences:
+            return [], dict(serve["left"])
+        batch, exclude = self._requests(sequences)
+        return self._allocate_requests(batch, exclude, len(sequences), serve)
+
+    def _allocate_options(self, n: int, stock, k, candidate_pool, allowed_items, user_ids, return_probabilities) -> dict:
+        """allocate's keywords for n users, checked and made ready for the model: what _allocate_requests takes.  left: the stock
+        of the known items as given, which is what remains when there is nobody to serve."""
+        if not hasattr(stock, "items"):
+            raise ValueError("stock maps each limited item to its units: a mapping")
+        k, pool, _ = engine_mod.check_rerank_args(k, candidate_pool, 0.0)
+        engine_mod.check_allocate_args(k, n, pool)
+        uid = engine_mod.check_allocate_user_ids(user_ids, n)
+        names = list(stock)
+        tokens = self._token_ids(names).tolist()
+        by_token = {}
+        for name, t in zip(names, tokens):
+            if t >= 0:
+                by_token[t] = stock[name]
+        capacity = engine_mod.stock_capacity(by_token, self.model.vocab_size)
+        known = [(name, t) for name, t in zip(names, tokens) if t >= 0]
+        left = {name: int(capacity[t]) for name, t in known}
+        allow, _ = self._allow_filters(n, allowed_items, None)
+        return dict(k=k, pool=pool, capacity=capacity, allow=allow, user_ids=uid, known=known, left=left,
+                    return_probabilities=bool(return_probabilities))
+
+    def _allocate_requests(self, batch, exclude, n: int, serve: dict):
+        """The n users' lists and the remaining stock from their requests (batch, exclude: _requests' pair, on the host or on the
+        device): one allocate_tensor call, one read-back of the lists and of the stock."""
+        k = serve["k"]
+        slot_uid = None
+        if serve["user_ids"] is not None:           # one id per ranked slot, as in _recommend_requests
+            slot_uid = serve["user_ids"][torch.nonzero(batch["masked_lm_weights"] != 0, as_tuple=True)[0].cpu()]
+        ids, util, slots, info = self.model.allocate_tensor(batch, serve["capacity"], k=k, pool=serve["pool"], calibrated=True, user_ids=slot_uid,
+                                                            exclude_seen=False, exclude=exclude, allow=serve["allow"])
+        P = int(batch["masked_lm_positions"].shape[1])
+        first = {}
+        for i, s in enumerate(slots.cpu().tolist()):
+            first.setdefault(s // P, i)
+        # ids, probabilities and the stock in one copy: an id and a count are exact in float64
+        both = torch.cat([ids.to(torch.float64).reshape(-1), torch.exp(util.to(torch.float64)).reshape(-1),
+                          info["remaining"].to(torch.float64)]).cpu()
+        nk = ids.numel()
+        ids_h = both[:nk].to(torch.int64).reshape(ids.shape).tolist()
+        prob_h = both[nk:2 * nk].reshape(ids.shape).tolist()
+        rem_h = both[2 * nk:].to(torch.int64).tolist()
+        tokenizer = self.dataloader.get_tokenizer()
+        out = []
+        for b in range(n):
+            kept = [(i, p) for i, p in zip(ids_h[first[b]], prob_h[first[b]]) if i >= 0] if b in first else []
+            items = tokenizer.detokenize([i for i, _ in kept])
+            out.append([(item, p) for item, (_, p) in zip(items, kept)] if serve["return_probabilities"] else items)
+        return out, {name: rem_h[t] for name, t in serve["known"]}
 
     def open_sessions(self, max_users: int, history_capacity=None):
         """A SessionStore (apps/session_store.py) for max_users users: their histories stay on the device, `append` adds events and

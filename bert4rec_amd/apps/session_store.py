@@ -158,6 +158,19 @@ class SessionStore:
         batch, exclude = self.requests(user_keys)
         return rec._recommend_requests(batch, exclude, len(user_keys), serve)
 
+    def allocate(self, user_keys, stock, k: int = 10, candidate_pool=None, allowed_items=None, user_ids=None,
+                 return_probabilities: bool = True):
+        """Recommender.allocate for the users' stored histories: limited items (`stock`: item -> units) are shared out among the
+        users of the call; every keyword means what it means there and the values returned are the same, as long as no history is
+        longer than history_capacity (see the module's docstring)."""
+        user_keys = list(user_keys)
+        rec = self.recommender
+        serve = rec._allocate_options(len(user_keys), stock, k, candidate_pool, allowed_items, user_ids, return_probabilities)
+        if not user_keys:
+            return [], dict(serve["left"])
+        batch, exclude = self.requests(user_keys)
+        return rec._allocate_requests(batch, exclude, len(user_keys), serve)
+
     # ---- persistence ----------------------------------------------------------------------------------------------------------------
     def state_dict(self) -> dict:
         """CPU tensors plus the key list, so that a store survives a restart: hist / count of the rows handed out so far, keys[i] /

@@ -370,6 +370,62 @@ def check_history_batch_args(users, L, P, E, capacity: int) -> Tuple[int, int, i
     return int(users.numel()), L, P, E
 
 
+ALLOCATE_MAX_SLOTS = 1 << 20   # b4r_allocate: R * K (and R)
+ALLOCATE_UNLIMITED = (1 << 31) - 1   # the capacity of an item that is not limited
+
+
+def check_allocate_args(k, n_rows: int, pool_width: int, max_rounds=None, chunk=32) -> Tuple[int, Optional[int], int]:
+    """Argument checks of an allocation that need no GPU: k in [0, pool_width] items per row, n_rows * k <= 2^20, max_rounds None
+    (run until the state has settled, `chunk` >= 1 rounds per read-back) or an integer >= 1.  Returns (k, max_rounds, chunk)."""
+    k = _int_in(k, 0, RANK_FULL_MAX_K, "k")
+    if k > pool_width:
+        raise ValueError(f"k = {k} items cannot be allocated from a pool of {pool_width}")
+    if n_rows > ALLOCATE_MAX_SLOTS or n_rows * k > ALLOCATE_MAX_SLOTS:
+        raise ValueError(f"an allocation holds at most 2^20 rows and 2^20 (row, item) places, got {n_rows} rows of k = {k}")
+    if max_rounds is not None:
+        max_rounds = _int_in(max_rounds, 1, (1 << 31) - 1, "max_rounds")
+    return k, max_rounds, _int_in(chunk, 1, 1 << 16, "chunk")
+
+
+def check_capacity(capacity, vocab_size: int) -> torch.Tensor:
+    """capacity of an allocation: one integer per token id [V] (the units on offer; <= 0: none).  Returns it as an int32 tensor, on
+    whatever device it lives; values past the int32 range raise."""
+    cap = torch.as_tensor(capacity)
+    if cap.ndim != 1 or cap.shape[0] != vocab_size or cap.dtype.is_floating_point or cap.dtype == torch.bool:
+        raise ValueError(f"capacity must be an integer tensor [{vocab_size}], got {cap.dtype} of shape {tuple(cap.shape)}")
+    if cap.dtype != torch.int32:
+        if cap.numel() and (int(cap.max()) > ALLOCATE_UNLIMITED or int(cap.min()) < -ALLOCATE_UNLIMITED - 1):
+            raise ValueError("capacity holds values outside the int32 range")
+        cap = cap.to(torch.int32)
+    return cap
+
+
+def check_allocate_user_ids(user_ids, n_rows: int) -> Optional[torch.Tensor]:
+    """user_ids of an allocation: None or one integer per row [R] -- the lower id wins a utility tie.  Returns int64 or None."""
+    if user_ids is None:
+        return None
+    u = torch.as_tensor(user_ids)
+    if u.ndim != 1 or u.shape[0] != n_rows or u.dtype.is_floating_point or u.dtype == torch.bool:
+        raise ValueError(f"user_ids must be an integer tensor [{n_rows}], got {u.dtype} of shape {tuple(u.shape)}")
+    return u.to(torch.int64)
+
+
+def stock_capacity(stock_tokens, vocab_size: int) -> torch.Tensor:
+    """{token id: units} -> capacity int32 [V] on the host: the named ids get their units (clamped at 0), every other id is unlimited."""
+    cap = torch.full((vocab_size,), ALLOCATE_UNLIMITED, dtype=torch.int32)
+    for t, units in stock_tokens.items():
+        if isinstance(units, bool):
+            raise ValueError(f"the stock of an item is an integer, got {units!r}")
+        try:
+            units = operator.index(units)
+        except TypeError:
+            raise ValueError(f"the stock of an item is an integer, got {units!r}") from None
+        if units > ALLOCATE_UNLIMITED:
+            raise ValueError(f"the stock of an item is at most {ALLOCATE_UNLIMITED}, got {units}")
+        cap[t] = max(units, 0)
+    return cap
+
+
 EXPLAIN_MAX_UNITS = 256    # b4r_attribution_select: W
 
 
@@ -1554,6 +1610,51 @@ class Engine:
                                               _ptr(out["weights"]), _ptr(out["exclude"]), _ptr(out["live"]), _stream(self.device)),
                    "b4r_history_batch")
         return out
+
+    def allocate(self, pool_ids: torch.Tensor, pool_util: torch.Tensor, k: int, capacity, user_ids=None, max_rounds=None, chunk: int = 32):
+        """b4r_allocate: share limited items out among the rows of one batch.  pool_ids / pool_util [R, M]: every row's candidates as
+        rank_full returns them (best first; the utilities must be comparable across rows); capacity [V] integers: the units of every
+        token id on offer (<= 0: none); user_ids [R] integers or None: the lower id wins a utility tie (None: the row index).  Every
+        live pool entry of every row is walked in one global order -- utility descending, then user id, row, pool position -- and
+        given to its row when the row holds fewer than k items and the item has units left.
+        Returns (ids [R,k] int64, util [R,k] fp32, pos [R,k] int32: each row's items in ascending pool position, -1 / -inf / -1 behind
+        them; row_n [R] int32; remaining [V] int32: the capacity minus what was given; unsettled: one int32 on the device).
+        The device works in rounds of deferred acceptance.  max_rounds=None: rounds are enqueued `chunk` at a time and the 4 bytes of
+        `unsettled` are read after each chunk until they are 0 -- the only synchronisation; the pools never leave the device.
+        max_rounds=n: exactly n rounds are enqueued and nothing is read back (graph-capturable); the lists are then feasible -- no row
+        above k, no item above its capacity -- and final exactly when unsettled is 0.
+        remaining fed in as the capacity of the next call serves the stock first come, first served: the result depends on how the
+        users are cut into calls.  The scratch buffer is kept between calls."""
+        R, M, ids_d, ut_d = self._pool(pool_ids, pool_util)
+        k, max_rounds, chunk = check_allocate_args(k, R, M, max_rounds, chunk)
+        V = self.cfg.vocab_size
+        cap_d = check_capacity(capacity, V).to(self.device).contiguous()
+        uid = check_allocate_user_ids(user_ids, R)
+        uid_d = None if uid is None else uid.to(self.device).contiguous()
+        dev = self.device
+        ids, util, pos = self._picks(R, k, torch.int64, torch.float32, torch.int32)
+        empty = R == 0 or k == 0                  # the call then launches nothing: no row holds anything, nothing is left to settle
+        row_n = (torch.zeros if empty else torch.empty)((R,), dtype=torch.int32, device=dev)
+        unsettled = (torch.zeros if empty else torch.empty)((1,), dtype=torch.int32, device=dev)
+        remaining = torch.empty((V,), dtype=torch.int32, device=dev)
+        sc = self._scratch("b4r_allocate", max(int(self.lib.b4r_allocate_scratch_bytes(R, M, k, V)), 8))
+
+        def call(rounds: int, resume: int) -> None:
+            _lib.check(self.lib.b4r_allocate(_ptr(ids_d), _ptr(ut_d), R, M, k, V, _ptr(cap_d), _ptr(uid_d), rounds, resume, _ptr(ids),
+                                             _ptr(util), _ptr(pos), _ptr(row_n), _ptr(remaining), _ptr(unsettled), _ptr(sc), sc.numel(),
+                                             _stream(self.device)), "b4r_allocate")
+
+        if max_rounds is not None or empty:
+            call(max_rounds or 1, 0)
+            return ids, util, pos, row_n, remaining, unsettled
+        call(chunk, 0)
+        budget = R * M + 1                        # every round but the last rejects an edge for good
+        while int(unsettled.item()) != 0:
+            budget -= chunk
+            if budget < -chunk:
+                raise B4RError("b4r_allocate did not settle within its bound of rounds")
+            call(chunk, 1)
+        return ids, util, pos, row_n, remaining, unsettled
 
     def explain_state(self, n_rows: int, L: int, P: int) -> Dict[str, torch.Tensor]:
         """One buffer set of occluded rows (b4r_occlude_rows writes all of it): tokens / mask [N, L] int64, len [N] int32, positions

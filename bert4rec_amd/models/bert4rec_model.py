@@ -1151,6 +1151,50 @@ class BERT4RecModel:
         cols = [t.cpu().tolist() for t in got]
         return [tuple(col[p] for col in cols) for p in range(len(cols[0]))]
 
+    def allocate_tensor(self, encoder_input: Dict[str, torch.Tensor], capacity, k: int = 10, pool: Optional[int] = None,
+                        calibrated: bool = True, user_ids=None, exclude_seen: bool = True, exclude: Optional[torch.Tensor] = None,
+                        allow=None, row_filter=None, temperature: float = 1.0, max_rounds: Optional[int] = None):
+        """Stock-aware recommendations: at most k items for every ranked slot, with every item handed out at most capacity[item]
+        times over the whole batch (coupons, one-off listings, seats, "this campaign reaches at most c users").  capacity: one
+        integer per token id [V], the units on offer (<= 0: none; engine.ALLOCATE_UNLIMITED = 2^31 - 1 for an item without a limit).
+        One forward (recommend_tensor's: the same slots, exclusions and filter), one b4r_rank_full sweep for the best `pool` allowed
+        items of every slot (default min(1024, max(10 k, 50)), the re-rankers'), then b4r_allocate over the pools on the device.
+        calibrated (default): the utility of a pool entry is its log probability under the slot's catalogue softmax at `temperature`
+        (one b4r_score_dist sweep with the pool ids as the queries), which is what makes the utilities of different users
+        comparable, as in recommend_joint_tensor; calibrated=False uses the raw sweep scores (temperature must be 1).
+        The entries of all slots are walked in one order -- utility descending, then the lower user_ids entry ([R] integers, one per
+        ranked slot; None: the slot's row number 0 .. R-1), the lower row, the lower pool position -- and an entry is given to its
+        slot while the slot holds fewer than k and the item has units left: a contended item goes to the users who want it most, and
+        a user who loses it gets the next item of their own pool instead.
+        Returns (ids [R,k] int64, util [R,k] fp32, slot_index [R] int64 = b*P+p, info), on the device; every slot's items stand in
+        its pool's order (best first), -1 / -inf behind them when the pool, under the stock, yields fewer than k.  info: pos [R,k]
+        int32 (the pool position of every item), row_n [R] int32 (the items the slot got), remaining [V] int32 (capacity minus what
+        was given: the capacity of the next batch, first come, first served -- the result depends on how users are cut into batches),
+        unsettled (one int32: 0 = the lists are final).  max_rounds=None settles the allocation (a 4-byte read-back per 32 rounds);
+        an integer enqueues exactly that many rounds without a synchronisation (Engine.allocate)."""
+        k = engine_mod.check_rank_full_args(k, exclude)
+        k, n_sweep, _ = engine_mod.check_rerank_args(k, pool, 0.0)
+        if not calibrated and not (isinstance(temperature, numbers.Real) and temperature == 1.0):
+            raise ValueError("temperature scales the calibrated utilities: calibrated=False takes temperature 1")
+        engine_mod.check_temperature(temperature)
+        cap = engine_mod.check_capacity(capacity, self.vocab_size)
+        allow, row_filter = engine_mod.check_item_filter(allow, row_filter, self.vocab_size)
+        hidden, slots, _ = self._ranked_slot_hidden(encoder_input)
+        R = int(slots.numel())
+        engine_mod.check_allocate_args(k, R, n_sweep, max_rounds)
+        uid = engine_mod.check_allocate_user_ids(user_ids, R)
+        dev, first = self.device, engine_mod.SPECIAL_IDS
+        if hidden is None:
+            info = {"pos": torch.empty((0, k), dtype=torch.int32, device=dev), "row_n": torch.empty((0,), dtype=torch.int32, device=dev),
+                    "remaining": cap.to(dev), "unsettled": torch.zeros((1,), dtype=torch.int32, device=dev)}
+            return torch.empty((0, k), dtype=torch.int64, device=dev), torch.empty((0, k), dtype=torch.float32, device=dev), slots, info
+        ex_rows = self._excluded_rows(encoder_input, slots, exclude_seen, exclude)
+        pool_ids, pool_util, _ = self.engine.rank_full(hidden, None, ex_rows, first, None, n_sweep, allow, row_filter)
+        if calibrated:
+            pool_util = self.engine.score_distribution(hidden, None, ex_rows, first, None, allow, row_filter, temperature, pool_ids)[4]
+        ids, util, pos, row_n, remaining, unsettled = self.engine.allocate(pool_ids, pool_util, k, cap, uid, max_rounds)
+        return ids, util, slots, {"pos": pos, "row_n": row_n, "remaining": remaining, "unsettled": unsettled}
+
     def _rank_items_ragged(self, encoder_input, items):
         """Candidate lists of different lengths: one kernel call per distinct length."""
         flat = [c for row in items for c in row]

@@ -659,6 +659,58 @@ int b4r_history_append(int64_t* hist, int64_t* count, int64_t U, int32_t C, int3
 int b4r_history_batch(const int64_t* hist, const int64_t* count, int64_t U, int32_t C, const int32_t* req_user, int32_t R, int32_t L,
                       int32_t P, int32_t E, int64_t mask_id, int64_t* tokens_out, int64_t* input_mask_out, int32_t* len_out,
                       int64_t* positions_out, int64_t* weights_out, int64_t* exclude_out, int32_t* live_out, b4r_stream_t stream);
+/* Stock-aware allocation: limited items (coupons, one-off listings, seats, a push budget per campaign) are shared out among the R
+ * users of a batch, so that no item is given more often than its capacity and no user gets more than K items.  This is the one call
+ * whose result for a row depends on the other rows.
+ *   pool_ids [R, M] int64, pool_util [R, M] fp32: every row's candidates as b4r_rank_full writes its top M -- best first, -1 / -inf
+ *       tail.  pool_util may hold any utility that is comparable across rows and does not increase along a row (the sweep's
+ *       scores, b4r_score_dist's log probabilities of the pool ids).
+ *   capacity [V] int32: the units of every token id on offer; a value <= 0 means none.  Read only at live ids.
+ *   user_ids [R] int64 or NULL: the users' ids, which break utility ties; NULL = the row index.
+ * An EDGE is a pool entry (r, p) that is live: id in [0, V), a finite utility, capacity[id] > 0.  A repeated id in a row is one edge
+ * per occurrence, as in the re-rankers.  All edges stand in one strict order:
+ *   utility descending, compared as u + 0.0f (-0.0 equals +0.0); then the lower user_ids[r]; then the lower row; then the lower pool
+ *   position.
+ * The result is the greedy walk over the edges in that order: edge (r, p) with item j is ASSIGNED when row r has fewer than K
+ * assigned edges and item j fewer than capacity[j]; nothing else is assigned.  (This is the unique stable many-to-many matching in
+ * which a user prefers its own pool order and an item the edge that stands earlier: the classical greedy b-matching.)
+ * Outputs, each of which may be NULL:
+ *   out_ids int64, out_util fp32, out_pos int32 [R, K]: the row's assigned entries in ascending pool position -- the id and the
+ *       utility bits of the pool entry and its position -- then -1 / -inf / -1.
+ *   row_n [R] int32: the entries assigned to the row.
+ *   remaining [V] int32: capacity[j] minus the units of j assigned, written for EVERY j (capacity[j] itself where nothing of j was
+ *       assigned, also for values <= 0).  It may be the capacity buffer itself.  Fed back in as the capacity of the next batch of
+ *       users it makes the stock first come, first served ACROSS calls: the result then depends on how the users are cut into
+ *       calls, since a later batch cannot displace an earlier one however high its utilities are.
+ *   unsettled: one int32 on the device, see below.
+ * How it is computed: deferred acceptance with the users proposing, in rounds that are separate launches.  In a round every row
+ * that holds fewer than K items proposes down its pool, from a pointer that only ever advances, until it holds K or the pool ends;
+ * then every item that is held more often than its capacity keeps its capacity[j] best holders in the order above and rejects the
+ * rest, and a rejected row goes on proposing in the next round.  Whatever the number of rounds per call this ends in the matching
+ * defined above (a row whose live entries are not in descending utility order is outside the contract: the result is still
+ * feasible).  A round that rejects nothing has settled the state; rounds enqueued after it return at once and change nothing.
+ *   rounds >= 1: the rounds this call enqueues (three launches each), followed by one launch that writes the outputs.
+ *   resume = 0: the state in the scratch is initialised first (one more launch).  resume = 1: the call continues from the state an
+ *       earlier call left in the same scratch, with the same pool_ids, pool_util, user_ids, R, M, K and V; capacity is not read.
+ *       A scratch that does not hold a state of this shape leaves every output untouched and writes unsettled = -1.
+ *   The outputs always describe the current state, and that state is always FEASIBLE: no row holds more than K entries, no item
+ *   gives more than its capacity.  Before the state has settled a row may hold fewer entries than it will in the end.
+ *   unsettled = the rejections of the last executed round; 0: the state has settled and the outputs are the result defined above.
+ *   At most (number of edges) + 1 rounds are ever needed; contended catalogues settle in tens.
+ * 0 <= R <= 2^20, 1 <= M <= 1024, 0 <= K <= M, V >= 1, R * K <= 2^20 (else B4R_E_SHAPE); rounds < 1, a resume other than 0 / 1,
+ * capacity NULL, and with R * K > 0 pool_ids, pool_util or scratch NULL or a scratch that is not 8-byte aligned: B4R_E_BADARG;
+ * scratch_bytes below b4r_allocate_scratch_bytes(R, M, K, V) = 4 * (16 + R + 2 V + 4 R K + ceil(R K / 256)) bytes (-1 for a shape outside the
+ * limits): B4R_E_NOMEM.  All checks happen before any launch; a refused call leaves the outputs untouched.  R = 0 or K = 0 succeeds,
+ * launches no kernel and changes no row output; remaining, if given, still becomes a copy of capacity (one device-to-device copy).
+ * Only enqueues (one stream, no host sync, graph-capturable).  No workgroup waits for another, every loop bound is known on entry,
+ * the only atomics are 32-bit integer adds whose results no thread reads within the same launch, so the outputs are bitwise
+ * reproducible; nothing is read or written out of bounds whatever the ids, utilities and capacities are.  The resolve step
+ * compares all R * K held slots with one another where an item is over-subscribed (tiles of 256 through LDS, as
+ * b4r_history_append counts): meant for thousands of rows per call. */
+int64_t b4r_allocate_scratch_bytes(int32_t R, int32_t M, int32_t K, int32_t V);
+int b4r_allocate(const int64_t* pool_ids, const float* pool_util, int32_t R, int32_t M, int32_t K, int32_t V, const int32_t* capacity,
+                 const int64_t* user_ids, int32_t rounds, int32_t resume, int64_t* out_ids, float* out_util, int32_t* out_pos,
+                 int32_t* row_n, int32_t* remaining, int32_t* unsettled, void* scratch, int64_t scratch_bytes, b4r_stream_t stream);
 /* Audience selection: given an item, which users?  b4r_audience_merge is the step ACROSS users: it merges one batch of users into
  * the K most likely users of each of Q items, which stay on the device while the batches of users go by (O(Q * K) state, no
  * [users, items] matrix), and counts reach and expected demand.  It only enqueues (one launch, one stream, no host sync,
